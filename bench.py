@@ -12,7 +12,13 @@ weak scaling: every rank runs its own 32 clips (config[4] = 256 clips over 8 GPU
 one RCCL broadcast before the timed region; there is no collective on the data path (the reference's analogue is
 Lightning's one-process-per-device launch, configs/trainer/default.yaml:6-9).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the headline fields: metric, value
+(samples/s over all ranks), unit, higher_is_better, dtype, ms_per_step (one timed step, max over ranks) and the workload
+description.  --dump-outputs DIR also writes the waveforms of the last timed step to DIR/waveform.npy (float32; one file
+per rank at N > 1, a seeded sample when they would exceed 64 MB): the inputs are seeded, so two builds can be compared
+output for output.
+
+With --full the line also carries everything else the benchmark measures or checks (the --no-* switches trim it):
   roofline        — the dominant kernel of the forward (by total time), timed live with hipEvents on the launch stream by
                     the engine's per-launch profiler (fv_profile_*): `achieved` / `frac` = matrix flops the kernel ISSUES per launch /
                     avg duration vs the fp32-MFMA peak (a hardware fraction, <= 1; bytes vs the HBM peak when that roof binds);
@@ -23,7 +29,10 @@ Rank 0 prints ONE JSON line with the contract fields plus
                     headline value;
   other_configs   — BASELINE config[2] (BigVGAN-24k B=64) and config[3] (Vocos-24k B=128): ms/step and step-level roofline;
   cpu_baseline    — the CPU oracle (oracle/, a C port of the reference forward) on a bounded sample of the same workload,
-                    rank 0 / N=1 only; host core count, CPU model and the thread count used are stated.
+                    rank 0 / N=1 only; host core count, CPU model and the thread count used are stated;
+  and the single-clip latency percentiles, the eager step, mixed shapes, output checks, per-rank diagnostics, alt_precision
+  (f16x3) and one_shot (engine creation + first forwards).  A plain run at N = 1 brings up no process group; --full and
+  N > 1 run on RCCL.
 """
 from __future__ import annotations
 
@@ -77,7 +86,19 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group / scatter-gather plumbing only, no engine and no timing claims "
                          "(backend gloo when there is no GPU: the CPU test of the self-launch path)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline, with_collectives, latency percentiles, eager step, mixed "
+                         "shapes, output checks, per-rank diagnostics, alt_precision, other_configs, one_shot, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveforms of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.profile_json and not (a.full or a.roofline_only):
+        ap.error("--profile-json needs --full or --roofline-only (a plain run takes no per-kernel table)")
+    if a.dump_outputs and (a.roofline_only or a.dry_run):
+        ap.error("--dump-outputs writes what the timed steps computed: --roofline-only and --dry-run time none")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -361,6 +382,25 @@ def time_engine(eng, mel, out, steps, warmup, dev) -> float:
     return (time.perf_counter() - t0) / steps
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, out: torch.Tensor, rank: int, world: int) -> None:
+    """--dump-outputs: the waveforms of the last timed step as float32 .npy, one file per rank, at most 64 MB over all ranks — beyond that a
+    fixed, seeded sample of the samples (the same one every run with the same arguments)."""
+    os.makedirs(d, exist_ok=True)
+    name = "waveform" if world == 1 else f"waveform_rank{rank}"
+    y = out.detach().reshape(-1)
+    cap = DUMP_LIMIT_BYTES // world // 4
+    if y.numel() > cap:
+        idx = np.unique(np.random.default_rng(0).integers(0, y.numel(), cap))
+        y = y[torch.from_numpy(idx).to(y.device)]
+        name += "_sample"
+    else:
+        y = y.reshape(out.shape)
+    np.save(os.path.join(d, name + ".npy"), y.float().cpu().numpy())
+
+
 MIXED_SHAPES = ((1, 86), (4, 200), (32, 86), (2, 431), (8, 47), (16, 120), (3, 301), (24, 64))   # (clips, mel frames)
 
 
@@ -511,12 +551,13 @@ def _main(a, real_stdout):
     dev = torch.device("cuda", local_rank)
     dist, rccl_error = None, None
     t_pg = time.perf_counter()
-    try:
-        dist = init_dist(dev)                               # RCCL over xGMI; a 1-rank group at N = 1
-    except Exception as exc:  # noqa: BLE001
-        if world > 1:
-            raise
-        rccl_error = f"{type(exc).__name__}: {exc}"         # N = 1 keeps its headline line without the process group
+    if world > 1 or a.full or a.roofline_only:              # a plain N = 1 run times one engine: nothing to fan out or collect
+        try:
+            dist = init_dist(dev)                           # RCCL over xGMI; a 1-rank group at N = 1
+        except Exception as exc:  # noqa: BLE001
+            if world > 1:
+                raise
+            rccl_error = f"{type(exc).__name__}: {exc}"     # N = 1 keeps its headline line without the process group
     ranks = dist.get_world_size() if dist is not None else 1
     t_pg = time.perf_counter() - t_pg
 
@@ -576,6 +617,28 @@ def _main(a, real_stdout):
     fence()
     local = time.perf_counter() - t0
     elapsed = max_over_ranks(local)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, rank, world)
+    value = world * samples_per_step * a.steps / elapsed
+    headline = {
+        "metric": "audio_samples_per_sec", "value": value, "unit": "samples/s",
+        "n_gpus": world, "rccl_ranks": ranks if dist is not None else 0, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if a.precision == "f32" else "f32 via f16x3 split (fp16 operand planes, fp32 accumulate)",
+        "data": "synthetic",
+        "config": {"workload": "hifigan V1 44.1 kHz, 80-bin mel, batch=32x1 s synthetic mel per MI355X (BASELINE config[1]; "
+                               "config[4] at 8 GPUs)",
+                   "clips_per_gpu": B, "t_mel": T, "samples_per_clip": eng.output_length(T),
+                   "global_batch": B * world, "parallelism": f"utterance-shard x{world}"},
+        "x_realtime": value / SAMPLE_RATE, "x_realtime_per_gpu": value / SAMPLE_RATE / world,
+    }
+    if not a.full:
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline), file=real_stdout, flush=True)
+        return
     # Self-diagnosis of the N > 1 line: every rank's own step time by its own GPU clock (hipEvents around its K steps, before
     # the closing barrier) and by the host clock, the one-time weight fan-out, the process-group start-up and the environment the transport depends
     # on — so that the first 8-GPU curve the driver measures explains itself (a slow rank, a slow link, a missing IPC mode).  No efficiency figure.
@@ -684,18 +747,8 @@ def _main(a, real_stdout):
         if a.profile_json:
             os.makedirs(os.path.dirname(os.path.abspath(a.profile_json)), exist_ok=True)
             json.dump(table, open(a.profile_json, "w"), indent=1)
-        value = world * samples_per_step * a.steps / elapsed
-        result = {
-            "metric": "audio_samples_per_sec", "value": value, "unit": "samples/s",
-            "n_gpus": world, "rccl_ranks": ranks if dist is not None else 0, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32" if a.precision == "f32" else "f32 via f16x3 split (fp16 operand planes, fp32 accumulate)",
-            "data": "synthetic",
-            "config": {"workload": "hifigan V1 44.1 kHz, 80-bin mel, batch=32x1 s synthetic mel per MI355X (BASELINE config[1]; "
-                                   "config[4] at 8 GPUs)",
-                       "clips_per_gpu": B, "t_mel": T, "samples_per_clip": eng.output_length(T),
-                       "global_batch": B * world, "parallelism": f"utterance-shard x{world}"},
-            "x_realtime": value / SAMPLE_RATE, "x_realtime_per_gpu": value / SAMPLE_RATE / world,
+        result = dict(headline)
+        result.update({
             "p50_clip_latency_ms": float(np.percentile(lat, 50)), "p90_clip_latency_ms": float(np.percentile(lat, 90)),
             "p50_clip_latency_batch_invariant_ms": float(np.percentile(lat_inv, 50)),
             "p50_clip_latency_eager_ms": float(np.percentile(lat_eager, 50)),
@@ -704,7 +757,7 @@ def _main(a, real_stdout):
             "mixed_shapes": mixed,
             "output_finite": ok,
             "roofline": roofline_from_profile(table, repeats),
-        }
+        })
         gpu_ms = [r[0] for r in per_rank]
         result["multi_gpu"] = {
             "ranks": ranks, "per_rank_ms_per_step_gpu_clock": gpu_ms, "per_rank_ms_per_step_host_clock": [r[1] for r in per_rank],

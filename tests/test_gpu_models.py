@@ -1005,7 +1005,7 @@ def test_hifigan_batch_256_the_eight_gpu_global_batch_on_one_gpu():
 def test_bench_runs_its_collectives_on_a_one_rank_rccl_group():
     """`torch.distributed.run --nproc-per-node 1 bench.py --gpus 1` (backend nccl = RCCL): the weights go through
     broadcast_state_dict, the timed with_collectives loop runs broadcast -> forward -> all_gather on the process group, and the
-    collected batch equals the direct forward bit for bit.  A plain `python bench.py` (what the driver runs) builds the same
+    collected batch equals the direct forward bit for bit.  `python bench.py --full` without a launcher builds the same
     1-rank group itself."""
     import json
     import os
@@ -1014,7 +1014,7 @@ def test_bench_runs_its_collectives_on_a_one_rank_rccl_group():
     repo = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--no-alt-precision"]
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs", "--no-alt-precision"]
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
         sk.bind(("127.0.0.1", 0))
@@ -1032,6 +1032,39 @@ def test_bench_runs_its_collectives_on_a_one_rank_rccl_group():
         assert c["backend"] == "rccl" and c["collected_finite"] and c["rank0_shard_equals_direct_forward"], c
         assert c["collected_shape"] == [32, 1, 44032] and c["all_gather_bytes_per_step"] == 32 * 44032 * 4
         assert j["output_finite"] and j["ms_per_step_eager"] > 0 and j["mixed_shapes"]["output_finite"]
+
+
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` times the steps and prints the headline fields only (no process group, none of --full's figures);
+    --dump-outputs writes the last timed step's waveforms, which equal a direct forward of the same seeded weights and mels bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from vocoder_amd import _lib
+    from vocoder_amd.engine import Engine, upsampler_config
+    repo = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=repo)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["metric"] == "audio_samples_per_sec" and j["unit"] == "samples/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["rccl_ranks"] == 0 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 32 * 44032 / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+    for k in ("roofline", "with_collectives", "cpu_baseline", "alt_precision", "other_configs", "one_shot", "p50_clip_latency_ms"):
+        assert k not in j, k
+    assert sorted(os.listdir(tmp_path)) == ["waveform.npy"]
+    y = np.load(tmp_path / "waveform.npy")
+    assert y.dtype == np.float32 and y.shape == (32, 1, 44032)
+    cfg = dict(syn.HIFIGAN_V1_44K)
+    eng = Engine(_lib.FV_MODEL_HIFIGAN, ups=upsampler_config(**cfg), state_dict=syn.hifigan_state_dict(cfg, seed=0))
+    ref = eng(torch.from_numpy(syn.synthetic_mel(32, cfg["num_mels"], 86, seed=1234)).to(_dev()))
+    torch.cuda.synchronize()
+    assert np.array_equal(y, ref.cpu().numpy())
+    eng.close()
 
 
 @pytest.fixture

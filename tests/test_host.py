@@ -330,6 +330,22 @@ def test_bench_self_launches_n_ranks_without_torchrun():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_within_the_size_cap(tmp_path):
+    """bench.py --dump-outputs: the whole waveform batch as float32 when it fits, otherwise (here: the 64 MB shared by many ranks) the same
+    seeded sample of it on every call."""
+    import bench
+    out = torch.arange(2 * 1 * 300, dtype=torch.float32).reshape(2, 1, 300)
+    bench.dump_outputs(str(tmp_path / "a"), out, 0, 1)
+    y = np.load(tmp_path / "a" / "waveform.npy")
+    assert y.dtype == np.float32 and y.shape == (2, 1, 300) and np.array_equal(y, out.numpy())
+    world = bench.DUMP_LIMIT_BYTES // 4 // 100          # 100 samples per rank
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out, 3, world)
+    s1, s2 = np.load(tmp_path / "b" / "waveform_rank3_sample.npy"), np.load(tmp_path / "c" / "waveform_rank3_sample.npy")
+    assert s1.dtype == np.float32 and 0 < s1.size <= 100 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0) and np.all(np.isin(s1, out.numpy()))
+
+
 def test_cpu_clip_worker_protocol():
     """bench.py's cpu_baseline leg: oracle/cpu_clips.py workers (one process per core in use, whole clips each) answer the
     run / quit protocol and agree with the in-process oracle on the clips they were given."""

@@ -1,7 +1,7 @@
 set -x
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r06d; mkdir -p $O; cd $R
 run() { # name lib extra-env
-  ( [ "$2" = base ] || export FV_LIB_PATH=$R/vocoder_amd/csrc/libfishvoc_$2.so; export $3; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-alt-precision --no-collectives --profile-json $O/$1.json 2>/dev/null | python -c "
+  ( [ "$2" = base ] || export FV_LIB_PATH=$R/vocoder_amd/csrc/libfishvoc_$2.so; export $3; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-alt-precision --no-collectives --profile-json $O/$1.json 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 print('$1: ms/step %.3f eager %.3f  dominant %.1f us' % (j['ms_per_step'], j['ms_per_step_eager'], j['roofline']['avg_ms']*1e3))" )

@@ -8,4 +8,4 @@ done
 grep -v amdgpu.ids $O/pair44_standalone.txt
 bash tools/ab_libs.sh "x_pqphase base" 3 > $O/ab_step.txt 2>&1
 cat $O/ab_step.txt
-python bench.py > $O/bench.json 2> $O/bench.err; head -c 2500 $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; head -c 2500 $O/bench.json

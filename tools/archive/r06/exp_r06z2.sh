@@ -9,7 +9,7 @@ python $R/tools/pmc_summary.py $O/pmc_hifigan_FETCH_SIZE $O/pmc_hifigan_WRITE_SI
 python $R/tools/pmc_traffic.py $O/pmc_hifigan_FETCH_SIZE $O/pmc_hifigan_WRITE_SIZE $O/traffic.json --build r06z
 cp $O/traffic.json $R/profiles/traffic.json; cp $O/traffic.json $O/traffic_merged.json
 cd $R
-timeout 1200 python bench.py --profile-json $O/bench_kernels_hipevents.json > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+timeout 1200 python bench.py --full --profile-json $O/bench_kernels_hipevents.json > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
 python tools/driver_repro.py $O r06z $O/bench.json > $O/driver_repro.md 2>> $O/bench.err
 rm -rf $O/pmc_hifigan_FETCH_SIZE $O/pmc_hifigan_WRITE_SIZE
 python -c "

@@ -23,7 +23,7 @@ python $R/tools/pmc_traffic.py $O/pmc_hifigan_FETCH_SIZE $O/pmc_hifigan_WRITE_SI
 # (written FRESH from this build's passes, not merged into the previous file: a key that no longer matches must show up as a missing entry, not as an old one — LOG R6.15)
 cp $O/traffic.json $R/profiles/traffic.json; cp $O/traffic.json $O/traffic_merged.json
 cd $R
-timeout 1200 python bench.py --profile-json $O/bench_kernels_hipevents.json > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.err
+timeout 1200 python bench.py --full --profile-json $O/bench_kernels_hipevents.json > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.err
 # how `roofline.traffic` was measured, with the by-kernel tables of the three configs
 python tools/driver_repro.py $O $TAG $O/bench.json > $O/driver_repro.md 2>> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
