@@ -656,12 +656,9 @@ def test_winograd_conv_offsets_beyond_2_gib(monkeypatch):
 def _heavy_tailed_weight(rng, c, k):
     """A folded weight-norm layer w = g * v / ||v|| (hifigan.py:31) with the per-output-channel gain g log-uniform over 100 x and
     0.4 % of the taps 30 x larger than their neighbours: the transforms of the Winograd kernels mix taps, so an outlier is added to
-    and subtracted from small values before the matrix product."""
-    v = rng.normal(size=(c, c, k))
-    hit = rng.random(size=v.shape) < 0.004
-    v = np.where(hit, 30.0 * v, v)
-    g = np.exp(rng.uniform(np.log(0.03), np.log(3.0), size=(c, 1, 1)))
-    return (g * v / np.sqrt((v * v).sum(axis=(1, 2), keepdims=True))).astype(np.float32)
+    and subtracted from small values before the matrix product.  (conv_reference.heavy_tailed_weight, square.)"""
+    import conv_reference
+    return conv_reference.heavy_tailed_weight(rng, c, c, k)
 
 
 def _conv1d_f64(x, w, b, d):

@@ -498,6 +498,26 @@ static int choose_gemm_pw_xcd_rows(const ConvLayer& L, const ConvRun& r, long lo
 
 static const char* const kTileNames[TILE_COUNT] = {"128x128", "64x256", "32x512", "128x64", "32x128", "64x128", "splitK32x64", "splitK32x32", "256x64", "256x32", "128x96"};
 
+int conv_tile_by_name(const char* name) {
+    for (int c = 0; c < TILE_COUNT; ++c)
+        if (std::strcmp(name, kTileNames[c]) == 0) return c;
+    return -1;
+}
+
+// Can FV_CONV_TILE put this layer's conv_mfma launches on tile `cfg`?  Only where launch_cfg<KS, DIL> (conv_mfma_impl.h) instantiates it — never through
+// the generic kernel — and, for the 256-row tiles, only where the packed weights and the bias cover whole 256-row blocks (they are padded to m_pad, a
+// multiple of 128 rows: a 256-row workgroup past it would read weights beyond the buffer, whose descriptor is unbounded)
+static bool conv_tile_forceable(const ConvLayer& L, int cfg) {
+    if (cfg < 0 || cfg >= TILE_COUNT) return false;
+    const bool spec = L.dil == 1 ? (L.ks == 1 || L.ks == 2 || L.ks == 3 || L.ks == 4 || L.ks == 7 || L.ks == 11 || L.ks == 13)
+                                 : ((L.dil == 3 || L.dil == 5) && (L.ks == 3 || L.ks == 7 || L.ks == 11));
+    if (!spec) return false;
+    if (cfg == TILE_256x32) return L.ks == 1 && L.m_pad % 256 == 0;
+    if (cfg == TILE_256x64) return (L.ks == 1 || L.ks == 2) && L.m_pad % 256 == 0;
+    if (cfg == TILE_128x96) return L.ks == 2;
+    return true;
+}
+
 static const char* const kSplitNames[SPLIT_COUNT] = {"128x128", "64x256", "32x256"};
 
 // f16x3 precision mode: tile choice + dispatch of the split-fp16 kernel (p already describes the layer call)
@@ -615,8 +635,7 @@ fv_status conv_layer_run(const ConvLayer& L, const ConvRun& r, hipStream_t strea
             set_error("conv_layer_run: x2 and x3 go together");
             return FV_ERR_INVALID;
         }
-        static const bool no_fuse = std::getenv("FV_NO_SUM3") != nullptr;   // experiments
-        if (L.transposed && conv_sum3_supported(L.ks) && L.dil == 1 && !f16 && !no_fuse) {
+        if (L.transposed && conv_sum3_supported(L.ks) && L.dil == 1 && !f16 && !knobs().no_sum3) {
             p.x2 = r.x2;
             p.x3 = r.x3;
         } else {
@@ -837,14 +856,15 @@ fv_status conv_layer_run(const ConvLayer& L, const ConvRun& r, hipStream_t strea
     // 256 x 64 tiles for the two-tap polyphase upsamplers with whole 256-row blocks (round 6, LOG R6.14): the staged window (three inputs + SiLU behind the
     // stack-mean) serves twice the rows — HiFiGAN-V1's stage-1 upsampler (1024 GEMM rows) 230 -> 217 us, alone on the step's critical path; same sums per
     // output (chunk, tap, channel pair order does not depend on the tile).  FV_X_UPS_TILE256=0: the 128-row tiles (A/B runs)
-    static const int ups256 = std::getenv("FV_X_UPS_TILE256") ? std::atoi(std::getenv("FV_X_UPS_TILE256")) : 1;
-    if (ups256 && L.transposed && L.ks == 2 && L.M % 256 == 0 && p.N > 96 && (cfg == TILE_128x128 || cfg == TILE_128x64)) cfg = TILE_256x64;
+    if (knobs().ups_tile256 && L.transposed && L.ks == 2 && L.M % 256 == 0 && p.N > 96 && (cfg == TILE_128x128 || cfg == TILE_128x64)) cfg = TILE_256x64;
     // the last, HBM-bound upsampler (C -> C / 2 with C / 2 * stride <= 32 rows): 32 x 128 tiles (HiFiGAN step -0.06 ms; for the
     // stride-1 convs of that width — BigVGAN's last stage — the 32 x 512 tile stays: +0.26 ms with the small one)
     if (cfg == TILE_32x512 && L.transposed) cfg = TILE_32x128;
     // pointwise convs have no halo, so batch and time flatten into one GEMM column axis: no per-item partial tiles
     // (Vocos: T = 94 frames per clip would waste 27 % of a 128-column tile)
     int launch_batch = r.batch;
+    // FV_CONV_TILE (tests): one tile for every launch that has it instantiated, in place of the choice above and below
+    const int forced = conv_tile_forceable(L, knobs().conv_tile) ? knobs().conv_tile : -1;
     if (!L.transposed && L.ks == 1 && L.pad_l == 0 && r.batch > 1 &&
         (long long)r.batch * std::max<long long>((long long)L.c_in * r.t_in, (long long)L.c_out * tout) < (1LL << 30)) {
         int cfg_flat = choose_tile(L.M, (long long)p.N * r.batch, 1);
@@ -854,6 +874,7 @@ fv_status conv_layer_run(const ConvLayer& L, const ConvRun& r, hipStream_t strea
         if (cfg_flat == TILE_128x128 && L.M >= 512 && ((L.M + 127) / 128) % 2 == 0) cfg_flat = TILE_256x64;
         // ... and 256 x 32 instead of 128 x 64 where the half-width tile was chosen (ConvNeXt's 4x contraction: +7 %)
         if (cfg_flat == TILE_128x64 && L.M >= 512 && ((L.M + 127) / 128) % 2 == 0) cfg_flat = TILE_256x32;
+        if (forced >= 0) cfg_flat = forced;
         if (cfg_flat != TILE_SPLITK_32x64 && cfg_flat != TILE_SPLITK_32x32) {
             cfg = cfg_flat;
             // 2: even T and 8-byte aligned rows -> the kernel stages column pairs (conv_mfma_impl.h)
@@ -862,6 +883,7 @@ fv_status conv_layer_run(const ConvLayer& L, const ConvRun& r, hipStream_t strea
             launch_batch = 1;
         }
     }
+    if (forced >= 0) cfg = forced;
     bool ok = false;
     bool specialised = true;
     auto try_launch = [&](int c) {
@@ -904,10 +926,12 @@ fv_status conv_layer_run(const ConvLayer& L, const ConvRun& r, hipStream_t strea
     std::snprintf(name, sizeof(name), "conv_mfma<%s k=%d d=%d tile=%s>", specialised ? "spec" : "generic", L.ks, L.dil,
                   kTileNames[cfg]);
     // (split-K launches whose B operands come straight from global memory — conv_mfma_splitk_direct_kernel — carry " direct": the rule of launch_cfg())
+    // (pointwise launches over the flattened (clip, time) columns carry " flat", or " flat2" where they stage 8-byte column pairs)
     const bool direct = specialised && (cfg == TILE_SPLITK_32x64 || cfg == TILE_SPLITK_32x32) && knobs().splitk_direct &&
                         splitk_direct_shape(L.ks, L.dil, cfg == TILE_SPLITK_32x64 ? 2 : 1, p.x2 != nullptr);
-    char tags[32];
-    std::snprintf(tags, sizeof(tags), "%s%s%s", L.transposed ? " convT" : "", p.x2 ? " sum3" : "", direct ? " direct" : "");
+    char tags[48];
+    std::snprintf(tags, sizeof(tags), "%s%s%s%s", L.transposed ? " convT" : "", p.x2 ? " sum3" : "", direct ? " direct" : "",
+                  p.flat == 2 ? " flat2" : p.flat ? " flat" : "");
     return finish_conv_launch(L, r, tout, stream, prof_idx, name, (long long)launch_batch * p.m_blks * p.n_tiles, tags, p.x2 != nullptr);
 }
 

@@ -85,6 +85,12 @@ static const Knobs* load_knobs() {
     if (const char* v = std::getenv("FV_WINO44_FLAT")) k->wino44_flat = std::atoi(v);
     if (const char* v = std::getenv("FV_VEC_STORE")) k->vec_store = std::atoi(v);
     if (const char* v = std::getenv("FV_PAIR_WINO44")) k->pair_wino44 = std::atoi(v);
+    if (const char* v = std::getenv("FV_CONV_TILE")) {
+        k->conv_tile = conv_tile_by_name(v);
+        if (k->conv_tile < 0 && v[0]) std::fprintf(stderr, "fishvoc: FV_CONV_TILE=%s names no conv tile; ignored\n", v);
+    }
+    if (const char* v = std::getenv("FV_X_UPS_TILE256")) k->ups_tile256 = std::atoi(v);
+    k->no_sum3 = std::getenv("FV_NO_SUM3") != nullptr;
     return k;
 }
 const Knobs& knobs() {
@@ -1148,7 +1154,7 @@ fv_status fv_engine::run_upsampler(const float* d_in, float* d_out, int B, int T
                 for (int j = 1; j < nk; ++j) FV_HIP_CHECK(hipStreamWaitEvent(s, bev_last[stage_idx * nk + j], 0));
             // the next stage's upsampler conv forms the mean while staging its input (conv_mfma_impl.h, SUM3); the last stage's
             // output goes through mean_of_three_kernel (its consumers are the narrow post kernels)
-            static const bool fuse_mean = std::getenv("FV_NO_SUM3") == nullptr;
+            const bool fuse_mean = !knobs().no_sum3;
             if (stage_idx + 1 < n_stages && fuse_mean && !dbg_here) {
                 sum_pending = true;
             } else if (stage_idx + 1 == n_stages && fuse_mean && post_mean_fused && !dbg_here &&

@@ -42,7 +42,13 @@ struct Knobs {
     int wino44_flat = 1;  // FV_WINO44_FLAT: 1 = conv_wino44 tiles a flattened (clip, quad column) axis where that needs fewer 32-column tiles than tiling every clip on its own (T = 688: 5.4 tiles per clip), 0 = per clip
     int wino_lat = 1;     // FV_WINO_LAT: 0 = launches below the Winograd gate run the direct split-K kernels, 1 = the Winograd latency kernel
     int pair_wino = 1;    // FV_PAIR_WINO: 0 = the fused (c1, c2) pairs run direct sums (resblock_pair.hip), 1 = Winograd tap groups where a kernel exists
+    int conv_tile = -1;   // FV_CONV_TILE: a TileCfg name ("128x64", "splitK32x32", ...) forced on every conv_mfma launch that has that tile instantiated
+                          //   (after all the shape remaps; tests pin the kernel instance by instance), -1 = by shape
+    int ups_tile256 = 1;  // FV_X_UPS_TILE256: 0 = the two-tap polyphase upsamplers keep the 128-row tiles instead of 256 x 64 (A/B runs, tests)
+    bool no_sum3 = false; // FV_NO_SUM3: the three-operand stack-mean goes through mean_of_three_kernel instead of the conv's staging (A/B runs, tests)
 };
+// TileCfg index of a tile name ("128x128", ..., "128x96"), -1 if there is none (conv_layer.hip)
+int conv_tile_by_name(const char* name);
 const Knobs& knobs();
 
 // Conv algorithm selection of the call being enqueued (fv_set_conv_algorithm / fv_set_batch_invariant): thread-local, set by the C-ABI entry
