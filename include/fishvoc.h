@@ -274,6 +274,59 @@ FV_API fv_status fv_forward_refinegan(fv_engine* e, const float* d_mel, const fl
                                       float* d_out, int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes,
                                       void* stream);
 
+/* -------- streaming synthesis: push mel chunks, get audio after a fixed lookahead.  No reference counterpart: the reference has no
+ *          streaming — its only caller (test.py:88-90) runs whole utterances through `self.generator(input_spec)`; this replaces cutting
+ *          windows by hand around that call.  --------
+ *
+ * A stream serves `batch` sessions that advance in lockstep (every push gives each the same number of frames).  R = fv_reach_frames, the
+ * generator's one-sided reach in input frames; K = context_frames and A = lookahead_frames (-1: R each).  Host counters: F frames received, E
+ * frames emitted.  A push of n frames sets F += n, E' = max(E, F - A) and, if E' > E, runs the model ONCE on the window of frames [w, F),
+ * w = max(0, E - K), and returns the output samples [(E - w) hop, (E' - w) hop) of that window: the frames [E, E').  A push emits at most n
+ * frames; afterwards F - E <= A.  fv_stream_flush does the same with E' = F (the window's right edge is the utterance's end; at most A
+ * frames) and then refuses pushes (FV_ERR_STATE) until fv_stream_reset (F = E = 0, allocations kept).
+ *   - each call's output is bit-identical to the same slice of fv_forward on the frames [w, F) by the same engine and batch size;
+ *   - K >= R and A >= R: the concatenated output is the whole utterance's shape and within 2e-5 * max(1, peak) of one fv_forward over it (the
+ *     windows anchor the Winograd lattices elsewhere, as the time tiles do); an utterance of T <= A frames comes out of the flush alone, as
+ *     the single window [0, T): bit-identical to fv_forward.
+ * Models stream exactly when they are frame-aligned (what the time tiles need): HiFiGAN / BigVGAN (with or without use_template), Firefly,
+ * Vocos and ISTFT heads with padding "same", the ConvNeXt encoder alone (hop = 1).  RefineGAN, LOGMEL, the "center" ISTFT head and upsamplers
+ * whose output is not hop x frames get FV_ERR_UNSUPPORTED at fv_stream_create, with the reason in fv_last_error. */
+
+/* R, the engine's one-sided reach in input frames (the halo of the time tiles); -1: this model cannot stream. */
+FV_API int32_t fv_reach_frames(const fv_engine* e);
+
+typedef struct fv_stream_config {
+    int32_t batch;             /* sessions in lockstep (B) */
+    int32_t max_chunk_frames;  /* largest n of one push */
+    int32_t context_frames;    /* K; -1 = R */
+    int32_t lookahead_frames;  /* A; -1 = R */
+} fv_stream_config;
+
+typedef struct fv_stream fv_stream;
+
+/* The stream's only device allocation, made here on the current HIP device and freed by fv_stream_destroy: a ring of the last
+ * K + A + max_chunk_frames frames per session, (batch, C_in, K + A + max_chunk_frames), plus (batch, 1, (K + A + max_chunk_frames) * hop) for
+ * the pitch template of a use_template generator.  Everything else lives in the caller's workspace. */
+FV_API fv_status fv_stream_create(fv_engine* e, const fv_stream_config* cfg, fv_stream** out);
+/* Bytes of device scratch every push / flush needs (256-byte aligned): the window's input, template and output, and the forward's own
+ * workspace for the largest window. */
+FV_API size_t fv_stream_workspace_bytes(const fv_stream* s);
+/* F - E: frames received but not yet emitted. */
+FV_API int64_t fv_stream_pending_frames(const fv_stream* s);
+/* d_mel: (batch, C_in, n) fp32, n <= max_chunk_frames (else FV_ERR_INVALID); d_template: (batch, 1, n * hop) for a use_template generator,
+ * NULL otherwise (a missing or unexpected template: FV_ERR_INVALID); d_out: (batch, C_out, *frames_out * hop) fp32, contiguous — room for
+ * min(n, max(0, pending + n - A)) frames, known before the call.  *frames_out receives the frames emitted; the counters are host-side, so the
+ * call never synchronises.  n = 0 is a no-op.  Asynchronous on `stream`; calls on one stream must be ordered (one stream after another, or one
+ * host thread), like fv_forward on its engine.  After a flush: FV_ERR_STATE. */
+FV_API fv_status fv_stream_push(fv_stream* s, const float* d_mel, const float* d_template, int32_t n, float* d_out, int64_t* frames_out,
+                                void* d_workspace, size_t workspace_bytes, void* stream);
+/* Emits the pending frames (at most A) against the utterance's true end; d_out: (batch, C_out, pending * hop). */
+FV_API fv_status fv_stream_flush(fv_stream* s, float* d_out, int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream);
+/* F = E = 0 for the next utterance; the ring and its size are kept. */
+FV_API fv_status fv_stream_reset(fv_stream* s);
+/* Frees the ring (call it before fv_destroy of its engine, once the stream's work has finished). */
+FV_API void fv_stream_destroy(fv_stream* s);
+
 /* -------- single fused conv layer (the hot kernel on its own; used by the parity tests and the roofline
  *          bench).  Stands in for one weight-normed nn.Conv1d / nn.ConvTranspose1d call plus the elementwise
  *          ops the reference runs around it (F.silu before, residual add after: hifigan.py:101-108). -------- */

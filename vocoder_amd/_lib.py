@@ -15,6 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FV_LIB_PATH") or os.path.join(CSRC, "libfishvoc_hip.so")
 
 FV_ABI_VERSION = 5
+FV_OK, FV_ERR_INVALID, FV_ERR_UNSUPPORTED, FV_ERR_STATE = 0, -1, -2, -6
 FV_MAX_STAGES = 8
 FV_MAX_KERNELS = 8
 FV_MAX_DILATIONS = 3
@@ -37,6 +38,8 @@ EXPORTS = (
     "fv_profile_begin", "fv_profile_end", "fv_conv_pair_forward", "fv_forward_template",
     "fv_set_precision", "fv_conv_set_precision", "fv_refinegan_noise_elems", "fv_forward_refinegan",
     "fv_set_graph_replay", "fv_get_graph_replay", "fv_reload_env", "fv_set_conv_algorithm", "fv_set_batch_invariant", "fv_conv_set_algorithm",
+    "fv_reach_frames", "fv_stream_create", "fv_stream_workspace_bytes", "fv_stream_pending_frames", "fv_stream_push", "fv_stream_flush",
+    "fv_stream_reset", "fv_stream_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -83,6 +86,10 @@ class ConvDesc(ctypes.Structure):
     _fields_ = [("transposed", _i32), ("c_in", _i32), ("c_out", _i32), ("kernel_size", _i32), ("dilation", _i32),
                 ("padding", _i32), ("stride", _i32), ("pre_act", _i32), ("post_act", _i32),
                 ("act_slope", ctypes.c_float)]
+
+
+class StreamConfig(ctypes.Structure):
+    _fields_ = [("batch", _i32), ("max_chunk_frames", _i32), ("context_frames", _i32), ("lookahead_frames", _i32)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -166,6 +173,23 @@ def lib() -> ctypes.CDLL:
     L.fv_profile_begin.restype = _i32
     L.fv_profile_end.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.fv_profile_end.restype = _i32
+    L.fv_reach_frames.argtypes = [vp]
+    L.fv_reach_frames.restype = _i32
+    L.fv_stream_create.argtypes = [vp, ctypes.POINTER(StreamConfig), ctypes.POINTER(vp)]
+    L.fv_stream_create.restype = _i32
+    L.fv_stream_workspace_bytes.argtypes = [vp]
+    L.fv_stream_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_stream_pending_frames.argtypes = [vp]
+    L.fv_stream_pending_frames.restype = ctypes.c_int64
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    L.fv_stream_push.argtypes = [vp, vp, vp, _i32, vp, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_stream_push.restype = _i32
+    L.fv_stream_flush.argtypes = [vp, vp, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_stream_flush.restype = _i32
+    L.fv_stream_reset.argtypes = [vp]
+    L.fv_stream_reset.restype = _i32
+    L.fv_stream_destroy.argtypes = [vp]
+    L.fv_stream_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

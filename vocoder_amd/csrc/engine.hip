@@ -677,6 +677,7 @@ struct fv_engine {
         int hi(int i, int T) const { return i + 1 == n ? T : i * stride + L - halo; }      // one past its last
     };
     int reach_frames() const;
+    int frame_hop(int t_a, int t_b, const char** why) const;
     int tile_frame_limit() const;
     TilePlan tile_plan(int t_in) const;
     int tile_frames_override = 0;   // FV_TILE_FRAMES: tile length in frames (tests / experiments); 0 = only when the addressing span needs it
@@ -2193,6 +2194,29 @@ int fv_engine::reach_frames() const {
     }
     return (int)std::min<int64_t>(R + 2, 1 << 20);
 }
+// The frame-aligned models, the ones a window of frames [a, b) can stand in for: a finite reach, no "center" ISTFT trim, and exactly hop output
+// samples per input frame at both t_a and t_b frames — the gather / scatter of the time tiles and the window / crop of a stream address rows at
+// frames x hop.  Returns hop, or 0 with the reason in *why (may be NULL).  Used by tile_plan and fv_stream_create.
+int fv_engine::frame_hop(int t_a, int t_b, const char** why) const {
+    const char* r = nullptr;
+    if (cfg.model == FV_MODEL_LOGMEL)
+        r = "the log-mel front-end (wave -> mel) is not frame-windowed";
+    else if (cfg.model == FV_MODEL_REFINEGAN)
+        r = "RefineGAN cannot be windowed (its U-Net spans the whole clip and its AdaIN noise is drawn per call)";
+    else if (reach_frames() < 0)
+        r = "the model has no finite reach";
+    else if ((cfg.model == FV_MODEL_VOCOS || cfg.model == FV_MODEL_ISTFT_HEAD) && head.center())
+        r = "ISTFT head with padding=\"center\": the output is (T - 1) * hop samples, trimmed at both ends";
+    if (!r && t_a >= 1 && t_b >= 1) {
+        // A transposed conv with odd (kernel - rate) yields T u + 1 samples per stage (ConvLayer::out_len): not frames x hop
+        const int64_t la = fv_output_length(this, t_a), lb = fv_output_length(this, t_b);
+        const int64_t hop = la / t_a;
+        if (hop >= 1 && la == hop * t_a && lb == hop * (int64_t)t_b) return (int)hop;
+        r = "the output is not hop x frames samples (a transposed conv with odd kernel - rate adds a sample per stage)";
+    }
+    if (why) *why = r ? r : "empty input";
+    return 0;
+}
 // Longest tile (frames) whose largest per-item tensor stays under HALF the 4 GiB addressing span of the conv kernels
 int fv_engine::tile_frame_limit() const {
     int64_t per_frame = 1;
@@ -2210,19 +2234,13 @@ int fv_engine::tile_frame_limit() const {
 fv_engine::TilePlan fv_engine::tile_plan(int t_in) const {
     TilePlan p;
     const int reach = reach_frames();
-    if (reach < 0 || ((cfg.model == FV_MODEL_VOCOS || cfg.model == FV_MODEL_ISTFT_HEAD) && head.center())) return p;
-    int limit = tile_frame_limit();
+    int limit = tile_frame_limit();   // 0 for the models that are never tiled (LOGMEL / REFINEGAN)
     if (tile_frames_override > 0) limit = std::min(limit, std::max(tile_frames_override, 4 * reach));
     if (limit <= 0 || t_in <= limit) return p;
     if (limit < 4 * reach) return p;   // (a model whose reach does not fit the span: the per-layer check reports it)
-    // The gather / scatter address tiles and clips at exactly frames x hop samples.  A transposed conv with odd (kernel - rate) yields
-    // T u + 1 samples per stage (ConvLayer::out_len), so the model's rows would be longer than that: such a generator is not tiled
-    //  — the clip runs whole, and past the addressing span the per-layer check refuses it by name.
-    {
-        const int64_t lout = fv_output_length(this, limit), clip_out = fv_output_length(this, t_in);
-        const int64_t hop = limit > 0 ? lout / limit : 0;
-        if (hop < 1 || lout != hop * limit || clip_out != hop * (int64_t)t_in) return p;
-    }
+    // The gather / scatter address tiles and clips at exactly frames x hop samples: a model that is not frame-aligned (frame_hop: e.g. a "center"
+    // ISTFT head, or odd (kernel - rate) upsamplers) runs whole, and past the addressing span the per-layer check refuses it by name.
+    if (frame_hop(limit, t_in, nullptr) < 1) return p;
     p.halo = reach;
     p.L = limit;
     p.stride = p.L - 2 * p.halo;
@@ -2293,7 +2311,205 @@ fv_status fv_engine::run_model_whole(const float* d_in, float* d_out, int batch,
     return FV_ERR_INVALID;
 }
 
+// ---- streaming synthesis ---------------------------------------------------------------------------------------------
+// B sessions advance in lockstep.  Host counters: F frames received, E emitted.  A push of n frames appends them (F += n) and emits the frames
+// [E, E'), E' = max(E, F - A), out of ONE forward over the window [w, F), w = max(0, E - K); a flush does the same with E' = F.  With K and A
+// >= the reach every emitted frame lies >= R frames inside each window edge that is not the utterance's own, so the window reproduces the whole
+// utterance's samples there (the rule of the time tiles, tile_plan).  The window is assembled in the caller's workspace at fixed addresses: a
+// steady-state push (fixed n: W = K + A + n frames) hands forward_common the same (buffers, batch, frames, stream) as the one before and
+// replays its captured graph.
+struct fv_stream {
+    fv_engine* e = nullptr;
+    int B = 0, max_chunk = 0, K = 0, A = 0, cin = 0, cout = 0, hop = 0;
+    int64_t cap = 0;              // ring length in frames: K + A + max_chunk, >= every window the stream forms
+    bool tmpl = false;            // use_template generator: a template ring at the hop rate beside the mel ring
+    float* ring = nullptr;        // (B, C_in, cap), then (B, 1, cap * hop) for the template: the stream's only device allocation
+    float* ring_tmpl = nullptr;
+    size_t n_win_in = 0, n_win_tmpl = 0, n_win_out = 0;   // workspace: window input | window template | window output (floats, 256-byte
+    size_t model_bytes = 0;                                //   aligned each) | the forward's own workspace for the largest window
+    int64_t F = 0, E = 0;
+    bool flushed = false;
+    size_t ws_bytes() const { return (n_win_in + n_win_tmpl + n_win_out) * sizeof(float) + model_bytes; }
+    ~fv_stream() {
+        if (ring) (void)hipFree(ring);
+    }
+};
+
+static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_template, int32_t n, bool flush, float* d_out,
+                             int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = flush ? "fv_stream_flush" : "fv_stream_push";
+    if (frames_out) *frames_out = 0;
+    if (!st || !frames_out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    if (st->flushed) {
+        set_error("%s: the stream was flushed; fv_stream_reset it before the next utterance", fn);
+        return FV_ERR_STATE;
+    }
+    if (!flush) {
+        if (n < 0 || n > st->max_chunk) {
+            set_error("fv_stream_push: %d frames, more than max_chunk_frames = %d of this stream", n, st->max_chunk);
+            return FV_ERR_INVALID;
+        }
+        if (n == 0) return FV_OK;
+        if (!d_mel) {
+            set_error("fv_stream_push: null mel chunk");
+            return FV_ERR_INVALID;
+        }
+        if (st->tmpl && !d_template) {
+            set_error("fv_stream_push: the generator was built with use_template=True and every push needs a template chunk (B, 1, n*hop)");
+            return FV_ERR_INVALID;
+        }
+        if (!st->tmpl && d_template) {
+            set_error("fv_stream_push: template given but the generator was built with use_template=False");
+            return FV_ERR_INVALID;
+        }
+    }
+    if (!d_workspace || workspace_bytes < st->ws_bytes()) {
+        set_error("%s: workspace too small (%zu < %zu bytes, fv_stream_workspace_bytes)", fn, d_workspace ? workspace_bytes : (size_t)0,
+                  st->ws_bytes());
+        return FV_ERR_INVALID;
+    }
+    const int64_t F = st->F + (flush ? 0 : n);
+    const int64_t E2 = flush ? F : std::max(st->E, F - st->A);
+    const bool emit = E2 > st->E;
+    if (emit && !d_out) {
+        set_error("%s: null output (this call emits %lld frames)", fn, (long long)(E2 - st->E));
+        return FV_ERR_INVALID;
+    }
+    fv_engine* e = st->e;
+    const int B = st->B, hop = st->hop;
+    const int64_t w = emit ? std::max<int64_t>(0, st->E - st->K) : st->F;   // no emission: the chunk only goes into the ring
+    hipStream_t s = (hipStream_t)stream;
+    float* win_in = (float*)d_workspace;
+    float* win_tmpl = win_in + st->n_win_in;
+    float* win_out = win_tmpl + st->n_win_tmpl;
+    float* mws = win_out + st->n_win_out;
+    struct ProfGuard {
+        fv_engine* e;
+        void on() { g_prof = e->profiling ? &e->prof : nullptr; }
+        ~ProfGuard() { g_prof = nullptr; }
+    } guard{e};
+    guard.on();
+    if (!flush || emit) {
+        // the chunk into the ring at F mod cap, and the window [w, F) beside it; a flush has no chunk (n = 0: the window comes from the ring alone)
+        const int64_t nc = flush ? 0 : n, W = F - w;
+        FV_PROF(s, "stream_window", 0.0, 4.0 * B * st->cin * (2.0 * nc + (emit ? 2.0 * W : 0.0)),
+                launch_stream_window(d_mel, st->ring, emit ? win_in : nullptr, B, st->cin, st->cap, st->F, nc, w, s));
+        if (st->tmpl)
+            FV_PROF(s, "stream_window", 0.0, 4.0 * B * hop * (2.0 * nc + (emit ? 2.0 * W : 0.0)),
+                    launch_stream_window(d_template, st->ring_tmpl, emit ? win_tmpl : nullptr, B, 1, st->cap * hop, st->F * hop, nc * hop, w * hop, s));
+    }
+    if (emit) {
+        const int W = (int)(F - w);
+        const fv_status r = forward_common(e, win_in, st->tmpl ? win_tmpl : nullptr, nullptr, win_out, B, W, mws, st->model_bytes, stream);
+        if (r) return r;
+        guard.on();   // (forward_common leaves the profiler detached)
+        const int64_t len = (E2 - st->E) * hop;
+        FV_PROF(s, "stream_crop", 0.0, 8.0 * B * st->cout * len,
+                launch_stream_crop(win_out, d_out, B, st->cout, (int64_t)W * hop, (st->E - w) * hop, len, s));
+    }
+    *frames_out = E2 - st->E;
+    st->F = F;
+    st->E = E2;
+    if (flush) st->flushed = true;
+    return FV_OK;
+}
+
 extern "C" {
+
+FV_API int32_t fv_reach_frames(const fv_engine* e) {
+    if (!e || !e->finalized || e->frame_hop(1, 2, nullptr) < 1) return -1;
+    return e->reach_frames();
+}
+
+FV_API fv_status fv_stream_create(fv_engine* e, const fv_stream_config* cfg, fv_stream** out) {
+    if (!e || !cfg || !out) {
+        set_error("fv_stream_create: null argument");
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!e->finalized) {
+        set_error("fv_stream_create: call fv_finalize first");
+        return FV_ERR_STATE;
+    }
+    const char* why = nullptr;
+    const int hop = e->frame_hop(1, 2, &why);
+    if (hop < 1) {
+        set_error("fv_stream_create: this model cannot stream: %s", why);
+        return FV_ERR_UNSUPPORTED;
+    }
+    const int R = e->reach_frames();
+    if (cfg->batch < 1 || cfg->max_chunk_frames < 1 || cfg->context_frames < -1 || cfg->lookahead_frames < -1) {
+        set_error("fv_stream_create: batch (%d) and max_chunk_frames (%d) must be >= 1, context_frames (%d) and lookahead_frames (%d) >= 0 "
+                  "(-1: the reach, %d frames)", cfg->batch, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames, R);
+        return FV_ERR_INVALID;
+    }
+    std::unique_ptr<fv_stream> st(new fv_stream());
+    st->e = e;
+    st->B = cfg->batch;
+    st->max_chunk = cfg->max_chunk_frames;
+    st->K = cfg->context_frames < 0 ? R : cfg->context_frames;
+    st->A = cfg->lookahead_frames < 0 ? R : cfg->lookahead_frames;
+    st->cin = fv_input_channels(e);
+    st->cout = fv_output_channels(e);
+    st->hop = hop;
+    st->cap = (int64_t)st->K + st->A + st->max_chunk;
+    st->tmpl = (e->cfg.model == FV_MODEL_HIFIGAN || e->cfg.model == FV_MODEL_BIGVGAN || e->cfg.model == FV_MODEL_FIREFLY) && e->cfg.ups.use_template;
+    if (st->cap > (1 << 20)) {
+        set_error("fv_stream_create: context + lookahead + max_chunk_frames = %lld frames, more than 2^20", (long long)st->cap);
+        return FV_ERR_INVALID;
+    }
+    // Every window length the stream can form (1 ... cap frames) must be frame-aligned; the forward's workspace is the largest over them
+    // (fv_workspace_bytes need not be monotone in t_in: the tile plan switches in at the addressing span)
+    for (int W = 1; W <= st->cap; ++W) {
+        if (e->frame_hop(1, W, &why) != hop) {
+            set_error("fv_stream_create: this model cannot stream: %s (%d-frame window)", why, W);
+            return FV_ERR_UNSUPPORTED;
+        }
+        const size_t b = fv_workspace_bytes(e, st->B, W);
+        if (b == 0) {
+            set_error("fv_stream_create: no forward of %d x %d frames fits (split the batch)", st->B, W);
+            return FV_ERR_UNSUPPORTED;
+        }
+        st->model_bytes = std::max(st->model_bytes, b);
+    }
+    const size_t cap = (size_t)st->cap, B = (size_t)st->B;
+    st->n_win_in = align_up(B * st->cin * cap, 64);
+    st->n_win_tmpl = st->tmpl ? align_up(B * cap * hop, 64) : 0;
+    st->n_win_out = align_up(B * st->cout * cap * hop, 64);
+    const size_t n_ring = align_up(B * st->cin * cap, 64), n_ring_tmpl = st->tmpl ? B * cap * hop : 0;
+    FV_HIP_CHECK(hipMalloc((void**)&st->ring, (n_ring + n_ring_tmpl) * sizeof(float)));
+    st->ring_tmpl = st->tmpl ? st->ring + n_ring : nullptr;
+    *out = st.release();
+    return FV_OK;
+}
+
+FV_API size_t fv_stream_workspace_bytes(const fv_stream* s) { return s ? s->ws_bytes() : 0; }
+
+FV_API int64_t fv_stream_pending_frames(const fv_stream* s) { return s ? s->F - s->E : 0; }
+
+FV_API fv_status fv_stream_push(fv_stream* s, const float* d_mel, const float* d_template, int32_t n, float* d_out, int64_t* frames_out,
+                                void* d_workspace, size_t workspace_bytes, void* stream) {
+    return stream_step(s, d_mel, d_template, n, false, d_out, frames_out, d_workspace, workspace_bytes, stream);
+}
+
+FV_API fv_status fv_stream_flush(fv_stream* s, float* d_out, int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+    return stream_step(s, nullptr, nullptr, 0, true, d_out, frames_out, d_workspace, workspace_bytes, stream);
+}
+
+FV_API fv_status fv_stream_reset(fv_stream* s) {
+    if (!s) {
+        set_error("fv_stream_reset: null stream");
+        return FV_ERR_INVALID;
+    }
+    s->F = s->E = 0;
+    s->flushed = false;
+    return FV_OK;
+}
+
+FV_API void fv_stream_destroy(fv_stream* s) { delete s; }
 
 // ---- per-launch profile ----
 FV_API fv_status fv_profile_begin(fv_engine* e) {

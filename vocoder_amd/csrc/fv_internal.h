@@ -366,6 +366,10 @@ fv_status launch_magnitude(const float* spec, float* mag, int B, int nb, int T, 
 // long clips as a batch of equal-length time tiles (engine.hip run_model); hop: frames -> samples of the tensor being moved
 fv_status launch_gather_tiles(const float* x, float* tiles, int B, int C, int T, int n, int L, int stride, int hop, hipStream_t s);
 fv_status launch_scatter_tiles(const float* tiles, float* y, int B, int C, int T, int n, int L, int stride, int halo, int hop, hipStream_t s);
+// streaming synthesis (fv_stream_push): chunk -> ring + window; the emitted samples of the window's output -> the caller's buffer
+fv_status launch_stream_window(const float* chunk, float* ring, float* win, int B, int C, long long cap, long long c0, long long n, long long w,
+                               hipStream_t s);
+fv_status launch_stream_crop(const float* y, float* out, int B, int C, long long Ly, long long a, long long len, hipStream_t s);
 // rows [0,nb) = Re, [nbp, nbp+nb) = Im, zero padded to nbp = round_up(nb, 8)
 fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T, int nb, int nbp, hipStream_t s);
 // frames (B, n_fft, T) (already windowed by the synthesis basis) -> overlap-add, crop, divide by the envelope.

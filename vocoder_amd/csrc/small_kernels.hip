@@ -1291,6 +1291,62 @@ fv_status launch_scatter_tiles(const float* tiles, float* y, int B, int C, int T
     return FV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Streaming synthesis (engine.hip fv_stream_push).  A session keeps its last `cap` columns in a ring: column f at slot f mod cap.  Columns are
+// frames x hop (hop = 1 for the mel, the generator's hop for the pitch template), counted from the start of the utterance.  The chunk holds
+// the columns [c0, c0 + n), the window the columns [w, c0 + n), w <= c0.
+//   stream_window: ring[b][c][f mod cap] = chunk[b][c][f - c0] for the chunk's columns, and win[b][c][f - w] = column f for the window's, from
+//                  the chunk for f >= c0 and from the ring before it (win = NULL: the chunk goes into the ring only).  A window spans at most
+//                  `cap` columns, so the slots it reads and the slots the chunk overwrites are distinct: one launch does both.
+//   stream_crop  : out[b][c][j] = y[b][c][a + j], j < len — the emitted samples of the window's output.
+// Window starts, chunk sizes and ring slots follow the caller's pushes, so rows are not 16-byte aligned in general: each lane moves one fp32,
+// coalesced along the row.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void stream_window_kernel(const float* __restrict__ chunk, float* __restrict__ ring, float* __restrict__ win,
+                                                            int C, long long cap, long long c0, long long n, long long w, long long W, int b0) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= W) return;
+    const long long row = (long long)(b0 + blockIdx.z) * C + blockIdx.y;
+    const long long f = w + j;
+    float* slot = ring + row * cap + f % cap;
+    float v;
+    if (f >= c0) {
+        v = chunk[row * n + (f - c0)];
+        *slot = v;
+    } else {
+        v = *slot;
+    }
+    if (win) win[row * W + j] = v;
+}
+fv_status launch_stream_window(const float* chunk, float* ring, float* win, int B, int C, long long cap, long long c0, long long n, long long w,
+                               hipStream_t s) {
+    const long long W = c0 + n - w;
+    if (W <= 0) return FV_OK;
+    for (long long b0 = 0; b0 < B; b0 += kMaxGridZ) {
+        const unsigned nz = (unsigned)std::min<long long>(kMaxGridZ, (long long)B - b0);
+        hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((W + 255) / 256), C, nz), dim3(256), 0, s, chunk, ring, win, C, cap, c0, n, w, W,
+                           (int)b0);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+__global__ __launch_bounds__(256) void stream_crop_kernel(const float* __restrict__ y, float* __restrict__ out, int C, long long Ly, long long a,
+                                                          long long len, int b0) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= len) return;
+    const long long row = (long long)(b0 + blockIdx.z) * C + blockIdx.y;
+    out[row * len + j] = y[row * Ly + a + j];
+}
+fv_status launch_stream_crop(const float* y, float* out, int B, int C, long long Ly, long long a, long long len, hipStream_t s) {
+    if (len <= 0) return FV_OK;
+    for (long long b0 = 0; b0 < B; b0 += kMaxGridZ) {
+        const unsigned nz = (unsigned)std::min<long long>(kMaxGridZ, (long long)B - b0);
+        hipLaunchKernelGGL(stream_crop_kernel, dim3((unsigned)((len + 255) / 256), C, nz), dim3(256), 0, s, y, out, C, Ly, a, len, (int)b0);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+
 #ifdef FV_DEBUG_HOOKS   // not in the product library: `make BUILD=build_dbg LIB=libfishvoc_dbg.so EXTRA=-DFV_DEBUG_HOOKS`, then FV_LIB_PATH
 // Debug aid (tools/probe_lds_poison.py): fills the LDS of every CU with signalling garbage (NaN bit patterns) so that a kernel
 // which reads LDS it never wrote shows up as a changed / non-finite result instead of silently inheriting whatever the previous

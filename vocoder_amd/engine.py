@@ -4,12 +4,13 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+import weakref
 from typing import Mapping
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, streaming
 from ._lib import FishVocError, check  # noqa: F401
 
 _SIDE_STREAM_FOR_DEFAULT = os.environ.get("FV_DEFAULT_STREAM_SIDE", "0") == "1"   # experiments: see Engine.forward
@@ -206,8 +207,12 @@ class Engine:
         self._lock = threading.Lock()
         self._done: torch.cuda.Event | None = None
         self._last_stream = None
+        self._streams: weakref.WeakSet = weakref.WeakSet()   # live Streams: closed before the engine is destroyed
 
     def close(self) -> None:
+        """Destroys the engine; its live streams are closed first (their pushes then raise)."""
+        for st in list(getattr(self, "_streams", ())):
+            st.close()
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.fv_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -288,26 +293,49 @@ class Engine:
                 if self._done is not None:
                     self._done.synchronize()   # the old workspace goes back to the caching allocator: nothing may still use it
                 self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
-            cur = torch.cuda.current_stream(x.device)
-            run = cur
-            if cur.cuda_stream == 0 and (_SIDE_STREAM_FOR_DEFAULT or not self.graph_replay):
-                # Calls on the legacy default stream: the library captures them on a stream of its own and replays the graph on stream 0 (round 5).
-                # With replay switched OFF the kernels go to an engine-owned side stream, ordered after / before the caller's: a single clip's ~80 eager
-                # launches on the null stream itself measured 0.95 ms against 0.84 this way.  FV_DEFAULT_STREAM_SIDE=1 forces the side stream (A/B runs).
-                if self._side is None or self._side.device != x.device:
-                    self._side = torch.cuda.Stream(x.device)
-                run = self._side
-                run.wait_stream(cur)
-            if self._done is not None and self._last_stream != run.cuda_stream:
-                run.wait_event(self._done)       # order after the previous forward when it ran on another stream
+            cur, run = self._order_begin(x.device)
             check(self._launch(x, tptr, nptr, out, B, T, int(run.cuda_stream)))
-            if self._done is None:
-                self._done = torch.cuda.Event()
-            self._done.record(run)
-            self._last_stream = run.cuda_stream
-            if run is not cur:
-                cur.wait_stream(run)
+            self._order_end(cur, run)
         return out
+
+    def _order_begin(self, device):
+        """Under ``self._lock``: (the caller's stream, the stream to enqueue on), the latter ordered after the engine's previous call.  Every
+        call that enqueues work on this engine (``forward``, ``Stream.push`` / ``flush``) goes through this pair."""
+        cur = torch.cuda.current_stream(device)
+        run = cur
+        if cur.cuda_stream == 0 and (_SIDE_STREAM_FOR_DEFAULT or not self.graph_replay):
+            # Calls on the legacy default stream: the library captures them on a stream of its own and replays the graph on stream 0 (round 5).
+            # With replay switched OFF the kernels go to an engine-owned side stream, ordered after / before the caller's: a single clip's ~80 eager
+            # launches on the null stream itself measured 0.95 ms against 0.84 this way.  FV_DEFAULT_STREAM_SIDE=1 forces the side stream (A/B runs).
+            if self._side is None or self._side.device != device:
+                self._side = torch.cuda.Stream(device)
+            run = self._side
+            run.wait_stream(cur)
+        if self._done is not None and self._last_stream != run.cuda_stream:
+            run.wait_event(self._done)       # order after the previous call when it ran on another stream
+        return cur, run
+
+    def _order_end(self, cur, run) -> None:
+        """Under ``self._lock``, after a successful enqueue on ``run``: record it for the next call, and order the caller's stream after it."""
+        if self._done is None:
+            self._done = torch.cuda.Event()
+        self._done.record(run)
+        self._last_stream = run.cuda_stream
+        if run is not cur:
+            cur.wait_stream(run)
+
+    @property
+    def reach_frames(self) -> int:
+        """R, the generator's one-sided reach in input frames (fv_reach_frames); -1 when the model cannot stream."""
+        return int(self._lib.fv_reach_frames(self._h))
+
+    def stream(self, batch: int, max_chunk_frames: int, context_frames: int | None = None,
+               lookahead_frames: int | None = None) -> "Stream":
+        """A streaming session (``Stream``): ``batch`` utterances in lockstep, pushed at most ``max_chunk_frames`` mel frames at a time;
+        ``context_frames`` (K) and ``lookahead_frames`` (A) default to the reach R, where the streamed output matches the whole utterance."""
+        st = Stream(self, batch, max_chunk_frames, context_frames, lookahead_frames)
+        self._streams.add(st)
+        return st
 
     def _launch(self, x, tptr, nptr, out, B, T, stream: int) -> int:
         if nptr is not None:
@@ -331,6 +359,135 @@ class Engine:
         buf = ctypes.create_string_buffer(1 << 20)
         check(self._lib.fv_profile_end(self._h, buf, len(buf), ctypes.byref(need)))
         return json.loads(buf.value.decode())
+
+
+class Stream:
+    """Streaming synthesis on an ``Engine`` (``fv_stream``, include/fishvoc.h): ``push`` mel chunks of ``(B, C_in, n)``, get the audio of every
+    frame once ``lookahead_frames`` more have arrived; ``flush`` emits the rest at the utterance's end.  Each call returns a
+    ``(B, C_out, k * hop)`` tensor (``k`` may be 0).  The emission rule is ``vocoder_amd.streaming``.  Calls are ordered like ``Engine.forward``
+    (torch's current stream, the engine's lock and events); the stream owns its workspace, so forwards and other streams on the same engine may
+    be interleaved with it.  ``reset()`` starts the next utterance, ``close()`` frees the stream (also a context manager).  A stream dies with
+    its engine: after ``Engine.close()`` — or a module's reload / ``.to()``, which rebuild the engine — its calls raise ``FishVocError``."""
+
+    def __init__(self, engine: Engine, batch: int, max_chunk_frames: int, context_frames: int | None = None,
+                 lookahead_frames: int | None = None):
+        self._engine = engine
+        self._lib = engine._lib
+        self._h = ctypes.c_void_p()
+        if not engine._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, "Engine.stream: the engine is closed")
+        cfg = _lib.StreamConfig(int(batch), int(max_chunk_frames), -1 if context_frames is None else int(context_frames),
+                                -1 if lookahead_frames is None else int(lookahead_frames))
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_stream_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h)))
+            self._ws = torch.empty((int(self._lib.fv_stream_workspace_bytes(self._h)) + 3) // 4, dtype=torch.float32, device=engine.device)
+        self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
+        self.reach_frames = engine.reach_frames
+        self.context_frames = self.reach_frames if context_frames is None else int(context_frames)
+        self.lookahead_frames = self.reach_frames if lookahead_frames is None else int(lookahead_frames)
+        self.hop = engine.output_length(1)
+        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
+        self._F = self._E = 0
+        self._done: torch.cuda.Event | None = None
+
+    # -- counters (host-side: reading them never synchronises) --
+    @property
+    def received_frames(self) -> int:
+        return self._F
+
+    @property
+    def emitted_frames(self) -> int:
+        return self._E
+
+    @property
+    def pending_frames(self) -> int:
+        """F - E as the library counts it (fv_stream_pending_frames)."""
+        self._check_open()
+        return int(self._lib.fv_stream_pending_frames(self._h))
+
+    @property
+    def workspace_bytes(self) -> int:
+        self._check_open()
+        return int(self._lib.fv_stream_workspace_bytes(self._h))
+
+    def _check_open(self) -> None:
+        if not self._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, "this stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
+                                                  "the module): create a new stream")
+
+    def push(self, mel: torch.Tensor, template: torch.Tensor | None = None) -> torch.Tensor:
+        """``mel``: ``(B, C_in, n)``, ``n <= max_chunk_frames``; ``template``: ``(B, 1, n * hop)`` for a use_template generator."""
+        self._check_open()
+        _require_cuda(mel, "Stream.push")
+        if mel.dim() != 3 or mel.shape[0] != self.batch or mel.shape[1] != self.in_channels:
+            raise ValueError(f"expected a mel chunk of shape ({self.batch}, {self.in_channels}, n), got {tuple(mel.shape)}")
+        mel = mel.contiguous()
+        n = int(mel.shape[2])
+        tptr = None
+        if template is not None:
+            _require_cuda(template, "Stream.push template")
+            template = template.contiguous()
+            if tuple(template.shape) != (self.batch, 1, n * self.hop):
+                raise ValueError(f"expected a template chunk of shape {(self.batch, 1, n * self.hop)}, got {tuple(template.shape)}")
+            tptr = template.data_ptr()
+        return self._call(mel, tptr, n, flush=False)
+
+    def flush(self) -> torch.Tensor:
+        """The pending frames (at most ``lookahead_frames``) against the utterance's end; pushes raise afterwards until ``reset()``."""
+        self._check_open()
+        return self._call(None, None, 0, flush=True)
+
+    def _call(self, mel, tptr, n: int, flush: bool) -> torch.Tensor:
+        F, _, E2 = streaming.step(self._F, self._E, n, self.context_frames, self.lookahead_frames, flush)
+        k = E2 - self._E if (flush or n <= self.max_chunk_frames) else 0
+        eng = self._engine
+        dev = eng.device
+        out = torch.empty((self.batch, self.out_channels, k * self.hop), dtype=torch.float32, device=dev)
+        got = ctypes.c_int64(0)
+        with eng._lock, torch.cuda.device(dev):
+            self._check_open()
+            cur, run = eng._order_begin(dev)
+            if flush:
+                st = self._lib.fv_stream_flush(self._h, out.data_ptr() if k else None, ctypes.byref(got), self._ws.data_ptr(),
+                                               self._ws.numel() * 4, int(run.cuda_stream))
+            else:
+                st = self._lib.fv_stream_push(self._h, mel.data_ptr(), tptr, n, out.data_ptr() if k else None, ctypes.byref(got),
+                                              self._ws.data_ptr(), self._ws.numel() * 4, int(run.cuda_stream))
+            check(st)
+            eng._order_end(cur, run)
+            if self._done is None:
+                self._done = torch.cuda.Event()
+            self._done.record(run)
+        if got.value != k:
+            raise RuntimeError(f"stream emitted {got.value} frames where the emission rule says {k}")
+        self._F, self._E = F, E2
+        return out
+
+    def reset(self) -> None:
+        """Start the next utterance: F = E = 0; the ring and the workspace are kept."""
+        self._check_open()
+        check(self._lib.fv_stream_reset(self._h))
+        self._F = self._E = 0
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if self._done is not None:
+                self._done.synchronize()    # the ring and the workspace may still be in use on the device
+            self._lib.fv_stream_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._ws = None
+
+    def __enter__(self) -> "Stream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FusedConv:

@@ -9,6 +9,7 @@
 * ``main`` mirrors test.py:50-99: ``.pt``/``.pth`` mels (add a batch dim to 2-D mels, transpose when the last dim is
   ``num_mels``) and ``.wav`` audio (channels become batch items, log-mel on the GPU), write ``(B, 1, T)`` -> wav.
   PCM wav only and no resampling (librosa / soundfile are not available here): other inputs are refused, not guessed.
+  ``--chunk-frames N`` streams each input N mel frames at a time (``stream_synthesis``) instead of one whole-utterance forward.
 """
 from __future__ import annotations
 
@@ -145,6 +146,31 @@ def build_model(generator="hifigan", resolution="44100_512_2048", overrides=None
 
 
 @torch.no_grad()
+def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int):
+    """Pushes ``mel`` (B, num_mels, T) through ``generator.stream()`` ``chunk_frames`` frames at a time, then flushes (exact mode: the lookahead
+    and the left context are the generator's reach).  Returns (waveform (B, 1, T * hop), seconds to the first non-empty output, seconds per push)."""
+    if not hasattr(generator, "stream"):
+        raise ValueError(f"--chunk-frames: {type(generator).__name__} has no stream(); HiFiGAN / BigVGAN generators stream")
+    B, _, T = mel.shape
+    outs, lat, first = [], [], None
+    t0 = time.perf_counter()
+    with generator.stream(batch=B, max_chunk_frames=chunk_frames) as st:
+        for f in range(0, T, chunk_frames):
+            t1 = time.perf_counter()
+            y = st.push(mel[:, :, f:f + chunk_frames])
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - t1)
+            if first is None and y.shape[-1]:
+                first = time.perf_counter() - t0
+            outs.append(y)
+        outs.append(st.flush())
+        torch.cuda.synchronize()
+        if first is None:
+            first = time.perf_counter() - t0
+    return torch.cat(outs, dim=-1), first, lat
+
+
+@torch.no_grad()
 def main(argv=None):
     ap = argparse.ArgumentParser(description="mel (.pt) or audio (.wav) -> wav on the MI355X engine (mirrors fish_vocoder/test.py)")
     ap.add_argument("--generator", default="hifigan")
@@ -158,7 +184,12 @@ def main(argv=None):
     ap.add_argument("--trust-checkpoint", action="store_true",
                     help="fall back to a full unpickle (like the reference's plain torch.load) when the weights-only loader "
                          "refuses a Lightning checkpoint that holds non-tensor objects")
+    ap.add_argument("--chunk-frames", type=int, default=None,
+                    help="push each input through a stream, N mel frames at a time (same wav as the whole-utterance run, within 1 LSB); "
+                         "prints the time to first audio and the per-chunk p50 latency")
     a = ap.parse_args(argv)
+    if a.chunk_frames is not None and a.chunk_frames < 1:
+        ap.error("--chunk-frames must be >= 1")
     model = build_model(a.generator, a.resolution, {"num_mels": a.num_mels} if a.num_mels else None, a.config_root,
                         a.ckpt_path, trust_checkpoint=a.trust_checkpoint)
     inp = Path(a.input_path)
@@ -178,9 +209,14 @@ def main(argv=None):
                 mel = diffsinger_mel_to_ln(mel)
             mel = prepare_mel(mel, model.num_mels).to(model.device)
         t0 = time.time()
-        fake = model(None, None, input_spec=mel)[0]
-        torch.cuda.synchronize()
-        print(f"{f}: {fake.shape[-1] / model.sampling_rate:.2f}s of audio in {time.time() - t0:.4f}s")
+        if a.chunk_frames:
+            fake, first, lat = stream_synthesis(model.generator, mel, a.chunk_frames)
+            print(f"{f}: {fake.shape[-1] / model.sampling_rate:.2f}s of audio in {time.time() - t0:.4f}s, streamed in {a.chunk_frames}-frame "
+                  f"chunks: first audio after {first * 1e3:.2f} ms, per-chunk p50 {np.percentile(lat, 50) * 1e3:.2f} ms")
+        else:
+            fake = model(None, None, input_spec=mel)[0]
+            torch.cuda.synchronize()
+            print(f"{f}: {fake.shape[-1] / model.sampling_rate:.2f}s of audio in {time.time() - t0:.4f}s")
         out = Path(a.output_path) / f.relative_to(base).with_suffix(".wav")
         write_wav(out, fake.squeeze(1).cpu().numpy().T, model.sampling_rate)
 

@@ -104,6 +104,17 @@ class EngineModule(nn.Module):
                 noise = noise.to(device=x.device, dtype=torch.float32).reshape(-1)
             return self.engine(x.device)(x.to(torch.float32), None, template, noise)
 
+    def stream(self, batch: int = 1, max_chunk_frames: int = 64, **kw):
+        """Streaming synthesis on this module's engine (``vocoder_amd.engine.Stream``): ``push(mel[, template])`` chunks of at most
+        ``max_chunk_frames`` frames, ``flush()`` at the end.  ``context_frames`` / ``lookahead_frames`` default to the generator's reach.  Reloading
+        the weights or moving the module rebuilds the engine and closes its streams: create a new one then."""
+        p = next(self.parameters(), None)
+        if p is None or not p.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.stream needs the module on a HIP device (.to('cuda')); vocoder_amd has no CPU path")
+        if self.training:
+            raise RuntimeError(f"{type(self).__name__} is inference-only: call .eval() first")
+        return self.engine(p.device).stream(batch, max_chunk_frames, **kw)
+
     def remove_parametrizations(self):
         """Kept for API compatibility (hifigan.py:251).  Weight-norm is folded inside the engine at load time, so this
         is a no-op; unlike the reference's version (which raises TypeError) it is harmless."""
