@@ -327,6 +327,63 @@ FV_API fv_status fv_stream_reset(fv_stream* s);
 /* Frees the ring (call it before fv_destroy of its engine, once the stream's work has finished). */
 FV_API void fv_stream_destroy(fv_stream* s);
 
+/* -------- ragged batches: one call for utterances of different lengths.  Replaces `sequence_mask(lengths)` over a padded forward
+ *          (models/gan.py:237-238,291-299, utils/mask.py — the reference masks the result, it never makes a padded item equal to the item
+ *          alone) and the per-file loop of test.py:52-99.  --------
+ *
+ * lengths[b] frames of clip b are valid inside a padded (batch, C_in, t_max) input.  One call writes (batch, C_out, t_max * hop):
+ *   - samples [0, lengths[b] * hop) of row b are the clip's own forward: within 2e-5 * max(1, peak) of fv_forward on that clip alone (the
+ *     bound of the time tiles, the streams and batches of other sizes), and bit-identical to the same slice of fv_forward over the clip's
+ *     window (below) by the same engine and batch size;
+ *   - samples from lengths[b] * hop on are exactly 0.0f (the reference's `fake_audio * audio_mask`);
+ *   - nothing the caller left in the padding (x[b, :, lengths[b]:], NaN included) influences any output bit: it is never loaded.
+ * The plan.  R = fv_reach_frames.  A window (clip b, start a, frames n, keep [lo, hi)) lets the forward see the frames [a, a + n) of clip b,
+ * zero-filled from lengths[b] on, and copies out the samples of the clip's frames [lo, hi); windows of equal n run as ONE forward (a group).
+ * A clip of T frames: T = 0: no window.  1 <= T <= 2R: the window (b, 0, T, [0, T)) — groups by exact length.  T > 2R: a body window
+ * (b, 0, Tg, [0, T - R)) in a body group of Tg >= T frames (the zero fill past T is not the clip's end — the layers pad at the tensor edge —
+ * so only frames >= R before T are kept) and a tail window (b, T - 2R, 2R, [T - R, T)), whose right edge is the clip's true end; a clip with
+ * T == Tg keeps [0, T) of its body window and has no tail.  All tails and the clips of exactly 2R frames share one group.  Body groups: the
+ * long clips sorted by (T, b), cut into at most max_groups contiguous runs (never between two clips of one length), minimising
+ *     sum over runs ( clips * Tg + 2R * #{clips with T < Tg} + launch_frames ),   Tg = the run's longest clip,
+ * ties: the fewest runs, then — from the last run backwards — the run that starts earliest.  Groups are numbered by descending length,
+ * windows are listed by group, then by clip.  launch_frames (default 192) is the fixed cost of one more forward in frames, max_groups
+ * (default 8) bounds the BODY groups (short clips group by exact length on top of it: up to 2R more forwards); both move speed only, never
+ * a sample.  Equal lengths plan to one window per clip of n = T: exactly fv_forward.  vocoder_amd/ragged.py states the same plan in Python.
+ * Eligible models are the ones that stream (fv_reach_frames >= 0); the others get FV_ERR_UNSUPPORTED at fv_ragged_create, with the reason
+ * in fv_last_error.  A group longer than the addressing span of the conv kernels goes through the forward's own time tiles. */
+typedef struct fv_ragged_window {
+    int32_t clip, start, frames, keep_lo, keep_hi, group;
+} fv_ragged_window;
+
+/* Pure host: needs no device and no engine.  Writes the plan's windows to out (up to cap; out may be NULL when cap is 0) and returns how
+ * many the plan has — a return value above cap says how large out must be.  reach < 1, batch < 1, a negative length: FV_ERR_INVALID.
+ * launch_frames / max_groups <= 0: the defaults. */
+FV_API int32_t fv_ragged_plan(int32_t reach, const int32_t* host_lengths, int32_t batch, int32_t launch_frames, int32_t max_groups,
+                              fv_ragged_window* out, int32_t cap);
+
+typedef struct fv_ragged fv_ragged;
+
+/* Plans host_lengths (batch entries, each in [0, t_max]; else FV_ERR_INVALID) and uploads the window table — the plan's only device
+ * allocation, made on the current HIP device and freed by fv_ragged_destroy.  May synchronise; fv_ragged_forward never does. */
+FV_API fv_status fv_ragged_create(fv_engine* e, const int32_t* host_lengths, int32_t batch, int32_t t_max, int32_t launch_frames,
+                                  int32_t max_groups, fv_ragged** out);
+/* Bytes of device scratch fv_ragged_forward needs (256-byte aligned): window input | window template | window output, each sized for the
+ * largest group, then the largest group's own fv_workspace_bytes. */
+FV_API size_t fv_ragged_workspace_bytes(const fv_ragged* p);
+FV_API int32_t fv_ragged_num_groups(const fv_ragged* p);
+/* What forward g runs: *batch windows of *frames frames.  Returns FV_OK, or FV_ERR_INVALID for a g outside [0, fv_ragged_num_groups). */
+FV_API int32_t fv_ragged_group(const fv_ragged* p, int32_t g, int32_t* batch, int32_t* frames);
+/* The plan's windows, as fv_ragged_plan returns them. */
+FV_API int32_t fv_ragged_windows(const fv_ragged* p, fv_ragged_window* out, int32_t cap);
+/* d_in: (batch, C_in, t_max) fp32; d_template: (batch, 1, t_max * hop) for a use_template generator, NULL otherwise (a missing or
+ * unexpected template: FV_ERR_INVALID, as fv_forward); d_out: (batch, C_out, t_max * hop) fp32, every sample of which is written.  Per
+ * group, on `stream`, at fixed workspace addresses: gather of the windows, the unchanged forward (enqueued eagerly: the engine's captured
+ * graphs and their bookkeeping are left alone), scatter of the kept samples; then the rows' tails are zeroed.  Asynchronous; ordered like
+ * fv_forward on its engine.  Call fv_ragged_destroy before fv_destroy of the engine, once the plan's work has finished. */
+FV_API fv_status fv_ragged_forward(fv_ragged* p, const float* d_in, const float* d_template, float* d_out, void* d_workspace,
+                                   size_t workspace_bytes, void* stream);
+FV_API void fv_ragged_destroy(fv_ragged* p);
+
 /* -------- single fused conv layer (the hot kernel on its own; used by the parity tests and the roofline
  *          bench).  Stands in for one weight-normed nn.Conv1d / nn.ConvTranspose1d call plus the elementwise
  *          ops the reference runs around it (F.silu before, residual add after: hifigan.py:101-108). -------- */

@@ -40,6 +40,8 @@ EXPORTS = (
     "fv_set_graph_replay", "fv_get_graph_replay", "fv_reload_env", "fv_set_conv_algorithm", "fv_set_batch_invariant", "fv_conv_set_algorithm",
     "fv_reach_frames", "fv_stream_create", "fv_stream_workspace_bytes", "fv_stream_pending_frames", "fv_stream_push", "fv_stream_flush",
     "fv_stream_reset", "fv_stream_destroy",
+    "fv_ragged_plan", "fv_ragged_create", "fv_ragged_workspace_bytes", "fv_ragged_num_groups", "fv_ragged_group", "fv_ragged_windows",
+    "fv_ragged_forward", "fv_ragged_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -90,6 +92,10 @@ class ConvDesc(ctypes.Structure):
 
 class StreamConfig(ctypes.Structure):
     _fields_ = [("batch", _i32), ("max_chunk_frames", _i32), ("context_frames", _i32), ("lookahead_frames", _i32)]
+
+
+class RaggedWindow(ctypes.Structure):
+    _fields_ = [("clip", _i32), ("start", _i32), ("frames", _i32), ("keep_lo", _i32), ("keep_hi", _i32), ("group", _i32)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -190,6 +196,23 @@ def lib() -> ctypes.CDLL:
     L.fv_stream_reset.restype = _i32
     L.fv_stream_destroy.argtypes = [vp]
     L.fv_stream_destroy.restype = None
+    i32p, rwp = ctypes.POINTER(_i32), ctypes.POINTER(RaggedWindow)
+    L.fv_ragged_plan.argtypes = [_i32, i32p, _i32, _i32, _i32, rwp, _i32]
+    L.fv_ragged_plan.restype = _i32
+    L.fv_ragged_create.argtypes = [vp, i32p, _i32, _i32, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_ragged_create.restype = _i32
+    L.fv_ragged_workspace_bytes.argtypes = [vp]
+    L.fv_ragged_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_ragged_num_groups.argtypes = [vp]
+    L.fv_ragged_num_groups.restype = _i32
+    L.fv_ragged_group.argtypes = [vp, _i32, i32p, i32p]
+    L.fv_ragged_group.restype = _i32
+    L.fv_ragged_windows.argtypes = [vp, rwp, _i32]
+    L.fv_ragged_windows.restype = _i32
+    L.fv_ragged_forward.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.fv_ragged_forward.restype = _i32
+    L.fv_ragged_destroy.argtypes = [vp]
+    L.fv_ragged_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

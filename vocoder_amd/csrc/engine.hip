@@ -1804,8 +1804,9 @@ FV_API fv_status fv_forward_refinegan(fv_engine* e, const float* d_mel, const fl
     return forward_common(e, d_mel, d_template, d_noise, d_out, batch, t_in, d_workspace, workspace_bytes, stream);
 }
 
-static fv_status forward_common(fv_engine* e, const float* d_in, const float* d_template, const float* d_noise, float* d_out,
-                                int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes, void* stream) {
+// What every entry that runs the model checks before it enqueues anything (forward_common; fv_ragged_forward for each of its groups)
+static fv_status check_forward(fv_engine* e, const float* d_in, const float* d_template, float* d_out, int32_t batch, int32_t t_in,
+                               void* d_workspace, size_t workspace_bytes) {
     if (!e || !d_in || !d_out) {
         set_error("fv_forward: null argument");
         return FV_ERR_INVALID;
@@ -1856,15 +1857,26 @@ static fv_status forward_common(fv_engine* e, const float* d_in, const float* d_
         set_error("fv_forward: template given but the generator was built with use_template=False");
         return FV_ERR_INVALID;
     }
-    e->cur_template = d_template;
-    e->cur_noise = d_noise;
-    const AlgoScope algo_scope(e->algo, e->invariant);
+    return FV_OK;
+}
+// ... and what it sets up around run_model for the duration of the call: the template / noise of this call, the engine's conv algorithm and
+// the profiler (detached again when the scope ends)
+struct ForwardScope {
+    AlgoScope algo;
+    ForwardScope(fv_engine* e, const float* d_template, const float* d_noise) : algo(e->algo, e->invariant) {
+        e->cur_template = d_template;
+        e->cur_noise = d_noise;
+        g_prof = e->profiling ? &e->prof : nullptr;
+    }
+    ~ForwardScope() { g_prof = nullptr; }
+};
+
+static fv_status forward_common(fv_engine* e, const float* d_in, const float* d_template, const float* d_noise, float* d_out,
+                                int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (const fv_status st = check_forward(e, d_in, d_template, d_out, batch, t_in, d_workspace, workspace_bytes)) return st;
+    const ForwardScope scope(e, d_template, d_noise);
     hipStream_t s = (hipStream_t)stream;
     float* ws = (float*)d_workspace;
-    struct ProfGuard {
-        ProfGuard(fv_engine* e) { g_prof = e->profiling ? &e->prof : nullptr; }
-        ~ProfGuard() { g_prof = nullptr; }
-    } guard(e);
 
     // hipGraph replay: a forward is ~110 launches plus fork/join events; at small batch the host launch cost dominates
     // (p50 clip latency).  The launch sequence is static for a given (pointers, batch, frames, stream), so the second
@@ -2510,6 +2522,268 @@ FV_API fv_status fv_stream_reset(fv_stream* s) {
 }
 
 FV_API void fv_stream_destroy(fv_stream* s) { delete s; }
+
+}  // extern "C"
+
+// ---- ragged batches ----------------------------------------------------------------------------------------------------
+// The plan (include/fishvoc.h states it; vocoder_amd/ragged.py restates it in Python, and the tests compare the two window for window).
+static constexpr int kRaggedLaunchFrames = 192, kRaggedMaxGroups = 8;
+
+static fv_status ragged_plan(int reach, const int32_t* lengths, int batch, int launch_frames, int max_groups, std::vector<fv_ragged_window>& out) {
+    out.clear();
+    if (reach < 1 || reach > (1 << 20) || !lengths || batch < 1) {
+        set_error("fv_ragged_plan: reach (%d) and batch (%d) must be >= 1 and the lengths given", reach, batch);
+        return FV_ERR_INVALID;
+    }
+    for (int b = 0; b < batch; ++b)
+        if (lengths[b] < 0) {
+            set_error("fv_ragged_plan: negative length %d of clip %d", lengths[b], b);
+            return FV_ERR_INVALID;
+        }
+    if (launch_frames <= 0) launch_frames = kRaggedLaunchFrames;
+    if (max_groups <= 0) max_groups = kRaggedMaxGroups;
+    const int R2 = 2 * reach;
+    std::vector<std::pair<int, int>> lng;   // (T, b) of the long clips, ascending
+    for (int b = 0; b < batch; ++b)
+        if (lengths[b] > R2) lng.emplace_back(lengths[b], b);
+    std::sort(lng.begin(), lng.end());
+    const int m = (int)lng.size();
+    struct Item {
+        int n, b, a, lo, hi;
+    };
+    std::vector<Item> items;
+    if (m > 0) {
+        // f[k][j]: the least cost of the first j clips in exactly k runs; a run [i, j) costs (j - i) Tg + 2R #{T < Tg} + launch_frames
+        const int K = std::min(max_groups, m);
+        const int64_t INF = (int64_t)1 << 62;
+        std::vector<int> first_eq(m);   // first index of the block of equal lengths that clip j belongs to
+        for (int j = 0; j < m; ++j) first_eq[j] = (j > 0 && lng[j].first == lng[j - 1].first) ? first_eq[j - 1] : j;
+        std::vector<std::vector<int64_t>> f(K + 1, std::vector<int64_t>(m + 1, INF));
+        std::vector<std::vector<int>> arg(K + 1, std::vector<int>(m + 1, -1));
+        f[0][0] = 0;
+        for (int k = 1; k <= K; ++k)
+            for (int j = k; j <= m; ++j) {
+                if (j < m && lng[j].first == lng[j - 1].first) continue;   // no cut between two clips of one length
+                for (int i = k - 1; i < j; ++i) {
+                    if (f[k - 1][i] >= INF) continue;
+                    const int64_t c = f[k - 1][i] + (int64_t)(j - i) * lng[j - 1].first + (int64_t)R2 * std::max(0, first_eq[j - 1] - i) + launch_frames;
+                    if (c < f[k][j]) {   // strict: the earliest start wins a tie
+                        f[k][j] = c;
+                        arg[k][j] = i;
+                    }
+                }
+            }
+        int best = 1;
+        for (int k = 2; k <= K; ++k)
+            if (f[k][m] < f[best][m]) best = k;   // strict: the fewest runs win a tie
+        for (int k = best, j = m; k >= 1; --k) {
+            const int i = arg[k][j], tg = lng[j - 1].first;
+            for (int t = i; t < j; ++t) {
+                const int T = lng[t].first, b = lng[t].second;
+                if (T == tg) {
+                    items.push_back({tg, b, 0, 0, T});
+                } else {
+                    items.push_back({tg, b, 0, 0, T - reach});
+                    items.push_back({R2, b, T - R2, T - reach, T});
+                }
+            }
+            j = i;
+        }
+    }
+    for (int b = 0; b < batch; ++b)
+        if (lengths[b] >= 1 && lengths[b] <= R2) items.push_back({lengths[b], b, 0, 0, lengths[b]});
+    std::sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.n != y.n ? x.n > y.n : x.b < y.b; });
+    int group = -1, prev = -1;
+    for (const Item& it : items) {
+        if (it.n != prev) {
+            ++group;
+            prev = it.n;
+        }
+        out.push_back({it.b, it.a, it.n, it.lo, it.hi, group});
+    }
+    return FV_OK;
+}
+
+struct fv_ragged {
+    fv_engine* e = nullptr;
+    int B = 0, t_max = 0, cin = 0, cout = 0, hop = 0, min_len = 0;
+    bool tmpl = false;
+    std::vector<fv_ragged_window> win;
+    struct Group {
+        int first, count, frames;
+    };
+    std::vector<Group> groups;
+    fv_ragged_window* d_win = nullptr;   // the window table, then the lengths: the plan's only device allocation
+    int32_t* d_len = nullptr;
+    size_t n_in = 0, n_tmpl = 0, n_out = 0;   // workspace: window input | window template | window output (floats, sized for the largest group)
+    size_t model_bytes = 0;                   //   | the largest group's own workspace
+    size_t ws_bytes() const { return (n_in + n_tmpl + n_out) * sizeof(float) + model_bytes; }
+    ~fv_ragged() {
+        if (d_win) (void)hipFree(d_win);
+    }
+};
+
+static int32_t copy_windows(const std::vector<fv_ragged_window>& w, fv_ragged_window* out, int32_t cap) {
+    if (out && cap > 0) std::copy(w.begin(), w.begin() + std::min<size_t>(w.size(), (size_t)cap), out);
+    return (int32_t)w.size();
+}
+
+extern "C" {
+
+FV_API int32_t fv_ragged_plan(int32_t reach, const int32_t* host_lengths, int32_t batch, int32_t launch_frames, int32_t max_groups,
+                              fv_ragged_window* out, int32_t cap) {
+    std::vector<fv_ragged_window> w;
+    if (const fv_status st = ragged_plan(reach, host_lengths, batch, launch_frames, max_groups, w)) return st;
+    if (cap < 0 || (cap > 0 && !out)) {
+        set_error("fv_ragged_plan: cap = %d without room for it", cap);
+        return FV_ERR_INVALID;
+    }
+    return copy_windows(w, out, cap);
+}
+
+FV_API fv_status fv_ragged_create(fv_engine* e, const int32_t* host_lengths, int32_t batch, int32_t t_max, int32_t launch_frames,
+                                  int32_t max_groups, fv_ragged** out) {
+    if (!e || !host_lengths || !out) {
+        set_error("fv_ragged_create: null argument");
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!e->finalized) {
+        set_error("fv_ragged_create: call fv_finalize first");
+        return FV_ERR_STATE;
+    }
+    const char* why = nullptr;
+    const int hop = e->frame_hop(1, 2, &why);
+    if (hop < 1) {
+        set_error("fv_ragged_create: this model cannot run ragged batches: %s", why);
+        return FV_ERR_UNSUPPORTED;
+    }
+    if (batch < 1 || t_max < 1) {
+        set_error("fv_ragged_create: batch (%d) and t_max (%d) must be >= 1", batch, t_max);
+        return FV_ERR_INVALID;
+    }
+    for (int b = 0; b < batch; ++b)
+        if (host_lengths[b] < 0 || host_lengths[b] > t_max) {
+            set_error("fv_ragged_create: length %d of clip %d is outside [0, t_max = %d]", host_lengths[b], b, t_max);
+            return FV_ERR_INVALID;
+        }
+    std::unique_ptr<fv_ragged> p(new fv_ragged());
+    p->e = e;
+    p->B = batch;
+    p->t_max = t_max;
+    p->cin = fv_input_channels(e);
+    p->cout = fv_output_channels(e);
+    p->hop = hop;
+    p->tmpl = (e->cfg.model == FV_MODEL_HIFIGAN || e->cfg.model == FV_MODEL_BIGVGAN || e->cfg.model == FV_MODEL_FIREFLY) && e->cfg.ups.use_template;
+    p->min_len = *std::min_element(host_lengths, host_lengths + batch);
+    if (const fv_status st = ragged_plan(e->reach_frames(), host_lengths, batch, launch_frames, max_groups, p->win)) return st;
+    size_t max_items = 0;
+    for (int i = 0; i < (int)p->win.size(); ++i) {
+        const fv_ragged_window& w = p->win[i];
+        // what the kernels rely on: the window starts inside the clip and its kept frames lie inside the window and the clip
+        if (w.start < 0 || w.start >= host_lengths[w.clip] || w.keep_lo < w.start || w.keep_hi > std::min(w.start + w.frames, host_lengths[w.clip]) ||
+            w.keep_lo >= w.keep_hi) {
+            set_error("fv_ragged_create: internal error, window %d of the plan is malformed", i);
+            return FV_ERR_STATE;
+        }
+        if (p->groups.empty() || w.group != (int)p->groups.size() - 1) p->groups.push_back({i, 0, w.frames});
+        p->groups.back().count++;
+    }
+    for (const auto& g : p->groups) {
+        if (e->frame_hop(1, g.frames, &why) != hop) {
+            set_error("fv_ragged_create: this model cannot run ragged batches: %s (%d-frame window)", why, g.frames);
+            return FV_ERR_UNSUPPORTED;
+        }
+        const size_t b = fv_workspace_bytes(e, g.count, g.frames);
+        if (b == 0) {
+            set_error("fv_ragged_create: no forward of %d x %d frames fits (split the batch)", g.count, g.frames);
+            return FV_ERR_UNSUPPORTED;
+        }
+        p->model_bytes = std::max(p->model_bytes, b);
+        max_items = std::max(max_items, (size_t)g.count * g.frames);
+    }
+    p->n_in = align_up(max_items * p->cin, 64);
+    p->n_tmpl = p->tmpl ? align_up(max_items * hop, 64) : 0;
+    p->n_out = align_up(max_items * p->cout * hop, 64);
+    const size_t wbytes = align_up(p->win.size() * sizeof(fv_ragged_window), 256);
+    FV_HIP_CHECK(hipMalloc((void**)&p->d_win, wbytes + (size_t)batch * sizeof(int32_t)));
+    p->d_len = (int32_t*)((char*)p->d_win + wbytes);
+    if (!p->win.empty()) FV_HIP_CHECK(hipMemcpy(p->d_win, p->win.data(), p->win.size() * sizeof(fv_ragged_window), hipMemcpyHostToDevice));
+    FV_HIP_CHECK(hipMemcpy(p->d_len, host_lengths, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice));
+    *out = p.release();
+    return FV_OK;
+}
+
+FV_API size_t fv_ragged_workspace_bytes(const fv_ragged* p) { return p ? p->ws_bytes() : 0; }
+
+FV_API int32_t fv_ragged_num_groups(const fv_ragged* p) { return p ? (int32_t)p->groups.size() : 0; }
+
+FV_API int32_t fv_ragged_group(const fv_ragged* p, int32_t g, int32_t* batch, int32_t* frames) {
+    if (!p || g < 0 || g >= (int32_t)p->groups.size()) {
+        set_error("fv_ragged_group: no group %d", g);
+        return FV_ERR_INVALID;
+    }
+    if (batch) *batch = p->groups[g].count;
+    if (frames) *frames = p->groups[g].frames;
+    return FV_OK;
+}
+
+FV_API int32_t fv_ragged_windows(const fv_ragged* p, fv_ragged_window* out, int32_t cap) {
+    if (!p || cap < 0 || (cap > 0 && !out)) {
+        set_error("fv_ragged_windows: null argument");
+        return FV_ERR_INVALID;
+    }
+    return copy_windows(p->win, out, cap);
+}
+
+FV_API fv_status fv_ragged_forward(fv_ragged* p, const float* d_in, const float* d_template, float* d_out, void* d_workspace,
+                                   size_t workspace_bytes, void* stream) {
+    if (!p || !d_in || !d_out) {
+        set_error("fv_ragged_forward: null argument");
+        return FV_ERR_INVALID;
+    }
+    if (!d_workspace || workspace_bytes < p->ws_bytes()) {
+        set_error("fv_ragged_forward: workspace too small (%zu < %zu bytes, fv_ragged_workspace_bytes)", d_workspace ? workspace_bytes : (size_t)0,
+                  p->ws_bytes());
+        return FV_ERR_INVALID;
+    }
+    fv_engine* e = p->e;
+    float* win_in = (float*)d_workspace;
+    float* win_tmpl = win_in + p->n_in;
+    float* win_out = win_tmpl + p->n_tmpl;
+    float* mws = win_out + p->n_out;
+    const float* group_tmpl = d_template ? win_tmpl : nullptr;   // (a missing / unexpected template: check_forward's message)
+    if (p->tmpl != (d_template != nullptr)) {   // (stated here too: a batch of empty clips runs no forward that would check it)
+        set_error(p->tmpl ? "fv_forward: this generator was built with use_template=True and needs a template (B, 1, T*hop)"
+                          : "fv_forward: template given but the generator was built with use_template=False");
+        return FV_ERR_INVALID;
+    }
+    for (const auto& g : p->groups)   // everything is checked before anything is enqueued
+        if (const fv_status st = check_forward(e, win_in, group_tmpl, win_out, g.count, g.frames, mws, p->model_bytes)) return st;
+    hipStream_t s = (hipStream_t)stream;
+    const int hop = p->hop;
+    const long long T = p->t_max;
+    const ForwardScope scope(e, nullptr, nullptr);
+    for (const auto& g : p->groups) {
+        const long long n = g.frames;
+        FV_PROF(s, "ragged_gather", 0.0, 8.0 * g.count * p->cin * n,
+                launch_ragged_gather(d_in, win_in, p->d_win, p->d_len, g.first, g.count, p->cin, T, n, 1, s));
+        if (p->tmpl)
+            FV_PROF(s, "ragged_gather", 0.0, 8.0 * g.count * n * hop,
+                    launch_ragged_gather(d_template, win_tmpl, p->d_win, p->d_len, g.first, g.count, 1, T * hop, n * hop, hop, s));
+        e->cur_template = group_tmpl;
+        // eagerly, past forward_common's graph bookkeeping: a ragged call neither evicts a captured graph nor resets the last key
+        const fv_status st = e->run_model(win_in, win_out, g.count, g.frames, mws, s);
+        if (st) return st;
+        FV_PROF(s, "ragged_scatter", 0.0, 8.0 * g.count * p->cout * n * hop,
+                launch_ragged_scatter(win_out, d_out, p->d_win, g.first, g.count, p->cout, T * hop, n * hop, hop, s));
+    }
+    FV_PROF(s, "ragged_zero_tail", 0.0, 4.0 * p->B * p->cout * (double)(p->t_max - p->min_len) * hop,
+            launch_ragged_zero_tail(d_out, p->d_len, p->B, p->cout, T * hop, (long long)(p->t_max - p->min_len) * hop, hop, s));
+    return FV_OK;
+}
+
+FV_API void fv_ragged_destroy(fv_ragged* p) { delete p; }
 
 // ---- per-launch profile ----
 FV_API fv_status fv_profile_begin(fv_engine* e) {

@@ -370,6 +370,13 @@ fv_status launch_scatter_tiles(const float* tiles, float* y, int B, int C, int T
 fv_status launch_stream_window(const float* chunk, float* ring, float* win, int B, int C, long long cap, long long c0, long long n, long long w,
                                hipStream_t s);
 fv_status launch_stream_crop(const float* y, float* out, int B, int C, long long Ly, long long a, long long len, hipStream_t s);
+// ragged batches (fv_ragged_forward): windows [first, first + count) of the device table `tab` <-> one group's buffers; T / L: columns of a
+// clip's row / of a window (frames x hop); the rows' tails past each clip's length zeroed
+fv_status launch_ragged_gather(const float* x, float* win, const fv_ragged_window* tab, const int* lens, int first, int count, int C,
+                               long long T, long long L, int hop, hipStream_t s);
+fv_status launch_ragged_scatter(const float* win, float* y, const fv_ragged_window* tab, int first, int count, int C, long long T,
+                                long long L, int hop, hipStream_t s);
+fv_status launch_ragged_zero_tail(float* y, const int* lens, int B, int C, long long T, long long span, int hop, hipStream_t s);
 // rows [0,nb) = Re, [nbp, nbp+nb) = Im, zero padded to nbp = round_up(nb, 8)
 fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T, int nb, int nbp, hipStream_t s);
 // frames (B, n_fft, T) (already windowed by the synthesis basis) -> overlap-add, crop, divide by the envelope.

@@ -1347,6 +1347,79 @@ fv_status launch_stream_crop(const float* y, float* out, int B, int C, long long
     return FV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ragged batches (engine.hip fv_ragged_forward).  `tab` is the plan's window table on the device (fv_ragged_window: clip b, start a, frames n,
+// keep [lo, hi)), `lens` the clips' lengths in frames; item i of a launch is window i0 + blockIdx.z of the table, stored as item
+// (i0 - first + blockIdx.z) of its group's buffer.  Columns are frames x hop (hop = 1 for the mel, the generator's hop for the pitch template
+// and the waveform); T = columns of a clip's row in the caller's tensor, L = columns of a window.
+//   gather   : win[i][c][l] = a hop + l < len_b hop ? x[b][c][a hop + l] : 0.  The padding is never LOADED: the address is clamped to the
+//              window's first column (a < len_b always) and the value selected, so a NaN the caller left there cannot enter through 0 * x.
+//   scatter  : y[b][c][lo hop + j] = out[i][c][(lo - a) hop + j], j < (hi - lo) hop
+//   zero_tail: y[b][c][len_b hop ...) = 0 up to the row's end
+// Rows start at arbitrary sample offsets: each lane moves one fp32, coalesced along the row (as the stream kernels).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ragged_gather_kernel(const float* __restrict__ x, float* __restrict__ win,
+                                                            const fv_ragged_window* __restrict__ tab, const int* __restrict__ lens, int C,
+                                                            long long T, long long L, int hop, int first, int i0) {
+    const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (l >= L) return;
+    const int c = blockIdx.y, i = i0 + blockIdx.z;
+    const fv_ragged_window w = tab[i];
+    const long long a = (long long)w.start * hop, len = (long long)lens[w.clip] * hop;
+    const bool valid = a + l < len;
+    const float v = x[((long long)w.clip * C + c) * T + (valid ? a + l : a)];
+    win[((long long)(i - first) * C + c) * L + l] = valid ? v : 0.0f;
+}
+fv_status launch_ragged_gather(const float* x, float* win, const fv_ragged_window* tab, const int* lens, int first, int count, int C,
+                               long long T, long long L, int hop, hipStream_t s) {
+    if (count <= 0 || L <= 0) return FV_OK;
+    for (long long i0 = 0; i0 < count; i0 += kMaxGridZ) {
+        const unsigned nz = (unsigned)std::min<long long>(kMaxGridZ, count - i0);
+        hipLaunchKernelGGL(ragged_gather_kernel, dim3((unsigned)((L + 255) / 256), C, nz), dim3(256), 0, s, x, win, tab, lens, C, T, L, hop,
+                           first, (int)(first + i0));
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+__global__ __launch_bounds__(256) void ragged_scatter_kernel(const float* __restrict__ win, float* __restrict__ y,
+                                                             const fv_ragged_window* __restrict__ tab, int C, long long T, long long L,
+                                                             int hop, int first, int i0) {
+    const int c = blockIdx.y, i = i0 + blockIdx.z;
+    const fv_ragged_window w = tab[i];
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= (long long)(w.keep_hi - w.keep_lo) * hop) return;
+    y[((long long)w.clip * C + c) * T + (long long)w.keep_lo * hop + j] =
+        win[((long long)(i - first) * C + c) * L + (long long)(w.keep_lo - w.start) * hop + j];
+}
+fv_status launch_ragged_scatter(const float* win, float* y, const fv_ragged_window* tab, int first, int count, int C, long long T,
+                                long long L, int hop, hipStream_t s) {
+    if (count <= 0 || L <= 0) return FV_OK;
+    for (long long i0 = 0; i0 < count; i0 += kMaxGridZ) {
+        const unsigned nz = (unsigned)std::min<long long>(kMaxGridZ, count - i0);
+        hipLaunchKernelGGL(ragged_scatter_kernel, dim3((unsigned)((L + 255) / 256), C, nz), dim3(256), 0, s, win, y, tab, C, T, L, hop, first,
+                           (int)(first + i0));
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+__global__ __launch_bounds__(256) void ragged_zero_tail_kernel(float* __restrict__ y, const int* __restrict__ lens, int C, long long T, int hop,
+                                                               int b0) {
+    const int b = b0 + blockIdx.z;
+    const long long j = (long long)lens[b] * hop + (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= T) return;
+    y[((long long)b * C + blockIdx.y) * T + j] = 0.0f;
+}
+// span: columns of the longest tail, (t_max - min length) * hop
+fv_status launch_ragged_zero_tail(float* y, const int* lens, int B, int C, long long T, long long span, int hop, hipStream_t s) {
+    if (span <= 0) return FV_OK;
+    for (long long b0 = 0; b0 < B; b0 += kMaxGridZ) {
+        const unsigned nz = (unsigned)std::min<long long>(kMaxGridZ, (long long)B - b0);
+        hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3((unsigned)((span + 255) / 256), C, nz), dim3(256), 0, s, y, lens, C, T, hop, (int)b0);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+
 #ifdef FV_DEBUG_HOOKS   // not in the product library: `make BUILD=build_dbg LIB=libfishvoc_dbg.so EXTRA=-DFV_DEBUG_HOOKS`, then FV_LIB_PATH
 // Debug aid (tools/probe_lds_poison.py): fills the LDS of every CU with signalling garbage (NaN bit patterns) so that a kernel
 // which reads LDS it never wrote shows up as a changed / non-finite result instead of silently inheriting whatever the previous

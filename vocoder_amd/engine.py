@@ -207,7 +207,8 @@ class Engine:
         self._lock = threading.Lock()
         self._done: torch.cuda.Event | None = None
         self._last_stream = None
-        self._streams: weakref.WeakSet = weakref.WeakSet()   # live Streams: closed before the engine is destroyed
+        self._streams: weakref.WeakSet = weakref.WeakSet()   # live Streams and RaggedPlans: closed before the engine is destroyed
+        self._ragged_last: RaggedPlan | None = None          # the plan forward_ragged made for the last (lengths, t_max) it saw
 
     def close(self) -> None:
         """Destroys the engine; its live streams are closed first (their pushes then raise)."""
@@ -298,12 +299,13 @@ class Engine:
             self._order_end(cur, run)
         return out
 
-    def _order_begin(self, device):
+    def _order_begin(self, device, eager: bool = False):
         """Under ``self._lock``: (the caller's stream, the stream to enqueue on), the latter ordered after the engine's previous call.  Every
-        call that enqueues work on this engine (``forward``, ``Stream.push`` / ``flush``) goes through this pair."""
+        call that enqueues work on this engine (``forward``, ``Stream.push`` / ``flush``, ``forward_ragged``) goes through this pair.
+        ``eager``: the call enqueues its kernels eagerly whatever the replay setting (``forward_ragged``)."""
         cur = torch.cuda.current_stream(device)
         run = cur
-        if cur.cuda_stream == 0 and (_SIDE_STREAM_FOR_DEFAULT or not self.graph_replay):
+        if cur.cuda_stream == 0 and (eager or _SIDE_STREAM_FOR_DEFAULT or not self.graph_replay):
             # Calls on the legacy default stream: the library captures them on a stream of its own and replays the graph on stream 0 (round 5).
             # With replay switched OFF the kernels go to an engine-owned side stream, ordered after / before the caller's: a single clip's ~80 eager
             # launches on the null stream itself measured 0.95 ms against 0.84 this way.  FV_DEFAULT_STREAM_SIDE=1 forces the side stream (A/B runs).
@@ -337,6 +339,78 @@ class Engine:
         self._streams.add(st)
         return st
 
+    def ragged_plan(self, lengths, t_max: int | None = None, launch_frames: int = 0, max_groups: int = 0) -> "RaggedPlan":
+        """The plan of a ragged batch (``RaggedPlan``; the rule: ``vocoder_amd.ragged``) for ``lengths[b]`` valid frames per clip inside a
+        ``(B, C_in, t_max)`` input (``t_max`` defaults to the longest clip).  Reuse it for every call with these lengths."""
+        p = RaggedPlan(self, lengths, t_max, launch_frames, max_groups)
+        self._streams.add(p)
+        return p
+
+    def forward_ragged(self, x: torch.Tensor, lengths, out: torch.Tensor | None = None, template: torch.Tensor | None = None,
+                       plan: "RaggedPlan | None" = None) -> torch.Tensor:
+        """``x``: ``(B, C_in, T_max)`` with ``lengths[b]`` valid frames in row ``b`` (host integers) -> ``(B, C_out, T_max * hop)``: the samples
+        ``[0, lengths[b] * hop)`` of row ``b`` are the clip's own forward, the rest is 0.0, and whatever the padding of ``x`` holds (NaN
+        included) is never read.  Without ``plan`` the engine keeps the plan of the last ``(lengths, T_max)`` it saw."""
+        _require_cuda(x, "Engine.forward_ragged")
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError(f"expected input of shape (B, {self.in_channels}, T), got {tuple(x.shape)}")
+        x = x.contiguous()
+        B, _, T = x.shape
+        lengths = [int(t) for t in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(lengths) != B:
+            raise ValueError(f"{len(lengths)} lengths for a batch of {B}")
+        if plan is None:
+            plan = self._ragged_last
+            if plan is None or not plan._h.value or plan.lengths != lengths or plan.t_max != T:
+                if plan is not None:
+                    plan.close()
+                plan = self._ragged_last = self.ragged_plan(lengths, T)
+        elif plan._engine is not self or plan.lengths != lengths or plan.t_max != T:
+            raise ValueError("Engine.forward_ragged: the plan was made for other lengths, another t_max or another engine")
+        L = T * plan.hop
+        if out is None:
+            out = torch.empty((B, self.out_channels, L), dtype=torch.float32, device=x.device)
+        elif tuple(out.shape) != (B, self.out_channels, L) or not out.is_contiguous():
+            raise ValueError(f"expected a contiguous out of shape {(B, self.out_channels, L)}, got {tuple(out.shape)}")
+        tptr = None
+        if template is not None:
+            _require_cuda(template, "Engine.forward_ragged template")
+            template = template.contiguous()
+            if tuple(template.shape) != (B, 1, L):
+                raise ValueError(f"expected template of shape {(B, 1, L)}, got {tuple(template.shape)}")
+            tptr = template.data_ptr()
+        with self._lock, torch.cuda.device(x.device):
+            plan._check_open()
+            cur, run = self._order_begin(x.device, eager=True)
+            check(self._lib.fv_ragged_forward(plan._h, x.data_ptr(), tptr, out.data_ptr(), plan._ws.data_ptr(), plan._ws.numel() * 4,
+                                              int(run.cuda_stream)))
+            self._order_end(cur, run)
+            if plan._done is None:
+                plan._done = torch.cuda.Event()
+            plan._done.record(run)
+        return out
+
+    def forward_list(self, mels, templates=None) -> list[torch.Tensor]:
+        """The convenience form: a list of ``(C_in, T_i)`` mels in, a list of ``(C_out, T_i * hop)`` views of one ``forward_ragged`` output
+        out (``templates``: a list of ``(1, T_i * hop)`` for a use_template generator)."""
+        mels = list(mels)
+        if not mels:
+            return []
+        lengths = [int(m.shape[-1]) for m in mels]
+        T = max(max(lengths), 1)
+        dev = mels[0].device
+        x = torch.zeros((len(mels), self.in_channels, T), dtype=torch.float32, device=dev)
+        for b, m in enumerate(mels):
+            x[b, :, :lengths[b]] = m
+        hop = self.output_length(1)
+        tt = None
+        if templates is not None:
+            tt = torch.zeros((len(mels), 1, T * hop), dtype=torch.float32, device=dev)
+            for b, t in enumerate(templates):
+                tt[b, :, :lengths[b] * hop] = t
+        y = self.forward_ragged(x, lengths, template=tt)
+        return [y[b, :, :lengths[b] * hop] for b in range(len(mels))]
+
     def _launch(self, x, tptr, nptr, out, B, T, stream: int) -> int:
         if nptr is not None:
             return self._lib.fv_forward_refinegan(self._h, x.data_ptr(), tptr, nptr, out.data_ptr(), B, T, self._ws.data_ptr(),
@@ -347,13 +421,13 @@ class Engine:
     def __call__(self, x, out=None, template=None, noise=None):
         return self.forward(x, out, template, noise)
 
-    def profile(self, x: torch.Tensor, repeats: int = 3) -> list[dict]:
+    def profile(self, x: torch.Tensor, repeats: int = 3, lengths=None) -> list[dict]:
         """Per-kernel hipEvent timings of `repeats` forwards (fv_profile_begin/end): a list of
-        {kernel, launches, total_ms, avg_ms, flops_per_launch, bytes_per_launch}."""
+        {kernel, launches, total_ms, avg_ms, flops_per_launch, bytes_per_launch}.  ``lengths``: of ``forward_ragged(x, lengths)`` instead."""
         import json
         check(self._lib.fv_profile_begin(self._h))
         for _ in range(repeats):
-            self.forward(x)
+            self.forward(x) if lengths is None else self.forward_ragged(x, lengths)
         torch.cuda.synchronize(x.device)
         need = ctypes.c_size_t(0)
         buf = ctypes.create_string_buffer(1 << 20)
@@ -478,6 +552,67 @@ class Stream:
             self._ws = None
 
     def __enter__(self) -> "Stream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RaggedPlan:
+    """The plan of one ragged batch on an ``Engine`` (``fv_ragged``, include/fishvoc.h): owns the device window table and the workspace of
+    ``Engine.forward_ragged`` for these ``lengths`` and ``t_max``.  ``windows`` / ``groups`` are what the library planned (the rule in plain
+    Python: ``vocoder_amd.ragged``).  A plan dies with its engine, like a ``Stream``."""
+
+    def __init__(self, engine: Engine, lengths, t_max: int | None = None, launch_frames: int = 0, max_groups: int = 0):
+        from .ragged import Window
+        self._engine = engine
+        self._lib = engine._lib
+        self._h = ctypes.c_void_p()
+        self._done: torch.cuda.Event | None = None
+        if not engine._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, "Engine.ragged_plan: the engine is closed")
+        self.lengths = [int(t) for t in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        self.t_max = int(max(self.lengths, default=0) if t_max is None else t_max)
+        arr = (ctypes.c_int32 * max(len(self.lengths), 1))(*self.lengths)
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_ragged_create(engine._h, arr, len(self.lengths), self.t_max, int(launch_frames), int(max_groups),
+                                             ctypes.byref(self._h)))
+            self._ws = torch.empty((int(self._lib.fv_ragged_workspace_bytes(self._h)) + 3) // 4 + 1, dtype=torch.float32, device=engine.device)
+        n = int(self._lib.fv_ragged_windows(self._h, None, 0))
+        buf = (_lib.RaggedWindow * max(n, 1))()
+        self._lib.fv_ragged_windows(self._h, buf, n)
+        self.windows = [Window(w.clip, w.start, w.frames, w.keep_lo, w.keep_hi, w.group) for w in buf[:n]]
+        self.groups = []
+        for g in range(int(self._lib.fv_ragged_num_groups(self._h))):
+            b, f = ctypes.c_int32(0), ctypes.c_int32(0)
+            check(self._lib.fv_ragged_group(self._h, g, ctypes.byref(b), ctypes.byref(f)))
+            self.groups.append((b.value, f.value))
+        self.hop = engine.output_length(1)
+
+    @property
+    def workspace_bytes(self) -> int:
+        self._check_open()
+        return int(self._lib.fv_ragged_workspace_bytes(self._h))
+
+    def _check_open(self) -> None:
+        if not self._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, "this ragged plan is closed (its engine was closed or rebuilt): create a new plan")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if self._done is not None:
+                self._done.synchronize()    # the table and the workspace may still be in use on the device
+            self._lib.fv_ragged_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._ws = None
+
+    def __enter__(self) -> "RaggedPlan":
         return self
 
     def __exit__(self, *exc) -> None:

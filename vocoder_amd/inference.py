@@ -170,6 +170,32 @@ def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int)
     return torch.cat(outs, dim=-1), first, lat
 
 
+def _main_batched(a, model, files, base) -> None:
+    """--batch-size N: the mel files N at a time, each batch (every mel of a file one utterance) through one ``forward_list`` call."""
+    if any(f.suffix == ".wav" for f in files):
+        raise ValueError("--batch-size takes mel inputs (.pt / .pth); run .wav inputs without it")
+    if not hasattr(model.generator, "forward_list"):
+        raise ValueError(f"--batch-size: {type(model.generator).__name__} has no forward_list()")
+    for i in range(0, len(files), a.batch_size):
+        chunk = files[i:i + a.batch_size]
+        mels, owner = [], []
+        for f in chunk:
+            mel = torch.load(f, map_location="cpu", weights_only=True)
+            if a.diffsinger:
+                mel = diffsinger_mel_to_ln(mel)
+            mel = prepare_mel(mel, model.num_mels).to(model.device)
+            mels.extend(mel[b] for b in range(mel.shape[0]))
+            owner.extend([f] * mel.shape[0])
+        t0 = time.time()
+        waves = model.generator.forward_list(mels)
+        torch.cuda.synchronize()
+        secs = sum(w.shape[-1] for w in waves) / model.sampling_rate
+        print(f"{len(chunk)} files ({chunk[0]} ...): {secs:.2f}s of audio in {time.time() - t0:.4f}s, one ragged forward")
+        for f in chunk:
+            fake = torch.stack([w for w, o in zip(waves, owner) if o is f])      # (B, 1, T): the items of one file share a length
+            write_wav(Path(a.output_path) / f.relative_to(base).with_suffix(".wav"), fake.squeeze(1).cpu().numpy().T, model.sampling_rate)
+
+
 @torch.no_grad()
 def main(argv=None):
     ap = argparse.ArgumentParser(description="mel (.pt) or audio (.wav) -> wav on the MI355X engine (mirrors fish_vocoder/test.py)")
@@ -187,14 +213,21 @@ def main(argv=None):
     ap.add_argument("--chunk-frames", type=int, default=None,
                     help="push each input through a stream, N mel frames at a time (same wav as the whole-utterance run, within 1 LSB); "
                          "prints the time to first audio and the per-chunk p50 latency")
+    ap.add_argument("--batch-size", type=int, default=None,
+                    help="take the mel (.pt / .pth) inputs N files at a time and run each batch of utterances, whatever their lengths, through "
+                         "ONE ragged forward (generator.forward_list); same wavs as the one-by-one run, within 1 LSB")
     a = ap.parse_args(argv)
     if a.chunk_frames is not None and a.chunk_frames < 1:
         ap.error("--chunk-frames must be >= 1")
+    if a.batch_size is not None and (a.batch_size < 1 or a.chunk_frames is not None):
+        ap.error("--batch-size must be >= 1 and cannot be combined with --chunk-frames")
     model = build_model(a.generator, a.resolution, {"num_mels": a.num_mels} if a.num_mels else None, a.config_root,
                         a.ckpt_path, trust_checkpoint=a.trust_checkpoint)
     inp = Path(a.input_path)
     files = [inp] if inp.is_file() else sorted(p for p in inp.rglob("*") if p.suffix in (".pt", ".pth", ".wav"))
     base = inp.parent if inp.is_file() else inp
+    if a.batch_size:
+        return _main_batched(a, model, files, base)
     for f in files:
         if f.suffix == ".wav":   # test.py:50-71: channels -> batch items, zero padding, mel_transforms.input
             y, sr = read_wav(f)

@@ -115,6 +115,25 @@ class EngineModule(nn.Module):
             raise RuntimeError(f"{type(self).__name__} is inference-only: call .eval() first")
         return self.engine(p.device).stream(batch, max_chunk_frames, **kw)
 
+    def _ragged_engine(self, what: str):
+        p = next(self.parameters(), None)
+        if p is None or not p.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.{what} needs the module on a HIP device (.to('cuda')); vocoder_amd has no CPU path")
+        if self.training:
+            raise RuntimeError(f"{type(self).__name__} is inference-only: call .eval() first")
+        return self.engine(p.device)
+
+    def forward_ragged(self, x: torch.Tensor, lengths, template: torch.Tensor | None = None) -> torch.Tensor:
+        """A padded batch ``(B, C_in, T_max)`` with ``lengths[b]`` valid frames per row in ONE call (``Engine.forward_ragged``): every clip's own
+        forward in ``[0, lengths[b] * hop)`` of its row, zeros after it; the padding of ``x`` is never read."""
+        with torch.no_grad():
+            return self._ragged_engine("forward_ragged").forward_ragged(x.to(torch.float32), lengths, template=template)
+
+    def forward_list(self, mels, templates=None) -> list:
+        """A list of ``(C_in, T_i)`` mels -> a list of ``(C_out, T_i * hop)`` waveforms through one ``forward_ragged`` call."""
+        with torch.no_grad():
+            return self._ragged_engine("forward_list").forward_list(mels, templates)
+
     def remove_parametrizations(self):
         """Kept for API compatibility (hifigan.py:251).  Weight-norm is folded inside the engine at load time, so this
         is a no-op; unlike the reference's version (which raises TypeError) it is harmless."""

@@ -29,6 +29,11 @@ def shard_sizes(batch: int, world_size: int) -> list[int]:
     return [shard_slice(batch, world_size, r).stop - shard_slice(batch, world_size, r).start for r in range(world_size)]
 
 
+def shard_lengths(lengths, world_size: int, rank: int) -> list[int]:
+    """The ``lengths`` of this rank's clips (``shard_slice``): what it passes to ``forward_ragged`` beside its slice of the padded batch."""
+    return [int(t) for t in lengths[shard_slice(len(lengths), world_size, rank)]]
+
+
 def broadcast_state_dict(state_dict: dict | None, src: int = 0, device=None) -> dict:
     """Rank ``src`` passes its (numpy or tensor) state dict; every rank returns an identical dict of CPU tensors.
     Keys/shapes travel as an object list, payload as ONE flat fp32 buffer (a single large collective, not 291 small
