@@ -1229,9 +1229,9 @@ def test_ragged_shards_against_the_global_batch_and_the_batch_invariant_switch()
     eng.close()
 
 
-# ---- long clips: time tiles with halo recompute, run as a batch (engine.hip run_model; SURVEY §5 long-context row, VERDICT r4 missing 3) ----
+# ---- long clips: time tiles with halo recompute, run as a batch (engine_windows.hip run_model; SURVEY §5 long-context row, VERDICT r4 missing 3) ----
 def _tile_layout(T, L, halo):
-    """The engine's plan (engine.hip TilePlan): n tiles of L frames, regular starts i * (L - 2 halo), the last pulled back to end at T;
+    """The engine's plan (engine_internal.h TilePlan, engine_windows.hip tile_plan): n tiles of L frames, regular starts i * (L - 2 halo), the last pulled back to end at T;
     tile i contributes the frames [lo_i, hi_i)."""
     stride = L - 2 * halo
     n = max(2, -(-(T - 2 * halo) // stride))
@@ -1376,7 +1376,7 @@ def test_thirty_minute_clip_runs_as_time_tiles_bit_identical_to_a_run_of_one_til
     assert y.shape == (1, 1, T * 512)
     assert bool(torch.isfinite(y).all()) and float(y.abs().max()) <= 1.0
     L = 65536
-    halo = 17   # the plan: 2^29 / 8192 = 65 536 frames per tile; halo = the engine's reach bound (15 + 2 frames for V1: engine.hip ups_reach)
+    halo = 17   # the plan: 2^29 / 8192 = 65 536 frames per tile; halo = the engine's reach bound (15 + 2 frames for V1: engine_windows.hip ups_reach)
     start, lo, hi = _tile_layout(T, L, halo)
     assert len(start) == 3
     i = 1
@@ -1481,7 +1481,7 @@ def test_graft_entry_build_then_smoke_in_one_process():
 
 
 def test_engine_built_on_all_host_cores_equals_the_serial_build(monkeypatch):
-    """fv_finalize folds / packs / uploads the layers on the host's cores (engine.hip run_jobs; LOG R6.3: the one-shot caller of test.py:31-38 waits for
+    """fv_finalize folds / packs / uploads the layers on the host's cores (engine_build.hip run_jobs; LOG R6.3: the one-shot caller of test.py:31-38 waits for
     engine creation).  A layer's weight-norm fold (hifigan.py:94-100, folded in double) and its fragment forms are one thread's work either way, so the
     engine built with FV_BUILD_THREADS=1 — the serial path — must give the same waveform bit for bit, for the three generator families."""
     from vocoder_amd import _lib

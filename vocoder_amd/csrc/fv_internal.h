@@ -363,7 +363,7 @@ fv_status launch_polyphase_reflect(const float* wave, float* yp, int B, int L, i
 fv_status launch_magnitude(const float* spec, float* mag, int B, int nb, int T, hipStream_t s);
 
 // ISTFT head glue: h (B, 2*n_fft, T) rows [0,nb) = log-mag, [n_fft, n_fft+nb) = phase -> spec (B, 2*nbp, T):
-// long clips as a batch of equal-length time tiles (engine.hip run_model); hop: frames -> samples of the tensor being moved
+// long clips as a batch of equal-length time tiles (engine_windows.hip run_model); hop: frames -> samples of the tensor being moved
 fv_status launch_gather_tiles(const float* x, float* tiles, int B, int C, int T, int n, int L, int stride, int hop, hipStream_t s);
 fv_status launch_scatter_tiles(const float* tiles, float* y, int B, int C, int T, int n, int L, int stride, int halo, int hop, hipStream_t s);
 // streaming synthesis (fv_stream_push): chunk -> ring + window; the emitted samples of the window's output -> the caller's buffer
