@@ -1,7 +1,7 @@
 """CPU: the arithmetic conv_wino_impl.h and conv_wino4_impl.h implement, restated in numpy (float64) against the oracle's direct conv — Winograd
 F(2,3) tap groups {0,1,2}, {4,5,6}, {8,9,10} on the dilated pair lattice plus the single taps 3, 7 folded into accumulators m0 / m3, and F(4,3)
 groups on the quad lattice split over two plane halves, each with the virtual-tap order, plane offsets and weight transform of the kernel /
-conv_layer_create.  Exact in real arithmetic: float64 agrees to ~1e-11, so an indexing or sign error in the scheme cannot hide behind a tolerance."""
+conv_pack.hip (wino_taps, wino4_rows).  Exact in real arithmetic: float64 agrees to ~1e-11, so an indexing or sign error in the scheme cannot hide behind a tolerance."""
 import numpy as np
 import pytest
 
@@ -18,7 +18,7 @@ def virtual_taps(k):
 
 
 def transformed_weights(w, k):
-    """(C_out, C_in, NV): what conv_layer_create packs for the kernel."""
+    """(C_out, C_in, NV): what wino_taps (conv_pack.hip) packs for the kernel."""
     out = []
     for (_, _, _, src) in virtual_taps(k):
         if src[0] == "g":

@@ -40,7 +40,7 @@ for C, T in ((256, 688), (128, 5504), (64, 11008)):
             x = torch.randn(32, C, T, device="cuda"); r = torch.randn(32, C, T, device="cuda"); y = torch.empty_like(x)
             cells = []
             for fi, (name, env) in enumerate(FORMS):
-                setenv(env)   # (before the layers are created: a layer packs only the Winograd form its knobs select — conv_layer.hip)
+                setenv(env)   # (before the layers are created: a layer packs only the Winograd form its knobs select — layer_forms(), conv_layer.hip)
                 conv = FusedConv(w, b, padding=pad, dilation=d, pre_act=_lib.FV_ACT_SILU).set_algorithm("winograd")
                 conv_na = FusedConv(w, b, padding=pad, dilation=d).set_algorithm("winograd")   # c2 of a pair: no activation in front
                 ys = torch.empty(2, C, 333, device="cuda")

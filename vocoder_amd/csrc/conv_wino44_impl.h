@@ -8,7 +8,7 @@
 //   E_a = x4 + c1 x2 + c0 x0,  O_a = x5 + c1 x3 + c0 x1,   V(±a) = O_a ± a E_a     (c0, c1) = (4, -5), (1, -17/4), (1/4, -5/4) for a = 1/2, 1, 2
 //   V(∞) = (x6 - x0) + 21/4 (x2 - x4)                                                          21 FMA-class instructions per lattice element
 // transformed weights (host, double): U(±a) = f_a (g0 ± a g1 + a² g2 ± a³ g3), f = 32/45, -2/9, 1/45 (the -a rows: -f for a = 1/2, 1 ... see
-// conv_layer.hip), U(∞) = g3; outputs y_j = sum_a a^j m(+a) + (-a)^j m(-a)  (+ m(∞) for j = 3).
+// G44 in conv_pack.hip), U(∞) = g3; outputs y_j = sum_a a^j m(+a) + (-a)^j m(-a)  (+ m(∞) for j = 3).
 // U(∞) = g3 is ZERO for the last group of both kernel sizes (taps 11 / 7 do not exist): the ∞ plane costs NG - 1 products, 20 / 13 per quad in all.
 // Accuracy (tools/experiments/winograd_f44_precision.py): per layer 1.3 - 1.8e-6 of full scale against 1.3 - 1.5e-6 for F(4,3) — symmetric points
 // with |a| <= 2 keep the transform constants <= 8; the set 0, ±1, ±2, 3 would cost 5 x that.

@@ -8,7 +8,7 @@
 // Tap groups {0,1,2}, {4,5,6}, {8,9,10} (group g reads column n + g D); interpolation points 0, ±1, ±2, ∞ (Lavin & Gray 2016):
 //   V0 = 4 x0 - 5 x2 + x4          V1 = (x4 - 4 x2) + (x3 - 4 x1)     V2 = (x4 - 4 x2) - (x3 - 4 x1)
 //   V3 = (x4 - x2) + 2 (x3 - x1)   V4 = (x4 - x2) - 2 (x3 - x1)       V5 = 4 x1 - 5 x3 + x5          (x4 = X0[n + D], x5 = X1[n + D])
-// transformed weights (host, in double, conv_layer.hip):  g0/4, -(g0+g1+g2)/6, -(g0-g1+g2)/6, g0/24+g1/12+g2/6, g0/24-g1/12+g2/6, g2
+// transformed weights (host, in double, conv_pack.hip: wino4_rows):  g0/4, -(g0+g1+g2)/6, -(g0-g1+g2)/6, g0/24+g1/12+g2/6, g0/24-g1/12+g2/6, g2
 // six accumulator planes m_p += U_p V_p and
 //   y[t0] = m0+m1+m2+m3+m4    y[t0+D] = (m1-m2) + 2 (m3-m4)    y[t0+2D] = (m1+m2) + 4 (m3+m4)    y[t0+3D] = (m1-m2) + 8 (m3-m4) + m5.
 // The taps between the groups (3, 7) are plain products: m0 only reaches y[t0] and m5 only y[t0+3D], so the first and fourth output take

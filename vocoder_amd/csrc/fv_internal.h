@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "conv_pack.h"
 #include "fishvoc.h"
 
 namespace fv {
@@ -31,7 +32,7 @@ struct Knobs {
     int wino_cfg = -1;    // FV_WINO_CFG: forced tile (WinoCfg 0 ... 2), -1 = by shape
     int wino_min_blocks = -1;   // FV_WINO_MIN_BLOCKS: fewest workgroups of a launch that takes it, -1 = default
     int vec_store = 1;    // FV_VEC_STORE: 0 = the stride-8 upsamplers store single floats instead of 16-byte output quads (A/B runs, tests)
-    // (FV_WINO4 / FV_WINO44 are also read when a layer is CREATED: it packs only the Winograd form they select — conv_layer.hip)
+    // (FV_WINO4 / FV_WINO44 are also read when a layer is CREATED: it packs only the Winograd form they select — layer_forms() in conv_layer.hip)
     int pair_wino44 = 1;  // FV_PAIR_WINO44: 1 = the fused narrow pairs at k = 7 / 11 on F(4,4) tap groups (pair_wino44_impl.h), 0 = F(2,3) (pair_wino_impl.h)
     int wino44 = 1;       // FV_WINO44: 1 = F(4,4) tap groups (conv_wino44_impl.h) for k = 7 / 11 where FV_WINO4 would take F(4,3), 0 = F(4,3) there
     int wino44_rows = 0;  // FV_WINO44_ROWS: 64 = one 32-row tile per wave (64-row workgroups) everywhere; otherwise two (128 rows) where the layer has whole 128-row blocks
@@ -61,6 +62,8 @@ struct AlgoScope {
 };
 int cur_algo();          // fv_conv_algo
 bool cur_invariant();    // kernel choices from the layer shape alone
+// fv_set_conv_algorithm of the running call, with the process-wide FV_WINO knob as the default behind FV_CONV_ALGO_AUTO
+int effective_algo();
 
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}).  Register-resident operand
 // rings need every index to be a constant expression in the source (an index that only becomes constant after loop unrolling
@@ -118,15 +121,13 @@ bool dynamic_lds_refused();
 // ConvTranspose1d:  polyphase form.  m = (c_out, r) with r = output phase in [0, stride), n = q, ks' = ceil(k/stride),
 //                   dil = 1, pad_l = ks'-1, and the result lands at t = q*stride + r - padding (scatter store).
 // ---------------------------------------------------------------------------------------------
-constexpr int kChunk = 8;  // input channels staged per LDS chunk (= 4 MFMA k-steps of 2 per tap)
-
 enum OutMode : int { OUT_SET = 0, OUT_ACCUM = 1 };  // OUT_ACCUM: y = (y_old + v) * out_scale  (MRF stack-mean)
 
 struct ConvParams {
     const float* x;      // (B, Cin, Tin)
     const float* x2;     // SUM3 kernels: the input is ((x + x2) + x3) / 3 — the stack-mean of three ResBlock branches formed while
     const float* x3;     //   staging (same layout as x); NULL otherwise
-    const float4* wp;    // packed weights, see pack_conv_weights()
+    const float4* wp;    // packed weights, see pack_conv_weights() (conv_pack.hip)
     const float* bias;   // (m_pad) zero padded, never NULL
     float* y;
     const float* res;    // residual, same indexing as y (may be NULL, may alias y)
@@ -156,7 +157,7 @@ struct ConvParams {
     long long* dbg_ts;   // experiment: per-workgroup phase time stamps (split-K kernel / tiled conv kernel)
 #endif
     // f16x3 precision mode (conv_f16x3_impl.h)
-    const void* wph;     // split fp16 weight planes, see pack_conv_weights_f16x3()
+    const void* wph;     // split fp16 weight planes, see pack_conv_weights_f16x3() (conv_pack.hip)
     int nch16;           // 16-channel chunks in the packed planes
     int nch16_real;      // ceil(Cin / 16)
 };
@@ -186,6 +187,12 @@ struct ConvLayer {
     int algo = FV_CONV_ALGO_AUTO;       // fv_conv_set_algorithm (single layers; an engine's layers follow the engine's setting)
     float* d_bias = nullptr;   // m_pad values, followed by their negatives (m_pad more)
     size_t wp_bytes = 0;
+
+    // every device allocation of the layer, in one place: conv_layer_destroy walks this list (a buffer added above is added here too)
+    template <class F>
+    void for_each_buffer(F&& f) {
+        f(d_wp), f(d_bias), f(d_wp16), f(d_wpw), f(d_wpw16), f(d_wpq16), f(d_wpw44), f(d_wpw4), f(d_wpwl), f(d_wph), f(d_wph16);
+    }
 
     int64_t out_len(int t_in) const {
         return transposed ? (int64_t)(t_in - 1) * stride - 2 * padding + k

@@ -13,7 +13,7 @@
 //     i.e. 32 consecutive floats of two consecutive K rows — already a coalesced access to X.  With an even T a lane loads
 //     the column PAIR (2c, 2c + 1) with one 8-byte buffer load and feeds two n-tiles (tile e holds columns 2c + e; the
 //     epilogue stores the pairs back as 8-byte stores), so a k-step costs NT / 2 vector-memory instructions per wave.
-//   A (weights): the packed fragment-order layout of conv_layer.hip, one 16-byte buffer load per m-tile per 4 k-steps.
+//   A (weights): the packed fragment-order layout of pack_conv_weights() (conv_pack.hip), one 16-byte buffer load per m-tile per 4 k-steps.
 //   Both operands run PD chunks (of 8 channels = 4 k-steps) ahead in a static register ring (the K loop is unrolled by
 //   the ring length, so there are no register moves); addresses live in SGPRs (descriptor base + scalar offset) plus one
 //   constant VGPR per load stream: the main loop has no VALU instruction at all — on gfx950 fp32 VALU work and fp32 MFMA
@@ -30,7 +30,7 @@ namespace fv {
 // rows x 64 columns, ordered rows-fastest inside a 64-column block, and dealt out round by round (wave g takes tiles g,
 // g + waves, ...; the blocks of one XCD are neighbours in that order, so a round's column blocks are read once per XCD and
 // the weights stay in every L2).  The host picks (MT, W) per layer so that the fullest SIMD is close to the average
-// (conv_layer.hip).
+// (choose_gemm_pw(), conv_layer.hip).
 // A wave requests the first chunks of its NEXT tile before it runs the epilogue of the current one (XPF), and spreads the
 // loads of the chunk PD ahead between the MFMAs of the current chunk.
 template <int MT, int PD, bool PAIR, int W, bool XPF, bool STAGGER, int EB>
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256, W) void gemm_pw_persist_kernel(const ConvParam
     const __amdgpu_buffer_rsrc_t yrs = uniform_rsrc(p.y, y_bytes);
     const __amdgpu_buffer_rsrc_t rrs = uniform_rsrc(p.res ? p.res : p.y, y_bytes);
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t brs = uniform_rsrc(p.bias, (unsigned)((p.M + 127) / 128 * 128 * 4));   // zero padded to 128 rows (conv_layer.hip)
+    const __amdgpu_buffer_rsrc_t brs = uniform_rsrc(p.bias, (unsigned)((p.M + 127) / 128 * 128 * 4));   // zero padded to 128 rows (conv_layer_create)
     const __amdgpu_buffer_rsrc_t grs = uniform_rsrc(p.gamma ? p.gamma : p.bias, (unsigned)(p.M * 4));
     const int wvoff = lane * 16;
     const int row2_b = __builtin_amdgcn_readfirstlane(2 * p.Tin * 4);

@@ -1,4 +1,4 @@
-// Launch parameters of the fused f16x3 (c1, c2) pair kernel, shared by the host dispatch (conv_layer.hip) and the kernel TUs.
+// Launch parameters of the fused f16x3 (c1, c2) pair kernel, shared by the host dispatch (conv_pair.hip) and the kernel TUs.
 #pragma once
 
 #include "fv_internal.h"
@@ -12,7 +12,7 @@ constexpr int kPairF16ColsC32 = 4 * kPairF16NtC32 * 32;
 struct PairF16Params {
     const float* x;        // (B, C, T)
     float* y;              // (B, C, T), must not alias x
-    const void* w1h;       // c1 / c2 split weight planes (pack_conv_weights_f16x3 layout)
+    const void* w1h;       // c1 / c2 split weight planes (pack_conv_weights_f16x3 layout, conv_pack.hip)
     const void* w2h;
     const float* b1;
     const float* b2;

@@ -306,7 +306,7 @@ __device__ __forceinline__ void pw_gemm_k3(f32x4w (&acc)[4][G::MT], const float*
 #pragma unroll
         for (int m = 0; m < 4 * KST * MT; ++m) {
             const int v = m % 4, mt = (m / 4) % MT, ks = m / (4 * MT);
-            const int comp = MT == 2 ? 2 * ks + mt : ks;          // (the fragment layouts of conv_layer.hip: C = 16 .[s], C = 32 .[2 s + mt])
+            const int comp = MT == 2 ? 2 * ks + mt : ks;          // (the fragment layouts of pack_pair_wino16(), conv_pack.hip: C = 16 .[s], C = 32 .[2 s + mt])
             const float4 a4 = wq[cur][v];
             float apin = comp == 0 ? a4.x : comp == 1 ? a4.y : comp == 2 ? a4.z : a4.w;
             asm volatile("" : "+v"(apin));                        // (pins the MFMA in program order: pw_gemm_chunk)
