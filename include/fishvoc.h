@@ -384,6 +384,91 @@ FV_API fv_status fv_ragged_forward(fv_ragged* p, const float* d_in, const float*
                                    size_t workspace_bytes, void* stream);
 FV_API void fv_ragged_destroy(fv_ragged* p);
 
+/* -------- session pool: streaming sessions that advance independently.  No reference counterpart: the reference has no streaming and no
+ *          server loop (test.py:52-99 runs whole files one by one); this replaces one fv_stream of batch 1, and one launch-bound forward,
+ *          per live utterance.  --------
+ *
+ * A pool holds `sessions` slots.  Each slot has its own host counters F (frames received) and E (frames emitted), its own `flushed` flag
+ * and its own ring row; K, A, R and the eligible models are the stream's (above).  One fv_pool_step serves any subset of the slots: item i
+ * names a session, gives it n >= 0 frames and says whether the utterance ends with them (flush; n > 0 with flush is a last chunk).
+ * Per item the counters move as a stream's: F' = F + n; E' = F' on a flush, else max(E, F' - A); w = max(0, E - K).  An item with E' > E is a
+ * ROW: its window is the frames [w, F'), W = F' - w <= K + A + max_chunk_frames, it emits the frames [E, E').  A row owns its left edge iff
+ * w = 0 and its right edge iff it flushes.
+ * The plan.  Wg = the largest W over the rows.  Group 0 holds every row except those that own both edges and have W < Wg, as ONE
+ * (rows, C_in, Wg) forward: a row that owns its left edge starts at column col0 = 0, any other row at col0 = Wg - W (right-aligned), and
+ * every other column of the row is zero.  An emitted frame lies >= K frames inside a left edge the row does not own and >= A frames inside
+ * such a right edge, so with K, A >= R it does not matter whether the tensor edge, zeros or other data lies beyond (the rule of the time
+ * tiles, the streams and the ragged batches).  The rows left out are whole short utterances (a single window that owns both edges): they
+ * form further groups by exact W, in descending W, at col0 = 0.  Rows within a group keep item order; rows are listed by group.
+ *   - each row's samples are bit-identical to the same slice of fv_forward over its group's tensor by the same engine;
+ *   - items in lockstep from equal state plan to one group with every col0 = 0: each step is bit-identical to fv_stream_push / _flush at
+ *     batch = the number of items;
+ *   - K >= R and A >= R: a session's concatenated output has the whole utterance's shape and is within 2e-5 * max(1, peak) of fv_forward
+ *     on that utterance alone, whatever the other sessions do;
+ *   - nothing in the chunk buffer's columns >= n of an item (NaN included), and nothing of another session, reaches any output bit;
+ *   - every sample of d_out is written: past an item's emitted samples, and in the rows of items that emit nothing, exactly 0.0f.
+ * vocoder_amd/sessions.py states the same plan in Python. */
+typedef struct fv_pool_config {
+    int32_t sessions;          /* slots (S) */
+    int32_t max_chunk_frames;  /* largest n of one item */
+    int32_t context_frames;    /* K; -1 = R (fv_pool_plan has no engine: >= 0 there) */
+    int32_t lookahead_frames;  /* A; -1 = R (likewise) */
+} fv_pool_config;
+
+typedef struct fv_pool_item {
+    int32_t session;           /* slot in [0, S); at most once per step */
+    int32_t frames;            /* n in [0, max_chunk_frames] */
+    int32_t flush;             /* 1: the utterance ends with these frames */
+} fv_pool_item;
+
+typedef struct fv_pool_row {
+    int32_t item;              /* index into the step's items */
+    int32_t group;             /* forward that runs it; group 0 is the aligned one */
+    int32_t col0;              /* first column of the window inside the group's tensor */
+    int32_t frames;            /* W */
+    int64_t w;                 /* the window is the utterance's frames [w, w + W) */
+    int64_t emit_lo, emit_hi;  /* the frames [E, E') the step emits: samples [(col0 + E - w) hop, (col0 + E' - w) hop) of the row's output */
+} fv_pool_row;
+
+/* Pure host: needs no device and no engine.  received / emitted / flushed: the S counters and flags (flushed may be NULL: none is).  Writes
+ * the plan's rows to rows (up to row_cap; NULL when 0) and, per group, its number of rows and its length in frames to group_rows /
+ * group_frames (up to group_cap; NULL when 0), the number of groups to *num_groups (may be NULL), and returns the number of rows — a plan
+ * has at most `count` rows and `count` groups.  Nothing is changed: the caller moves the counters.  Refusals, each named in fv_last_error:
+ * a session outside [0, S), a duplicate session, frames outside [0, max_chunk_frames], in_frames < the largest n, out_frames < the largest
+ * E' - E (either may be -1: not checked), K or A < 0 (FV_ERR_INVALID); an item for a flushed session (FV_ERR_STATE). */
+FV_API int32_t fv_pool_plan(const fv_pool_config* cfg, const int64_t* received, const int64_t* emitted, const int32_t* flushed,
+                            const fv_pool_item* items, int32_t count, int32_t in_frames, int32_t out_frames, fv_pool_row* rows,
+                            int32_t row_cap, int32_t* group_rows, int32_t* group_frames, int32_t group_cap, int32_t* num_groups);
+
+typedef struct fv_pool fv_pool;
+
+/* The pool's only device allocation, made here on the current HIP device and freed by fv_pool_destroy: one ring row per slot,
+ * (S, C_in, cap) with cap = K + A + max_chunk_frames, plus (S, 1, cap * hop) for the pitch template of a use_template generator.  Models
+ * that cannot stream get FV_ERR_UNSUPPORTED, with the reason in fv_last_error (as fv_stream_create). */
+FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool** out);
+/* Bytes of device scratch every step needs (256-byte aligned): a group's input, template and output for S rows of cap frames, and the
+ * forward's own workspace for the largest window at batch S. */
+FV_API size_t fv_pool_workspace_bytes(const fv_pool* p);
+/* F - E of one slot: frames received but not yet emitted (0 for a session outside [0, S)). */
+FV_API int64_t fv_pool_pending_frames(const fv_pool* p, int32_t session);
+/* One step.  d_chunks: (count, C_in, in_frames) fp32, row i holding item i's n frames first (the rest is never loaded; NULL when no item
+ * has frames); d_templates: (count, 1, in_frames * hop) for a use_template generator, NULL otherwise; d_out: (count, C_out, out_frames *
+ * hop), row i receiving item i's emitted samples first and 0.0f after them (NULL when out_frames is 0); frames_out (may be NULL): count
+ * entries, E' - E of every item.  The whole step is checked before any counter moves or anything is enqueued — the refusals of
+ * fv_pool_plan, a missing or unexpected template, a missing chunk buffer, a workspace below fv_pool_workspace_bytes (FV_ERR_INVALID) —
+ * and a refused step leaves every counter and every ring as it was.  Per group, on `stream`: one gather launch (chunk -> ring, ring +
+ * chunk -> the group's tensor), the unchanged forward, one crop launch.  Group 0 runs at fixed workspace addresses through the graph
+ * bookkeeping of fv_forward: a steady state with the same rows and the same Wg replays its captured graph; further groups are enqueued
+ * eagerly.  The step's row table travels in the kernel arguments: no device allocation, no copy, no host synchronisation.  Asynchronous;
+ * ordered like fv_forward on its engine. */
+FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const float* d_chunks, const float* d_templates,
+                              int32_t in_frames, float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace,
+                              size_t workspace_bytes, void* stream);
+/* F = E = 0 and not flushed for one slot: the next utterance; the ring is kept.  A session outside [0, S): FV_ERR_INVALID. */
+FV_API fv_status fv_pool_reset(fv_pool* p, int32_t session);
+/* Frees the rings (call it before fv_destroy of its engine, once the pool's work has finished). */
+FV_API void fv_pool_destroy(fv_pool* p);
+
 /* -------- single fused conv layer (the hot kernel on its own; used by the parity tests and the roofline
  *          bench).  Stands in for one weight-normed nn.Conv1d / nn.ConvTranspose1d call plus the elementwise
  *          ops the reference runs around it (F.silu before, residual add after: hifigan.py:101-108). -------- */

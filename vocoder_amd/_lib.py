@@ -42,6 +42,7 @@ EXPORTS = (
     "fv_stream_reset", "fv_stream_destroy",
     "fv_ragged_plan", "fv_ragged_create", "fv_ragged_workspace_bytes", "fv_ragged_num_groups", "fv_ragged_group", "fv_ragged_windows",
     "fv_ragged_forward", "fv_ragged_destroy",
+    "fv_pool_plan", "fv_pool_create", "fv_pool_workspace_bytes", "fv_pool_pending_frames", "fv_pool_step", "fv_pool_reset", "fv_pool_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -96,6 +97,19 @@ class StreamConfig(ctypes.Structure):
 
 class RaggedWindow(ctypes.Structure):
     _fields_ = [("clip", _i32), ("start", _i32), ("frames", _i32), ("keep_lo", _i32), ("keep_hi", _i32), ("group", _i32)]
+
+
+class PoolConfig(ctypes.Structure):
+    _fields_ = [("sessions", _i32), ("max_chunk_frames", _i32), ("context_frames", _i32), ("lookahead_frames", _i32)]
+
+
+class PoolItem(ctypes.Structure):
+    _fields_ = [("session", _i32), ("frames", _i32), ("flush", _i32)]
+
+
+class PoolRow(ctypes.Structure):
+    _fields_ = [("item", _i32), ("group", _i32), ("col0", _i32), ("frames", _i32), ("w", ctypes.c_int64), ("emit_lo", ctypes.c_int64),
+                ("emit_hi", ctypes.c_int64)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -213,6 +227,21 @@ def lib() -> ctypes.CDLL:
     L.fv_ragged_forward.restype = _i32
     L.fv_ragged_destroy.argtypes = [vp]
     L.fv_ragged_destroy.restype = None
+    pip, prp = ctypes.POINTER(PoolItem), ctypes.POINTER(PoolRow)
+    L.fv_pool_plan.argtypes = [ctypes.POINTER(PoolConfig), i64p, i64p, i32p, pip, _i32, _i32, _i32, prp, _i32, i32p, i32p, _i32, i32p]
+    L.fv_pool_plan.restype = _i32
+    L.fv_pool_create.argtypes = [vp, ctypes.POINTER(PoolConfig), ctypes.POINTER(vp)]
+    L.fv_pool_create.restype = _i32
+    L.fv_pool_workspace_bytes.argtypes = [vp]
+    L.fv_pool_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_pool_pending_frames.argtypes = [vp, _i32]
+    L.fv_pool_pending_frames.restype = ctypes.c_int64
+    L.fv_pool_step.argtypes = [vp, pip, _i32, vp, vp, _i32, vp, _i32, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_pool_step.restype = _i32
+    L.fv_pool_reset.argtypes = [vp, _i32]
+    L.fv_pool_reset.restype = _i32
+    L.fv_pool_destroy.argtypes = [vp]
+    L.fv_pool_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

@@ -588,3 +588,319 @@ FV_API fv_status fv_ragged_forward(fv_ragged* p, const float* d_in, const float*
 FV_API void fv_ragged_destroy(fv_ragged* p) { delete p; }
 
 }  // extern "C"
+
+// ---- session pool: streaming sessions that advance independently ---------------------------------------------------------
+// The plan (include/fishvoc.h states it; vocoder_amd/sessions.py restates it in Python, and the tests compare the two row for row).  Per
+// item the counters move as stream_step moves them; the rows are then placed in groups: group 0 aligns every row against the tensor edge it
+// owns, the whole short utterances that would not fill it run in groups of their own length.
+struct PoolPlan {
+    std::vector<fv_pool_row> rows;               // by group, then by item
+    std::vector<int32_t> group_rows, group_frames;
+    std::vector<int64_t> F2, E2;                 // per item: the session's counters after the step
+    std::vector<char> seen;                      // per session (scratch of the duplicate check)
+    std::vector<fv_pool_row> cand;               // scratch: the rows in item order
+};
+
+static fv_status pool_plan(const char* fn, int S, int max_chunk, int K, int A, const int64_t* F, const int64_t* E, const int32_t* flushed,
+                           const fv_pool_item* items, int count, int in_frames, int out_frames, PoolPlan& p) {
+    p.rows.clear();
+    p.group_rows.clear();
+    p.group_frames.clear();
+    p.cand.clear();
+    if (S < 1 || max_chunk < 1 || K < 0 || A < 0 || (int64_t)K + A + max_chunk > (1 << 20)) {
+        set_error("%s: sessions (%d) and max_chunk_frames (%d) must be >= 1, context_frames (%d) and lookahead_frames (%d) >= 0, and their "
+                  "sum with max_chunk_frames at most 2^20", fn, S, max_chunk, K, A);
+        return FV_ERR_INVALID;
+    }
+    if (count < 0 || !F || !E || (count > 0 && !items)) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    p.seen.assign((size_t)S, 0);
+    p.F2.assign((size_t)count, 0);
+    p.E2.assign((size_t)count, 0);
+    int max_n = 0;
+    int64_t max_emit = 0, Wg = 0;
+    for (int i = 0; i < count; ++i) {
+        const fv_pool_item& it = items[i];
+        if (it.session < 0 || it.session >= S) {
+            set_error("%s: item %d names session %d, outside [0, %d)", fn, i, it.session, S);
+            return FV_ERR_INVALID;
+        }
+        if (p.seen[(size_t)it.session]) {
+            set_error("%s: duplicate session %d (item %d): a session appears at most once per step", fn, it.session, i);
+            return FV_ERR_INVALID;
+        }
+        p.seen[(size_t)it.session] = 1;
+        if (it.frames < 0 || it.frames > max_chunk) {
+            set_error("%s: item %d has %d frames, outside [0, max_chunk_frames = %d]", fn, i, it.frames, max_chunk);
+            return FV_ERR_INVALID;
+        }
+        const int64_t f = F[it.session], e = E[it.session];
+        if (f < 0 || e < 0 || e > f) {
+            set_error("%s: invalid counters of session %d (F = %lld, E = %lld)", fn, it.session, (long long)f, (long long)e);
+            return FV_ERR_INVALID;
+        }
+        if (flushed && flushed[it.session]) {
+            set_error("%s: session %d was flushed (item %d); fv_pool_reset it before the next utterance", fn, it.session, i);
+            return FV_ERR_STATE;
+        }
+        const int64_t f2 = f + it.frames, e2 = it.flush ? f2 : std::max(e, f2 - A);
+        p.F2[(size_t)i] = f2;
+        p.E2[(size_t)i] = e2;
+        max_n = std::max(max_n, it.frames);
+        max_emit = std::max(max_emit, e2 - e);
+        if (e2 > e) {
+            const int64_t w = std::max<int64_t>(0, e - K);
+            p.cand.push_back({i, 0, 0, (int32_t)(f2 - w), w, e, e2});
+            Wg = std::max(Wg, f2 - w);
+        }
+    }
+    if (in_frames >= 0 && in_frames < max_n) {
+        set_error("%s: in_frames = %d, but an item of this step has %d frames", fn, in_frames, max_n);
+        return FV_ERR_INVALID;
+    }
+    if (out_frames >= 0 && out_frames < max_emit) {
+        set_error("%s: out_frames = %d, but an item of this step emits %lld frames", fn, out_frames, (long long)max_emit);
+        return FV_ERR_INVALID;
+    }
+    if (p.cand.empty()) return FV_OK;
+    // group 0: every row but the whole utterances shorter than Wg; a row that does not own its left edge is right-aligned
+    auto whole_short = [&](const fv_pool_row& r) { return r.w == 0 && items[r.item].flush && r.frames < Wg; };
+    for (fv_pool_row r : p.cand)
+        if (!whole_short(r)) {
+            r.col0 = r.w == 0 ? 0 : (int32_t)(Wg - r.frames);
+            p.rows.push_back(r);
+        }
+    p.group_rows.push_back((int32_t)p.rows.size());
+    p.group_frames.push_back((int32_t)Wg);
+    // the rest by exact length, descending; item order within a length
+    const size_t first_short = p.rows.size();
+    for (const fv_pool_row& r : p.cand)
+        if (whole_short(r)) p.rows.push_back(r);
+    std::stable_sort(p.rows.begin() + (ptrdiff_t)first_short, p.rows.end(),
+                     [](const fv_pool_row& a, const fv_pool_row& b) { return a.frames > b.frames; });
+    for (size_t i = first_short; i < p.rows.size(); ++i) {
+        if (i == first_short || p.rows[i].frames != p.rows[i - 1].frames) {
+            p.group_rows.push_back(0);
+            p.group_frames.push_back(p.rows[i].frames);
+        }
+        p.rows[i].group = (int32_t)p.group_rows.size() - 1;
+        p.group_rows.back()++;
+    }
+    return FV_OK;
+}
+
+struct fv_pool {
+    fv_engine* e = nullptr;
+    int S = 0, max_chunk = 0, K = 0, A = 0, cin = 0, cout = 0, hop = 0;
+    int64_t cap = 0;              // ring length in frames: K + A + max_chunk, >= every window a session forms
+    bool tmpl = false;
+    float* ring = nullptr;        // (S, C_in, cap), then (S, 1, cap * hop) for the template: the pool's only device allocation
+    float* ring_tmpl = nullptr;
+    WindowWorkspace ws;           // sized for S x cap frames, and the forward's own workspace for the largest window at batch S
+    std::vector<int64_t> F, E;
+    std::vector<int32_t> flushed;
+    PoolPlan plan;                // the step's plan and launch tables: host vectors that keep their capacity from step to step
+    std::vector<PoolGatherEntry> gather;
+    std::vector<PoolCropEntry> crop;
+    ~fv_pool() {
+        if (ring) (void)hipFree(ring);
+    }
+};
+
+extern "C" {
+
+FV_API int32_t fv_pool_plan(const fv_pool_config* cfg, const int64_t* received, const int64_t* emitted, const int32_t* flushed,
+                            const fv_pool_item* items, int32_t count, int32_t in_frames, int32_t out_frames, fv_pool_row* rows,
+                            int32_t row_cap, int32_t* group_rows, int32_t* group_frames, int32_t group_cap, int32_t* num_groups) {
+    if (num_groups) *num_groups = 0;
+    if (!cfg || row_cap < 0 || group_cap < 0 || (row_cap > 0 && !rows) || (group_cap > 0 && (!group_rows || !group_frames))) {
+        set_error("fv_pool_plan: null argument, or a capacity without room for it");
+        return FV_ERR_INVALID;
+    }
+    PoolPlan p;
+    if (const fv_status st = pool_plan("fv_pool_plan", cfg->sessions, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames, received,
+                                       emitted, flushed, items, count, in_frames, out_frames, p))
+        return st;
+    std::copy(p.rows.begin(), p.rows.begin() + (ptrdiff_t)std::min<size_t>(p.rows.size(), (size_t)row_cap), rows);
+    const ptrdiff_t ng = (ptrdiff_t)std::min<size_t>(p.group_rows.size(), (size_t)group_cap);
+    std::copy(p.group_rows.begin(), p.group_rows.begin() + ng, group_rows);
+    std::copy(p.group_frames.begin(), p.group_frames.begin() + ng, group_frames);
+    if (num_groups) *num_groups = (int32_t)p.group_rows.size();
+    return (int32_t)p.rows.size();
+}
+
+FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool** out) {
+    if (!e || !cfg || !out) {
+        set_error("fv_pool_create: null argument");
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!e->finalized) {
+        set_error("fv_pool_create: call fv_finalize first");
+        return FV_ERR_STATE;
+    }
+    const char* why = nullptr;
+    const int hop = e->frame_hop(1, 2, &why);
+    if (hop < 1) {
+        set_error("fv_pool_create: this model cannot stream: %s", why);
+        return FV_ERR_UNSUPPORTED;
+    }
+    const int R = e->reach_frames();
+    if (cfg->sessions < 1 || cfg->max_chunk_frames < 1 || cfg->context_frames < -1 || cfg->lookahead_frames < -1) {
+        set_error("fv_pool_create: sessions (%d) and max_chunk_frames (%d) must be >= 1, context_frames (%d) and lookahead_frames (%d) >= 0 "
+                  "(-1: the reach, %d frames)", cfg->sessions, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames, R);
+        return FV_ERR_INVALID;
+    }
+    std::unique_ptr<fv_pool> p(new fv_pool());
+    p->e = e;
+    p->S = cfg->sessions;
+    p->max_chunk = cfg->max_chunk_frames;
+    p->K = cfg->context_frames < 0 ? R : cfg->context_frames;
+    p->A = cfg->lookahead_frames < 0 ? R : cfg->lookahead_frames;
+    p->cin = fv_input_channels(e);
+    p->cout = fv_output_channels(e);
+    p->hop = hop;
+    p->cap = (int64_t)p->K + p->A + p->max_chunk;
+    p->tmpl = e->wants_template();
+    if (p->cap > (1 << 20)) {
+        set_error("fv_pool_create: context + lookahead + max_chunk_frames = %lld frames, more than 2^20", (long long)p->cap);
+        return FV_ERR_INVALID;
+    }
+    // as a stream: every window length 1 ... cap must be frame-aligned, and the forward's workspace is the largest over them at batch S
+    size_t model_bytes = 0;
+    for (int W = 1; W <= p->cap; ++W)
+        if (const fv_status r = admit_window(e, "fv_pool_create", "stream", hop, p->S, W, &model_bytes)) return r;
+    const size_t cap = (size_t)p->cap, S = (size_t)p->S;
+    p->ws = WindowWorkspace(S * cap, p->cin, p->cout, hop, p->tmpl, model_bytes);
+    p->F.assign(S, 0);
+    p->E.assign(S, 0);
+    p->flushed.assign(S, 0);
+    p->gather.reserve(S);
+    p->crop.reserve(S);
+    const size_t n_ring = align_up(S * p->cin * cap, 64), n_ring_tmpl = p->tmpl ? S * cap * hop : 0;
+    FV_HIP_CHECK(hipMalloc((void**)&p->ring, (n_ring + n_ring_tmpl) * sizeof(float)));
+    p->ring_tmpl = p->tmpl ? p->ring + n_ring : nullptr;
+    *out = p.release();
+    return FV_OK;
+}
+
+FV_API size_t fv_pool_workspace_bytes(const fv_pool* p) { return p ? p->ws.bytes() : 0; }
+
+FV_API int64_t fv_pool_pending_frames(const fv_pool* p, int32_t session) {
+    return p && session >= 0 && session < p->S ? p->F[(size_t)session] - p->E[(size_t)session] : 0;
+}
+
+FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const float* d_chunks, const float* d_templates,
+                              int32_t in_frames, float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (!p || count < 0 || (count > 0 && !items) || in_frames < 0 || out_frames < 0) {
+        set_error("fv_pool_step: null argument, or a negative count, in_frames or out_frames");
+        return FV_ERR_INVALID;
+    }
+    // ---- the whole step is checked before any counter moves or anything is enqueued ----
+    PoolPlan& pl = p->plan;
+    if (const fv_status st = pool_plan("fv_pool_step", p->S, p->max_chunk, p->K, p->A, p->F.data(), p->E.data(), p->flushed.data(), items, count,
+                                       in_frames, out_frames, pl))
+        return st;
+    bool any_frames = false;
+    for (int i = 0; i < count; ++i) any_frames |= items[i].frames > 0;
+    if (any_frames && !d_chunks) {
+        set_error("fv_pool_step: null chunk buffer, but an item of this step has frames");
+        return FV_ERR_INVALID;
+    }
+    if (any_frames && p->tmpl && !d_templates) {
+        set_error("fv_pool_step: the generator was built with use_template=True and every chunk needs a template chunk (count, 1, in_frames*hop)");
+        return FV_ERR_INVALID;
+    }
+    if (!p->tmpl && d_templates) {
+        set_error("fv_pool_step: template given but the generator was built with use_template=False");
+        return FV_ERR_INVALID;
+    }
+    if (count > 0 && out_frames > 0 && !d_out) {
+        set_error("fv_pool_step: null output (out_frames = %d)", out_frames);
+        return FV_ERR_INVALID;
+    }
+    if (!d_workspace || workspace_bytes < p->ws.bytes()) {
+        set_error("fv_pool_step: workspace too small (%zu < %zu bytes, fv_pool_workspace_bytes)", d_workspace ? workspace_bytes : (size_t)0,
+                  p->ws.bytes());
+        return FV_ERR_INVALID;
+    }
+    fv_engine* e = p->e;
+    const WindowWorkspace::Parts win = p->ws.carve(d_workspace);
+    const int G = (int)pl.group_rows.size();
+    for (int g = 0; g < G; ++g)
+        if (const fv_status st = check_forward(e, win.in, win.tmpl, win.out, pl.group_rows[g], pl.group_frames[g], win.model, p->ws.model_bytes))
+            return st;
+    // ---- enqueue: per group gather -> forward -> crop; the first gather also files the chunks of the items that emit nothing, the first crop
+    //      also zeroes their output rows (with no group at all, one launch of each does only that) ----
+    hipStream_t s = (hipStream_t)stream;
+    const int hop = p->hop;
+    const ProfScope prof(e);
+    std::vector<char>& has_row = pl.seen;   // reused as: item i has a row
+    has_row.assign((size_t)count, 0);
+    for (const fv_pool_row& r : pl.rows) has_row[(size_t)r.item] = 1;
+    size_t r0 = 0;
+    for (int g = 0; g < std::max(G, 1); ++g) {
+        const int rows = G ? pl.group_rows[g] : 0;
+        const long long Wg = G ? pl.group_frames[g] : 0;
+        p->gather.clear();
+        p->crop.clear();
+        for (int k = 0; k < rows; ++k) {
+            const fv_pool_row& r = pl.rows[r0 + (size_t)k];
+            const fv_pool_item& it = items[r.item];
+            p->gather.push_back({r.item, it.session, k, r.col0, r.frames, it.frames, r.w, p->F[(size_t)it.session]});
+            p->crop.push_back({r.item, k, r.col0 + (r.emit_lo - r.w), r.emit_hi - r.emit_lo});
+        }
+        if (g == 0)
+            for (int i = 0; i < count; ++i)
+                if (!has_row[(size_t)i]) {
+                    if (items[i].frames > 0) p->gather.push_back({i, items[i].session, -1, 0, 0, items[i].frames, 0, p->F[(size_t)items[i].session]});
+                    p->crop.push_back({i, -1, 0, 0});
+                }
+        const int ng = (int)p->gather.size(), nc = (int)p->crop.size();
+        FV_PROF(s, "pool_gather", 0.0, 8.0 * rows * p->cin * Wg,
+                launch_pool_gather(d_chunks, p->ring, win.in, p->gather.data(), ng, p->cin, p->cap, in_frames, Wg, 1, s));
+        if (p->tmpl)
+            FV_PROF(s, "pool_gather", 0.0, 8.0 * rows * Wg * hop,
+                    launch_pool_gather(d_templates, p->ring_tmpl, win.tmpl, p->gather.data(), ng, 1, p->cap, in_frames, Wg, hop, s));
+        if (rows > 0) {
+            if (g == 0) {
+                // fixed addresses: a steady state with the same rows and the same Wg repeats its key and replays the captured graph
+                if (const fv_status st = forward_common(e, win.in, win.tmpl, nullptr, win.out, rows, (int)Wg, win.model, p->ws.model_bytes, stream))
+                    return st;
+            } else {
+                // eagerly, past forward_common's graph bookkeeping (as the groups of a ragged batch)
+                const ForwardScope scope(e, win.tmpl, nullptr);
+                if (const fv_status st = e->run_model(win.in, win.out, rows, (int)Wg, win.model, s)) return st;
+            }
+        }
+        FV_PROF(s, "pool_crop", 0.0, 4.0 * nc * p->cout * (double)out_frames * hop,
+                launch_pool_crop(win.out, d_out, p->crop.data(), nc, p->cout, Wg, out_frames, hop, s));
+        r0 += (size_t)rows;
+    }
+    // ---- the counters move ----
+    for (int i = 0; i < count; ++i) {
+        const size_t sess = (size_t)items[i].session;
+        if (frames_out) frames_out[i] = pl.E2[(size_t)i] - p->E[sess];
+        p->F[sess] = pl.F2[(size_t)i];
+        p->E[sess] = pl.E2[(size_t)i];
+        if (items[i].flush) p->flushed[sess] = 1;
+    }
+    return FV_OK;
+}
+
+FV_API fv_status fv_pool_reset(fv_pool* p, int32_t session) {
+    if (!p || session < 0 || session >= p->S) {
+        set_error("fv_pool_reset: no session %d", (int)session);
+        return FV_ERR_INVALID;
+    }
+    p->F[(size_t)session] = p->E[(size_t)session] = 0;
+    p->flushed[(size_t)session] = 0;
+    return FV_OK;
+}
+
+FV_API void fv_pool_destroy(fv_pool* p) { delete p; }
+
+}  // extern "C"

@@ -384,6 +384,32 @@ fv_status launch_ragged_gather(const float* x, float* win, const fv_ragged_windo
 fv_status launch_ragged_scatter(const float* win, float* y, const fv_ragged_window* tab, int first, int count, int C, long long T,
                                 long long L, int hop, hipStream_t s);
 fv_status launch_ragged_zero_tail(float* y, const int* lens, int B, int C, long long T, long long span, int hop, hipStream_t s);
+// session pool (fv_pool_step): the step's tables change every call, so they travel BY VALUE in the kernel arguments, kPoolBlock entries per
+// launch — no device table, no copy that could read a host buffer after the next step has rewritten it.  Entries count in frames; the
+// launchers take `hop` (1 for the mel, the generator's hop for the pitch template and the waveform) and scale to columns.
+static constexpr int kPoolBlock = 32;
+struct PoolGatherEntry {
+    int item, slot;       // row of the chunk buffer, row of the ring
+    int row;              // row of the group's tensor; -1: no window in this launch, the chunk only goes into the ring
+    int col0, W, n;       // first column of the window in the group's tensor, its length, the chunk's frames
+    long long w, F;       // the window is the frames [w, w + W); F frames were received before this step
+};
+struct PoolCropEntry {
+    int item, row;        // row of the caller's output; row of the group's output, -1: the item emits nothing (a row of zeros)
+    long long src, len;   // out[item][c][j] = j < len ? y[row][c][src + j] : 0
+};
+struct PoolGatherBlock {
+    PoolGatherEntry e[kPoolBlock];
+};
+struct PoolCropBlock {
+    PoolCropEntry e[kPoolBlock];
+};
+// chunk (., C, in_frames) -> ring (., C, cap) at F mod cap, and ring + chunk -> win (rows, C, Wg), zero outside [col0, col0 + W)
+fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const PoolGatherEntry* tab, int count, int C, long long cap,
+                             long long in_frames, long long Wg, int hop, hipStream_t s);
+// y (rows, C, Ly) -> out (., C, out_frames): each entry's samples, then zeros to the row's end
+fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames,
+                           int hop, hipStream_t s);
 // rows [0,nb) = Re, [nbp, nbp+nb) = Im, zero padded to nbp = round_up(nb, 8)
 fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T, int nb, int nbp, hipStream_t s);
 // frames (B, n_fft, T) (already windowed by the synthesis basis) -> overlap-add, crop, divide by the envelope.

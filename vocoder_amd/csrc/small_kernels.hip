@@ -1420,6 +1420,89 @@ fv_status launch_ragged_zero_tail(float* y, const int* lens, int B, int C, long 
     return FV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Session pool (engine_windows.hip fv_pool_step).  Every session keeps a ring row as a stream does (column f at slot f mod cap); the rows of
+// one group are windows of different lengths placed inside one (rows, C, Wg) tensor.  The entry tables arrive by value (PoolGatherBlock /
+// PoolCropBlock, kPoolBlock entries per launch: blockIdx.z picks the entry); entries count in frames and `hop` scales them to columns.
+//   pool_gather: entry with a row: win[row][c][j] = column w + (j - col0) of the session for j in [col0, col0 + W), 0.0f elsewhere; as in
+//                stream_window a column comes from the chunk when it lies at or after the old F — and goes into the ring on the way — and from
+//                the ring before it, so no value is written to the ring and read back in one launch (W <= cap: the slots read and the slots
+//                written are distinct).  Entry without a row (row < 0): chunk -> ring only.  Chunk columns >= n are never addressed: a
+//                window column f reads chunk[f - F] with f < F + n, and a ring-only entry clamps the address and selects, as ragged_gather.
+//   pool_crop  : out[item][c][j] = j < len ? y[row][c][src + j] : 0.0f over the whole output row (row < 0: a row of zeros).
+// Rows start at arbitrary columns: each lane moves one fp32, coalesced along the row (as the stream and ragged kernels).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pool_gather_kernel(const float* __restrict__ chunk, float* __restrict__ ring, float* __restrict__ win,
+                                                          const PoolGatherBlock tab, int C, long long cap, long long in_cols, long long Wg,
+                                                          int hop) {
+    const PoolGatherEntry e = tab.e[blockIdx.z];
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    const long long F = e.F * hop, n = (long long)e.n * hop;
+    const float* src = chunk + ((long long)e.item * C + c) * in_cols;
+    float* rg = ring + ((long long)e.slot * C + c) * cap;
+    if (e.row < 0) {
+        if (n <= 0 || j >= in_cols) return;
+        const bool valid = j < n;
+        const float v = src[valid ? j : 0];
+        if (valid) rg[(F + j) % cap] = v;
+        return;
+    }
+    if (j >= Wg) return;
+    const long long jj = j - (long long)e.col0 * hop, f = e.w * hop + jj;
+    float v = 0.0f;
+    if (jj >= 0 && jj < (long long)e.W * hop) {
+        float* slot = rg + f % cap;
+        if (f >= F) {
+            v = src[f - F];
+            *slot = v;
+        } else {
+            v = *slot;
+        }
+    }
+    win[((long long)e.row * C + c) * Wg + j] = v;
+}
+fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const PoolGatherEntry* tab, int count, int C, long long cap,
+                             long long in_frames, long long Wg, int hop, hipStream_t s) {
+    for (int i0 = 0; i0 < count; i0 += kPoolBlock) {
+        const int nz = std::min(kPoolBlock, count - i0);
+        PoolGatherBlock blk{};
+        long long X = 0;   // columns this launch spans: the group's tensor for a row, the chunk for a ring-only entry
+        for (int i = 0; i < nz; ++i) {
+            blk.e[i] = tab[i0 + i];
+            X = std::max(X, tab[i0 + i].row >= 0 ? Wg * hop : (long long)tab[i0 + i].n * hop);
+        }
+        if (X <= 0) continue;
+        hipLaunchKernelGGL(pool_gather_kernel, dim3((unsigned)((X + 255) / 256), C, nz), dim3(256), 0, s, chunk, ring, win, blk, C, cap * hop,
+                           in_frames * hop, Wg * hop, hop);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+__global__ __launch_bounds__(256) void pool_crop_kernel(const float* __restrict__ y, float* __restrict__ out, const PoolCropBlock tab, int C,
+                                                        long long Ly, long long out_cols, int hop) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= out_cols) return;
+    const PoolCropEntry e = tab.e[blockIdx.z];
+    const int c = blockIdx.y;
+    float v = 0.0f;
+    if (e.row >= 0 && j < e.len * hop) v = y[((long long)e.row * C + c) * Ly + e.src * hop + j];
+    out[((long long)e.item * C + c) * out_cols + j] = v;
+}
+fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames, int hop,
+                           hipStream_t s) {
+    if (out_frames <= 0) return FV_OK;
+    for (int i0 = 0; i0 < count; i0 += kPoolBlock) {
+        const int nz = std::min(kPoolBlock, count - i0);
+        PoolCropBlock blk{};
+        for (int i = 0; i < nz; ++i) blk.e[i] = tab[i0 + i];
+        hipLaunchKernelGGL(pool_crop_kernel, dim3((unsigned)((out_frames * hop + 255) / 256), C, nz), dim3(256), 0, s, y, out, blk, C, Ly * hop,
+                           out_frames * hop, hop);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+
 #ifdef FV_DEBUG_HOOKS   // not in the product library: `make BUILD=build_dbg LIB=libfishvoc_dbg.so EXTRA=-DFV_DEBUG_HOOKS`, then FV_LIB_PATH
 // Debug aid (tools/probe_lds_poison.py): fills the LDS of every CU with signalling garbage (NaN bit patterns) so that a kernel
 // which reads LDS it never wrote shows up as a changed / non-finite result instead of silently inheriting whatever the previous

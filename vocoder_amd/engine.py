@@ -10,7 +10,7 @@ from typing import Mapping
 import numpy as np
 import torch
 
-from . import _lib, streaming
+from . import _lib, sessions as _sessions, streaming
 from ._lib import FishVocError, check  # noqa: F401
 
 _SIDE_STREAM_FOR_DEFAULT = os.environ.get("FV_DEFAULT_STREAM_SIDE", "0") == "1"   # experiments: see Engine.forward
@@ -339,6 +339,14 @@ class Engine:
         self._streams.add(st)
         return st
 
+    def session_pool(self, sessions: int, max_chunk_frames: int, context_frames: int | None = None,
+                     lookahead_frames: int | None = None) -> "SessionPool":
+        """A pool of ``sessions`` streaming sessions that advance independently (``SessionPool``; the plan of a step: ``vocoder_amd.sessions``):
+        one ``step`` serves any subset of them, each with its own chunk size, each ending at its own length, in one batched forward."""
+        p = SessionPool(self, sessions, max_chunk_frames, context_frames, lookahead_frames)
+        self._streams.add(p)
+        return p
+
     def ragged_plan(self, lengths, t_max: int | None = None, launch_frames: int = 0, max_groups: int = 0) -> "RaggedPlan":
         """The plan of a ragged batch (``RaggedPlan``; the rule: ``vocoder_amd.ragged``) for ``lengths[b]`` valid frames per clip inside a
         ``(B, C_in, t_max)`` input (``t_max`` defaults to the longest clip).  Reuse it for every call with these lengths."""
@@ -552,6 +560,162 @@ class Stream:
             self._ws = None
 
     def __enter__(self) -> "Stream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SessionPool:
+    """Streaming sessions that advance independently on an ``Engine`` (``fv_pool``, include/fishvoc.h).  ``step(items)`` takes
+    ``(session, mel, flush)`` or ``(session, mel, flush, template)`` tuples — ``mel``: ``(C_in, n)`` with ``n <= max_chunk_frames``, or ``None``
+    for no frames; ``flush``: the utterance ends with these frames — and returns one ``(C_out, k * hop)`` tensor per item (``k`` may be 0): the
+    frames that session emits in this step.  A session appears at most once per step.  After its flush a session refuses items until
+    ``reset(session)``.  The whole step is checked before anything moves: a refused step leaves every session as it was.  Calls are ordered like
+    ``Stream.push``; the pool owns its workspace.  A pool dies with its engine, like a ``Stream``."""
+
+    def __init__(self, engine: Engine, sessions: int, max_chunk_frames: int, context_frames: int | None = None,
+                 lookahead_frames: int | None = None):
+        self._engine = engine
+        self._lib = engine._lib
+        self._h = ctypes.c_void_p()
+        self._done: torch.cuda.Event | None = None
+        if not engine._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, "Engine.session_pool: the engine is closed")
+        cfg = _lib.PoolConfig(int(sessions), int(max_chunk_frames), -1 if context_frames is None else int(context_frames),
+                              -1 if lookahead_frames is None else int(lookahead_frames))
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_pool_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h)))
+            self._ws = torch.empty((int(self._lib.fv_pool_workspace_bytes(self._h)) + 3) // 4, dtype=torch.float32, device=engine.device)
+        self.sessions, self.max_chunk_frames = int(sessions), int(max_chunk_frames)
+        self.reach_frames = engine.reach_frames
+        self.context_frames = self.reach_frames if context_frames is None else int(context_frames)
+        self.lookahead_frames = self.reach_frames if lookahead_frames is None else int(lookahead_frames)
+        self.hop = engine.output_length(1)
+        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
+        self.state = _sessions.PoolState(self.sessions, self.max_chunk_frames, self.context_frames, self.lookahead_frames)
+
+    # -- counters (host-side: reading them never synchronises) --
+    def received_frames(self, session: int) -> int:
+        return self.state.received[session]
+
+    def emitted_frames(self, session: int) -> int:
+        return self.state.emitted[session]
+
+    def pending_frames(self, session: int) -> int:
+        """F - E of one session as the library counts it (fv_pool_pending_frames)."""
+        self._check_open()
+        return int(self._lib.fv_pool_pending_frames(self._h, int(session)))
+
+    @property
+    def workspace_bytes(self) -> int:
+        self._check_open()
+        return int(self._lib.fv_pool_workspace_bytes(self._h))
+
+    def _check_open(self) -> None:
+        if not self._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, "this session pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or "
+                                                  ".to() on the module): create a new pool")
+
+    def step(self, items) -> list[torch.Tensor]:
+        """One step for ``items`` (see the class); returns each item's emitted audio ``(C_out, k * hop)``, views of one output buffer."""
+        self._check_open()
+        items = [(it[0], it[1], it[2] if len(it) > 2 else False, it[3] if len(it) > 3 else None) for it in map(tuple, items)]
+        dev = self._engine.device
+        meta = []
+        for s, mel, flush, tt in items:
+            n = 0
+            if mel is not None:
+                _require_cuda(mel, "SessionPool.step")
+                if mel.dim() != 2 or mel.shape[0] != self.in_channels:
+                    raise ValueError(f"expected a mel chunk of shape ({self.in_channels}, n), got {tuple(mel.shape)}")
+                n = int(mel.shape[1])
+                if tt is not None:
+                    _require_cuda(tt, "SessionPool.step template")
+                    if tuple(tt.shape) != (1, n * self.hop):
+                        raise ValueError(f"expected a template chunk of shape {(1, n * self.hop)}, got {tuple(tt.shape)}")
+            meta.append((int(s), n, bool(flush)))
+        in_frames = max((n for _, n, _ in meta), default=0)
+        chunks = tmpl = None
+        if in_frames:
+            chunks = torch.zeros((len(items), self.in_channels, in_frames), dtype=torch.float32, device=dev)
+            if any(tt is not None for _, mel, _, tt in items if mel is not None):
+                tmpl = torch.zeros((len(items), 1, in_frames * self.hop), dtype=torch.float32, device=dev)
+            for i, (_, mel, _, tt) in enumerate(items):
+                if mel is not None and mel.shape[1]:
+                    chunks[i, :, :mel.shape[1]] = mel
+                    if tt is not None:
+                        tmpl[i, :, :tt.shape[1]] = tt
+        out, emit = self.step_padded(meta, chunks, tmpl)
+        return [out[i, :, :k * self.hop] for i, k in enumerate(emit)]
+
+    def step_padded(self, items, chunks: torch.Tensor | None, templates: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None) -> tuple[torch.Tensor, list[int]]:
+        """The step on the caller's padded buffers, as ``fv_pool_step`` takes them: ``items``: ``(session, n, flush)``; ``chunks``:
+        ``(count, C_in, in_frames)`` with item i's ``n`` frames first in row i (the rest is never read); ``templates``: ``(count, 1, in_frames *
+        hop)`` for a use_template generator; ``out``: ``(count, C_out, out_frames * hop)``, sized from the Python plan when not given.  Returns
+        ``(out, frames emitted per item)``: row i holds item i's samples first, zeros after them."""
+        self._check_open()
+        items = [(int(s), int(n), bool(f)) for s, n, f in items]
+        count = len(items)
+        in_frames = 0
+        if chunks is not None:
+            _require_cuda(chunks, "SessionPool.step_padded")
+            if chunks.dim() != 3 or chunks.shape[0] != count or chunks.shape[1] != self.in_channels or not chunks.is_contiguous():
+                raise ValueError(f"expected contiguous chunks of shape ({count}, {self.in_channels}, in_frames), got {tuple(chunks.shape)}")
+            in_frames = int(chunks.shape[2])
+        if templates is not None:
+            _require_cuda(templates, "SessionPool.step_padded templates")
+            if tuple(templates.shape) != (count, 1, in_frames * self.hop) or not templates.is_contiguous():
+                raise ValueError(f"expected contiguous templates of shape {(count, 1, in_frames * self.hop)}, got {tuple(templates.shape)}")
+        plan = self.state.plan(items)                             # sizes the output before anything is launched; refuses what the library would
+        eng = self._engine
+        dev = eng.device
+        if out is None:
+            out = torch.empty((count, self.out_channels, max(plan.emit_frames, default=0) * self.hop), dtype=torch.float32, device=dev)
+        elif out.dim() != 3 or out.shape[0] != count or out.shape[1] != self.out_channels or out.shape[2] % self.hop or not out.is_contiguous():
+            raise ValueError(f"expected a contiguous out of shape ({count}, {self.out_channels}, out_frames * {self.hop}), got {tuple(out.shape)}")
+        out_frames = int(out.shape[2]) // self.hop
+        arr = (_lib.PoolItem * max(count, 1))(*[_lib.PoolItem(s, n, int(f)) for s, n, f in items])
+        got = (ctypes.c_int64 * max(count, 1))()
+        with eng._lock, torch.cuda.device(dev):
+            self._check_open()
+            cur, run = eng._order_begin(dev)
+            check(self._lib.fv_pool_step(self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None,
+                                         templates.data_ptr() if templates is not None and templates.numel() else None, in_frames,
+                                         out.data_ptr() if out.numel() else None, out_frames, got, self._ws.data_ptr(), self._ws.numel() * 4,
+                                         int(run.cuda_stream)))
+            eng._order_end(cur, run)
+            if self._done is None:
+                self._done = torch.cuda.Event()
+            self._done.record(run)
+        emit = [int(got[i]) for i in range(count)]
+        self.state.apply(items, plan)                             # the Python counters move as the library's did
+        if plan.emit_frames != emit:
+            raise RuntimeError(f"the pool emitted {emit} frames where the plan says {plan.emit_frames}")
+        return out, emit
+
+    def reset(self, session: int) -> None:
+        """Start the next utterance in one slot: F = E = 0; its ring row is kept."""
+        self._check_open()
+        check(self._lib.fv_pool_reset(self._h, int(session)))
+        self.state.reset(int(session))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            if self._done is not None:
+                self._done.synchronize()    # the rings and the workspace may still be in use on the device
+            self._lib.fv_pool_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._ws = None
+
+    def __enter__(self) -> "SessionPool":
         return self
 
     def __exit__(self, *exc) -> None:

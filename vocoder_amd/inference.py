@@ -196,6 +196,51 @@ def _main_batched(a, model, files, base) -> None:
             write_wav(Path(a.output_path) / f.relative_to(base).with_suffix(".wav"), fake.squeeze(1).cpu().numpy().T, model.sampling_rate)
 
 
+def _main_sessions(a, model, files, base) -> None:
+    """--chunk-frames n --sessions N: N mel files in flight through one session pool (``generator.session_pool``).  Every step gives each live
+    session its next n frames (the last chunk flushes it); a file ends at its own length and its slot takes the next file."""
+    if any(f.suffix == ".wav" for f in files):
+        raise ValueError("--sessions takes mel inputs (.pt / .pth); run .wav inputs without it")
+    if not hasattr(model.generator, "session_pool"):
+        raise ValueError(f"--sessions: {type(model.generator).__name__} has no session_pool()")
+    n, queue, steps = a.chunk_frames, list(files), 0
+    slots: list = [None] * min(a.sessions, max(len(files), 1))      # per slot: [file, mel (num_mels, T), frames pushed, outputs]
+    t0 = time.time()
+    secs = 0.0
+    with model.generator.session_pool(sessions=len(slots), max_chunk_frames=n) as pool:
+        while queue or any(s is not None for s in slots):
+            for i, s in enumerate(slots):
+                if s is None and queue:
+                    f = queue.pop(0)
+                    mel = torch.load(f, map_location="cpu", weights_only=True)
+                    if a.diffsinger:
+                        mel = diffsinger_mel_to_ln(mel)
+                    mel = prepare_mel(mel, model.num_mels).to(model.device)
+                    if mel.shape[0] != 1:
+                        raise ValueError(f"{f}: --sessions takes one utterance per file, got a batch of {mel.shape[0]}")
+                    slots[i] = [f, mel[0], 0, []]
+            live = [i for i, s in enumerate(slots) if s is not None]
+            items = []
+            for i in live:
+                _, mel, done, _ = slots[i]
+                items.append((i, mel[:, done:done + n], done + n >= mel.shape[1]))
+            outs = pool.step(items)
+            steps += 1
+            for i, (_, chunk, last), y in zip(live, items, outs):
+                s = slots[i]
+                s[2] += chunk.shape[1]
+                s[3].append(y.clone())      # (the views share one buffer per step)
+                if last:
+                    fake = torch.cat(s[3], dim=-1)
+                    secs += fake.shape[-1] / model.sampling_rate
+                    write_wav(Path(a.output_path) / s[0].relative_to(base).with_suffix(".wav"), fake.cpu().numpy().T, model.sampling_rate)
+                    pool.reset(i)
+                    slots[i] = None
+        torch.cuda.synchronize()
+    print(f"{len(files)} files: {secs:.2f}s of audio in {time.time() - t0:.4f}s, {len(slots)} sessions in one pool, {steps} steps of "
+          f"{n}-frame chunks")
+
+
 @torch.no_grad()
 def main(argv=None):
     ap = argparse.ArgumentParser(description="mel (.pt) or audio (.wav) -> wav on the MI355X engine (mirrors fish_vocoder/test.py)")
@@ -216,9 +261,14 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=None,
                     help="take the mel (.pt / .pth) inputs N files at a time and run each batch of utterances, whatever their lengths, through "
                          "ONE ragged forward (generator.forward_list); same wavs as the one-by-one run, within 1 LSB")
+    ap.add_argument("--sessions", type=int, default=None,
+                    help="with --chunk-frames: keep N mel (.pt / .pth) files in flight through ONE session pool (generator.session_pool); each "
+                         "file ends at its own length and its slot takes the next file; same wavs as the one-by-one run, within 1 LSB")
     a = ap.parse_args(argv)
     if a.chunk_frames is not None and a.chunk_frames < 1:
         ap.error("--chunk-frames must be >= 1")
+    if a.sessions is not None and (a.sessions < 1 or a.chunk_frames is None or a.batch_size is not None):
+        ap.error("--sessions must be >= 1, needs --chunk-frames and cannot be combined with --batch-size")
     if a.batch_size is not None and (a.batch_size < 1 or a.chunk_frames is not None):
         ap.error("--batch-size must be >= 1 and cannot be combined with --chunk-frames")
     model = build_model(a.generator, a.resolution, {"num_mels": a.num_mels} if a.num_mels else None, a.config_root,
@@ -228,6 +278,8 @@ def main(argv=None):
     base = inp.parent if inp.is_file() else inp
     if a.batch_size:
         return _main_batched(a, model, files, base)
+    if a.sessions:
+        return _main_sessions(a, model, files, base)
     for f in files:
         if f.suffix == ".wav":   # test.py:50-71: channels -> batch items, zero padding, mel_transforms.input
             y, sr = read_wav(f)

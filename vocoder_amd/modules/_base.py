@@ -115,6 +115,12 @@ class EngineModule(nn.Module):
             raise RuntimeError(f"{type(self).__name__} is inference-only: call .eval() first")
         return self.engine(p.device).stream(batch, max_chunk_frames, **kw)
 
+    def session_pool(self, sessions: int = 1, max_chunk_frames: int = 64, **kw):
+        """A pool of ``sessions`` streaming sessions that advance independently on this module's engine (``vocoder_amd.engine.SessionPool``):
+        every ``step`` serves any subset of them with chunks of different sizes, each session ending at its own length.  Lives and dies with
+        the engine like ``stream()``."""
+        return self._ragged_engine("session_pool").session_pool(sessions, max_chunk_frames, **kw)
+
     def _ragged_engine(self, what: str):
         p = next(self.parameters(), None)
         if p is None or not p.is_cuda:
