@@ -469,6 +469,91 @@ FV_API fv_status fv_pool_reset(fv_pool* p, int32_t session);
 /* Frees the rings (call it before fv_destroy of its engine, once the pool's work has finished). */
 FV_API void fv_pool_destroy(fv_pool* p);
 
+/* -------- sample-rate conversion: audio at any rate in, audio at any rate out.  Replaces the reference's two resampling front doors:
+ *          `librosa.load(..., sr=cfg.model.sampling_rate)` (test.py:54) and `torchaudio.functional.resample` (AF.resample,
+ *          data/transforms/hq_pitch_shift.py:33).  --------
+ *
+ * The arithmetic is the polyphase windowed-sinc resampler of torchaudio.transforms.Resample (restated; torchaudio is not a dependency):
+ *   g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g, base = min(o, n) * rolloff, width = ceil(lpw * o / base);
+ *   for phase p in [0, n), tap j in [0, 2 width + o):  t = clamp(((j - width) / o - p / n) * base, -lpw, +lpw),
+ *     h[p][j] = (t == 0 ? 1 : sin(pi t) / (pi t)) * win(t) * base / o,  win = cos(t pi / lpw / 2)^2 (hann) | I0(beta sqrt(1 - (t / lpw)^2)) / I0(beta);
+ *   y[f n + p] = sum_j h[p][j] xp[f o + j], xp = x with `width` zeros in front; the first ceil(n L / o) outputs are kept.
+ * The taps are computed on the host in float64 and rounded to fp32.  Only the band |t| < lpw of a phase is not zero: phase p keeps the taps
+ * j in [first[p], first[p] + count[p]), count[p] <= Kp, and output m = f n + p reads x[f o + first[p] - width + i], i < count[p].  Each output is
+ * summed over ascending i in one fp32 accumulator (fused multiply-adds), whatever the tile, the row, the launch or the chunking: the results of
+ * fv_resample_forward on a row alone, on the same row inside a ragged batch, and of a stream's pushes over it are bit-identical.
+ * The kernel is a banded FIR on the vector ALU, not an MFMA GEMM: the dense form holds 7 - 14 times the taps of the band.
+ *
+ * LDS limit: a workgroup keeps the whole table (n rows of Kp taps, rows padded to an odd length, plus first[] and count[]) and a tile of
+ * fv_resample_input_tile() + Kp + 3 input samples in 64 KiB of LDS.  A rate pair whose table does not fit beside the tile (roughly
+ * n * Kp > 7000, e.g. 44101 -> 48000) gets FV_ERR_UNSUPPORTED from fv_resample_create, with the pair and the size in fv_last_error. */
+typedef enum fv_resample_method {
+    FV_RESAMPLE_SINC_HANN = 0,   /* resampling_method="sinc_interp_hann", torchaudio's default (what hq_pitch_shift.py:33 gets) */
+    FV_RESAMPLE_SINC_KAISER = 1  /* "sinc_interp_kaiser" */
+} fv_resample_method;
+
+/* The arguments of torchaudio.functional.resample / transforms.Resample (hq_pitch_shift.py:33 passes the first two; test.py:54 names the
+ * target rate).  beta <= 0: torchaudio's default, 14.769656459379492 (kaiser only). */
+typedef struct fv_resample_config {
+    int32_t orig_freq;
+    int32_t new_freq;
+    int32_t lowpass_filter_width;  /* lpw, torchaudio's default 6 */
+    double rolloff;                /* in (0, 1], torchaudio's default 0.99 */
+    int32_t method;                /* fv_resample_method */
+    double beta;
+} fv_resample_config;
+
+/* The filter design alone, on the host (no GPU), as fv_ragged_plan / fv_pool_plan are: what test.py:54 / hq_pitch_shift.py:33 leave to their
+ * libraries.  *o, *n, *width, *kp always; first / count (n entries each, capacity phase_cap) and taps (n rows of kp, zero past count[p];
+ * capacity taps_cap floats) when not NULL — call once with NULL arrays for the sizes.  FV_ERR_INVALID names the offending field. */
+FV_API fv_status fv_resample_design(const fv_resample_config* cfg, int32_t* o, int32_t* n, int32_t* width, int32_t* kp, int32_t* first,
+                                    int32_t* count, int32_t phase_cap, float* taps, int64_t taps_cap);
+/* Input samples of the kernel's tile (a workgroup owns the outputs whose first input sample falls into one tile). */
+FV_API int32_t fv_resample_input_tile(void);
+
+typedef struct fv_resample fv_resample;
+
+/* Designs the filter and uploads its table to the current HIP device (the object's only allocation); stands in for building
+ * torchaudio.transforms.Resample(orig_freq, new_freq, ...) in front of test.py:54 / hq_pitch_shift.py:33. */
+FV_API fv_status fv_resample_create(const fv_resample_config* cfg, fv_resample** out);
+FV_API void fv_resample_destroy(fv_resample* r);
+/* ceil(n L / o): the length librosa.load(sr=...) (test.py:54) / AF.resample (hq_pitch_shift.py:33) return for L input samples; -1: bad argument. */
+FV_API int64_t fv_resample_output_length(const fv_resample* r, int64_t L);
+/* d_x: `batch` rows of L fp32 samples, row b at d_x + b * x_row_stride (rows = the flattened leading dimensions of the waveform that
+ * test.py:54 / hq_pitch_shift.py:33 resample); d_y: `batch` rows of fv_resample_output_length(r, L), row b at d_y + b * y_row_stride; the strides
+ * count floats and are >= the row's width.  d_y must not overlap d_x (FV_ERR_INVALID).  d_lengths: NULL, or `batch` int32 on the device — row b
+ * holds lengths[b] <= L samples (clamped to [0, L]; fv_resample_check_lengths refuses others from the host side); the samples past a row's length
+ * are never loaded, its ceil(n lengths[b] / o) outputs are bit-identical to the row run alone and are followed by exact zeros.  Asynchronous on
+ * `stream`. */
+FV_API fv_status fv_resample_forward(fv_resample* r, const float* d_x, int64_t x_row_stride, const int32_t* d_lengths, float* d_y,
+                                     int64_t y_row_stride, int32_t batch, int64_t L, void* stream);
+/* Host-side check of a ragged call's lengths before they go to the device (test.py:54 resamples one file, this batches several): FV_ERR_INVALID
+ * with the row named when a length is negative or > L. */
+FV_API fv_status fv_resample_check_lengths(const fv_resample* r, const int32_t* host_lengths, int32_t batch, int64_t L);
+
+/* Streaming form (no reference counterpart: test.py:54 / hq_pitch_shift.py:33 resample whole clips): `batch` rows advance in lockstep.  Host
+ * counters: N input samples received, E outputs emitted.  Output m is emitted as soon as its band has arrived: a push sets N += c and emits the
+ * outputs [E, M(N)), M(N) = #{m : first_input(m) + count[p(m)] <= N}; the flush emits [E, ceil(n N / o)) against zeros and then refuses pushes
+ * (FV_ERR_STATE) until fv_resample_stream_reset.  The latency is the band's half width, about lpw * o / base input samples.  The concatenated
+ * outputs are bit-identical to fv_resample_forward over the whole rows.  A refused call changes nothing. */
+typedef struct fv_resample_stream fv_resample_stream;
+
+/* The stream's only device allocation, made here and freed by fv_resample_stream_destroy: two (batch, Kp + max_chunk) buffers that carry each
+ * row's last Kp input samples from push to push. */
+FV_API fv_status fv_resample_stream_create(fv_resample* r, int32_t batch, int32_t max_chunk, fv_resample_stream** out);
+/* ceil(n N / o) - E: the outputs a flush would emit now. */
+FV_API int64_t fv_resample_stream_pending(const fv_resample_stream* s);
+/* d_x: (batch, c) with row stride x_row_stride, c <= max_chunk (else FV_ERR_INVALID); d_y: (batch, M(N + c) - E) with row stride y_row_stride —
+ * the count is known before the call (vocoder_amd.resample emit_count) and may be 0, then d_y may be NULL.  *emitted receives it; the counters are
+ * host-side, so the call never synchronises.  c = 0 is a no-op.  Asynchronous on `stream`; calls on one stream object must be ordered. */
+FV_API fv_status fv_resample_stream_push(fv_resample_stream* s, const float* d_x, int64_t x_row_stride, int32_t c, float* d_y,
+                                         int64_t y_row_stride, int64_t* emitted, void* stream);
+FV_API fv_status fv_resample_stream_flush(fv_resample_stream* s, float* d_y, int64_t y_row_stride, int64_t* emitted, void* stream);
+/* N = E = 0 for the next utterance; the buffers are kept. */
+FV_API fv_status fv_resample_stream_reset(fv_resample_stream* s);
+/* Call it before fv_resample_destroy of its resampler, once the stream's work has finished. */
+FV_API void fv_resample_stream_destroy(fv_resample_stream* s);
+
 /* -------- single fused conv layer (the hot kernel on its own; used by the parity tests and the roofline
  *          bench).  Stands in for one weight-normed nn.Conv1d / nn.ConvTranspose1d call plus the elementwise
  *          ops the reference runs around it (F.silu before, residual add after: hifigan.py:101-108). -------- */

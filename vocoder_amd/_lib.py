@@ -29,6 +29,8 @@ FV_CONV_ALGO_AUTO, FV_CONV_ALGO_DIRECT, FV_CONV_ALGO_WINOGRAD = 0, 1, 2
 CONV_ALGOS = {"auto": FV_CONV_ALGO_AUTO, "direct": FV_CONV_ALGO_DIRECT, "winograd": FV_CONV_ALGO_WINOGRAD}
 FV_ISTFT_SAME, FV_ISTFT_CENTER = 0, 1
 FV_ACT_NONE, FV_ACT_SILU, FV_ACT_LEAKY_RELU, FV_ACT_GELU, FV_ACT_TANH, FV_ACT_LOG_CLAMP = 0, 1, 2, 3, 4, 5
+FV_RESAMPLE_SINC_HANN, FV_RESAMPLE_SINC_KAISER = 0, 1
+RESAMPLE_METHODS = {"sinc_interp_hann": FV_RESAMPLE_SINC_HANN, "sinc_interp_kaiser": FV_RESAMPLE_SINC_KAISER}
 FV_POST_ACT_DEFAULT, FV_POST_ACT_IDENTITY = 0, -1   # fv_upsampler_config.post_activation (ABI 5): 0 = reference default SiLU, -1 = nn.Identity
 
 EXPORTS = (
@@ -43,6 +45,9 @@ EXPORTS = (
     "fv_ragged_plan", "fv_ragged_create", "fv_ragged_workspace_bytes", "fv_ragged_num_groups", "fv_ragged_group", "fv_ragged_windows",
     "fv_ragged_forward", "fv_ragged_destroy",
     "fv_pool_plan", "fv_pool_create", "fv_pool_workspace_bytes", "fv_pool_pending_frames", "fv_pool_step", "fv_pool_reset", "fv_pool_destroy",
+    "fv_resample_design", "fv_resample_input_tile", "fv_resample_create", "fv_resample_destroy", "fv_resample_output_length",
+    "fv_resample_forward", "fv_resample_check_lengths", "fv_resample_stream_create", "fv_resample_stream_pending", "fv_resample_stream_push",
+    "fv_resample_stream_flush", "fv_resample_stream_reset", "fv_resample_stream_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -110,6 +115,11 @@ class PoolItem(ctypes.Structure):
 class PoolRow(ctypes.Structure):
     _fields_ = [("item", _i32), ("group", _i32), ("col0", _i32), ("frames", _i32), ("w", ctypes.c_int64), ("emit_lo", ctypes.c_int64),
                 ("emit_hi", ctypes.c_int64)]
+
+
+class ResampleConfig(ctypes.Structure):
+    _fields_ = [("orig_freq", _i32), ("new_freq", _i32), ("lowpass_filter_width", _i32), ("rolloff", ctypes.c_double), ("method", _i32),
+                ("beta", ctypes.c_double)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -242,6 +252,33 @@ def lib() -> ctypes.CDLL:
     L.fv_pool_reset.restype = _i32
     L.fv_pool_destroy.argtypes = [vp]
     L.fv_pool_destroy.restype = None
+    rcp, i64 = ctypes.POINTER(ResampleConfig), ctypes.c_int64
+    L.fv_resample_design.argtypes = [rcp, i32p, i32p, i32p, i32p, i32p, i32p, _i32, fp, i64]
+    L.fv_resample_design.restype = _i32
+    L.fv_resample_input_tile.argtypes = []
+    L.fv_resample_input_tile.restype = _i32
+    L.fv_resample_create.argtypes = [rcp, ctypes.POINTER(vp)]
+    L.fv_resample_create.restype = _i32
+    L.fv_resample_destroy.argtypes = [vp]
+    L.fv_resample_destroy.restype = None
+    L.fv_resample_output_length.argtypes = [vp, i64]
+    L.fv_resample_output_length.restype = i64
+    L.fv_resample_forward.argtypes = [vp, vp, i64, vp, vp, i64, _i32, i64, vp]
+    L.fv_resample_forward.restype = _i32
+    L.fv_resample_check_lengths.argtypes = [vp, i32p, _i32, i64]
+    L.fv_resample_check_lengths.restype = _i32
+    L.fv_resample_stream_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_resample_stream_create.restype = _i32
+    L.fv_resample_stream_pending.argtypes = [vp]
+    L.fv_resample_stream_pending.restype = i64
+    L.fv_resample_stream_push.argtypes = [vp, vp, i64, _i32, vp, i64, i64p, vp]
+    L.fv_resample_stream_push.restype = _i32
+    L.fv_resample_stream_flush.argtypes = [vp, vp, i64, i64p, vp]
+    L.fv_resample_stream_flush.restype = _i32
+    L.fv_resample_stream_reset.argtypes = [vp]
+    L.fv_resample_stream_reset.restype = _i32
+    L.fv_resample_stream_destroy.argtypes = [vp]
+    L.fv_resample_stream_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp
@@ -267,6 +304,11 @@ def check(status: int) -> None:
 def reload_env() -> None:
     """Re-read the experiment knobs (FV_PW ...) that the library caches at first use (fv_reload_env)."""
     lib().fv_reload_env()
+
+
+def resample_input_tile() -> int:
+    """Input samples of the resampler kernel's tile (fv_resample_input_tile): the tests size their rows from it."""
+    return int(lib().fv_resample_input_tile())
 
 
 def last_kernel() -> str:

@@ -8,7 +8,9 @@
   (``{"state_dict": {"generator.<key>": ...}}``, test.py:32-37).
 * ``main`` mirrors test.py:50-99: ``.pt``/``.pth`` mels (add a batch dim to 2-D mels, transpose when the last dim is
   ``num_mels``) and ``.wav`` audio (channels become batch items, log-mel on the GPU), write ``(B, 1, T)`` -> wav.
-  PCM wav only and no resampling (librosa / soundfile are not available here): other inputs are refused, not guessed.
+  PCM wav only (librosa / soundfile are not available here): other inputs are refused, not guessed.  ``--resample`` converts a ``.wav`` at
+  another rate to the model's on the GPU (test.py:54 ``librosa.load(sr=...)``; ``vocoder_amd.resample``), ``--output-rate HZ`` converts the
+  generated audio before it is written.
   ``--chunk-frames N`` streams each input N mel frames at a time (``stream_synthesis``) instead of one whole-utterance forward.
 """
 from __future__ import annotations
@@ -146,11 +148,15 @@ def build_model(generator="hifigan", resolution="44100_512_2048", overrides=None
 
 
 @torch.no_grad()
-def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int):
+def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int, resample: nn.Module | None = None):
     """Pushes ``mel`` (B, num_mels, T) through ``generator.stream()`` ``chunk_frames`` frames at a time, then flushes (exact mode: the lookahead
-    and the left context are the generator's reach).  Returns (waveform (B, 1, T * hop), seconds to the first non-empty output, seconds per push)."""
+    and the left context are the generator's reach).  Returns (waveform (B, 1, T * hop), seconds to the first non-empty output, seconds per push).
+    ``resample`` (a ``vocoder_amd.resample.Resample``): each push's audio goes through a resample stream on the device, and the waveform comes
+    back at its ``new_freq``."""
     if not hasattr(generator, "stream"):
         raise ValueError(f"--chunk-frames: {type(generator).__name__} has no stream(); HiFiGAN / BigVGAN generators stream")
+    if resample is not None:
+        return _stream_synthesis_resampled(generator, mel, chunk_frames, resample)
     B, _, T = mel.shape
     outs, lat, first = [], [], None
     t0 = time.perf_counter()
@@ -168,6 +174,31 @@ def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int)
         if first is None:
             first = time.perf_counter() - t0
     return torch.cat(outs, dim=-1), first, lat
+
+
+def _stream_synthesis_resampled(generator, mel, chunk_frames, resample):
+    B, _, T = mel.shape
+    outs, lat, first = [], [], None
+    t0 = time.perf_counter()
+    with generator.stream(batch=B, max_chunk_frames=chunk_frames) as st:
+        if st.out_channels != 1:
+            raise ValueError(f"--output-rate: the generator emits {st.out_channels} channels; the resample stream takes waveforms (B, 1, T)")
+        # a push emits at most chunk_frames frames, the flush at most the lookahead
+        with resample.stream(batch=B, max_chunk=max(chunk_frames, st.lookahead_frames) * st.hop) as rst:
+            for f in range(0, T, chunk_frames):
+                t1 = time.perf_counter()
+                y = rst.push(st.push(mel[:, :, f:f + chunk_frames])[:, 0])
+                torch.cuda.synchronize()
+                lat.append(time.perf_counter() - t1)
+                if first is None and y.shape[-1]:
+                    first = time.perf_counter() - t0
+                outs.append(y)
+            outs.append(rst.push(st.flush()[:, 0]))
+            outs.append(rst.flush())
+            torch.cuda.synchronize()
+            if first is None:
+                first = time.perf_counter() - t0
+    return torch.cat(outs, dim=-1)[:, None], first, lat
 
 
 def _main_batched(a, model, files, base) -> None:
@@ -264,7 +295,17 @@ def main(argv=None):
     ap.add_argument("--sessions", type=int, default=None,
                     help="with --chunk-frames: keep N mel (.pt / .pth) files in flight through ONE session pool (generator.session_pool); each "
                          "file ends at its own length and its slot takes the next file; same wavs as the one-by-one run, within 1 LSB")
+    ap.add_argument("--resample", action="store_true",
+                    help="convert a .wav whose sampling rate is not the model's to the model's rate on the GPU (the reference's "
+                         "librosa.load(sr=...)); without it such a file is refused")
+    ap.add_argument("--output-rate", type=int, default=None, metavar="HZ",
+                    help="convert the generated audio to HZ on the GPU before it is written (with --chunk-frames: chunk by chunk through a "
+                         "resample stream); not with --batch-size / --sessions")
     a = ap.parse_args(argv)
+    if a.output_rate is not None and a.output_rate < 1:
+        ap.error("--output-rate must be >= 1 Hz")
+    if a.output_rate is not None and (a.batch_size is not None or a.sessions is not None):
+        ap.error("--output-rate is not available with --batch-size / --sessions yet: run those at the model's rate, or the files one by one")
     if a.chunk_frames is not None and a.chunk_frames < 1:
         ap.error("--chunk-frames must be >= 1")
     if a.sessions is not None and (a.sessions < 1 or a.chunk_frames is None or a.batch_size is not None):
@@ -276,6 +317,11 @@ def main(argv=None):
     inp = Path(a.input_path)
     files = [inp] if inp.is_file() else sorted(p for p in inp.rglob("*") if p.suffix in (".pt", ".pth", ".wav"))
     base = inp.parent if inp.is_file() else inp
+    out_rate = a.output_rate if a.output_rate is not None else model.sampling_rate
+    to_out = None
+    if out_rate != model.sampling_rate:
+        from .resample import Resample
+        to_out = Resample(model.sampling_rate, out_rate)
     if a.batch_size:
         return _main_batched(a, model, files, base)
     if a.sessions:
@@ -283,9 +329,12 @@ def main(argv=None):
     for f in files:
         if f.suffix == ".wav":   # test.py:50-71: channels -> batch items, zero padding, mel_transforms.input
             y, sr = read_wav(f)
-            if sr != model.sampling_rate:
+            if sr != model.sampling_rate and not a.resample:
                 raise ValueError(f"{f}: {sr} Hz, the model runs at {model.sampling_rate} Hz and this tool does not resample")
             y = torch.from_numpy(y)[:, None]
+            if sr != model.sampling_rate:      # test.py:54: librosa.load(..., sr=cfg.model.sampling_rate)
+                from .resample import Resample
+                y = Resample(sr, model.sampling_rate)(y.to(model.device))
             y = torch.nn.functional.pad(y, (0, model.hop_length - (model.hop_length % y.shape[-1])))   # as written upstream
             mel = model.mel_transform(y.to(model.device).squeeze(1))
         else:
@@ -295,15 +344,17 @@ def main(argv=None):
             mel = prepare_mel(mel, model.num_mels).to(model.device)
         t0 = time.time()
         if a.chunk_frames:
-            fake, first, lat = stream_synthesis(model.generator, mel, a.chunk_frames)
-            print(f"{f}: {fake.shape[-1] / model.sampling_rate:.2f}s of audio in {time.time() - t0:.4f}s, streamed in {a.chunk_frames}-frame "
+            fake, first, lat = stream_synthesis(model.generator, mel, a.chunk_frames, resample=to_out)
+            print(f"{f}: {fake.shape[-1] / out_rate:.2f}s of audio in {time.time() - t0:.4f}s, streamed in {a.chunk_frames}-frame "
                   f"chunks: first audio after {first * 1e3:.2f} ms, per-chunk p50 {np.percentile(lat, 50) * 1e3:.2f} ms")
         else:
             fake = model(None, None, input_spec=mel)[0]
+            if to_out is not None:
+                fake = to_out(fake)
             torch.cuda.synchronize()
-            print(f"{f}: {fake.shape[-1] / model.sampling_rate:.2f}s of audio in {time.time() - t0:.4f}s")
+            print(f"{f}: {fake.shape[-1] / out_rate:.2f}s of audio in {time.time() - t0:.4f}s")
         out = Path(a.output_path) / f.relative_to(base).with_suffix(".wav")
-        write_wav(out, fake.squeeze(1).cpu().numpy().T, model.sampling_rate)
+        write_wav(out, fake.squeeze(1).cpu().numpy().T, out_rate)
 
 
 if __name__ == "__main__":
