@@ -1,6 +1,7 @@
 // Windowed forwards: the unchanged model run on windows of frames under the reach rule, keeping only the frames that lie a reach inside each
-// window edge.  The reach and the frame-alignment test, and the three callers that share them and the window workspace: the time tiles of a
-// long clip (run_model), streams (fv_stream_*) and ragged batches (fv_ragged_*, planner included).
+// window edge.  The reach and the frame-alignment test, and the four callers that share them and the window workspace: the time tiles of a
+// long clip (run_model), streams (fv_stream_*), ragged batches (fv_ragged_*, planner included) and session pools (fv_pool_*, planner included).
+// The copy kernels they launch: window_kernels.hip.
 #include "engine_internal.h"
 
 // ---- long clips as a batch of time tiles -------------------------------------------------------------------------
@@ -101,7 +102,7 @@ fv_engine::TilePlan fv_engine::tile_plan(int t_in) const {
 
 // The workspace of a windowed forward: [window input | window template | window output | the model's own workspace], for `item_frames`
 // = windows x frames of input at `hop` samples per frame; each of the first three parts is rounded to 64 floats (256 bytes).  Sized and
-// carved here only: the tiles build one per call, a stream and a ragged plan hold theirs.
+// carved here only: the tiles build one per call, a stream, a ragged plan and a session pool hold theirs.
 struct WindowWorkspace {
     size_t n_in = 0, n_tmpl = 0, n_out = 0;   // floats
     size_t model_bytes = 0;
@@ -118,7 +119,35 @@ struct WindowWorkspace {
         float* out = in + n_in + n_tmpl;
         return {in, n_tmpl ? in + n_in : nullptr, out, out + n_out};
     }
+    // what `fn` refuses when the caller's workspace is shorter than its `getter` said
+    fv_status check(const char* fn, const char* getter, const void* ws, size_t ws_bytes) const {
+        if (ws && ws_bytes >= bytes()) return FV_OK;
+        set_error("%s: workspace too small (%zu < %zu bytes, %s)", fn, ws ? ws_bytes : (size_t)0, bytes(), getter);
+        return FV_ERR_INVALID;
+    }
 };
+
+// What fv_stream_create, fv_ragged_create and fv_pool_create (`fn`, which wants to `verb`) check first: their arguments, a finalized engine, a
+// frame-aligned model.  Clears *out; *hop: the model's samples per frame.
+template <class Handle>
+static fv_status create_preamble(const fv_engine* e, const void* arg, Handle** out, const char* fn, const char* verb, int* hop) {
+    if (!e || !arg || !out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!e->finalized) {
+        set_error("%s: call fv_finalize first", fn);
+        return FV_ERR_STATE;
+    }
+    const char* why = nullptr;
+    *hop = e->frame_hop(1, 2, &why);
+    if (*hop < 1) {
+        set_error("%s: this model cannot %s: %s", fn, verb, why);
+        return FV_ERR_UNSUPPORTED;
+    }
+    return FV_OK;
+}
 
 // One window length a windowed caller (`fn`, which wants to `verb`) can form: frame-aligned with this hop, and a forward of batch x frames
 // fits.  Raises *model_bytes to that forward's workspace (fv_workspace_bytes need not be monotone in t_in: the tile plan switches in at the
@@ -169,6 +198,64 @@ fv_status fv_engine::run_model(const float* d_in, float* d_out, int batch, int t
     return FV_OK;
 }
 
+// ---- rings: what streams and session pools share ---------------------------------------------------------------------
+// What a stream and a session pool share: `rows` sessions (the stream's batch, advancing in lockstep; the pool's slots, each on its own) that
+// keep their last `cap` frames in a ring and form windows of at most `cap` frames in the caller's workspace.
+struct RingWindows {
+    fv_engine* e = nullptr;
+    int rows = 0, max_chunk = 0, K = 0, A = 0, cin = 0, cout = 0, hop = 0;
+    int64_t cap = 0;              // ring length in frames: K + A + max_chunk, >= every window a session forms
+    bool tmpl = false;            // use_template generator: a template ring at the hop rate beside the mel ring
+    float* ring = nullptr;        // (rows, C_in, cap), then (rows, 1, cap * hop) for the template: the only device allocation
+    float* ring_tmpl = nullptr;
+    WindowWorkspace ws;           // sized for rows x cap frames, and the forward's own workspace for the largest window at batch `rows`
+    ~RingWindows() {
+        if (ring) (void)hipFree(ring);
+    }
+    // For `fn`, which calls its rows `rows_name`, past its create_preamble (`hop` is set); context / lookahead: -1 = the reach
+    fv_status create(fv_engine* e_, const char* fn, const char* rows_name, int rows_, int max_chunk_, int context, int lookahead) {
+        const int R = e_->reach_frames();
+        if (rows_ < 1 || max_chunk_ < 1 || context < -1 || lookahead < -1) {
+            set_error("%s: %s (%d) and max_chunk_frames (%d) must be >= 1, context_frames (%d) and lookahead_frames (%d) >= 0 "
+                      "(-1: the reach, %d frames)", fn, rows_name, rows_, max_chunk_, context, lookahead, R);
+            return FV_ERR_INVALID;
+        }
+        e = e_;
+        rows = rows_;
+        max_chunk = max_chunk_;
+        K = context < 0 ? R : context;
+        A = lookahead < 0 ? R : lookahead;
+        cin = fv_input_channels(e);
+        cout = fv_output_channels(e);
+        cap = (int64_t)K + A + max_chunk;
+        tmpl = e->wants_template();
+        if (cap > (1 << 20)) {
+            set_error("%s: context + lookahead + max_chunk_frames = %lld frames, more than 2^20", fn, (long long)cap);
+            return FV_ERR_INVALID;
+        }
+        // Every window length a session can form (1 ... cap frames) must be frame-aligned; the forward's workspace is the largest over them
+        size_t model_bytes = 0;
+        for (int W = 1; W <= cap; ++W)
+            if (const fv_status r = admit_window(e, fn, "stream", hop, rows, W, &model_bytes)) return r;
+        const size_t n = (size_t)rows * (size_t)cap;
+        ws = WindowWorkspace(n, cin, cout, hop, tmpl, model_bytes);
+        const size_t n_ring = align_up(n * cin, 64), n_ring_tmpl = tmpl ? n * hop : 0;
+        FV_HIP_CHECK(hipMalloc((void**)&ring, (n_ring + n_ring_tmpl) * sizeof(float)));
+        ring_tmpl = tmpl ? ring + n_ring : nullptr;
+        return FV_OK;
+    }
+};
+
+// The emission rule, of a stream and of each session of a pool alike: n more frames arrive at the counters (F, E); the frames [E, E2) are
+// emitted out of one forward over the window [w, F2) (vocoder_amd/streaming.py restates it in Python).
+struct Emission {
+    int64_t F2, E2, w;
+};
+static inline Emission emission(int64_t F, int64_t E, int64_t n, int K, int A, bool flush) {
+    const int64_t F2 = F + n;
+    return {F2, flush ? F2 : std::max(E, F2 - A), std::max<int64_t>(0, E - K)};
+}
+
 // ---- streaming synthesis ---------------------------------------------------------------------------------------------
 // B sessions advance in lockstep.  Host counters: F frames received, E emitted.  A push of n frames appends them (F += n) and emits the frames
 // [E, E'), E' = max(E, F - A), out of ONE forward over the window [w, F), w = max(0, E - K); a flush does the same with E' = F.  With K and A
@@ -176,19 +263,9 @@ fv_status fv_engine::run_model(const float* d_in, float* d_out, int batch, int t
 // utterance's samples there (the rule of the time tiles, tile_plan).  The window is assembled in the caller's workspace at fixed addresses: a
 // steady-state push (fixed n: W = K + A + n frames) hands forward_common the same (buffers, batch, frames, stream) as the one before and
 // replays its captured graph.
-struct fv_stream {
-    fv_engine* e = nullptr;
-    int B = 0, max_chunk = 0, K = 0, A = 0, cin = 0, cout = 0, hop = 0;
-    int64_t cap = 0;              // ring length in frames: K + A + max_chunk, >= every window the stream forms
-    bool tmpl = false;            // use_template generator: a template ring at the hop rate beside the mel ring
-    float* ring = nullptr;        // (B, C_in, cap), then (B, 1, cap * hop) for the template: the stream's only device allocation
-    float* ring_tmpl = nullptr;
-    WindowWorkspace ws;           // sized for cap frames, and the forward's own workspace for the largest window
+struct fv_stream : RingWindows {
     int64_t F = 0, E = 0;
     bool flushed = false;
-    ~fv_stream() {
-        if (ring) (void)hipFree(ring);
-    }
 };
 
 static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_template, int32_t n, bool flush, float* d_out,
@@ -222,21 +299,17 @@ static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_t
             return FV_ERR_INVALID;
         }
     }
-    if (!d_workspace || workspace_bytes < st->ws.bytes()) {
-        set_error("%s: workspace too small (%zu < %zu bytes, fv_stream_workspace_bytes)", fn, d_workspace ? workspace_bytes : (size_t)0,
-                  st->ws.bytes());
-        return FV_ERR_INVALID;
-    }
-    const int64_t F = st->F + (flush ? 0 : n);
-    const int64_t E2 = flush ? F : std::max(st->E, F - st->A);
+    if (const fv_status r = st->ws.check(fn, "fv_stream_workspace_bytes", d_workspace, workspace_bytes)) return r;
+    const Emission em = emission(st->F, st->E, flush ? 0 : n, st->K, st->A, flush);
+    const int64_t F = em.F2, E2 = em.E2;
     const bool emit = E2 > st->E;
     if (emit && !d_out) {
         set_error("%s: null output (this call emits %lld frames)", fn, (long long)(E2 - st->E));
         return FV_ERR_INVALID;
     }
     fv_engine* e = st->e;
-    const int B = st->B, hop = st->hop;
-    const int64_t w = emit ? std::max<int64_t>(0, st->E - st->K) : st->F;   // no emission: the chunk only goes into the ring
+    const int B = st->rows, hop = st->hop;
+    const int64_t w = emit ? em.w : st->F;   // no emission: the chunk only goes into the ring
     hipStream_t s = (hipStream_t)stream;
     const WindowWorkspace::Parts win = st->ws.carve(d_workspace);
     const ProfScope prof(e);
@@ -272,51 +345,10 @@ FV_API int32_t fv_reach_frames(const fv_engine* e) {
 }
 
 FV_API fv_status fv_stream_create(fv_engine* e, const fv_stream_config* cfg, fv_stream** out) {
-    if (!e || !cfg || !out) {
-        set_error("fv_stream_create: null argument");
-        return FV_ERR_INVALID;
-    }
-    *out = nullptr;
-    if (!e->finalized) {
-        set_error("fv_stream_create: call fv_finalize first");
-        return FV_ERR_STATE;
-    }
-    const char* why = nullptr;
-    const int hop = e->frame_hop(1, 2, &why);
-    if (hop < 1) {
-        set_error("fv_stream_create: this model cannot stream: %s", why);
-        return FV_ERR_UNSUPPORTED;
-    }
-    const int R = e->reach_frames();
-    if (cfg->batch < 1 || cfg->max_chunk_frames < 1 || cfg->context_frames < -1 || cfg->lookahead_frames < -1) {
-        set_error("fv_stream_create: batch (%d) and max_chunk_frames (%d) must be >= 1, context_frames (%d) and lookahead_frames (%d) >= 0 "
-                  "(-1: the reach, %d frames)", cfg->batch, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames, R);
-        return FV_ERR_INVALID;
-    }
     std::unique_ptr<fv_stream> st(new fv_stream());
-    st->e = e;
-    st->B = cfg->batch;
-    st->max_chunk = cfg->max_chunk_frames;
-    st->K = cfg->context_frames < 0 ? R : cfg->context_frames;
-    st->A = cfg->lookahead_frames < 0 ? R : cfg->lookahead_frames;
-    st->cin = fv_input_channels(e);
-    st->cout = fv_output_channels(e);
-    st->hop = hop;
-    st->cap = (int64_t)st->K + st->A + st->max_chunk;
-    st->tmpl = e->wants_template();
-    if (st->cap > (1 << 20)) {
-        set_error("fv_stream_create: context + lookahead + max_chunk_frames = %lld frames, more than 2^20", (long long)st->cap);
-        return FV_ERR_INVALID;
-    }
-    // Every window length the stream can form (1 ... cap frames) must be frame-aligned; the forward's workspace is the largest over them
-    size_t model_bytes = 0;
-    for (int W = 1; W <= st->cap; ++W)
-        if (const fv_status r = admit_window(e, "fv_stream_create", "stream", hop, st->B, W, &model_bytes)) return r;
-    const size_t cap = (size_t)st->cap, B = (size_t)st->B;
-    st->ws = WindowWorkspace(B * cap, st->cin, st->cout, hop, st->tmpl, model_bytes);
-    const size_t n_ring = align_up(B * st->cin * cap, 64), n_ring_tmpl = st->tmpl ? B * cap * hop : 0;
-    FV_HIP_CHECK(hipMalloc((void**)&st->ring, (n_ring + n_ring_tmpl) * sizeof(float)));
-    st->ring_tmpl = st->tmpl ? st->ring + n_ring : nullptr;
+    if (const fv_status r = create_preamble(e, cfg, out, "fv_stream_create", "stream", &st->hop)) return r;
+    if (const fv_status r = st->create(e, "fv_stream_create", "batch", cfg->batch, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames))
+        return r;
     *out = st.release();
     return FV_OK;
 }
@@ -464,21 +496,8 @@ FV_API int32_t fv_ragged_plan(int32_t reach, const int32_t* host_lengths, int32_
 
 FV_API fv_status fv_ragged_create(fv_engine* e, const int32_t* host_lengths, int32_t batch, int32_t t_max, int32_t launch_frames,
                                   int32_t max_groups, fv_ragged** out) {
-    if (!e || !host_lengths || !out) {
-        set_error("fv_ragged_create: null argument");
-        return FV_ERR_INVALID;
-    }
-    *out = nullptr;
-    if (!e->finalized) {
-        set_error("fv_ragged_create: call fv_finalize first");
-        return FV_ERR_STATE;
-    }
-    const char* why = nullptr;
-    const int hop = e->frame_hop(1, 2, &why);
-    if (hop < 1) {
-        set_error("fv_ragged_create: this model cannot run ragged batches: %s", why);
-        return FV_ERR_UNSUPPORTED;
-    }
+    int hop = 0;
+    if (const fv_status st = create_preamble(e, host_lengths, out, "fv_ragged_create", "run ragged batches", &hop)) return st;
     if (batch < 1 || t_max < 1) {
         set_error("fv_ragged_create: batch (%d) and t_max (%d) must be >= 1", batch, t_max);
         return FV_ERR_INVALID;
@@ -552,11 +571,7 @@ FV_API fv_status fv_ragged_forward(fv_ragged* p, const float* d_in, const float*
         set_error("fv_ragged_forward: null argument");
         return FV_ERR_INVALID;
     }
-    if (!d_workspace || workspace_bytes < p->ws.bytes()) {
-        set_error("fv_ragged_forward: workspace too small (%zu < %zu bytes, fv_ragged_workspace_bytes)", d_workspace ? workspace_bytes : (size_t)0,
-                  p->ws.bytes());
-        return FV_ERR_INVALID;
-    }
+    if (const fv_status st = p->ws.check("fv_ragged_forward", "fv_ragged_workspace_bytes", d_workspace, workspace_bytes)) return st;
     fv_engine* e = p->e;
     if (const fv_status st = check_template(e, d_template)) return st;   // (up front: a batch of empty clips runs no forward that would check it)
     const WindowWorkspace::Parts win = p->ws.carve(d_workspace);
@@ -645,15 +660,15 @@ static fv_status pool_plan(const char* fn, int S, int max_chunk, int K, int A, c
             set_error("%s: session %d was flushed (item %d); fv_pool_reset it before the next utterance", fn, it.session, i);
             return FV_ERR_STATE;
         }
-        const int64_t f2 = f + it.frames, e2 = it.flush ? f2 : std::max(e, f2 - A);
+        const Emission em = emission(f, e, it.frames, K, A, it.flush != 0);
+        const int64_t f2 = em.F2, e2 = em.E2;
         p.F2[(size_t)i] = f2;
         p.E2[(size_t)i] = e2;
         max_n = std::max(max_n, it.frames);
         max_emit = std::max(max_emit, e2 - e);
         if (e2 > e) {
-            const int64_t w = std::max<int64_t>(0, e - K);
-            p.cand.push_back({i, 0, 0, (int32_t)(f2 - w), w, e, e2});
-            Wg = std::max(Wg, f2 - w);
+            p.cand.push_back({i, 0, 0, (int32_t)(f2 - em.w), em.w, e, e2});
+            Wg = std::max(Wg, f2 - em.w);
         }
     }
     if (in_frames >= 0 && in_frames < max_n) {
@@ -691,22 +706,12 @@ static fv_status pool_plan(const char* fn, int S, int max_chunk, int K, int A, c
     return FV_OK;
 }
 
-struct fv_pool {
-    fv_engine* e = nullptr;
-    int S = 0, max_chunk = 0, K = 0, A = 0, cin = 0, cout = 0, hop = 0;
-    int64_t cap = 0;              // ring length in frames: K + A + max_chunk, >= every window a session forms
-    bool tmpl = false;
-    float* ring = nullptr;        // (S, C_in, cap), then (S, 1, cap * hop) for the template: the pool's only device allocation
-    float* ring_tmpl = nullptr;
-    WindowWorkspace ws;           // sized for S x cap frames, and the forward's own workspace for the largest window at batch S
-    std::vector<int64_t> F, E;
+struct fv_pool : RingWindows {
+    std::vector<int64_t> F, E;    // per session
     std::vector<int32_t> flushed;
     PoolPlan plan;                // the step's plan and launch tables: host vectors that keep their capacity from step to step
     std::vector<PoolGatherEntry> gather;
     std::vector<PoolCropEntry> crop;
-    ~fv_pool() {
-        if (ring) (void)hipFree(ring);
-    }
 };
 
 extern "C" {
@@ -732,56 +737,16 @@ FV_API int32_t fv_pool_plan(const fv_pool_config* cfg, const int64_t* received, 
 }
 
 FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool** out) {
-    if (!e || !cfg || !out) {
-        set_error("fv_pool_create: null argument");
-        return FV_ERR_INVALID;
-    }
-    *out = nullptr;
-    if (!e->finalized) {
-        set_error("fv_pool_create: call fv_finalize first");
-        return FV_ERR_STATE;
-    }
-    const char* why = nullptr;
-    const int hop = e->frame_hop(1, 2, &why);
-    if (hop < 1) {
-        set_error("fv_pool_create: this model cannot stream: %s", why);
-        return FV_ERR_UNSUPPORTED;
-    }
-    const int R = e->reach_frames();
-    if (cfg->sessions < 1 || cfg->max_chunk_frames < 1 || cfg->context_frames < -1 || cfg->lookahead_frames < -1) {
-        set_error("fv_pool_create: sessions (%d) and max_chunk_frames (%d) must be >= 1, context_frames (%d) and lookahead_frames (%d) >= 0 "
-                  "(-1: the reach, %d frames)", cfg->sessions, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames, R);
-        return FV_ERR_INVALID;
-    }
     std::unique_ptr<fv_pool> p(new fv_pool());
-    p->e = e;
-    p->S = cfg->sessions;
-    p->max_chunk = cfg->max_chunk_frames;
-    p->K = cfg->context_frames < 0 ? R : cfg->context_frames;
-    p->A = cfg->lookahead_frames < 0 ? R : cfg->lookahead_frames;
-    p->cin = fv_input_channels(e);
-    p->cout = fv_output_channels(e);
-    p->hop = hop;
-    p->cap = (int64_t)p->K + p->A + p->max_chunk;
-    p->tmpl = e->wants_template();
-    if (p->cap > (1 << 20)) {
-        set_error("fv_pool_create: context + lookahead + max_chunk_frames = %lld frames, more than 2^20", (long long)p->cap);
-        return FV_ERR_INVALID;
-    }
-    // as a stream: every window length 1 ... cap must be frame-aligned, and the forward's workspace is the largest over them at batch S
-    size_t model_bytes = 0;
-    for (int W = 1; W <= p->cap; ++W)
-        if (const fv_status r = admit_window(e, "fv_pool_create", "stream", hop, p->S, W, &model_bytes)) return r;
-    const size_t cap = (size_t)p->cap, S = (size_t)p->S;
-    p->ws = WindowWorkspace(S * cap, p->cin, p->cout, hop, p->tmpl, model_bytes);
+    if (const fv_status r = create_preamble(e, cfg, out, "fv_pool_create", "stream", &p->hop)) return r;
+    if (const fv_status r = p->create(e, "fv_pool_create", "sessions", cfg->sessions, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames))
+        return r;
+    const size_t S = (size_t)p->rows;
     p->F.assign(S, 0);
     p->E.assign(S, 0);
     p->flushed.assign(S, 0);
     p->gather.reserve(S);
     p->crop.reserve(S);
-    const size_t n_ring = align_up(S * p->cin * cap, 64), n_ring_tmpl = p->tmpl ? S * cap * hop : 0;
-    FV_HIP_CHECK(hipMalloc((void**)&p->ring, (n_ring + n_ring_tmpl) * sizeof(float)));
-    p->ring_tmpl = p->tmpl ? p->ring + n_ring : nullptr;
     *out = p.release();
     return FV_OK;
 }
@@ -789,7 +754,7 @@ FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool
 FV_API size_t fv_pool_workspace_bytes(const fv_pool* p) { return p ? p->ws.bytes() : 0; }
 
 FV_API int64_t fv_pool_pending_frames(const fv_pool* p, int32_t session) {
-    return p && session >= 0 && session < p->S ? p->F[(size_t)session] - p->E[(size_t)session] : 0;
+    return p && session >= 0 && session < p->rows ? p->F[(size_t)session] - p->E[(size_t)session] : 0;
 }
 
 FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const float* d_chunks, const float* d_templates,
@@ -801,7 +766,7 @@ FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t cou
     }
     // ---- the whole step is checked before any counter moves or anything is enqueued ----
     PoolPlan& pl = p->plan;
-    if (const fv_status st = pool_plan("fv_pool_step", p->S, p->max_chunk, p->K, p->A, p->F.data(), p->E.data(), p->flushed.data(), items, count,
+    if (const fv_status st = pool_plan("fv_pool_step", p->rows, p->max_chunk, p->K, p->A, p->F.data(), p->E.data(), p->flushed.data(), items, count,
                                        in_frames, out_frames, pl))
         return st;
     bool any_frames = false;
@@ -822,11 +787,7 @@ FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t cou
         set_error("fv_pool_step: null output (out_frames = %d)", out_frames);
         return FV_ERR_INVALID;
     }
-    if (!d_workspace || workspace_bytes < p->ws.bytes()) {
-        set_error("fv_pool_step: workspace too small (%zu < %zu bytes, fv_pool_workspace_bytes)", d_workspace ? workspace_bytes : (size_t)0,
-                  p->ws.bytes());
-        return FV_ERR_INVALID;
-    }
+    if (const fv_status st = p->ws.check("fv_pool_step", "fv_pool_workspace_bytes", d_workspace, workspace_bytes)) return st;
     fv_engine* e = p->e;
     const WindowWorkspace::Parts win = p->ws.carve(d_workspace);
     const int G = (int)pl.group_rows.size();
@@ -892,7 +853,7 @@ FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t cou
 }
 
 FV_API fv_status fv_pool_reset(fv_pool* p, int32_t session) {
-    if (!p || session < 0 || session >= p->S) {
+    if (!p || session < 0 || session >= p->rows) {
         set_error("fv_pool_reset: no session %d", (int)session);
         return FV_ERR_INVALID;
     }

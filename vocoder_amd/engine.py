@@ -29,6 +29,87 @@ def _stream_ptr(device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _exact(t: "torch.Tensor | None", what: str, noun: str, shape: tuple, make_contiguous: bool = True):
+    """An optional tensor that must have exactly ``shape`` -> (the tensor, its device pointer); (None, None) without one.  ``noun`` is what the
+    ValueError calls it; ``make_contiguous=False``: the caller's own layout must be contiguous already."""
+    if t is None:
+        return None, None
+    _require_cuda(t, what)
+    if make_contiguous:
+        t = t.contiguous()
+    if tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"expected {noun} of shape {shape}, got {tuple(t.shape)}")
+    return t, t.data_ptr()
+
+
+def _int_list(lengths) -> list[int]:
+    return [int(t) for t in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+
+
+class _Handle:
+    """Owner of one library handle ``_h``, with the name of its destroy function and the message of a call on a closed one; optionally a
+    workspace tensor ``_ws`` and an event ``_done``, recorded after the last call that used either on the device."""
+    _destroy = ""
+    _closed = ""
+    _h: "ctypes.c_void_p | None" = None            # class defaults: close() also serves an object whose __init__ raised half way
+    _ws: "torch.Tensor | None" = None
+    _done: "torch.cuda.Event | None" = None
+
+    def _check_open(self) -> None:
+        if not self._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, self._closed)
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            if self._done is not None:
+                self._done.synchronize()    # what the handle owns on the device and the workspace may still be in use there
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = ctypes.c_void_p()
+            self._ws = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _EngineHandle(_Handle):
+    """A handle made on an ``Engine`` that owns its workspace (``Stream``, ``SessionPool``, ``RaggedPlan``) and dies with the engine."""
+    _ws_getter = ""
+
+    def _attach(self, engine: "Engine", where: str) -> None:
+        self._engine = engine
+        self._lib = engine._lib
+        self._h = ctypes.c_void_p()
+        if not engine._h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, f"{where}: the engine is closed")
+
+    def _alloc_workspace(self, spare: int = 0) -> None:
+        self._ws = torch.empty((self.workspace_bytes + 3) // 4 + spare, dtype=torch.float32, device=self._engine.device)
+
+    def _ring_attrs(self, max_chunk_frames: int, context_frames: "int | None", lookahead_frames: "int | None") -> None:
+        """What a ``Stream`` and a ``SessionPool`` tell about their windows; K and A default to the reach."""
+        eng = self._engine
+        self.max_chunk_frames = int(max_chunk_frames)
+        self.reach_frames = eng.reach_frames
+        self.context_frames = self.reach_frames if context_frames is None else int(context_frames)
+        self.lookahead_frames = self.reach_frames if lookahead_frames is None else int(lookahead_frames)
+        self.hop = eng.output_length(1)
+        self.in_channels, self.out_channels = eng.in_channels, eng.out_channels
+
+    @property
+    def workspace_bytes(self) -> int:
+        self._check_open()
+        return int(getattr(self._lib, self._ws_getter)(self._h))
+
+
 def post_activation_to_act(act) -> tuple[int, float]:
     """``post_activation()`` of the reference ctor (hifigan.py:150,213: any nn.Module factory) -> (fv_act, slope).  The element-wise modules
     that have a kernel form map onto ``fv_act``; anything else raises NotImplementedError naming what is accepted."""
@@ -156,8 +237,9 @@ def _host_arrays(state_dict):
         yield name, np.ascontiguousarray(a, dtype=np.float32)
 
 
-class Engine:
+class Engine(_Handle):
     """Owns one ``fv_engine`` on the current device.  ``state_dict`` uses the reference's key names."""
+    _destroy = "fv_destroy"
 
     def __init__(self, model_kind: int, *, ups=None, backbone=None, head=None, mel=None, refine=None,
                  state_dict: Mapping[str, "np.ndarray | torch.Tensor"], device=None, precision: str = "f32"):
@@ -214,15 +296,7 @@ class Engine:
         """Destroys the engine; its live streams are closed first (their pushes then raise)."""
         for st in list(getattr(self, "_streams", ())):
             st.close()
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.fv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def set_graph_replay(self, enable: bool) -> None:
         """hipGraph replay of repeated identical calls (default on); off = every forward enqueues its kernels eagerly."""
@@ -260,11 +334,7 @@ class Engine:
                 noise: torch.Tensor | None = None) -> torch.Tensor:
         """``noise`` (RefineGAN engines only): flat fp32 tensor of ``noise_elems(B, T)`` standard-normal samples standing in
         for AdaIN's torch.randn_like draws (reference refinegan.py:125), in order of use."""
-        _require_cuda(x, "Engine.forward")
-        if x.dim() != 3 or x.shape[1] != self.in_channels:
-            raise ValueError(f"expected input of shape (B, {self.in_channels}, T), got {tuple(x.shape)}")
-        x = x.contiguous()
-        B, _, T = x.shape
+        x, B, T = self._input(x, "Engine.forward")
         if T == 0:   # the reference fails here too: conv_pre's kernel is wider than the padded input
             raise ValueError(f"empty input {tuple(x.shape)}")
         L = self.output_length(T)
@@ -274,13 +344,7 @@ class Engine:
             return out if out is not None else torch.empty((0, self.out_channels, L), dtype=torch.float32, device=x.device)
         if out is None:
             out = torch.empty((B, self.out_channels, L), dtype=torch.float32, device=x.device)
-        tptr = None
-        if template is not None:
-            _require_cuda(template, "Engine.forward template")
-            template = template.contiguous()
-            if tuple(template.shape) != (B, 1, L):
-                raise ValueError(f"expected template of shape {(B, 1, L)}, got {tuple(template.shape)}")
-            tptr = template.data_ptr()
+        template, tptr = _exact(template, "Engine.forward template", "template", (B, 1, L))
         nptr = None
         if noise is not None:
             _require_cuda(noise, "Engine.forward noise")
@@ -289,20 +353,41 @@ class Engine:
                 raise ValueError(f"expected {self.noise_elems(B, T)} fp32 noise samples, got {noise.numel()} ({noise.dtype})")
             nptr = noise.data_ptr()
         need = self.workspace_bytes(B, T)
-        with self._lock, torch.cuda.device(x.device):
+
+        def launch(stream: int) -> int:
             if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != x.device:
                 if self._done is not None:
                     self._done.synchronize()   # the old workspace goes back to the caching allocator: nothing may still use it
                 self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
-            cur, run = self._order_begin(x.device)
-            check(self._launch(x, tptr, nptr, out, B, T, int(run.cuda_stream)))
-            self._order_end(cur, run)
+            return self._launch(x, tptr, nptr, out, B, T, stream)
+        self._enqueue(x.device, launch)
         return out
 
+    def _input(self, x: torch.Tensor, what: str):
+        """The ``(B, C_in, T)`` input of ``what`` -> (x made contiguous, B, T)."""
+        _require_cuda(x, what)
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError(f"expected input of shape (B, {self.in_channels}, T), got {tuple(x.shape)}")
+        return x.contiguous(), x.shape[0], x.shape[2]
+
+    def _enqueue(self, device, launch, owner: "_Handle | None" = None, eager: bool = False) -> None:
+        """Every call that enqueues work on this engine (``forward``, ``forward_ragged``, ``Stream.push`` / ``flush``, ``SessionPool.step``):
+        under the lock and the device guard, ``launch(stream)`` -> fv_status runs between ``_order_begin`` and ``_order_end``.  ``owner``: the
+        open handle whose workspace the call uses; its ``_done`` is recorded after the call.  A refused call records nothing."""
+        with self._lock, torch.cuda.device(device):
+            if owner is not None:
+                owner._check_open()
+            cur, run = self._order_begin(device, eager)
+            check(launch(int(run.cuda_stream)))
+            self._order_end(cur, run)
+            if owner is not None:
+                if owner._done is None:
+                    owner._done = torch.cuda.Event()
+                owner._done.record(run)
+
     def _order_begin(self, device, eager: bool = False):
-        """Under ``self._lock``: (the caller's stream, the stream to enqueue on), the latter ordered after the engine's previous call.  Every
-        call that enqueues work on this engine (``forward``, ``Stream.push`` / ``flush``, ``forward_ragged``) goes through this pair.
-        ``eager``: the call enqueues its kernels eagerly whatever the replay setting (``forward_ragged``)."""
+        """Under ``self._lock``: (the caller's stream, the stream to enqueue on), the latter ordered after the engine's previous call
+        (``_enqueue``).  ``eager``: the call enqueues its kernels eagerly whatever the replay setting (``forward_ragged``)."""
         cur = torch.cuda.current_stream(device)
         run = cur
         if cur.cuda_stream == 0 and (eager or _SIDE_STREAM_FOR_DEFAULT or not self.graph_replay):
@@ -359,12 +444,8 @@ class Engine:
         """``x``: ``(B, C_in, T_max)`` with ``lengths[b]`` valid frames in row ``b`` (host integers) -> ``(B, C_out, T_max * hop)``: the samples
         ``[0, lengths[b] * hop)`` of row ``b`` are the clip's own forward, the rest is 0.0, and whatever the padding of ``x`` holds (NaN
         included) is never read.  Without ``plan`` the engine keeps the plan of the last ``(lengths, T_max)`` it saw."""
-        _require_cuda(x, "Engine.forward_ragged")
-        if x.dim() != 3 or x.shape[1] != self.in_channels:
-            raise ValueError(f"expected input of shape (B, {self.in_channels}, T), got {tuple(x.shape)}")
-        x = x.contiguous()
-        B, _, T = x.shape
-        lengths = [int(t) for t in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        x, B, T = self._input(x, "Engine.forward_ragged")
+        lengths = _int_list(lengths)
         if len(lengths) != B:
             raise ValueError(f"{len(lengths)} lengths for a batch of {B}")
         if plan is None:
@@ -380,22 +461,9 @@ class Engine:
             out = torch.empty((B, self.out_channels, L), dtype=torch.float32, device=x.device)
         elif tuple(out.shape) != (B, self.out_channels, L) or not out.is_contiguous():
             raise ValueError(f"expected a contiguous out of shape {(B, self.out_channels, L)}, got {tuple(out.shape)}")
-        tptr = None
-        if template is not None:
-            _require_cuda(template, "Engine.forward_ragged template")
-            template = template.contiguous()
-            if tuple(template.shape) != (B, 1, L):
-                raise ValueError(f"expected template of shape {(B, 1, L)}, got {tuple(template.shape)}")
-            tptr = template.data_ptr()
-        with self._lock, torch.cuda.device(x.device):
-            plan._check_open()
-            cur, run = self._order_begin(x.device, eager=True)
-            check(self._lib.fv_ragged_forward(plan._h, x.data_ptr(), tptr, out.data_ptr(), plan._ws.data_ptr(), plan._ws.numel() * 4,
-                                              int(run.cuda_stream)))
-            self._order_end(cur, run)
-            if plan._done is None:
-                plan._done = torch.cuda.Event()
-            plan._done.record(run)
+        template, tptr = _exact(template, "Engine.forward_ragged template", "template", (B, 1, L))
+        self._enqueue(x.device, lambda stream: self._lib.fv_ragged_forward(plan._h, x.data_ptr(), tptr, out.data_ptr(), plan._ws.data_ptr(),
+                                                                          plan._ws.numel() * 4, stream), owner=plan, eager=True)
         return out
 
     def forward_list(self, mels, templates=None) -> list[torch.Tensor]:
@@ -443,34 +511,28 @@ class Engine:
         return json.loads(buf.value.decode())
 
 
-class Stream:
+class Stream(_EngineHandle):
     """Streaming synthesis on an ``Engine`` (``fv_stream``, include/fishvoc.h): ``push`` mel chunks of ``(B, C_in, n)``, get the audio of every
     frame once ``lookahead_frames`` more have arrived; ``flush`` emits the rest at the utterance's end.  Each call returns a
     ``(B, C_out, k * hop)`` tensor (``k`` may be 0).  The emission rule is ``vocoder_amd.streaming``.  Calls are ordered like ``Engine.forward``
     (torch's current stream, the engine's lock and events); the stream owns its workspace, so forwards and other streams on the same engine may
     be interleaved with it.  ``reset()`` starts the next utterance, ``close()`` frees the stream (also a context manager).  A stream dies with
     its engine: after ``Engine.close()`` — or a module's reload / ``.to()``, which rebuild the engine — its calls raise ``FishVocError``."""
+    _destroy, _ws_getter = "fv_stream_destroy", "fv_stream_workspace_bytes"
+    _closed = ("this stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
+               "the module): create a new stream")
 
     def __init__(self, engine: Engine, batch: int, max_chunk_frames: int, context_frames: int | None = None,
                  lookahead_frames: int | None = None):
-        self._engine = engine
-        self._lib = engine._lib
-        self._h = ctypes.c_void_p()
-        if not engine._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, "Engine.stream: the engine is closed")
+        self._attach(engine, "Engine.stream")
         cfg = _lib.StreamConfig(int(batch), int(max_chunk_frames), -1 if context_frames is None else int(context_frames),
                                 -1 if lookahead_frames is None else int(lookahead_frames))
         with torch.cuda.device(engine.device):
             check(self._lib.fv_stream_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h)))
-            self._ws = torch.empty((int(self._lib.fv_stream_workspace_bytes(self._h)) + 3) // 4, dtype=torch.float32, device=engine.device)
-        self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
-        self.reach_frames = engine.reach_frames
-        self.context_frames = self.reach_frames if context_frames is None else int(context_frames)
-        self.lookahead_frames = self.reach_frames if lookahead_frames is None else int(lookahead_frames)
-        self.hop = engine.output_length(1)
-        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
+            self._alloc_workspace()
+        self.batch = int(batch)
+        self._ring_attrs(max_chunk_frames, context_frames, lookahead_frames)
         self._F = self._E = 0
-        self._done: torch.cuda.Event | None = None
 
     # -- counters (host-side: reading them never synchronises) --
     @property
@@ -487,16 +549,6 @@ class Stream:
         self._check_open()
         return int(self._lib.fv_stream_pending_frames(self._h))
 
-    @property
-    def workspace_bytes(self) -> int:
-        self._check_open()
-        return int(self._lib.fv_stream_workspace_bytes(self._h))
-
-    def _check_open(self) -> None:
-        if not self._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, "this stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
-                                                  "the module): create a new stream")
-
     def push(self, mel: torch.Tensor, template: torch.Tensor | None = None) -> torch.Tensor:
         """``mel``: ``(B, C_in, n)``, ``n <= max_chunk_frames``; ``template``: ``(B, 1, n * hop)`` for a use_template generator."""
         self._check_open()
@@ -505,13 +557,7 @@ class Stream:
             raise ValueError(f"expected a mel chunk of shape ({self.batch}, {self.in_channels}, n), got {tuple(mel.shape)}")
         mel = mel.contiguous()
         n = int(mel.shape[2])
-        tptr = None
-        if template is not None:
-            _require_cuda(template, "Stream.push template")
-            template = template.contiguous()
-            if tuple(template.shape) != (self.batch, 1, n * self.hop):
-                raise ValueError(f"expected a template chunk of shape {(self.batch, 1, n * self.hop)}, got {tuple(template.shape)}")
-            tptr = template.data_ptr()
+        template, tptr = _exact(template, "Stream.push template", "a template chunk", (self.batch, 1, n * self.hop))
         return self._call(mel, tptr, n, flush=False)
 
     def flush(self) -> torch.Tensor:
@@ -522,24 +568,17 @@ class Stream:
     def _call(self, mel, tptr, n: int, flush: bool) -> torch.Tensor:
         F, _, E2 = streaming.step(self._F, self._E, n, self.context_frames, self.lookahead_frames, flush)
         k = E2 - self._E if (flush or n <= self.max_chunk_frames) else 0
-        eng = self._engine
-        dev = eng.device
+        dev = self._engine.device
         out = torch.empty((self.batch, self.out_channels, k * self.hop), dtype=torch.float32, device=dev)
         got = ctypes.c_int64(0)
-        with eng._lock, torch.cuda.device(dev):
-            self._check_open()
-            cur, run = eng._order_begin(dev)
+
+        def launch(stream: int) -> int:
             if flush:
-                st = self._lib.fv_stream_flush(self._h, out.data_ptr() if k else None, ctypes.byref(got), self._ws.data_ptr(),
-                                               self._ws.numel() * 4, int(run.cuda_stream))
-            else:
-                st = self._lib.fv_stream_push(self._h, mel.data_ptr(), tptr, n, out.data_ptr() if k else None, ctypes.byref(got),
-                                              self._ws.data_ptr(), self._ws.numel() * 4, int(run.cuda_stream))
-            check(st)
-            eng._order_end(cur, run)
-            if self._done is None:
-                self._done = torch.cuda.Event()
-            self._done.record(run)
+                return self._lib.fv_stream_flush(self._h, out.data_ptr() if k else None, ctypes.byref(got), self._ws.data_ptr(),
+                                                 self._ws.numel() * 4, stream)
+            return self._lib.fv_stream_push(self._h, mel.data_ptr(), tptr, n, out.data_ptr() if k else None, ctypes.byref(got),
+                                            self._ws.data_ptr(), self._ws.numel() * 4, stream)
+        self._engine._enqueue(dev, launch, owner=self)
         if got.value != k:
             raise RuntimeError(f"stream emitted {got.value} frames where the emission rule says {k}")
         self._F, self._E = F, E2
@@ -551,54 +590,28 @@ class Stream:
         check(self._lib.fv_stream_reset(self._h))
         self._F = self._E = 0
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if self._done is not None:
-                self._done.synchronize()    # the ring and the workspace may still be in use on the device
-            self._lib.fv_stream_destroy(self._h)
-            self._h = ctypes.c_void_p()
-            self._ws = None
 
-    def __enter__(self) -> "Stream":
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SessionPool:
+class SessionPool(_EngineHandle):
     """Streaming sessions that advance independently on an ``Engine`` (``fv_pool``, include/fishvoc.h).  ``step(items)`` takes
     ``(session, mel, flush)`` or ``(session, mel, flush, template)`` tuples — ``mel``: ``(C_in, n)`` with ``n <= max_chunk_frames``, or ``None``
     for no frames; ``flush``: the utterance ends with these frames — and returns one ``(C_out, k * hop)`` tensor per item (``k`` may be 0): the
     frames that session emits in this step.  A session appears at most once per step.  After its flush a session refuses items until
     ``reset(session)``.  The whole step is checked before anything moves: a refused step leaves every session as it was.  Calls are ordered like
     ``Stream.push``; the pool owns its workspace.  A pool dies with its engine, like a ``Stream``."""
+    _destroy, _ws_getter = "fv_pool_destroy", "fv_pool_workspace_bytes"
+    _closed = ("this session pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or "
+               ".to() on the module): create a new pool")
 
     def __init__(self, engine: Engine, sessions: int, max_chunk_frames: int, context_frames: int | None = None,
                  lookahead_frames: int | None = None):
-        self._engine = engine
-        self._lib = engine._lib
-        self._h = ctypes.c_void_p()
-        self._done: torch.cuda.Event | None = None
-        if not engine._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, "Engine.session_pool: the engine is closed")
+        self._attach(engine, "Engine.session_pool")
         cfg = _lib.PoolConfig(int(sessions), int(max_chunk_frames), -1 if context_frames is None else int(context_frames),
                               -1 if lookahead_frames is None else int(lookahead_frames))
         with torch.cuda.device(engine.device):
             check(self._lib.fv_pool_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h)))
-            self._ws = torch.empty((int(self._lib.fv_pool_workspace_bytes(self._h)) + 3) // 4, dtype=torch.float32, device=engine.device)
-        self.sessions, self.max_chunk_frames = int(sessions), int(max_chunk_frames)
-        self.reach_frames = engine.reach_frames
-        self.context_frames = self.reach_frames if context_frames is None else int(context_frames)
-        self.lookahead_frames = self.reach_frames if lookahead_frames is None else int(lookahead_frames)
-        self.hop = engine.output_length(1)
-        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
+            self._alloc_workspace()
+        self.sessions = int(sessions)
+        self._ring_attrs(max_chunk_frames, context_frames, lookahead_frames)
         self.state = _sessions.PoolState(self.sessions, self.max_chunk_frames, self.context_frames, self.lookahead_frames)
 
     # -- counters (host-side: reading them never synchronises) --
@@ -613,16 +626,6 @@ class SessionPool:
         self._check_open()
         return int(self._lib.fv_pool_pending_frames(self._h, int(session)))
 
-    @property
-    def workspace_bytes(self) -> int:
-        self._check_open()
-        return int(self._lib.fv_pool_workspace_bytes(self._h))
-
-    def _check_open(self) -> None:
-        if not self._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, "this session pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or "
-                                                  ".to() on the module): create a new pool")
-
     def step(self, items) -> list[torch.Tensor]:
         """One step for ``items`` (see the class); returns each item's emitted audio ``(C_out, k * hop)``, views of one output buffer."""
         self._check_open()
@@ -636,10 +639,7 @@ class SessionPool:
                 if mel.dim() != 2 or mel.shape[0] != self.in_channels:
                     raise ValueError(f"expected a mel chunk of shape ({self.in_channels}, n), got {tuple(mel.shape)}")
                 n = int(mel.shape[1])
-                if tt is not None:
-                    _require_cuda(tt, "SessionPool.step template")
-                    if tuple(tt.shape) != (1, n * self.hop):
-                        raise ValueError(f"expected a template chunk of shape {(1, n * self.hop)}, got {tuple(tt.shape)}")
+                _exact(tt, "SessionPool.step template", "a template chunk", (1, n * self.hop))
             meta.append((int(s), n, bool(flush)))
         in_frames = max((n for _, n, _ in meta), default=0)
         chunks = tmpl = None
@@ -670,13 +670,10 @@ class SessionPool:
             if chunks.dim() != 3 or chunks.shape[0] != count or chunks.shape[1] != self.in_channels or not chunks.is_contiguous():
                 raise ValueError(f"expected contiguous chunks of shape ({count}, {self.in_channels}, in_frames), got {tuple(chunks.shape)}")
             in_frames = int(chunks.shape[2])
-        if templates is not None:
-            _require_cuda(templates, "SessionPool.step_padded templates")
-            if tuple(templates.shape) != (count, 1, in_frames * self.hop) or not templates.is_contiguous():
-                raise ValueError(f"expected contiguous templates of shape {(count, 1, in_frames * self.hop)}, got {tuple(templates.shape)}")
+        _, tptr = _exact(templates, "SessionPool.step_padded templates", "contiguous templates", (count, 1, in_frames * self.hop),
+                         make_contiguous=False)
         plan = self.state.plan(items)                             # sizes the output before anything is launched; refuses what the library would
-        eng = self._engine
-        dev = eng.device
+        dev = self._engine.device
         if out is None:
             out = torch.empty((count, self.out_channels, max(plan.emit_frames, default=0) * self.hop), dtype=torch.float32, device=dev)
         elif out.dim() != 3 or out.shape[0] != count or out.shape[1] != self.out_channels or out.shape[2] % self.hop or not out.is_contiguous():
@@ -684,17 +681,10 @@ class SessionPool:
         out_frames = int(out.shape[2]) // self.hop
         arr = (_lib.PoolItem * max(count, 1))(*[_lib.PoolItem(s, n, int(f)) for s, n, f in items])
         got = (ctypes.c_int64 * max(count, 1))()
-        with eng._lock, torch.cuda.device(dev):
-            self._check_open()
-            cur, run = eng._order_begin(dev)
-            check(self._lib.fv_pool_step(self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None,
-                                         templates.data_ptr() if templates is not None and templates.numel() else None, in_frames,
-                                         out.data_ptr() if out.numel() else None, out_frames, got, self._ws.data_ptr(), self._ws.numel() * 4,
-                                         int(run.cuda_stream)))
-            eng._order_end(cur, run)
-            if self._done is None:
-                self._done = torch.cuda.Event()
-            self._done.record(run)
+        self._engine._enqueue(dev, lambda stream: self._lib.fv_pool_step(
+            self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None,
+            tptr if count and in_frames else None, in_frames, out.data_ptr() if out.numel() else None, out_frames, got, self._ws.data_ptr(),
+            self._ws.numel() * 4, stream), owner=self)
         emit = [int(got[i]) for i in range(count)]
         self.state.apply(items, plan)                             # the Python counters move as the library's did
         if plan.emit_frames != emit:
@@ -707,47 +697,24 @@ class SessionPool:
         check(self._lib.fv_pool_reset(self._h, int(session)))
         self.state.reset(int(session))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if self._done is not None:
-                self._done.synchronize()    # the rings and the workspace may still be in use on the device
-            self._lib.fv_pool_destroy(self._h)
-            self._h = ctypes.c_void_p()
-            self._ws = None
 
-    def __enter__(self) -> "SessionPool":
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RaggedPlan:
+class RaggedPlan(_EngineHandle):
     """The plan of one ragged batch on an ``Engine`` (``fv_ragged``, include/fishvoc.h): owns the device window table and the workspace of
     ``Engine.forward_ragged`` for these ``lengths`` and ``t_max``.  ``windows`` / ``groups`` are what the library planned (the rule in plain
     Python: ``vocoder_amd.ragged``).  A plan dies with its engine, like a ``Stream``."""
+    _destroy, _ws_getter = "fv_ragged_destroy", "fv_ragged_workspace_bytes"
+    _closed = "this ragged plan is closed (its engine was closed or rebuilt): create a new plan"
 
     def __init__(self, engine: Engine, lengths, t_max: int | None = None, launch_frames: int = 0, max_groups: int = 0):
         from .ragged import Window
-        self._engine = engine
-        self._lib = engine._lib
-        self._h = ctypes.c_void_p()
-        self._done: torch.cuda.Event | None = None
-        if not engine._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, "Engine.ragged_plan: the engine is closed")
-        self.lengths = [int(t) for t in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        self._attach(engine, "Engine.ragged_plan")
+        self.lengths = _int_list(lengths)
         self.t_max = int(max(self.lengths, default=0) if t_max is None else t_max)
         arr = (ctypes.c_int32 * max(len(self.lengths), 1))(*self.lengths)
         with torch.cuda.device(engine.device):
             check(self._lib.fv_ragged_create(engine._h, arr, len(self.lengths), self.t_max, int(launch_frames), int(max_groups),
                                              ctypes.byref(self._h)))
-            self._ws = torch.empty((int(self._lib.fv_ragged_workspace_bytes(self._h)) + 3) // 4 + 1, dtype=torch.float32, device=engine.device)
+            self._alloc_workspace(spare=1)
         n = int(self._lib.fv_ragged_windows(self._h, None, 0))
         buf = (_lib.RaggedWindow * max(n, 1))()
         self._lib.fv_ragged_windows(self._h, buf, n)
@@ -759,38 +726,10 @@ class RaggedPlan:
             self.groups.append((b.value, f.value))
         self.hop = engine.output_length(1)
 
-    @property
-    def workspace_bytes(self) -> int:
-        self._check_open()
-        return int(self._lib.fv_ragged_workspace_bytes(self._h))
 
-    def _check_open(self) -> None:
-        if not self._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, "this ragged plan is closed (its engine was closed or rebuilt): create a new plan")
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if self._done is not None:
-                self._done.synchronize()    # the table and the workspace may still be in use on the device
-            self._lib.fv_ragged_destroy(self._h)
-            self._h = ctypes.c_void_p()
-            self._ws = None
-
-    def __enter__(self) -> "RaggedPlan":
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FusedConv:
+class FusedConv(_Handle):
     """One fused conv layer (``fv_conv``): pre-act -> Conv1d/ConvTranspose1d -> bias [+res] -> post-act."""
+    _destroy = "fv_conv_destroy"
 
     def __init__(self, weight, bias=None, *, transposed=False, dilation=1, padding=0, stride=1,
                  pre_act=_lib.FV_ACT_NONE, post_act=_lib.FV_ACT_NONE, act_slope=0.0):
@@ -859,14 +798,3 @@ class FusedConv:
             check(self._lib.fv_conv_pair_forward(self._h, c2._h, x.data_ptr(), out.data_ptr(), B, T,
                                                  _stream_ptr(x.device)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.fv_conv_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
