@@ -554,6 +554,73 @@ FV_API fv_status fv_resample_stream_reset(fv_resample_stream* s);
 /* Call it before fv_resample_destroy of its resampler, once the stream's work has finished. */
 FV_API void fv_resample_stream_destroy(fv_resample_stream* s);
 
+/* -------- audio in: the log-mel front-end on rows of different lengths and on chunks of a stream.  Replaces calling
+ *          `LogMelSpectrogram.forward` (data/transforms/spectrogram.py:25-104) on one whole, equal-length tensor per file, as the wav branch of
+ *          test.py:64-71 does (zero padding, then `mel_transforms.input`); the reference has neither a ragged nor a streaming form.  --------
+ *
+ * These entries take a FV_MODEL_LOGMEL engine (any other: FV_ERR_UNSUPPORTED).  fv_stream_create, fv_ragged_* and fv_pool_* keep refusing such
+ * an engine: they window FRAMES under a reach rule, while the front-end windows SAMPLES under the framing rule below.
+ * pad_l = (win_length - hop) / 2, pad_r = (win_length - hop + 1) / 2 (spectrogram.py:30-33).  Frame f of a row reads the wave indices
+ * [f hop - pad_l, f hop - pad_l + n_fft), reflected at 0 and at the row's last sample.  Only the first step differs from fv_forward: one kernel
+ * writes the polyphase signal of the frames [f0, f0 + n) with per-row edges (samples at or past a row's end are never loaded), and the
+ * forward's own STFT conv, magnitude and filterbank conv run behind it.  With fv_set_batch_invariant(e, 1) every output column is one
+ * fixed-order sum, so a frame's values do not depend on the call that produced it: a row inside a ragged batch, the same row through
+ * fv_forward and any chunking of it through a stream agree bit for bit.  All calls enqueue eagerly and leave the captured graphs of fv_forward
+ * alone. */
+
+/* Pure host (no engine, no GPU), as fv_ragged_plan and fv_resample_design are; stand in for the frame count that torch.stft(center=False) derives
+ * inside spectrogram.py:25-56 / test.py:64-71.  Frames of a whole row of L samples: 1 + (L + pad_l + pad_r - n_fft) / hop, 0 when the padded
+ * row is shorter than one frame (or the config is unusable). */
+FV_API int64_t fv_logmel_frames(const fv_logmel_config* cfg, int64_t L);
+/* Frames that need no sample at or after N, i.e. that a stream can emit once N samples have arrived (spectrogram.py:25-56 / test.py:64-71 see
+ * whole files only): 1 + (N + pad_l - n_fft) / hop once N + pad_l >= n_fft, else 0.  Never above fv_logmel_frames(cfg, N). */
+FV_API int64_t fv_logmel_frames_ready(const fv_logmel_config* cfg, int64_t N);
+
+/* One call for rows of different lengths (replaces one spectrogram.py:25-104 call per file, test.py:64-71).  d_wave: `batch` rows, row b at
+ * d_wave + b * row_stride (floats, >= L_max) holding host_lengths[b] <= L_max samples; d_out: (batch, C_out, fv_logmel_frames(L_max)) fp32;
+ * fv_workspace_bytes(e, batch, L_max) bytes of workspace are enough.  Row b holds its own log-mel in the columns [0, T_b),
+ * T_b = fv_logmel_frames(lengths[b]) — within 2e-4 of the reference on the log values, the front-end's bar — and exactly 0.0f after them; a
+ * length of 0 is an empty row, all zeros.  Samples at or after lengths[b] (NaN included) are never loaded.  Any other length that fv_forward
+ * alone would refuse (no frame, or not longer than the reflect padding), a negative length and one above L_max get FV_ERR_INVALID with the
+ * row named; everything is validated before anything is enqueued.  Known cost: every row's convs run over T_max = fv_logmel_frames(L_max)
+ * columns, so the work is batch * T_max, not the sum of T_b — group rows of similar length into one call.  Asynchronous on `stream`; ordered
+ * like fv_forward on its engine. */
+FV_API fv_status fv_logmel_ragged_forward(fv_engine* e, const float* d_wave, int64_t row_stride, const int32_t* host_lengths, int32_t batch,
+                                          int32_t L_max, float* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Streaming form (no reference counterpart: spectrogram.py:25-104 / test.py:64-71 take whole files): `batch` rows advance in lockstep.  Host
+ * counters: N samples received, E frames emitted.  A push sets N += c and emits the frames [E, fv_logmel_frames_ready(N)); the flush emits
+ * [E, fv_logmel_frames(N)) against the rows' true end (right reflection) and then refuses pushes (FV_ERR_STATE) until
+ * fv_logmel_stream_reset.  A flush at N = 0 emits nothing; a flush of an utterance too short for one frame or for the reflection is
+ * FV_ERR_INVALID.  A refused call changes nothing.  Latency: a frame comes out pad_r samples after its own hop has arrived — 768 samples, 17 ms,
+ * at 44100 Hz / n_fft 2048 / hop 512.  No call synchronises. */
+typedef struct fv_logmel_stream fv_logmel_stream;
+
+/* The stream's only device allocation, made here (spectrogram.py:25-104 / test.py:64-71 keep no state) and freed by fv_logmel_stream_destroy: two
+ * (batch, n_fft) carry buffers used in turn, so that no launch writes the carry and reads it back.  After a call the carry covers the samples
+ * [max(0, E hop - pad_l), N) that later frames still need: fewer than n_fft of them.  max_chunk_samples: the largest c of one push. */
+FV_API fv_status fv_logmel_stream_create(fv_engine* e, int32_t batch, int32_t max_chunk_samples, fv_logmel_stream** out);
+/* Bytes of device scratch every push / flush needs (256-byte aligned): the front-end's workspace (spectrogram.py:25-104 / test.py:64-71 allocate
+ * theirs per call) for the most frames one call can emit. */
+FV_API size_t fv_logmel_stream_workspace_bytes(const fv_logmel_stream* s);
+/* N - max(0, E hop - pad_l): samples received that frames not yet emitted still read (what spectrogram.py:25-104 / test.py:64-71 would hold as
+ * the file's tail). */
+FV_API int64_t fv_logmel_stream_pending_samples(const fv_logmel_stream* s);
+/* d_wave: (batch, c) with row stride row_stride, c <= max_chunk_samples (else FV_ERR_INVALID) — the next samples of what test.py:64-71 hands
+ * spectrogram.py:25-104 whole; d_out: (batch, C_out, k) fp32, contiguous, k = fv_logmel_frames_ready(N + c) - E known before the call; k may be
+ * 0, then d_out may be NULL.  *frames_out receives k.  c = 0 is a no-op.  Asynchronous on `stream`; calls on one stream must be ordered. */
+FV_API fv_status fv_logmel_stream_push(fv_logmel_stream* s, const float* d_wave, int64_t row_stride, int32_t c, float* d_out,
+                                       int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Emits the frames [E, fv_logmel_frames(N)) against the utterance's end, the right edge of spectrogram.py:25-104 / test.py:64-71;
+ * d_out: (batch, C_out, fv_logmel_frames(N) - E). */
+FV_API fv_status fv_logmel_stream_flush(fv_logmel_stream* s, float* d_out, int64_t* frames_out, void* d_workspace, size_t workspace_bytes,
+                                        void* stream);
+/* N = E = 0 for the next utterance (the next file of test.py:64-71 / spectrogram.py:25-104); the carry buffers are kept. */
+FV_API fv_status fv_logmel_stream_reset(fv_logmel_stream* s);
+/* Frees the carry (call it before fv_destroy of its engine, once the stream's work has finished); spectrogram.py:25-104 / test.py:64-71 have
+ * nothing to free. */
+FV_API void fv_logmel_stream_destroy(fv_logmel_stream* s);
+
 /* -------- single fused conv layer (the hot kernel on its own; used by the parity tests and the roofline
  *          bench).  Stands in for one weight-normed nn.Conv1d / nn.ConvTranspose1d call plus the elementwise
  *          ops the reference runs around it (F.silu before, residual add after: hifigan.py:101-108). -------- */

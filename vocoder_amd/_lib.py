@@ -48,6 +48,8 @@ EXPORTS = (
     "fv_resample_design", "fv_resample_input_tile", "fv_resample_create", "fv_resample_destroy", "fv_resample_output_length",
     "fv_resample_forward", "fv_resample_check_lengths", "fv_resample_stream_create", "fv_resample_stream_pending", "fv_resample_stream_push",
     "fv_resample_stream_flush", "fv_resample_stream_reset", "fv_resample_stream_destroy",
+    "fv_logmel_frames", "fv_logmel_frames_ready", "fv_logmel_ragged_forward", "fv_logmel_stream_create", "fv_logmel_stream_workspace_bytes",
+    "fv_logmel_stream_pending_samples", "fv_logmel_stream_push", "fv_logmel_stream_flush", "fv_logmel_stream_reset", "fv_logmel_stream_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -279,6 +281,27 @@ def lib() -> ctypes.CDLL:
     L.fv_resample_stream_reset.restype = _i32
     L.fv_resample_stream_destroy.argtypes = [vp]
     L.fv_resample_stream_destroy.restype = None
+    lcp = ctypes.POINTER(LogMelConfig)
+    L.fv_logmel_frames.argtypes = [lcp, i64]
+    L.fv_logmel_frames.restype = i64
+    L.fv_logmel_frames_ready.argtypes = [lcp, i64]
+    L.fv_logmel_frames_ready.restype = i64
+    L.fv_logmel_ragged_forward.argtypes = [vp, vp, i64, i32p, _i32, _i32, vp, vp, ctypes.c_size_t, vp]
+    L.fv_logmel_ragged_forward.restype = _i32
+    L.fv_logmel_stream_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_logmel_stream_create.restype = _i32
+    L.fv_logmel_stream_workspace_bytes.argtypes = [vp]
+    L.fv_logmel_stream_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_logmel_stream_pending_samples.argtypes = [vp]
+    L.fv_logmel_stream_pending_samples.restype = i64
+    L.fv_logmel_stream_push.argtypes = [vp, vp, i64, _i32, vp, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_logmel_stream_push.restype = _i32
+    L.fv_logmel_stream_flush.argtypes = [vp, vp, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_logmel_stream_flush.restype = _i32
+    L.fv_logmel_stream_reset.argtypes = [vp]
+    L.fv_logmel_stream_reset.restype = _i32
+    L.fv_logmel_stream_destroy.argtypes = [vp]
+    L.fv_logmel_stream_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

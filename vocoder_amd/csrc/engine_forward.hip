@@ -382,32 +382,45 @@ fv_status fv_engine::run_head(const float* d_in, float* d_out, int B, int T, flo
     return FV_OK;
 }
 
+// The front-end's workspace for B rows of T frames: [Yp (B, hop, T + taps - 1) | Sp (B, 2 nb, T) | Mg (B, nb, T)], the first two rounded to 64 floats
+fv_engine::LogmelParts fv_engine::logmel_carve(float* ws, int B, int T) const {
+    const size_t n_yp = ((size_t)B * mel.cfg.hop_length * (T + mel.taps - 1) + 63) / 64 * 64, n_sp = ((size_t)B * 2 * mel.nb * T + 63) / 64 * 64;
+    return {ws, ws + n_yp, ws + n_yp + n_sp};
+}
+size_t fv_engine::logmel_ws_elems(int B, int T) const {
+    return ((size_t)B * cfg.mel.hop_length * ((size_t)T + mel.taps) + 64) + ((size_t)B * 3 * mel.nb * T + 128);
+}
+
 fv_status fv_engine::run_logmel(const float* d_in, float* d_out, int B, int L, float* ws, hipStream_t s) {
-    const int hop = mel.cfg.hop_length, nb = mel.nb;
+    const int hop = mel.cfg.hop_length;
     const int T = mel.frames(L);
     const int TP = T + mel.taps - 1;
-    const size_t n_yp = ((size_t)B * hop * TP + 63) / 64 * 64, n_sp = ((size_t)B * 2 * nb * T + 63) / 64 * 64;
-    float* Yp = ws;
-    float* Sp = ws + n_yp;
-    float* Mg = Sp + n_sp;
+    const LogmelParts p = logmel_carve(ws, B, T);
     FV_PROF(s, "polyphase_reflect", 0.0, 8.0 * B * (double)hop * TP,
-            launch_polyphase_reflect(d_in, Yp, B, L, hop, TP, mel.pad_l, mel.pad_r, s));
+            launch_polyphase_reflect(d_in, p.Yp, B, L, hop, TP, mel.pad_l, mel.pad_r, s));
+    return run_logmel_tail(p, d_out, B, T, s);
+}
+
+// Everything behind the polyphase signal: STFT conv -> magnitude -> filterbank conv with log(clamp).  Shared by the whole forward, the
+// ragged call and the stream (engine_logmel.hip): T frames out of Yp's T + taps - 1 slots
+fv_status fv_engine::run_logmel_tail(const LogmelParts& p, float* d_out, int B, int T, hipStream_t s) {
+    const int nb = mel.nb;
     fv_status st;
     ConvRun r;
     r.batch = B;
-    r.t_in = TP;
-    r.x = Yp;
-    r.y = Sp;
+    r.t_in = T + mel.taps - 1;
+    r.x = p.Yp;
+    r.y = p.Sp;
     if ((st = conv_layer_run(mel.stft, r, s))) return st;
     if (mel.cfg.n_mels == 0) {   // LinearSpectrogram alone (spectrogram.py:25-56): the magnitude is the result
-        FV_PROF(s, "magnitude", 4.0 * B * nb * T, 12.0 * B * nb * T, launch_magnitude(Sp, d_out, B, nb, T, s));
+        FV_PROF(s, "magnitude", 4.0 * B * nb * T, 12.0 * B * nb * T, launch_magnitude(p.Sp, d_out, B, nb, T, s));
         return FV_OK;
     }
-    FV_PROF(s, "magnitude", 4.0 * B * nb * T, 12.0 * B * nb * T, launch_magnitude(Sp, Mg, B, nb, T, s));
+    FV_PROF(s, "magnitude", 4.0 * B * nb * T, 12.0 * B * nb * T, launch_magnitude(p.Sp, p.Mg, B, nb, T, s));
     r = ConvRun();
     r.batch = B;
     r.t_in = T;
-    r.x = Mg;
+    r.x = p.Mg;
     r.y = d_out;
     r.post_act = FV_ACT_LOG_CLAMP;   // compress(): log(clamp(x, 1e-5))  (spectrogram.py:93-94)
     return conv_layer_run(mel.mel, r, s);
@@ -465,9 +478,7 @@ static size_t whole_workspace_bytes(const fv_engine* e, int32_t batch, int32_t t
         case FV_MODEL_CONVNEXT: elems = cnx_ws_elems(e, batch, t_in); break;
         case FV_MODEL_ISTFT_HEAD: elems = head_ws_elems(e, batch, t_in); break;
         case FV_MODEL_LOGMEL: {
-            const size_t T = (size_t)std::max(1, e->mel.frames(t_in));
-            elems = ((size_t)batch * e->cfg.mel.hop_length * (T + e->mel.taps) + 64) +
-                    ((size_t)batch * 3 * e->mel.nb * T + 128);
+            elems = e->logmel_ws_elems(batch, std::max(1, e->mel.frames(t_in)));
             break;
         }
         case FV_MODEL_REFINEGAN: elems = refine_ws_elems(e, batch, t_in); break;

@@ -496,6 +496,12 @@ struct fv_engine {
     fv_status build_head(const std::string& pfx);
     fv_status build_logmel(const std::string& pfx);
     fv_status run_logmel(const float* d_in, float* d_out, int B, int L, float* ws, hipStream_t s);
+    struct LogmelParts {
+        float *Yp, *Sp, *Mg;
+    };
+    LogmelParts logmel_carve(float* ws, int B, int T) const;
+    size_t logmel_ws_elems(int B, int T) const;   // floats that logmel_carve's parts span (what fv_workspace_bytes reports for T frames)
+    fv_status run_logmel_tail(const LogmelParts& p, float* d_out, int B, int T, hipStream_t s);
 
     fv_status build_refinegan();
     fv_status run_refinegan(const float* d_mel, float* d_out, int B, int T, float* ws, hipStream_t s);

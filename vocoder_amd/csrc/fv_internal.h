@@ -410,6 +410,23 @@ fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const 
 // y (rows, C, Ly) -> out (., C, out_frames): each entry's samples, then zeros to the row's end
 fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames,
                            int hop, hipStream_t s);
+// log-mel front-end on ragged rows and stream chunks (logmel_windows.hip; fv_logmel_ragged_forward, fv_logmel_stream_*): per-row values travel
+// BY VALUE, kLogmelRows rows per launch, as the session pool's tables do
+static constexpr int kLogmelRows = 32;
+struct LogmelRowBlock {
+    long long len[kLogmelRows];
+};
+// yp[b][r][tp] = sample (f0 + tp) hop + r - pad_l of row b, reflected at 0 and — where row_len[b] >= 0 (row_len NULL: no row's end is known) — at
+// the row's end, 0 past the padded row / from `avail` on; the sample is read from `chunk` (samples [chunk_origin, ...)) or from `carry`
+// (samples [carry_origin, chunk_origin)); either may be NULL only when it holds no sample of any row (refused otherwise)
+fv_status launch_logmel_window(const float* carry, long long carry_stride, long long carry_origin, const float* chunk, long long chunk_stride,
+                               long long chunk_origin, const long long* row_len, long long avail, float* yp, int B, long long f0, int hop,
+                               int TP, int pad_l, int pad_r, hipStream_t s);
+// y (B, C, T): columns >= row_cols[b] of row b set to 0.0f
+fv_status launch_zero_columns(float* y, const long long* row_cols, int B, int C, long long T, hipStream_t s);
+// next (B, H) = the samples [N2 - H, N2) of every row out of prev (B, H) = [N - H, N) and the chunk = [N, N2)
+fv_status launch_logmel_carry(const float* prev, float* next, const float* chunk, long long chunk_stride, int B, int H, long long N,
+                              long long N2, hipStream_t s);
 // rows [0,nb) = Re, [nbp, nbp+nb) = Im, zero padded to nbp = round_up(nb, 8)
 fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T, int nb, int nbp, hipStream_t s);
 // frames (B, n_fft, T) (already windowed by the synthesis basis) -> overlap-add, crop, divide by the envelope.

@@ -37,7 +37,59 @@ def melscale_fbanks_slaney(n_freqs: int, f_min: float, f_max: float, n_mels: int
     return (fb * (2.0 / (f_pts[2:n_mels + 2] - f_pts[:n_mels])).unsqueeze(0)).to(torch.float32)
 
 
-class LinearSpectrogram(_base.EngineModule):
+class _FrontEnd(_base.EngineModule):
+    """What both transforms add to the whole-tensor ``forward``: rows of different lengths and chunks of a stream (include/fishvoc.h
+    ``fv_logmel_*``; the framing rule: ``vocoder_amd.framing``).  They replace the frame-windowed ``forward_ragged`` / ``forward_list`` /
+    ``stream`` of the generators, which a front-end cannot have: it windows samples, not frames.  A session pool is not built: ``session_pool`` is the base's, and the engine refuses it."""
+
+    def frames(self, L: int) -> int:
+        """Frames of a whole row of ``L`` samples."""
+        return self._framing().frames(L)
+
+    def frames_ready(self, N: int) -> int:
+        """Frames that need no sample at or after ``N``."""
+        return self._framing().frames_ready(N)
+
+    def _framing(self):
+        from ...framing import Framing
+        return Framing(int(self.n_fft), int(self.win_length), int(self.hop_length))
+
+    def _ragged_engine(self, what: str):
+        b = next(self.buffers(), None)      # a front-end has buffers only (the window, the filterbank)
+        if b is None or not b.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.{what} needs the module on a HIP device (.to('cuda')); vocoder_amd has no CPU path")
+        if self.training:
+            raise RuntimeError(f"{type(self).__name__} is inference-only: call .eval() first")
+        return self.engine(b.device)
+
+    def forward_ragged(self, waves: torch.Tensor, lengths):
+        """``waves`` ``(B, L_max)`` or ``(B, 1, L_max)`` with ``lengths[b]`` valid samples per row -> ``(mel (B, C, frames(L_max)),
+        frame_lengths)``: row ``b`` holds its own result in ``[0, frame_lengths[b])`` and zeros after it; the padding of ``waves`` is never read."""
+        with torch.no_grad():
+            eng = self._ragged_engine("forward_ragged")
+            lengths = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            mel = eng.logmel_ragged(waves.to(torch.float32), lengths)
+            return mel, [eng.framing.frames(n) for n in lengths]
+
+    def forward_list(self, waves) -> list:
+        """A list of ``(L_i,)`` or ``(1, L_i)`` waveforms -> a list of ``(C, frames(L_i))`` views of one ``forward_ragged`` result."""
+        waves = [w.reshape(-1) for w in waves]
+        if not waves:
+            return []
+        lengths = [int(w.shape[0]) for w in waves]
+        x = torch.zeros((len(waves), max(max(lengths), 1)), dtype=torch.float32, device=waves[0].device)
+        for b, w in enumerate(waves):
+            x[b, :lengths[b]] = w
+        mel, fl = self.forward_ragged(x, lengths)
+        return [mel[b, :, :fl[b]] for b in range(len(waves))]
+
+    def stream(self, batch: int = 1, max_chunk_samples: int = 4096):
+        """The front-end chunk by chunk (``vocoder_amd.engine.LogMelStream``): ``push`` at most ``max_chunk_samples`` samples per row, ``flush``
+        at the utterance's end.  Reloading the weights or moving the module rebuilds the engine and closes its streams: create a new one then."""
+        return self._ragged_engine("stream").logmel_stream(batch, max_chunk_samples)
+
+
+class LinearSpectrogram(_FrontEnd):
     """Reference spectrogram.py:8-56: reflect-padded ``torch.stft(center=False)`` magnitude ``sqrt(re^2 + im^2 + 1e-6)``,
     ``forward(y (B, L) or (B, 1, L)) -> (B, n_fft/2+1, frames)``.  Same buffer name (``window``); runs on the log-mel
     engine with the filterbank stage switched off (``n_mels = 0``).  Inside LogMelSpectrogram it only holds the window."""
@@ -67,7 +119,7 @@ class _MelScaleBuffers(nn.Module):
         self.register_buffer("fb", fb)
 
 
-class LogMelSpectrogram(_base.EngineModule):
+class LogMelSpectrogram(_FrontEnd):
     def __init__(self, sample_rate=44100, n_fft=2048, win_length=2048, hop_length=512, n_mels=128, center=False,
                  f_min=0.0, f_max=None):
         super().__init__()

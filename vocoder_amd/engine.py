@@ -10,7 +10,7 @@ from typing import Mapping
 import numpy as np
 import torch
 
-from . import _lib, sessions as _sessions, streaming
+from . import _lib, framing as _framing, sessions as _sessions, streaming
 from ._lib import FishVocError, check  # noqa: F401
 
 _SIDE_STREAM_FOR_DEFAULT = os.environ.get("FV_DEFAULT_STREAM_SIDE", "0") == "1"   # experiments: see Engine.forward
@@ -279,6 +279,10 @@ class Engine(_Handle):
             except Exception:
                 self.close()
                 raise
+        self.model_kind = int(model_kind)
+        # the framing rule of a log-mel engine (vocoder_amd.framing); None for every other model
+        self.framing = (_framing.Framing(int(mel.n_fft), int(mel.win_length), int(mel.hop_length))
+                        if model_kind == _lib.FV_MODEL_LOGMEL and mel is not None else None)
         self.in_channels = self._lib.fv_input_channels(self._h)
         self.out_channels = self._lib.fv_output_channels(self._h)
         self._ws: torch.Tensor | None = None
@@ -487,6 +491,56 @@ class Engine(_Handle):
         y = self.forward_ragged(x, lengths, template=tt)
         return [y[b, :, :lengths[b] * hop] for b in range(len(mels))]
 
+    # -- log-mel front-end on ragged rows and on chunks (fv_logmel_*): the feature's own entry points; stream() / ragged_plan() / session_pool()
+    #    keep refusing a log-mel engine --
+    def _require_logmel(self, what: str) -> "_framing.Framing":
+        if self.framing is None:
+            raise FishVocError(_lib.FV_ERR_UNSUPPORTED, f"{what}: the engine is not a log-mel front-end (FV_MODEL_LOGMEL)")
+        return self.framing
+
+    def logmel_ragged(self, waves: torch.Tensor, lengths, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``waves``: ``(B, L_max)`` or ``(B, 1, L_max)`` with ``lengths[b]`` valid samples in row ``b`` (host integers) ->
+        ``(B, C_out, frames(L_max))``: row ``b`` holds its own log-mel in the columns ``[0, frames(lengths[b]))`` and 0.0 after them; a length of
+        0 is an empty row.  Samples at or after ``lengths[b]`` (NaN included) are never read.  Every row's convs run over ``frames(L_max)``
+        columns: the work is ``B * T_max``, not the sum of the rows' frames."""
+        fr = self._require_logmel("Engine.logmel_ragged")
+        _require_cuda(waves, "Engine.logmel_ragged")
+        if waves.dim() == 3 and waves.shape[1] == 1:
+            waves = waves[:, 0]
+        if waves.dim() != 2:
+            raise ValueError(f"expected waves of shape (B, L_max) or (B, 1, L_max), got {tuple(waves.shape)}")
+        waves = waves.contiguous()
+        B, L = int(waves.shape[0]), int(waves.shape[1])
+        lengths = _int_list(lengths)
+        if len(lengths) != B:
+            raise ValueError(f"{len(lengths)} lengths for a batch of {B}")
+        T = fr.frames(L)
+        if out is None:
+            out = torch.empty((B, self.out_channels, T), dtype=torch.float32, device=waves.device)
+        elif tuple(out.shape) != (B, self.out_channels, T) or not out.is_contiguous():
+            raise ValueError(f"expected a contiguous out of shape {(B, self.out_channels, T)}, got {tuple(out.shape)}")
+        if B == 0:
+            return out
+        arr = (ctypes.c_int32 * B)(*lengths)
+        need = self.workspace_bytes(B, max(L, 1))
+
+        def launch(stream: int) -> int:
+            if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != waves.device:
+                if self._done is not None:
+                    self._done.synchronize()
+                self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=waves.device)
+            return self._lib.fv_logmel_ragged_forward(self._h, waves.data_ptr(), max(L, 1), arr, B, L, out.data_ptr() if out.numel() else None,
+                                                      self._ws.data_ptr(), self._ws.numel() * 4, stream)
+        self._enqueue(waves.device, launch, eager=True)
+        return out
+
+    def logmel_stream(self, batch: int = 1, max_chunk_samples: int = 4096) -> "LogMelStream":
+        """The front-end as a stream (``LogMelStream``): ``batch`` rows in lockstep, pushed at most ``max_chunk_samples`` samples at a time."""
+        self._require_logmel("Engine.logmel_stream")
+        st = LogMelStream(self, batch, max_chunk_samples)
+        self._streams.add(st)
+        return st
+
     def _launch(self, x, tptr, nptr, out, B, T, stream: int) -> int:
         if nptr is not None:
             return self._lib.fv_forward_refinegan(self._h, x.data_ptr(), tptr, nptr, out.data_ptr(), B, T, self._ws.data_ptr(),
@@ -589,6 +643,87 @@ class Stream(_EngineHandle):
         self._check_open()
         check(self._lib.fv_stream_reset(self._h))
         self._F = self._E = 0
+
+
+class LogMelStream(_EngineHandle):
+    """The log-mel front-end chunk by chunk on a log-mel ``Engine`` (``fv_logmel_stream``, include/fishvoc.h): ``push`` a ``(B, c)`` or
+    ``(B, 1, c)`` chunk of samples, ``c <= max_chunk_samples``, and get the ``(B, C_out, k)`` frames that need no later sample (``k`` may be 0,
+    ``emit_count(c)`` says it beforehand); ``flush`` emits the rest against the utterance's true end and then refuses pushes until ``reset``.
+    The rule is ``vocoder_amd.framing``.  A frame comes out ``pad_r`` samples after its own hop has arrived.  Calls are ordered like
+    ``Engine.forward``; the stream owns its workspace.  A stream dies with its engine, like a ``Stream``."""
+    _destroy, _ws_getter = "fv_logmel_stream_destroy", "fv_logmel_stream_workspace_bytes"
+    _closed = ("this log-mel stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
+               "the module): create a new stream")
+
+    def __init__(self, engine: Engine, batch: int, max_chunk_samples: int):
+        self._attach(engine, "Engine.logmel_stream")
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_logmel_stream_create(engine._h, int(batch), int(max_chunk_samples), ctypes.byref(self._h)))
+            self._alloc_workspace()
+        self.batch, self.max_chunk_samples = int(batch), int(max_chunk_samples)
+        self.framing = engine.framing
+        self.hop = self.framing.hop_length
+        self.out_channels = engine.out_channels
+        self._c = _framing.Counters(self.framing)
+
+    # -- counters (host-side: reading them never synchronises) --
+    @property
+    def received_samples(self) -> int:
+        return self._c.N
+
+    @property
+    def emitted_frames(self) -> int:
+        return self._c.E
+
+    @property
+    def pending_samples(self) -> int:
+        """Samples that frames not yet emitted still read, as the library counts them (fv_logmel_stream_pending_samples)."""
+        self._check_open()
+        return int(self._lib.fv_logmel_stream_pending_samples(self._h))
+
+    def emit_count(self, c: int) -> int:
+        """Frames a push of ``c`` samples would emit now."""
+        return self._c.emit_count(c)
+
+    def push(self, chunk: torch.Tensor) -> torch.Tensor:
+        self._check_open()
+        _require_cuda(chunk, "LogMelStream.push")
+        if chunk.dim() == 3 and chunk.shape[1] == 1:
+            chunk = chunk[:, 0]
+        if chunk.dim() != 2 or chunk.shape[0] != self.batch:
+            raise ValueError(f"expected a chunk of shape ({self.batch}, c) or ({self.batch}, 1, c), got {tuple(chunk.shape)}")
+        return self._call(chunk.contiguous(), int(chunk.shape[1]), flush=False)
+
+    def flush(self) -> torch.Tensor:
+        """The frames ``[E, frames(N))`` against the utterance's end; pushes raise afterwards until ``reset()``."""
+        self._check_open()
+        return self._call(None, 0, flush=True)
+
+    def _call(self, x, c: int, flush: bool) -> torch.Tensor:
+        cn = self._c
+        refused = cn.flushed or (not flush and c > self.max_chunk_samples) or (flush and cn.N > 0 and self.framing.too_short(cn.N))
+        k = 0 if refused else (cn.flush_count() if flush else cn.emit_count(c))     # a refused call emits nothing; the library says why
+        dev = self._engine.device
+        out = torch.empty((self.batch, self.out_channels, k), dtype=torch.float32, device=dev)
+        got = ctypes.c_int64(0)
+
+        def launch(stream: int) -> int:
+            if flush:
+                return self._lib.fv_logmel_stream_flush(self._h, out.data_ptr() if k else None, ctypes.byref(got), self._ws.data_ptr(),
+                                                        self._ws.numel() * 4, stream)
+            return self._lib.fv_logmel_stream_push(self._h, x.data_ptr() if c else None, max(c, 1), c, out.data_ptr() if k else None,
+                                                   ctypes.byref(got), self._ws.data_ptr(), self._ws.numel() * 4, stream)
+        self._engine._enqueue(dev, launch, owner=self, eager=True)
+        if got.value != k:
+            raise RuntimeError(f"log-mel stream emitted {got.value} frames where the framing rule says {k}")
+        cn.flush() if flush else cn.push(c)
+        return out
+
+    def reset(self) -> None:
+        """Start the next utterance: N = E = 0; the carry and the workspace are kept."""
+        self._check_open()
+        check(self._lib.fv_logmel_stream_reset(self._h))
+        self._c.reset()
 
 
 class SessionPool(_EngineHandle):

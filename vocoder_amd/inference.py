@@ -11,7 +11,10 @@
   PCM wav only (librosa / soundfile are not available here): other inputs are refused, not guessed.  ``--resample`` converts a ``.wav`` at
   another rate to the model's on the GPU (test.py:54 ``librosa.load(sr=...)``; ``vocoder_amd.resample``), ``--output-rate HZ`` converts the
   generated audio before it is written.
-  ``--chunk-frames N`` streams each input N mel frames at a time (``stream_synthesis``) instead of one whole-utterance forward.
+  ``--chunk-frames N`` streams each input N mel frames at a time (``stream_synthesis``) instead of one whole-utterance forward; a ``.wav`` is
+  read, converted and written ``N * hop`` samples at a time through ``stream_wav_synthesis`` (resample stream, log-mel stream, generator
+  stream, resample stream), so the first audio is out long before the file has been read.  ``--batch-size N`` takes ``.wav`` files too: their
+  rows go through the front-end's ``forward_list`` and then the generator's.
 """
 from __future__ import annotations
 
@@ -112,12 +115,8 @@ def write_wav(path, audio: np.ndarray, sampling_rate: int) -> None:
         w.writeframes(pcm.tobytes())
 
 
-def read_wav(path) -> tuple[np.ndarray, int]:
-    """PCM wav (8 / 16 / 24 / 32 bit) -> ((channels, T) float32 in [-1, 1), sampling rate), like
-    ``librosa.load(path, sr=None, mono=False)`` for such files (test.py:51)."""
-    with wave.open(str(path), "rb") as w:
-        nch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
-        raw = w.readframes(n)
+def _decode_pcm(raw: bytes, width: int, nch: int, path) -> np.ndarray:
+    """Whole frames of PCM bytes (8 / 16 / 24 / 32 bit) -> (channels, T) float32 in [-1, 1)."""
     if width == 1:
         a = (np.frombuffer(raw, np.uint8).astype(np.float32) - 128.0) / 128.0
     elif width == 2:
@@ -130,7 +129,16 @@ def read_wav(path) -> tuple[np.ndarray, int]:
         a = np.frombuffer(raw, "<i4").astype(np.float32) / 2147483648.0
     else:
         raise ValueError(f"{path}: unsupported sample width {width}")
-    return np.ascontiguousarray(a.reshape(-1, nch).T), int(sr)
+    return np.ascontiguousarray(a.reshape(-1, nch).T)
+
+
+def read_wav(path) -> tuple[np.ndarray, int]:
+    """PCM wav (8 / 16 / 24 / 32 bit) -> ((channels, T) float32 in [-1, 1), sampling rate), like
+    ``librosa.load(path, sr=None, mono=False)`` for such files (test.py:51)."""
+    with wave.open(str(path), "rb") as w:
+        nch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        raw = w.readframes(n)
+    return _decode_pcm(raw, width, nch, path), int(sr)
 
 
 def build_model(generator="hifigan", resolution="44100_512_2048", overrides=None, config_root=None,
@@ -201,22 +209,188 @@ def _stream_synthesis_resampled(generator, mel, chunk_frames, resample):
     return torch.cat(outs, dim=-1)[:, None], first, lat
 
 
+def _feed(push, x: torch.Tensor, limit: int) -> torch.Tensor:
+    """``x`` (..., n) through ``push`` in pieces of at most ``limit`` columns (a stage may emit more at once than the next one takes per push);
+    the pieces' outputs concatenated.  An empty ``x`` is pushed once, so that the result has the stage's output shape."""
+    outs = [push(x[..., i:i + limit]) for i in range(0, max(int(x.shape[-1]), 1), limit)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=-1)
+
+
+def _pad_samples(hop: int, L: int) -> int:
+    return hop - (hop % L) if L > 0 else 0      # test.py:64-68, as written upstream
+
+
+@torch.no_grad()
+def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chunk_frames: int, to_model: nn.Module | None = None,
+                         to_out: nn.Module | None = None, sink=None):
+    """wav -> wav chunk by chunk: [resample stream ->] log-mel stream -> generator stream [-> resample stream].  ``chunks`` yields ``(B, c)``
+    tensors of input samples (``c <= chunk_frames * hop``), ``total_samples`` is their sum (the zero padding of the whole-file branch,
+    test.py:64-68, depends on it); ``to_model`` / ``to_out``: ``Resample`` modules into and out of the model's rate.  Every stage's output is
+    pushed into the next one as it comes (its emit count sizes that push), and at the end the flushes cascade from the first stage to the
+    last.  Each piece of finished audio ``(B, 1, k)`` goes to ``sink`` (default: collected).  Returns (the collected waveform or None, stats):
+    ``first_audio_s``, ``push_s`` (seconds per input chunk), ``reads`` and ``reads_before_first_audio`` (input chunks consumed in all / when
+    the first audio left)."""
+    gen, front, hop = model.generator, model.mel_transform, model.hop_length
+    if front is None or not hasattr(front, "stream"):
+        raise ValueError("--chunk-frames on a .wav needs the GPU log-mel front-end (build_model attaches one)")
+    if not hasattr(gen, "stream"):
+        raise ValueError(f"--chunk-frames: {type(gen).__name__} has no stream(); HiFiGAN / BigVGAN generators stream")
+    limit = chunk_frames * hop
+    L_model = to_model.output_length(total_samples) if to_model is not None else total_samples
+    pad = _pad_samples(hop, L_model)
+    collected = [] if sink is None else None
+    stats = dict(first_audio_s=None, push_s=[], reads=0, reads_before_first_audio=None)
+    t0 = time.perf_counter()
+
+    def emit(y):                                    # y: (B, 1, k) at the output rate
+        if y.shape[-1] == 0:
+            return
+        if stats["first_audio_s"] is None:
+            torch.cuda.synchronize()
+            stats["first_audio_s"] = time.perf_counter() - t0
+            stats["reads_before_first_audio"] = stats["reads"]
+        (collected.append if sink is None else sink)(y)
+
+    chunks = iter(chunks)
+    first = next(chunks, None)      # (the first chunk tells the batch size)
+    if first is None:
+        raise ValueError("stream_wav_synthesis: no input samples")
+    B = int(first.shape[0])
+    from contextlib import ExitStack
+    with ExitStack() as stack:
+        rin = stack.enter_context(to_model.stream(batch=B, max_chunk=limit)) if to_model is not None else None
+        mst = stack.enter_context(front.stream(batch=B, max_chunk_samples=limit))
+        gst = stack.enter_context(gen.stream(batch=B, max_chunk_frames=chunk_frames))
+        if gst.out_channels != 1:
+            raise ValueError(f"the generator emits {gst.out_channels} channels; wav -> wav streaming takes waveforms (B, 1, T)")
+        rout = stack.enter_context(to_out.stream(batch=B, max_chunk=limit)) if to_out is not None else None
+
+        def from_audio(y):                          # generator output (B, 1, k) -> the sink
+            emit(y if rout is None else _feed(rout.push, y[:, 0], limit)[:, None])
+
+        def from_mel(m):                            # (B, num_mels, k)
+            from_audio(_feed(gst.push, m, chunk_frames))
+
+        def from_model_rate(x):                     # (B, c) at the model's rate
+            from_mel(_feed(mst.push, x, limit))
+
+        def one(x):
+            t1 = time.perf_counter()
+            stats["reads"] += 1
+            x = x.to(model.device, torch.float32)
+            from_model_rate(x if rin is None else _feed(rin.push, x, limit))
+            torch.cuda.synchronize()
+            stats["push_s"].append(time.perf_counter() - t1)
+
+        one(first)
+        for x in chunks:
+            one(x)
+        # the flushes cascade: each stage's tail goes through every later stage before that stage is flushed itself
+        if rin is not None:
+            from_model_rate(rin.flush())
+        if pad:
+            from_model_rate(torch.zeros((B, pad), dtype=torch.float32, device=model.device))
+        from_mel(mst.flush())
+        from_audio(gst.flush())
+        if rout is not None:
+            emit(rout.flush()[:, None])
+        torch.cuda.synchronize()
+    if stats["first_audio_s"] is None:
+        stats["first_audio_s"] = time.perf_counter() - t0
+        stats["reads_before_first_audio"] = stats["reads"]
+    return (torch.cat(collected, dim=-1) if collected else None), stats
+
+
+def _wav_chunks(path, chunk: int):
+    """A PCM wav (every width ``read_wav`` takes) ``chunk`` frames at a time: yields ``(channels, c)`` float32 tensors, read as the loop asks
+    for them; together they are ``read_wav``'s samples."""
+    with wave.open(str(path), "rb") as w:
+        nch, width = w.getnchannels(), w.getsampwidth()
+        while True:
+            raw = w.readframes(chunk)      # whole frames: at most chunk * nch * width bytes
+            if not raw:
+                return
+            yield torch.from_numpy(_decode_pcm(raw, width, nch, path))
+
+
+class _WavSink:
+    """16-bit PCM wav of ``channels`` channels written piece by piece: each ``(B, 1, k)`` tensor becomes ``k`` frames of ``B`` channels
+    (``write_wav``'s rounding).  The header is complete from the start, so closing a sink that received nothing leaves an empty wav."""
+
+    def __init__(self, path, sampling_rate: int, channels: int):
+        Path(path).parent.mkdir(parents=True, exist_ok=True)
+        self._w, self.frames = wave.open(str(path), "wb"), 0
+        self._w.setnchannels(int(channels))
+        self._w.setsampwidth(2)
+        self._w.setframerate(int(sampling_rate))
+
+    def __call__(self, y: torch.Tensor) -> None:
+        a = y[:, 0].cpu().numpy().T
+        self._w.writeframes((np.clip(a, -1.0, 1.0) * 32767.0).round().astype("<i2").tobytes())
+        self.frames += a.shape[0]
+
+    def close(self) -> None:
+        self._w.close()
+
+
+def _main_wav_streamed(a, model, f, out, to_out, out_rate) -> None:
+    """One .wav under --chunk-frames: read, converted and written ``chunk_frames * hop`` samples at a time."""
+    with wave.open(str(f), "rb") as w:
+        sr, total, nch = w.getframerate(), w.getnframes(), w.getnchannels()
+    if total == 0:
+        raise ValueError(f"{f}: the file holds no samples")
+    to_model = None
+    if sr != model.sampling_rate:
+        if not a.resample:
+            raise ValueError(f"{f}: {sr} Hz, the model runs at {model.sampling_rate} Hz and this tool does not resample")
+        from .resample import Resample
+        to_model = Resample(sr, model.sampling_rate)
+    sink = _WavSink(out, out_rate, nch)
+    t0 = time.time()
+    try:
+        _, stats = stream_wav_synthesis(model, _wav_chunks(f, a.chunk_frames * model.hop_length), total, a.chunk_frames, to_model, to_out, sink)
+    finally:
+        sink.close()
+    print(f"{f}: {sink.frames / out_rate:.2f}s of audio in {time.time() - t0:.4f}s, wav -> wav streamed in {a.chunk_frames}-frame chunks: "
+          f"first audio after {stats['first_audio_s'] * 1e3:.2f} ms ({stats['reads_before_first_audio']} of {stats['reads']} chunks read), "
+          f"per-chunk p50 {np.percentile(stats['push_s'], 50) * 1e3:.2f} ms")
+
+
+def _wav_rows(a, model, f) -> torch.Tensor:
+    """A .wav as the whole-file branch prepares it (test.py:50-68): channels -> rows at the model's rate, zero padding; ``(channels, L)``."""
+    y, sr = read_wav(f)
+    if sr != model.sampling_rate and not a.resample:
+        raise ValueError(f"{f}: {sr} Hz, the model runs at {model.sampling_rate} Hz and this tool does not resample")
+    y = torch.from_numpy(y).to(model.device)
+    if sr != model.sampling_rate:      # test.py:54: librosa.load(..., sr=cfg.model.sampling_rate), file by file
+        from .resample import Resample
+        y = Resample(sr, model.sampling_rate)(y)
+    return torch.nn.functional.pad(y, (0, _pad_samples(model.hop_length, y.shape[-1])))
+
+
 def _main_batched(a, model, files, base) -> None:
     """--batch-size N: the mel files N at a time, each batch (every mel of a file one utterance) through one ``forward_list`` call."""
-    if any(f.suffix == ".wav" for f in files):
-        raise ValueError("--batch-size takes mel inputs (.pt / .pth); run .wav inputs without it")
     if not hasattr(model.generator, "forward_list"):
         raise ValueError(f"--batch-size: {type(model.generator).__name__} has no forward_list()")
     for i in range(0, len(files), a.batch_size):
         chunk = files[i:i + a.batch_size]
         mels, owner = [], []
         for f in chunk:
+            if f.suffix == ".wav":     # the rows of every .wav of the batch go through the front-end together, below
+                rows = _wav_rows(a, model, f)
+                mels.extend(rows[b] for b in range(rows.shape[0]))
+                owner.extend([f] * rows.shape[0])
+                continue
             mel = torch.load(f, map_location="cpu", weights_only=True)
             if a.diffsinger:
                 mel = diffsinger_mel_to_ln(mel)
             mel = prepare_mel(mel, model.num_mels).to(model.device)
             mels.extend(mel[b] for b in range(mel.shape[0]))
             owner.extend([f] * mel.shape[0])
+        wav_at = [j for j, o in enumerate(owner) if o.suffix == ".wav"]
+        if wav_at:
+            for j, m in zip(wav_at, model.mel_transform.forward_list([mels[j] for j in wav_at])):
+                mels[j] = m
         t0 = time.time()
         waves = model.generator.forward_list(mels)
         torch.cuda.synchronize()
@@ -287,11 +461,14 @@ def main(argv=None):
                     help="fall back to a full unpickle (like the reference's plain torch.load) when the weights-only loader "
                          "refuses a Lightning checkpoint that holds non-tensor objects")
     ap.add_argument("--chunk-frames", type=int, default=None,
-                    help="push each input through a stream, N mel frames at a time (same wav as the whole-utterance run, within 1 LSB); "
-                         "prints the time to first audio and the per-chunk p50 latency")
+                    help="push each input through a stream, N mel frames at a time (same wav as the whole-utterance run, within 1 LSB); a "
+                         ".wav (any PCM width the whole-file run reads) is read, converted and written N * hop samples at a time (log-mel "
+                         "stream -> generator stream); prints the "
+                         "time to first audio and the per-chunk p50 latency")
     ap.add_argument("--batch-size", type=int, default=None,
-                    help="take the mel (.pt / .pth) inputs N files at a time and run each batch of utterances, whatever their lengths, through "
-                         "ONE ragged forward (generator.forward_list); same wavs as the one-by-one run, within 1 LSB")
+                    help="take the inputs N files at a time and run each batch of utterances, whatever their lengths, through ONE ragged "
+                         "forward (generator.forward_list; .wav inputs through the front-end's forward_list first); same wavs as the "
+                         "one-by-one run, within 1 LSB")
     ap.add_argument("--sessions", type=int, default=None,
                     help="with --chunk-frames: keep N mel (.pt / .pth) files in flight through ONE session pool (generator.session_pool); each "
                          "file ends at its own length and its slot takes the next file; same wavs as the one-by-one run, within 1 LSB")
@@ -327,6 +504,9 @@ def main(argv=None):
     if a.sessions:
         return _main_sessions(a, model, files, base)
     for f in files:
+        if f.suffix == ".wav" and a.chunk_frames:
+            _main_wav_streamed(a, model, f, Path(a.output_path) / f.relative_to(base).with_suffix(".wav"), to_out, out_rate)
+            continue
         if f.suffix == ".wav":   # test.py:50-71: channels -> batch items, zero padding, mel_transforms.input
             y, sr = read_wav(f)
             if sr != model.sampling_rate and not a.resample:
