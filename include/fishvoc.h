@@ -621,6 +621,76 @@ FV_API fv_status fv_logmel_stream_reset(fv_logmel_stream* s);
  * nothing to free. */
 FV_API void fv_logmel_stream_destroy(fv_logmel_stream* s);
 
+/* -------- the resampler with its table in global memory: any rate pair.  fv_resample_create keeps the whole table in LDS and refuses the
+ *          pairs whose table does not fit (44101 -> 48000; the 52400 -> 44100 of a pitch shift at lowpass_filter_width 64); this entry takes them.
+ *          Same object, same design (fv_resample_design), same functions: fv_resample_forward with or without d_lengths and
+ *          fv_resample_stream_* dispatch on where the table lives.  The kernel stages only the input tile in LDS and reads first[], count[] and
+ *          the taps from global memory (they stay in L2); its tiling and every output's sum — ascending taps, one fp32 accumulator, fused
+ *          multiply-adds — are those of the LDS kernel, so for a pair that both forms take the results agree bit for bit.  Stands in for
+ *          torchaudio.transforms.Resample in front of test.py:54 / hq_pitch_shift.py:33 and for the resample step of
+ *          librosa.effects.pitch_shift (test.py:61-62).  FV_ERR_UNSUPPORTED only when one phase's band does not fit beside the input tile
+ *          (Kp of several thousand taps) or the table passes 1 GiB.  (Named outside the fv_resample_ prefix: that family's list of entries is
+ *          pinned by its host test.) -------- */
+FV_API fv_status fv_global_resample_create(const fv_resample_config* cfg, fv_resample** out);
+
+/* -------- pitch shift: `librosa.effects.pitch_shift(gt_y, sr=sr, n_steps=cfg.pitch_shift)` (test.py:61-62), the step between loading /
+ *          resampling a file and the mel front-end.  librosa is not a dependency; its arithmetic is restated: a time stretch by
+ *          rate = 2^(-n_steps / bins_per_octave) with a phase vocoder (stft, n_fft 2048, hop n_fft / 4, periodic hann, center=True with zero
+ *          padding; phase_vocoder; istft), then a resample from sr / rate back to sr, fixed to the input length.  --------
+ *
+ * Plan (integers): orig_freq = floor(sr * 2^(n_steps / bpo) + 0.5), then orig_freq -= orig_freq % freq_granularity (the reference's own rule,
+ * hq_pitch_shift.py:30-31); g = gcd(orig_freq, sr), o = orig_freq / g, n = sr / g: the stretch rate is exactly n / o.  orig_freq == sr: the
+ * output is a bit-for-bit copy of the input.
+ * Analysis: T = 1 + L / hop frames; D[k][f] = rfft of the hann-windowed samples [f hop - n_fft / 2, ... + n_fft), zeros outside [0, L);
+ * D[:, T] = D[:, T + 1] = 0.
+ * Stretch: T' = ceil(T o / n) output frames; frame s: q = s n, j = q / o, alpha = (q % o) / o (no float time axis, so no drift);
+ * mag = (1 - alpha) |D[k][j]| + alpha |D[k][j + 1]|.  The phase is held in turns in unsigned 32-bit fixed point:
+ * Theta[k][f] = uint32(llrint(atan2(Im, Re) / (2 pi) * 2^32)) (0 where D = 0), Phi[k][s] = Theta[k][0] + sum_{u < s} (Theta[k][j_u + 1] -
+ * Theta[k][j_u]) in wrapping arithmetic — the wrap is the modulo 2 pi, and librosa's phi_advance and its wrap cancel out of e^{i Phi}.  An fp32
+ * accumulator holds ~1e6 rad after 200 000 samples and is off by 0.12 of peak; this form stays within 2e-6.  Integer addition is associative:
+ * the scan gives the same bits whatever its decomposition.  S[k][s] = mag (cos, sin)(2 pi Phi / 2^32).
+ * Synthesis: irfft(S[:, s]) times the window, overlap-added, divided by the overlap-added window^2 where that is positive, n_fft / 2 samples
+ * cropped from the front, cut or zero-padded to Ls = (2 L o + n) / (2 n) (round(L o / n), halves up).
+ * Resample: orig_freq -> sr with fv_resample_design's filter (table in global memory): ceil(n Ls / o) samples, cut or zero-padded to L.
+ * Not built: a streaming form, ragged rows in one call, a chunk-parallel scan for very long single rows. */
+typedef struct fv_pitch_shift_config {
+    int32_t sample_rate;           /* sr of test.py:61-62 */
+    double n_steps;                /* cfg.pitch_shift (configs/train.yaml), in steps of an octave / bins_per_octave */
+    int32_t bins_per_octave;       /* librosa's default 12 */
+    int32_t n_fft;                 /* librosa's default 2048 */
+    int32_t hop_length;            /* 0: n_fft / 4 (librosa's default) */
+    int32_t freq_granularity;      /* 100 in hq_pitch_shift.py:31; 1 keeps orig_freq as rounded */
+    int32_t lowpass_filter_width;  /* 64 with the values below: torchaudio's documented equivalent of librosa's kaiser_best */
+    double rolloff;                /* 0.9475937167399596 */
+    int32_t method;                /* fv_resample_method; FV_RESAMPLE_SINC_KAISER */
+    double beta;                   /* 14.769656459379492; <= 0: that default */
+} fv_pitch_shift_config;
+
+/* Pure host (no GPU): the plan of test.py:61-62's pitch shift.  FV_ERR_INVALID names the offending field. */
+FV_API fv_status fv_pitch_shift_plan(const fv_pitch_shift_config* cfg, int32_t* orig_freq, int32_t* o, int32_t* n);
+/* Pure host: for L input samples (test.py:61-62's gt_y), T analysis frames, T' stretched frames, Ls stretched samples and ceil(n Ls / o) resampled
+ * samples (before the cut / padding to L).  NULL outputs are skipped. */
+FV_API fv_status fv_pitch_shift_lengths(const fv_pitch_shift_config* cfg, int64_t L, int64_t* frames, int64_t* frames_out, int64_t* stretched,
+                                        int64_t* resampled);
+
+typedef struct fv_pitch_shift fv_pitch_shift;
+
+/* Builds the DFT bases, the window envelope and the resampler's table on the current HIP device (test.py:61-62 builds nothing: librosa
+ * recomputes per call).  n_fft must be a multiple of hop_length and both even, else FV_ERR_UNSUPPORTED naming the values. */
+FV_API fv_status fv_pitch_shift_create(const fv_pitch_shift_config* cfg, fv_pitch_shift** out);
+FV_API void fv_pitch_shift_destroy(fv_pitch_shift* p);
+/* Bytes of device scratch fv_pitch_shift_stretch / fv_pitch_shift_forward need for `batch` rows of L samples (test.py:61-62 allocates per
+ * call); 0 for a bad argument. */
+FV_API size_t fv_pitch_shift_workspace_bytes(const fv_pitch_shift* p, int32_t batch, int64_t L);
+/* librosa.effects.time_stretch(rate = n / o), the first half of test.py:61-62: d_x `batch` rows of L samples (row b at d_x + b * x_row_stride),
+ * d_y `batch` rows of Ls (fv_pitch_shift_lengths) samples.  d_y must not overlap d_x.  Asynchronous on `stream`. */
+FV_API fv_status fv_pitch_shift_stretch(fv_pitch_shift* p, const float* d_x, int64_t x_row_stride, float* d_y, int64_t y_row_stride,
+                                        int32_t batch, int64_t L, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The whole of test.py:61-62: d_y `batch` rows of L samples.  Rows are the flattened leading dimensions (stereo: two rows, test.py:56-64).
+ * d_y must not overlap d_x (FV_ERR_INVALID).  Asynchronous on `stream`. */
+FV_API fv_status fv_pitch_shift_forward(fv_pitch_shift* p, const float* d_x, int64_t x_row_stride, float* d_y, int64_t y_row_stride,
+                                        int32_t batch, int64_t L, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* -------- single fused conv layer (the hot kernel on its own; used by the parity tests and the roofline
  *          bench).  Stands in for one weight-normed nn.Conv1d / nn.ConvTranspose1d call plus the elementwise
  *          ops the reference runs around it (F.silu before, residual add after: hifigan.py:101-108). -------- */

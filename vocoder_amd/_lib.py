@@ -50,6 +50,9 @@ EXPORTS = (
     "fv_resample_stream_flush", "fv_resample_stream_reset", "fv_resample_stream_destroy",
     "fv_logmel_frames", "fv_logmel_frames_ready", "fv_logmel_ragged_forward", "fv_logmel_stream_create", "fv_logmel_stream_workspace_bytes",
     "fv_logmel_stream_pending_samples", "fv_logmel_stream_push", "fv_logmel_stream_flush", "fv_logmel_stream_reset", "fv_logmel_stream_destroy",
+    "fv_global_resample_create",
+    "fv_pitch_shift_plan", "fv_pitch_shift_lengths", "fv_pitch_shift_create", "fv_pitch_shift_destroy", "fv_pitch_shift_workspace_bytes",
+    "fv_pitch_shift_stretch", "fv_pitch_shift_forward",
 )
 
 _i32 = ctypes.c_int32
@@ -121,6 +124,12 @@ class PoolRow(ctypes.Structure):
 
 class ResampleConfig(ctypes.Structure):
     _fields_ = [("orig_freq", _i32), ("new_freq", _i32), ("lowpass_filter_width", _i32), ("rolloff", ctypes.c_double), ("method", _i32),
+                ("beta", ctypes.c_double)]
+
+
+class PitchShiftConfig(ctypes.Structure):
+    _fields_ = [("sample_rate", _i32), ("n_steps", ctypes.c_double), ("bins_per_octave", _i32), ("n_fft", _i32), ("hop_length", _i32),
+                ("freq_granularity", _i32), ("lowpass_filter_width", _i32), ("rolloff", ctypes.c_double), ("method", _i32),
                 ("beta", ctypes.c_double)]
 
 
@@ -302,6 +311,23 @@ def lib() -> ctypes.CDLL:
     L.fv_logmel_stream_reset.restype = _i32
     L.fv_logmel_stream_destroy.argtypes = [vp]
     L.fv_logmel_stream_destroy.restype = None
+    L.fv_global_resample_create.argtypes = [rcp, ctypes.POINTER(vp)]
+    L.fv_global_resample_create.restype = _i32
+    pcp = ctypes.POINTER(PitchShiftConfig)
+    L.fv_pitch_shift_plan.argtypes = [pcp, i32p, i32p, i32p]
+    L.fv_pitch_shift_plan.restype = _i32
+    L.fv_pitch_shift_lengths.argtypes = [pcp, i64, i64p, i64p, i64p, i64p]
+    L.fv_pitch_shift_lengths.restype = _i32
+    L.fv_pitch_shift_create.argtypes = [pcp, ctypes.POINTER(vp)]
+    L.fv_pitch_shift_create.restype = _i32
+    L.fv_pitch_shift_destroy.argtypes = [vp]
+    L.fv_pitch_shift_destroy.restype = None
+    L.fv_pitch_shift_workspace_bytes.argtypes = [vp, _i32, i64]
+    L.fv_pitch_shift_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_pitch_shift_stretch.argtypes = [vp, vp, i64, vp, i64, _i32, i64, vp, ctypes.c_size_t, vp]
+    L.fv_pitch_shift_stretch.restype = _i32
+    L.fv_pitch_shift_forward.argtypes = [vp, vp, i64, vp, i64, _i32, i64, vp, ctypes.c_size_t, vp]
+    L.fv_pitch_shift_forward.restype = _i32
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

@@ -206,6 +206,34 @@ fv_status fv_engine::build_convnext(const std::string& pfx) {
     return FV_OK;
 }
 
+std::vector<float> fv::stft_basis(const std::vector<float>& win, int N, int hop, int taps) {
+    const int nb = N / 2 + 1;
+    std::vector<float> wst((size_t)2 * nb * hop * taps, 0.f);
+    for (int k = 0; k < nb; ++k)
+        for (int r = 0; r < hop; ++r)
+            for (int q = 0; q < taps; ++q) {
+                const int n = q * hop + r;
+                if (n >= N) continue;
+                const double ang = 2.0 * M_PI * (double)(((int64_t)k * n) % N) / N;
+                wst[((size_t)k * hop + r) * taps + q] = (float)(win[n] * std::cos(ang));
+                wst[((size_t)(nb + k) * hop + r) * taps + q] = (float)(-(double)win[n] * std::sin(ang));
+            }
+    return wst;
+}
+
+std::vector<float> fv::istft_basis(const std::vector<float>& win, int N) {
+    const int nb = N / 2 + 1;
+    std::vector<float> basis((size_t)N * 2 * nb);
+    for (int n = 0; n < N; ++n)
+        for (int k = 0; k < nb; ++k) {
+            const double ck = (k == 0 || k == N / 2) ? 1.0 : 2.0;
+            const double ang = 2.0 * M_PI * (double)(((int64_t)k * n) % N) / N;
+            basis[(size_t)n * 2 * nb + k] = (float)(ck * std::cos(ang) / N * win[n]);
+            basis[(size_t)n * 2 * nb + nb + k] = (float)(-ck * std::sin(ang) / N * win[n]);
+        }
+    return basis;
+}
+
 fv_status fv_engine::build_head(const std::string& pfx) {
     const fv_istft_head_config& c = cfg.head;
     head.cfg = c;
@@ -238,14 +266,7 @@ fv_status fv_engine::build_head(const std::string& pfx) {
     }
     // windowed inverse real DFT as a (n_fft) x (2 nb) matrix: frame[n] = win[n]/N * sum_k c_k (Re_k cos - Im_k sin),
     // c_0 = c_{N/2} = 1, else 2  == torch.fft.irfft(S, n_fft, norm="backward") * window  (vocos ISTFT, restated)
-    std::vector<float> basis((size_t)N * 2 * nb);
-    for (int n = 0; n < N; ++n)
-        for (int k = 0; k < nb; ++k) {
-            const double ck = (k == 0 || k == N / 2) ? 1.0 : 2.0;
-            const double ang = 2.0 * M_PI * (double)(((int64_t)k * n) % N) / N;
-            basis[(size_t)n * 2 * nb + k] = (float)(ck * std::cos(ang) / N * win[n]);
-            basis[(size_t)n * 2 * nb + nb + k] = (float)(-ck * std::sin(ang) / N * win[n]);
-        }
+    const std::vector<float> basis = istft_basis(win, N);
     if ((st = conv_layer_create(head.idft, false, 2 * nb, N, 1, 1, 0, 1, basis.data(), nullptr))) return st;
     std::vector<float> win2(N);
     for (int n = 0; n < N; ++n) win2[n] = win[n] * win[n];
@@ -288,16 +309,7 @@ fv_status fv_engine::build_logmel(const std::string& pfx) {
         for (int n = 0; n < N; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / N));   // hann, periodic
     }
     // STFT as a stride-1 conv over the polyphase signal: X_k[t] = sum_{r<hop} sum_{q<taps} w[qh+r] e^{-2 pi i k (qh+r)/N} yp[r][t+q]
-    std::vector<float> wst((size_t)2 * nb * hop * taps, 0.f);
-    for (int k = 0; k < nb; ++k)
-        for (int r = 0; r < hop; ++r)
-            for (int q = 0; q < taps; ++q) {
-                const int n = q * hop + r;
-                if (n >= N) continue;
-                const double ang = 2.0 * M_PI * (double)(((int64_t)k * n) % N) / N;
-                wst[((size_t)k * hop + r) * taps + q] = (float)(win[n] * std::cos(ang));
-                wst[((size_t)(nb + k) * hop + r) * taps + q] = (float)(-(double)win[n] * std::sin(ang));
-            }
+    const std::vector<float> wst = stft_basis(win, N, hop, taps);
     fv_status st;
     if ((st = conv_layer_create(mel.stft, false, hop, 2 * nb, taps, 1, 0, 1, wst.data(), nullptr))) return st;
     if (c.n_mels == 0) return FV_OK;   // linear spectrogram only: no filterbank

@@ -433,6 +433,14 @@ fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T
 fv_status launch_istft_ola(const float* frames, const float* inv_env, float* y, int B, int n_fft, int T, int hop, int pad, long long out_len,
                            hipStream_t s);
 
+// The DFT bases the STFT / ISTFT convs are built from (engine_build.hip): the log-mel front-end, the ISTFT head and the pitch shift share them.
+// stft_basis: the window-folded real DFT in polyphase form, a (2 nb, hop, taps) conv weight — rows [0, nb) win[n] cos, [nb, 2 nb) -win[n] sin at
+// n = q hop + r, zero for n >= N.  istft_basis: the windowed inverse real DFT, an (N, 2 nb) pointwise weight — c_k cos / N win[n] | -c_k sin / N win[n].
+std::vector<float> stft_basis(const std::vector<float>& win, int N, int hop, int taps);
+std::vector<float> istft_basis(const std::vector<float>& win, int N);
+// resample.hip: the outputs [0, m_end) of `batch` rows of `len` samples through r's kernel, unchecked (pitch_shift.hip)
+fv_status resample_rows(const fv_resample* r, const char* fn, const float* x, long long x_stride, long long len, float* y, long long y_stride,
+                        int batch, long long m_end, hipStream_t s);
 
 // RefineGAN glue (small_kernels.hip): linear interpolation (nn.Upsample(mode="linear")) with optional leaky_relu, written into
 // a channel slice of a wider tensor; channel-slice copy; AdaIN with caller-supplied noise

@@ -1,5 +1,6 @@
 // Sample-rate conversion (fv_resample_*, include/fishvoc.h): the polyphase windowed-sinc resampler of torchaudio.transforms.Resample as a banded
-// FIR on the vector ALU.  Host: the filter design in float64 (fv_resample_design, no GPU), the object, the stream.  Device: one kernel.
+// FIR on the vector ALU.  Host: the filter design in float64 (fv_resample_design, no GPU), the object, the stream.  Device: one kernel body in two forms
+// (table staged in LDS / read from global memory).
 //
 // Output m = f n + p reads x[f o + first[p] - width + i], i < count[p] (count <= Kp: 13 taps for 44100 -> 48000, 73 for 48000 -> 8000), where the
 // dense form of the reference holds 2 width + o = 161 ... 475 taps per output, all but the band zero: an MFMA GEMM over the dense form would do
@@ -64,17 +65,35 @@ struct ResampleParams {
     int o, n, width, kpad, table_dwords, sx;   // sx: staged samples, a multiple of 4
 };
 
-__global__ __launch_bounds__(kResThreads) void resample_kernel(const ResampleParams p) {
+// how the kernel holds its table: plain pointers into LDS (staged by the workgroup itself), or __restrict__ pointers into global memory that
+// nothing writes during the launch
+template <bool kGlobalTable>
+struct TablePtr {
+    using I = const int*;
+    using F = const float*;
+};
+template <>
+struct TablePtr<true> {
+    using I = const int* __restrict__;
+    using F = const float* __restrict__;
+};
+
+// kGlobalTable: first[], count[] and the taps are read where they lie, in global memory (fv_global_resample_create: a table of any size, served
+// by L2), and LDS holds the input tile alone.  Tiling, indices and the sum of an output are the same statements in both forms.
+template <bool kGlobalTable>
+__device__ __forceinline__ void resample_body(const ResampleParams& p) {
     extern __shared__ __align__(16) uint32_t smem[];
-    const int* s_first = (const int*)smem;
-    const int* s_count = s_first + p.n;
-    const float* s_taps = (const float*)(s_count + p.n);
-    float* s_x = (float*)(smem + p.table_dwords);
+    const uint32_t* table = kGlobalTable ? p.table : smem;
+    const typename TablePtr<kGlobalTable>::I s_first = (const int*)table;
+    const typename TablePtr<kGlobalTable>::I s_count = s_first + p.n;
+    const typename TablePtr<kGlobalTable>::F s_taps = (const float*)(s_count + p.n);
+    float* s_x = (float*)(smem + (kGlobalTable ? 0 : p.table_dwords));
     const int tid = threadIdx.x;
     const int tile = blockIdx.x % p.ntiles;
     const long long row = blockIdx.x / p.ntiles;
 
-    for (int q = tid; q < p.table_dwords / 4; q += kResThreads) ((uint4*)smem)[q] = ((const uint4*)p.table)[q];
+    if (!kGlobalTable)
+        for (int q = tid; q < p.table_dwords / 4; q += kResThreads) ((uint4*)smem)[q] = ((const uint4*)p.table)[q];
 
     long long len_b = p.len;
     if (p.lengths) len_b = min((long long)max(p.lengths[row], 0), p.len);
@@ -131,6 +150,9 @@ __global__ __launch_bounds__(kResThreads) void resample_kernel(const ResamplePar
         }
     }
 }
+
+__global__ __launch_bounds__(kResThreads) void resample_kernel(const ResampleParams p) { resample_body<false>(p); }
+__global__ __launch_bounds__(kResThreads) void resample_global_kernel(const ResampleParams p) { resample_body<true>(p); }
 
 // stream: the next work buffer [last H samples | chunk] out of the previous one and the caller's chunk
 __global__ void resample_carry_kernel(const float* prev, float* next, const float* chunk, long long cols, long long x_stride, int H, int prev_c,
@@ -270,6 +292,7 @@ struct fv_resample {
     std::vector<int> end;       // first[] + count[]
     int kpad = 0, table_dwords = 0, sx = 0;
     uint32_t* d_table = nullptr;
+    bool global_table = false;   // fv_global_resample_create: the kernel reads the table from global memory
     ~fv_resample() {
         if (d_table) (void)hipFree(d_table);
     }
@@ -307,11 +330,23 @@ static fv_status resample_run(const fv_resample* r, const char* fn, const float*
     }
     p.ntiles = (int)ntiles;
     p.o = r->d.o, p.n = r->d.n, p.width = r->d.width, p.kpad = r->kpad, p.table_dwords = r->table_dwords, p.sx = r->sx;
+    if (r->global_table) {
+        hipLaunchKernelGGL(resample_global_kernel, dim3((unsigned)(ntiles * batch)), dim3(kResThreads), (size_t)r->sx * 4, s, p);
+        FV_HIP_CHECK(hipGetLastError());
+        set_last_kernel("resample_global_kernel");
+        return FV_OK;
+    }
     const size_t lds = ((size_t)r->table_dwords + r->sx) * 4;
     hipLaunchKernelGGL(resample_kernel, dim3((unsigned)(ntiles * batch)), dim3(kResThreads), lds, s, p);
     FV_HIP_CHECK(hipGetLastError());
     set_last_kernel("resample_kernel");
     return FV_OK;
+}
+
+// pitch_shift.hip: the outputs [0, m_end) of `batch` rows of `len` samples (fv_resample_forward without its argument checks)
+fv_status fv::resample_rows(const fv_resample* r, const char* fn, const float* x, long long x_stride, long long len, float* y, long long y_stride,
+                            int batch, long long m_end, hipStream_t s) {
+    return resample_run(r, fn, x, x_stride, 0, nullptr, len, y, y_stride, batch, 0, m_end, s);
 }
 
 extern "C" {
@@ -342,26 +377,41 @@ FV_API fv_status fv_resample_design(const fv_resample_config* cfg, int32_t* o, i
 
 FV_API int32_t fv_resample_input_tile(void) { return kResTile; }
 
-FV_API fv_status fv_resample_create(const fv_resample_config* cfg, fv_resample** out) {
+}  // extern "C"
+
+// both create entries: the same design, the same table layout; global_table decides where the kernel reads it and what must fit in LDS
+static fv_status resample_create(const fv_resample_config* cfg, fv_resample** out, bool global_table, const char* fn) {
     if (!out) {
-        set_error("fv_resample_create: null argument");
+        set_error("%s: null argument", fn);
         return FV_ERR_INVALID;
     }
     *out = nullptr;
     std::unique_ptr<fv_resample> r(new fv_resample());
-    if (const fv_status st = design(cfg, "fv_resample_create", r->d, false)) return st;
+    if (const fv_status st = design(cfg, fn, r->d, false)) return st;
     const Design& d0 = r->d;
     const long long kpad = d0.kp | 1;   // odd rows: lanes on consecutive phases read consecutive LDS banks
     const long long table = ((2LL * d0.n + (long long)d0.n * kpad + 3) / 4) * 4, sx = (((long long)kResTile + d0.kp + 3 + 3) / 4) * 4;
-    if ((table + sx) * 4 > (long long)kResLdsBudget) {
+    if (global_table) {
+        if (sx * 4 > (long long)kResLdsBudget) {
+            set_error("%s: %d -> %d Hz has bands of %d taps: the staged input (the %d-sample tile plus one band, %lld bytes) passes the LDS "
+                      "budget of %zu", fn, cfg->orig_freq, cfg->new_freq, d0.kp, kResTile, sx * 4, kResLdsBudget);
+            return FV_ERR_UNSUPPORTED;
+        }
+        if (table * 4 > (1LL << 30)) {
+            set_error("%s: %d -> %d Hz needs a table of %d phases x %d taps, %lld bytes: more than the limit of 2^30", fn, cfg->orig_freq,
+                      cfg->new_freq, d0.n, d0.kp, table * 4);
+            return FV_ERR_UNSUPPORTED;
+        }
+    } else if ((table + sx) * 4 > (long long)kResLdsBudget) {
         set_error("fv_resample_create: %d -> %d Hz needs a table of %d phases x %d taps (%lld bytes with its index rows); beside the %d-sample "
                   "input tile that is %lld bytes of LDS, over the budget of %zu", cfg->orig_freq, cfg->new_freq, d0.n, d0.kp, table * 4, kResTile,
                   (table + sx) * 4, kResLdsBudget);
         return FV_ERR_UNSUPPORTED;
     }
-    if (const fv_status st = design(cfg, "fv_resample_create", r->d, true)) return st;
+    if (const fv_status st = design(cfg, fn, r->d, true)) return st;
     const Design& d = r->d;
     r->cfg = *cfg;
+    r->global_table = global_table;
     r->kpad = (int)kpad, r->table_dwords = (int)table, r->sx = (int)sx;
     r->end.resize(d.n);
     for (int p = 0; p < d.n; ++p) r->end[p] = d.first[p] + d.count[p];
@@ -375,6 +425,16 @@ FV_API fv_status fv_resample_create(const fv_resample_config* cfg, fv_resample**
     FV_HIP_CHECK(hipMemcpy(r->d_table, host.data(), host.size() * 4, hipMemcpyHostToDevice));
     *out = r.release();
     return FV_OK;
+}
+
+extern "C" {
+
+FV_API fv_status fv_resample_create(const fv_resample_config* cfg, fv_resample** out) {
+    return resample_create(cfg, out, false, "fv_resample_create");
+}
+
+FV_API fv_status fv_global_resample_create(const fv_resample_config* cfg, fv_resample** out) {
+    return resample_create(cfg, out, true, "fv_global_resample_create");
 }
 
 FV_API void fv_resample_destroy(fv_resample* r) { delete r; }

@@ -10,7 +10,8 @@
   ``num_mels``) and ``.wav`` audio (channels become batch items, log-mel on the GPU), write ``(B, 1, T)`` -> wav.
   PCM wav only (librosa / soundfile are not available here): other inputs are refused, not guessed.  ``--resample`` converts a ``.wav`` at
   another rate to the model's on the GPU (test.py:54 ``librosa.load(sr=...)``; ``vocoder_amd.resample``), ``--output-rate HZ`` converts the
-  generated audio before it is written.
+  generated audio before it is written.  ``--pitch-shift N_STEPS`` shifts a ``.wav`` after loading / resampling and before the mel front-end
+  (test.py:61-62 ``librosa.effects.pitch_shift``; ``vocoder_amd.pitch_shift``); whole files and ``--batch-size`` only.
   ``--chunk-frames N`` streams each input N mel frames at a time (``stream_synthesis``) instead of one whole-utterance forward; a ``.wav`` is
   read, converted and written ``N * hop`` samples at a time through ``stream_wav_synthesis`` (resample stream, log-mel stream, generator
   stream, resample stream), so the first audio is out long before the file has been read.  ``--batch-size N`` takes ``.wav`` files too: their
@@ -356,8 +357,18 @@ def _main_wav_streamed(a, model, f, out, to_out, out_rate) -> None:
           f"per-chunk p50 {np.percentile(stats['push_s'], 50) * 1e3:.2f} ms")
 
 
+def _pitch_shifted(a, model, y: torch.Tensor) -> torch.Tensor:
+    """test.py:61-62: ``librosa.effects.pitch_shift(gt_y, sr=sr, n_steps=cfg.pitch_shift)`` after loading / resampling, before the zero padding
+    and the mel front-end; every row of ``y`` (..., L) on its own, on the GPU.  ``--pitch-shift 0`` (the default) returns ``y``."""
+    if not a.pitch_shift:
+        return y
+    from .pitch_shift import PitchShift
+    return PitchShift(model.sampling_rate, a.pitch_shift)(y)
+
+
 def _wav_rows(a, model, f) -> torch.Tensor:
-    """A .wav as the whole-file branch prepares it (test.py:50-68): channels -> rows at the model's rate, zero padding; ``(channels, L)``."""
+    """A .wav as the whole-file branch prepares it (test.py:50-68): channels -> rows at the model's rate, pitch shift, zero padding;
+    ``(channels, L)``."""
     y, sr = read_wav(f)
     if sr != model.sampling_rate and not a.resample:
         raise ValueError(f"{f}: {sr} Hz, the model runs at {model.sampling_rate} Hz and this tool does not resample")
@@ -365,6 +376,7 @@ def _wav_rows(a, model, f) -> torch.Tensor:
     if sr != model.sampling_rate:      # test.py:54: librosa.load(..., sr=cfg.model.sampling_rate), file by file
         from .resample import Resample
         y = Resample(sr, model.sampling_rate)(y)
+    y = _pitch_shifted(a, model, y)    # each file on its own, before the ragged call
     return torch.nn.functional.pad(y, (0, _pad_samples(model.hop_length, y.shape[-1])))
 
 
@@ -478,7 +490,14 @@ def main(argv=None):
     ap.add_argument("--output-rate", type=int, default=None, metavar="HZ",
                     help="convert the generated audio to HZ on the GPU before it is written (with --chunk-frames: chunk by chunk through a "
                          "resample stream); not with --batch-size / --sessions")
+    ap.add_argument("--pitch-shift", type=float, default=0.0, metavar="N_STEPS",
+                    help="shift every .wav input by N_STEPS semitones on the GPU after loading and --resample, before the mel front-end (the "
+                         "reference's librosa.effects.pitch_shift, test.py:61-62); whole files and --batch-size, not mel inputs, "
+                         "--chunk-frames or --sessions")
     a = ap.parse_args(argv)
+    if a.pitch_shift and (a.chunk_frames is not None or a.sessions is not None):
+        raise ValueError("--pitch-shift is not available with --chunk-frames / --sessions: the phase vocoder has no streaming form; run the "
+                         "files whole or under --batch-size")
     if a.output_rate is not None and a.output_rate < 1:
         ap.error("--output-rate must be >= 1 Hz")
     if a.output_rate is not None and (a.batch_size is not None or a.sessions is not None):
@@ -499,6 +518,9 @@ def main(argv=None):
     if out_rate != model.sampling_rate:
         from .resample import Resample
         to_out = Resample(model.sampling_rate, out_rate)
+    if a.pitch_shift and any(f.suffix != ".wav" for f in files):
+        raise ValueError(f"--pitch-shift takes .wav inputs ({next(f for f in files if f.suffix != '.wav')} is a mel): the shift is applied to the "
+                         "waveform in front of the mel front-end")
     if a.batch_size:
         return _main_batched(a, model, files, base)
     if a.sessions:
@@ -515,6 +537,7 @@ def main(argv=None):
             if sr != model.sampling_rate:      # test.py:54: librosa.load(..., sr=cfg.model.sampling_rate)
                 from .resample import Resample
                 y = Resample(sr, model.sampling_rate)(y.to(model.device))
+            y = _pitch_shifted(a, model, y.to(model.device))      # test.py:61-62
             y = torch.nn.functional.pad(y, (0, model.hop_length - (model.hop_length % y.shape[-1])))   # as written upstream
             mel = model.mel_transform(y.to(model.device).squeeze(1))
         else:

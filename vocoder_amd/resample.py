@@ -171,11 +171,18 @@ class Resample(nn.Module):
 
     ``lengths`` (a list or an int tensor, one entry per row of the flattened leading dimensions) makes the call ragged: row ``b`` holds
     ``lengths[b] <= L`` samples, its outputs are bit-identical to the row run alone and exact zeros follow them.  ``stream(batch, max_chunk)``
-    gives the streaming form.  ``orig_freq == new_freq`` returns the input, as torchaudio does."""
+    gives the streaming form.  ``orig_freq == new_freq`` returns the input, as torchaudio does.
+
+    ``table="lds"`` keeps the filter's table in LDS (``fv_resample_create``: rate pairs whose table fits, roughly ``n * kp <= 7000``);
+    ``table="global"`` leaves it in global memory (``fv_global_resample_create``: any pair, e.g. 44101 -> 48000).  Where both exist their
+    outputs agree bit for bit."""
 
     def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, resampling_method: str = "sinc_interp_hann",
-                 lowpass_filter_width: int = 6, rolloff: float = 0.99, beta: float | None = None):
+                 lowpass_filter_width: int = 6, rolloff: float = 0.99, beta: float | None = None, table: str = "lds"):
         super().__init__()
+        if table not in ("lds", "global"):
+            raise ValueError(f"table {table!r} is neither 'lds' nor 'global'")
+        self.table = table
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
         self.resampling_method, self.lowpass_filter_width, self.rolloff, self.beta = resampling_method, int(lowpass_filter_width), rolloff, beta
         self.design = design(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
@@ -197,7 +204,8 @@ class Resample(nn.Module):
             h = ctypes.c_void_p()
             cfg = _config(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
             with torch.cuda.device(idx):
-                check(_lib.lib().fv_resample_create(ctypes.byref(cfg), ctypes.byref(h)))
+                create = _lib.lib().fv_global_resample_create if self.table == "global" else _lib.lib().fv_resample_create
+                check(create(ctypes.byref(cfg), ctypes.byref(h)))
             self._handles[idx] = h
         return h
 
