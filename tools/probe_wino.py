@@ -71,7 +71,7 @@ for cfg in ([] if os.environ.get('PROBE_TIMED_ONLY') else range(3)):
         worst = max(worst, case(cin, cout, k, d, B, T, False, cfg=cfg))
         worst = max(worst, case(cin, cout, k, d, B, T, False, silu=False, with_res=False, cfg=cfg))
 print(f"worst wino-direct deviation on the small cases: {worst:.2e}")
-for (c, T, B, cfgs) in [(128, 5504, 32, (0,)), (256, 688, 32, (0,)), (64, 11008, 32, (1,)), (32, 12032, 64, (2,))]:   # (3, 4 with -DFV_X_WINO_NT2)
+for (c, T, B, cfgs) in [(128, 5504, 32, (0,)), (256, 688, 32, (0,)), (64, 11008, 32, (1,)), (32, 12032, 64, (2,))]:
     for k in (3, 7, 11):
         for d in (1, 5):
             for cfg in cfgs:

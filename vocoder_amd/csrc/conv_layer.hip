@@ -508,17 +508,13 @@ static Routed run_wino_latency(const ConvLayer& L, const ConvRun& r, ConvParams 
 static Routed run_winograd(const ConvLayer& L, const ConvRun& r, const ConvParams& p, long long tout, hipStream_t stream) {
     const int algo = effective_algo();
     if (algo == FV_CONV_ALGO_DIRECT || !L.wino || p.x2 || L.M < knobs().wino_min_m) return std::nullopt;
-    static const int wdims[WINO_COUNT][2] = {{128, 32}, {64, 64}, {32, 128}, {128, 64}, {64, 128}};
+    static const int wdims[WINO_COUNT][2] = {{128, 32}, {64, 64}, {32, 128}};
     // 64 accumulator registers per wave (32 output pairs x 4 planes): three waves per SIMD; the 128 x 64-pair tile (two waves) measured
     // 8 % slower on the headline's C = 128 stage although it fetches each weight fragment half as often
     int wcfg = L.M > 64 ? WINO_128x32 : L.M > 32 ? WINO_64x64 : WINO_32x128;
     const long long np = (long long)L.dil * ((tout + 2 * L.dil - 1) / (2 * L.dil));   // pair columns: whole blocks of 2 D samples
     const long long nq = (long long)L.dil * ((tout + 4 * L.dil - 1) / (4 * L.dil));   // quad columns: whole blocks of 4 D samples
-#ifdef FV_X_WINO_NT2
-    if (knobs().wino_cfg >= 0 && knobs().wino_cfg < WINO_COUNT) wcfg = knobs().wino_cfg;
-#else
     if (knobs().wino_cfg >= 0 && knobs().wino_cfg <= WINO_32x128) wcfg = knobs().wino_cfg;
-#endif
     const int mb = wdims[wcfg][0], pairs = wdims[wcfg][1];
     const long long blocks = (long long)r.batch * ((L.M + mb - 1) / mb) * ((np + pairs - 1) / pairs);
     const long long min_blocks = knobs().wino_min_blocks >= 0 ? knobs().wino_min_blocks : num_cus();

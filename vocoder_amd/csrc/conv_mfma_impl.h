@@ -217,9 +217,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
     conv_epilogue_cols<MT, NT>(p, acc, b, mt0, coff, cok, lane);
 }
 
-#ifndef FV_X_INTERLEAVE
-#define FV_X_INTERLEAVE 1
-#endif
 #ifndef FV_X_DA
 #define FV_X_DA 3
 #endif
@@ -247,12 +244,8 @@ constexpr int subs_for(int ks, int w) {
 // the way into LDS instead of by a pass of its own (mean_of_three_kernel: 4 tensors of HBM traffic, 65 us per wide stage at B = 32,
 // ~10 us of launch + dependency per stage for a single clip).  Two more staging register sets: two workgroups per CU.
 template <int KS, int DIL, int WM, int WN, int MT, int NT, bool SUM3 = false>
-#ifndef FV_X_SUM3_OCC
-#define FV_X_SUM3_OCC 0
-#endif
-// (FV_X_SUM3_OCC=1, experiment: asks for four / three workgroups per CU in the narrow SUM3 tiles — the HBM-bound last upsamplers are bound by bytes in flight.
-//  Measured nothing on top of dropping the flat-mode row plan from these instances, which already took the 64 x 128 tile from two to three: LOG R6.12)
-__global__ __launch_bounds__(256, (SUM3 ? (FV_X_SUM3_OCC && MT * NT == 1 ? 4 : (FV_X_SUM3_OCC && MT * NT == 2 ? 3 : 2)) : (NT >= 4 ? 2 : (MT * NT >= 4 ? 3 : 4)))) void conv_mfma_kernel(const ConvParams p) {
+// (asking for four / three workgroups per CU in the narrow SUM3 tiles measured nothing: LOG R6.12)
+__global__ __launch_bounds__(256, (SUM3 ? 2 : (NT >= 4 ? 2 : (MT * NT >= 4 ? 3 : 4)))) void conv_mfma_kernel(const ConvParams p) {
     static_assert(WM * WN == 4, "4 waves per workgroup");
     constexpr int N_BLK = WN * NT * 32;
     constexpr int SPAN = (KS - 1) * DIL;
@@ -461,48 +454,30 @@ __global__ __launch_bounds__(256, (SUM3 ? (FV_X_SUM3_OCC && MT * NT == 1 ? 4 : (
         load_b(b_cur, xsb, 0, 0);
 #pragma unroll
         for (int st = 0; st < STEPS; ++st) {
-#if FV_X_INTERLEAVE
             // the step's memory operations (MT weight loads for k-step st + DA, 4 NT LDS fragment reads for k-step st + 1)
             // spread between its MFMAs instead of issued in a burst before them: an in-order wave hides a memory
             // instruction's issue time only under an MFMA that is already executing (gemm_pw.hip, round 2)
-            {
-                constexpr int NM = 4 * MT * NT, NLDX = MT + 4 * NT;
-                const int sub_n = (st + 1) / KS, j_n = (st + 1) % KS;
+            constexpr int NM = 4 * MT * NT, NLDX = MT + 4 * NT;
+            const int sub_n = (st + 1) / KS, j_n = (st + 1) % KS;
 #pragma unroll
-                for (int m = 0; m < NM; ++m) {
-                    const int pp = m / (MT * NT), i = (m / NT) % MT, jn = m % NT;
-                    const float av = pp == 0 ? aq[0][i].x : pp == 1 ? aq[0][i].y : pp == 2 ? aq[0][i].z : aq[0][i].w;
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b_cur[pp][jn], acc[i][jn], 0, 0, 0);
+            for (int m = 0; m < NM; ++m) {
+                const int pp = m / (MT * NT), i = (m / NT) % MT, jn = m % NT;
+                const float av = pp == 0 ? aq[0][i].x : pp == 1 ? aq[0][i].y : pp == 2 ? aq[0][i].z : aq[0][i].w;
+                acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b_cur[pp][jn], acc[i][jn], 0, 0, 0);
 #pragma unroll
-                    for (int k = 0; k < NLDX; ++k) {
-                        if (k * NM / NLDX == m) {
-                            if (k < MT) {
-                                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, wbase[k] + gchunk_b + st * 1024, 0);
-                                aq[DA][k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-                            } else if (st + 1 < STEPS) {
-                                const int pp2 = (k - MT) / NT, jn2 = (k - MT) % NT;
-                                b_nxt[pp2][jn2] = xsb[b_lane + (sub_n * kChunk + 2 * pp2) * WL + jn2 * 32 + j_n * DIL];
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
+                for (int k = 0; k < NLDX; ++k) {
+                    if (k * NM / NLDX == m) {
+                        if (k < MT) {
+                            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, wbase[k] + gchunk_b + st * 1024, 0);
+                            aq[DA][k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+                        } else if (st + 1 < STEPS) {
+                            const int pp2 = (k - MT) / NT, jn2 = (k - MT) % NT;
+                            b_nxt[pp2][jn2] = xsb[b_lane + (sub_n * kChunk + 2 * pp2) * WL + jn2 * 32 + j_n * DIL];
                         }
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
             }
-#else
-            load_a(aq[DA], gchunk_b + st * 1024);
-            if (st + 1 < STEPS) load_b(b_nxt, xsb, (st + 1) / KS, (st + 1) % KS);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int pp = 0; pp < 4; ++pp) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    const float av = pp == 0 ? aq[0][i].x : pp == 1 ? aq[0][i].y : pp == 2 ? aq[0][i].z : aq[0][i].w;
-#pragma unroll
-                    for (int jn = 0; jn < NT; ++jn)
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b_cur[pp][jn], acc[i][jn], 0, 0, 0);
-                }
-            }
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int d = 0; d < DA; ++d)

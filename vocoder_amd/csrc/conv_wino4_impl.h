@@ -181,13 +181,7 @@ __global__ __launch_bounds__(128 * WM, (WM == 2 ? FV_X_WINO4_OCC : 4)) void conv
     for (int d = 0; d < DA; ++d) aq[d] = load_a(d * 1024);
     for (int c = 0; c < nch; ++c) {
         float* xsb = xs + (c & 1) * (CH * ROW);
-#ifdef FV_X_WINO4_PRIO
-        __builtin_amdgcn_s_setprio(FV_X_WINO4_PRIO);
-#endif
         store_chunk(xsb);
-#ifdef FV_X_WINO4_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         __syncthreads();
         if (c < 12) FV_CV_STAMP(1 + c);
         if (c + 1 < nch) load_chunk(c + 1);

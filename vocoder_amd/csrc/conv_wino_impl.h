@@ -222,7 +222,6 @@ __global__ __launch_bounds__(256, (NT == 1 ? FV_X_WINO_OCC1 : 2)) void conv_wino
     // output transform + the shared fused epilogue: n-tile jn of the wave becomes two column sets, t0(n) and t0(n) + D.
     // (An 8-byte store per pair at D = 1 measured 1.75 x the HBM write bytes of the two 4-byte stores — 158 vs 90 MB per launch by
     // WRITE_SIZE — and no time gain: not used.)
-#ifndef FV_X_WINO_NO_LEAN_EPI
     // The common case — whole 32-row tiles, bias [+ residual] [+ post-activation], plain store (every ResBlock / AMPBlock conv of the
     // three-stream forward) —
     // without per-element offset registers: a row is the SGPR offset of the buffer instruction, the column the VGPR one (the range check
@@ -303,7 +302,6 @@ __global__ __launch_bounds__(256, (NT == 1 ? FV_X_WINO_OCC1 : 2)) void conv_wino
         FV_CV_STAMP(14);
         return;
     }
-#endif
 #pragma unroll
     for (int jn = 0; jn < NT; ++jn) {
         f32x16 out[1][2];
@@ -331,10 +329,6 @@ inline bool launch_wino_cfg(const ConvParams& p0, int cfg, int batch, hipStream_
         case WINO_128x32: hipLaunchKernelGGL((conv_wino_kernel<KS, DIL, 4, 1, 1>), dim3(grid), dim3(256), 0, s, p); return true;
         case WINO_64x64: hipLaunchKernelGGL((conv_wino_kernel<KS, DIL, 2, 2, 1>), dim3(grid), dim3(256), 0, s, p); return true;
         case WINO_32x128: hipLaunchKernelGGL((conv_wino_kernel<KS, DIL, 1, 4, 1>), dim3(grid), dim3(256), 0, s, p); return true;
-#ifdef FV_X_WINO_NT2
-        case WINO_128x64: hipLaunchKernelGGL((conv_wino_kernel<KS, DIL, 4, 1, 2>), dim3(grid), dim3(256), 0, s, p); return true;
-        case WINO_64x128: hipLaunchKernelGGL((conv_wino_kernel<KS, DIL, 2, 2, 2>), dim3(grid), dim3(256), 0, s, p); return true;
-#endif
         default: return false;
     }
 }

@@ -29,7 +29,7 @@ struct WLGeom {
     static constexpr int PLANE = 8 * PW;                      // one plane of the wave's 8-channel block: [ch][PW]
     // planes d0 d1 d2 d3 E O; k = 3 with the register transform (K3R): E O only — a third of the LDS, so that more of a single clip's concurrent
     // workgroups (three branches: ~5 per CU wanted, the k = 7 / 11 kernels hold 53 - 61 KB each) are resident together
-    static constexpr bool K3R = KS == 3 && FV_X_PW_K3_REG != 0;
+    static constexpr bool K3R = KS == 3;
     static constexpr int EOP = K3R ? 0 : 4;                   // plane index of E (O follows)
     static constexpr int WAVE_F = (K3R ? 2 : 6) * PLANE;
     static constexpr int XCH_F = 4 * 4 * 2 * NT * MT * 64;    // the reduction's exchange buffer

@@ -310,9 +310,8 @@ constexpr bool splitk_direct_shape(int ks, int dil, int nt, bool sum3) {
 enum TileCfg : int { TILE_128x128 = 0, TILE_64x256 = 1, TILE_32x512 = 2, TILE_128x64 = 3, TILE_32x128 = 4, TILE_64x128 = 5, TILE_SPLITK_32x64 = 6, TILE_SPLITK_32x32 = 7, TILE_256x64 = 8, TILE_256x32 = 9, TILE_128x96 = 10, TILE_COUNT };
 void tile_dims(int cfg, int* m_blk, int* n_blk);
 // conv_wino_impl.h: Winograd F(2,3) variant of the dilated "same" convs; tiles = output rows x output PAIRS per workgroup
-// (two-n-tile variants — 128 x 64 and 64 x 128 pairs, 128 accumulator registers, two waves per SIMD — measured 8 % slower: LOG R3.16;
-//  -DFV_X_WINO_NT2 builds them back in as configurations 3 and 4)
-enum WinoCfg : int { WINO_128x32 = 0, WINO_64x64 = 1, WINO_32x128 = 2, WINO_128x64 = 3, WINO_64x128 = 4, WINO_COUNT };
+// (two-n-tile variants — 128 x 64 and 64 x 128 pairs, 128 accumulator registers, two waves per SIMD — measured 8 % slower: LOG R3.16)
+enum WinoCfg : int { WINO_128x32 = 0, WINO_64x64 = 1, WINO_32x128 = 2, WINO_COUNT };
 // p.wp = the layer's d_wpw, p.n_tiles in pair columns
 bool launch_conv_wino_k3(const ConvParams& p, int cfg, int batch, hipStream_t s);
 bool launch_conv_wino_k7(const ConvParams& p, int cfg, int batch, hipStream_t s);

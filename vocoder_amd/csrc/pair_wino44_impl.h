@@ -49,13 +49,8 @@ struct PQGeom {
     // two, and the transform's vector instructions come from the wave that owns the MFMA stream instead of a phase of their own (conv_wino44_impl.h's in-loop
     // staging, LOG R6.2).  The second buffer takes the raw centre tile's place in LDS (three workgroups per CU: 53.3 KB each): the residual is re-read
     // from global memory — the lines this workgroup staged ~20 us earlier, requested before c2's loop.
-#ifndef FV_X_PQ_INLOOP
-#define FV_X_PQ_INLOOP 1
-#endif
-#ifndef FV_X_PQ_INLOOP16
-#define FV_X_PQ_INLOOP16 0
-#endif
-    static constexpr bool INLOOP = FV_X_PQ_INLOOP && (C == 32 || (FV_X_PQ_INLOOP16 && C == 16 && DIL == 1));
+    // (the same in-loop form at C = 16, D = 1 measured inside the noise: LOG R6.4)
+    static constexpr bool INLOOP = C == 32;
     static constexpr bool XRES = !INLOOP;                // raw centre tile in LDS
     static constexpr int NVB = INLOOP ? 2 : 1;           // V buffers
     static constexpr int X_F = C * SX, XR_F = XRES ? C * XS + 16 : 0;
@@ -142,25 +137,21 @@ __device__ __forceinline__ void pq_stage_window(const float* __restrict__ xb, in
 // X planes of the chunk's 8 channel rows -> seven V planes [plane][channel][column] (conv_wino44_impl.h's transform: symmetric points, the
 // even / odd parts shared by +-a).  32 threads per channel row, consecutive columns.
 // FULL whole slots of TPR consecutive columns per channel row; the TW columns left over (WD = 64 + D (NG - 1): 1 ... 10 of a 32-column slot) are
-// flattened over (row, column) into the first CH * TW threads — the waves past them skip the slot instead of running it all but empty
-// (-DFV_X_PQ_TAIL=0: the masked third slot of every wave, A/B builds).
+// flattened over (row, column) into the first CH * TW threads — the waves past them skip the slot instead of running it all but empty.
 // In pieces (round 6): load() = the 7 (FULL + 1) LDS reads, slot(j) / tail_slot() = one lattice element's 21 FMA-class instructions and seven LDS writes;
 // pq_transform() runs them as a phase, the in-loop form (PQGeom::INLOOP) spreads them over the previous chunk's matrix loop.
-#ifndef FV_X_PQ_TAIL
-#define FV_X_PQ_TAIL 1
-#endif
 template <class G, int DX, int WD>
 struct PQXform {
     static constexpr int TPR = 256 / G::CH;
-    static constexpr int FULL = FV_X_PQ_TAIL ? WD / TPR : (WD + TPR - 1) / TPR, TW = FV_X_PQ_TAIL ? WD - FULL * TPR : 0;
+    static constexpr int FULL = WD / TPR, TW = WD - FULL * TPR;
     static constexpr int PS = G::CH * G::PV;   // plane stride
     static constexpr int NP = 1 + FULL + (TW > 0 ? 1 : 0);   // pieces: load, FULL slots, the tail slot
-    int xo, vo, xt, vt, c0;
+    int xo, vo, xt, vt;
     bool tail;
     float a[FULL > 0 ? FULL : 1][7], t[7];
     __device__ __forceinline__ void init(int tid) {
         const int row = tid / TPR;
-        c0 = tid % TPR;
+        const int c0 = tid % TPR;
         xo = row * G::SX + c0;
         vo = row * G::PV + c0;
         tail = TW > 0 && tid < G::CH * TW;
@@ -199,7 +190,7 @@ struct PQXform {
     }
     template <int J>
     __device__ __forceinline__ void slot(float* __restrict__ v) {
-        if (FV_X_PQ_TAIL || TPR * (J + 1) <= WD || c0 + TPR * J < WD) xform7(a[J], v + vo + TPR * J);
+        xform7(a[J], v + vo + TPR * J);
     }
     __device__ __forceinline__ void tail_slot(float* __restrict__ v) {
         if constexpr (TW > 0) {

@@ -35,14 +35,11 @@ constexpr int pw_da(int ks, int mt) { return mt == 2 ? (ks == 7 ? 4 : 3) : 4; }
 
 // k = 3 is ONE tap group: every transformed value d0..d3 of a (channel, pair column) feeds exactly one matrix product per m-tile, in the wave that owns
 // the column — so the narrow k = 3 pairs form their B operands in registers straight from the E / O planes (pw_gemm_k3) instead of passing them
-// through a d-plane buffer in LDS: no chunk buffer, no barrier inside a conv, a third of the LDS instructions.  0 = the LDS transform (A/B builds).
-#ifndef FV_X_PW_K3_REG
-#define FV_X_PW_K3_REG 1
-#endif
+// through a d-plane buffer in LDS: no chunk buffer, no barrier inside a conv, a third of the LDS instructions.
 
 template <int KS, int DIL, int C, int CH>
 struct PWGeom {
-    static constexpr bool K3R = KS == 3 && FV_X_PW_K3_REG != 0;
+    static constexpr bool K3R = KS == 3;
     static_assert(C == 16 || C == 32, "16x16x4 kernel: one or two 16-row m-tiles");
     static_assert(CH == 8 || CH == 16, "chunk = 8 or 16 channels");
     static_assert(C % CH == 0 && CH * (C / 16) >= 16, "a chunk holds whole weight fragments");
@@ -210,9 +207,6 @@ __device__ __forceinline__ void pw_gemm_chunk(f32x4w (&acc)[4][G::MT], const flo
     for (int i = 0; i < NB; ++i) b_cur[i] = *b_addr(i / KST, i % KST);
     static_for<G::NMS>([&](auto ms_c) __attribute__((always_inline)) {
         constexpr int ms = decltype(ms_c)::value;
-#ifdef FV_X_PW_SKIP
-        if constexpr (ms * 8 >= G::NMS * 5) return;   // timing experiment (wrong results): 5 of every 8 products, as F(4,4) tap groups would leave
-#endif
         constexpr int f0 = ms * U;
         constexpr int NLDX = U + NB;   // memory operations of this macro-step: U weight loads (DA fragments ahead), NB LDS reads (next macro-step)
         // each of them is requested BETWEEN two MFMAs: an in-order wave hides a memory instruction's issue time only under a matrix
@@ -447,11 +441,7 @@ __global__ __launch_bounds__(256, 4) void pair_wino16_kernel(const PairParams p)
         const bool accum = p.out_mode == OUT_ACCUM;
         // the lane's two outputs are adjacent samples: one 8-byte store (and accumulate load) per row where every row starts 8-byte aligned — whole 64-byte
         // lines per 16 lanes instead of two passes over every other float (round 5; the 16-byte form of conv_wino44's epilogue, LOG R5.3)
-#ifdef FV_X_NO_PAIR8
-        const bool pair8 = false;
-#else
         const bool pair8 = (T & 1) == 0 && ((unsigned long long)p.y & 7ull) == 0;
-#endif
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const f32x4w y0 = (acc[0][i] + acc[1][i]) + acc[2][i];
@@ -515,9 +505,8 @@ __global__ __launch_bounds__(256, 4) void pair_wino16_kernel(const PairParams p)
 // XRES: the raw tile for the residual stays in LDS (C = 64 at most: at C = 128 it does not fit next to the window); otherwise the last
 // epilogue reads x again, requested before c2's matrix loop starts.
 // ---------------------------------------------------------------------------------------------------------------------------------------
-template <int KS, int DIL, int C, int CH, int NT, bool XRES_, bool DBUF_ = false>
+template <int KS, int DIL, int C, int CH, int NT, bool XRES_>
 struct PW32Geom {
-    static constexpr bool DBUF = DBUF_;                  // two chunk buffers: one workgroup barrier per chunk instead of two
     static_assert(C == 64 || C == 128, "one 32-row m-tile per wave");
     static_assert(CH % 8 == 0 && C % CH == 0, "chunks of whole 8-channel fragments");
     static constexpr bool XRES = XRES_;
@@ -536,8 +525,7 @@ struct PW32Geom {
     static constexpr int PD = pw_up(WD1, 8, 4);          //  for CH = 8; the 16-lane row segments of CH = 16 want 4 PD == 16 (mod 32))
     static constexpr int SE = 2 * PE, SD = 4 * PD;
     static constexpr int XS = TT + 2;
-    static constexpr int DB_F = CH * SD;                 // one chunk buffer
-    static constexpr int EO_F = C * SE, D_F = (DBUF ? 2 : 1) * DB_F, XR_F = XRES ? C * XS + 16 : 0;
+    static constexpr int EO_F = C * SE, D_F = CH * SD, XR_F = XRES ? C * XS + 16 : 0;
     static constexpr int TRASH = EO_F + D_F + XR_F;
     static constexpr int LDS_FLOATS = TRASH + 4;
     static constexpr int CHN = CH;
@@ -587,9 +575,9 @@ __device__ __forceinline__ void pw32_gemm_chunk(f32x16 (&acc)[4][1], const float
     });
 }
 
-template <int KS, int DIL, int C, int CH, bool XRES, bool DBUF>
+template <int KS, int DIL, int C, int CH, bool XRES>
 __global__ __launch_bounds__(256, 2) void pair_wino32_kernel(const PairParams p) {
-    using G = PW32Geom<KS, DIL, C, CH, 1, XRES, DBUF>;
+    using G = PW32Geom<KS, DIL, C, CH, 1, XRES>;
     constexpr int DA = G::DA, NCHK = C / CH, WN = G::WN;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* EO = lds;
@@ -646,24 +634,11 @@ __global__ __launch_bounds__(256, 2) void pair_wino32_kernel(const PairParams p)
     __syncthreads();
 
     // ---- c1 ----
-    if constexpr (DBUF) {
-        // chunk c + 1 is transformed into the other buffer BEFORE chunk c's matrix loop: one barrier per chunk, and the transform's LDS
-        // round trip runs under the matrix instructions that follow it
-        pw_transform<G, DIL, G::WD1>(EO, Db, tid);
+    for (int c = 0; c < NCHK; ++c) {
+        pw_transform<G, DIL, G::WD1>(EO + c * CH * G::SE, Db, tid);
         __syncthreads();
-        for (int c = 0; c < NCHK; ++c) {
-            if (c + 1 < NCHK) pw_transform<G, DIL, G::WD1>(EO + (c + 1) * CH * G::SE, Db + ((c + 1) & 1) * G::DB_F, tid);
-            pw32_gemm_chunk<G, DIL>(acc, dl + (c & 1) * G::DB_F, el + c * CH * G::SE, w1rs, wvoff,
-                                    __builtin_amdgcn_readfirstlane(wbase + (c * G::NF4 + DA) * 1024), aq);
-            __syncthreads();
-        }
-    } else {
-        for (int c = 0; c < NCHK; ++c) {
-            pw_transform<G, DIL, G::WD1>(EO + c * CH * G::SE, Db, tid);
-            __syncthreads();
-            pw32_gemm_chunk<G, DIL>(acc, dl, el + c * CH * G::SE, w1rs, wvoff, __builtin_amdgcn_readfirstlane(wbase + (c * G::NF4 + DA) * 1024), aq);
-            __syncthreads();
-        }
+        pw32_gemm_chunk<G, DIL>(acc, dl, el + c * CH * G::SE, w1rs, wvoff, __builtin_amdgcn_readfirstlane(wbase + (c * G::NF4 + DA) * 1024), aq);
+        __syncthreads();
     }
 #pragma unroll
     for (int d = 0; d < DA; ++d) aq[d] = load_w(w2rs, d);
@@ -705,11 +680,7 @@ __global__ __launch_bounds__(256, 2) void pair_wino32_kernel(const PairParams p)
     const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (long long)b * C * T), 0, (unsigned)(C * T) * 4u, 0x00020000);
     // the lane's two outputs are adjacent samples: 8-byte residual loads / accumulate loads / stores where every row of x and y starts 8-byte aligned
     // (pair_wino16_kernel's epilogue)
-#ifdef FV_X_NO_PAIR8
-    const bool pair8 = false;
-#else
     const bool pair8 = (T & 1) == 0 && (((unsigned long long)p.y | (unsigned long long)p.x) & 7ull) == 0;
-#endif
     float ra[XRES ? 1 : 16], rb[XRES ? 1 : 16];
     if constexpr (!XRES) {
         const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (unsigned)(C * T) * 4u, 0x00020000);
@@ -732,22 +703,11 @@ __global__ __launch_bounds__(256, 2) void pair_wino32_kernel(const PairParams p)
     __syncthreads();
 
     // ---- c2 (dilation 1) ----
-    if constexpr (DBUF) {
-        pw_transform<G, 1, G::WD2>(EO, Db, tid);
+    for (int c = 0; c < NCHK; ++c) {
+        pw_transform<G, 1, G::WD2>(EO + c * CH * G::SE, Db, tid);
         __syncthreads();
-        for (int c = 0; c < NCHK; ++c) {
-            if (c + 1 < NCHK) pw_transform<G, 1, G::WD2>(EO + (c + 1) * CH * G::SE, Db + ((c + 1) & 1) * G::DB_F, tid);
-            pw32_gemm_chunk<G, 1>(acc, dl + (c & 1) * G::DB_F, el + c * CH * G::SE, w2rs, wvoff,
-                                  __builtin_amdgcn_readfirstlane(wbase + (c * G::NF4 + DA) * 1024), aq);
-            if (c + 1 < NCHK) __syncthreads();
-        }
-    } else {
-        for (int c = 0; c < NCHK; ++c) {
-            pw_transform<G, 1, G::WD2>(EO + c * CH * G::SE, Db, tid);
-            __syncthreads();
-            pw32_gemm_chunk<G, 1>(acc, dl, el + c * CH * G::SE, w2rs, wvoff, __builtin_amdgcn_readfirstlane(wbase + (c * G::NF4 + DA) * 1024), aq);
-            if (c + 1 < NCHK) __syncthreads();
-        }
+        pw32_gemm_chunk<G, 1>(acc, dl, el + c * CH * G::SE, w2rs, wvoff, __builtin_amdgcn_readfirstlane(wbase + (c * G::NF4 + DA) * 1024), aq);
+        if (c + 1 < NCHK) __syncthreads();
     }
 
     // ---- c2 epilogue: + raw x -> y ----
@@ -813,9 +773,6 @@ __global__ __launch_bounds__(256, 2) void pair_wino32_kernel(const PairParams p)
 #ifndef FV_X_PW_CH64
 #define FV_X_PW_CH64 8
 #endif
-#ifndef FV_X_PW_DBUF
-#define FV_X_PW_DBUF 0
-#endif
 #ifndef FV_X_PW_CH128
 #define FV_X_PW_CH128 8
 #endif
@@ -823,15 +780,15 @@ __global__ __launch_bounds__(256, 2) void pair_wino32_kernel(const PairParams p)
 #define FV_X_PW_XRES64 1   // the raw tile stays in LDS at C = 64 (two workgroups per CU; measured equal to three without it, at 1.0 x the traffic)
 #endif
 
-template <int KS, int DIL, int C, int CH, bool XRES, bool DBUF>
+template <int KS, int DIL, int C, int CH, bool XRES>
 inline bool launch_pair_wino32_one(const PairParams& p, int batch, hipStream_t s) {
-    using G = PW32Geom<KS, DIL, C, CH, 1, XRES, DBUF>;
+    using G = PW32Geom<KS, DIL, C, CH, 1, XRES>;
     PairParams q = p;
     q.n_tiles = (p.T + G::TT - 1) / G::TT;
     q.batch = batch;
     const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float);
-    if (!FV_ENSURE_DYN_LDS((pair_wino32_kernel<KS, DIL, C, CH, XRES, DBUF>), lds)) return false;
-    hipLaunchKernelGGL((pair_wino32_kernel<KS, DIL, C, CH, XRES, DBUF>), dim3((batch * q.n_tiles + 7) / 8 * 8), dim3(256), lds, s, q);
+    if (!FV_ENSURE_DYN_LDS((pair_wino32_kernel<KS, DIL, C, CH, XRES>), lds)) return false;
+    hipLaunchKernelGGL((pair_wino32_kernel<KS, DIL, C, CH, XRES>), dim3((batch * q.n_tiles + 7) / 8 * 8), dim3(256), lds, s, q);
     return true;
 }
 
@@ -858,8 +815,8 @@ inline bool launch_pair_wino16_k(const PairParams& p, int C, int dil, int batch,
         if (C == 16) return launch_pair_wino16_one<KS, D, 16, 16>(p, batch, s);            \
         if (C == 32) return launch_pair_wino16_one<KS, D, 32, FV_X_PW_CH32>(p, batch, s);  \
         if constexpr (KS == 3) {                                                           \
-            if (C == 64) return launch_pair_wino32_one<KS, D, 64, FV_X_PW_CH64, FV_X_PW_XRES64 != 0, FV_X_PW_DBUF != 0>(p, batch, s);   \
-            if (C == 128) return launch_pair_wino32_one<KS, D, 128, FV_X_PW_CH128, false, FV_X_PW_DBUF != 0>(p, batch, s);              \
+            if (C == 64) return launch_pair_wino32_one<KS, D, 64, FV_X_PW_CH64, FV_X_PW_XRES64 != 0>(p, batch, s);   \
+            if (C == 128) return launch_pair_wino32_one<KS, D, 128, FV_X_PW_CH128, false>(p, batch, s);              \
         }                                                                                  \
     }
     FV_PW_CASE(1) FV_PW_CASE(3) FV_PW_CASE(5)

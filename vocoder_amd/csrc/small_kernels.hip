@@ -311,9 +311,6 @@ fv_status launch_conv_narrow(const float* x, const float* w, const float* bias, 
 constexpr int AA_TT = 1024;
 constexpr int AA_ODD = AA_TT + 64;   // offset of the odd-sample array behind the even-sample one (a multiple of 64 dwords)
 
-// sin(z)^2 with a three-constant Cody-Waite reduction to [-pi/2, pi/2] and an odd degree-11 polynomial: |error| < 2e-7 for
-// |z| < 1e3 (the snake argument alpha*u stays far below that).  libm's sinf costs ~4x more VALU work and made this
-// kernel compute- instead of bandwidth-bound.  The sign lost by the reduction does not matter for the square.
 // Packed math: gfx950 issues a wave64 v_fma_f32 in ~4.4 cycles and a v_pk_fma_f32 (twice the work) in ~4.9
 // (tools/ubench/valu_rates.hip), and this kernel spends ~80 VALU instructions per element when written with scalar FMAs.
 // Both phases are arranged so that every FIR step is one packed FMA on a register PAIR that one ds_read2_b32 delivers:
@@ -322,54 +319,27 @@ constexpr int AA_ODD = AA_TT + 64;   // offset of the odd-sample array behind th
 //   phase 3: (s0, s1) += (dn[2q], dn[2q+1]) * (A_odd(t+q-3), A_even(t+q-2))   -- A[2m'+1], A[2m'+2]: consecutive again
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ f32x2 sin_squared2(f32x2 z) {
-    f32x2 k;
-    k.x = rintf(z.x * 0.318309886183790672f);
-    k.y = rintf(z.y * 0.318309886183790672f);
-    f32x2 r = __builtin_elementwise_fma(k, (f32x2)(-3.140625f), z);
-    r = __builtin_elementwise_fma(k, (f32x2)(-9.67502593994140625e-4f), r);
-    r = __builtin_elementwise_fma(k, (f32x2)(-1.509957990978376432e-7f), r);
-    const f32x2 r2 = r * r;
-    f32x2 p = __builtin_elementwise_fma(r2, (f32x2)(-2.50521083854417188e-8f), (f32x2)(2.75573192239858925e-6f));
-    p = __builtin_elementwise_fma(r2, p, (f32x2)(-1.98412698412698413e-4f));
-    p = __builtin_elementwise_fma(r2, p, (f32x2)(8.33333333333333322e-3f));
-    p = __builtin_elementwise_fma(r2, p, (f32x2)(-1.66666666666666657e-1f));
-    const f32x2 sn = __builtin_elementwise_fma(r * r2, p, r);
-    return sn * sn;
-}
-
 // Snake on a sample pair: a = u + inv_beta * sin(alpha u)^2 = (u + hb) - hb * cos(2 alpha u), hb = inv_beta / 2, with the hardware cosine
 // (v_cos_f32 takes revolutions: cos(2 pi x), x = u * alpha / pi, reduced by v_fract_f32 — the instruction's own domain is |x| <= 256).
 // Seven instructions per pair instead of the polynomial's sixteen: what this kernel costs is its VALU INSTRUCTION COUNT — beside
 // the fp32 MFMAs of the conv kernels that share the SIMDs (other ResBlock branches) every VALU instruction, plain, packed or
 // transcendental, takes ~12 - 20 cycles out of the matrix stream (tools/ubench/mfma_mix.hip).  Accuracy against sin^2 in double
-// (same ubench): 3.8e-7 for |alpha u| <= 5, 3.1e-6 up to 40 with the plain product u * al_pi (the polynomial: 2.9e-7 / 3.2e-7) — hence the
-// compensated phase below (four more instructions per pair; FV_X_SNAKE_FAST builds the plain product, FV_X_SNAKE_POLY the polynomial).
+// (same ubench): 3.8e-7 for |alpha u| <= 5, 3.1e-6 up to 40 with the plain product u * al_pi (a degree-11 polynomial: 2.9e-7 / 3.2e-7) — hence the
+// compensated phase below (four more instructions per pair).
 // The phase u * alpha / pi is formed to better than fp32: ph = fl(u * al_pi) plus the product's exact residual (one FMA) plus u times the
 // low part of alpha / pi (one FMA) — without them the cosine's argument carries two fp32 roundings that grow with |alpha u| (3e-6 at
 // |alpha u| = 40, 1e-5 at the |alpha u| ~ 100 a trained log-scale alpha of e^3 reaches), times inv_beta / 2 in the output.
 __device__ __forceinline__ float snake_al_lo(float al, float al_pi) {   // alpha / pi - al_pi: product residual + alpha * (1/pi - fl(1/pi))
     return fmaf(al, 0.318309886183790672f, -al_pi) + al * 1.2841276653e-8f;
 }
-__device__ __forceinline__ f32x2 snake2(f32x2 u, float al, float ib, float al_pi, float al_lo, float hb) {
-#ifdef FV_X_SNAKE_POLY
-    (void)al_pi; (void)al_lo; (void)hb;
-    return __builtin_elementwise_fma((f32x2)(ib), sin_squared2(u * al), u);
-#else
-    (void)al; (void)ib;
+__device__ __forceinline__ f32x2 snake2(f32x2 u, float al_pi, float al_lo, float hb) {
     const f32x2 ph = u * al_pi;
-#ifndef FV_X_SNAKE_FAST
     f32x2 r = __builtin_elementwise_fma(u, (f32x2)(al_pi), -ph);
     r = __builtin_elementwise_fma(u, (f32x2)(al_lo), r);
-#else
-    (void)al_lo;
-    const f32x2 r = f32x2{0.f, 0.f};
-#endif
     f32x2 c;
     c.x = __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(ph.x) + r.x);
     c.y = __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(ph.y) + r.y);
     return __builtin_elementwise_fma(c, (f32x2)(-hb), u + hb);
-#endif
 }
 
 // EDGE = false: the tile and its 6-sample halo lie inside [0, T) — no clamps, no bounds tests, fixed trip counts (the
@@ -412,7 +382,7 @@ __device__ __forceinline__ void aa_snake_tile(const float* __restrict__ xr, floa
             const f32x2 xp = {xs[xi + 2 - q], xs[xi + 3 - q]};
             u = __builtin_elementwise_fma(upp[q], xp, u);
         }
-        f32x2 a = snake2(u, al, ib, al_pi, al_lo, hb);
+        f32x2 a = snake2(u, al_pi, al_lo, hb);
         if (EDGE) {   // replicate padding of the down-sampler input: n < 0 -> a[0] (even sample of h = 0), n > 2T-1 -> a[2T-1]
             if (h < 0) a.y = a.x;
             if (h > T - 1) a.x = a.y;
@@ -520,7 +490,7 @@ __device__ __forceinline__ void aa_snake4_tile(const AaRegs& regs, float* __rest
                 uo = __builtin_elementwise_fma((f32x2)(upo[q]), P[k + 6 - q], uo);
             }
             // snake2 is element-wise: (ue(m), ue(m + 1)) and (uo(m), uo(m + 1)) instead of (ue(m), uo(m)) twice
-            const f32x2 ae = snake2(ue, al, ib, al_pi, al_lo, hb), ao = snake2(uo, al, ib, al_pi, al_lo, hb);
+            const f32x2 ae = snake2(ue, al_pi, al_lo, hb), ao = snake2(uo, al_pi, al_lo, hb);
             ev[k] = ae.x; ev[k + 1] = ae.y;
             od[k] = ao.x; od[k + 1] = ao.y;
         }
