@@ -349,6 +349,77 @@ def test_branch_mean_in_the_next_upsampler_is_bit_identical_to_the_ordered_accum
             assert torch.equal(ya, yb) and torch.equal(ya, yb2) and torch.equal(ya, yb3), (kind, prec, B, T, float((ya - yb).abs().max()))
 
 
+_TINY3 = dict(hop_length=16, upsample_rates=[4, 2, 2], upsample_kernel_sizes=[8, 4, 4], resblock_kernel_sizes=[3, 7, 11],
+              resblock_dilation_sizes=[[1, 3, 5]] * 3, num_mels=20, upsample_initial_channel=64, use_template=False,
+              pre_conv_kernel_size=7, post_conv_kernel_size=7)
+
+
+def _sum3_labels(eng, x):
+    return [r["kernel"] for r in eng.profile(x, repeats=1) if "sum3" in r["kernel"] or "mean_of_three" in r["kernel"]]
+
+
+def test_two_branch_chain_on_branch_streams_equals_the_single_stream_chain(monkeypatch):
+    """A stage with other than three branches forms its mean as the ordered accumulate (chain) — by default on the branch streams, each
+    branch's last kernel ordered after the previous branch's by events; FV_SINGLE_STREAM=1 runs the same launches back to back on one
+    stream and one buffer set.  Same additions, same order: bit for bit; and within the bar of the oracle.  Reference: hifigan.py:113-133."""
+    cfg = dict(_TINY3, hop_length=4, upsample_rates=[2, 2], upsample_kernel_sizes=[4, 4], resblock_kernel_sizes=[3, 7],
+               resblock_dilation_sizes=[[1, 3, 5]] * 2)
+    sd = syn.hifigan_state_dict(cfg, seed=4)
+    mel = syn.synthetic_mel(2, 20, 9, seed=17)
+    ref = orc.hifigan_forward(sd, cfg, mel)
+    streams = _hifigan_engine(cfg, sd)
+    monkeypatch.setenv("FV_SINGLE_STREAM", "1")
+    single = _hifigan_engine(cfg, sd)
+    monkeypatch.delenv("FV_SINGLE_STREAM")
+    ya, yb = _fwd(streams, mel), _fwd(single, mel)
+    assert np.array_equal(ya, yb), float(np.abs(ya - yb).max())
+    assert np.abs(ya - ref).max() <= TOL, float(np.abs(ya - ref).max())
+    streams.close()
+    single.close()
+
+
+def test_branch_mean_chain_knob_on_branch_streams_is_bit_identical_to_the_tree(monkeypatch):
+    """FV_BRANCH_MEAN=chain (a process-wide knob: fv_reload_env) turns the three-branch stages from the tree form — own outputs, the mean formed
+    by the consumer (` sum3` launches) — to the ordered accumulate on the branch streams.  DESIGN §3: the same additions in the same order."""
+    from vocoder_amd import _lib
+    sd = syn.hifigan_state_dict(_TINY3, seed=6)
+    x = torch.from_numpy(syn.synthetic_mel(2, 20, 9, seed=31)).to(_dev())
+    eng = _hifigan_engine(_TINY3, sd)
+    try:
+        tree = eng(x).clone()
+        torch.cuda.synchronize()
+        assert _sum3_labels(eng, x)
+        monkeypatch.setenv("FV_BRANCH_MEAN", "chain")
+        _lib.reload_env()
+        chain = eng(x).clone()
+        torch.cuda.synchronize()
+        assert _sum3_labels(eng, x) == []
+        assert torch.equal(tree, chain), float((tree - chain).abs().max())
+    finally:
+        monkeypatch.delenv("FV_BRANCH_MEAN", raising=False)
+        _lib.reload_env()
+        eng.close()
+
+
+def test_chain_max_c_mixes_tree_and_chain_stages_bit_identically(monkeypatch):
+    """FV_CHAIN_MAX_C = the narrowest stage's width (8 of 32 / 16 / 8): the wide stages keep the tree form, the last one accumulates in its
+    branches' last epilogues, so conv_post reads one tensor (no `conv_post_narrow sum3`).  Bit for bit the default's waveform."""
+    sd = syn.hifigan_state_dict(_TINY3, seed=6)
+    x = torch.from_numpy(syn.synthetic_mel(2, 20, 9, seed=31)).to(_dev())
+    base = _hifigan_engine(_TINY3, sd)
+    monkeypatch.setenv("FV_CHAIN_MAX_C", "8")
+    mixed = _hifigan_engine(_TINY3, sd)
+    monkeypatch.delenv("FV_CHAIN_MAX_C")
+    ya, yb = base(x).clone(), mixed(x).clone()
+    torch.cuda.synchronize()
+    assert torch.equal(ya, yb), float((ya - yb).abs().max())
+    assert "conv_post_narrow sum3" in _sum3_labels(base, x)
+    labels = _sum3_labels(mixed, x)
+    assert labels and "conv_post_narrow sum3" not in labels, labels
+    base.close()
+    mixed.close()
+
+
 def test_long_clip_and_odd_lengths_vs_oracle():
     """A 35 s clip at hop 16 (T_mel = 1501, prime-ish) and a 2-frame clip through the tiny config: exercises many tiles,
     ragged last tiles in every stage and the fused-pair kernels' halo logic at both ends."""
@@ -1329,6 +1400,11 @@ def test_generators_whose_output_is_not_frames_times_hop_are_not_tiled(monkeypat
     assert y.shape == ref.shape and np.abs(y - ref).max() <= TOL
     assert "gather_tiles" not in {r["kernel"] for r in tiled.profile(xt, repeats=1)}
     assert np.array_equal(y, whole(xt).cpu().numpy())
+    # (two branches: the chain form of the branch mean on the branch streams — against the same launches on one stream)
+    monkeypatch.setenv("FV_SINGLE_STREAM", "1")
+    single = Engine(_lib.FV_MODEL_HIFIGAN, ups=upsampler_config(**cfg), state_dict=sd)
+    monkeypatch.delenv("FV_SINGLE_STREAM")
+    assert np.array_equal(y, single(xt).cpu().numpy())
 
 
 def test_tile_batches_past_the_grid_z_limit(monkeypatch):

@@ -1,6 +1,5 @@
 // Host side of the fused conv layer: which weight forms a layer keeps (packed by conv_pack.hip), tile selection, per-layer dispatch.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <optional>
 
@@ -180,8 +179,7 @@ static int choose_tile(int M, long long N, int batch) {
     if (blocks_big < 1024 || cols_small < cols_big) {
         // still fewer workgroups than CUs: 32 x 64 tiles with K split across the four waves (latency variant)
         const long long blocks_small = tiles_small * m_blks * batch;
-        static const long long sk_max = std::getenv("FV_SPLITK_MAX") ? std::atoll(std::getenv("FV_SPLITK_MAX")) : 200;   // experiments
-        if (blocks_small < sk_max && !cur_invariant()) {   // (batch-invariant mode: the split-K kernels sum K in another order)
+        if (blocks_small < knobs().splitk_max && !cur_invariant()) {   // (batch-invariant mode: the split-K kernels sum K in another order)
             // 32 x 64 tiles: 4x the workgroups of 128 x 64 / 2x those of 32 x 128.  Workgroups are dealt out one per CU and
             // round, and a workgroup's time is its MFMA chain (proportional to the tile width): the busiest CU decides, so
             // take 32 x 32 tiles when their rounds are shorter in total (344 tiles of 32 x 64 = 2 rounds of 2 units against
@@ -189,8 +187,7 @@ static int choose_tile(int M, long long N, int batch) {
             const long long cus = num_cus();
             const long long blocks_64 = ((M + 31) / 32) * ((N + 63) / 64) * batch, blocks_32 = ((M + 31) / 32) * ((N + 31) / 32) * batch;
             const double cost_64 = (double)((blocks_64 + cus - 1) / cus) * 2.0, cost_32 = (double)((blocks_32 + cus - 1) / cus) * 1.1;
-            static const char* const force = std::getenv("FV_SPLITK");   // experiments: "32" / "64"
-            if (force) return force[0] == '3' ? TILE_SPLITK_32x32 : TILE_SPLITK_32x64;
+            if (const int force = knobs().splitk) return force == 32 ? TILE_SPLITK_32x32 : TILE_SPLITK_32x64;
             return cost_32 < cost_64 ? TILE_SPLITK_32x32 : TILE_SPLITK_32x64;
         }
         return small;

@@ -1,6 +1,5 @@
 // Host side of the fused ResBlock (c1, c2) pairs: which kernel family takes a pair, its launch parameters, the launch bookkeeping.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
 #include "fv_internal.h"
@@ -77,7 +76,7 @@ bool pair_f16x3_supported(const ConvLayer& c1, const ConvLayer& c2) {
     return c1.precision == FV_PRECISION_F16X3 && c2.precision == FV_PRECISION_F16X3 && c1.d_wph && c2.d_wph &&
            !c1.transposed && !c2.transposed && (C == 256 || C == 128 || C == 64 || C == 32) && c1.c_out == C && c2.c_in == C && c2.c_out == C &&
            c1.k == c2.k && (c1.k == 3 || c1.k == 7 || c1.k == 11) && (c1.dil == 1 || c1.dil == 3 || c1.dil == 5) && c2.dil == 1 &&
-           c1.padding == (c1.k - 1) / 2 * c1.dil && c2.padding == (c2.k - 1) / 2 && getenv("FV_NO_F16X3_PAIRS") == nullptr;
+           c1.padding == (c1.k - 1) / 2 * c1.dil && c2.padding == (c2.k - 1) / 2 && !knobs().no_f16x3_pairs;
 }
 
 static fv_status conv_pair_run_f16x3(const ConvLayer& c1, const ConvLayer& c2, const float* x, float* y, int batch, int t,
@@ -111,7 +110,7 @@ static bool pair16_f16x3_usable(const ConvLayer& c1, const ConvLayer& c2, const 
            c1.k == c2.k && (c1.dil == 1 || c1.dil == 3 || c1.dil == 5) && c2.dil == 1 &&
            c1.padding == (c1.k - 1) / 2 * c1.dil && c2.padding == (c2.k - 1) / 2 && t % 2 == 0 &&
            (((uintptr_t)x | (uintptr_t)y) & 7) == 0 && x != y && (long long)16 * t < (1LL << 30) &&
-           getenv("FV_NO_F16X3_PAIRS") == nullptr;
+           !knobs().no_f16x3_pairs;
 }
 
 static fv_status conv_pair16_run_f16x3(const ConvLayer& c1, const ConvLayer& c2, const float* x, float* y, int batch, int t,

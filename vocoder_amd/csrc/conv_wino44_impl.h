@@ -592,8 +592,7 @@ __global__ __launch_bounds__(256, (MT == 1 ? FV_X_WINO44_OCC : 2)) void conv_win
 
 // the row-split epilogue: whole quads per row (N % 4 == 0), 16-byte aligned rows of y and the residual, the lean operand set
 inline bool wino44_quad_rows(const ConvParams& p) {
-    static const bool off = std::getenv("FV_X_W44_NO_QR") != nullptr;   // A/B runs
-    return !off && p.dil == 1 && p.M % 32 == 0 && p.gamma == nullptr && p.out_mode == OUT_SET && p.acc_scale == 1.0f && p.N % 4 == 0 && (p.y_bstride & 3) == 0 &&
+    return !knobs().w44_no_qr && p.dil == 1 && p.M % 32 == 0 && p.gamma == nullptr && p.out_mode == OUT_SET && p.acc_scale == 1.0f && p.N % 4 == 0 && (p.y_bstride & 3) == 0 &&
            (((unsigned long long)p.y | (unsigned long long)(p.res ? p.res : p.y)) & 15ull) == 0;
 }
 

@@ -399,6 +399,29 @@ static fv_status validate_ups(const fv_upsampler_config& c) {
     return FV_OK;
 }
 
+// The per-engine options of the environment fv_create runs in (EngineOptions, engine_internal.h)
+static EngineOptions read_engine_options() {
+    EngineOptions o;
+    if (const char* v = std::getenv("FV_NO_PAIR_FUSION")) o.fuse_pairs = !(v[0] == '1');
+    if (const char* v = std::getenv("FV_PAIR_MAXC")) o.pair_max_c = std::atoi(v);
+    if (const char* v = std::getenv("FV_CHAIN_MAX_C")) o.chain_max_c = std::atoi(v);
+    if (const char* v = std::getenv("FV_NO_POST_SUM3")) o.post_mean_fused = !(v[0] == '1');
+    if (const char* v = std::getenv("FV_NO_AMP_FUSION")) o.fuse_amp_convs = !(v[0] == '1');
+    if (const char* v = std::getenv("FV_AMP_MAXC")) o.fuse_amp_max_c = std::atoi(v);
+    if (const char* v = std::getenv("FV_AMP_MAXK")) o.fuse_amp_max_k = std::atoi(v);
+    if (const char* v = std::getenv("FV_SINGLE_STREAM")) {
+        o.branch_streams = !(v[0] == '1' || v[0] == '2');
+        o.single_tree = v[0] == '2';
+    }
+    if (const char* v = std::getenv("FV_NO_GRAPH")) o.use_graph = !(v[0] == '1');
+    if (const char* v = std::getenv("FV_DEBUG_STOP")) {
+        o.debug_stop = std::atoi(v);
+        o.use_graph = false;   // the early return leaves forked branch streams unjoined: not capturable
+    }
+    if (const char* v = std::getenv("FV_TILE_FRAMES")) o.tile_frames_override = std::atoi(v);
+    return o;
+}
+
 extern "C" {
 
 FV_API fv_status fv_create(const fv_config* cfg, fv_engine** out) {
@@ -484,20 +507,7 @@ FV_API fv_status fv_create(const fv_config* cfg, fv_engine** out) {
     // ABI 5: 0 (a zero-initialised struct) is the reference default SiLU, -1 nn.Identity; inside the engine the field is a plain fv_act
     if (e->cfg.ups.post_activation == FV_POST_ACT_DEFAULT) e->cfg.ups.post_activation = FV_ACT_SILU;
     else if (e->cfg.ups.post_activation == FV_POST_ACT_IDENTITY) e->cfg.ups.post_activation = FV_ACT_NONE;
-    if (const char* v = std::getenv("FV_NO_PAIR_FUSION")) e->fuse_pairs = !(v[0] == '1');
-    if (const char* v = std::getenv("FV_PAIR_MAXC")) e->pair_max_c = std::atoi(v);
-    if (const char* v = std::getenv("FV_CHAIN_MAX_C")) e->chain_max_c = std::atoi(v);
-    if (const char* v = std::getenv("FV_NO_POST_SUM3")) e->post_mean_fused = !(v[0] == '1');
-    if (const char* v = std::getenv("FV_NO_AMP_FUSION")) e->fuse_amp_convs = !(v[0] == '1');
-    if (const char* v = std::getenv("FV_AMP_MAXC")) e->fuse_amp_max_c = std::atoi(v);
-    if (const char* v = std::getenv("FV_AMP_MAXK")) e->fuse_amp_max_k = std::atoi(v);
-    if (const char* v = std::getenv("FV_SINGLE_STREAM")) {
-        e->branch_streams = !(v[0] == '1' || v[0] == '2');
-        e->single_tree = v[0] == '2';
-    }
-    if (const char* v = std::getenv("FV_NO_GRAPH")) e->use_graph = !(v[0] == '1');
-    if (std::getenv("FV_DEBUG_STOP")) e->use_graph = false;   // the early return leaves forked branch streams unjoined: not capturable
-    if (const char* v = std::getenv("FV_TILE_FRAMES")) e->tile_frames_override = std::atoi(v);
+    e->opt = read_engine_options();
     *out = e;
     return FV_OK;
 }
@@ -578,11 +588,11 @@ FV_API fv_status fv_set_graph_replay(fv_engine* e, int32_t enable) {
         set_error("fv_set_graph_replay: null engine");
         return FV_ERR_INVALID;
     }
-    e->use_graph = enable != 0;
+    e->opt.use_graph = enable != 0;
     return FV_OK;
 }
 
-FV_API int32_t fv_get_graph_replay(const fv_engine* e) { return e && e->use_graph ? 1 : 0; }
+FV_API int32_t fv_get_graph_replay(const fv_engine* e) { return e && e->opt.use_graph ? 1 : 0; }
 
 FV_API fv_status fv_finalize(fv_engine* e) {
     if (!e) {

@@ -14,8 +14,6 @@
 // ------------------------------------------------------------------------------------------------
 // forward passes
 // ------------------------------------------------------------------------------------------------
-// Workspace of the upsampler: cur / S / Y plus (XB, XT, XA) per concurrent branch = 3 + 3 * num_kernels buffers
-
 fv_status fv_engine::ensure_branch_streams(int nk) {
     if ((int)bstreams.size() >= nk - 1 && !bev_fork.empty()) return FV_OK;
     while ((int)bstreams.size() < nk - 1) {
@@ -37,256 +35,337 @@ fv_status fv_engine::ensure_branch_streams(int nk) {
     return FV_OK;
 }
 
-fv_status fv_engine::run_upsampler(const float* d_in, float* d_out, int B, int T, float* ws, hipStream_t s) {
-    const int64_t me = (ups.max_elems(T) * B + 63) / 64 * 64;
-    const int nk = ups.cfg.num_kernels;
-    float *cur = ws, *S = ws + me, *Y = ws + 2 * me;
-    auto XB = [&](int j) { return ws + (size_t)(3 + 3 * j) * me; };
-    auto XT = [&](int j) { return ws + (size_t)(4 + 3 * j) * me; };
-    auto XA = [&](int j) { return ws + (size_t)(5 + 3 * j) * me; };
-    fv_status st;
-    // The nk ResBlock branches of a stage are independent until the stack-mean: run them on their own streams
-    // (fork after the upsampler conv, join after the last branch) so that one branch's tail / barrier phases are
-    // filled by the others' workgroups.  The MRF accumulate into Y stays ordered j = 0, 1, 2 through events.
-    // Profiling runs stay on one stream so that per-kernel hipEvent durations do not overlap.
-    const bool multi = branch_streams && nk > 1 && !profiling;
-    if (multi && (st = ensure_branch_streams(nk))) return st;
+namespace {
+
+// Workspace of the upsampler: cur / S / Y plus (XB, XT, XA) per concurrent branch = 3 + 3 * num_kernels buffers of `me` floats
+struct UpsWorkspace {
+    float* ws;
+    int64_t me;
+    float *cur, *S, *Y;   // the running activation, the upsampler conv's output (the branches' input), the stage output (swapped with cur after every stage)
+    UpsWorkspace(float* ws_, int64_t me_) : ws(ws_), me(me_), cur(ws_), S(ws_ + me_), Y(ws_ + 2 * me_) {}
+    float* XB(int j) const { return ws + (size_t)(3 + 3 * j) * me; }
+    float* XT(int j) const { return ws + (size_t)(4 + 3 * j) * me; }
+    float* XA(int j) const { return ws + (size_t)(5 + 3 * j) * me; }
+};
+
+enum BranchForm { BRANCH_PAIRS, BRANCH_AMP, BRANCH_LAYERS };   // run_branch_pairs / run_branch_amp / run_branch_layers
+// where the stage's branch mean is formed
+enum MeanForm {
+    MEAN_IN_BRANCHES,   // chain: accumulated into Y by the branches' last epilogues
+    MEAN_IN_NEXT_UP,    // tree: the next stage's upsampler conv forms it while staging its input (conv_mfma_impl.h, SUM3)
+    MEAN_IN_POST,       // tree, last stage: conv_post (HiFiGAN) / activation_post (BigVGAN) forms it while loading its input
+    MEAN_KERNEL,        // tree: mean_of_three_kernel into Y after the join
+};
+struct BranchPlan {
+    int j;         // the branch (UpStage::branches)
+    int bj;        // its buffer set XB / XT / XA
+    int stream;    // 0: the caller's stream, j > 0: branch stream j - 1
+    BranchForm form;
+    float* y_last;   // the branch's last kernel writes here, as (y_last [+ v]) * scale_last
+    int mode_last;
+    float scale_last;
+};
+struct StagePlan {
+    int B, t, ch;
+    bool tree;     // the form of the branch mean (plan_stage)
+    MeanForm mean;
+    bool dbg_here;   // FV_DEBUG_STOP names this stage: the forward ends after it, and the per-layer branches after dilation pair dbg_pair (dbg_half 0: after its c1)
+    int dbg_pair, dbg_half;
+    BranchPlan br[FV_MAX_KERNELS];   // in the order the host enqueues them
+};
+
+BranchForm plan_branch_form(const fv_engine& e, const ResBranch& br, bool dbg_here, int B, int t, int ch) {
+    const EngineOptions& o = e.opt;
+    // HiFiGAN narrow stages: the whole (c1, c2) pair in one kernel, intermediate kept in LDS.  Not in place
+    // (workgroups read their neighbours' halo), so the branch ping-pongs S -> XB -> XT -> Y.
+    // (C = 64 / 128 pairs — k = 3 only — fuse when the launch fills the chip; a single clip's 44 - 88 tiles are better served by the
+    //  per-layer latency kernels: conv_wino_lat_impl.h)
+    const bool fuse_narrow = ch <= o.pair_max_c && pair_supported(ch, br.k, br.dil[0]) && pair_supported(ch, br.k, br.dil[1]) &&
+                             pair_supported(ch, br.k, br.dil[2]) && (ch < 64 || cur_invariant() || (long long)B * ((t + 125) / 126) >= 2LL * num_cus());
+    // f16x3 precision mode: the wide stages (C = 128 / 64) fuse too (pair_f16x3_impl.h)
+    const bool fuse_wide = pair_f16x3_supported(br.c1[0], br.c2[0]) && pair_f16x3_supported(br.c1[1], br.c2[1]) &&
+                           pair_f16x3_supported(br.c1[2], br.c2[2]);
+    if (!e.ups.bigvgan && (fuse_narrow || fuse_wide) && o.fuse_pairs) return BRANCH_PAIRS;
+    // BigVGAN narrow stages (C = 32 / 64): each conv runs with its anti-aliased SnakeBeta fused in front (amp_conv.hip) —
+    // no activation launches, no activated tensors in HBM
+    bool fuse_amp = e.ups.bigvgan && o.fuse_amp_convs && !dbg_here && ch <= o.fuse_amp_max_c && br.k <= o.fuse_amp_max_k;
+    for (int n = 0; n < FV_MAX_DILATIONS && fuse_amp; ++n)
+        fuse_amp = br.c1[n].precision == FV_PRECISION_F32 && br.c2[n].precision == FV_PRECISION_F32 && br.c1[n].c_in == ch &&
+                   br.c1[n].c_out == ch && br.c2[n].c_in == ch && br.c2[n].c_out == ch && br.c1[n].k == br.k && br.c2[n].k == br.k &&
+                   amp_conv_supported(ch, br.k, br.c1[n].dil) && br.c2[n].dil == 1 &&
+                   br.c1[n].padding == (br.k - 1) / 2 * br.c1[n].dil && br.c2[n].padding == (br.k - 1) / 2 && (long long)ch * t < (1LL << 30);
+    return fuse_amp ? BRANCH_AMP : BRANCH_LAYERS;
+}
+
+// tree form, after the join: who forms Y = ((y0 + y1) + y2) / 3 — the same additions in the same order as the accumulate chain
+MeanForm plan_tree_mean(const fv_engine& e, const Knobs& kn, bool dbg_here, int stage_idx, int B, int t) {
+    const UpsamplerModel& ups = e.ups;
+    const int n_stages = (int)ups.stages.size();
+    // the next stage's upsampler conv forms the mean while staging its input (conv_mfma_impl.h, SUM3); the last stage's
+    // output goes through mean_of_three_kernel (its consumers are the narrow post kernels)
+    const bool fuse_mean = !kn.no_sum3;
+    if (stage_idx + 1 < n_stages && fuse_mean && !dbg_here) return MEAN_IN_NEXT_UP;
+    if (stage_idx + 1 == n_stages && fuse_mean && e.opt.post_mean_fused && !dbg_here &&
+        (ups.bigvgan || conv_narrow_sum3_ok(B, ups.post_cin, t, 1, ups.cfg.post_conv_kernel_size, get_padding(ups.cfg.post_conv_kernel_size))))
+        return MEAN_IN_POST;
+    return MEAN_KERNEL;
+}
+
+// Every decision of one stage — t: its length after the upsampler conv; multi: the branches run on their own streams.  Enqueues nothing.
+StagePlan plan_stage(const fv_engine& e, const Knobs& kn, const UpsWorkspace& w, int stage_idx, int B, int t, bool multi) {
+    const EngineOptions& o = e.opt;
+    const UpStage& stg = *e.ups.stages[stage_idx];
+    const int nk = e.ups.cfg.num_kernels;
+    StagePlan sp{B, t, stg.ch};
+    sp.dbg_here = o.debug_stop >= 0 && o.debug_stop / 100 == stage_idx;
+    sp.dbg_pair = (o.debug_stop / 10) % 10;
+    sp.dbg_half = o.debug_stop % 10;
+    // ParralelBlock / stack-mean of the three ResBlock1 / AMPBlock branches (hifigan.py:132-133, bigvgan.py:358-365)
+    // Y = ((y0 + y1) + y2) / 3 is formed in one of two ways — the same additions in the same order, so bit-identical:
+    //   chain  y0 -> Y, (Y + y1) -> Y, (Y + y2) / 3 -> Y in the branches' last epilogues, ordered by events (single stream, other
+    //          branch counts, FV_BRANCH_MEAN=chain)
+    //   tree   the branches keep their outputs in their own buffers and mean_of_three_kernel forms Y after the join.
+    // The chain makes each branch's last kernel wait for the previous branch's: a single clip paid 20-65 us of cross-queue
+    // waits per stage (tools/latency_timeline.py), and at B = 32 the k = 7 and k = 11 branches' final convs ran one after the
+    // other, alone on the chip, at the end of every stage (rocprofv3 trace).  Without it the host is also free to enqueue the
+    // branches longest first (k = 11, 7, 3): a replayed graph starts sibling nodes in creation order, and the k = 11 chain —
+    // every stage's critical path — used to start last (53 us after the fork in stage 0 of a single clip).  Tree + longest
+    // first: B = 1 1.07 -> 0.97 ms per forward, B = 32 15.12 -> 15.00 ms (the extra pass over four tensors included; with
+    // the branches enqueued shortest first the tree was 0.1 ms *slower* than the chain at B = 32).  Summing the other two
+    // outputs in the last branch's final epilogue instead of a separate kernel measured 15.02 / 1.04 ms: not kept.  Neither
+    // were: two streams, the longest branch on the caller's stream, a wake-up kernel on the side queues, stream priorities.
+    // Narrow stages (ch <= chain_max_c, FV_CHAIN_MAX_C): the chain, so that the HBM-bound consumers — the last upsamplers, conv_post — read ONE
+    // tensor instead of three; the k = 3 / 7 / 11 branches finish in that order anyway
+    // Profiling runs (one stream, hipEvents around every launch: the source of the bench line's `roofline`) take the tree form too since round 6 — the
+    // branches back to back, each into its own buffers — so that the table holds the kernel instances the shipped step launches: the chain's last
+    // epilogues accumulate (the slow general epilogue of conv_wino44: 321 against 265 us for the dominant layer) and its upsamplers read one tensor,
+    // neither of which the three-stream step ever runs.
+    sp.tree = (multi || e.profiling || o.single_tree) && nk == 3 && !kn.branch_mean_chain && stg.ch > o.chain_max_c;
+    sp.mean = sp.tree ? plan_tree_mean(e, kn, sp.dbg_here, stage_idx, B, t) : MEAN_IN_BRANCHES;
+    for (int jj = 0; jj < nk; ++jj) {
+        BranchPlan& bp = sp.br[jj];
+        bp.j = sp.tree ? nk - 1 - jj : jj;   // tree: longest branch first
+        bp.stream = multi ? bp.j : 0;
+        bp.bj = (multi || sp.tree) ? bp.j : 0;   // single-stream chain: branches run back to back and share one buffer set
+        bp.form = plan_branch_form(e, *stg.branches[bp.j], sp.dbg_here, B, t, stg.ch);
+        bp.y_last = sp.tree ? w.XB(bp.bj) : w.Y;   // tree: the branch keeps its own output, summed after the join
+        bp.mode_last = !sp.tree && bp.j > 0 ? OUT_ACCUM : OUT_SET;
+        bp.scale_last = !sp.tree && bp.j == nk - 1 ? 1.0f / (float)nk : 1.0f;
+    }
+    return sp;
+}
+
+// The nk ResBlock branches of a stage are independent until the stack-mean: they run on their own streams
+// (fork after the upsampler conv, join after the last branch) so that one branch's tail / barrier phases are
+// filled by the others' workgroups.  The MRF accumulate into Y (chain form) stays ordered j = 0, 1, 2 through events.
+// With !multi every operation is a no-op and every branch runs on the caller's stream.
+struct BranchOrder {
+    fv_engine& e;
+    hipStream_t s;   // the caller's stream
+    bool multi;
+    int nk;
+    int stage = 0;
+    bool tree = false;
+    hipStream_t stream(int idx) const { return idx > 0 ? e.bstreams[idx - 1] : s; }
+    hipEvent_t last(int j) const { return e.bev_last[stage * nk + j]; }
+    fv_status fork(int stage_idx, bool tree_) {   // after the upsampler conv
+        stage = stage_idx;
+        tree = tree_;
+        if (multi) FV_HIP_CHECK(hipEventRecord(e.bev_fork[stage], s));
+        return FV_OK;
+    }
+    fv_status enter(const BranchPlan& bp) {
+        if (bp.stream > 0) FV_HIP_CHECK(hipStreamWaitEvent(stream(bp.stream), e.bev_fork[stage], 0));
+        return FV_OK;
+    }
+    // ordering of the accumulate into Y: branch j's last kernel runs after branch j-1's
+    fv_status before_last(const BranchPlan& bp) {
+        if (bp.stream > 0 && !tree) FV_HIP_CHECK(hipStreamWaitEvent(stream(bp.stream), last(bp.j - 1), 0));
+        return FV_OK;
+    }
+    fv_status after_last(const BranchPlan& bp) {
+        if (multi) FV_HIP_CHECK(hipEventRecord(last(bp.j), stream(bp.stream)));
+        return FV_OK;
+    }
+    fv_status join() {
+        if (!multi) return FV_OK;
+        if (tree) {   // all three
+            for (int j = 1; j < nk; ++j) FV_HIP_CHECK(hipStreamWaitEvent(s, last(j), 0));
+        } else {      // chain: the last branch's final kernel is ordered after every other branch's
+            FV_HIP_CHECK(hipStreamWaitEvent(s, last(nk - 1), 0));
+        }
+        return FV_OK;
+    }
+};
+
+ConvRun conv_run(int B, int t_in, const float* x, float* y) {
     ConvRun r;
     r.batch = B;
-    // conv_pre (hifigan.py:227)
-    r.x = d_in;
-    r.y = cur;
-    r.t_in = T;
-    if ((st = conv_layer_run(ups.conv_pre, r, s))) return st;
-    int t = (int)ups.conv_pre.out_len(T);
-    int stage_idx = 0;
-    bool sum_pending = false;   // tree mode: the stage output is still three branch buffers (XB(0..2))
-    bool post_sum3 = false;     // ... and so is the last stage's, for conv_post to average
-    const int n_stages = (int)ups.stages.size();
-    for (auto& stg : ups.stages) {
-        // x = ups[i](silu(x))  — HiFiGAN (hifigan.py:230-231); BigVGAN has no pre-activation (bigvgan.py:355-356)
-        r = ConvRun();
-        r.batch = B;
-        r.x = cur;
-        if (sum_pending) {   // the previous stage left its three branch outputs: the upsampler conv forms their mean itself
-            r.x = XB(0);
-            r.x2 = XB(1);
-            r.x3 = XB(2);
-            r.sum_tmp = cur;   // (kernels without the three-operand staging form it here first)
-            sum_pending = false;
-        }
-        r.y = S;
-        r.t_in = t;
-        r.pre_act = ups.bigvgan ? FV_ACT_NONE : FV_ACT_SILU;
-        if ((st = conv_layer_run(stg->up, r, s))) return st;
-        t = (int)stg->up.out_len(t);
-        const int ch = stg->ch;
-        if (ups.cfg.use_template) {   // x = x + noise_convs[i](template)  (hifigan.py:233-234)
-            const int Ta = (int)ups.out_len(T);
-            FV_PROF(s, "noise_conv_add", 2.0 * B * ch * stg->nk * t, 8.0 * B * ch * t,
-                    launch_noise_conv_add(cur_template, stg->d_nw, stg->d_nb, S, B, ch, t, Ta, stg->nk, stg->nstride, stg->npad, s));
-        }
-        if (multi) FV_HIP_CHECK(hipEventRecord(bev_fork[stage_idx], s));
-        // debugging knob: FV_DEBUG_STOP = stage * 100 + pair * 10 + half stops the forward after that stage's dilation pair (half 0:
-        // after c1, 1: after c2) with the branch buffers left in the workspace for inspection (tools/probe_f16_locate.py)
-        static const int dbg_stop = std::getenv("FV_DEBUG_STOP") ? std::atoi(std::getenv("FV_DEBUG_STOP")) : -1;
-        const bool dbg_here = dbg_stop >= 0 && dbg_stop / 100 == stage_idx;
-        const int dbg_pair = (dbg_stop / 10) % 10, dbg_half = dbg_stop % 10;
-        // ParralelBlock / stack-mean of the three ResBlock1 / AMPBlock branches (hifigan.py:132-133, bigvgan.py:358-365)
-        // Y = ((y0 + y1) + y2) / 3 is formed in one of two ways — the same additions in the same order, so bit-identical:
-        //   chain  y0 -> Y, (Y + y1) -> Y, (Y + y2) / 3 -> Y in the branches' last epilogues, ordered by events (single stream, other
-        //          branch counts, FV_BRANCH_MEAN=chain)
-        //   tree   the branches keep their outputs in their own buffers and mean_of_three_kernel forms Y after the join.
-        // The chain makes each branch's last kernel wait for the previous branch's: a single clip paid 20-65 us of cross-queue
-        // waits per stage (tools/latency_timeline.py), and at B = 32 the k = 7 and k = 11 branches' final convs ran one after the
-        // other, alone on the chip, at the end of every stage (rocprofv3 trace).  Without it the host is also free to enqueue the
-        // branches longest first (k = 11, 7, 3): a replayed graph starts sibling nodes in creation order, and the k = 11 chain —
-        // every stage's critical path — used to start last (53 us after the fork in stage 0 of a single clip).  Tree + longest
-        // first: B = 1 1.07 -> 0.97 ms per forward, B = 32 15.12 -> 15.00 ms (the extra pass over four tensors included; with
-        // the branches enqueued shortest first the tree was 0.1 ms *slower* than the chain at B = 32).  Summing the other two
-        // outputs in the last branch's final epilogue instead of a separate kernel measured 15.02 / 1.04 ms: not kept.  Neither
-        // were: two streams, the longest branch on the caller's stream, a wake-up kernel on the side queues, stream priorities.
-        static const char* const mean_env = std::getenv("FV_BRANCH_MEAN");   // experiments: "chain"
-        // Narrow stages (ch <= chain_max_c, FV_CHAIN_MAX_C): the chain, so that the HBM-bound consumers — the last upsamplers, conv_post — read ONE
-        // tensor instead of three; the k = 3 / 7 / 11 branches finish in that order anyway
-        // Profiling runs (one stream, hipEvents around every launch: the source of the bench line's `roofline`) take the tree form too since round 6 — the
-        // branches back to back, each into its own buffers — so that the table holds the kernel instances the shipped step launches: the chain's last
-        // epilogues accumulate (the slow general epilogue of conv_wino44: 321 against 265 us for the dominant layer) and its upsamplers read one tensor,
-        // neither of which the three-stream step ever runs.
-        const bool tree = (multi || profiling || single_tree) && nk == 3 && !(mean_env && mean_env[0] == 'c') && stg->ch > chain_max_c;
-        const bool order_desc = true;
-        for (int jj = 0; jj < nk; ++jj) {
-            const int j = (tree && order_desc) ? nk - 1 - jj : jj;
-            ResBranch& br = *stg->branches[j];
-            hipStream_t bs = (multi && j > 0) ? bstreams[j - 1] : s;
-            if (multi && j > 0) FV_HIP_CHECK(hipStreamWaitEvent(bs, bev_fork[stage_idx], 0));
-            const int bj = (multi || tree) ? j : 0;   // single-stream chain: branches run back to back and share one buffer set
-            // ordering of the accumulate into Y: branch j's last kernel runs after branch j-1's
-            auto before_last = [&]() -> fv_status {
-                if (multi && j > 0 && !tree) FV_HIP_CHECK(hipStreamWaitEvent(bs, bev_last[stage_idx * nk + j - 1], 0));
-                return FV_OK;
-            };
-            auto after_last = [&]() -> fv_status {
-                if (multi) FV_HIP_CHECK(hipEventRecord(bev_last[stage_idx * nk + j], bs));
-                return FV_OK;
-            };
-            int mode_last = OUT_SET;
-            float scale_last = 1.0f;
-            if (nk > 1 && !tree) {
-                mode_last = j == 0 ? OUT_SET : OUT_ACCUM;
-                scale_last = (j == nk - 1) ? 1.0f / (float)nk : 1.0f;
-            }
-            float* const y_last = tree ? XB(bj) : Y;   // tree: the branch keeps its own output, summed after the join
-            // HiFiGAN narrow stages: the whole (c1, c2) pair in one kernel, intermediate kept in LDS.  Not in place
-            // (workgroups read their neighbours' halo), so the branch ping-pongs S -> XB -> XT -> Y.
-            // (C = 64 / 128 pairs — k = 3 only — fuse when the launch fills the chip; a single clip's 44 - 88 tiles are better served by the
-            //  per-layer latency kernels: conv_wino_lat_impl.h)
-            const bool fuse_narrow = ch <= pair_max_c && pair_supported(ch, br.k, br.dil[0]) && pair_supported(ch, br.k, br.dil[1]) &&
-                                     pair_supported(ch, br.k, br.dil[2]) && (ch < 64 || cur_invariant() || (long long)B * ((t + 125) / 126) >= 2LL * num_cus());
-            // f16x3 precision mode: the wide stages (C = 128 / 64) fuse too (pair_f16x3_impl.h)
-            const bool fuse_wide = pair_f16x3_supported(br.c1[0], br.c2[0]) && pair_f16x3_supported(br.c1[1], br.c2[1]) &&
-                                   pair_f16x3_supported(br.c1[2], br.c2[2]);
-            const bool fuse = !ups.bigvgan && (fuse_narrow || fuse_wide) && fuse_pairs;
-            if (fuse) {
-                const float* src = S;
-                for (int n = 0; n < FV_MAX_DILATIONS; ++n) {
-                    const bool last = n == FV_MAX_DILATIONS - 1;
-                    float* dst = last ? y_last : (n == 0 ? XB(bj) : XT(bj));
-                    if (last && (st = before_last())) return st;
-                    if ((st = conv_pair_run(br.c1[n], br.c2[n], src, dst, B, t, last ? mode_last : OUT_SET,
-                                            last ? scale_last : 1.0f, bs)))
-                        return st;
-                    src = dst;
-                }
-                if ((st = after_last())) return st;
-                continue;
-            }
-            // BigVGAN narrow stages (C = 32 / 64): each conv runs with its anti-aliased SnakeBeta fused in front (amp_conv.hip) —
-            // no activation launches, no activated tensors in HBM
-            bool fuse_amp = ups.bigvgan && fuse_amp_convs && !dbg_here && ch <= fuse_amp_max_c && br.k <= fuse_amp_max_k;
-            for (int n = 0; n < FV_MAX_DILATIONS && fuse_amp; ++n)
-                fuse_amp = br.c1[n].precision == FV_PRECISION_F32 && br.c2[n].precision == FV_PRECISION_F32 && br.c1[n].c_in == ch &&
-                           br.c1[n].c_out == ch && br.c2[n].c_in == ch && br.c2[n].c_out == ch && br.c1[n].k == br.k && br.c2[n].k == br.k &&
-                           amp_conv_supported(ch, br.k, br.c1[n].dil) && br.c2[n].dil == 1 &&
-                           br.c1[n].padding == (br.k - 1) / 2 * br.c1[n].dil && br.c2[n].padding == (br.k - 1) / 2 && (long long)ch * t < (1LL << 30);
-            if (fuse_amp) {
-                for (int n = 0; n < FV_MAX_DILATIONS; ++n) {
-                    const float* src = n == 0 ? S : XB(bj);
-                    const bool last = n == FV_MAX_DILATIONS - 1;
-                    const AASnake &a1 = br.act[2 * n], &a2 = br.act[2 * n + 1];
-                    const double fl = 2.0 * ch * ch * br.k * (double)t * B, el = (double)B * ch * t * 4.0;
-                    char lbl[96];
-                    std::snprintf(lbl, sizeof(lbl), "amp_conv<k=%d d=%d C=%d>", br.k, br.c1[n].dil, ch);
-                    FV_PROF(bs, lbl, fl + 60.0 * B * ch * t, 2.0 * el,
-                            (launch_amp_conv(br.c1[n], src, XT(bj), nullptr, a1.d_alpha, a1.d_inv_beta, a1.d_up, a1.d_down, B, t, OUT_SET,
-                                             1.0f, bs) ? FV_OK : FV_ERR_HIP));
-                    if (last && (st = before_last())) return st;
-                    std::snprintf(lbl, sizeof(lbl), "amp_conv<k=%d d=1 C=%d>+res", br.k, ch);
-                    FV_PROF(bs, lbl, fl + 60.0 * B * ch * t, (last && mode_last == OUT_ACCUM ? 4.0 : 3.0) * el,
-                            (launch_amp_conv(br.c2[n], XT(bj), last ? y_last : XB(bj), src, a2.d_alpha, a2.d_inv_beta, a2.d_up, a2.d_down, B, t,
-                                             last ? mode_last : OUT_SET, last ? scale_last : 1.0f, bs) ? FV_OK : FV_ERR_HIP));
-                }
-                if ((st = after_last())) return st;
-                continue;
-            }
-            for (int n = 0; n < FV_MAX_DILATIONS; ++n) {
-                if (dbg_here && n > dbg_pair) break;
-                const float* src = n == 0 ? S : XB(bj);
-                const bool last = n == FV_MAX_DILATIONS - 1;
-                const float* c1_in = src;
-                if (ups.bigvgan) {
-                    FV_PROF(bs, "aa_snake", 60.0 * B * ch * t, 8.0 * B * ch * t,
-                            launch_aa_snake(src, XA(bj), br.act[2 * n].d_alpha, br.act[2 * n].d_inv_beta,
-                                            br.act[2 * n].d_up, br.act[2 * n].d_down, B, ch, t, bs));
-                    c1_in = XA(bj);
-                }
-                // xt = c1(act(x)); the second activation is fused into c1's epilogue for SiLU
-                r = ConvRun();
-                r.batch = B;
-                r.t_in = t;
-                r.x = c1_in;
-                r.y = XT(bj);
-                r.pre_act = ups.bigvgan ? FV_ACT_NONE : FV_ACT_SILU;
-                r.post_act = ups.bigvgan ? FV_ACT_NONE : FV_ACT_SILU;
-                if ((st = conv_layer_run(br.c1[n], r, bs))) return st;
-                if (dbg_here && n == dbg_pair && dbg_half == 0) break;
-                const float* c2_in = XT(bj);
-                if (ups.bigvgan) {
-                    FV_PROF(bs, "aa_snake", 60.0 * B * ch * t, 8.0 * B * ch * t,
-                            launch_aa_snake(XT(bj), XA(bj), br.act[2 * n + 1].d_alpha, br.act[2 * n + 1].d_inv_beta,
-                                            br.act[2 * n + 1].d_up, br.act[2 * n + 1].d_down, B, ch, t, bs));
-                    c2_in = XA(bj);
-                }
-                // x = c2(act(xt)) + x ; the last pair of each branch accumulates the branch mean into Y
-                r = ConvRun();
-                r.batch = B;
-                r.t_in = t;
-                r.x = c2_in;
-                r.res = src;
-                if (!last) {
-                    r.y = XB(bj);
-                } else {
-                    r.y = y_last;
-                    r.out_mode = mode_last;
-                    r.out_scale = scale_last;
-                    if ((st = before_last())) return st;
-                }
-                if ((st = conv_layer_run(br.c2[n], r, bs))) return st;
-            }
-            if ((st = after_last())) return st;
-        }
-        if (tree) {
-            // join all three, then Y = ((y0 + y1) + y2) / 3 — the same additions in the same order as the accumulate chain
-            if (multi)
-                for (int j = 1; j < nk; ++j) FV_HIP_CHECK(hipStreamWaitEvent(s, bev_last[stage_idx * nk + j], 0));
-            // the next stage's upsampler conv forms the mean while staging its input (conv_mfma_impl.h, SUM3); the last stage's
-            // output goes through mean_of_three_kernel (its consumers are the narrow post kernels)
-            const bool fuse_mean = !knobs().no_sum3;
-            if (stage_idx + 1 < n_stages && fuse_mean && !dbg_here) {
-                sum_pending = true;
-            } else if (stage_idx + 1 == n_stages && fuse_mean && post_mean_fused && !dbg_here &&
-                       (ups.bigvgan || conv_narrow_sum3_ok(B, ups.post_cin, t, 1, ups.cfg.post_conv_kernel_size,
-                                                           get_padding(ups.cfg.post_conv_kernel_size)))) {
-                post_sum3 = true;   // conv_post (HiFiGAN) / activation_post (BigVGAN) forms the last stage's branch mean while loading its input
-            } else if ((st = launch_mean_of_three(XB(0), XB(1), XB(2), Y, (long long)B * ch * t, s))) {
-                return st;
-            }
-        } else if (multi) {
-            // join: the last branch's final kernel is ordered after every other branch's
-            FV_HIP_CHECK(hipStreamWaitEvent(s, bev_last[stage_idx * nk + nk - 1], 0));
-        }
-        if (dbg_here) {
-            std::fprintf(stderr, "FV_DEBUG_STOP: stage %d ch=%d t=%d me=%lld S=%lld Y=%lld\n", stage_idx, ch, t, (long long)me,
-                         (long long)(S - ws), (long long)(Y - ws));
-            return FV_OK;
-        }
-        std::swap(cur, Y);
-        ++stage_idx;
+    r.t_in = t_in;
+    r.x = x;
+    r.y = y;
+    return r;
+}
+
+// The whole (c1, c2) pair in one kernel: S -> XB -> XT -> y_last
+fv_status run_branch_pairs(const ResBranch& br, const UpsWorkspace& w, const StagePlan& sp, const BranchPlan& bp, BranchOrder& ord) {
+    const hipStream_t bs = ord.stream(bp.stream);
+    fv_status st;
+    const float* src = w.S;
+    for (int n = 0; n < FV_MAX_DILATIONS; ++n) {
+        const bool last = n == FV_MAX_DILATIONS - 1;
+        float* dst = last ? bp.y_last : (n == 0 ? w.XB(bp.bj) : w.XT(bp.bj));
+        if (last && (st = ord.before_last(bp))) return st;
+        if ((st = conv_pair_run(br.c1[n], br.c2[n], src, dst, sp.B, sp.t, last ? bp.mode_last : OUT_SET, last ? bp.scale_last : 1.0f, bs)))
+            return st;
+        src = dst;
     }
-    // activation_post -> conv_post -> tanh (hifigan.py:245-247 / bigvgan.py:367-369)
-    const float* post_in = cur;
+    return FV_OK;
+}
+
+// BigVGAN: amp_conv for c1 and for c2 + residual
+fv_status run_branch_amp(const ResBranch& br, const UpsWorkspace& w, const StagePlan& sp, const BranchPlan& bp, BranchOrder& ord) {
+    const hipStream_t bs = ord.stream(bp.stream);
+    const int B = sp.B, t = sp.t, ch = sp.ch, bj = bp.bj;
+    fv_status st;
+    for (int n = 0; n < FV_MAX_DILATIONS; ++n) {
+        const float* src = n == 0 ? w.S : w.XB(bj);
+        const bool last = n == FV_MAX_DILATIONS - 1;
+        const AASnake &a1 = br.act[2 * n], &a2 = br.act[2 * n + 1];
+        const double fl = 2.0 * ch * ch * br.k * (double)t * B, el = (double)B * ch * t * 4.0;
+        char lbl[96];
+        std::snprintf(lbl, sizeof(lbl), "amp_conv<k=%d d=%d C=%d>", br.k, br.c1[n].dil, ch);
+        FV_PROF(bs, lbl, fl + 60.0 * B * ch * t, 2.0 * el,
+                (launch_amp_conv(br.c1[n], src, w.XT(bj), nullptr, a1.d_alpha, a1.d_inv_beta, a1.d_up, a1.d_down, B, t, OUT_SET,
+                                 1.0f, bs) ? FV_OK : FV_ERR_HIP));
+        if (last && (st = ord.before_last(bp))) return st;
+        std::snprintf(lbl, sizeof(lbl), "amp_conv<k=%d d=1 C=%d>+res", br.k, ch);
+        FV_PROF(bs, lbl, fl + 60.0 * B * ch * t, (last && bp.mode_last == OUT_ACCUM ? 4.0 : 3.0) * el,
+                (launch_amp_conv(br.c2[n], w.XT(bj), last ? bp.y_last : w.XB(bj), src, a2.d_alpha, a2.d_inv_beta, a2.d_up, a2.d_down, B, t,
+                                 last ? bp.mode_last : OUT_SET, last ? bp.scale_last : 1.0f, bs) ? FV_OK : FV_ERR_HIP));
+    }
+    return FV_OK;
+}
+
+fv_status run_aa_snake(const AASnake& a, const float* x, float* y, const StagePlan& sp, hipStream_t bs) {
+    FV_PROF(bs, "aa_snake", 60.0 * sp.B * sp.ch * sp.t, 8.0 * sp.B * sp.ch * sp.t,
+            launch_aa_snake(x, y, a.d_alpha, a.d_inv_beta, a.d_up, a.d_down, sp.B, sp.ch, sp.t, bs));
+    return FV_OK;
+}
+
+// One launch per conv (BigVGAN: and per activation, through XA)
+fv_status run_branch_layers(const ResBranch& br, bool bigvgan, const UpsWorkspace& w, const StagePlan& sp, const BranchPlan& bp,
+                                   BranchOrder& ord) {
+    const hipStream_t bs = ord.stream(bp.stream);
+    const int bj = bp.bj;
+    const int act = bigvgan ? FV_ACT_NONE : FV_ACT_SILU;
+    fv_status st;
+    for (int n = 0; n < FV_MAX_DILATIONS; ++n) {
+        if (sp.dbg_here && n > sp.dbg_pair) break;
+        const float* src = n == 0 ? w.S : w.XB(bj);
+        const bool last = n == FV_MAX_DILATIONS - 1;
+        if (bigvgan && (st = run_aa_snake(br.act[2 * n], src, w.XA(bj), sp, bs))) return st;
+        // xt = c1(act(x)); the second activation is fused into c1's epilogue for SiLU
+        ConvRun r = conv_run(sp.B, sp.t, bigvgan ? w.XA(bj) : src, w.XT(bj));
+        r.pre_act = r.post_act = act;
+        if ((st = conv_layer_run(br.c1[n], r, bs))) return st;
+        if (sp.dbg_here && n == sp.dbg_pair && sp.dbg_half == 0) break;
+        if (bigvgan && (st = run_aa_snake(br.act[2 * n + 1], w.XT(bj), w.XA(bj), sp, bs))) return st;
+        // x = c2(act(xt)) + x ; the last pair of each branch accumulates the branch mean into Y
+        r = conv_run(sp.B, sp.t, bigvgan ? w.XA(bj) : w.XT(bj), last ? bp.y_last : w.XB(bj));
+        r.res = src;
+        if (last) {
+            r.out_mode = bp.mode_last;
+            r.out_scale = bp.scale_last;
+            if ((st = ord.before_last(bp))) return st;
+        }
+        if ((st = conv_layer_run(br.c2[n], r, bs))) return st;
+    }
+    return FV_OK;
+}
+
+// x = ups[i](silu(x))  — HiFiGAN (hifigan.py:230-231); BigVGAN has no pre-activation (bigvgan.py:355-356); returns the stage's length through t
+fv_status run_stage_up(fv_engine& e, const UpStage& stg, const UpsWorkspace& w, bool sum3, int B, int T, int& t, hipStream_t s) {
+    ConvRun r = conv_run(B, t, w.cur, w.S);
+    if (sum3) {   // the previous stage left its three branch outputs: the upsampler conv forms their mean itself
+        r.x = w.XB(0);
+        r.x2 = w.XB(1);
+        r.x3 = w.XB(2);
+        r.sum_tmp = w.cur;   // (kernels without the three-operand staging form it here first)
+    }
+    r.pre_act = e.ups.bigvgan ? FV_ACT_NONE : FV_ACT_SILU;
+    if (const fv_status st = conv_layer_run(stg.up, r, s)) return st;
+    t = (int)stg.up.out_len(t);
+    if (e.ups.cfg.use_template) {   // x = x + noise_convs[i](template)  (hifigan.py:233-234)
+        const int Ta = (int)e.ups.out_len(T);
+        FV_PROF(s, "noise_conv_add", 2.0 * B * stg.ch * stg.nk * t, 8.0 * B * stg.ch * t,
+                launch_noise_conv_add(e.cur_template, stg.d_nw, stg.d_nb, w.S, B, stg.ch, t, Ta, stg.nk, stg.nstride, stg.npad, s));
+    }
+    return FV_OK;
+}
+
+// activation_post -> conv_post -> tanh (hifigan.py:245-247 / bigvgan.py:367-369); sum3: the last stage left its three branch outputs
+fv_status run_post(const UpsamplerModel& ups, const UpsWorkspace& w, bool sum3, float* d_out, int B, int t, hipStream_t s) {
+    const float* post_in = w.cur;
     int pre = ups.cfg.post_activation;   // post_activation() (hifigan.py:213,245): SiLU by default
     const float pre_slope = ups.cfg.post_activation_slope;
     if (ups.bigvgan) {
         // (XA(0) is free again: every branch has joined)
-        FV_PROF(s, post_sum3 ? "aa_snake sum3" : "aa_snake", 60.0 * B * ups.post_cin * t, (post_sum3 ? 16.0 : 8.0) * B * ups.post_cin * t,
-                launch_aa_snake(post_sum3 ? XB(0) : cur, XA(0), ups.act_post.d_alpha, ups.act_post.d_inv_beta, ups.act_post.d_up,
-                                ups.act_post.d_down, B, ups.post_cin, t, s, post_sum3 ? XB(1) : nullptr, post_sum3 ? XB(2) : nullptr));
-        post_in = XA(0);
+        FV_PROF(s, sum3 ? "aa_snake sum3" : "aa_snake", 60.0 * B * ups.post_cin * t, (sum3 ? 16.0 : 8.0) * B * ups.post_cin * t,
+                launch_aa_snake(sum3 ? w.XB(0) : w.cur, w.XA(0), ups.act_post.d_alpha, ups.act_post.d_inv_beta, ups.act_post.d_up,
+                                ups.act_post.d_down, B, ups.post_cin, t, s, sum3 ? w.XB(1) : nullptr, sum3 ? w.XB(2) : nullptr));
+        post_in = w.XA(0);
         pre = FV_ACT_NONE;
-        post_sum3 = false;   // the mean is in: conv_post reads the activated tensor
+        sum3 = false;   // the mean is in: conv_post reads the activated tensor
     }
     const int qk = ups.cfg.post_conv_kernel_size;
-    if (post_sum3) {
-        FV_PROF(s, "conv_post_narrow sum3", 2.0 * B * ups.post_cin * qk * t, 4.0 * B * (3 * ups.post_cin + 1) * t,
-                launch_conv_narrow(XB(0), ups.d_wpost, ups.d_bpost, d_out, B, ups.post_cin, t, 1, qk, get_padding(qk), pre, FV_ACT_TANH, pre_slope,
-                                   s, XB(1), XB(2)));
-        return FV_OK;
-    }
-    FV_PROF(s, "conv_post_narrow", 2.0 * B * ups.post_cin * qk * t, 4.0 * B * (ups.post_cin + 1) * t,
-            launch_conv_narrow(post_in, ups.d_wpost, ups.d_bpost, d_out, B, ups.post_cin, t, 1, qk, get_padding(qk), pre,
-                               FV_ACT_TANH, pre_slope, s));
+    FV_PROF(s, sum3 ? "conv_post_narrow sum3" : "conv_post_narrow", 2.0 * B * ups.post_cin * qk * t, 4.0 * B * ((sum3 ? 3 : 1) * ups.post_cin + 1) * t,
+            launch_conv_narrow(sum3 ? w.XB(0) : post_in, ups.d_wpost, ups.d_bpost, d_out, B, ups.post_cin, t, 1, qk, get_padding(qk), pre, FV_ACT_TANH,
+                               pre_slope, s, sum3 ? w.XB(1) : nullptr, sum3 ? w.XB(2) : nullptr));
     return FV_OK;
+}
+
+}  // namespace
+
+fv_status fv_engine::run_upsampler(const float* d_in, float* d_out, int B, int T, float* ws, hipStream_t s) {
+    const int nk = ups.cfg.num_kernels, n_stages = (int)ups.stages.size();
+    UpsWorkspace w(ws, (ups.max_elems(T) * B + 63) / 64 * 64);
+    fv_status st;
+    // Profiling runs stay on one stream so that per-kernel hipEvent durations do not overlap.
+    const bool multi = opt.branch_streams && nk > 1 && !profiling;
+    if (multi && (st = ensure_branch_streams(nk))) return st;
+    BranchOrder ord{*this, s, multi, nk};
+    // conv_pre (hifigan.py:227)
+    if ((st = conv_layer_run(ups.conv_pre, conv_run(B, T, d_in, w.cur), s))) return st;
+    int t = (int)ups.conv_pre.out_len(T);
+    MeanForm mean = MEAN_IN_BRANCHES;   // of the previous stage
+    for (int i = 0; i < n_stages; ++i) {
+        const UpStage& stg = *ups.stages[i];
+        if ((st = run_stage_up(*this, stg, w, mean == MEAN_IN_NEXT_UP, B, T, t, s))) return st;
+        const StagePlan sp = plan_stage(*this, knobs(), w, i, B, t, multi);
+        if ((st = ord.fork(i, sp.tree))) return st;
+        for (int jj = 0; jj < nk; ++jj) {
+            const BranchPlan& bp = sp.br[jj];
+            const ResBranch& br = *stg.branches[bp.j];
+            if ((st = ord.enter(bp))) return st;
+            switch (bp.form) {
+                case BRANCH_PAIRS: st = run_branch_pairs(br, w, sp, bp, ord); break;
+                case BRANCH_AMP: st = run_branch_amp(br, w, sp, bp, ord); break;
+                case BRANCH_LAYERS: st = run_branch_layers(br, ups.bigvgan, w, sp, bp, ord); break;
+            }
+            if (st || (st = ord.after_last(bp))) return st;
+        }
+        if ((st = ord.join())) return st;
+        mean = sp.mean;
+        if (mean == MEAN_KERNEL && (st = launch_mean_of_three(w.XB(0), w.XB(1), w.XB(2), w.Y, (long long)B * sp.ch * t, s))) return st;
+        if (sp.dbg_here) {
+            std::fprintf(stderr, "FV_DEBUG_STOP: stage %d ch=%d t=%d me=%lld S=%lld Y=%lld\n", i, sp.ch, t, (long long)w.me,
+                         (long long)(w.S - ws), (long long)(w.Y - ws));
+            return FV_OK;
+        }
+        std::swap(w.cur, w.Y);
+    }
+    return run_post(ups, w, mean == MEAN_IN_POST, d_out, B, t, s);
 }
 
 fv_status fv_engine::run_convnext(const float* d_in, float* d_out, int B, int T, float* ws, hipStream_t s) {
@@ -563,7 +642,7 @@ fv_status forward_common(fv_engine* e, const float* d_in, const float* d_templat
     // it: the sequence is captured on an engine-owned stream and replayed on stream 0 — without the two cross-stream waits a redirect through a side
     // stream costs every call (single clip: ~0.04 ms of 0.75).
     fv_engine::GraphKey key{d_in, d_out, d_workspace, d_template, d_noise, batch, t_in, s};
-    const bool graphable = e->use_graph && !e->profiling;
+    const bool graphable = e->opt.use_graph && !e->profiling;
     if (graphable) {
         for (auto& g : e->graphs)
             if (g.key == key) {
@@ -601,11 +680,11 @@ fv_status forward_common(fv_engine* e, const float* d_in, const float* d_templat
                     (void)hipGraphDestroy(graph);
                 }
                 (void)hipGetLastError();
-                e->use_graph = false;   // capture is not available in this context: stay eager from now on
+                e->opt.use_graph = false;   // capture is not available in this context: stay eager from now on
                 if (st) return st;
             } else {
                 (void)hipGetLastError();
-                e->use_graph = false;
+                e->opt.use_graph = false;
             }
         }
         e->last_key = key;

@@ -283,6 +283,30 @@ struct RefineModel {
 
 using namespace fv;
 
+// Per-engine options: read from the environment once, at fv_create (read_engine_options, engine_build.hip) — an engine keeps the values it was
+// created under, so two engines of one process can differ (the tests' A/B pairs)
+struct EngineOptions {
+    bool fuse_pairs = true;   // FV_NO_PAIR_FUSION=1 in the environment disables the fused (c1, c2) kernels (A/B runs)
+    bool post_mean_fused = true;   // FV_NO_POST_SUM3=1: mean_of_three_kernel before conv_post instead of the mean formed in its staging (A/B runs)
+    int chain_max_c = 0;      // FV_CHAIN_MAX_C: stages this narrow accumulate the branch mean in the branches' last epilogues (ordered by events) instead of keeping three outputs
+    int pair_max_c = 128;     // FV_PAIR_MAXC: widest stage whose (c1, c2) pairs fuse where a kernel exists (experiments)
+    bool fuse_amp_convs = true;   // FV_NO_AMP_FUSION=1: BigVGAN's narrow stages run aa_snake + conv launches instead of amp_conv (A/B runs)
+    // Measured in the step (BigVGAN-24k B = 64, interleaved, tools/ab_bigvgan.py): none 37.35 ms; k = 3 only 37.15; k <= 7 37.5; all 38.1.
+    // Serialized, amp_conv equals conv + aa_snake within 5 % everywhere, but the separate activation pass is HBM-bound work that the
+    // other branches' MFMA-bound convs overlap, while the fused one is VALU work inside an MFMA kernel (12 - 20 cycles of matrix
+    // time per VALU instruction of a co-resident wave, tools/ubench/mfma_mix.hip) — so only the shortest convs fuse by default.
+    // Round 6: with the unfused convs on Winograd tap groups the fused form lost its margin — BigVGAN-24k B = 64, interleaved: fused at C <= 64 25.98 - 26.04 ms,
+    // at C = 32 only 25.85 - 25.93, nowhere 25.79 - 25.93 (profiles/r06v_bigvgan_amp_fusion.txt): C = 32 stays fused (its launches are the HBM-bound ones).
+    int fuse_amp_max_c = 32, fuse_amp_max_k = 3;   // FV_AMP_MAXC / FV_AMP_MAXK override (experiments, tests)
+    bool use_graph = true;        // FV_NO_GRAPH=1 disables hipGraph replay (so do FV_DEBUG_STOP, fv_set_graph_replay(0) and a failed capture)
+    bool branch_streams = true;   // FV_SINGLE_STREAM=1 runs the ResBlock branches back to back on the caller's stream (the chain form of the branch mean)
+    bool single_tree = false;     // FV_SINGLE_STREAM=2: one stream too, but the TREE form — the kernel instances of the shipped three-stream step, launch by launch (rocprofv3 / PMC passes: tools/probe_model.py)
+    int tile_frames_override = 0;   // FV_TILE_FRAMES: tile length in frames (tests / experiments); 0 = only when the addressing span needs it
+    // FV_DEBUG_STOP = stage * 100 + pair * 10 + half stops the upsampler forward after that stage's dilation pair (half 0: after c1, 1: after c2)
+    // with the branch buffers left in the workspace for inspection (tools/archive/probe_f16_locate.py); -1 = unset
+    int debug_stop = -1;
+};
+
 struct fv_engine {
     fv_config cfg{};
     std::map<std::string, HostTensor> raw;
@@ -300,18 +324,7 @@ struct fv_engine {
     int algo = FV_CONV_ALGO_AUTO;       // fv_set_conv_algorithm
     bool invariant = false;             // fv_set_batch_invariant
     void drop_graphs();
-    bool fuse_pairs = true;   // FV_NO_PAIR_FUSION=1 in the environment disables the fused (c1, c2) kernels (A/B runs)
-    bool post_mean_fused = true;   // FV_NO_POST_SUM3=1: mean_of_three_kernel before conv_post instead of the mean formed in its staging (A/B runs)
-    int chain_max_c = 0;      // FV_CHAIN_MAX_C: stages this narrow accumulate the branch mean in the branches' last epilogues (ordered by events) instead of keeping three outputs
-    int pair_max_c = 128;     // FV_PAIR_MAXC: widest stage whose (c1, c2) pairs fuse where a kernel exists (experiments)
-    bool fuse_amp_convs = true;   // FV_NO_AMP_FUSION=1: BigVGAN's narrow stages run aa_snake + conv launches instead of amp_conv (A/B runs)
-    // Measured in the step (BigVGAN-24k B = 64, interleaved, tools/ab_bigvgan.py): none 37.35 ms; k = 3 only 37.15; k <= 7 37.5; all 38.1.
-    // Serialized, amp_conv equals conv + aa_snake within 5 % everywhere, but the separate activation pass is HBM-bound work that the
-    // other branches' MFMA-bound convs overlap, while the fused one is VALU work inside an MFMA kernel (12 - 20 cycles of matrix
-    // time per VALU instruction of a co-resident wave, tools/ubench/mfma_mix.hip) — so only the shortest convs fuse by default.
-    // Round 6: with the unfused convs on Winograd tap groups the fused form lost its margin — BigVGAN-24k B = 64, interleaved: fused at C <= 64 25.98 - 26.04 ms,
-    // at C = 32 only 25.85 - 25.93, nowhere 25.79 - 25.93 (profiles/r06v_bigvgan_amp_fusion.txt): C = 32 stays fused (its launches are the HBM-bound ones).
-    int fuse_amp_max_c = 32, fuse_amp_max_k = 3;   // FV_AMP_MAXC / FV_AMP_MAXK override (experiments, tests)
+    EngineOptions opt;
     struct GraphKey {
         const void* in;
         void* out;
@@ -333,9 +346,6 @@ struct fv_engine {
     std::vector<GraphEntry> graphs;
     GraphKey last_key{};
     bool have_last = false;
-    bool use_graph = true;        // FV_NO_GRAPH=1 disables hipGraph replay
-    bool branch_streams = true;   // FV_SINGLE_STREAM=1 runs the ResBlock branches back to back on the caller's stream (the chain form of the branch mean)
-    bool single_tree = false;     // FV_SINGLE_STREAM=2: one stream too, but the TREE form — the kernel instances of the shipped three-stream step, launch by launch (rocprofv3 / PMC passes: tools/probe_model.py)
     std::vector<hipStream_t> bstreams;   // nk-1 auxiliary streams (branch 0 runs on the caller's stream)
     hipStream_t null_capture = nullptr;   // calls on the legacy default stream: the launch sequence is captured here, the graph is launched on stream 0
     std::vector<hipEvent_t> bev_fork, bev_last;
@@ -523,7 +533,6 @@ struct fv_engine {
     int tile_frame_limit() const;
     TilePlan tile_plan(int t_in) const;
     size_t tile_workspace_bytes(int batch, const TilePlan& tp) const;   // what run_model carves for batch clips as tp.n tiles each
-    int tile_frames_override = 0;   // FV_TILE_FRAMES: tile length in frames (tests / experiments); 0 = only when the addressing span needs it
     fv_status run_upsampler(const float* d_in, float* d_out, int B, int T, float* ws, hipStream_t s);
     const float* cur_template = nullptr;   // set by fv_forward_template for the duration of one call
     // the generators that take a pitch template beside the mel: RefineGAN always, the upsampler family when built with use_template

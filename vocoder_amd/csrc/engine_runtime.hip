@@ -74,6 +74,12 @@ static const Knobs* load_knobs() {
     }
     if (const char* v = std::getenv("FV_X_UPS_TILE256")) k->ups_tile256 = std::atoi(v);
     k->no_sum3 = std::getenv("FV_NO_SUM3") != nullptr;
+    if (const char* v = std::getenv("FV_BRANCH_MEAN")) k->branch_mean_chain = v[0] == 'c';
+    if (const char* v = std::getenv("FV_SPLITK")) k->splitk = v[0] == '3' ? 32 : 64;
+    if (const char* v = std::getenv("FV_SPLITK_MAX")) k->splitk_max = std::atoll(v);
+    if (const char* v = std::getenv("FV_AA_VEC4")) k->aa_vec4 = v[0] != '0';
+    k->no_f16x3_pairs = std::getenv("FV_NO_F16X3_PAIRS") != nullptr;
+    k->w44_no_qr = std::getenv("FV_X_W44_NO_QR") != nullptr;
     return k;
 }
 const Knobs& knobs() {

@@ -85,7 +85,7 @@ fv_engine::TilePlan fv_engine::tile_plan(int t_in) const {
     TilePlan p;
     const int reach = reach_frames();
     int limit = tile_frame_limit();   // 0 for the models that are never tiled (LOGMEL / REFINEGAN)
-    if (tile_frames_override > 0) limit = std::min(limit, std::max(tile_frames_override, 4 * reach));
+    if (opt.tile_frames_override > 0) limit = std::min(limit, std::max(opt.tile_frames_override, 4 * reach));
     if (limit <= 0 || t_in <= limit) return p;
     if (limit < 4 * reach) return p;   // (a model whose reach does not fit the span: the per-layer check reports it)
     // The gather / scatter address tiles and clips at exactly frames x hop samples: a model that is not frame-aligned (frame_hop: e.g. a "center"

@@ -47,6 +47,12 @@ struct Knobs {
                           //   (after all the shape remaps; tests pin the kernel instance by instance), -1 = by shape
     int ups_tile256 = 1;  // FV_X_UPS_TILE256: 0 = the two-tap polyphase upsamplers keep the 128-row tiles instead of 256 x 64 (A/B runs, tests)
     bool no_sum3 = false; // FV_NO_SUM3: the three-operand stack-mean goes through mean_of_three_kernel instead of the conv's staging (A/B runs, tests)
+    bool branch_mean_chain = false;   // FV_BRANCH_MEAN=chain: the branch mean as the ordered accumulate on branch streams too (engine_forward.hip plan_stage; experiments, tests)
+    int splitk = 0;       // FV_SPLITK: 32 / 64 = that tile of the split-K latency kernel wherever one is taken, 0 = by shape (experiments)
+    long long splitk_max = 200;   // FV_SPLITK_MAX: largest launch, in workgroups of the small tile, that still takes the split-K latency kernel (experiments)
+    bool aa_vec4 = true;  // FV_AA_VEC4=0: aa_snake runs the pair form on every tile instead of 16-byte accesses on interior tiles
+    bool no_f16x3_pairs = false;   // FV_NO_F16X3_PAIRS: f16x3 precision mode runs per-layer split-fp16 convs instead of the fused pair kernels (diagnostics)
+    bool w44_no_qr = false;   // FV_X_W44_NO_QR: conv_wino44 without the row-split 16-byte-store epilogue (A/B runs)
 };
 // TileCfg index of a tile name ("128x128", ..., "128x96"), -1 if there is none (conv_layer.hip)
 int conv_tile_by_name(const char* name);

@@ -1,7 +1,6 @@
 // HBM-bound helper kernels around the MFMA conv: narrow-output conv (conv_post), anti-aliased SnakeBeta,
 // depthwise-conv + LayerNorm, ISTFT spectrum / overlap-add.  All are coalesced along T (the contiguous axis of
 // the reference's (B, C, T) layout) and stage their reuse windows in LDS.
-#include <cstdlib>
 
 #include "conv_mfma_impl.h"
 
@@ -598,8 +597,7 @@ fv_status launch_aa_snake(const float* x, float* y, const float* alpha_eff, cons
     }
     const int n_tiles = (T + AA_TT - 1) / AA_TT;
     // interior tiles move 16 bytes per lane when every row starts 16-byte aligned (aa_snake4_tile); FV_AA_VEC4=0: the pair form
-    static const bool no_vec4 = std::getenv("FV_AA_VEC4") && std::getenv("FV_AA_VEC4")[0] == '0';
-    const int vec4 = !no_vec4 && T % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    const int vec4 = knobs().aa_vec4 && T % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
     hipLaunchKernelGGL(aa_snake_pk_kernel, dim3((unsigned)((long long)B * C * ((n_tiles + 1) / 2))), dim3(256), 0, s, x, y, alpha_eff,
                        inv_beta, up_taps, down_taps, C, T, n_tiles, vec4, x2, x3);
     FV_HIP_CHECK(hipGetLastError());
