@@ -16,8 +16,8 @@ torch = pytest.importorskip("torch")
 TOL = 2e-4
 
 # (n_fft, hop, n_mels): plain; hop does not divide n_fft (the last tap is partial, as 24000_2048_3072); win - hop odd (pad_l != pad_r);
-# LinearSpectrogram
-CONFIGS = [(256, 64, 20), (96, 64, 12), (256, 51, 20), (256, 64, 0)]
+# LinearSpectrogram; a stream carry (n_fft samples) wider than one 256-thread block of the carry kernel, with a partial last block
+CONFIGS = [(256, 64, 20), (96, 64, 12), (256, 51, 20), (256, 64, 0), (320, 80, 16)]
 _modules: dict = {}
 _refs: dict = {}
 

@@ -140,6 +140,32 @@ def test_streaming_is_bit_identical_to_the_whole_row(orig, new):
                 st.reset()
 
 
+def test_stream_with_the_smallest_carry_uneven_chunks_and_strided_rows():
+    """2 -> 3 Hz has the smallest carry, H samples: chunks below, at and above H, each a strided slice of one (2, L) tensor (the row stride
+    exceeds the chunk), are bit-identical to the whole row; so is a second utterance after reset(), which starts from zeros whatever the
+    first one left in the carry."""
+    mod, ref, d = _pair(2, 3, HANN)
+    H = (d.kp + 3) // 4 * 4                                     # the samples a stream carries (fv_resample_stream_create)
+    chunks = [1, H - 1, H, H + 1, 1]
+    L = sum(chunks)
+    rng = np.random.default_rng(23)
+    with mod.stream(batch=2, max_chunk=H + 1) as st:
+        for _ in range(2):
+            x = torch.from_numpy(rng.uniform(-1, 1, size=(2, L)).astype(np.float32)).cuda()
+            want = _bits(mod(x).cpu().numpy())
+            outs, N = [], 0
+            for c in chunks:
+                piece = x[:, N:N + c]
+                assert piece.stride(0) == L > c
+                outs.append(st.push(piece))
+                N += c
+                assert st.received_samples == N and st.emitted_samples == d.emit_count(N)
+            outs.append(st.flush())
+            got = _bits(torch.cat(outs, dim=1).cpu().numpy())
+            assert got.shape == want.shape and np.array_equal(got, want)
+            st.reset()
+
+
 def test_a_refused_push_leaves_the_stream_intact():
     mod, ref, d = _pair(44100, 48000, HANN)
     x = torch.from_numpy(np.random.default_rng(2).uniform(-1, 1, size=(1, 400)).astype(np.float32)).cuda()

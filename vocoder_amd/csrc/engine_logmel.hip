@@ -6,8 +6,9 @@
 #include <memory>
 
 #include "engine_internal.h"
+#include "sample_stream.h"
 
-static constexpr int64_t kLogmelMaxLen = 1LL << 40;   // N hop stays far inside 64 bits
+static constexpr int64_t kLogmelMaxLen = kSampleStreamMaxLen;   // N hop stays far inside 64 bits
 
 static int64_t logmel_frames(const fv_logmel_config& c, int64_t L) {
     const int64_t pad = c.win_length - c.hop_length;   // pad_l + pad_r
@@ -40,16 +41,10 @@ static fv_status logmel_engine_check(const fv_engine* e, const char* fn) {
     return FV_OK;
 }
 
-struct fv_logmel_stream {
+// the core's buffers are two (B, H) carries: buf[cur] holds the samples [N - H, N), and a push reads its chunk in place
+struct fv_logmel_stream : SampleStream {
     fv_engine* e = nullptr;
-    int B = 0, max_chunk = 0, H = 0, cur = 0;
     int max_frames = 0;                     // the most frames one call emits
-    float* buf[2] = {nullptr, nullptr};     // one allocation: two (B, H) carries, buf[cur] holding the samples [N - H, N)
-    int64_t N = 0, E = 0;
-    bool flushed = false;
-    ~fv_logmel_stream() {
-        if (buf[0]) (void)hipFree(buf[0]);
-    }
     size_t ws_bytes() const { return align_up(e->logmel_ws_elems(B, max_frames) * sizeof(float), 256); }
 };
 
@@ -73,33 +68,18 @@ static fv_status logmel_stream_step(fv_logmel_stream* st, const float* d_wave, i
         set_error("%s: null argument", fn);
         return FV_ERR_INVALID;
     }
-    if (st->flushed) {
-        set_error("%s: the stream was flushed; fv_logmel_stream_reset it before the next utterance", fn);
-        return FV_ERR_STATE;
-    }
+    long long N2;
+    bool noop;
+    if (const fv_status rs = st->admit(fn, "fv_logmel_stream_reset", d_wave, row_stride, c, flush, &N2, &noop)) return rs;
+    if (noop) return FV_OK;
     fv_engine* e = st->e;
     const fv_logmel_config& mc = e->cfg.mel;
-    if (!flush) {
-        if (c < 0 || c > st->max_chunk) {
-            set_error("fv_logmel_stream_push: %d samples, outside [0, max_chunk_samples = %d] of this stream", c, st->max_chunk);
-            return FV_ERR_INVALID;
-        }
-        if (c == 0) return FV_OK;
-        if (!d_wave || row_stride < c) {
-            set_error("fv_logmel_stream_push: %s", d_wave ? "row_stride is shorter than the chunk" : "null chunk");
-            return FV_ERR_INVALID;
-        }
-        if (st->N + c > kLogmelMaxLen) {
-            set_error("fv_logmel_stream_push: more than 2^40 samples in one utterance");
-            return FV_ERR_INVALID;
-        }
-    } else if (st->N > 0 && logmel_row_too_short(e, st->N)) {
+    if (flush && st->N > 0 && logmel_row_too_short(e, st->N)) {
         set_error("fv_logmel_stream_flush: the utterance has %lld samples: too short for reflect padding %d/%d and one %d-sample frame",
                   (long long)st->N, e->mel.pad_l, e->mel.pad_r, mc.n_fft);
         return FV_ERR_INVALID;
     }
-    const int64_t N2 = st->N + (flush ? 0 : c);
-    const int64_t E2 = flush ? std::max(st->E, logmel_frames(mc, N2)) : std::max(st->E, logmel_frames_ready(mc, N2));
+    const int64_t E2 = std::max<int64_t>(st->E, flush ? logmel_frames(mc, N2) : logmel_frames_ready(mc, N2));
     const int64_t k = E2 - st->E;
     if (k > 0) {
         if (!d_out) {
@@ -128,13 +108,11 @@ static fv_status logmel_stream_step(fv_logmel_stream* st, const float* d_wave, i
     }
     if (!flush) {
         FV_PROF(s, "logmel_carry", 0.0, 8.0 * st->B * (double)st->H,
-                launch_logmel_carry(prev, st->buf[st->cur ^ 1], d_wave, row_stride, st->B, st->H, st->N, N2, s));
-        st->cur ^= 1;
+                launch_sample_carry(prev, st->buf[st->cur ^ 1], d_wave, st->stride, row_stride, st->B, st->N, N2 - st->H, st->N - st->H, st->H,
+                                    s));
     }
     *frames_out = k;
-    st->N = N2;
-    st->E = E2;
-    if (flush) st->flushed = true;
+    st->commit(N2, E2, flush, !flush);
     return FV_OK;
 }
 
@@ -220,21 +198,13 @@ FV_API fv_status fv_logmel_stream_create(fv_engine* e, int32_t batch, int32_t ma
         set_error("%s: null argument", fn);
         return FV_ERR_INVALID;
     }
-    if (batch < 1 || batch > 65535 || max_chunk_samples < 1 || max_chunk_samples > (1 << 28)) {
-        set_error("%s: batch (%d) must lie in [1, 65535] and max_chunk_samples (%d) in [1, 2^28]", fn, batch, max_chunk_samples);
-        return FV_ERR_INVALID;
-    }
     std::unique_ptr<fv_logmel_stream> st(new fv_logmel_stream());
     st->e = e;
-    st->B = batch, st->max_chunk = max_chunk_samples;
     // A frame not yet emitted starts less than n_fft samples before N (fv_logmel_frames_ready), and the flush reflects pad_r + 1 < n_fft samples back
-    st->H = e->cfg.mel.n_fft;
+    const int H = e->cfg.mel.n_fft;
+    if (const fv_status rs = st->create(fn, batch, max_chunk_samples, H, H)) return rs;
     // A push emits the frames that became ready: at most (n_fft + max_chunk) / hop + 1 when the first ones come out; the flush at most pad_r / hop + 1
-    st->max_frames = (int)(((int64_t)e->cfg.mel.n_fft + max_chunk_samples) / e->cfg.mel.hop_length + 2);
-    const size_t elems = (size_t)batch * (size_t)st->H;
-    FV_HIP_CHECK(hipMalloc((void**)&st->buf[0], 2 * elems * sizeof(float)));
-    st->buf[1] = st->buf[0] + elems;
-    FV_HIP_CHECK(hipMemset(st->buf[0], 0, 2 * elems * sizeof(float)));
+    st->max_frames = (int)(((int64_t)H + max_chunk_samples) / e->cfg.mel.hop_length + 2);
     *out = st.release();
     return FV_OK;
 }
@@ -261,8 +231,7 @@ FV_API fv_status fv_logmel_stream_reset(fv_logmel_stream* s) {
         set_error("fv_logmel_stream_reset: null stream");
         return FV_ERR_INVALID;
     }
-    s->N = s->E = 0;      // samples before 0 do not exist by index, whatever the carry holds
-    s->flushed = false;
+    s->reset();
     return FV_OK;
 }
 

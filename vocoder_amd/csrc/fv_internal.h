@@ -415,6 +415,11 @@ fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const 
 // y (rows, C, Ly) -> out (., C, out_frames): each entry's samples, then zeros to the row's end
 fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames,
                            int hop, hipStream_t s);
+// sample streams (sample_stream.h): next[b][i] = sample next_origin + i of row b, i < count, where `N` samples have arrived before this call — from
+// chunk[b][idx - N] at or after N, from prev[b][idx - prev_origin] before it, 0.0f before the utterance's start; prev and next are two buffers
+// of row stride `stride`
+fv_status launch_sample_carry(const float* prev, float* next, const float* chunk, long long stride, long long chunk_stride, int B, long long N,
+                              long long next_origin, long long prev_origin, long long count, hipStream_t s);
 // log-mel front-end on ragged rows and stream chunks (logmel_windows.hip; fv_logmel_ragged_forward, fv_logmel_stream_*): per-row values travel
 // BY VALUE, kLogmelRows rows per launch, as the session pool's tables do
 static constexpr int kLogmelRows = 32;
@@ -429,9 +434,6 @@ fv_status launch_logmel_window(const float* carry, long long carry_stride, long 
                                int TP, int pad_l, int pad_r, hipStream_t s);
 // y (B, C, T): columns >= row_cols[b] of row b set to 0.0f
 fv_status launch_zero_columns(float* y, const long long* row_cols, int B, int C, long long T, hipStream_t s);
-// next (B, H) = the samples [N2 - H, N2) of every row out of prev (B, H) = [N - H, N) and the chunk = [N, N2)
-fv_status launch_logmel_carry(const float* prev, float* next, const float* chunk, long long chunk_stride, int B, int H, long long N,
-                              long long N2, hipStream_t s);
 // rows [0,nb) = Re, [nbp, nbp+nb) = Im, zero padded to nbp = round_up(nb, 8)
 fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T, int nb, int nbp, hipStream_t s);
 // frames (B, n_fft, T) (already windowed by the synthesis basis) -> overlap-add, crop, divide by the envelope.

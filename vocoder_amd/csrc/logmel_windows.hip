@@ -2,7 +2,6 @@
 // (fish_vocoder/data/transforms/spectrogram.py:25-56 pads whole, equal-length rows; test.py:64-71 feeds it one file at a time).
 //   logmel_window : the polyphase signal Yp[row][r][tp] of the frames [f0, f0 + n) of every row, with per-row edges
 //   zero_columns  : columns >= T_b of a (B, C, T) result set to 0.0f
-//   logmel_carry  : a stream's last H samples moved from one ping-pong buffer to the other
 // HBM-bound copies: each lane moves one fp32.
 #include <algorithm>
 
@@ -107,28 +106,6 @@ fv_status launch_zero_columns(float* y, const long long* row_cols, int B, int C,
         hipLaunchKernelGGL(zero_columns_kernel, dim3((unsigned)((span + 255) / 256), C, nz), dim3(256), 0, s, y, blk, C, T, b0);
         FV_HIP_CHECK(hipGetLastError());
     }
-    return FV_OK;
-}
-
-// next[b][i] = sample N2 - H + i of row b, i < H: from the chunk (samples [N, N2)) or from prev (samples [N - H, N)); samples before 0 do not
-// exist and are never read (the window kernel does not read them either)
-__global__ __launch_bounds__(256) void logmel_carry_kernel(const float* __restrict__ prev, float* __restrict__ next,
-                                                           const float* __restrict__ chunk, long long chunk_stride, int H, long long N,
-                                                           long long N2) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= H) return;
-    const long long b = blockIdx.y;
-    const long long idx = N2 - H + i;
-    float v = 0.f;
-    if (idx >= N) v = chunk[b * chunk_stride + (idx - N)];
-    else if (idx >= 0) v = prev[b * H + (idx - (N - H))];
-    next[b * H + i] = v;
-}
-
-fv_status launch_logmel_carry(const float* prev, float* next, const float* chunk, long long chunk_stride, int B, int H, long long N,
-                              long long N2, hipStream_t s) {
-    hipLaunchKernelGGL(logmel_carry_kernel, dim3((H + 255) / 256, B), dim3(256), 0, s, prev, next, chunk, chunk_stride, H, N, N2);
-    FV_HIP_CHECK(hipGetLastError());
     return FV_OK;
 }
 

@@ -21,7 +21,7 @@
 #include <numeric>
 #include <vector>
 
-#include "fv_internal.h"
+#include "sample_stream.h"
 
 namespace fv {
 namespace {
@@ -153,15 +153,6 @@ __device__ __forceinline__ void resample_body(const ResampleParams& p) {
 
 __global__ __launch_bounds__(kResThreads) void resample_kernel(const ResampleParams p) { resample_body<false>(p); }
 __global__ __launch_bounds__(kResThreads) void resample_global_kernel(const ResampleParams p) { resample_body<true>(p); }
-
-// stream: the next work buffer [last H samples | chunk] out of the previous one and the caller's chunk
-__global__ void resample_carry_kernel(const float* prev, float* next, const float* chunk, long long cols, long long x_stride, int H, int prev_c,
-                                      int c) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const long long row = blockIdx.y;
-    if (i >= H + c) return;
-    next[row * cols + i] = i < H ? prev[row * cols + prev_c + i] : chunk[row * x_stride + (i - H)];
-}
 
 constexpr double kKaiserBeta = 14.769656459379492;
 
@@ -301,19 +292,14 @@ struct fv_resample {
     long long emit_count(long long N) const { return count_below(end.data(), d.n, d.o, N + d.width + 1); }
 };
 
-struct fv_resample_stream {
+// the core's buffers are the work buffers [last H samples | chunk] with row stride H + max_chunk rounded up to 4: buf[cur] holds the samples
+// [N - H - prev_c, N)
+struct fv_resample_stream : SampleStream {
     fv_resample* r = nullptr;
-    int B = 0, max_chunk = 0, H = 0, prev_c = 0, cur = 0;
-    long long cols = 0;          // H + max_chunk rounded up to 4: the row stride of buf[]
-    float* buf[2] = {nullptr, nullptr};   // one allocation
-    long long N = 0, E = 0;
-    bool flushed = false;
-    ~fv_resample_stream() {
-        if (buf[0]) (void)hipFree(buf[0]);
-    }
+    int prev_c = 0;
 };
 
-static constexpr long long kResMaxLen = 1LL << 40;   // n L stays far inside 64 bits
+static constexpr long long kResMaxLen = kSampleStreamMaxLen;   // n L stays far inside 64 bits
 
 // outputs [m_begin, m_end) of every row into y columns [0, m_end - m_begin)
 static fv_status resample_run(const fv_resample* r, const char* fn, const float* x, long long x_stride, long long in_origin, const int* d_lengths,
@@ -492,19 +478,10 @@ FV_API fv_status fv_resample_stream_create(fv_resample* r, int32_t batch, int32_
         return FV_ERR_INVALID;
     }
     *out = nullptr;
-    if (batch < 1 || batch > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
-        set_error("fv_resample_stream_create: batch (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", batch, max_chunk);
-        return FV_ERR_INVALID;
-    }
     std::unique_ptr<fv_resample_stream> st(new fv_resample_stream());
     st->r = r;
-    st->B = batch, st->max_chunk = max_chunk;
-    st->H = (r->d.kp + 3) / 4 * 4;   // an output not yet emitted starts less than Kp samples before N
-    st->cols = ((long long)st->H + max_chunk + 3) / 4 * 4;
-    const size_t elems = (size_t)batch * (size_t)st->cols;
-    FV_HIP_CHECK(hipMalloc((void**)&st->buf[0], 2 * elems * sizeof(float)));
-    st->buf[1] = st->buf[0] + elems;
-    FV_HIP_CHECK(hipMemset(st->buf[0], 0, 2 * elems * sizeof(float)));
+    const int H = (r->d.kp + 3) / 4 * 4;   // an output not yet emitted starts less than Kp samples before N
+    if (const fv_status rs = st->create("fv_resample_stream_create", batch, max_chunk, H, ((long long)H + max_chunk + 3) / 4 * 4)) return rs;
     *out = st.release();
     return FV_OK;
 }
@@ -519,27 +496,11 @@ static fv_status resample_stream_step(fv_resample_stream* st, const float* d_x, 
         set_error("%s: null argument", fn);
         return FV_ERR_INVALID;
     }
-    if (st->flushed) {
-        set_error("%s: the stream was flushed; fv_resample_stream_reset it before the next utterance", fn);
-        return FV_ERR_STATE;
-    }
-    if (!flush) {
-        if (c < 0 || c > st->max_chunk) {
-            set_error("fv_resample_stream_push: %d samples, more than max_chunk = %d of this stream", c, st->max_chunk);
-            return FV_ERR_INVALID;
-        }
-        if (c == 0) return FV_OK;
-        if (!d_x || x_row_stride < c) {
-            set_error("fv_resample_stream_push: %s", d_x ? "x_row_stride is shorter than the chunk" : "null chunk");
-            return FV_ERR_INVALID;
-        }
-    }
+    long long N2;
+    bool noop;
+    if (const fv_status rs = st->admit(fn, "fv_resample_stream_reset", d_x, x_row_stride, c, flush, &N2, &noop)) return rs;
+    if (noop) return FV_OK;
     const fv_resample* r = st->r;
-    const long long N2 = st->N + (flush ? 0 : c);
-    if (N2 > kResMaxLen) {
-        set_error("%s: more than 2^40 samples in one utterance", fn);
-        return FV_ERR_INVALID;
-    }
     const long long E2 = flush ? r->out_len(N2) : std::max(st->E, r->emit_count(N2));
     const long long k = E2 - st->E;
     if (k > 0 && (!d_y || y_row_stride < k)) {
@@ -547,20 +508,18 @@ static fv_status resample_stream_step(fv_resample_stream* st, const float* d_x, 
         return FV_ERR_INVALID;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (!flush || k > 0) {
-        const int nc = flush ? 0 : c, cols = st->H + nc;
+    const bool run = !flush || k > 0;
+    if (run) {
+        const int nc = flush ? 0 : c;
         float* next = st->buf[st->cur ^ 1];
-        hipLaunchKernelGGL(resample_carry_kernel, dim3((cols + 255) / 256, st->B), dim3(256), 0, s, st->buf[st->cur], next, d_x, st->cols,
-                           (long long)x_row_stride, st->H, st->prev_c, nc);
-        FV_HIP_CHECK(hipGetLastError());
-        if (const fv_status rs = resample_run(r, fn, next, st->cols, st->N - st->H, nullptr, N2, d_y, y_row_stride, st->B, st->E, E2, s)) return rs;
-        st->cur ^= 1;
+        if (const fv_status rs = launch_sample_carry(st->buf[st->cur], next, d_x, st->stride, x_row_stride, st->B, st->N, st->N - st->H,
+                                                     st->N - st->H - st->prev_c, st->H + nc, s))
+            return rs;
+        if (const fv_status rs = resample_run(r, fn, next, st->stride, st->N - st->H, nullptr, N2, d_y, y_row_stride, st->B, st->E, E2, s)) return rs;
         st->prev_c = nc;
     }
     *emitted = k;
-    st->N = N2;
-    st->E = E2;
-    if (flush) st->flushed = true;
+    st->commit(N2, E2, flush, run);
     return FV_OK;
 }
 
@@ -578,8 +537,7 @@ FV_API fv_status fv_resample_stream_reset(fv_resample_stream* s) {
         set_error("fv_resample_stream_reset: null stream");
         return FV_ERR_INVALID;
     }
-    s->N = s->E = 0;      // samples before 0 are zeros by index, whatever the carried buffer holds
-    s->flushed = false;
+    s->reset();
     return FV_OK;
 }
 

@@ -1,5 +1,6 @@
 // The device half of engine_windows.hip: the copy kernels between the caller's tensors, the rings and the window workspace of the time
-// tiles, streams, ragged batches and session pools.  HBM-bound: each lane moves one fp32, coalesced along T.
+// tiles, streams, ragged batches and session pools; and the carry copy of the sample streams (sample_stream.h).  HBM-bound: each lane moves
+// one fp32, coalesced along T.
 #include <algorithm>
 
 #include "fv_internal.h"
@@ -265,6 +266,34 @@ fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab,
                            out_frames * hop, hop);
         FV_HIP_CHECK(hipGetLastError());
     }
+    return FV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sample streams (sample_stream.h: fv_resample_stream_*, fv_logmel_stream_*).  A stream carries the last samples of every row in two ping-pong
+// buffers of row stride `stride`; `N` samples have arrived before this call and the chunk holds the samples [N, ...).
+//   sample_carry: next[b][i] = sample idx = next_origin + i of row b, i < count: chunk[b][idx - N] for idx >= N, prev[b][idx - prev_origin] for
+//                 0 <= idx < N, 0.0f for idx < 0 (samples before the utterance's start do not exist and are never loaded).  prev is only read
+//                 and next only written: no launch does both to one buffer.
+// Indices and row offsets are 64-bit; each lane moves one fp32, coalesced along the row.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sample_carry_kernel(const float* __restrict__ prev, float* __restrict__ next,
+                                                           const float* __restrict__ chunk, long long stride, long long chunk_stride,
+                                                           long long N, long long next_origin, long long prev_origin, long long count) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const long long b = blockIdx.y, idx = next_origin + i;
+    float v = 0.0f;
+    if (idx >= N) v = chunk[b * chunk_stride + (idx - N)];
+    else if (idx >= 0) v = prev[b * stride + (idx - prev_origin)];
+    next[b * stride + i] = v;
+}
+fv_status launch_sample_carry(const float* prev, float* next, const float* chunk, long long stride, long long chunk_stride, int B, long long N,
+                              long long next_origin, long long prev_origin, long long count, hipStream_t s) {
+    if (B <= 0 || count <= 0) return FV_OK;
+    hipLaunchKernelGGL(sample_carry_kernel, dim3((unsigned)((count + 255) / 256), B), dim3(256), 0, s, prev, next, chunk, stride, chunk_stride, N,
+                       next_origin, prev_origin, count);
+    FV_HIP_CHECK(hipGetLastError());
     return FV_OK;
 }
 }  // namespace fv

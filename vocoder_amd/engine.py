@@ -11,18 +11,10 @@ import numpy as np
 import torch
 
 from . import _lib, framing as _framing, sessions as _sessions, streaming
+from ._handle import _Handle, _emit, _require_cuda
 from ._lib import FishVocError, check  # noqa: F401
 
 _SIDE_STREAM_FOR_DEFAULT = os.environ.get("FV_DEFAULT_STREAM_SIDE", "0") == "1"   # experiments: see Engine.forward
-
-
-def _require_cuda(x: torch.Tensor, what: str) -> None:
-    if not x.is_cuda:
-        raise RuntimeError(
-            f"{what}: expected a CUDA/HIP tensor on an MI355X, got device '{x.device}'. "
-            "vocoder_amd runs only through its HIP kernels (no CPU fallback).")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{what}: expected float32, got {x.dtype}")
 
 
 def _stream_ptr(device) -> int:
@@ -44,40 +36,6 @@ def _exact(t: "torch.Tensor | None", what: str, noun: str, shape: tuple, make_co
 
 def _int_list(lengths) -> list[int]:
     return [int(t) for t in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-
-
-class _Handle:
-    """Owner of one library handle ``_h``, with the name of its destroy function and the message of a call on a closed one; optionally a
-    workspace tensor ``_ws`` and an event ``_done``, recorded after the last call that used either on the device."""
-    _destroy = ""
-    _closed = ""
-    _h: "ctypes.c_void_p | None" = None            # class defaults: close() also serves an object whose __init__ raised half way
-    _ws: "torch.Tensor | None" = None
-    _done: "torch.cuda.Event | None" = None
-
-    def _check_open(self) -> None:
-        if not self._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, self._closed)
-
-    def close(self) -> None:
-        if self._h is not None and self._h.value:
-            if self._done is not None:
-                self._done.synchronize()    # what the handle owns on the device and the workspace may still be in use there
-            getattr(self._lib, self._destroy)(self._h)
-            self._h = ctypes.c_void_p()
-            self._ws = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _EngineHandle(_Handle):
@@ -359,10 +317,7 @@ class Engine(_Handle):
         need = self.workspace_bytes(B, T)
 
         def launch(stream: int) -> int:
-            if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != x.device:
-                if self._done is not None:
-                    self._done.synchronize()   # the old workspace goes back to the caching allocator: nothing may still use it
-                self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+            self._grow_workspace(need, x.device)
             return self._launch(x, tptr, nptr, out, B, T, stream)
         self._enqueue(x.device, launch)
         return out
@@ -373,6 +328,13 @@ class Engine(_Handle):
         if x.dim() != 3 or x.shape[1] != self.in_channels:
             raise ValueError(f"expected input of shape (B, {self.in_channels}, T), got {tuple(x.shape)}")
         return x.contiguous(), x.shape[0], x.shape[2]
+
+    def _grow_workspace(self, need: int, device) -> None:
+        """Under ``self._lock`` (inside a ``launch`` of ``_enqueue``): the engine's own workspace holds ``need`` bytes on ``device``."""
+        if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != device:
+            if self._done is not None:
+                self._done.synchronize()   # the old workspace goes back to the caching allocator: nothing may still use it
+            self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
 
     def _enqueue(self, device, launch, owner: "_Handle | None" = None, eager: bool = False) -> None:
         """Every call that enqueues work on this engine (``forward``, ``forward_ragged``, ``Stream.push`` / ``flush``, ``SessionPool.step``):
@@ -385,9 +347,7 @@ class Engine(_Handle):
             check(launch(int(run.cuda_stream)))
             self._order_end(cur, run)
             if owner is not None:
-                if owner._done is None:
-                    owner._done = torch.cuda.Event()
-                owner._done.record(run)
+                owner._record_done(run)
 
     def _order_begin(self, device, eager: bool = False):
         """Under ``self._lock``: (the caller's stream, the stream to enqueue on), the latter ordered after the engine's previous call
@@ -525,10 +485,7 @@ class Engine(_Handle):
         need = self.workspace_bytes(B, max(L, 1))
 
         def launch(stream: int) -> int:
-            if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != waves.device:
-                if self._done is not None:
-                    self._done.synchronize()
-                self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=waves.device)
+            self._grow_workspace(need, waves.device)
             return self._lib.fv_logmel_ragged_forward(self._h, waves.data_ptr(), max(L, 1), arr, B, L, out.data_ptr() if out.numel() else None,
                                                       self._ws.data_ptr(), self._ws.numel() * 4, stream)
         self._enqueue(waves.device, launch, eager=True)
@@ -623,18 +580,15 @@ class Stream(_EngineHandle):
         F, _, E2 = streaming.step(self._F, self._E, n, self.context_frames, self.lookahead_frames, flush)
         k = E2 - self._E if (flush or n <= self.max_chunk_frames) else 0
         dev = self._engine.device
-        out = torch.empty((self.batch, self.out_channels, k * self.hop), dtype=torch.float32, device=dev)
-        got = ctypes.c_int64(0)
 
-        def launch(stream: int) -> int:
-            if flush:
-                return self._lib.fv_stream_flush(self._h, out.data_ptr() if k else None, ctypes.byref(got), self._ws.data_ptr(),
-                                                 self._ws.numel() * 4, stream)
-            return self._lib.fv_stream_push(self._h, mel.data_ptr(), tptr, n, out.data_ptr() if k else None, ctypes.byref(got),
-                                            self._ws.data_ptr(), self._ws.numel() * 4, stream)
-        self._engine._enqueue(dev, launch, owner=self)
-        if got.value != k:
-            raise RuntimeError(f"stream emitted {got.value} frames where the emission rule says {k}")
+        def enqueue(optr, got) -> None:
+            def launch(stream: int) -> int:
+                ws = (self._ws.data_ptr(), self._ws.numel() * 4, stream)
+                return (self._lib.fv_stream_flush(self._h, optr, got, *ws) if flush else
+                        self._lib.fv_stream_push(self._h, mel.data_ptr(), tptr, n, optr, got, *ws))
+            self._engine._enqueue(dev, launch, owner=self)
+        out = _emit((self.batch, self.out_channels, k * self.hop), k, dev, enqueue,
+                    "stream emitted {got} frames where the emission rule says {k}")
         self._F, self._E = F, E2
         return out
 
@@ -704,18 +658,15 @@ class LogMelStream(_EngineHandle):
         refused = cn.flushed or (not flush and c > self.max_chunk_samples) or (flush and cn.N > 0 and self.framing.too_short(cn.N))
         k = 0 if refused else (cn.flush_count() if flush else cn.emit_count(c))     # a refused call emits nothing; the library says why
         dev = self._engine.device
-        out = torch.empty((self.batch, self.out_channels, k), dtype=torch.float32, device=dev)
-        got = ctypes.c_int64(0)
 
-        def launch(stream: int) -> int:
-            if flush:
-                return self._lib.fv_logmel_stream_flush(self._h, out.data_ptr() if k else None, ctypes.byref(got), self._ws.data_ptr(),
-                                                        self._ws.numel() * 4, stream)
-            return self._lib.fv_logmel_stream_push(self._h, x.data_ptr() if c else None, max(c, 1), c, out.data_ptr() if k else None,
-                                                   ctypes.byref(got), self._ws.data_ptr(), self._ws.numel() * 4, stream)
-        self._engine._enqueue(dev, launch, owner=self, eager=True)
-        if got.value != k:
-            raise RuntimeError(f"log-mel stream emitted {got.value} frames where the framing rule says {k}")
+        def enqueue(optr, got) -> None:
+            def launch(stream: int) -> int:
+                ws = (self._ws.data_ptr(), self._ws.numel() * 4, stream)
+                return (self._lib.fv_logmel_stream_flush(self._h, optr, got, *ws) if flush else
+                        self._lib.fv_logmel_stream_push(self._h, x.data_ptr() if c else None, max(c, 1), c, optr, got, *ws))
+            self._engine._enqueue(dev, launch, owner=self, eager=True)
+        out = _emit((self.batch, self.out_channels, k), k, dev, enqueue,
+                    "log-mel stream emitted {got} frames where the framing rule says {k}")
         cn.flush() if flush else cn.push(c)
         return out
 

@@ -22,6 +22,7 @@ from __future__ import annotations
 import argparse
 import time
 import wave
+from contextlib import ExitStack
 from pathlib import Path
 
 import numpy as np
@@ -156,6 +157,44 @@ def build_model(generator="hifigan", resolution="44100_512_2048", overrides=None
     return model.eval().to(device)
 
 
+def _feed(push, x: torch.Tensor, limit: int) -> torch.Tensor:
+    """``x`` (..., n) through ``push`` in pieces of at most ``limit`` columns (a stage may emit more at once than the next one takes per push);
+    the pieces' outputs concatenated.  An empty ``x`` is pushed once, so that the result has the stage's output shape."""
+    outs = [push(x[..., i:i + limit]) for i in range(0, max(int(x.shape[-1]), 1), limit)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=-1)
+
+
+class _Stage:
+    """One stream of a cascade: its ``push`` and ``flush`` and the most columns one push takes.  ``audio``: the stream takes ``(B, c)`` and
+    gives ``(B, k)`` where the cascade carries ``(B, 1, c)`` (a resample stream behind a generator)."""
+
+    def __init__(self, stream, limit: int, audio: bool = False):
+        self.limit = int(limit)
+        self.push = (lambda y: stream.push(y[:, 0])[:, None]) if audio else stream.push
+        self.flush = (lambda: stream.flush()[:, None]) if audio else stream.flush
+
+
+class _Cascade:
+    """Streams in a row: what a stage emits goes into the next one as it comes, and what the last one emits goes to ``sink``."""
+
+    def __init__(self, stages: list, sink):
+        self.stages, self.sink = stages, sink
+
+    def feed(self, i: int, x: torch.Tensor) -> None:
+        """``x`` into stage ``i`` (``_feed``'s rule) and its output on to stage ``i + 1``; past the last stage, to the sink."""
+        if i == len(self.stages):
+            return self.sink(x)
+        self.feed(i + 1, _feed(self.stages[i].push, x, self.stages[i].limit))
+
+    def finish(self, inject=None) -> None:
+        """The flushes, first stage to last, each tail going through every later stage before that stage is flushed itself.
+        ``inject = (stage, x)``: ``x`` is fed to that stage just before its own flush."""
+        for i, st in enumerate(self.stages):
+            if inject is not None and inject[0] is st:
+                self.feed(i, inject[1])
+            self.feed(i + 1, st.flush())
+
+
 @torch.no_grad()
 def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int, resample: nn.Module | None = None):
     """Pushes ``mel`` (B, num_mels, T) through ``generator.stream()`` ``chunk_frames`` frames at a time, then flushes (exact mode: the lookahead
@@ -164,57 +203,30 @@ def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int,
     back at its ``new_freq``."""
     if not hasattr(generator, "stream"):
         raise ValueError(f"--chunk-frames: {type(generator).__name__} has no stream(); HiFiGAN / BigVGAN generators stream")
-    if resample is not None:
-        return _stream_synthesis_resampled(generator, mel, chunk_frames, resample)
     B, _, T = mel.shape
     outs, lat, first = [], [], None
     t0 = time.perf_counter()
-    with generator.stream(batch=B, max_chunk_frames=chunk_frames) as st:
+    with ExitStack() as stack:
+        st = stack.enter_context(generator.stream(batch=B, max_chunk_frames=chunk_frames))
+        stages = [_Stage(st, chunk_frames)]
+        if resample is not None:
+            if st.out_channels != 1:
+                raise ValueError(f"--output-rate: the generator emits {st.out_channels} channels; the resample stream takes waveforms (B, 1, T)")
+            limit = max(chunk_frames, st.lookahead_frames) * st.hop      # a push emits at most chunk_frames frames, the flush at most the lookahead
+            stages.append(_Stage(stack.enter_context(resample.stream(batch=B, max_chunk=limit)), limit, audio=True))
+        cascade = _Cascade(stages, outs.append)
         for f in range(0, T, chunk_frames):
             t1 = time.perf_counter()
-            y = st.push(mel[:, :, f:f + chunk_frames])
+            cascade.feed(0, mel[:, :, f:f + chunk_frames])      # (one piece per stage: one output per push)
             torch.cuda.synchronize()
             lat.append(time.perf_counter() - t1)
-            if first is None and y.shape[-1]:
+            if first is None and outs[-1].shape[-1]:
                 first = time.perf_counter() - t0
-            outs.append(y)
-        outs.append(st.flush())
+        cascade.finish()
         torch.cuda.synchronize()
         if first is None:
             first = time.perf_counter() - t0
     return torch.cat(outs, dim=-1), first, lat
-
-
-def _stream_synthesis_resampled(generator, mel, chunk_frames, resample):
-    B, _, T = mel.shape
-    outs, lat, first = [], [], None
-    t0 = time.perf_counter()
-    with generator.stream(batch=B, max_chunk_frames=chunk_frames) as st:
-        if st.out_channels != 1:
-            raise ValueError(f"--output-rate: the generator emits {st.out_channels} channels; the resample stream takes waveforms (B, 1, T)")
-        # a push emits at most chunk_frames frames, the flush at most the lookahead
-        with resample.stream(batch=B, max_chunk=max(chunk_frames, st.lookahead_frames) * st.hop) as rst:
-            for f in range(0, T, chunk_frames):
-                t1 = time.perf_counter()
-                y = rst.push(st.push(mel[:, :, f:f + chunk_frames])[:, 0])
-                torch.cuda.synchronize()
-                lat.append(time.perf_counter() - t1)
-                if first is None and y.shape[-1]:
-                    first = time.perf_counter() - t0
-                outs.append(y)
-            outs.append(rst.push(st.flush()[:, 0]))
-            outs.append(rst.flush())
-            torch.cuda.synchronize()
-            if first is None:
-                first = time.perf_counter() - t0
-    return torch.cat(outs, dim=-1)[:, None], first, lat
-
-
-def _feed(push, x: torch.Tensor, limit: int) -> torch.Tensor:
-    """``x`` (..., n) through ``push`` in pieces of at most ``limit`` columns (a stage may emit more at once than the next one takes per push);
-    the pieces' outputs concatenated.  An empty ``x`` is pushed once, so that the result has the stage's output shape."""
-    outs = [push(x[..., i:i + limit]) for i in range(0, max(int(x.shape[-1]), 1), limit)]
-    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=-1)
 
 
 def _pad_samples(hop: int, L: int) -> int:
@@ -257,44 +269,31 @@ def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chun
     if first is None:
         raise ValueError("stream_wav_synthesis: no input samples")
     B = int(first.shape[0])
-    from contextlib import ExitStack
     with ExitStack() as stack:
-        rin = stack.enter_context(to_model.stream(batch=B, max_chunk=limit)) if to_model is not None else None
-        mst = stack.enter_context(front.stream(batch=B, max_chunk_samples=limit))
+        stages = []
+        if to_model is not None:
+            stages.append(_Stage(stack.enter_context(to_model.stream(batch=B, max_chunk=limit)), limit))
+        mel_stage = _Stage(stack.enter_context(front.stream(batch=B, max_chunk_samples=limit)), limit)
         gst = stack.enter_context(gen.stream(batch=B, max_chunk_frames=chunk_frames))
         if gst.out_channels != 1:
             raise ValueError(f"the generator emits {gst.out_channels} channels; wav -> wav streaming takes waveforms (B, 1, T)")
-        rout = stack.enter_context(to_out.stream(batch=B, max_chunk=limit)) if to_out is not None else None
-
-        def from_audio(y):                          # generator output (B, 1, k) -> the sink
-            emit(y if rout is None else _feed(rout.push, y[:, 0], limit)[:, None])
-
-        def from_mel(m):                            # (B, num_mels, k)
-            from_audio(_feed(gst.push, m, chunk_frames))
-
-        def from_model_rate(x):                     # (B, c) at the model's rate
-            from_mel(_feed(mst.push, x, limit))
+        stages += [mel_stage, _Stage(gst, chunk_frames)]
+        if to_out is not None:
+            stages.append(_Stage(stack.enter_context(to_out.stream(batch=B, max_chunk=limit)), limit, audio=True))
+        cascade = _Cascade(stages, emit)
 
         def one(x):
             t1 = time.perf_counter()
             stats["reads"] += 1
-            x = x.to(model.device, torch.float32)
-            from_model_rate(x if rin is None else _feed(rin.push, x, limit))
+            cascade.feed(0, x.to(model.device, torch.float32))
             torch.cuda.synchronize()
             stats["push_s"].append(time.perf_counter() - t1)
 
         one(first)
         for x in chunks:
             one(x)
-        # the flushes cascade: each stage's tail goes through every later stage before that stage is flushed itself
-        if rin is not None:
-            from_model_rate(rin.flush())
-        if pad:
-            from_model_rate(torch.zeros((B, pad), dtype=torch.float32, device=model.device))
-        from_mel(mst.flush())
-        from_audio(gst.flush())
-        if rout is not None:
-            emit(rout.flush()[:, None])
+        # the zero padding of test.py:64-68 follows the input resampler's tail into the log-mel stream
+        cascade.finish((mel_stage, torch.zeros((B, pad), dtype=torch.float32, device=model.device)) if pad else None)
         torch.cuda.synchronize()
     if stats["first_audio_s"] is None:
         stats["first_audio_s"] = time.perf_counter() - t0

@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._handle import _DeviceHandles
 from ._lib import check
 from .resample import KAISER_BETA, _require_cuda, _rows
 
@@ -77,7 +78,7 @@ class PitchShift(nn.Module):
         self.orig_freq, self.o, self.n = plan(self.sample_rate, self.n_steps, self.bins_per_octave, self.freq_granularity)
         if self.n_fft < 2 or self.hop_length < 1 or self.n_fft % self.hop_length or self.n_fft % 2 or self.hop_length % 2:
             raise ValueError(f"n_fft ({self.n_fft}) must be a multiple of hop_length ({self.hop_length}) and both even")
-        self._handles: dict = {}     # device index -> fv_pitch_shift (its tables live on one device)
+        self._handles = _DeviceHandles("fv_pitch_shift_destroy")     # fv_pitch_shift: its tables live on one device
 
     def plan(self) -> tuple[int, int, int]:
         return self.orig_freq, self.o, self.n
@@ -91,15 +92,7 @@ class PitchShift(nn.Module):
                                      self.lowpass_filter_width, self.rolloff, int(method), KAISER_BETA if self.beta is None else float(self.beta))
 
     def _handle(self, device: torch.device) -> ctypes.c_void_p:
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        h = self._handles.get(idx)
-        if h is None:
-            h = ctypes.c_void_p()
-            cfg = self.config()
-            with torch.cuda.device(idx):
-                check(_lib.lib().fv_pitch_shift_create(ctypes.byref(cfg), ctypes.byref(h)))
-            self._handles[idx] = h
-        return h
+        return self._handles.get(device, lambda h: _lib.lib().fv_pitch_shift_create(ctypes.byref(self.config()), h))
 
     def _run(self, wave: torch.Tensor, whole: bool, what: str) -> torch.Tensor:
         _require_cuda(wave, what)
@@ -129,15 +122,7 @@ class PitchShift(nn.Module):
         return self._run(wave, False, "PitchShift.time_stretch")
 
     def close(self) -> None:
-        for h in self._handles.values():
-            _lib.lib().fv_pitch_shift_destroy(h)
-        self._handles = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._handles.close()
 
     def extra_repr(self) -> str:
         return (f"{self.sample_rate} Hz, n_steps={self.n_steps}, orig_freq={self.orig_freq} (rate {self.n}/{self.o}), n_fft={self.n_fft}, "

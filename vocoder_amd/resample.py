@@ -30,7 +30,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import FishVocError, check
+from ._handle import _DeviceHandles, _Handle, _emit, _require_cuda as _require
+from ._lib import check
 
 KAISER_BETA = 14.769656459379492
 
@@ -149,10 +150,7 @@ def _config(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_metho
 
 
 def _require_cuda(t: torch.Tensor, what: str) -> None:
-    if not t.is_cuda:
-        raise ValueError(f"{what}: expected a CUDA (HIP) tensor, got device {t.device}; vocoder_amd has no CPU fallback")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{what}: expected float32, got {t.dtype}")
+    _require(t, what, ValueError, ValueError)
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
@@ -186,7 +184,7 @@ class Resample(nn.Module):
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
         self.resampling_method, self.lowpass_filter_width, self.rolloff, self.beta = resampling_method, int(lowpass_filter_width), rolloff, beta
         self.design = design(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
-        self._handles: dict = {}     # device index -> fv_resample (the table lives on one device)
+        self._handles = _DeviceHandles("fv_resample_destroy")     # fv_resample: the table lives on one device
 
     def output_length(self, L: int) -> int:
         return self.design.output_length(L)
@@ -198,16 +196,10 @@ class Resample(nn.Module):
         return self.design.first_input(m)
 
     def _handle(self, device: torch.device) -> ctypes.c_void_p:
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        h = self._handles.get(idx)
-        if h is None:
-            h = ctypes.c_void_p()
+        def create(h) -> int:
             cfg = _config(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
-            with torch.cuda.device(idx):
-                create = _lib.lib().fv_global_resample_create if self.table == "global" else _lib.lib().fv_resample_create
-                check(create(ctypes.byref(cfg), ctypes.byref(h)))
-            self._handles[idx] = h
-        return h
+            return getattr(_lib.lib(), "fv_global_resample_create" if self.table == "global" else "fv_resample_create")(ctypes.byref(cfg), h)
+        return self._handles.get(device, create)
 
     def forward(self, waveform: torch.Tensor, lengths=None) -> torch.Tensor:
         _require_cuda(waveform, "Resample.forward")
@@ -242,25 +234,19 @@ class Resample(nn.Module):
         return ResampleStream(self, batch, max_chunk)
 
     def close(self) -> None:
-        for h in self._handles.values():
-            _lib.lib().fv_resample_destroy(h)
-        self._handles = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._handles.close()
 
     def extra_repr(self) -> str:
         return (f"{self.orig_freq} -> {self.new_freq} Hz, {self.resampling_method}, lowpass_filter_width={self.lowpass_filter_width}, "
                 f"rolloff={self.rolloff}, phases={self.design.n}, taps={self.design.kp}")
 
 
-class ResampleStream:
+class ResampleStream(_Handle):
     """``batch`` rows resampled chunk by chunk, in lockstep (``fv_resample_stream``): ``push`` a ``(batch, c)`` chunk, ``c <= max_chunk``, and get
     the ``(batch, k)`` outputs whose bands have arrived (``k`` may be 0); ``flush`` emits the rest against zeros; ``reset`` starts the next
     utterance; ``close`` frees the stream (also a context manager).  Work is enqueued on torch's current stream; calls must be ordered."""
+    _destroy = "fv_resample_stream_destroy"
+    _closed = "this resample stream is closed: create a new one"
 
     def __init__(self, resample: Resample, batch: int, max_chunk: int, device=None):
         self._resample, self._lib = resample, _lib.lib()
@@ -288,10 +274,6 @@ class ResampleStream:
         self._check_open()
         return int(self._lib.fv_resample_stream_pending(self._h))
 
-    def _check_open(self) -> None:
-        if not self._h.value:
-            raise FishVocError(_lib.FV_ERR_STATE, "this resample stream is closed: create a new one")
-
     def push(self, chunk: torch.Tensor) -> torch.Tensor:
         self._check_open()
         _require_cuda(chunk, "ResampleStream.push")
@@ -308,18 +290,16 @@ class ResampleStream:
         ok = flush or c <= self.max_chunk                   # a refused push emits nothing; the library says why
         E2 = self.design.output_length(N2) if flush else max(self._E, self.design.emit_count(N2))
         k = E2 - self._E if ok and not self._flushed else 0
-        out = torch.empty((self.batch, k), dtype=torch.float32, device=self.device)
-        got = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            s = int(torch.cuda.current_stream().cuda_stream)
-            if flush:
-                st = self._lib.fv_resample_stream_flush(self._h, out.data_ptr() if k else None, max(k, 1), ctypes.byref(got), s)
-            else:
-                st = self._lib.fv_resample_stream_push(self._h, x.data_ptr(), x.stride(0) if self.batch > 1 else max(c, 1), c,
-                                                       out.data_ptr() if k else None, max(k, 1), ctypes.byref(got), s)
-        check(st)
-        if got.value != k:
-            raise RuntimeError(f"resample stream emitted {got.value} samples where the emission rule says {k}")
+
+        def enqueue(optr, got) -> None:
+            with torch.cuda.device(self.device):
+                run = torch.cuda.current_stream()
+                s = int(run.cuda_stream)
+                check(self._lib.fv_resample_stream_flush(self._h, optr, max(k, 1), got, s) if flush else
+                      self._lib.fv_resample_stream_push(self._h, x.data_ptr(), x.stride(0) if self.batch > 1 else max(c, 1), c, optr,
+                                                        max(k, 1), got, s))
+                self._record_done(run)      # the carried buffers are in use on the device until then
+        out = _emit((self.batch, k), k, self.device, enqueue, "resample stream emitted {got} samples where the emission rule says {k}")
         self._N, self._E = N2, E2
         self._flushed = flush
         return out
@@ -329,21 +309,3 @@ class ResampleStream:
         check(self._lib.fv_resample_stream_reset(self._h))
         self._N = self._E = 0
         self._flushed = False
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            torch.cuda.synchronize(self.device)       # the carried buffers may still be in use on the device
-            self._lib.fv_resample_stream_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self) -> "ResampleStream":
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
