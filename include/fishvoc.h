@@ -691,6 +691,37 @@ FV_API fv_status fv_pitch_shift_stretch(fv_pitch_shift* p, const float* d_x, int
 FV_API fv_status fv_pitch_shift_forward(fv_pitch_shift* p, const float* d_x, int64_t x_row_stride, float* d_y, int64_t y_row_stride,
                                         int32_t batch, int64_t L, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* -------- scoring generated audio: the distances eval.py and the STFT loss compute between a source and a generated waveform, as metrics.
+ *          eval.py:29-33's spec_diff is mean |LogMelSpectrogram(target) - LogMelSpectrogram(preds)|; stft.py:55 is the spectral convergence
+ *          ||y_mag - x_mag||_F / ||y_mag||_F and stft.py:74 the log-magnitude L1, mean |log y_mag - log x_mag|.  All three are ratios of the
+ *          four sums below, taken per row over the valid columns of two spectrogram tensors.  eval.py's PESQ is not built (a standardised CPU
+ *          algorithm).  Deviation for the STFT formulas: the callers feed this project's LinearSpectrogram magnitudes
+ *          (win_length = n_fft, center=False, sqrt(re^2 + im^2 + 1e-6)), not stft.py:24-36's torch.stft(center=True, win_length < n_fft)
+ *          with a clamp: the front-end config, frozen at ABI 5, has neither.  No gradients: a metric, not a loss. -------- */
+#define FV_SPEC_DISTANCE_LOG 1 /* fv_spec_distance flags: also form S_log (positive magnitudes; leave it off for log-mels, which may be negative) */
+
+/* Columns per tile of the reduction (eval.py:29-33 / stft.py:55,74 reduce whole tensors with torch.mean / torch.norm): a row's sums are its
+ * tiles' partial sums added in tile order.  Exported for the tests' shapes, as fv_resample_input_tile is. */
+FV_API int32_t fv_spec_distance_tile(void);
+/* Bytes of device scratch fv_spec_distance needs for `batch` rows of T columns (the tiles' partial sums; eval.py:29-33 / stft.py:55,74
+ * allocate theirs per call): 256-byte aligned, non-decreasing in both arguments, 0 for an empty or negative one. */
+FV_API size_t fv_spec_distance_workspace_bytes(int32_t batch, int64_t T);
+/* The sums behind eval.py:29-33 (spec_diff = S_l1 / count), stft.py:55 (sqrt(S_sq) / sqrt(S_ref)) and stft.py:74 (S_log / count) for rows of
+ * different lengths in one call.  d_est / d_ref: fp32 (batch, channels, T); element (b, c, t) at b * row_stride + c * ld + t floats in both,
+ * ld >= T, row_stride >= channels * ld — none of them, nor the base pointers, need be a multiple of 4 floats (a view x[:, :, 1:] is fine).
+ * host_frames[b] <= T: the valid columns of row b.  d_out: (batch, 4) doubles per row,
+ *   S_l1 = sum |est - ref|, S_sq = sum (est - ref)^2, S_ref = sum ref^2, S_log = sum |log ref - log est|     over c < channels, t < frames[b];
+ * S_log only with FV_SPEC_DISTANCE_LOG in flags, otherwise exactly 0.0.  Every term is formed in fp32 with one rounding per operation
+ * (d = est - ref, |d|, d * d, ref * ref, logf(ref) - logf(est); no clamp: non-positive inputs give what torch.log gives), widened to double
+ * and accumulated in fp64 in a fixed order: no float atomics.  A row's four doubles are therefore bit-identical whether it is scored alone,
+ * inside any batch, at any T >= frames[b], at any strides, and on every run.  Columns at or past frames[b] (NaN included) are never loaded;
+ * a row with frames[b] = 0 gives four zeros.  count = channels * frames[b] is the caller's division (0 / 0 = NaN for an empty row).
+ * Everything is validated before any device call: a null pointer, channels < 1, ld < T, row_stride < channels * ld, a frame count below 0 or
+ * above T (the row is named), too little workspace -> FV_ERR_INVALID.  batch = 0 is a no-op.  Asynchronous on `stream`; never synchronises. */
+FV_API fv_status fv_spec_distance(const float* d_est, const float* d_ref, int64_t row_stride, int64_t ld, int32_t channels, int64_t T,
+                                  const int32_t* host_frames, int32_t batch, int32_t flags, double* d_out, void* d_workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* -------- single fused conv layer (the hot kernel on its own; used by the parity tests and the roofline
  *          bench).  Stands in for one weight-normed nn.Conv1d / nn.ConvTranspose1d call plus the elementwise
  *          ops the reference runs around it (F.silu before, residual add after: hifigan.py:101-108). -------- */

@@ -8,6 +8,8 @@ Public surface (mirrors /root/reference/fish_vocoder for the generator hot path 
 * ``vocoder_amd.config`` — loads the reference's ``configs/model/generator/*.yaml`` keys and instantiates ``_target_``;
 * ``vocoder_amd.engine`` — thin handle on the C ABI (``include/fishvoc.h``, ``csrc/libfishvoc_hip.so``);
 * ``vocoder_amd.resample`` — ``Resample``, the GPU drop-in for ``torchaudio.transforms.Resample`` (whole rows, ragged rows, streaming);
+* ``vocoder_amd.scoring`` — ``MelDistance`` / ``MultiResolutionSTFTDistance``, the reference's ``eval.py`` mel distance and the STFT loss's two
+  formulas as GPU metrics; ``python -m vocoder_amd.eval SOURCE GENERATED`` scores a directory;
 * ``vocoder_amd.sharding`` — utterance-batch sharding helpers for one process per GPU.
 
 The compute path is hand-written HIP only; importing works on a CPU-only box (for config/host logic), running does not.

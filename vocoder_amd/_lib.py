@@ -31,6 +31,7 @@ FV_ISTFT_SAME, FV_ISTFT_CENTER = 0, 1
 FV_ACT_NONE, FV_ACT_SILU, FV_ACT_LEAKY_RELU, FV_ACT_GELU, FV_ACT_TANH, FV_ACT_LOG_CLAMP = 0, 1, 2, 3, 4, 5
 FV_RESAMPLE_SINC_HANN, FV_RESAMPLE_SINC_KAISER = 0, 1
 RESAMPLE_METHODS = {"sinc_interp_hann": FV_RESAMPLE_SINC_HANN, "sinc_interp_kaiser": FV_RESAMPLE_SINC_KAISER}
+FV_SPEC_DISTANCE_LOG = 1     # fv_spec_distance flags: also form S_log = sum |log ref - log est|
 FV_POST_ACT_DEFAULT, FV_POST_ACT_IDENTITY = 0, -1   # fv_upsampler_config.post_activation (ABI 5): 0 = reference default SiLU, -1 = nn.Identity
 
 EXPORTS = (
@@ -53,6 +54,7 @@ EXPORTS = (
     "fv_global_resample_create",
     "fv_pitch_shift_plan", "fv_pitch_shift_lengths", "fv_pitch_shift_create", "fv_pitch_shift_destroy", "fv_pitch_shift_workspace_bytes",
     "fv_pitch_shift_stretch", "fv_pitch_shift_forward",
+    "fv_spec_distance_tile", "fv_spec_distance_workspace_bytes", "fv_spec_distance",
 )
 
 _i32 = ctypes.c_int32
@@ -328,6 +330,12 @@ def lib() -> ctypes.CDLL:
     L.fv_pitch_shift_stretch.restype = _i32
     L.fv_pitch_shift_forward.argtypes = [vp, vp, i64, vp, i64, _i32, i64, vp, ctypes.c_size_t, vp]
     L.fv_pitch_shift_forward.restype = _i32
+    L.fv_spec_distance_tile.argtypes = []
+    L.fv_spec_distance_tile.restype = _i32
+    L.fv_spec_distance_workspace_bytes.argtypes = [_i32, i64]
+    L.fv_spec_distance_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_spec_distance.argtypes = [vp, vp, i64, i64, _i32, i64, i32p, _i32, _i32, vp, vp, ctypes.c_size_t, vp]
+    L.fv_spec_distance.restype = _i32
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp
@@ -358,6 +366,11 @@ def reload_env() -> None:
 def resample_input_tile() -> int:
     """Input samples of the resampler kernel's tile (fv_resample_input_tile): the tests size their rows from it."""
     return int(lib().fv_resample_input_tile())
+
+
+def spec_distance_tile() -> int:
+    """Columns per tile of the scoring reduction (fv_spec_distance_tile): the tests size their rows from it."""
+    return int(lib().fv_spec_distance_tile())
 
 
 def last_kernel() -> str:
