@@ -1,6 +1,6 @@
-"""float64 references and the per-output error bound for the direct-sum conv kernel (conv_mfma_impl.h): shared by the GPU instance tests
-(test_gpu_conv_instances.py) and the CPU test that shows the bound catches subtly wrong kernels (test_conv_checker.py).  CPU only: numpy and
-torch.nn.functional in float64."""
+"""float64 references and the per-output error bounds for the direct-sum conv kernel (conv_mfma_impl.h) and the fused ResBlock (c1, c2) pair
+kernels (conv_pair.hip): shared by the GPU instance tests (test_gpu_conv_instances.py, test_gpu_pair_instances.py) and the CPU tests that show
+the bounds catch subtly wrong kernels (test_conv_checker.py, test_pair_checker.py).  CPU only: numpy and torch.nn.functional in float64."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -178,3 +178,116 @@ def conv_transpose1d_loops(x, w, b, stride, padding):
                         if 0 <= t < To:
                             y[bi, o, t] += float(w[c, o, j]) * float(x[bi, c, q])
     return y
+
+
+# ---- the fused ResBlock pair  y = x + c2(silu(c1(silu(x))))  (conv_pair.hip) ------------------------------------------------------------------
+# The pair's bound is the single layer's, composed:  e1 = b(A1, K) for the intermediate h, e = b(A2, K) + SILU_SLOPE * conv(e1, |w2|) for the
+# output (|silu'| <= 1.0998; silu's own rounding is inside A_BOUND).  b() per kernel family of conv_pair_run:
+#   direct  (resblock_pair)            b = bound(A, K): the constants above, unchanged
+#   f16x3   (pair_f16x3, both kernels) b = bound(A, K) + C_F16 * 2^-22 * A + 2^-25 * sum|w| + 2^-38 * max|w| * sum|a|.  Both operands are split
+#           into two fp16 planes and the lo * lo product is dropped: every product carries a systematic relative error of order 2^-22; the
+#           activation's low plane bottoms out at fp16's subnormal spacing (2^-25 absolute per activation, times the row's sum|w|), the weight's
+#           — scaled so that max|w| s lies in [2^13, 2^14), conv_pack.hip — at 2^-25 / s <= 2^-38 max|w| per weight, times the window's sum|a|
+#   wino23 / wino44 (pair_wino, pair_wino44)  b = M_WINO * U * (sqrt(K) + A_BOUND) * A_W: the transforms mix neighbouring samples of a channel
+#           and the taps of one (o, i), so A_W[o, t] = sum_i (sum_j |w[o, i, j]|) max_{|t' - t| <= r} |a[i, t']| + |b| + |res| takes A's place,
+#           r = the kernel's tile span (2 d for F(2,3), 4 d for F(4,4)) + (k - 1) d / 2.  A_W >= A, and it is still per output channel.
+# The three multipliers cannot be derived: each is twice the largest value measured on an MI355X against the float64 reference over every
+# instance of its family (test_gpu_pair_instances.py, all its lengths, batch sizes and alignments; heavy-tailed weights, unequal channels) —
+# the margin C_BOUND has over its 0.55.  The measured unit is |y - ref| over the bound's multiplied part with the multiplier at 1 (f16x3: over
+# the composed 2^-22 A term alone, so the fp32 term b(A, K) and the floors stay on top of the doubled measurement).  Measured (PAIR_MEASURED;
+# profiles/r20_pair_instances.txt): direct 0.235 of its bound (C_BOUND = 1, A_BOUND = 8 unchanged: 4 x of margin); f16x3 0.837 on the wide
+# kernels, 0.610 on the C = 16 layout -> C_F16 = 1.7; F(2,3) 0.316 -> M_WINO23 = 0.64; F(4,4) 0.325 -> M_WINO44 = 0.65 (below 1: A_W counts
+# every tap at the neighbourhood's largest activation).  Never calibrated against another kernel of the project.
+SILU_SLOPE = 1.1
+PAIR_MEASURED = {"direct": 0.235, "f16x3": 0.837, "wino23": 0.316, "wino44": 0.325}   # largest ratio measured on an MI355X, multiplier at 1
+C_F16 = 1.7
+M_WINO23 = 0.64
+M_WINO44 = 0.65
+PAIR_FAMILIES = ("direct", "f16x3", "wino23", "wino44")
+
+
+def _pair_layers(x, w1, b1, w2, b2, k, d):
+    g1 = dict(transposed=False, padding=(k - 1) * d // 2, dilation=d)
+    g2 = dict(transposed=False, padding=(k - 1) // 2, dilation=1)
+    h, _, A1 = layer_ref(x, w1, b1, g1, pre="silu")
+    ref, _, A2 = layer_ref(h, w2, b2, g2, pre="silu", res=np.asarray(x, dtype=np.float64))
+    return ref, h, A1, A2, int(np.asarray(w1).shape[1]) * k
+
+
+def pair_ref(x, w1, b1, w2, b2, k, d):
+    """(ref, A1, A2, K) of y = x + c2(silu(c1(silu x) + b1)) + b2 in float64, from layer_ref: A1 / A2 the absolute-value convs of the two layers
+    (A2 with the residual |x|), K = C k the terms of either sum."""
+    ref, _, A1, A2, K = _pair_layers(x, w1, b1, w2, b2, k, d)
+    return ref, A1, A2, K
+
+
+def _window_max(a, r):
+    """max over |t' - t| <= r of a[..., t'] (a >= 0; positions outside the row count as 0)."""
+    if r == 0:
+        return a
+    return F.max_pool1d(F.pad(torch.from_numpy(np.ascontiguousarray(a)), (r, r)), kernel_size=2 * r + 1, stride=1).numpy()
+
+
+def wino_A(a, w, b, r, res=None):
+    """A_W of one layer on the activated input a (see above)."""
+    w1 = np.abs(np.asarray(w, dtype=np.float64)).sum(axis=2)            # (O, I)
+    A = np.einsum("oi,bit->bot", w1, _window_max(np.abs(np.asarray(a, dtype=np.float64)), r))
+    if b is not None:
+        A = A + np.abs(np.asarray(b, dtype=np.float64))[None, :, None]
+    if res is not None:
+        A = A + np.abs(np.asarray(res, dtype=np.float64))
+    return A
+
+
+def pair_bound_parts(family, x, w1, b1, w2, b2, k, d):
+    """(ref, fixed, unit): the float64 output, and the family's per-output bound as fixed + multiplier * unit (direct: no multiplier, unit =
+    fixed = the bound)."""
+    x64 = np.asarray(x, dtype=np.float64)
+    ref, h, A1, A2, K = _pair_layers(x, w1, b1, w2, b2, k, d)
+    aw1, aw2 = np.abs(np.asarray(w1, dtype=np.float64)), np.abs(np.asarray(w2, dtype=np.float64))
+    pad1, pad2 = (k - 1) * d // 2, (k - 1) // 2
+    scale = C_BOUND * U * (np.sqrt(K) + A_BOUND)      # bound(A, K) = scale * A
+
+    def through_c2(e1):
+        return SILU_SLOPE * conv64(e1, aw2, padding=pad2)
+
+    if family in ("direct", "f16x3"):
+        A12 = A2 + through_c2(A1)                     # the composition is linear in (A1, A2)
+        if family == "direct":
+            return ref, scale * A12, scale * A12
+        ones = np.ones((1,) + aw1.shape[1:])
+        f1 = 2.0 ** -25 * aw1.sum(axis=(1, 2))[None, :, None] + 2.0 ** -38 * aw1.max() * conv64(np.abs(act64(x64, "silu")), ones, padding=pad1, dilation=d)
+        f2 = 2.0 ** -25 * aw2.sum(axis=(1, 2))[None, :, None] + 2.0 ** -38 * aw2.max() * conv64(np.abs(act64(h, "silu")), ones, padding=pad2)
+        return ref, scale * A12 + f2 + through_c2(f1), 2.0 ** -22 * A12
+    span = {"wino23": 2, "wino44": 4}[family]
+    AW1 = wino_A(act64(x64, "silu"), w1, b1, span * d + pad1)
+    AW2 = wino_A(act64(h, "silu"), w2, b2, span + pad2, res=x64)
+    return ref, np.zeros_like(ref), U * (np.sqrt(K) + A_BOUND) * (AW2 + through_c2(AW1))
+
+
+def pair_multiplier(family):
+    return {"direct": 0.0, "f16x3": C_F16, "wino23": M_WINO23, "wino44": M_WINO44}[family]
+
+
+def pair_bound(family, x, w1, b1, w2, b2, k, d):
+    """The per-output bound of the family's pair kernel."""
+    _, fixed, unit = pair_bound_parts(family, x, w1, b1, w2, b2, k, d)
+    return fixed + pair_multiplier(family) * unit
+
+
+def pair_ratio(y, ref, unit):
+    """max |y - ref| / unit: what the family multipliers were measured in (direct: <= 1 passes)."""
+    return float((np.abs(np.asarray(y, dtype=np.float64) - ref) / unit).max())
+
+
+def check_pair_per_output(y, ref, bnd, what=""):
+    """Every output finite and within its bound."""
+    y64 = np.asarray(y, dtype=np.float64)
+    assert y64.shape == ref.shape, (what, y64.shape, ref.shape)
+    assert np.isfinite(y64).all(), f"{what}: non-finite outputs"
+    err = np.abs(y64 - ref)
+    bad = err > bnd
+    if bad.any():
+        i = np.unravel_index(int(np.argmax(err / bnd)), err.shape)
+        raise AssertionError(f"{what}: {int(bad.sum())} outputs past the per-output bound; worst at {tuple(int(v) for v in i)}: "
+                             f"|d| = {err[i]:.3e}, bound {bnd[i]:.3e} ({err[i] / bnd[i]:.2f} x), ref {ref[i]:.6e}")

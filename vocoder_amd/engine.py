@@ -874,12 +874,21 @@ class FusedConv(_Handle):
                                             _stream_ptr(x.device)))
         return out
 
-    def pair(self, c2: "FusedConv", x: torch.Tensor) -> torch.Tensor:
-        """One ResBlock1 iteration in a single launch: x + c2(silu(self(silu(x)))) (fv_conv_pair_forward)."""
+    def pair(self, c2: "FusedConv", x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """One ResBlock1 iteration in a single launch: x + c2(silu(self(silu(x)))) (fv_conv_pair_forward).  `out`: a contiguous float32
+        tensor of x's shape on x's device to write into; it must not overlap x (workgroups read their neighbours' halo)."""
         _require_cuda(x, "FusedConv.pair")
         x = x.contiguous()
         B, C, T = x.shape
-        out = torch.empty_like(x)
+        if out is None:
+            out = torch.empty_like(x)
+        else:
+            _require_cuda(out, "FusedConv.pair out")
+            if out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(x.shape)} on {x.device}")
+            nbytes = 4 * x.numel()
+            if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
+                raise ValueError("FusedConv.pair: out must not alias x (halo reads)")
         with torch.cuda.device(x.device):
             check(self._lib.fv_conv_pair_forward(self._h, c2._h, x.data_ptr(), out.data_ptr(), B, T,
                                                  _stream_ptr(x.device)))
