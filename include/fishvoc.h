@@ -691,6 +691,83 @@ FV_API fv_status fv_pitch_shift_stretch(fv_pitch_shift* p, const float* d_x, int
 FV_API fv_status fv_pitch_shift_forward(fv_pitch_shift* p, const float* d_x, int64_t x_row_stride, float* d_y, int64_t y_row_stride,
                                         int32_t batch, int64_t L, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* -------- pitch template: the `template (B, 1, T * hop)` that refinegan.py:287 / hifigan.py:226 take next to the mel.  The reference does not
+ *          make one: its users bring an F0 track from a CPU tracker (pyworld, parselmouth, librosa.yin) and synthesise the template from it.
+ *          Both steps are here: a YIN tracker and an exact-phase oscillator driven by its F0.  --------
+ *
+ * Plan (integers): tau_max = sr / fmin, tau_min = max(2, sr / fmax) (floors), Wi = W - (tau_max + 1) the integration window, the same for
+ * every lag; T = L / hop frames, one per mel frame.
+ * Framing: frame t is centred on sample c = t hop + hop / 2 (the centre of mel frame t under the log-mel front-end's framing) and covers
+ * [c - W / 2, c + W / 2); samples before 0 or at or past the row's length are zeros and are never loaded (a ragged row's padding may hold NaN).
+ * Difference function, direct form: d(tau) = sum_{j < Wi} (x[j] - x[j + tau])^2 for tau = 1 ... tau_max + 1, one fp32 accumulator over
+ * ascending j (not E(0) + E(tau) - 2 r(tau): that cancels where d is small, the voiced case).
+ * Normalisation: d'(tau) = d(tau) tau / sum_{k <= tau} d(k); 1 where the running sum is 0 (silence stays finite and unvoiced).
+ * Decision: the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, d'(tau) <= d'(tau - 1) and d'(tau) < d'(tau + 1): voiced,
+ * delta = (a - c) / (2 (a - 2 b + c)) on d'(tau - 1, tau, tau + 1) (0 when the denominator is <= 0), f0 = sr / (tau + delta),
+ * aperiodicity = d'(tau).  None: unvoiced, f0 = 0, aperiodicity = min d' over the range.
+ * Template: F_t = rint(f0_t / sr * 2^32) in double, held as uint32, 0 (unvoiced) unless 0 < f0_t < sr.  Sample n lies between the frame
+ * centres a = floor((n - hop / 2) / hop) and a + 1, both clamped to the row's frames, k in [0, hop) samples past centre a:
+ * inc[n] = (F_a (hop - k) + F_b k) / hop in 64-bit integers, an unvoiced neighbour taking the other one's value; the phase
+ * phi[n] = sum_{m <= n} inc[m] mod 2^32 is an integer prefix sum, exact in any order (an fp32 accumulator drifts audibly within seconds).
+ * Output amplitude sin(2 pi phi / 2^32) or amplitude (2 phi / 2^32 - 1), exactly 0 where frame n / hop is unvoiced.
+ * Not built: a streaming form (it would carry phi and a lookahead of W / 2 samples), pYIN / Viterbi smoothing, octave-error correction. */
+typedef struct fv_f0_config {
+    int32_t sample_rate;   /* the model's rate: the tracker runs on the samples the mel is made from */
+    int32_t frame_length;  /* W, even; 2048 */
+    int32_t hop_length;    /* the model's hop: one F0 value per mel frame */
+    double fmin;           /* 40 Hz */
+    double fmax;           /* 1100 Hz */
+    double threshold;      /* in (0, 1]; 0.1 */
+} fv_f0_config;
+
+typedef enum fv_template_kind { FV_TEMPLATE_SINE = 0, FV_TEMPLATE_SAWTOOTH = 1 } fv_template_kind;
+
+typedef struct fv_template_config {
+    int32_t sample_rate;
+    int32_t hop_length;
+    int32_t kind;      /* fv_template_kind */
+    float amplitude;   /* 1.0 */
+} fv_template_config;
+
+/* Pure host (no GPU): the plan of the tracker that stands in for the CPU F0 tracker in front of refinegan.py:287 / hifigan.py:226, and the
+ * frames of a row of L samples.  NULL outputs are skipped.  FV_ERR_INVALID says which knob to move: tau_min >= tau_max (fmin, fmax),
+ * Wi < tau_max / 2 (frame_length or fmin), an odd frame_length, hop_length < 1, threshold outside (0, 1]. */
+FV_API fv_status fv_f0_plan(const fv_f0_config* cfg, int64_t L, int32_t* tau_min, int32_t* tau_max, int32_t* window, int64_t* frames);
+
+typedef struct fv_f0 fv_f0;
+typedef struct fv_template fv_template;
+
+/* The tracker (replaces the CPU F0 tracker a user of refinegan.py:287 / hifigan.py:226 runs today).  FV_ERR_UNSUPPORTED for a frame_length
+ * above 4096: one workgroup stages the frame in LDS. */
+FV_API fv_status fv_f0_create(const fv_f0_config* cfg, fv_f0** out);
+FV_API void fv_f0_destroy(fv_f0* p);
+/* Bytes of device scratch fv_f0_forward needs (the CPU trackers in front of refinegan.py:287 / hifigan.py:226 allocate per call): 0 today,
+ * every frame lives in its workgroup's LDS; callers pass what this returns. */
+FV_API size_t fv_f0_workspace_bytes(const fv_f0* p, int32_t batch, int64_t L);
+/* F0 and aperiodicity per mel frame, the input of fv_template_forward (refinegan.py:287 / hifigan.py:226 take its output).  d_x: `batch` rows
+ * of L samples, row b at d_x + b * x_row_stride; host_lengths (NULL: every row has L): row b holds host_lengths[b] <= L samples, the rest is
+ * never loaded.  d_f0 / d_aperiodicity: `batch` rows of T = L / hop values, row b at + b * out_row_stride; frames at or past
+ * host_lengths[b] / hop are exact zeros in both.  A row's values are bit-identical alone, in any batch and at any L.  Everything is validated
+ * before anything is enqueued.  Asynchronous on `stream`. */
+FV_API fv_status fv_f0_forward(fv_f0* p, const float* d_x, int64_t x_row_stride, const int32_t* host_lengths, float* d_f0,
+                               float* d_aperiodicity, int64_t out_row_stride, int32_t batch, int64_t L, void* d_workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* The synthesiser of the template refinegan.py:287 / hifigan.py:226 take (replaces the CPU oscillator their users write).  FV_ERR_INVALID
+ * names the field. */
+FV_API fv_status fv_template_create(const fv_template_config* cfg, fv_template** out);
+FV_API void fv_template_destroy(fv_template* p);
+/* Bytes of device scratch fv_template_forward needs for `batch` rows of T frames (F and the chunk sums; a CPU oscillator in front of
+ * refinegan.py:287 / hifigan.py:226 allocates per call); 0 for a bad argument. */
+FV_API size_t fv_template_workspace_bytes(const fv_template* p, int32_t batch, int64_t T);
+/* The template of refinegan.py:287 / hifigan.py:226 from frame-level F0.  d_f0: `batch` rows of T values in Hz (0, negative, NaN or >= sr:
+ * unvoiced), row b at d_f0 + b * f0_row_stride; host_frames (NULL: every row has T): row b holds host_frames[b] <= T frames, the rest is
+ * never loaded.  d_out: `batch` rows of T * hop samples, row b at d_out + b * out_row_stride, exact zeros from host_frames[b] * hop on.  A
+ * row's samples are bit-identical alone, in any batch and at any T.  T * hop <= 2^30.  Asynchronous on `stream`. */
+FV_API fv_status fv_template_forward(fv_template* p, const float* d_f0, int64_t f0_row_stride, const int32_t* host_frames, float* d_out,
+                                     int64_t out_row_stride, int32_t batch, int64_t T, void* d_workspace, size_t workspace_bytes,
+                                     void* stream);
+
 /* -------- scoring generated audio: the distances eval.py and the STFT loss compute between a source and a generated waveform, as metrics.
  *          eval.py:29-33's spec_diff is mean |LogMelSpectrogram(target) - LogMelSpectrogram(preds)|; stft.py:55 is the spectral convergence
  *          ||y_mag - x_mag||_F / ||y_mag||_F and stft.py:74 the log-magnitude L1, mean |log y_mag - log x_mag|.  All three are ratios of the

@@ -32,6 +32,8 @@ FV_ACT_NONE, FV_ACT_SILU, FV_ACT_LEAKY_RELU, FV_ACT_GELU, FV_ACT_TANH, FV_ACT_LO
 FV_RESAMPLE_SINC_HANN, FV_RESAMPLE_SINC_KAISER = 0, 1
 RESAMPLE_METHODS = {"sinc_interp_hann": FV_RESAMPLE_SINC_HANN, "sinc_interp_kaiser": FV_RESAMPLE_SINC_KAISER}
 FV_SPEC_DISTANCE_LOG = 1     # fv_spec_distance flags: also form S_log = sum |log ref - log est|
+FV_TEMPLATE_SINE, FV_TEMPLATE_SAWTOOTH = 0, 1
+TEMPLATE_KINDS = {"sine": FV_TEMPLATE_SINE, "sawtooth": FV_TEMPLATE_SAWTOOTH}
 FV_POST_ACT_DEFAULT, FV_POST_ACT_IDENTITY = 0, -1   # fv_upsampler_config.post_activation (ABI 5): 0 = reference default SiLU, -1 = nn.Identity
 
 EXPORTS = (
@@ -55,6 +57,8 @@ EXPORTS = (
     "fv_pitch_shift_plan", "fv_pitch_shift_lengths", "fv_pitch_shift_create", "fv_pitch_shift_destroy", "fv_pitch_shift_workspace_bytes",
     "fv_pitch_shift_stretch", "fv_pitch_shift_forward",
     "fv_spec_distance_tile", "fv_spec_distance_workspace_bytes", "fv_spec_distance",
+    "fv_f0_plan", "fv_f0_create", "fv_f0_destroy", "fv_f0_workspace_bytes", "fv_f0_forward",
+    "fv_template_create", "fv_template_destroy", "fv_template_workspace_bytes", "fv_template_forward",
 )
 
 _i32 = ctypes.c_int32
@@ -133,6 +137,15 @@ class PitchShiftConfig(ctypes.Structure):
     _fields_ = [("sample_rate", _i32), ("n_steps", ctypes.c_double), ("bins_per_octave", _i32), ("n_fft", _i32), ("hop_length", _i32),
                 ("freq_granularity", _i32), ("lowpass_filter_width", _i32), ("rolloff", ctypes.c_double), ("method", _i32),
                 ("beta", ctypes.c_double)]
+
+
+class F0Config(ctypes.Structure):
+    _fields_ = [("sample_rate", _i32), ("frame_length", _i32), ("hop_length", _i32), ("fmin", ctypes.c_double), ("fmax", ctypes.c_double),
+                ("threshold", ctypes.c_double)]
+
+
+class TemplateConfig(ctypes.Structure):
+    _fields_ = [("sample_rate", _i32), ("hop_length", _i32), ("kind", _i32), ("amplitude", ctypes.c_float)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -336,6 +349,25 @@ def lib() -> ctypes.CDLL:
     L.fv_spec_distance_workspace_bytes.restype = ctypes.c_size_t
     L.fv_spec_distance.argtypes = [vp, vp, i64, i64, _i32, i64, i32p, _i32, _i32, vp, vp, ctypes.c_size_t, vp]
     L.fv_spec_distance.restype = _i32
+    fcp, tcp = ctypes.POINTER(F0Config), ctypes.POINTER(TemplateConfig)
+    L.fv_f0_plan.argtypes = [fcp, i64, i32p, i32p, i32p, i64p]
+    L.fv_f0_plan.restype = _i32
+    L.fv_f0_create.argtypes = [fcp, ctypes.POINTER(vp)]
+    L.fv_f0_create.restype = _i32
+    L.fv_f0_destroy.argtypes = [vp]
+    L.fv_f0_destroy.restype = None
+    L.fv_f0_workspace_bytes.argtypes = [vp, _i32, i64]
+    L.fv_f0_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_f0_forward.argtypes = [vp, vp, i64, i32p, vp, vp, i64, _i32, i64, vp, ctypes.c_size_t, vp]
+    L.fv_f0_forward.restype = _i32
+    L.fv_template_create.argtypes = [tcp, ctypes.POINTER(vp)]
+    L.fv_template_create.restype = _i32
+    L.fv_template_destroy.argtypes = [vp]
+    L.fv_template_destroy.restype = None
+    L.fv_template_workspace_bytes.argtypes = [vp, _i32, i64]
+    L.fv_template_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_template_forward.argtypes = [vp, vp, i64, i32p, vp, i64, _i32, i64, vp, ctypes.c_size_t, vp]
+    L.fv_template_forward.restype = _i32
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

@@ -1,0 +1,190 @@
+"""F0 tracking and pitch templates on the GPU (include/fishvoc.h ``fv_f0_*`` / ``fv_template_*``): the plan in plain Python and the drop-in
+modules.
+
+``RefineGANGenerator.forward(mel, template)`` (refinegan.py:287) and the ``use_template=True`` generators (hifigan.py:226) take a pitch
+``template (B, 1, T * hop)`` next to the mel.  The reference does not make one; its users track F0 on the CPU (pyworld, parselmouth,
+``librosa.yin``) and write their own oscillator.  Here both steps run on the device, on the samples the mel is made from::
+
+    tau_max = sr // fmin;  tau_min = max(2, sr // fmax);  Wi = W - (tau_max + 1);  T = L // hop
+    frame t: the W samples centred on t hop + hop // 2 (zeros outside the row)
+    d(tau)  = sum_{j < Wi} (x[j] - x[j + tau])^2                   tau = 1 ... tau_max + 1, direct form
+    d'(tau) = d(tau) tau / sum_{k <= tau} d(k)                     1 where the running sum is 0
+    voiced: the smallest tau in [tau_min, tau_max] with d' < threshold, d'(tau) <= d'(tau - 1), d'(tau) < d'(tau + 1);
+            f0 = sr / (tau + parabolic offset), aperiodicity = d'(tau); otherwise f0 = 0, aperiodicity = min d'
+    F_t = rint(f0_t / sr * 2^32) as uint32;  inc[n] = (F_a (hop - k) + F_b k) // hop between the frame centres a, a + 1
+    phi[n] = sum_{m <= n} inc[m] mod 2^32;  template = amplitude sin(2 pi phi / 2^32), exactly 0 in unvoiced frames
+
+The phase is an unsigned 32-bit count of turns / 2^32, as the pitch shift's accumulator is (``pitch_shift.py``): it wraps where a float grows,
+so a long file keeps its pitch.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+from torch import nn
+
+from . import _lib
+from ._handle import _DeviceHandles
+from ._lib import check
+from .resample import _require_cuda, _rows
+
+MAX_FRAME_LENGTH = 4096      # one workgroup stages the frame in LDS (fv_f0_create)
+
+
+def plan(sample_rate: int, frame_length: int = 2048, hop_length: int = 512, fmin: float = 40.0, fmax: float = 1100.0,
+         threshold: float = 0.1) -> tuple[int, int, int]:
+    """``(tau_min, tau_max, Wi)`` as ``fv_f0_plan`` computes them; ValueError says which knob to move."""
+    sample_rate, frame_length, hop_length = int(sample_rate), int(frame_length), int(hop_length)
+    fmin, fmax, threshold = float(fmin), float(fmax), float(threshold)
+    if sample_rate <= 0:
+        raise ValueError(f"sample_rate ({sample_rate}) must be > 0")
+    if hop_length < 1:
+        raise ValueError(f"hop_length ({hop_length}) must be >= 1")
+    if frame_length < 2 or frame_length % 2:
+        raise ValueError(f"frame_length ({frame_length}) must be even and >= 2")
+    if not (0.0 < fmin < float("inf") and 0.0 < fmax < float("inf")):
+        raise ValueError(f"fmin ({fmin}) and fmax ({fmax}) must be positive and finite")
+    if not 0.0 < threshold <= 1.0:
+        raise ValueError(f"threshold ({threshold}) must lie in (0, 1]")
+    tau_max, tau_min = math.floor(sample_rate / fmin), max(2, math.floor(sample_rate / fmax))      # (floors of the double quotients, as in C)
+    if tau_max > 1 << 24:
+        raise ValueError(f"fmin ({fmin}) gives a longest lag of {tau_max} samples; raise fmin")
+    Wi = frame_length - (tau_max + 1)
+    if tau_min >= tau_max:
+        raise ValueError(f"fmin ({fmin}) and fmax ({fmax}) at {sample_rate} Hz give lags [{tau_min}, {tau_max}]: no lag to search; lower fmin "
+                         "or raise fmax")
+    if 2 * Wi < tau_max:
+        raise ValueError(f"frame_length ({frame_length}) leaves an integration window of {Wi} samples, less than half the longest lag "
+                         f"({tau_max}, from fmin = {fmin}); raise frame_length or fmin")
+    return tau_min, tau_max, Wi
+
+
+def _host_counts(counts, rows: int, what: str):
+    host = [int(v) for v in (counts.tolist() if torch.is_tensor(counts) else counts)]
+    if len(host) != rows:
+        raise ValueError(f"{what}: {len(host)} entries for {rows} rows")
+    return host, (ctypes.c_int32 * max(rows, 1))(*host)
+
+
+class YinF0(nn.Module):
+    """YIN on the MI355X: ``forward(wave (..., L)) -> (f0 (..., T), aperiodicity (..., T))`` with ``T = L // hop_length``, one value per mel
+    frame; ``f0`` is 0 in unvoiced frames.  ``forward_ragged(wave (B, Lmax), lengths)``: row ``b`` holds ``lengths[b]`` samples (the rest is
+    never loaded), its values are bit-identical to the row run alone and exact zeros follow them."""
+
+    def __init__(self, sample_rate: int, hop_length: int, frame_length: int = 2048, fmin: float = 40.0, fmax: float = 1100.0,
+                 threshold: float = 0.1):
+        super().__init__()
+        self.sample_rate, self.hop_length, self.frame_length = int(sample_rate), int(hop_length), int(frame_length)
+        self.fmin, self.fmax, self.threshold = float(fmin), float(fmax), float(threshold)
+        self.tau_min, self.tau_max, self.window = plan(self.sample_rate, self.frame_length, self.hop_length, self.fmin, self.fmax, self.threshold)
+        if self.frame_length > MAX_FRAME_LENGTH:
+            raise ValueError(f"frame_length ({self.frame_length}) is above {MAX_FRAME_LENGTH}, what one workgroup stages in LDS")
+        self._handles = _DeviceHandles("fv_f0_destroy")
+
+    def plan(self) -> tuple[int, int, int]:
+        return self.tau_min, self.tau_max, self.window
+
+    def frames(self, L: int) -> int:
+        return int(L) // self.hop_length
+
+    def config(self) -> _lib.F0Config:
+        return _lib.F0Config(self.sample_rate, self.frame_length, self.hop_length, self.fmin, self.fmax, self.threshold)
+
+    def _handle(self, device: torch.device) -> ctypes.c_void_p:
+        return self._handles.get(device, lambda h: _lib.lib().fv_f0_create(ctypes.byref(self.config()), h))
+
+    def _run(self, wave: torch.Tensor, lengths, what: str):
+        _require_cuda(wave, what)
+        if wave.dim() < 1:
+            raise ValueError(f"{what}: expected a waveform of shape (..., L)")
+        L = int(wave.shape[-1])
+        x = _rows(wave)
+        B, T = int(x.shape[0]), self.frames(L)
+        lptr = None if lengths is None else _host_counts(lengths, B, what)[1]
+        lib = _lib.lib()
+        h = self._handle(x.device)
+        out = torch.empty((2, B, T), dtype=torch.float32, device=x.device)
+        need = int(lib.fv_f0_workspace_bytes(h, B, L))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib.fv_f0_forward(h, x.data_ptr(), x.stride(0) if B > 1 else max(L, 1), lptr, out[0].data_ptr(), out[1].data_ptr(), max(T, 1),
+                                    B, L, ws.data_ptr(), need, int(torch.cuda.current_stream().cuda_stream)))
+        return out[0].reshape(*wave.shape[:-1], T), out[1].reshape(*wave.shape[:-1], T)
+
+    def forward(self, wave: torch.Tensor):
+        return self._run(wave, None, "YinF0.forward")
+
+    def forward_ragged(self, wave: torch.Tensor, lengths):
+        if wave.dim() != 2:
+            raise ValueError("YinF0.forward_ragged: expected a waveform of shape (B, Lmax)")
+        return self._run(wave, lengths, "YinF0.forward_ragged")
+
+    def close(self) -> None:
+        self._handles.close()
+
+    def extra_repr(self) -> str:
+        return (f"{self.sample_rate} Hz, hop_length={self.hop_length}, frame_length={self.frame_length}, lags [{self.tau_min}, {self.tau_max}], "
+                f"window={self.window}, threshold={self.threshold}")
+
+
+class PitchTemplate(nn.Module):
+    """The exact-phase oscillator: ``forward(f0 (..., T)) -> (..., 1, T * hop_length)``, what ``forward(mel, template)`` takes.  ``f0`` in Hz,
+    0 (or negative, NaN, >= sample_rate) in unvoiced frames, where the template is exactly 0.  ``forward_ragged(f0 (B, Tmax), frames)``: row
+    ``b`` holds ``frames[b]`` frames; its samples are bit-identical to the row run alone and exact zeros follow them."""
+
+    def __init__(self, sample_rate: int, hop_length: int, kind: str = "sine", amplitude: float = 1.0):
+        super().__init__()
+        self.sample_rate, self.hop_length, self.kind, self.amplitude = int(sample_rate), int(hop_length), kind, float(amplitude)
+        if kind not in _lib.TEMPLATE_KINDS:
+            raise ValueError(f"kind ({kind!r}) must be one of {sorted(_lib.TEMPLATE_KINDS)}")
+        if self.sample_rate <= 0 or not 1 <= self.hop_length <= 1 << 20:
+            raise ValueError(f"sample_rate ({self.sample_rate}) must be > 0 and hop_length ({self.hop_length}) in [1, 2^20]")
+        self._handles = _DeviceHandles("fv_template_destroy")
+
+    def config(self) -> _lib.TemplateConfig:
+        return _lib.TemplateConfig(self.sample_rate, self.hop_length, _lib.TEMPLATE_KINDS[self.kind], self.amplitude)
+
+    def _handle(self, device: torch.device) -> ctypes.c_void_p:
+        return self._handles.get(device, lambda h: _lib.lib().fv_template_create(ctypes.byref(self.config()), h))
+
+    def _run(self, f0: torch.Tensor, frames, what: str) -> torch.Tensor:
+        _require_cuda(f0, what)
+        if f0.dim() < 1:
+            raise ValueError(f"{what}: expected f0 of shape (..., T)")
+        T = int(f0.shape[-1])
+        x = _rows(f0)
+        B, N = int(x.shape[0]), T * self.hop_length
+        fptr = None if frames is None else _host_counts(frames, B, what)[1]
+        lib = _lib.lib()
+        h = self._handle(x.device)
+        out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+        need = int(lib.fv_template_workspace_bytes(h, B, T))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib.fv_template_forward(h, x.data_ptr(), x.stride(0) if B > 1 else max(T, 1), fptr, out.data_ptr(), max(N, 1), B, T,
+                                          ws.data_ptr(), need, int(torch.cuda.current_stream().cuda_stream)))
+        return out.reshape(*f0.shape[:-1], 1, N)
+
+    def forward(self, f0: torch.Tensor) -> torch.Tensor:
+        return self._run(f0, None, "PitchTemplate.forward")
+
+    def forward_ragged(self, f0: torch.Tensor, frames) -> torch.Tensor:
+        if f0.dim() != 2:
+            raise ValueError("PitchTemplate.forward_ragged: expected f0 of shape (B, Tmax)")
+        return self._run(f0, frames, "PitchTemplate.forward_ragged")
+
+    def close(self) -> None:
+        self._handles.close()
+
+    def extra_repr(self) -> str:
+        return f"{self.sample_rate} Hz, hop_length={self.hop_length}, kind={self.kind!r}, amplitude={self.amplitude}"
+
+
+def template_from_audio(wave: torch.Tensor, sample_rate: int, hop_length: int, frame_length: int = 2048, fmin: float = 40.0,
+                        fmax: float = 1100.0, threshold: float = 0.1, kind: str = "sine", amplitude: float = 1.0) -> torch.Tensor:
+    """``wave (..., L) -> template (..., 1, (L // hop_length) * hop_length)``: ``YinF0`` then ``PitchTemplate`` on the same samples the mel is
+    made from."""
+    f0, _ = YinF0(sample_rate, hop_length, frame_length, fmin, fmax, threshold)(wave)
+    return PitchTemplate(sample_rate, hop_length, kind, amplitude)(f0)

@@ -15,7 +15,10 @@
   ``--chunk-frames N`` streams each input N mel frames at a time (``stream_synthesis``) instead of one whole-utterance forward; a ``.wav`` is
   read, converted and written ``N * hop`` samples at a time through ``stream_wav_synthesis`` (resample stream, log-mel stream, generator
   stream, resample stream), so the first audio is out long before the file has been read.  ``--batch-size N`` takes ``.wav`` files too: their
-  rows go through the front-end's ``forward_list`` and then the generator's.
+  rows go through the front-end's ``forward_list`` and then the generator's.  A generator that takes a pitch template next to the mel
+  (``RefineGANGenerator``, ``use_template=True``; refinegan.py:287, hifigan.py:226) gets one: for a ``.wav`` it is made on the GPU from the
+  samples the mel is made from (``vocoder_amd.f0``: YIN, then an exact-phase oscillator; ``--f0-min`` / ``--f0-max`` / ``--f0-threshold`` /
+  ``--template-kind``), for a mel from the sidecar ``<stem>.f0.npy`` (Hz per mel frame, 0 = unvoiced); whole files and ``--batch-size``.
 """
 from __future__ import annotations
 
@@ -44,13 +47,15 @@ class InferenceModel(nn.Module):
     def device(self):
         return next(self.generator.parameters()).device
 
-    def forward(self, audio, mask=None, input_spec=None):
+    def forward(self, audio, mask=None, input_spec=None, template=None):
         if input_spec is None:
             if self.mel_transform is None or audio is None:
                 raise NotImplementedError(
                     "wave -> mel (mel_transforms.input, gan.py:284) needs a mel_transform (build_model attaches one); "
                     "pass input_spec= otherwise")
             input_spec = self.mel_transform(audio.squeeze(1) if audio.dim() == 3 else audio)
+        if template is not None:      # refinegan.py:287 / hifigan.py:226: forward(mel, template)
+            return self.generator(input_spec, template), 0
         return self.generator(input_spec), 0
 
 
@@ -365,6 +370,39 @@ def _pitch_shifted(a, model, y: torch.Tensor) -> torch.Tensor:
     return PitchShift(model.sampling_rate, a.pitch_shift)(y)
 
 
+def takes_template(generator: nn.Module) -> bool:
+    """Does ``generator.forward`` take a pitch template next to the mel (refinegan.py:287; hifigan.py:226 / bigvgan.py with use_template)?"""
+    from .modules.generators.refinegan import RefineGANGenerator
+    return isinstance(generator, RefineGANGenerator) or bool(getattr(generator, "use_template", False))
+
+
+def _wav_template(a, model, y: torch.Tensor) -> torch.Tensor:
+    """The template of the rows ``y`` (..., L) — the samples the mel is made from: after loading, --resample, --pitch-shift and the zero
+    padding — ``(..., 1, (L // hop) * hop)``, on the GPU."""
+    from .f0 import template_from_audio
+    return template_from_audio(y, model.sampling_rate, model.hop_length, fmin=a.f0_min, fmax=a.f0_max, threshold=a.f0_threshold,
+                               kind=a.template_kind)
+
+
+def _sidecar_template(a, model, f, mel: torch.Tensor) -> torch.Tensor:
+    """The template of a mel input ``(B, num_mels, T)`` from ``<stem>.f0.npy``: Hz per mel frame, 0 in unvoiced frames, ``(T,)`` or
+    ``(B, T)``; ``(B, 1, T * hop)``."""
+    from .f0 import PitchTemplate
+    side = f.with_suffix(".f0.npy")
+    if not side.is_file():
+        raise ValueError(f"{f}: {type(model.generator).__name__} takes a pitch template and a mel input carries no audio to track; {side} "
+                         "(frame-level F0 in Hz, 0 = unvoiced) is missing")
+    f0 = np.load(side, allow_pickle=False)
+    B, T = int(mel.shape[0]), int(mel.shape[-1])
+    if f0.ndim == 1:
+        f0 = f0[None]
+    if f0.ndim != 2 or f0.shape[1] != T or f0.shape[0] not in (1, B):
+        raise ValueError(f"{side}: F0 of shape {tuple(np.load(side, allow_pickle=False).shape)}, the mel {f} has {T} frames"
+                         + (f" in {B} items" if B > 1 else ""))
+    f0 = torch.from_numpy(np.array(np.broadcast_to(f0, (B, T)), dtype=np.float32)).to(model.device)      # (a writable copy)
+    return PitchTemplate(model.sampling_rate, model.hop_length, kind=a.template_kind)(f0)
+
+
 def _wav_rows(a, model, f) -> torch.Tensor:
     """A .wav as the whole-file branch prepares it (test.py:50-68): channels -> rows at the model's rate, pitch shift, zero padding;
     ``(channels, L)``."""
@@ -386,11 +424,14 @@ def _main_batched(a, model, files, base) -> None:
     for i in range(0, len(files), a.batch_size):
         chunk = files[i:i + a.batch_size]
         mels, owner = [], []
+        templates = [] if takes_template(model.generator) else None
         for f in chunk:
             if f.suffix == ".wav":     # the rows of every .wav of the batch go through the front-end together, below
                 rows = _wav_rows(a, model, f)
                 mels.extend(rows[b] for b in range(rows.shape[0]))
                 owner.extend([f] * rows.shape[0])
+                if templates is not None:
+                    templates.extend(_wav_template(a, model, rows))
                 continue
             mel = torch.load(f, map_location="cpu", weights_only=True)
             if a.diffsinger:
@@ -398,12 +439,14 @@ def _main_batched(a, model, files, base) -> None:
             mel = prepare_mel(mel, model.num_mels).to(model.device)
             mels.extend(mel[b] for b in range(mel.shape[0]))
             owner.extend([f] * mel.shape[0])
+            if templates is not None:
+                templates.extend(_sidecar_template(a, model, f, mel))
         wav_at = [j for j, o in enumerate(owner) if o.suffix == ".wav"]
         if wav_at:
             for j, m in zip(wav_at, model.mel_transform.forward_list([mels[j] for j in wav_at])):
                 mels[j] = m
         t0 = time.time()
-        waves = model.generator.forward_list(mels)
+        waves = model.generator.forward_list(mels) if templates is None else model.generator.forward_list(mels, templates)
         torch.cuda.synchronize()
         secs = sum(w.shape[-1] for w in waves) / model.sampling_rate
         print(f"{len(chunk)} files ({chunk[0]} ...): {secs:.2f}s of audio in {time.time() - t0:.4f}s, one ragged forward")
@@ -493,6 +536,11 @@ def main(argv=None):
                     help="shift every .wav input by N_STEPS semitones on the GPU after loading and --resample, before the mel front-end (the "
                          "reference's librosa.effects.pitch_shift, test.py:61-62); whole files and --batch-size, not mel inputs, "
                          "--chunk-frames or --sessions")
+    ap.add_argument("--f0-min", type=float, default=40.0, metavar="HZ",
+                    help="lowest F0 the tracker searches, for a generator that takes a pitch template (RefineGAN, use_template=True)")
+    ap.add_argument("--f0-max", type=float, default=1100.0, metavar="HZ", help="highest F0 the tracker searches")
+    ap.add_argument("--f0-threshold", type=float, default=0.1, help="YIN's voicing threshold on the normalised difference function, in (0, 1]")
+    ap.add_argument("--template-kind", choices=("sine", "sawtooth"), default="sine", help="waveform of the pitch template")
     a = ap.parse_args(argv)
     if a.pitch_shift and (a.chunk_frames is not None or a.sessions is not None):
         raise ValueError("--pitch-shift is not available with --chunk-frames / --sessions: the phase vocoder has no streaming form; run the "
@@ -508,7 +556,13 @@ def main(argv=None):
     if a.batch_size is not None and (a.batch_size < 1 or a.chunk_frames is not None):
         ap.error("--batch-size must be >= 1 and cannot be combined with --chunk-frames")
     model = build_model(a.generator, a.resolution, {"num_mels": a.num_mels} if a.num_mels else None, a.config_root,
-                        a.ckpt_path, trust_checkpoint=a.trust_checkpoint)
+                        a.ckpt_path, device="cpu", trust_checkpoint=a.trust_checkpoint)      # (on the host first: the refusal below needs no GPU)
+    with_template = takes_template(model.generator)
+    if with_template and (a.chunk_frames is not None or a.sessions is not None):
+        raise ValueError(f"{type(model.generator).__name__} takes a pitch template, and the template has no streaming form yet (it would carry "
+                         "the oscillator's phase and half a tracker frame of lookahead): run without --chunk-frames / --sessions, whole files "
+                         "or --batch-size")
+    model = model.to("cuda")
     inp = Path(a.input_path)
     files = [inp] if inp.is_file() else sorted(p for p in inp.rglob("*") if p.suffix in (".pt", ".pth", ".wav"))
     base = inp.parent if inp.is_file() else inp
@@ -539,18 +593,20 @@ def main(argv=None):
             y = _pitch_shifted(a, model, y.to(model.device))      # test.py:61-62
             y = torch.nn.functional.pad(y, (0, model.hop_length - (model.hop_length % y.shape[-1])))   # as written upstream
             mel = model.mel_transform(y.to(model.device).squeeze(1))
+            template = _wav_template(a, model, y.squeeze(1)) if with_template else None
         else:
             mel = torch.load(f, map_location="cpu", weights_only=True)
             if a.diffsinger:
                 mel = diffsinger_mel_to_ln(mel)
             mel = prepare_mel(mel, model.num_mels).to(model.device)
+            template = _sidecar_template(a, model, f, mel) if with_template else None
         t0 = time.time()
         if a.chunk_frames:
             fake, first, lat = stream_synthesis(model.generator, mel, a.chunk_frames, resample=to_out)
             print(f"{f}: {fake.shape[-1] / out_rate:.2f}s of audio in {time.time() - t0:.4f}s, streamed in {a.chunk_frames}-frame "
                   f"chunks: first audio after {first * 1e3:.2f} ms, per-chunk p50 {np.percentile(lat, 50) * 1e3:.2f} ms")
         else:
-            fake = model(None, None, input_spec=mel)[0]
+            fake = model(None, None, input_spec=mel, template=template)[0]
             if to_out is not None:
                 fake = to_out(fake)
             torch.cuda.synchronize()
