@@ -710,7 +710,8 @@ FV_API fv_status fv_pitch_shift_forward(fv_pitch_shift* p, const float* d_x, int
  * inc[n] = (F_a (hop - k) + F_b k) / hop in 64-bit integers, an unvoiced neighbour taking the other one's value; the phase
  * phi[n] = sum_{m <= n} inc[m] mod 2^32 is an integer prefix sum, exact in any order (an fp32 accumulator drifts audibly within seconds).
  * Output amplitude sin(2 pi phi / 2^32) or amplitude (2 phi / 2^32 - 1), exactly 0 where frame n / hop is unvoiced.
- * Not built: a streaming form (it would carry phi and a lookahead of W / 2 samples), pYIN / Viterbi smoothing, octave-error correction. */
+ * The streaming form (fv_yin_stream_*, fv_osc_stream_*) follows the whole-row entries.  Not built: pYIN / Viterbi smoothing, octave-error
+ * correction. */
 typedef struct fv_f0_config {
     int32_t sample_rate;   /* the model's rate: the tracker runs on the samples the mel is made from */
     int32_t frame_length;  /* W, even; 2048 */
@@ -767,6 +768,79 @@ FV_API size_t fv_template_workspace_bytes(const fv_template* p, int32_t batch, i
 FV_API fv_status fv_template_forward(fv_template* p, const float* d_f0, int64_t f0_row_stride, const int32_t* host_frames, float* d_out,
                                      int64_t out_row_stride, int32_t batch, int64_t T, void* d_workspace, size_t workspace_bytes,
                                      void* stream);
+
+/* Streaming form of both steps (no reference counterpart: the CPU trackers in front of refinegan.py:287 / hifigan.py:226 take whole files):
+ * `batch` rows advance in lockstep, as in fv_resample_stream_* and fv_logmel_stream_*; what comes out feeds fv_stream_push's d_template.  (Named
+ * outside the fv_f0_ / fv_template_ prefixes: those families' lists of entries are pinned by their host test.)
+ *
+ * Tracker stream.  Host counters: N samples received, E frames emitted.  Frame t reads the samples [t hop + hop / 2 - W / 2, ... + W) and
+ * leaves once none of them is at or after N: ready(N) = 0 for N < hop / 2 + W / 2, else min(1 + (N - hop / 2 - W / 2) / hop, N / hop).  A
+ * push sets N += c and emits the frames [E, ready(N)); the flush emits [E, N / hop) against the rows' true end (samples at or past N are
+ * zeros by index, as fv_f0_forward treats a row's length) and then refuses pushes (FV_ERR_STATE) until the reset.  Latency: a frame leaves
+ * W / 2 + hop / 2 - hop samples after its own hop has arrived — 768 samples, 17 ms, at 44100 Hz / W 2048 / hop 512, the log-mel stream's own
+ * figure.  A YIN frame's bits depend on the plan alone, so the concatenated values are bit-identical to fv_f0_forward over the whole rows.
+ *
+ * Oscillator stream.  Host counters: Tn F0 frames received, E frames emitted, each `hop` samples.  The samples of frame t interpolate between
+ * the frame centres t - 1, t and t + 1: a push sets Tn += c and emits the samples of the frames [E, max(E, Tn - 1)); the flush emits [E, Tn)
+ * with the last centre clamped to Tn - 1, as fv_template_forward clamps to the row's last frame.  Latency: one F0 frame.  The phase at the start
+ * of frame E is carried on the device as a wrapping uint32; integer addition is exact in any order, so the concatenated samples are
+ * bit-identical to fv_template_forward over the whole rows.
+ *
+ * Every call validates everything before it enqueues anything, enqueues eagerly on `stream` and never synchronises; a refused call changes
+ * nothing.  Not built: per-session (non-lockstep) template streams for fv_pool_step, a streaming RefineGAN, a streaming pitch shift. */
+typedef struct fv_yin_stream fv_yin_stream;
+typedef struct fv_osc_stream fv_osc_stream;
+
+/* Pure host (no GPU): ready(N) above, the frames a tracker stream has emitted once N samples have arrived (the CPU trackers in front of
+ * refinegan.py:287 / hifigan.py:226 see whole files only); never above N / hop.  -1: N < 0 or a configuration fv_f0_plan refuses. */
+FV_API int64_t fv_yin_frames_ready(const fv_f0_config* cfg, int64_t N);
+
+/* The stream's only device allocation (a CPU tracker in front of refinegan.py:287 / hifigan.py:226 keeps no state), freed by
+ * fv_yin_stream_destroy: two (batch, H + max_chunk_samples) buffers used in turn that carry each row's last H = W / 2 + max(W / 2,
+ * (hop + 1) / 2) samples (W when hop <= W) from push to push.  `p` must outlive the stream. */
+FV_API fv_status fv_yin_stream_create(fv_f0* p, int32_t batch, int32_t max_chunk_samples, fv_yin_stream** out);
+/* N - max(0, E hop + hop / 2 - W / 2), never negative: samples received that frames not yet emitted still read, fewer than H (what a CPU
+ * tracker in front of refinegan.py:287 / hifigan.py:226 would hold as the file's tail). */
+FV_API int64_t fv_yin_stream_pending_samples(const fv_yin_stream* s);
+/* d_wave: (batch, c) with row stride row_stride, c <= max_chunk_samples (else FV_ERR_INVALID) — the next samples of what the tracker in front
+ * of refinegan.py:287 / hifigan.py:226 is handed whole; d_f0 / d_aperiodicity: (batch, k) with row stride out_row_stride,
+ * k = fv_yin_frames_ready(N + c) - E known before the call; k may be 0, then both may be NULL.  *frames_out receives k.  c = 0 is a no-op.
+ * Asynchronous on `stream`; calls on one stream object must be ordered. */
+FV_API fv_status fv_yin_stream_push(fv_yin_stream* s, const float* d_wave, int64_t row_stride, int32_t c, float* d_f0, float* d_aperiodicity,
+                                    int64_t out_row_stride, int64_t* frames_out, void* stream);
+/* Emits the frames [E, N / hop) against the utterance's end, the last values a whole-file tracker in front of refinegan.py:287 /
+ * hifigan.py:226 returns; d_f0 / d_aperiodicity: (batch, N / hop - E).  A flush at N = 0 emits nothing. */
+FV_API fv_status fv_yin_stream_flush(fv_yin_stream* s, float* d_f0, float* d_aperiodicity, int64_t out_row_stride, int64_t* frames_out,
+                                     void* stream);
+/* N = E = 0 for the next utterance (the next file of a tracker in front of refinegan.py:287 / hifigan.py:226); the buffers are kept, and
+ * samples before 0 are zeros by index whatever they hold. */
+FV_API fv_status fv_yin_stream_reset(fv_yin_stream* s);
+/* Call it before fv_f0_destroy of its tracker, once the stream's work has finished (a CPU tracker in front of refinegan.py:287 /
+ * hifigan.py:226 has nothing to free). */
+FV_API void fv_yin_stream_destroy(fv_yin_stream* s);
+
+/* The stream's only device allocations (a CPU oscillator in front of refinegan.py:287 / hifigan.py:226 keeps its phase in a host float), freed
+ * by fv_osc_stream_destroy: two (batch, 2 + max_chunk_frames) buffers used in turn that carry the F0 of the frames [E - 1, Tn), the
+ * increments and chunk sums of one call, and two (batch) uint32 phases used in turn.  (2 + max_chunk_frames) * hop <= 2^30.  `p` must outlive
+ * the stream. */
+FV_API fv_status fv_osc_stream_create(fv_template* p, int32_t batch, int32_t max_chunk_frames, fv_osc_stream** out);
+/* Tn - E: F0 frames received whose samples have not left, 0 or 1 between calls (a CPU oscillator in front of refinegan.py:287 /
+ * hifigan.py:226 waits for the whole track). */
+FV_API int64_t fv_osc_stream_pending_frames(const fv_osc_stream* s);
+/* d_f0: (batch, c) in Hz with row stride row_stride, c <= max_chunk_frames (else FV_ERR_INVALID) — the next frames of the track a user of
+ * refinegan.py:287 / hifigan.py:226 brings whole; d_out: (batch, k hop) with row stride out_row_stride, k = max(E, Tn + c - 1) - E frames known
+ * before the call; k may be 0, then d_out may be NULL.  *samples_out receives k hop.  c = 0 is a no-op.  Asynchronous on `stream`; calls on
+ * one stream object must be ordered. */
+FV_API fv_status fv_osc_stream_push(fv_osc_stream* s, const float* d_f0, int64_t row_stride, int32_t c, float* d_out, int64_t out_row_stride,
+                                    int64_t* samples_out, void* stream);
+/* Emits the samples of the frames [E, Tn), the end of the template refinegan.py:287 / hifigan.py:226 take; d_out: (batch, (Tn - E) hop). */
+FV_API fv_status fv_osc_stream_flush(fv_osc_stream* s, float* d_out, int64_t out_row_stride, int64_t* samples_out, void* stream);
+/* Tn = E = 0 for the next utterance (the next track of refinegan.py:287 / hifigan.py:226's user); the buffers are kept: the first call of an
+ * utterance takes phase 0 by index, not from memory. */
+FV_API fv_status fv_osc_stream_reset(fv_osc_stream* s);
+/* Call it before fv_template_destroy of its synthesiser, once the stream's work has finished (refinegan.py:287 / hifigan.py:226's users free
+ * nothing). */
+FV_API void fv_osc_stream_destroy(fv_osc_stream* s);
 
 /* -------- scoring generated audio: the distances eval.py and the STFT loss compute between a source and a generated waveform, as metrics.
  *          eval.py:29-33's spec_diff is mean |LogMelSpectrogram(target) - LogMelSpectrogram(preds)|; stft.py:55 is the spectral convergence

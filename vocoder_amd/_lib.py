@@ -59,6 +59,10 @@ EXPORTS = (
     "fv_spec_distance_tile", "fv_spec_distance_workspace_bytes", "fv_spec_distance",
     "fv_f0_plan", "fv_f0_create", "fv_f0_destroy", "fv_f0_workspace_bytes", "fv_f0_forward",
     "fv_template_create", "fv_template_destroy", "fv_template_workspace_bytes", "fv_template_forward",
+    "fv_yin_frames_ready", "fv_yin_stream_create", "fv_yin_stream_pending_samples", "fv_yin_stream_push", "fv_yin_stream_flush",
+    "fv_yin_stream_reset", "fv_yin_stream_destroy",
+    "fv_osc_stream_create", "fv_osc_stream_pending_frames", "fv_osc_stream_push", "fv_osc_stream_flush", "fv_osc_stream_reset",
+    "fv_osc_stream_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -368,6 +372,32 @@ def lib() -> ctypes.CDLL:
     L.fv_template_workspace_bytes.restype = ctypes.c_size_t
     L.fv_template_forward.argtypes = [vp, vp, i64, i32p, vp, i64, _i32, i64, vp, ctypes.c_size_t, vp]
     L.fv_template_forward.restype = _i32
+    L.fv_yin_frames_ready.argtypes = [fcp, i64]
+    L.fv_yin_frames_ready.restype = i64
+    L.fv_yin_stream_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_yin_stream_create.restype = _i32
+    L.fv_yin_stream_pending_samples.argtypes = [vp]
+    L.fv_yin_stream_pending_samples.restype = i64
+    L.fv_yin_stream_push.argtypes = [vp, vp, i64, _i32, vp, vp, i64, i64p, vp]
+    L.fv_yin_stream_push.restype = _i32
+    L.fv_yin_stream_flush.argtypes = [vp, vp, vp, i64, i64p, vp]
+    L.fv_yin_stream_flush.restype = _i32
+    L.fv_yin_stream_reset.argtypes = [vp]
+    L.fv_yin_stream_reset.restype = _i32
+    L.fv_yin_stream_destroy.argtypes = [vp]
+    L.fv_yin_stream_destroy.restype = None
+    L.fv_osc_stream_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_osc_stream_create.restype = _i32
+    L.fv_osc_stream_pending_frames.argtypes = [vp]
+    L.fv_osc_stream_pending_frames.restype = i64
+    L.fv_osc_stream_push.argtypes = [vp, vp, i64, _i32, vp, i64, i64p, vp]
+    L.fv_osc_stream_push.restype = _i32
+    L.fv_osc_stream_flush.argtypes = [vp, vp, i64, i64p, vp]
+    L.fv_osc_stream_flush.restype = _i32
+    L.fv_osc_stream_reset.argtypes = [vp]
+    L.fv_osc_stream_reset.restype = _i32
+    L.fv_osc_stream_destroy.argtypes = [vp]
+    L.fv_osc_stream_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

@@ -7,6 +7,10 @@
 //   f0_increment_kernel        f0 (Hz) -> F = rint(f0 / sr * 2^32), the phase increment per sample in turns / 2^32 as uint32; 0 = unvoiced
 //   f0_template_sums_kernel    per kTmplChunk samples of a row: the sum of the interpolated increments, wrapping uint32
 //   f0_template_kernel         carry = the sums of the chunks before this one; a workgroup scan inside the chunk; sin / sawtooth of the phase
+//   osc_stream_sums_kernel,    the same two levels on the frames a stream has staged (fv_osc_stream_*), the carry started from the phase the
+//   osc_stream_kernel          call before left on the device
+// The streams (fv_yin_stream_*, fv_osc_stream_*) sit on the sample streams' carry core (sample_stream.h): the tracker carries the last samples of
+// every row and runs yin_f0_kernel on [carried | chunk]; the oscillator carries the last two F0 frames, as its "samples", and the phase.
 //
 // Why the direct form: E(0) + E(tau) - 2 r(tau) cancels in fp32 exactly where d is small, the voiced case.  Every d(tau) is one fp32 accumulator
 // over ascending j with fused multiply-adds, and the running sum is scanned in chunks of 64 lags whatever the launch: a frame's bits depend on
@@ -16,6 +20,7 @@
 #include <memory>
 
 #include "engine_internal.h"
+#include "sample_stream.h"
 
 namespace fv {
 namespace {
@@ -101,20 +106,22 @@ __device__ __forceinline__ float wave_scan_add(float v, int lane) {   // inclusi
     return v;
 }
 
-// grid (frames T, rows); block pl.threads().  LDS: xs[W + 8] (the frame, then zeros) | dl[d_elems] (d, then d') | cs[d_elems] (the prefix inside
-// a 64-lag chunk) | ct[d_elems / 64] (chunk totals) | red[32].  Samples before 0 or at or past the row's length are zeros by index: the address is
-// clamped and the value selected, so no sample past the length is loaded.
+// grid (frames, rows); block pl.threads().  LDS: xs[W + 8] (the frame, then zeros) | dl[d_elems] (d, then d') | cs[d_elems] (the prefix inside
+// a 64-lag chunk) | ct[d_elems / 64] (chunk totals) | red[32].  Workgroup x computes frame t0 + x into column x.  x[b] holds the samples
+// [origin, origin + rows.len) of row b (the whole row: origin 0, t0 0, len the row's length; a stream: its carried samples and the chunk), the
+// frame's global indices map to index - origin.  Samples before 0 or at or past limit = origin + len are zeros by index: the address is clamped
+// and the value selected, so no sample outside [origin, limit) is loaded.
 __global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __restrict__ x, long long x_stride, F0RowBlock rows, int row0,
-                                                                float* __restrict__ f0, float* __restrict__ ap, long long out_stride, int T,
-                                                                YinPlan pl) {
+                                                                float* __restrict__ f0, float* __restrict__ ap, long long out_stride,
+                                                                long long origin, long long t0, YinPlan pl) {
     extern __shared__ __align__(16) float lds[];
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
-    const int t = blockIdx.x, b = row0 + blockIdx.y;
-    const int len = rows.len[blockIdx.y];
+    const int col = blockIdx.x, b = row0 + blockIdx.y;
+    const long long t = t0 + col, limit = origin + rows.len[blockIdx.y], first = origin > 0 ? origin : 0;
     float* f0r = f0 + (long long)b * out_stride;
     float* apr = ap + (long long)b * out_stride;
-    if (t >= len / pl.hop) {   // (the whole workgroup leaves: no barrier below is reached by a part of it)
-        if (tid == 0) f0r[t] = 0.f, apr[t] = 0.f;
+    if (t >= limit / pl.hop) {   // (the whole workgroup leaves: no barrier below is reached by a part of it)
+        if (tid == 0) f0r[col] = 0.f, apr[col] = 0.f;
         return;
     }
     const int W = pl.W, Wi = pl.Wi, NL = pl.lags(), DE = pl.d_elems();
@@ -124,12 +131,12 @@ __global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __r
     float* ct = cs + DE;
     float* red = ct + DE / 64;
     const float* xr = x + (long long)b * x_stride;
-    const long long lo = (long long)t * pl.hop + pl.hop / 2 - W / 2;
+    const long long lo = t * pl.hop + pl.hop / 2 - W / 2;
     for (int i = tid; i < W + 8; i += nthr) {
         const long long idx = lo + i;
-        const bool in = i < W && idx >= 0 && idx < len;
-        const long long at = idx < 0 ? 0 : (idx >= len ? len - 1 : idx);
-        const float v = xr[at];
+        const bool in = i < W && idx >= first && idx < limit;
+        const long long at = idx < first ? first : (idx >= limit ? limit - 1 : idx);
+        const float v = xr[at - origin];
         xs[i] = in ? v : 0.f;
     }
     for (int i = tid; i < DE; i += nthr) dl[i] = 0.f;
@@ -218,8 +225,8 @@ __global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __r
             f = (float)pl.sr / ((float)best + delta);
             aper = bb;
         }
-        f0r[t] = f;
-        apr[t] = aper;
+        f0r[col] = f;
+        apr[col] = aper;
     }
 }
 
@@ -237,49 +244,44 @@ __global__ __launch_bounds__(256) void f0_increment_kernel(const float* __restri
     F[(long long)b * T + t] = v;
 }
 
-// The increment of sample n of a row of Ti frames: between the frame centres a = floor((n - hop / 2) / hop) and a + 1, both clamped to
-// [0, Ti - 1], k samples past centre a; an unvoiced neighbour (F = 0) takes the other one's value
-__device__ __forceinline__ uint32_t tmpl_inc(const uint32_t* __restrict__ Fr, int Ti, int hop, int n) {
+// The increment of sample n of a row whose staged frames are Fr[lo_c ... hi_c]: between the frame centres a = floor((n - hop / 2) / hop) and
+// a + 1, both clamped to [lo_c, hi_c], k samples past centre a; an unvoiced neighbour (F = 0) takes the other one's value.  The whole row:
+// lo_c = 0, hi_c = Ti - 1.  A stream counts n and a from the first staged frame, which is frame `o` of the row: lo_c = max(0, -o) and
+// hi_c = (frames received) - 1 - o, and n - hop / 2 >= 0 for every sample it emits.
+__device__ __forceinline__ uint32_t tmpl_inc(const uint32_t* __restrict__ Fr, int lo_c, int hi_c, int hop, int n) {
     const int m = n - hop / 2;
     const int a = m >= 0 ? m / hop : -1;
     const int k = m - a * hop;
-    uint32_t Fa = Fr[min(max(a, 0), Ti - 1)], Fb = Fr[min(a + 1, Ti - 1)];
+    uint32_t Fa = Fr[min(max(a, lo_c), hi_c)], Fb = Fr[min(max(a + 1, lo_c), hi_c)];
     if (Fa == 0u) Fa = Fb;
     else if (Fb == 0u) Fb = Fa;
     return (uint32_t)(((unsigned long long)Fa * (unsigned)(hop - k) + (unsigned long long)Fb * (unsigned)k) / (unsigned)hop);
 }
 
-// grid (chunks, rows): sums[b][chunk] = the sum of the chunk's increments, wrapping
-__global__ __launch_bounds__(256) void f0_template_sums_kernel(const uint32_t* __restrict__ F, F0RowBlock rows, int row0,
-                                                               uint32_t* __restrict__ sums, int T, int hop, int nchunk) {
+// One workgroup of 256: the sum of the increments of the samples [n0, n0 + kTmplItems) of every thread that lie before n_end, wrapping; the
+// total is returned to thread 0
+__device__ __forceinline__ uint32_t tmpl_chunk_sum(const uint32_t* __restrict__ Fr, int lo_c, int hi_c, int hop, int n0, int n_end) {
     __shared__ uint32_t part[4];
-    const int b = row0 + blockIdx.y, Ti = rows.len[blockIdx.y], lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int Ni = Ti * hop;
-    const uint32_t* Fr = F + (long long)b * T;
-    const int n0 = blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t s = 0u;
 #pragma unroll
     for (int i = 0; i < kTmplItems; ++i)
-        if (n0 + i < Ni) s += tmpl_inc(Fr, Ti, hop, n0 + i);
+        if (n0 + i < n_end) s += tmpl_inc(Fr, lo_c, hi_c, hop, n0 + i);
 #pragma unroll
     for (int sh = 32; sh > 0; sh >>= 1) s += __shfl_xor(s, sh, 64);
     if (lane == 0) part[wave] = s;
     __syncthreads();
-    if (threadIdx.x == 0) sums[(long long)b * nchunk + blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    return part[0] + part[1] + part[2] + part[3];
 }
 
-// grid (chunks, rows): phi[n] = sum_{m <= n} inc[m] = (the chunks before) + (the threads before, a workgroup scan) + (this thread's own samples)
-__global__ __launch_bounds__(256) void f0_template_kernel(const uint32_t* __restrict__ F, const uint32_t* __restrict__ sums, F0RowBlock rows,
-                                                          int row0, float* __restrict__ out, long long out_stride, int T, int hop, int nchunk,
-                                                          int kind, float amplitude) {
+// One workgroup of 256: phi[n] = (the phase before the chunk: the threads' `carry` summed) + (the threads before, a workgroup scan) + (this
+// thread's own samples); sample n < n_out goes to orow[n - out0], a zero from n_inc on and in an unvoiced frame Fr[n / hop].  phase_after
+// (NULL: not wanted): the last thread stores the phase after the chunk's last sample, an ordinary store.
+__device__ __forceinline__ void tmpl_chunk_emit(const uint32_t* __restrict__ Fr, int lo_c, int hi_c, int hop, int n0, int n_inc, int n_out,
+                                                uint32_t carry, float* __restrict__ orow, int out0, int kind, float amplitude,
+                                                uint32_t* __restrict__ phase_after) {
     __shared__ uint32_t part[4], wtot[4];
-    const int b = row0 + blockIdx.y, Ti = rows.len[blockIdx.y], lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int N = T * hop, Ni = Ti * hop;
-    const uint32_t* Fr = F + (long long)b * T;
-    float* orow = out + (long long)b * out_stride;
-    const int n0 = blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems;
-    uint32_t carry = 0u;
-    for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) carry += sums[(long long)b * nchunk + c];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int sh = 32; sh > 0; sh >>= 1) carry += __shfl_xor(carry, sh, 64);
     if (lane == 0) part[wave] = carry;
@@ -287,7 +289,7 @@ __global__ __launch_bounds__(256) void f0_template_kernel(const uint32_t* __rest
     uint32_t s = 0u;
 #pragma unroll
     for (int i = 0; i < kTmplItems; ++i) {
-        if (n0 + i < Ni) s += tmpl_inc(Fr, Ti, hop, n0 + i);
+        if (n0 + i < n_inc) s += tmpl_inc(Fr, lo_c, hi_c, hop, n0 + i);
         ph[i] = s;
     }
     uint32_t inc = s;
@@ -300,20 +302,62 @@ __global__ __launch_bounds__(256) void f0_template_kernel(const uint32_t* __rest
     __syncthreads();
     uint32_t base = part[0] + part[1] + part[2] + part[3] + (inc - s);
     for (int w = 0; w < wave; ++w) base += wtot[w];
+    if (phase_after && threadIdx.x == 255) *phase_after = base + ph[kTmplItems - 1];
 #pragma unroll
     for (int i = 0; i < kTmplItems; ++i) {
         const int n = n0 + i;
-        if (n >= N) break;
+        if (n >= n_out) break;
         float v = 0.f;
-        if (n < Ni && Fr[n / hop] != 0u) {
+        if (n < n_inc && Fr[n / hop] != 0u) {
             const uint32_t phi = base + ph[i];
             if (kind == FV_TEMPLATE_SAWTOOTH)
                 v = amplitude * ((float)(int32_t)(phi ^ 0x80000000u) * (1.0f / 2147483648.0f));   // 2 phi / 2^32 - 1
             else
                 v = amplitude * sinpif((float)(int32_t)phi * (1.0f / 2147483648.0f));   // phi as signed turns: 2 pi phi / 2^32 = pi x
         }
-        orow[n] = v;
+        orow[n - out0] = v;
     }
+}
+
+// grid (chunks, rows): sums[b][chunk] = the sum of the chunk's increments, wrapping
+__global__ __launch_bounds__(256) void f0_template_sums_kernel(const uint32_t* __restrict__ F, F0RowBlock rows, int row0,
+                                                               uint32_t* __restrict__ sums, int T, int hop, int nchunk) {
+    const int b = row0 + blockIdx.y, Ti = rows.len[blockIdx.y];
+    const uint32_t s = tmpl_chunk_sum(F + (long long)b * T, 0, Ti - 1, hop, blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, Ti * hop);
+    if (threadIdx.x == 0) sums[(long long)b * nchunk + blockIdx.x] = s;
+}
+
+// grid (chunks, rows): the carry is the sums of the chunks before this one
+__global__ __launch_bounds__(256) void f0_template_kernel(const uint32_t* __restrict__ F, const uint32_t* __restrict__ sums, F0RowBlock rows,
+                                                          int row0, float* __restrict__ out, long long out_stride, int T, int hop, int nchunk,
+                                                          int kind, float amplitude) {
+    const int b = row0 + blockIdx.y, Ti = rows.len[blockIdx.y];
+    uint32_t carry = 0u;
+    for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) carry += sums[(long long)b * nchunk + c];
+    tmpl_chunk_emit(F + (long long)b * T, 0, Ti - 1, hop, blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, Ti * hop, T * hop, carry,
+                    out + (long long)b * out_stride, 0, kind, amplitude, nullptr);
+}
+
+// The oscillator stream's two levels, grid (chunks, rows), every row in lockstep.  F[b] holds the increments of `fcount` staged frames, the first
+// of them frame `o` of the row; a call emits the samples [n_lo, n_hi) counted from frame o's first sample into the columns [0, n_hi - n_lo).
+__global__ __launch_bounds__(256) void osc_stream_sums_kernel(const uint32_t* __restrict__ F, int fcount, uint32_t* __restrict__ sums, int nchunk,
+                                                              int lo_c, int hi_c, int hop, int n_lo, int n_hi) {
+    const int b = blockIdx.y;
+    const uint32_t s = tmpl_chunk_sum(F + (long long)b * fcount, lo_c, hi_c, hop, n_lo + blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, n_hi);
+    if (threadIdx.x == 0) sums[(long long)b * nchunk + blockIdx.x] = s;
+}
+
+// the chunk carry starts from phase_in[b], the phase at the start of the first emitted frame (NULL: 0, the utterance's first frame, by index);
+// the last chunk's last thread stores the phase after the last emitted sample in phase_out[b], another buffer than phase_in
+__global__ __launch_bounds__(256) void osc_stream_kernel(const uint32_t* __restrict__ F, int fcount, const uint32_t* __restrict__ sums, int nchunk,
+                                                         const uint32_t* __restrict__ phase_in, uint32_t* __restrict__ phase_out,
+                                                         float* __restrict__ out, long long out_stride, int lo_c, int hi_c, int hop, int n_lo,
+                                                         int n_hi, int kind, float amplitude) {
+    const int b = blockIdx.y;
+    uint32_t carry = threadIdx.x == 0 && phase_in ? phase_in[b] : 0u;
+    for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) carry += sums[(long long)b * nchunk + c];
+    tmpl_chunk_emit(F + (long long)b * fcount, lo_c, hi_c, hop, n_lo + blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, n_hi, n_hi, carry,
+                    out + (long long)b * out_stride, n_lo, kind, amplitude, (int)blockIdx.x == nchunk - 1 ? phase_out + b : nullptr);
 }
 
 // the lengths of the rows [row0, row0 + count) by value; host == NULL: every row has `whole`
@@ -445,7 +489,7 @@ FV_API fv_status fv_f0_forward(fv_f0* p, const float* d_x, int64_t x_row_stride,
     for (size_t i = 0; i < blocks.size(); ++i) {
         const int row0 = (int)i * kF0Rows, count = std::min(kF0Rows, batch - row0);
         hipLaunchKernelGGL(yin_f0_kernel, dim3((unsigned)T, count), dim3(pl.threads()), pl.lds_bytes(), s, d_x, (long long)x_row_stride,
-                           blocks[i], row0, d_f0, d_aperiodicity, (long long)out_row_stride, (int)T, pl);
+                           blocks[i], row0, d_f0, d_aperiodicity, (long long)out_row_stride, 0LL, 0LL, pl);
         FV_HIP_CHECK(hipGetLastError());
     }
     set_last_kernel("yin_f0_kernel");
@@ -524,5 +568,238 @@ FV_API fv_status fv_template_forward(fv_template* p, const float* d_f0, int64_t 
     set_last_kernel("f0_template_kernel");
     return FV_OK;
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Streams.  buf[cur] holds the samples (tracker) or F0 frames (oscillator) [N - H - prev_c, N) of every row; a push writes [N - H, N + c) into
+// buf[cur ^ 1] and runs on it, the flush runs on buf[cur] as it stands.
+// ---------------------------------------------------------------------------------------------
+struct fv_yin_stream : SampleStream {
+    fv_f0* p = nullptr;
+    int prev_c = 0;
+};
+
+struct fv_osc_stream : SampleStream {
+    fv_template* p = nullptr;
+    int prev_c = 0, pcur = 0;
+    uint32_t* aux = nullptr;   // one allocation: F (B, 2 + max_chunk) | sums (B, chunks) | phase[2] (B)
+    uint32_t *F = nullptr, *sums = nullptr, *phase[2] = {nullptr, nullptr};
+    ~fv_osc_stream() {
+        if (aux) (void)hipFree(aux);
+    }
+};
+
+static long long yin_ready(const YinPlan& pl, long long N) {
+    const long long need = pl.hop / 2 + pl.W / 2;
+    return N < need ? 0 : std::min(1 + (N - need) / pl.hop, N / pl.hop);
+}
+
+static long long yin_pending(const YinPlan& pl, long long N, long long E) {
+    return std::max(0LL, N - std::max(0LL, E * pl.hop + pl.hop / 2 - pl.W / 2));
+}
+
+static fv_status yin_stream_step(fv_yin_stream* st, const float* d_wave, int64_t row_stride, int32_t c, bool flush, float* d_f0, float* d_ap,
+                                 int64_t out_row_stride, int64_t* frames_out, void* stream) {
+    const char* fn = flush ? "fv_yin_stream_flush" : "fv_yin_stream_push";
+    if (frames_out) *frames_out = 0;
+    if (!st || !frames_out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    long long N2;
+    bool noop;
+    if (const fv_status rs = st->admit(fn, "fv_yin_stream_reset", d_wave, row_stride, c, flush, &N2, &noop)) return rs;
+    if (noop) return FV_OK;
+    const YinPlan& pl = st->p->plan;
+    const long long E2 = flush ? N2 / pl.hop : std::max(st->E, yin_ready(pl, N2));
+    const long long k = E2 - st->E;
+    if (k > 0 && (!d_f0 || !d_ap || out_row_stride < k)) {
+        set_error("%s: %s (this call emits %lld frames per row)", fn,
+                  !d_f0 ? "null d_f0" : (!d_ap ? "null d_aperiodicity" : "out_row_stride is shorter than the output"), k);
+        return FV_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const float* x = st->buf[st->cur];
+    long long origin = st->N - st->H - st->prev_c;
+    if (!flush) {
+        float* next = st->buf[st->cur ^ 1];
+        if (const fv_status rs = launch_sample_carry(st->buf[st->cur], next, d_wave, st->stride, row_stride, st->B, st->N, st->N - st->H, origin,
+                                                     (long long)st->H + c, s))
+            return rs;
+        x = next, origin = st->N - st->H;
+        st->prev_c = c;
+    }
+    if (k > 0) {
+        F0RowBlock rb;
+        for (int row0 = 0; row0 < st->B; row0 += kF0Rows) {
+            const int count = std::min(kF0Rows, st->B - row0);
+            for (int i = 0; i < kF0Rows; ++i) rb.len[i] = i < count ? (int)(N2 - origin) : 0;
+            hipLaunchKernelGGL(yin_f0_kernel, dim3((unsigned)k, count), dim3(pl.threads()), pl.lds_bytes(), s, x, st->stride, rb, row0, d_f0, d_ap,
+                               (long long)out_row_stride, origin, st->E, pl);
+            FV_HIP_CHECK(hipGetLastError());
+        }
+        set_last_kernel("yin_f0_kernel");
+    }
+    *frames_out = k;
+    st->commit(N2, E2, flush, !flush);
+    return FV_OK;
+}
+
+static fv_status osc_stream_step(fv_osc_stream* st, const float* d_f0, int64_t row_stride, int32_t c, bool flush, float* d_out,
+                                 int64_t out_row_stride, int64_t* samples_out, void* stream) {
+    const char* fn = flush ? "fv_osc_stream_flush" : "fv_osc_stream_push";
+    if (samples_out) *samples_out = 0;
+    if (!st || !samples_out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    long long T2;
+    bool noop;
+    if (const fv_status rs = st->admit(fn, "fv_osc_stream_reset", d_f0, row_stride, c, flush, &T2, &noop)) return rs;
+    if (noop) return FV_OK;
+    const fv_template_config& cfg = st->p->cfg;
+    const int hop = cfg.hop_length;
+    const long long E2 = flush ? T2 : std::max(st->E, T2 - 1);
+    const long long k = E2 - st->E;
+    if (k > 0 && (!d_out || out_row_stride < k * hop)) {
+        set_error("%s: %s (this call emits %lld samples per row)", fn, d_out ? "out_row_stride is shorter than the output" : "null output", k * hop);
+        return FV_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const float* x = st->buf[st->cur];
+    long long o = st->N - st->H - st->prev_c;   // the row's frame that column 0 of x holds
+    int fcount = st->H + st->prev_c;
+    if (!flush) {
+        float* next = st->buf[st->cur ^ 1];
+        if (const fv_status rs = launch_sample_carry(st->buf[st->cur], next, d_f0, st->stride, row_stride, st->B, st->N, st->N - st->H, o,
+                                                     (long long)st->H + c, s))
+            return rs;
+        x = next, o = st->N - st->H, fcount = st->H + c;
+        st->prev_c = c;
+    }
+    if (k > 0) {
+        F0RowBlock rb;
+        for (int row0 = 0; row0 < st->B; row0 += kF0Rows) {
+            const int count = std::min(kF0Rows, st->B - row0);
+            for (int i = 0; i < kF0Rows; ++i) rb.len[i] = i < count ? fcount : 0;
+            hipLaunchKernelGGL(f0_increment_kernel, dim3((unsigned)((fcount + 255) / 256), count), dim3(256), 0, s, x, st->stride, rb, row0, st->F,
+                               fcount, cfg.sample_rate);
+            FV_HIP_CHECK(hipGetLastError());
+        }
+        const int n_lo = (int)((st->E - o) * hop), n_hi = (int)((E2 - o) * hop);
+        const int nchunk = (n_hi - n_lo + kTmplChunk - 1) / kTmplChunk;
+        const int lo_c = o < 0 ? (int)-o : 0, hi_c = (int)(T2 - 1 - o);
+        hipLaunchKernelGGL(osc_stream_sums_kernel, dim3(nchunk, st->B), dim3(256), 0, s, st->F, fcount, st->sums, nchunk, lo_c, hi_c, hop, n_lo, n_hi);
+        FV_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(osc_stream_kernel, dim3(nchunk, st->B), dim3(256), 0, s, st->F, fcount, st->sums, nchunk,
+                           st->E > 0 ? st->phase[st->pcur] : nullptr, st->phase[st->pcur ^ 1], d_out, (long long)out_row_stride, lo_c, hi_c, hop, n_lo,
+                           n_hi, cfg.kind, cfg.amplitude);
+        FV_HIP_CHECK(hipGetLastError());
+        st->pcur ^= 1;
+        set_last_kernel("osc_stream_kernel");
+    }
+    *samples_out = k * hop;
+    st->commit(T2, E2, flush, !flush);
+    return FV_OK;
+}
+
+extern "C" {
+
+FV_API int64_t fv_yin_frames_ready(const fv_f0_config* cfg, int64_t N) {
+    YinPlan p;
+    if (make_yin_plan(cfg, "fv_yin_frames_ready", p)) return -1;
+    if (N < 0 || N > kSampleStreamMaxLen) {
+        set_error("fv_yin_frames_ready: N = %lld must lie in [0, 2^40]", (long long)N);
+        return -1;
+    }
+    return yin_ready(p, N);
+}
+
+FV_API fv_status fv_yin_stream_create(fv_f0* p, int32_t batch, int32_t max_chunk_samples, fv_yin_stream** out) {
+    if (!p || !out) {
+        set_error("fv_yin_stream_create: null argument");
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    std::unique_ptr<fv_yin_stream> st(new fv_yin_stream());
+    st->p = p;
+    // a frame not yet emitted starts less than H samples before N: W when hop <= W, half a hop more than half a frame otherwise
+    const int H = p->plan.W / 2 + std::max(p->plan.W / 2, (p->plan.hop + 1) / 2);
+    if (const fv_status rs = st->create("fv_yin_stream_create", batch, max_chunk_samples, H, ((long long)H + max_chunk_samples + 3) / 4 * 4))
+        return rs;
+    *out = st.release();
+    return FV_OK;
+}
+
+FV_API int64_t fv_yin_stream_pending_samples(const fv_yin_stream* s) { return s ? yin_pending(s->p->plan, s->N, s->E) : 0; }
+
+FV_API fv_status fv_yin_stream_push(fv_yin_stream* s, const float* d_wave, int64_t row_stride, int32_t c, float* d_f0, float* d_aperiodicity,
+                                    int64_t out_row_stride, int64_t* frames_out, void* stream) {
+    return yin_stream_step(s, d_wave, row_stride, c, false, d_f0, d_aperiodicity, out_row_stride, frames_out, stream);
+}
+
+FV_API fv_status fv_yin_stream_flush(fv_yin_stream* s, float* d_f0, float* d_aperiodicity, int64_t out_row_stride, int64_t* frames_out,
+                                     void* stream) {
+    return yin_stream_step(s, nullptr, 0, 0, true, d_f0, d_aperiodicity, out_row_stride, frames_out, stream);
+}
+
+FV_API fv_status fv_yin_stream_reset(fv_yin_stream* s) {
+    if (!s) {
+        set_error("fv_yin_stream_reset: null stream");
+        return FV_ERR_INVALID;
+    }
+    s->reset();
+    return FV_OK;
+}
+
+FV_API void fv_yin_stream_destroy(fv_yin_stream* s) { delete s; }
+
+FV_API fv_status fv_osc_stream_create(fv_template* p, int32_t batch, int32_t max_chunk_frames, fv_osc_stream** out) {
+    const char* fn = "fv_osc_stream_create";
+    if (!p || !out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    const int hop = p->cfg.hop_length;
+    if (max_chunk_frames >= 1 && (2LL + max_chunk_frames) * hop > kF0MaxLen) {
+        set_error("%s: max_chunk_frames = %d frames of %d samples, with the two carried frames, pass 2^30 samples", fn, max_chunk_frames, hop);
+        return FV_ERR_INVALID;
+    }
+    std::unique_ptr<fv_osc_stream> st(new fv_osc_stream());
+    st->p = p;
+    const long long stride = (2LL + max_chunk_frames + 3) / 4 * 4;
+    if (const fv_status rs = st->create(fn, batch, max_chunk_frames, 2, stride)) return rs;
+    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+    const size_t nchunk = (size_t)(((long long)max_chunk_frames * hop + kTmplChunk - 1) / kTmplChunk);
+    const size_t nf = up((size_t)batch * (size_t)(2 + max_chunk_frames)), ns = up((size_t)batch * nchunk), np = up((size_t)batch);
+    FV_HIP_CHECK(hipMalloc((void**)&st->aux, (nf + ns + 2 * np) * sizeof(uint32_t)));
+    st->F = st->aux, st->sums = st->F + nf, st->phase[0] = st->sums + ns, st->phase[1] = st->phase[0] + np;
+    *out = st.release();
+    return FV_OK;
+}
+
+FV_API int64_t fv_osc_stream_pending_frames(const fv_osc_stream* s) { return s ? s->N - s->E : 0; }
+
+FV_API fv_status fv_osc_stream_push(fv_osc_stream* s, const float* d_f0, int64_t row_stride, int32_t c, float* d_out, int64_t out_row_stride,
+                                    int64_t* samples_out, void* stream) {
+    return osc_stream_step(s, d_f0, row_stride, c, false, d_out, out_row_stride, samples_out, stream);
+}
+
+FV_API fv_status fv_osc_stream_flush(fv_osc_stream* s, float* d_out, int64_t out_row_stride, int64_t* samples_out, void* stream) {
+    return osc_stream_step(s, nullptr, 0, 0, true, d_out, out_row_stride, samples_out, stream);
+}
+
+FV_API fv_status fv_osc_stream_reset(fv_osc_stream* s) {
+    if (!s) {
+        set_error("fv_osc_stream_reset: null stream");
+        return FV_ERR_INVALID;
+    }
+    s->reset();
+    return FV_OK;
+}
+
+FV_API void fv_osc_stream_destroy(fv_osc_stream* s) { delete s; }
 
 }  // extern "C"

@@ -16,6 +16,11 @@ modules.
 
 The phase is an unsigned 32-bit count of turns / 2^32, as the pitch shift's accumulator is (``pitch_shift.py``): it wraps where a float grows,
 so a long file keeps its pitch.  No CPU fallback.
+
+Streaming (``fv_yin_stream_*`` / ``fv_osc_stream_*``): ``YinF0.stream`` takes samples chunk by chunk and emits frame ``t`` once none of its
+samples is at or after the ``N`` received, ``frames_ready(N)``; ``PitchTemplate.stream`` takes F0 frames and emits the ``hop`` samples of frame
+``t`` once frame ``t + 1`` has arrived; ``TemplateStream`` is the first into the second.  Concatenated, every stream's output has the bits of
+the whole-row call.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._handle import _DeviceHandles
+from ._handle import _DeviceHandles, _Handle, _emit
 from ._lib import check
 from .resample import _require_cuda, _rows
 
@@ -59,6 +64,14 @@ def plan(sample_rate: int, frame_length: int = 2048, hop_length: int = 512, fmin
         raise ValueError(f"frame_length ({frame_length}) leaves an integration window of {Wi} samples, less than half the longest lag "
                          f"({tau_max}, from fmin = {fmin}); raise frame_length or fmin")
     return tau_min, tau_max, Wi
+
+
+def frames_ready(N: int, frame_length: int, hop_length: int) -> int:
+    """Frames of the tracker that read no sample at or after ``N`` (``fv_yin_frames_ready``): frame ``t`` reads
+    ``[t hop + hop // 2 - W // 2, ... + W)``; never above ``N // hop``."""
+    N, W, hop = int(N), int(frame_length), int(hop_length)
+    need = hop // 2 + W // 2
+    return 0 if N < need else min(1 + (N - need) // hop, N // hop)
 
 
 def _host_counts(counts, rows: int, what: str):
@@ -121,6 +134,9 @@ class YinF0(nn.Module):
             raise ValueError("YinF0.forward_ragged: expected a waveform of shape (B, Lmax)")
         return self._run(wave, lengths, "YinF0.forward_ragged")
 
+    def stream(self, batch: int, max_chunk_samples: int) -> "YinF0Stream":
+        return YinF0Stream(self, batch, max_chunk_samples)
+
     def close(self) -> None:
         self._handles.close()
 
@@ -175,6 +191,9 @@ class PitchTemplate(nn.Module):
             raise ValueError("PitchTemplate.forward_ragged: expected f0 of shape (B, Tmax)")
         return self._run(f0, frames, "PitchTemplate.forward_ragged")
 
+    def stream(self, batch: int, max_chunk_frames: int) -> "PitchTemplateStream":
+        return PitchTemplateStream(self, batch, max_chunk_frames)
+
     def close(self) -> None:
         self._handles.close()
 
@@ -188,3 +207,198 @@ def template_from_audio(wave: torch.Tensor, sample_rate: int, hop_length: int, f
     made from."""
     f0, _ = YinF0(sample_rate, hop_length, frame_length, fmin, fmax, threshold)(wave)
     return PitchTemplate(sample_rate, hop_length, kind, amplitude)(f0)
+
+
+class _F0Stream(_Handle):
+    """What the two streams share: the handle's creation on one device, the chunk check, the host counters ``_N`` received / ``_E`` emitted."""
+    _create = ""
+
+    def __init__(self, parent, batch: int, max_chunk: int, device=None):
+        self._parent, self._lib = parent, _lib.lib()
+        self.batch, self.max_chunk = int(batch), int(max_chunk)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(getattr(self._lib, self._create)(parent._handle(self.device), self.batch, self.max_chunk, ctypes.byref(self._h)))
+        self._N = self._E = 0
+        self._flushed = False
+
+    def _chunk(self, chunk: torch.Tensor, what: str) -> torch.Tensor:
+        self._check_open()
+        _require_cuda(chunk, what)
+        if chunk.dim() != 2 or chunk.shape[0] != self.batch:
+            raise ValueError(f"{what}: expected a chunk of shape ({self.batch}, c), got {tuple(chunk.shape)}")
+        return _rows(chunk)
+
+    def _moved(self, N2: int, E2: int, flush: bool) -> None:
+        self._N, self._E = N2, E2
+        self._flushed = self._flushed or flush
+
+
+class YinF0Stream(_F0Stream):
+    """``batch`` rows tracked chunk by chunk, in lockstep (``fv_yin_stream``): ``push`` a ``(batch, c)`` chunk of samples,
+    ``c <= max_chunk_samples``, and get ``(f0 (batch, k), aperiodicity (batch, k))`` for the frames that read no later sample (``k`` may be 0);
+    ``flush`` emits the rest against the rows' true end and then refuses pushes until ``reset``; ``close`` frees the stream (also a context
+    manager).  A frame leaves ``W / 2 + hop / 2 - hop`` samples after its own hop has arrived.  The concatenated values have the bits of
+    ``YinF0.forward`` on the whole rows.  Work is enqueued on torch's current stream; calls must be ordered."""
+    _destroy, _create = "fv_yin_stream_destroy", "fv_yin_stream_create"
+    _closed = "this F0 stream is closed: create a new one"
+
+    def __init__(self, yin: YinF0, batch: int, max_chunk_samples: int, device=None):
+        super().__init__(yin, batch, max_chunk_samples, device)
+        self.frame_length, self.hop_length = yin.frame_length, yin.hop_length
+
+    # -- counters (host-side: reading them never synchronises) --
+    @property
+    def received_samples(self) -> int:
+        return self._N
+
+    @property
+    def emitted_frames(self) -> int:
+        return self._E
+
+    @property
+    def pending_samples(self) -> int:
+        """``N - max(0, E hop + hop // 2 - W // 2)`` as the library counts it (fv_yin_stream_pending_samples)."""
+        self._check_open()
+        return int(self._lib.fv_yin_stream_pending_samples(self._h))
+
+    def push(self, chunk: torch.Tensor):
+        return self._call(self._chunk(chunk, "YinF0Stream.push"), int(chunk.shape[1]), flush=False)
+
+    def flush(self):
+        self._check_open()
+        return self._call(None, 0, flush=True)
+
+    def _call(self, x, c: int, flush: bool):
+        N2 = self._N + c
+        ok = flush or c <= self.max_chunk                   # a refused push emits nothing; the library says why
+        E2 = N2 // self.hop_length if flush else max(self._E, frames_ready(N2, self.frame_length, self.hop_length))
+        k = E2 - self._E if ok and not self._flushed else 0
+
+        def enqueue(optr, got) -> None:
+            aptr = None if optr is None else optr + 4 * self.batch * k
+            with torch.cuda.device(self.device):
+                run = torch.cuda.current_stream()
+                s = int(run.cuda_stream)
+                check(self._lib.fv_yin_stream_flush(self._h, optr, aptr, max(k, 1), got, s) if flush else
+                      self._lib.fv_yin_stream_push(self._h, x.data_ptr(), x.stride(0) if self.batch > 1 else max(c, 1), c, optr, aptr,
+                                                   max(k, 1), got, s))
+                self._record_done(run)      # the carried buffers are in use on the device until then
+        out = _emit((2, self.batch, k), k, self.device, enqueue, "F0 stream emitted {got} frames where the emission rule says {k}")
+        self._moved(N2, E2, flush)
+        return out[0], out[1]
+
+    def reset(self) -> None:
+        self._check_open()
+        check(self._lib.fv_yin_stream_reset(self._h))
+        self._N = self._E = 0
+        self._flushed = False
+
+
+class PitchTemplateStream(_F0Stream):
+    """``batch`` rows of the oscillator chunk by chunk, in lockstep (``fv_osc_stream``): ``push`` a ``(batch, c)`` chunk of F0 frames,
+    ``c <= max_chunk_frames``, and get the ``(batch, 1, k hop)`` samples of the frames whose next frame has arrived (``k`` may be 0); ``flush``
+    emits the last frame and then refuses pushes until ``reset``.  Latency: one F0 frame.  The concatenated samples have the bits of
+    ``PitchTemplate.forward`` on the whole rows: the phase carried between calls is a wrapping integer."""
+    _destroy, _create = "fv_osc_stream_destroy", "fv_osc_stream_create"
+    _closed = "this pitch template stream is closed: create a new one"
+
+    def __init__(self, template: PitchTemplate, batch: int, max_chunk_frames: int, device=None):
+        super().__init__(template, batch, max_chunk_frames, device)
+        self.hop_length = template.hop_length
+
+    @property
+    def received_frames(self) -> int:
+        return self._N
+
+    @property
+    def emitted_frames(self) -> int:
+        return self._E
+
+    @property
+    def pending_frames(self) -> int:
+        """``Tn - E`` as the library counts it (fv_osc_stream_pending_frames)."""
+        self._check_open()
+        return int(self._lib.fv_osc_stream_pending_frames(self._h))
+
+    def push(self, f0: torch.Tensor) -> torch.Tensor:
+        return self._call(self._chunk(f0, "PitchTemplateStream.push"), int(f0.shape[1]), flush=False)
+
+    def flush(self) -> torch.Tensor:
+        self._check_open()
+        return self._call(None, 0, flush=True)
+
+    def _call(self, x, c: int, flush: bool) -> torch.Tensor:
+        T2 = self._N + c
+        ok = flush or c <= self.max_chunk
+        E2 = T2 if flush else max(self._E, T2 - 1)
+        k = (E2 - self._E) * self.hop_length if ok and not self._flushed else 0
+
+        def enqueue(optr, got) -> None:
+            with torch.cuda.device(self.device):
+                run = torch.cuda.current_stream()
+                s = int(run.cuda_stream)
+                check(self._lib.fv_osc_stream_flush(self._h, optr, max(k, 1), got, s) if flush else
+                      self._lib.fv_osc_stream_push(self._h, x.data_ptr(), x.stride(0) if self.batch > 1 else max(c, 1), c, optr, max(k, 1), got, s))
+                self._record_done(run)
+        out = _emit((self.batch, 1, k), k, self.device, enqueue, "pitch template stream emitted {got} samples where the emission rule says {k}")
+        self._moved(T2, E2, flush)
+        return out
+
+    def reset(self) -> None:
+        self._check_open()
+        check(self._lib.fv_osc_stream_reset(self._h))
+        self._N = self._E = 0
+        self._flushed = False
+
+
+class TemplateStream:
+    """Audio in, template samples out: a ``YinF0Stream`` into a ``PitchTemplateStream``.  ``push((batch, c))``, ``c <= max_chunk_samples``,
+    returns the ``(batch, 1, k hop)`` template samples that are final; ``flush()`` flushes both, tracker first; concatenated they have the
+    bits of ``template_from_audio`` on the whole rows.  Latency: the tracker's ``W / 2 + hop / 2 - hop`` samples plus one frame."""
+
+    def __init__(self, sample_rate: int, hop_length: int, batch: int, max_chunk_samples: int, frame_length: int = 2048, fmin: float = 40.0,
+                 fmax: float = 1100.0, threshold: float = 0.1, kind: str = "sine", amplitude: float = 1.0):
+        self.yin = YinF0(sample_rate, hop_length, frame_length, fmin, fmax, threshold)
+        self.oscillator = PitchTemplate(sample_rate, hop_length, kind, amplitude)
+        self.batch, self.max_chunk_samples, self.hop_length = int(batch), int(max_chunk_samples), int(hop_length)
+        # the most frames the tracker emits at once: c // hop + 1 from a push, the frames still waiting for lookahead from the flush
+        self.max_chunk_frames = max(self.max_chunk_samples, self.yin.frame_length // 2 + self.hop_length // 2) // self.hop_length + 1
+        self.tracker = self.yin.stream(batch, max_chunk_samples)
+        try:
+            self.template = self.oscillator.stream(batch, self.max_chunk_frames)
+        except Exception:
+            self.tracker.close()
+            raise
+
+    @property
+    def received_samples(self) -> int:
+        return self.tracker.received_samples
+
+    @property
+    def emitted_samples(self) -> int:
+        return self.template.emitted_frames * self.hop_length
+
+    def push(self, chunk: torch.Tensor) -> torch.Tensor:
+        return self.template.push(self.tracker.push(chunk)[0])
+
+    def flush(self) -> torch.Tensor:
+        head = self.template.push(self.tracker.flush()[0])
+        return torch.cat([head, self.template.flush()], dim=-1)
+
+    def reset(self) -> None:
+        self.tracker.reset()
+        self.template.reset()
+
+    def close(self) -> None:
+        self.tracker.close()
+        self.template.close()
+        self.yin.close()
+        self.oscillator.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()

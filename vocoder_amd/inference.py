@@ -200,12 +200,54 @@ class _Cascade:
             self.feed(i + 1, st.flush())
 
 
+class _TemplateJoin:
+    """The stage of a wav -> wav cascade in front of a generator that takes a pitch template: the model-rate samples go into the log-mel stream
+    and into a ``TemplateStream``, whatever one branch has emitted ahead of the other waits here (the two latencies differ by a fixed number of
+    samples, so the wait is bounded), and every ``n`` frames that both have emitted go into the generator stream with their ``n * hop``
+    template samples.  ``push`` / ``flush`` return the generator's audio ``(B, 1, k)``."""
+
+    def __init__(self, mel_stream, template_stream, gen_stream, chunk_frames: int, hop: int):
+        self.mel_stream, self.template_stream, self.gen_stream = mel_stream, template_stream, gen_stream
+        self.chunk_frames, self.hop = int(chunk_frames), int(hop)
+        self.mel = self.template = None           # emitted by one branch, not yet pushed into the generator
+        self.mel_frames = self.template_frames = 0      # emitted in all
+
+    def _take(self, mel: torch.Tensor, template: torch.Tensor) -> None:
+        self.mel_frames += int(mel.shape[-1])
+        self.template_frames += int(template.shape[-1]) // self.hop
+        self.mel = mel if self.mel is None else torch.cat([self.mel, mel], dim=-1)
+        self.template = template if self.template is None else torch.cat([self.template, template], dim=-1)
+
+    def _drain(self) -> list:
+        n = min(int(self.mel.shape[-1]), int(self.template.shape[-1]) // self.hop)
+        outs = []
+        for i in range(0, n, self.chunk_frames):
+            j = min(i + self.chunk_frames, n)
+            outs.append(self.gen_stream.push(self.mel[..., i:j], self.template[..., i * self.hop:j * self.hop]))
+        self.mel, self.template = self.mel[..., n:], self.template[..., n * self.hop:]
+        return outs
+
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        self._take(self.mel_stream.push(x), self.template_stream.push(x))
+        outs = self._drain()
+        return torch.cat(outs, dim=-1) if outs else x.new_zeros((x.shape[0], 1, 0))
+
+    def flush(self) -> torch.Tensor:
+        self._take(self.mel_stream.flush(), self.template_stream.flush())
+        if self.mel_frames != self.template_frames:
+            raise ValueError(f"the log-mel front-end made {self.mel_frames} frames and the pitch template {self.template_frames} frames of "
+                             f"{self.hop} samples: the generator takes one template frame per mel frame")
+        return torch.cat(self._drain() + [self.gen_stream.flush()], dim=-1)
+
+
 @torch.no_grad()
-def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int, resample: nn.Module | None = None):
+def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int, resample: nn.Module | None = None,
+                     template: torch.Tensor | None = None):
     """Pushes ``mel`` (B, num_mels, T) through ``generator.stream()`` ``chunk_frames`` frames at a time, then flushes (exact mode: the lookahead
     and the left context are the generator's reach).  Returns (waveform (B, 1, T * hop), seconds to the first non-empty output, seconds per push).
     ``resample`` (a ``vocoder_amd.resample.Resample``): each push's audio goes through a resample stream on the device, and the waveform comes
-    back at its ``new_freq``."""
+    back at its ``new_freq``.  ``template`` ``(B, 1, T * hop)``: the whole pitch template of a ``use_template`` generator (``PitchTemplate`` on the
+    F0 of the mel's frames), sliced per push."""
     if not hasattr(generator, "stream"):
         raise ValueError(f"--chunk-frames: {type(generator).__name__} has no stream(); HiFiGAN / BigVGAN generators stream")
     B, _, T = mel.shape
@@ -214,6 +256,17 @@ def stream_synthesis(generator: nn.Module, mel: torch.Tensor, chunk_frames: int,
     with ExitStack() as stack:
         st = stack.enter_context(generator.stream(batch=B, max_chunk_frames=chunk_frames))
         stages = [_Stage(st, chunk_frames)]
+        if template is not None:
+            if tuple(template.shape) != (B, 1, T * st.hop):
+                raise ValueError(f"stream_synthesis: a template of shape {tuple(template.shape)} for a mel of {T} frames; expected "
+                                 f"{(B, 1, T * st.hop)}")
+            done = [0]
+
+            def push_with_template(m: torch.Tensor) -> torch.Tensor:
+                f, n = done[0], int(m.shape[-1])
+                done[0] = f + n
+                return st.push(m, template[:, :, f * st.hop:(f + n) * st.hop])
+            stages[0].push = push_with_template
         if resample is not None:
             if st.out_channels != 1:
                 raise ValueError(f"--output-rate: the generator emits {st.out_channels} channels; the resample stream takes waveforms (B, 1, T)")
@@ -240,14 +293,17 @@ def _pad_samples(hop: int, L: int) -> int:
 
 @torch.no_grad()
 def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chunk_frames: int, to_model: nn.Module | None = None,
-                         to_out: nn.Module | None = None, sink=None):
+                         to_out: nn.Module | None = None, sink=None, template: dict | None = None):
     """wav -> wav chunk by chunk: [resample stream ->] log-mel stream -> generator stream [-> resample stream].  ``chunks`` yields ``(B, c)``
     tensors of input samples (``c <= chunk_frames * hop``), ``total_samples`` is their sum (the zero padding of the whole-file branch,
     test.py:64-68, depends on it); ``to_model`` / ``to_out``: ``Resample`` modules into and out of the model's rate.  Every stage's output is
     pushed into the next one as it comes (its emit count sizes that push), and at the end the flushes cascade from the first stage to the
     last.  Each piece of finished audio ``(B, 1, k)`` goes to ``sink`` (default: collected).  Returns (the collected waveform or None, stats):
     ``first_audio_s``, ``push_s`` (seconds per input chunk), ``reads`` and ``reads_before_first_audio`` (input chunks consumed in all / when
-    the first audio left)."""
+    the first audio left).  ``template``: the keyword arguments of a ``vocoder_amd.f0.TemplateStream`` after its sizes (``frame_length``,
+    ``fmin``, ``fmax``, ``threshold``, ``kind``, ``amplitude``) for a generator that takes a pitch template: the model-rate samples, the zero
+    padding included, go into the log-mel stream and into the template stream, and the generator stream gets the frames both have emitted
+    (``_TemplateJoin``); a ValueError names the two frame totals if they differ at the end."""
     gen, front, hop = model.generator, model.mel_transform, model.hop_length
     if front is None or not hasattr(front, "stream"):
         raise ValueError("--chunk-frames on a .wav needs the GPU log-mel front-end (build_model attaches one)")
@@ -278,11 +334,18 @@ def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chun
         stages = []
         if to_model is not None:
             stages.append(_Stage(stack.enter_context(to_model.stream(batch=B, max_chunk=limit)), limit))
-        mel_stage = _Stage(stack.enter_context(front.stream(batch=B, max_chunk_samples=limit)), limit)
+        mel_stream = stack.enter_context(front.stream(batch=B, max_chunk_samples=limit))
         gst = stack.enter_context(gen.stream(batch=B, max_chunk_frames=chunk_frames))
         if gst.out_channels != 1:
             raise ValueError(f"the generator emits {gst.out_channels} channels; wav -> wav streaming takes waveforms (B, 1, T)")
-        stages += [mel_stage, _Stage(gst, chunk_frames)]
+        if template is None:
+            mel_stage = _Stage(mel_stream, limit)
+            stages += [mel_stage, _Stage(gst, chunk_frames)]
+        else:
+            from .f0 import TemplateStream
+            tst = stack.enter_context(TemplateStream(model.sampling_rate, hop, B, limit, **template))
+            mel_stage = _Stage(_TemplateJoin(mel_stream, tst, gst, chunk_frames, hop), limit)      # (the zero padding goes into both branches)
+            stages.append(mel_stage)
         if to_out is not None:
             stages.append(_Stage(stack.enter_context(to_out.stream(batch=B, max_chunk=limit)), limit, audio=True))
         cascade = _Cascade(stages, emit)
