@@ -652,7 +652,8 @@ FV_API fv_status fv_global_resample_create(const fv_resample_config* cfg, fv_res
  * Synthesis: irfft(S[:, s]) times the window, overlap-added, divided by the overlap-added window^2 where that is positive, n_fft / 2 samples
  * cropped from the front, cut or zero-padded to Ls = (2 L o + n) / (2 n) (round(L o / n), halves up).
  * Resample: orig_freq -> sr with fv_resample_design's filter (table in global memory): ceil(n Ls / o) samples, cut or zero-padded to L.
- * Not built: a streaming form, ragged rows in one call, a chunk-parallel scan for very long single rows. */
+ * The streaming form (fv_pv_stream_*) follows the whole-row entries.  Not built: ragged rows in one call, a chunk-parallel scan for very long
+ * single rows, per-session (non-lockstep) shift streams for fv_pool_step, the command line's --pitch-shift with --chunk-frames. */
 typedef struct fv_pitch_shift_config {
     int32_t sample_rate;           /* sr of test.py:61-62 */
     double n_steps;                /* cfg.pitch_shift (configs/train.yaml), in steps of an octave / bins_per_octave */
@@ -690,6 +691,61 @@ FV_API fv_status fv_pitch_shift_stretch(fv_pitch_shift* p, const float* d_x, int
  * d_y must not overlap d_x (FV_ERR_INVALID).  Asynchronous on `stream`. */
 FV_API fv_status fv_pitch_shift_forward(fv_pitch_shift* p, const float* d_x, int64_t x_row_stride, float* d_y, int64_t y_row_stride,
                                         int32_t batch, int64_t L, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* -------- streaming pitch shift: test.py:61-62 chunk by chunk (no reference counterpart: librosa shifts whole files).  `batch` rows advance in
+ *          lockstep, as in fv_resample_stream_*.  (Named fv_pv_*, outside the fv_pitch_shift_ prefix: that family's list of entries is pinned
+ *          by its host test.)  --------
+ *
+ * The rule, in integers (F = n_fft, h = hop_length, rate n / o, N samples received per row):
+ *   A(N) = 0 if N < F / 2, else (N - F / 2) / h + 1        analysis frames that read no sample at or after N (frame f reads [f h - F/2, f h + F/2))
+ *   S(A) = 0 if A < 2, else ceil((A - 1) o / n)            stretched frames whose columns j = floor(s n / o) and j + 1 are both analysed
+ *   Y    = min(max(0, S h - F / 2), Ls(N))                 stretched samples under which every covering frame exists; Ls(N) = (2 N o + n) / (2 n)
+ *   E    = min(M(Y), N)                                    M: what fv_resample_stream_push has emitted after Y input samples (orig_freq -> sr)
+ * A push sets N += c and emits the outputs [E, E(N)).  The flush, with L = N now known, analyses the frames [A, T) against zeros, takes the
+ * columns T and T + 1 as zero, synthesises the frames [S, T'), emits the stretched samples up to Ls(L), flushes the resampler, cuts at
+ * min(ceil(n Ls / o), L) and writes zeros up to L: after it E = L exactly.  Pushes are then refused (FV_ERR_STATE) until fv_pv_stream_reset.  A
+ * flush at N = 0 emits nothing.  A refused call changes nothing.  The min with Ls(N) keeps a push from emitting a stretched sample that the cut
+ * to Ls(L) would drop; it binds only when hop_length == n_fft.  The min with N never binds for lowpass_filter_width >= 1 (a push that would need
+ * it is refused as an internal error, before anything is enqueued).  orig_freq == sr: a push emits its own c samples bit for bit, the flush nothing.
+ * Latency: N - E is about F / 2 (the analysis frame's centre) + h (column j + 1) + (F / 2 + the resampler's half band, lowpass_filter_width *
+ * o / (min(o, n) rolloff) stretched samples) * n / o input samples — 2460 samples (56 ms) at 44100 Hz / 2048 / 512 and n_steps = 3, 2910
+ * (66 ms) at n_steps = -4; N - E <= F / 2 + h + ceil((F / 2 + D) n / o) with D = max_p(first[p] + count[p] - width - p o / n) of the resampler's
+ * design.  The counts are host arithmetic (vocoder_amd.pitch_shift.stream_ready): no call synchronises.
+ * Bits: the stream enqueues its two DFT convs in batch-invariant mode (every column one fixed-order sum, as fv_logmel_stream_* does), the scan
+ * resumes from a carried uint32 total, the overlap-add sums a sample's frames in the whole-row order, and the resampler's stream is
+ * bit-identical to its rows.  So the concatenated output of any chunking is bit-identical to fv_pitch_shift_forward over the whole rows after
+ * fv_pv_set_batch_invariant(p, 1), and within the pitch shift's parity bar of it otherwise (the whole-row call may then pick split-K convs). */
+typedef struct fv_pv_stream fv_pv_stream;
+
+/* Pure host (no GPU): A(N), S(A(N)) and Y of the rule above for test.py:61-62's shift taken chunk by chunk.  NULL outputs are skipped;
+ * FV_ERR_INVALID names the offending field, N must lie in [0, 2^30]. */
+FV_API fv_status fv_pv_stream_ready(const fv_pitch_shift_config* cfg, int64_t N, int64_t* frames, int64_t* stretched_frames,
+                                    int64_t* stretched_samples);
+/* 1: fv_pitch_shift_stretch / fv_pitch_shift_forward (test.py:61-62) enqueue their two DFT convs in batch-invariant mode, as the stream always
+ * does — the mode in which whole rows and streams agree bit for bit.  0 (the default): those calls keep the kernels and the bits they had. */
+FV_API fv_status fv_pv_set_batch_invariant(fv_pitch_shift* p, int32_t enable);
+/* All of the stream's device state is allocated here (test.py:61-62 keeps none) and freed by fv_pv_stream_destroy, every carry as a pair of
+ * buffers used in turn so that no launch reads and writes one buffer: the last n_fft samples (batch, n_fft); |D| and Theta of the last analysed
+ * column and the phase total Phi as uint32, (batch, n_fft / 2 + 1) each; the last n_fft / hop synthesised frames (batch, n_fft, n_fft / hop) —
+ * one more than the overlap needs, for the pushes at which Ls(N) binds; and an fv_resample_stream on the shifter's own resampler.
+ * max_chunk: the largest c of one push. */
+FV_API fv_status fv_pv_stream_create(fv_pitch_shift* p, int32_t batch, int32_t max_chunk, fv_pv_stream** out);
+/* Bytes of device scratch every push / flush of the stream needs (256-byte aligned; test.py:61-62 allocates per call); 0 for NULL. */
+FV_API size_t fv_pv_stream_workspace_bytes(const fv_pv_stream* s);
+/* N - E: the samples received and not yet emitted (what test.py:61-62 would still hold of the file); the flush emits exactly these. */
+FV_API int64_t fv_pv_stream_pending(const fv_pv_stream* s);
+/* d_x: (batch, c) with row stride x_row_stride, c <= max_chunk (else FV_ERR_INVALID) — the next samples of test.py:61-62's gt_y; d_y:
+ * (batch, k) with row stride y_row_stride, k = E(N + c) - E known before the call and possibly 0, then d_y may be NULL.  *emitted receives k.
+ * c = 0 is a no-op.  Asynchronous on `stream`; calls on one stream object must be ordered. */
+FV_API fv_status fv_pv_stream_push(fv_pv_stream* s, const float* d_x, int64_t x_row_stride, int32_t c, float* d_y, int64_t y_row_stride,
+                                   int64_t* emitted, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Emits the outputs [E, N): the end of test.py:61-62's file, zeros where the resampled row is shorter than the input. */
+FV_API fv_status fv_pv_stream_flush(fv_pv_stream* s, float* d_y, int64_t y_row_stride, int64_t* emitted, void* d_workspace,
+                                    size_t workspace_bytes, void* stream);
+/* N = E = 0 for the next utterance (the next file of test.py:61-62); the buffers are kept. */
+FV_API fv_status fv_pv_stream_reset(fv_pv_stream* s);
+/* Call it before fv_pitch_shift_destroy of its shifter, once the stream's work has finished (test.py:61-62 has nothing to free). */
+FV_API void fv_pv_stream_destroy(fv_pv_stream* s);
 
 /* -------- pitch template: the `template (B, 1, T * hop)` that refinegan.py:287 / hifigan.py:226 take next to the mel.  The reference does not
  *          make one: its users bring an F0 track from a CPU tracker (pyworld, parselmouth, librosa.yin) and synthesise the template from it.
@@ -787,7 +843,7 @@ FV_API fv_status fv_template_forward(fv_template* p, const float* d_f0, int64_t 
  * bit-identical to fv_template_forward over the whole rows.
  *
  * Every call validates everything before it enqueues anything, enqueues eagerly on `stream` and never synchronises; a refused call changes
- * nothing.  Not built: per-session (non-lockstep) template streams for fv_pool_step, a streaming RefineGAN, a streaming pitch shift. */
+ * nothing.  Not built: per-session (non-lockstep) template streams for fv_pool_step, a streaming RefineGAN. */
 typedef struct fv_yin_stream fv_yin_stream;
 typedef struct fv_osc_stream fv_osc_stream;
 

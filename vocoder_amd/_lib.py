@@ -56,6 +56,8 @@ EXPORTS = (
     "fv_global_resample_create",
     "fv_pitch_shift_plan", "fv_pitch_shift_lengths", "fv_pitch_shift_create", "fv_pitch_shift_destroy", "fv_pitch_shift_workspace_bytes",
     "fv_pitch_shift_stretch", "fv_pitch_shift_forward",
+    "fv_pv_stream_ready", "fv_pv_set_batch_invariant", "fv_pv_stream_create", "fv_pv_stream_workspace_bytes", "fv_pv_stream_pending",
+    "fv_pv_stream_push", "fv_pv_stream_flush", "fv_pv_stream_reset", "fv_pv_stream_destroy",
     "fv_spec_distance_tile", "fv_spec_distance_workspace_bytes", "fv_spec_distance",
     "fv_f0_plan", "fv_f0_create", "fv_f0_destroy", "fv_f0_workspace_bytes", "fv_f0_forward",
     "fv_template_create", "fv_template_destroy", "fv_template_workspace_bytes", "fv_template_forward",
@@ -347,6 +349,24 @@ def lib() -> ctypes.CDLL:
     L.fv_pitch_shift_stretch.restype = _i32
     L.fv_pitch_shift_forward.argtypes = [vp, vp, i64, vp, i64, _i32, i64, vp, ctypes.c_size_t, vp]
     L.fv_pitch_shift_forward.restype = _i32
+    L.fv_pv_stream_ready.argtypes = [pcp, i64, i64p, i64p, i64p]
+    L.fv_pv_stream_ready.restype = _i32
+    L.fv_pv_set_batch_invariant.argtypes = [vp, _i32]
+    L.fv_pv_set_batch_invariant.restype = _i32
+    L.fv_pv_stream_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_pv_stream_create.restype = _i32
+    L.fv_pv_stream_workspace_bytes.argtypes = [vp]
+    L.fv_pv_stream_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_pv_stream_pending.argtypes = [vp]
+    L.fv_pv_stream_pending.restype = i64
+    L.fv_pv_stream_push.argtypes = [vp, vp, i64, _i32, vp, i64, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_pv_stream_push.restype = _i32
+    L.fv_pv_stream_flush.argtypes = [vp, vp, i64, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_pv_stream_flush.restype = _i32
+    L.fv_pv_stream_reset.argtypes = [vp]
+    L.fv_pv_stream_reset.restype = _i32
+    L.fv_pv_stream_destroy.argtypes = [vp]
+    L.fv_pv_stream_destroy.restype = None
     L.fv_spec_distance_tile.argtypes = []
     L.fv_spec_distance_tile.restype = _i32
     L.fv_spec_distance_workspace_bytes.argtypes = [_i32, i64]

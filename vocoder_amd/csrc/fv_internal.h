@@ -448,6 +448,9 @@ std::vector<float> istft_basis(const std::vector<float>& win, int N);
 // resample.hip: the outputs [0, m_end) of `batch` rows of `len` samples through r's kernel, unchecked (pitch_shift.hip)
 fv_status resample_rows(const fv_resample* r, const char* fn, const float* x, long long x_stride, long long len, float* y, long long y_stride,
                         int batch, long long m_end, hipStream_t s);
+// resample.hip: what a stream on r has emitted once N input samples have arrived (fv_resample_stream_push's rule), and Kp, the longest band
+long long resample_emit_count(const fv_resample* r, long long N);
+int resample_band_taps(const fv_resample* r);
 
 // RefineGAN glue (small_kernels.hip): linear interpolation (nn.Upsample(mode="linear")) with optional leaky_relu, written into
 // a channel slice of a wider tensor; channel-slice copy; AdaIN with caller-supplied noise

@@ -11,12 +11,21 @@
 //   istft_ola_kernel       overlap-add, envelope, crop n_fft / 2, Ls samples
 //   resample_global_kernel orig_freq -> sr (resample.hip), cut or zero-padded to L
 //
+// The stream (fv_pv_stream_*) runs the same chain on the frames, columns and samples that a push made ready (the rule is stream_ready below):
+//   pv_frame_window_kernel       the polyphase signal of the analysis frames [A, A2) from the carried samples plus the chunk
+//   pv_scan_synth_stream_kernel  pv_scan_synth_kernel over the stretched frames [S, S2), resumed from the carried column A - 1 and the carried Phi
+//   istft_ola_window_kernel      the stretched samples [Y, Y2) from the carried frames plus the new ones, istft_ola_kernel's sum and order
+//   pv_frame_carry_kernel        the last n_fft / hop synthesised frames, into the other buffer of the pair
+// with pv_polar_kernel, the two convs (always in batch-invariant mode) and an fv_resample_stream between and behind them.
+//
 // Why integers: librosa's accumulator grows by about pi per hop and bin — 1e6 rad after 200 000 samples, where fp32 resolves 0.06 rad.  In
 // turns modulo 1 the sum never grows: a uint32 holds it to 2^-32 turns, exactly, in any summation order.
 #include <memory>
 #include <numeric>
+#include <optional>
 
 #include "engine_internal.h"
+#include "sample_stream.h"
 
 namespace fv {
 namespace {
@@ -122,6 +131,176 @@ __global__ void pv_zero_tail_kernel(float* y, long long y_stride, long long from
     if (i < to) y[(long long)blockIdx.y * y_stride + i] = 0.f;
 }
 
+
+// The stream's pv_frame_kernel: slot (tp, r) is sample idx = (f0 + tp) hop + r - pad of row b.  The carry holds the samples [N - H, N), the chunk
+// [N, N + c); zeros stand before sample 0 and from `end` on (a push: N + c, no frame of the launch reaches it; the flush: N).  A slot that takes a
+// sample selects its piece and clamps the address into it: nothing outside the chunk and the carry is loaded.  Neither piece is written here.
+__global__ __launch_bounds__(256) void pv_frame_window_kernel(const float* __restrict__ carry, const float* __restrict__ chunk,
+                                                              float* __restrict__ yp, long long carry_stride, long long chunk_stride, long long N,
+                                                              int H, int c, long long end, long long f0, int hop, int TP, int pad) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z;
+    const int r0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int i = ty; i < 32; i += 8) {   // read: consecutive lanes = consecutive samples (r) of frame slot t0 + i
+        const int tp = t0 + i, r = r0 + tx;
+        const long long idx = (f0 + tp) * hop + r - pad;
+        float v = 0.f;
+        if (tp < TP && r < hop && idx >= 0 && idx >= N - H && idx < end) {
+            if (idx >= N) {
+                const long long at = idx - N;
+                v = chunk[(long long)b * chunk_stride + (at > c - 1 ? c - 1 : at)];
+            } else {
+                v = carry[(long long)b * carry_stride + (idx - (N - H))];
+            }
+        }
+        tile[i][tx] = v;
+    }
+    __syncthreads();
+    float* yb = yp + (long long)b * hop * TP;
+    for (int i = ty; i < 32; i += 8) {   // write: consecutive lanes = consecutive frame slots
+        const int r = r0 + i, tp = t0 + tx;
+        if (r < hop && tp < TP) yb[(long long)r * TP + tp] = tile[tx][i];
+    }
+}
+
+// pv_scan_synth_kernel over the stretched frames [S, S + dS).  mag / theta: (rows, dA + 2), the analysed columns [A, A + dA) and two zero columns
+// behind them (read at the flush only, where they are the columns T and T + 1); column A - 1 is the carried (cmag, ctheta).  The scan starts from
+// the carried total cphi — Theta[k][0] plus the increments of the frames [0, S) — or, at S = 0, from Theta[k][0] itself, and lane 0 stores the new
+// total and the new last column into the other buffers of the pairs.  q, j, alpha, the fmaf and the sincospif are pv_scan_synth_kernel's statements,
+// and the wrapping sum is associative: the bits are the whole row's.
+__global__ __launch_bounds__(256) void pv_scan_synth_stream_kernel(const float* __restrict__ mag, const uint32_t* __restrict__ theta,
+                                                                   const float* __restrict__ cmag, const uint32_t* __restrict__ ctheta,
+                                                                   const uint32_t* __restrict__ cphi, float* __restrict__ nmag,
+                                                                   uint32_t* __restrict__ ntheta, uint32_t* __restrict__ nphi,
+                                                                   float* __restrict__ spec, int rows, int nb, long long A, int dA, long long S,
+                                                                   int dS, int o, int n) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;   // (whole waves leave: the shuffles below always see 64 lanes)
+    const int b = row / nb, k = row - b * nb;
+    const int W = dA + 2;
+    const float* mr = mag + (long long)row * W;
+    const uint32_t* tr = theta + (long long)row * W;
+    const float cm = cmag[row];
+    const uint32_t ct = ctheta[row];
+    // column j of the row: w = j - A in [-1, dA + 1] by the rule (clamped, so that no address leaves the window)
+    auto col = [&](long long j, float& m, uint32_t& th) {
+        long long w = j - A;
+        w = w > dA + 1 ? dA + 1 : w;
+        const int at = w < 0 ? 0 : (int)w;
+        const float mw = mr[at];
+        const uint32_t tw = tr[at];
+        m = w < 0 ? cm : mw;
+        th = w < 0 ? ct : tw;
+    };
+    float* re = spec + ((long long)b * 2 * nb + k) * dS;
+    float* im = re + (long long)nb * dS;
+    const float inv_o = 1.0f / (float)o;
+    uint32_t carry;
+    {
+        float m0;
+        uint32_t t0;
+        col(0, m0, t0);   // (S = 0 means A <= 1: column 0 is in the window or is the carried one)
+        carry = S == 0 ? t0 : cphi[row];
+    }
+    for (int s0 = 0; s0 < dS; s0 += 64 * kPvUnroll) {
+#pragma unroll
+        for (int u = 0; u < kPvUnroll; ++u) {
+            const int sl = s0 + u * 64 + lane;
+            const bool live = sl < dS;
+            const long long q = (S + (live ? sl : 0)) * n;
+            const long long j = q / o;
+            const int rem = (int)(q - j * o);
+            float m0, m1;
+            uint32_t th0, th1;
+            col(j, m0, th0);
+            col(j + 1, m1, th1);
+            const uint32_t d = live ? th1 - th0 : 0u;
+            uint32_t inc = d;
+#pragma unroll
+            for (int sh = 1; sh < 64; sh <<= 1) {
+                const uint32_t v = __shfl_up(inc, sh, 64);
+                if (lane >= sh) inc += v;
+            }
+            const uint32_t phi = carry + (inc - d);
+            carry += __shfl(inc, 63, 64);
+            if (live) {
+                const float alpha = (float)rem * inv_o;
+                const float m = fmaf(alpha, m1, (1.0f - alpha) * m0);
+                float sn, cs;
+                sincospif((float)(int32_t)phi * (1.0f / 2147483648.0f), &sn, &cs);
+                re[sl] = m * cs;
+                im[sl] = m * sn;
+            }
+        }
+    }
+    if (lane == 0) {
+        nphi[row] = carry;
+        nmag[row] = dA > 0 ? mr[dA - 1] : cm;
+        ntheta[row] = dA > 0 ? tr[dA - 1] : ct;
+    }
+}
+
+// istft_ola_kernel on the stretched samples [Y, Y2): sample tau hop + r - pad sums the frames t = tau - g in ascending g, t a GLOBAL frame index
+// that must lie in [0, Tend) — frames [S, S + dS) from `frames` (B, n_fft, dS), frames [S - G, S) from the carried `cfr` (B, n_fft, G).  During
+// pushes Tend = S + dS cannot bind (every frame that covers a sample below Y2 exists); at the flush it is T'.  Reads run along tau, the write is
+// transposed through LDS so that it runs along r, as in istft_ola_kernel.
+__global__ __launch_bounds__(256) void istft_ola_window_kernel(const float* __restrict__ frames, const float* __restrict__ cfr,
+                                                               const float* __restrict__ win2, float* __restrict__ y, int n_fft, int hop, int pad,
+                                                               int G, long long S, int dS, long long Tend, long long Y, long long Y2,
+                                                               long long y_stride, long long tau0, int n_tau, int r_tiles, int tau_tiles) {
+    __shared__ float tile[32][33];
+    int bid = blockIdx.x;
+    const int tt = bid % tau_tiles;
+    bid /= tau_tiles;
+    const int rt = bid % r_tiles;
+    const int b = bid / r_tiles;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    const float* fb = frames + (long long)b * n_fft * dS;
+    const float* cb = cfr + (long long)b * n_fft * G;
+    for (int rr = ty; rr < 32; rr += 8) {
+        const int r = rt * 32 + rr, ti = tt * 32 + tx;
+        float acc = 0.f, env = 0.f;
+        if (r < hop && ti < n_tau) {
+            const long long tau = tau0 + ti;
+            for (int g = 0; g * hop + r < n_fft; ++g) {
+                const long long t = tau - g;
+                if (t >= 0 && t < Tend) {
+                    float v = 0.f;   // (a frame below S - G is never reached: fv_pv_stream_create's note on G)
+                    if (t >= S) v = fb[(long long)(g * hop + r) * dS + (t - S)];
+                    else if (t >= S - G) v = cb[(long long)(g * hop + r) * G + (t - (S - G))];
+                    acc += v;
+                    env += win2[g * hop + r];
+                }
+            }
+        }
+        tile[rr][tx] = env > 0.f ? acc / env : 0.f;
+    }
+    __syncthreads();
+    for (int cc = ty; cc < 32; cc += 8) {
+        const int ti = tt * 32 + cc, r = rt * 32 + tx;
+        if (r < hop && ti < n_tau) {
+            const long long sidx = (tau0 + ti) * hop + r - pad;
+            if (sidx >= Y && sidx < Y2) y[(long long)b * y_stride + (sidx - Y)] = tile[tx][cc];
+        }
+    }
+}
+
+// nfr[b][f][i] = frame S + dS - G + i: from the new frames at or after S, from the carried ones below it, 0 before frame 0
+__global__ __launch_bounds__(256) void pv_frame_carry_kernel(const float* __restrict__ frames, const float* __restrict__ cfr,
+                                                             float* __restrict__ nfr, int n_fft, int G, long long S, int dS) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)n_fft * G) return;
+    const int b = blockIdx.y;
+    const int f = (int)(e / G), i = (int)(e - (long long)f * G);
+    const long long t = S + dS - G + i;
+    float v = 0.f;
+    if (t >= S) v = frames[((long long)b * n_fft + f) * dS + (t - S)];
+    else if (t >= 0) v = cfr[((long long)b * n_fft + f) * G + (t - (S - G))];
+    nfr[((long long)b * n_fft + f) * G + i] = v;
+}
+
 struct Plan {
     int orig_freq = 0, o = 0, n = 0, N = 0, hop = 0;
 };
@@ -188,6 +367,20 @@ Lengths lengths_of(const Plan& p, int64_t L) {
     return l;
 }
 
+// The stream rule (include/fishvoc.h): after N samples, A analysis frames read no sample at or after N; S stretched frames have both their columns
+// among those; Y stretched samples lie under frames that all exist and below Ls(N)
+struct Ready {
+    int64_t A = 0, S = 0, Y = 0;
+};
+Ready stream_ready(const Plan& p, int64_t N) {
+    const int64_t F = p.N, h = p.hop;
+    Ready r;
+    r.A = N < F / 2 ? 0 : (N - F / 2) / h + 1;
+    r.S = r.A < 2 ? 0 : ((r.A - 1) * p.o + p.n - 1) / p.n;
+    r.Y = std::min(std::max<int64_t>(0, r.S * h - F / 2), (2 * N * p.o + p.n) / (2 * (int64_t)p.n));
+    return r;
+}
+
 fv_resample_config resample_config(const fv_pitch_shift_config& c, const Plan& p) {
     fv_resample_config r{};
     r.orig_freq = p.orig_freq, r.new_freq = c.sample_rate, r.lowpass_filter_width = c.lowpass_filter_width;
@@ -205,6 +398,7 @@ struct fv_pitch_shift {
     ConvLayer stft, idft;
     float* d_win2 = nullptr;
     fv_resample* rs = nullptr;   // NULL when orig_freq == sample_rate: the call is a copy
+    bool invariant = false;      // fv_pv_set_batch_invariant: the whole-row calls run their two convs in batch-invariant mode, as the stream does
     ~fv_pitch_shift() {
         conv_layer_destroy(stft);
         conv_layer_destroy(idft);
@@ -240,6 +434,9 @@ static fv_status pv_stretch(fv_pitch_shift* p, const float* d_x, long long x_str
     const int hop = pl.hop, N = pl.N, nb = p->nb, T = (int)l.T, Tout = (int)l.Tout, TP = T + p->taps - 1;
     hipLaunchKernelGGL(pv_frame_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, B), dim3(256), 0, s, d_x, w.Yp, x_stride, L, hop, TP, N / 2);
     FV_HIP_CHECK(hipGetLastError());
+    // (the default leaves the calling thread's mode alone: the calls keep the kernels, and the bits, they have always had)
+    std::optional<AlgoScope> scope;
+    if (p->invariant) scope.emplace(FV_CONV_ALGO_AUTO, true);
     ConvRun r;
     r.batch = B, r.t_in = TP, r.x = w.Yp, r.y = w.Sp;
     if (const fv_status st = conv_layer_run(p->stft, r, s)) return st;
@@ -316,6 +513,205 @@ static fv_status pv_call(fv_pitch_shift* p, const char* fn, bool whole, const fl
                            (long long)keep, (long long)L);
         FV_HIP_CHECK(hipGetLastError());
     }
+    return FV_OK;
+}
+
+
+// The core's buffers carry the samples: buf[cur] holds [N - H, N), H = n_fft (frame A reads from A h - n_fft / 2 > N - n_fft on).  Polar and phase
+// carries are one pair (pol[pcur]: |D| and Theta of column A - 1, Phi after the frames [0, S)), the synthesised frames [S - G, S) another (fr[fcur]).
+// Each pair toggles when a launch has written its other half; the rule's counters A, S, Y follow from N alone.
+struct fv_pv_stream : SampleStream {
+    fv_pitch_shift* p = nullptr;
+    fv_resample_stream* rs = nullptr;   // NULL for the pass-through
+    long long Er = 0;                    // what rs has emitted
+    int G = 0;                           // carried frames
+    int maxA = 0, maxS = 0, maxY = 0, maxR = 0;   // the most frames / stretched frames / stretched samples / resampled samples of one call
+    float* pol[2] = {nullptr, nullptr};  // one allocation: per half [mag (B, nb) | theta (B, nb) | phi (B, nb)]
+    float* fr[2] = {nullptr, nullptr};   // one allocation: (B, n_fft, G) each
+    int pcur = 0, fcur = 0;
+    ~fv_pv_stream() {
+        fv_resample_stream_destroy(rs);
+        if (pol[0]) (void)hipFree(pol[0]);
+        if (fr[0]) (void)hipFree(fr[0]);
+    }
+    float* mag(int h) const { return pol[h]; }
+    uint32_t* theta(int h) const { return (uint32_t*)(pol[h] + (size_t)B * p->nb); }
+    uint32_t* phi(int h) const { return (uint32_t*)(pol[h] + 2 * (size_t)B * p->nb); }
+
+    // [Yp (B, hop, maxA + taps - 1) | Sp (B, 2 nb, maxA) | Mg (B, nb, maxA + 2) | Th (same, uint32) | S2 (B, 2 nb, maxS) | Fr (B, N, maxS) |
+    //  St (B, maxY) | Rs (B, maxR)], each part rounded up to 64 floats
+    struct Parts {
+        float *Yp, *Sp, *Mg, *S2, *Fr, *St, *Rs;
+        uint32_t* Th;
+        size_t elems;
+    };
+    Parts carve(float* ws) const {
+        auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+        const size_t b = (size_t)B, nb = (size_t)p->nb;
+        const size_t n_yp = up(b * p->plan.hop * (size_t)(maxA + p->taps - 1)), n_sp = up(b * 2 * nb * (size_t)maxA);
+        const size_t n_mg = up(b * nb * (size_t)(maxA + 2)), n_s2 = up(b * 2 * nb * (size_t)maxS), n_fr = up(b * p->plan.N * (size_t)maxS);
+        const size_t n_st = up(b * (size_t)maxY), n_rs = up(b * (size_t)maxR);
+        Parts w;
+        w.Yp = ws, w.Sp = w.Yp + n_yp, w.Mg = w.Sp + n_sp, w.Th = (uint32_t*)(w.Mg + n_mg);
+        w.S2 = w.Mg + 2 * n_mg, w.Fr = w.S2 + n_s2, w.St = w.Fr + n_fr, w.Rs = w.St + n_st;
+        w.elems = n_yp + n_sp + 2 * n_mg + n_s2 + n_fr + n_st + n_rs;
+        return w;
+    }
+    size_t ws_bytes() const { return p->identity() ? 0 : align_up(carve(nullptr).elems * sizeof(float), 256); }
+};
+
+static fv_status pv_stream_step(fv_pv_stream* st, const float* d_x, int64_t x_row_stride, int32_t c, bool flush, float* d_y, int64_t y_row_stride,
+                                int64_t* emitted, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = flush ? "fv_pv_stream_flush" : "fv_pv_stream_push";
+    if (emitted) *emitted = 0;
+    if (!st || !emitted) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    long long N2;
+    bool noop;
+    if (const fv_status rs = st->admit(fn, "fv_pv_stream_reset", d_x, x_row_stride, c, flush, &N2, &noop)) return rs;
+    if (noop) return FV_OK;
+    if (N2 > kPvMaxLen) {
+        set_error("%s: more than 2^30 samples in one utterance", fn);
+        return FV_ERR_INVALID;
+    }
+    if (flush && st->N == 0) {   // an utterance without samples: nothing to analyse, nothing comes out
+        st->commit(0, 0, true, false);
+        return FV_OK;
+    }
+    fv_pitch_shift* p = st->p;
+    const Plan& pl = p->plan;
+    const int B = st->B;
+    const long long N = st->N;
+    hipStream_t s = (hipStream_t)stream;
+    const auto check_out = [&](long long k) -> fv_status {
+        if (k > 0 && (!d_y || y_row_stride < k)) {
+            set_error("%s: %s (this call emits %lld outputs per row)", fn, d_y ? "y_row_stride is shorter than the output" : "null output", k);
+            return FV_ERR_INVALID;
+        }
+        if (k > 0 && c > 0) {
+            const float *x_end = d_x + (int64_t)(B - 1) * x_row_stride + c, *y_end = d_y + (int64_t)(B - 1) * y_row_stride + k;
+            if (d_x < y_end && d_y < x_end) {
+                set_error("%s: d_y overlaps d_x; the stream does not run in place", fn);
+                return FV_ERR_INVALID;
+            }
+        }
+        return FV_OK;
+    };
+    if (p->identity()) {   // rate 1: a push hands its own samples back bit for bit, the flush has nothing left
+        if (const fv_status rs = check_out(c)) return rs;
+        if (c > 0)
+            FV_HIP_CHECK(hipMemcpy2DAsync(d_y, (size_t)y_row_stride * 4, d_x, (size_t)x_row_stride * 4, (size_t)c * 4, (size_t)B,
+                                          hipMemcpyDeviceToDevice, s));
+        *emitted = c;
+        st->commit(N2, st->E + c, flush, false);
+        return FV_OK;
+    }
+    // what the call makes ready, all of it known before anything is enqueued
+    const Ready r1 = stream_ready(pl, N);
+    Ready r2 = stream_ready(pl, N2);
+    if (flush) {
+        const Lengths l = lengths_of(pl, N2);
+        r2.A = l.T, r2.S = l.Tout, r2.Y = l.Ls;
+    }
+    const long long dA = r2.A - r1.A, dS = r2.S - r1.S, dY = r2.Y - r1.Y;
+    const long long Er1 = dY > 0 ? std::max(st->Er, resample_emit_count(p->rs, r2.Y)) : st->Er;   // after the inner push
+    const long long Er2 = flush ? fv_resample_output_length(p->rs, r2.Y) : Er1;                  // after the inner flush
+    const long long E2 = flush ? N2 : std::min(Er2, N2);
+    const long long k = E2 - st->E;
+    if (!flush && Er2 > N2) {   // (not reached for lowpass_filter_width >= 1: an output's band ends after the samples its own index stands for)
+        set_error("%s: internal: the resampler would emit output %lld after %lld input samples", fn, Er2 - 1, N2);
+        return FV_ERR_INVALID;
+    }
+    if (dA < 0 || dS < 0 || dY < 0 || k < 0 || dA > st->maxA || dS > st->maxS || dY > st->maxY || Er2 - st->Er > st->maxR) {
+        set_error("%s: internal: %lld frames, %lld stretched frames, %lld stretched samples, %lld resampled in one call; the stream was sized for "
+                  "%d, %d, %d, %d", fn, dA, dS, dY, Er2 - st->Er, st->maxA, st->maxS, st->maxY, st->maxR);
+        return FV_ERR_INVALID;
+    }
+    if (const fv_status rs = check_out(k)) return rs;
+    const bool work = dA > 0 || dS > 0 || dY > 0 || k > 0;
+    if (work && (!ws || ws_bytes < st->ws_bytes())) {
+        set_error("%s: workspace too small (%zu < %zu bytes, fv_pv_stream_workspace_bytes)", fn, ws ? ws_bytes : (size_t)0, st->ws_bytes());
+        return FV_ERR_INVALID;
+    }
+    const fv_pv_stream::Parts w = st->carve((float*)ws);
+    const int hop = pl.hop, F = pl.N, nb = p->nb, G = st->G, H = st->H;
+    {
+        const AlgoScope scope(FV_CONV_ALGO_AUTO, true);   // every column one fixed-order sum, whatever the launch holds
+        if (dA > 0) {
+            const int TP = (int)dA + p->taps - 1;
+            hipLaunchKernelGGL(pv_frame_window_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, B), dim3(256), 0, s, st->buf[st->cur], d_x, w.Yp,
+                               st->stride, (long long)x_row_stride, N, H, (int)c, (long long)N2, (long long)r1.A, hop, TP, F / 2);
+            FV_HIP_CHECK(hipGetLastError());
+            ConvRun r;
+            r.batch = B, r.t_in = TP, r.x = w.Yp, r.y = w.Sp;
+            if (const fv_status rs = conv_layer_run(p->stft, r, s)) return rs;
+        }
+        if (dA > 0 || dS > 0) {
+            const long long per = (long long)nb * (dA + 2);
+            hipLaunchKernelGGL(pv_polar_kernel, dim3((unsigned)((per + 255) / 256), B), dim3(256), 0, s, w.Sp, w.Mg, w.Th, nb, (int)dA);
+            FV_HIP_CHECK(hipGetLastError());
+            const int rows = B * nb, pc = st->pcur;
+            hipLaunchKernelGGL(pv_scan_synth_stream_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, w.Mg, w.Th, st->mag(pc), st->theta(pc),
+                               st->phi(pc), st->mag(pc ^ 1), st->theta(pc ^ 1), st->phi(pc ^ 1), w.S2, rows, nb, (long long)r1.A, (int)dA,
+                               (long long)r1.S, (int)dS, pl.o, pl.n);
+            FV_HIP_CHECK(hipGetLastError());
+            set_last_kernel("pv_scan_synth_stream_kernel");
+            st->pcur ^= 1;
+        }
+        if (!flush)
+            if (const fv_status rs = launch_sample_carry(st->buf[st->cur], st->buf[st->cur ^ 1], d_x, st->stride, x_row_stride, B, N, N2 - H, N - H,
+                                                         H, s))
+                return rs;
+        if (dS > 0) {
+            ConvRun r;
+            r.batch = B, r.t_in = (int)dS, r.x = w.S2, r.y = w.Fr;
+            if (const fv_status rs = conv_layer_run(p->idft, r, s)) return rs;
+        }
+    }
+    if (dY > 0) {
+        const long long tau0 = (r1.Y + F / 2) / hop;
+        const int n_tau = (int)((r2.Y - 1 + F / 2) / hop - tau0 + 1);
+        const int r_tiles = (hop + 31) / 32, tau_tiles = (n_tau + 31) / 32;
+        hipLaunchKernelGGL(istft_ola_window_kernel, dim3((unsigned)((long long)B * r_tiles * tau_tiles)), dim3(256), 0, s, w.Fr, st->fr[st->fcur],
+                           p->d_win2, w.St, F, hop, F / 2, G, (long long)r1.S, (int)dS, (long long)r2.S, (long long)r1.Y, (long long)r2.Y, dY, tau0,
+                           n_tau, r_tiles, tau_tiles);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    if (dS > 0) {
+        hipLaunchKernelGGL(pv_frame_carry_kernel, dim3((unsigned)(((long long)F * G + 255) / 256), B), dim3(256), 0, s, w.Fr, st->fr[st->fcur],
+                           st->fr[st->fcur ^ 1], F, G, (long long)r1.S, (int)dS);
+        FV_HIP_CHECK(hipGetLastError());
+        st->fcur ^= 1;
+    }
+    // the resampler: a push writes the caller's rows; the flush goes through Rs, because its last outputs may lie past L
+    float* dst = flush ? w.Rs : d_y;
+    const long long dst_stride = flush ? st->maxR : y_row_stride;
+    int64_t got = 0;
+    if (dY > 0) {
+        if (const fv_status rs = fv_resample_stream_push(st->rs, w.St, dY, (int32_t)dY, dst, dst_stride, &got, stream)) return rs;
+        if (got != Er1 - st->Er) {
+            set_error("%s: internal: the resampler emitted %lld outputs where the rule says %lld", fn, (long long)got, Er1 - st->Er);
+            return FV_ERR_INVALID;
+        }
+    }
+    if (flush) {
+        int64_t rest = 0;
+        if (const fv_status rs = fv_resample_stream_flush(st->rs, w.Rs + got, dst_stride, &rest, stream)) return rs;
+        const long long keep = std::min(Er2, N2) - st->E;   // (Ls = 0: nothing came out, the rows end in zeros)
+        if (keep > 0)
+            FV_HIP_CHECK(hipMemcpy2DAsync(d_y, (size_t)y_row_stride * 4, w.Rs, (size_t)dst_stride * 4, (size_t)keep * 4, (size_t)B,
+                                          hipMemcpyDeviceToDevice, s));
+        if (keep < k) {
+            hipLaunchKernelGGL(pv_zero_tail_kernel, dim3((unsigned)((k - keep + 255) / 256), B), dim3(256), 0, s, d_y, (long long)y_row_stride,
+                               (long long)std::max(keep, 0LL), (long long)k);
+            FV_HIP_CHECK(hipGetLastError());
+        }
+    }
+    *emitted = k;
+    st->Er = Er2;
+    st->commit(N2, E2, flush, !flush);
     return FV_OK;
 }
 
@@ -397,5 +793,100 @@ FV_API fv_status fv_pitch_shift_forward(fv_pitch_shift* p, const float* d_x, int
                                         int32_t batch, int64_t L, void* d_workspace, size_t workspace_bytes, void* stream) {
     return pv_call(p, "fv_pitch_shift_forward", true, d_x, x_row_stride, d_y, y_row_stride, batch, L, d_workspace, workspace_bytes, stream);
 }
+
+FV_API fv_status fv_pv_stream_ready(const fv_pitch_shift_config* cfg, int64_t N, int64_t* frames, int64_t* stretched_frames,
+                                    int64_t* stretched_samples) {
+    Plan p;
+    if (const fv_status st = make_plan(cfg, "fv_pv_stream_ready", p)) return st;
+    if (N < 0 || N > kPvMaxLen) {
+        set_error("fv_pv_stream_ready: N = %lld must lie in [0, 2^30]", (long long)N);
+        return FV_ERR_INVALID;
+    }
+    const Ready r = stream_ready(p, N);
+    if (frames) *frames = r.A;
+    if (stretched_frames) *stretched_frames = r.S;
+    if (stretched_samples) *stretched_samples = r.Y;
+    return FV_OK;
+}
+
+FV_API fv_status fv_pv_set_batch_invariant(fv_pitch_shift* p, int32_t enable) {
+    if (!p) {
+        set_error("fv_pv_set_batch_invariant: null pitch shifter");
+        return FV_ERR_INVALID;
+    }
+    p->invariant = enable != 0;
+    return FV_OK;
+}
+
+FV_API fv_status fv_pv_stream_create(fv_pitch_shift* p, int32_t batch, int32_t max_chunk, fv_pv_stream** out) {
+    const char* fn = "fv_pv_stream_create";
+    if (!p || !out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    std::unique_ptr<fv_pv_stream> st(new fv_pv_stream());
+    st->p = p;
+    if (p->identity()) {   // the pass-through carries nothing
+        if (const fv_status rs = st->create(fn, batch, max_chunk, 0, 1)) return rs;
+        *out = st.release();
+        return FV_OK;
+    }
+    const Plan& pl = p->plan;
+    const long long F = pl.N, h = pl.hop, o = pl.o, n = pl.n;
+    // One call's most: a push analyses at most c / h + 1 frames, the flush T - A <= F / (2 h) + 1; S moves by at most (dA + 1) o / n + 1; Y by at most
+    // dS h, and up to Ls < T' h + F / 2 at the flush; the resampler then still owes the outputs whose bands had not ended
+    const int kp = resample_band_taps(p->rs);
+    const long long maxA = std::max<long long>((long long)max_chunk / h + 1, F / (2 * h) + 2);
+    const long long maxS = ((maxA + 1) * o + n - 1) / n + 2;
+    const long long maxY = maxS * h + F;
+    const long long maxR = ((maxY + 2LL * kp + 2) * n + o - 1) / o + 8;
+    if (batch >= 1 && max_chunk >= 1 && (maxY > (1 << 28) || maxR > (1LL << 30) || F * maxS >= (1LL << 31))) {
+        set_error("%s: max_chunk = %d gives %lld stretched frames of %lld samples in one push, more than 2^31 elements per row or 2^28 stretched "
+                  "samples; push smaller chunks", fn, max_chunk, maxS, F);
+        return FV_ERR_UNSUPPORTED;
+    }
+    if (const fv_status rs = st->create(fn, batch, max_chunk, (int)F, F)) return rs;
+    st->G = (int)(F / h);   // one more than the overlap: where Ls(N) binds (h = F only), Y lies up to h samples below S h - F / 2
+    st->maxA = (int)maxA, st->maxS = (int)maxS, st->maxY = (int)maxY, st->maxR = (int)maxR;
+    const size_t pol = 3 * (size_t)batch * p->nb, frm = (size_t)batch * F * st->G;
+    FV_HIP_CHECK(hipMalloc((void**)&st->pol[0], 2 * pol * sizeof(float)));
+    st->pol[1] = st->pol[0] + pol;
+    FV_HIP_CHECK(hipMemset(st->pol[0], 0, 2 * pol * sizeof(float)));
+    FV_HIP_CHECK(hipMalloc((void**)&st->fr[0], 2 * frm * sizeof(float)));
+    st->fr[1] = st->fr[0] + frm;
+    FV_HIP_CHECK(hipMemset(st->fr[0], 0, 2 * frm * sizeof(float)));
+    if (const fv_status rs = fv_resample_stream_create(p->rs, batch, (int32_t)maxY, &st->rs)) return rs;
+    *out = st.release();
+    return FV_OK;
+}
+
+FV_API size_t fv_pv_stream_workspace_bytes(const fv_pv_stream* s) { return s ? s->ws_bytes() : 0; }
+
+FV_API int64_t fv_pv_stream_pending(const fv_pv_stream* s) { return s ? s->N - s->E : 0; }
+
+FV_API fv_status fv_pv_stream_push(fv_pv_stream* s, const float* d_x, int64_t x_row_stride, int32_t c, float* d_y, int64_t y_row_stride,
+                                   int64_t* emitted, void* d_workspace, size_t workspace_bytes, void* stream) {
+    return pv_stream_step(s, d_x, x_row_stride, c, false, d_y, y_row_stride, emitted, d_workspace, workspace_bytes, stream);
+}
+
+FV_API fv_status fv_pv_stream_flush(fv_pv_stream* s, float* d_y, int64_t y_row_stride, int64_t* emitted, void* d_workspace,
+                                    size_t workspace_bytes, void* stream) {
+    return pv_stream_step(s, nullptr, 0, 0, true, d_y, y_row_stride, emitted, d_workspace, workspace_bytes, stream);
+}
+
+FV_API fv_status fv_pv_stream_reset(fv_pv_stream* s) {
+    if (!s) {
+        set_error("fv_pv_stream_reset: null stream");
+        return FV_ERR_INVALID;
+    }
+    if (s->rs)
+        if (const fv_status rs = fv_resample_stream_reset(s->rs)) return rs;
+    s->reset();
+    s->Er = 0;
+    return FV_OK;
+}
+
+FV_API void fv_pv_stream_destroy(fv_pv_stream* s) { delete s; }
 
 }  // extern "C"

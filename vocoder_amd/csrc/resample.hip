@@ -335,6 +335,9 @@ fv_status fv::resample_rows(const fv_resample* r, const char* fn, const float* x
     return resample_run(r, fn, x, x_stride, 0, nullptr, len, y, y_stride, batch, 0, m_end, s);
 }
 
+long long fv::resample_emit_count(const fv_resample* r, long long N) { return r->emit_count(N); }
+int fv::resample_band_taps(const fv_resample* r) { return r->d.kp; }
+
 extern "C" {
 
 FV_API fv_status fv_resample_design(const fv_resample_config* cfg, int32_t* o, int32_t* n, int32_t* width, int32_t* kp, int32_t* first,

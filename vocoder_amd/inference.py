@@ -293,8 +293,9 @@ def _pad_samples(hop: int, L: int) -> int:
 
 @torch.no_grad()
 def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chunk_frames: int, to_model: nn.Module | None = None,
-                         to_out: nn.Module | None = None, sink=None, template: dict | None = None):
-    """wav -> wav chunk by chunk: [resample stream ->] log-mel stream -> generator stream [-> resample stream].  ``chunks`` yields ``(B, c)``
+                         to_out: nn.Module | None = None, sink=None, template: dict | None = None, pitch_shift: nn.Module | None = None):
+    """wav -> wav chunk by chunk: [resample stream ->] [pitch-shift stream ->] log-mel stream -> generator stream [-> resample stream].
+    ``chunks`` yields ``(B, c)``
     tensors of input samples (``c <= chunk_frames * hop``), ``total_samples`` is their sum (the zero padding of the whole-file branch,
     test.py:64-68, depends on it); ``to_model`` / ``to_out``: ``Resample`` modules into and out of the model's rate.  Every stage's output is
     pushed into the next one as it comes (its emit count sizes that push), and at the end the flushes cascade from the first stage to the
@@ -303,8 +304,12 @@ def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chun
     the first audio left).  ``template``: the keyword arguments of a ``vocoder_amd.f0.TemplateStream`` after its sizes (``frame_length``,
     ``fmin``, ``fmax``, ``threshold``, ``kind``, ``amplitude``) for a generator that takes a pitch template: the model-rate samples, the zero
     padding included, go into the log-mel stream and into the template stream, and the generator stream gets the frames both have emitted
-    (``_TemplateJoin``); a ValueError names the two frame totals if they differ at the end."""
+    (``_TemplateJoin``); a ValueError names the two frame totals if they differ at the end.  ``pitch_shift``: a
+    ``vocoder_amd.pitch_shift.PitchShift`` at the model's rate (test.py:61-62); its stream stands behind ``to_model``, gives back as many
+    samples as it takes, and the log-mel front-end and the template are made from the shifted samples, as in the whole-file branch."""
     gen, front, hop = model.generator, model.mel_transform, model.hop_length
+    if pitch_shift is not None and pitch_shift.sample_rate != model.sampling_rate:
+        raise ValueError(f"pitch_shift runs at {pitch_shift.sample_rate} Hz, the model at {model.sampling_rate} Hz")
     if front is None or not hasattr(front, "stream"):
         raise ValueError("--chunk-frames on a .wav needs the GPU log-mel front-end (build_model attaches one)")
     if not hasattr(gen, "stream"):
@@ -334,6 +339,8 @@ def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chun
         stages = []
         if to_model is not None:
             stages.append(_Stage(stack.enter_context(to_model.stream(batch=B, max_chunk=limit)), limit))
+        if pitch_shift is not None:
+            stages.append(_Stage(stack.enter_context(pitch_shift.stream(batch=B, max_chunk=limit)), limit))
         mel_stream = stack.enter_context(front.stream(batch=B, max_chunk_samples=limit))
         gst = stack.enter_context(gen.stream(batch=B, max_chunk_frames=chunk_frames))
         if gst.out_channels != 1:
@@ -606,8 +613,8 @@ def main(argv=None):
     ap.add_argument("--template-kind", choices=("sine", "sawtooth"), default="sine", help="waveform of the pitch template")
     a = ap.parse_args(argv)
     if a.pitch_shift and (a.chunk_frames is not None or a.sessions is not None):
-        raise ValueError("--pitch-shift is not available with --chunk-frames / --sessions: the phase vocoder has no streaming form; run the "
-                         "files whole or under --batch-size")
+        raise ValueError("--pitch-shift is not available with --chunk-frames / --sessions on the command line: run the files whole or under "
+                         "--batch-size, or call stream_wav_synthesis(pitch_shift=PitchShift(...)), which shifts chunk by chunk")
     if a.output_rate is not None and a.output_rate < 1:
         ap.error("--output-rate must be >= 1 Hz")
     if a.output_rate is not None and (a.batch_size is not None or a.sessions is not None):

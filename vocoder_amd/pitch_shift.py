@@ -14,6 +14,15 @@ to the input length.  What differs from librosa is stated in integers::
 
 The phase accumulator is an unsigned 32-bit count of turns / 2^32: it wraps where librosa's float grows, so a long file keeps its phase
 (an fp32 accumulator is off by 0.12 of peak after 200 000 samples).  ``orig_freq == sr`` returns the input.
+
+Streaming rule (``PitchShiftStream``, ``fv_pv_stream_*``), with ``F = n_fft``, ``h = hop_length`` and ``N`` samples received per row::
+
+    A = 0 if N < F / 2 else (N - F / 2) / h + 1              analysis frames that read no sample at or after N
+    S = 0 if A < 2 else ceil((A - 1) o / n)                  stretched frames whose columns j = s n / o and j + 1 are analysed
+    Y = min(max(0, S h - F / 2), (2 N o + n) / (2 n))        stretched samples under which every covering frame exists
+    E = min(emit_count(Y), N)                                the resampler's stream (orig_freq -> sr) after Y samples
+
+The flush emits the rest, ``E = N``.  With ``batch_invariant=True`` the concatenated chunks are bit-identical to ``forward`` over whole rows.
 """
 from __future__ import annotations
 
@@ -24,9 +33,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._handle import _DeviceHandles
+from ._handle import _DeviceHandles, _Handle, _emit
 from ._lib import check
-from .resample import KAISER_BETA, _require_cuda, _rows
+from .resample import KAISER_BETA, _require_cuda, _rows, design
 
 KAISER_BEST_ROLLOFF = 0.9475937167399596     # torchaudio's documented equivalent of librosa's kaiser_best, with width 64 and KAISER_BETA
 
@@ -62,19 +71,31 @@ def lengths(L: int, o: int, n: int, hop_length: int) -> tuple[int, int, int, int
     return T, Tout, Ls, M
 
 
+def stream_ready(N: int, o: int, n: int, n_fft: int, hop_length: int) -> tuple[int, int, int]:
+    """``(A, S, Y)`` once ``N`` samples have arrived, as ``fv_pv_stream_ready`` computes them."""
+    N, F, h = int(N), int(n_fft), int(hop_length)
+    A = 0 if N < F // 2 else (N - F // 2) // h + 1
+    S = 0 if A < 2 else -((-(A - 1) * o) // n)
+    Y = min(max(0, S * h - F // 2), (2 * N * o + n) // (2 * n))
+    return A, S, Y
+
+
 class PitchShift(nn.Module):
     """``librosa.effects.pitch_shift(y, sr=sample_rate, n_steps=n_steps)`` on the MI355X (test.py:61-62): ``forward(wave (..., L)) -> (..., L)``.
     Leading dimensions are flattened to rows (a stereo file is two rows, test.py:56-64).  ``time_stretch(wave)`` is the first stage alone,
-    ``(..., Ls)``.  No CPU fallback."""
+    ``(..., Ls)``.  ``stream(batch, max_chunk)`` gives the streaming form.  ``batch_invariant=True`` runs the two DFT convs as fixed-order sums
+    whatever the launch size (``fv_pv_set_batch_invariant``): the mode in which whole rows and any chunking of a stream agree bit for bit.
+    No CPU fallback."""
 
     def __init__(self, sample_rate: int, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None,
                  freq_granularity: int = 100, lowpass_filter_width: int = 64, rolloff: float = KAISER_BEST_ROLLOFF,
-                 resampling_method: str = "sinc_interp_kaiser", beta: float | None = None):
+                 resampling_method: str = "sinc_interp_kaiser", beta: float | None = None, batch_invariant: bool = False):
         super().__init__()
         self.sample_rate, self.n_steps, self.bins_per_octave = int(sample_rate), float(n_steps), int(bins_per_octave)
         self.n_fft, self.hop_length = int(n_fft), int(n_fft) // 4 if hop_length is None else int(hop_length)
         self.freq_granularity, self.lowpass_filter_width, self.rolloff = int(freq_granularity), int(lowpass_filter_width), float(rolloff)
-        self.resampling_method, self.beta = resampling_method, beta
+        self.resampling_method, self.beta, self.batch_invariant = resampling_method, beta, bool(batch_invariant)
+        self._design = None
         self.orig_freq, self.o, self.n = plan(self.sample_rate, self.n_steps, self.bins_per_octave, self.freq_granularity)
         if self.n_fft < 2 or self.hop_length < 1 or self.n_fft % self.hop_length or self.n_fft % 2 or self.hop_length % 2:
             raise ValueError(f"n_fft ({self.n_fft}) must be a multiple of hop_length ({self.hop_length}) and both even")
@@ -92,7 +113,29 @@ class PitchShift(nn.Module):
                                      self.lowpass_filter_width, self.rolloff, int(method), KAISER_BETA if self.beta is None else float(self.beta))
 
     def _handle(self, device: torch.device) -> ctypes.c_void_p:
-        return self._handles.get(device, lambda h: _lib.lib().fv_pitch_shift_create(ctypes.byref(self.config()), h))
+        def create(h) -> int:
+            lib = _lib.lib()
+            st = lib.fv_pitch_shift_create(ctypes.byref(self.config()), h)
+            return st or lib.fv_pv_set_batch_invariant(h._obj, int(self.batch_invariant))
+        return self._handles.get(device, create)
+
+    def resample_design(self):
+        """The filter of the second stage, ``orig_freq -> sample_rate`` (``vocoder_amd.resample.design``): the stream's emission rule counts with it."""
+        if self._design is None:
+            self._design = design(self.orig_freq, self.sample_rate, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
+        return self._design
+
+    def stream_ready(self, N: int) -> tuple[int, int, int]:
+        return stream_ready(N, self.o, self.n, self.n_fft, self.hop_length)
+
+    def stream_emitted(self, N: int) -> int:
+        """Outputs a stream has emitted once ``N`` samples have arrived (before the flush)."""
+        if self.orig_freq == self.sample_rate:
+            return int(N)
+        return min(self.resample_design().emit_count(self.stream_ready(N)[2]), int(N))
+
+    def stream(self, batch: int, max_chunk: int) -> "PitchShiftStream":
+        return PitchShiftStream(self, batch, max_chunk)
 
     def _run(self, wave: torch.Tensor, whole: bool, what: str) -> torch.Tensor:
         _require_cuda(wave, what)
@@ -127,3 +170,76 @@ class PitchShift(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.sample_rate} Hz, n_steps={self.n_steps}, orig_freq={self.orig_freq} (rate {self.n}/{self.o}), n_fft={self.n_fft}, "
                 f"hop_length={self.hop_length}")
+
+
+class PitchShiftStream(_Handle):
+    """``batch`` rows shifted chunk by chunk, in lockstep (``fv_pv_stream``): ``push`` a ``(batch, c)`` chunk, ``c <= max_chunk``, and get the
+    ``(batch, k)`` outputs that no later sample can change (``k`` may be 0); ``flush`` emits the rest, so that as many samples have come out as
+    went in; ``reset`` starts the next utterance; ``close`` frees the stream (also a context manager).  Work is enqueued on torch's current
+    stream; calls must be ordered."""
+    _destroy = "fv_pv_stream_destroy"
+    _closed = "this pitch-shift stream is closed: create a new one"
+
+    def __init__(self, shift: PitchShift, batch: int, max_chunk: int, device=None):
+        self._shift, self._lib = shift, _lib.lib()
+        self.batch, self.max_chunk = int(batch), int(max_chunk)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self._lib.fv_pv_stream_create(shift._handle(self.device), self.batch, self.max_chunk, ctypes.byref(self._h)))
+            self._need = int(self._lib.fv_pv_stream_workspace_bytes(self._h))
+            self._ws = torch.empty(max(self._need, 1), dtype=torch.uint8, device=self.device)
+        self._N = self._E = 0
+        self._flushed = False
+
+    # -- counters (host-side: reading them never synchronises) --
+    @property
+    def received_samples(self) -> int:
+        return self._N
+
+    @property
+    def emitted_samples(self) -> int:
+        return self._E
+
+    @property
+    def pending_samples(self) -> int:
+        """``N - E`` as the library counts it (fv_pv_stream_pending): what a flush would emit now."""
+        self._check_open()
+        return int(self._lib.fv_pv_stream_pending(self._h))
+
+    def push(self, chunk: torch.Tensor) -> torch.Tensor:
+        self._check_open()
+        _require_cuda(chunk, "PitchShiftStream.push")
+        if chunk.dim() != 2 or chunk.shape[0] != self.batch:
+            raise ValueError(f"expected a chunk of shape ({self.batch}, c), got {tuple(chunk.shape)}")
+        return self._call(_rows(chunk), int(chunk.shape[1]), flush=False)
+
+    def flush(self) -> torch.Tensor:
+        self._check_open()
+        return self._call(None, 0, flush=True)
+
+    def _call(self, x, c: int, flush: bool, workspace_bytes: int | None = None) -> torch.Tensor:
+        N2 = self._N + c
+        ok = flush or c <= self.max_chunk                   # a refused push emits nothing; the library says why
+        E2 = N2 if flush else max(self._E, self._shift.stream_emitted(N2))
+        k = E2 - self._E if ok and not self._flushed else 0
+        need = self._need if workspace_bytes is None else int(workspace_bytes)
+
+        def enqueue(optr, got) -> None:
+            with torch.cuda.device(self.device):
+                run = torch.cuda.current_stream()
+                s = int(run.cuda_stream)
+                check(self._lib.fv_pv_stream_flush(self._h, optr, max(k, 1), got, self._ws.data_ptr(), need, s) if flush else
+                      self._lib.fv_pv_stream_push(self._h, x.data_ptr(), x.stride(0) if self.batch > 1 else max(c, 1), c, optr, max(k, 1), got,
+                                                  self._ws.data_ptr(), need, s))
+                self._record_done(run)      # the carried buffers and the workspace are in use on the device until then
+        out = _emit((self.batch, k), k, self.device, enqueue, "pitch-shift stream emitted {got} samples where the emission rule says {k}")
+        self._N, self._E = N2, E2
+        self._flushed = flush
+        return out
+
+    def reset(self) -> None:
+        self._check_open()
+        check(self._lib.fv_pv_stream_reset(self._h))
+        self._N = self._E = 0
+        self._flushed = False
