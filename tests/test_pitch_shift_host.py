@@ -176,3 +176,36 @@ def test_the_global_resampler_takes_its_design_from_fv_resample_design(kwargs, f
     # the pair the LDS form refuses has a design: 48000 phases of 13 taps
     d = rs.native_design(44101, 48000)
     assert (d.o, d.n, d.kp) == (44101, 48000, 13) and d.n * d.kp > 7000
+
+
+@pytest.mark.gpu   # (a handle holds device tables: the sizes are host arithmetic, but only a created shifter answers)
+@pytest.mark.parametrize("n_fft,hop,B,L,max_chunk", [(64, 16, 3, 1000, 100), (2048, 512, 2, 20000, 4096)])
+def test_workspace_sizes_are_the_closed_forms_of_the_one_layout(n_fft, hop, B, L, max_chunk):
+    """One layout function serves the whole-row call and the stream (fv_pitch_shift::carve): parts [Yp (B, hop, nA + taps - 1) | Sp (B, 2 nb, nA) |
+    Mg (B, nb, nA + 2) | Th (same) | S2 (B, 2 nb, nS) | Fr (B, N, nS) | St (B, nY) | Rs (B, nR)], each rounded up to 64 floats, the sum to 256
+    bytes.  A whole-row call has (nA, nS, nY, nR) = (T, T', Ls, 0), a stream the most of one call as fv_pv_stream_create states them."""
+    import torch
+    lib = _lib.lib()
+    shift = ps.PitchShift(44100, 3, n_fft=n_fft, hop_length=hop)
+    _, o, n = shift.plan()
+    nb, taps = n_fft // 2 + 1, n_fft // hop
+
+    def up(v):
+        return (v + 63) // 64 * 64
+
+    def closed_form(nA, nS, nY, nR):
+        elems = (up(B * hop * (nA + taps - 1)) + up(B * 2 * nb * nA) + 2 * up(B * nb * (nA + 2)) + up(B * 2 * nb * nS) + up(B * n_fft * nS)
+                 + up(B * nY) + up(B * nR))
+        return (elems * 4 + 255) // 256 * 256
+
+    dev = torch.device("cuda", 0)
+    T, Tout, Ls, _ = shift.lengths(L)
+    assert int(lib.fv_pitch_shift_workspace_bytes(shift._handle(dev), B, L)) == closed_form(T, Tout, Ls, 0)
+    kp = shift.resample_design().kp
+    maxA = max(max_chunk // hop + 1, n_fft // (2 * hop) + 2)
+    maxS = ((maxA + 1) * o + n - 1) // n + 2
+    maxY = maxS * hop + n_fft
+    maxR = ((maxY + 2 * kp + 2) * n + o - 1) // o + 8
+    with shift.stream(B, max_chunk) as st:
+        assert int(lib.fv_pv_stream_workspace_bytes(st._h)) == closed_form(maxA, maxS, maxY, maxR)
+    shift.close()

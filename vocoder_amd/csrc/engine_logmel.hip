@@ -1,6 +1,6 @@
 // The log-mel front-end on rows of different lengths and on chunks of a stream (fv_logmel_*, include/fishvoc.h): what
 // fish_vocoder/data/transforms/spectrogram.py:25-104 computes for whole, equal-length rows and test.py:64-71 calls once per file.
-// Only the first step differs from fv_forward on a log-mel engine: logmel_window_kernel (logmel_windows.hip) writes the polyphase signal of
+// Only the first step differs from fv_forward on a log-mel engine: logmel_window_kernel (frame_kernels.hip) writes the polyphase signal of
 // the frames [f0, f0 + n) with per-row edges; behind it the forward's own tail runs unchanged (fv_engine::run_logmel_tail).  These entries
 // enqueue eagerly and leave the engine's captured graphs and their bookkeeping alone.
 #include <memory>

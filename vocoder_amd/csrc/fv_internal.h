@@ -367,7 +367,7 @@ fv_status launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b,
 fv_status launch_noise_conv_add(const float* tmpl, const float* w, const float* bias, float* x, int B, int C, int T, int Ta,
                                 int k, int stride, int pad, hipStream_t s);
 
-// Log-mel front-end glue (small_kernels.hip)
+// Log-mel front-end glue (frame_kernels.hip, small_kernels.hip)
 // yp[b][r][tp] = wave[b][reflect(tp*hop + r - pad_l)] (0 past the padded length): polyphase layout so that the STFT becomes
 // a stride-1 conv with hop channels and n_fft/hop taps
 fv_status launch_polyphase_reflect(const float* wave, float* yp, int B, int L, int hop, int TP, int pad_l, int pad_r, hipStream_t s);
@@ -420,7 +420,7 @@ fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab,
 // of row stride `stride`
 fv_status launch_sample_carry(const float* prev, float* next, const float* chunk, long long stride, long long chunk_stride, int B, long long N,
                               long long next_origin, long long prev_origin, long long count, hipStream_t s);
-// log-mel front-end on ragged rows and stream chunks (logmel_windows.hip; fv_logmel_ragged_forward, fv_logmel_stream_*): per-row values travel
+// log-mel front-end on ragged rows and stream chunks (frame_kernels.hip; fv_logmel_ragged_forward, fv_logmel_stream_*): per-row values travel
 // BY VALUE, kLogmelRows rows per launch, as the session pool's tables do
 static constexpr int kLogmelRows = 32;
 struct LogmelRowBlock {
@@ -436,9 +436,21 @@ fv_status launch_logmel_window(const float* carry, long long carry_stride, long 
 fv_status launch_zero_columns(float* y, const long long* row_cols, int B, int C, long long T, hipStream_t s);
 // rows [0,nb) = Re, [nbp, nbp+nb) = Im, zero padded to nbp = round_up(nb, 8)
 fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T, int nb, int nbp, hipStream_t s);
-// frames (B, n_fft, T) (already windowed by the synthesis basis) -> overlap-add, crop, divide by the envelope.
+// frames (B, n_fft, T) (already windowed by the synthesis basis) -> overlap-add, crop, divide by the envelope (frame_kernels.hip).
 fv_status launch_istft_ola(const float* frames, const float* inv_env, float* y, int B, int n_fft, int T, int hop, int pad, long long out_len,
                            hipStream_t s);
+// the same sum for the samples [Y, Y2) of a stream, y (B, Y2 - Y): the frames [S, S + dS) from `frames` (B, n_fft, dS), the frames [S - G, S) from
+// the carried `cfr` (B, n_fft, G); only frames in [0, Tend) exist
+fv_status launch_istft_ola_window(const float* frames, const float* cfr, const float* win2, float* y, int B, int n_fft, int hop, int pad, int G,
+                                  long long S, int dS, long long Tend, long long Y, long long Y2, hipStream_t s);
+// nfr (B, n_fft, G) = the frames [S + dS - G, S + dS) of the same two pieces, 0 before frame 0
+fv_status launch_pv_frame_carry(const float* frames, const float* cfr, float* nfr, int B, int n_fft, int G, long long S, int dS, hipStream_t s);
+// the pitch shift's frames: yp[b][r][tp] = wave[b][tp hop + r - pad] inside [0, L), else 0 ...
+fv_status launch_pv_frame(const float* wave, long long x_stride, float* yp, int B, long long L, int hop, int TP, int pad, hipStream_t s);
+// ... and for the frames from f0 on of a stream: sample (f0 + tp) hop + r - pad, 0 before sample 0 and from `end` on; `carry` holds the samples
+// [N - H, N), `chunk` the samples [N, end)
+fv_status launch_pv_frame_window(const float* carry, long long carry_stride, const float* chunk, long long chunk_stride, float* yp, int B,
+                                 long long N, int H, long long end, long long f0, int hop, int TP, int pad, hipStream_t s);
 
 // The DFT bases the STFT / ISTFT convs are built from (engine_build.hip): the log-mel front-end, the ISTFT head and the pitch shift share them.
 // stft_basis: the window-folded real DFT in polyphase form, a (2 nb, hop, taps) conv weight — rows [0, nb) win[n] cos, [nb, 2 nb) -win[n] sin at

@@ -2,19 +2,20 @@
 // rate = n / o, then a resample from orig_freq back to sr — restated in integers where librosa keeps floats.
 //
 //   pv_frame_kernel        wave -> the zero-padded polyphase signal (B, hop, T + taps - 1) of the centred frames (polyphase_reflect_kernel's
-//                          layout, zeros where that one reflects)
+//                          layout, zeros where that one reflects; frame_kernels.hip)
 //   [STFT conv]            the window-folded DFT basis the log-mel front-end uses (stft_basis) -> Sp (B, 2 nb, T)
 //   pv_polar_kernel        Sp -> |D| (float) and Theta (phase in turns, uint32 fixed point), each (B, nb, T + 2), the last two columns zero
 //   pv_scan_synth_kernel   one wave per (b, k) row: an exclusive scan of Theta[j + 1] - Theta[j] over the T' output frames in wrapping uint32
 //                          arithmetic (the wrap is the modulo 2 pi), magnitude interpolation, sincospi -> S (B, 2 nb, T')
 //   [inverse-DFT conv]     the ISTFT head's basis (istft_basis) -> frames (B, n_fft, T')
-//   istft_ola_kernel       overlap-add, envelope, crop n_fft / 2, Ls samples
+//   istft_ola_kernel       overlap-add, envelope, crop n_fft / 2, Ls samples (frame_kernels.hip)
 //   resample_global_kernel orig_freq -> sr (resample.hip), cut or zero-padded to L
 //
-// The stream (fv_pv_stream_*) runs the same chain on the frames, columns and samples that a push made ready (the rule is stream_ready below):
+// The stream (fv_pv_stream_*) runs the same chain on the frames, columns and samples that a push made ready (the rule is stream_ready below);
+// every stage is the whole row's body behind another fetch (pv_scan_row here, polyphase_tile and ola_tile in frame_kernels.hip):
 //   pv_frame_window_kernel       the polyphase signal of the analysis frames [A, A2) from the carried samples plus the chunk
-//   pv_scan_synth_stream_kernel  pv_scan_synth_kernel over the stretched frames [S, S2), resumed from the carried column A - 1 and the carried Phi
-//   istft_ola_window_kernel      the stretched samples [Y, Y2) from the carried frames plus the new ones, istft_ola_kernel's sum and order
+//   pv_scan_synth_stream_kernel  the scan over the stretched frames [S, S2), resumed from the carried column A - 1 and the carried Phi
+//   istft_ola_window_kernel      the stretched samples [Y, Y2) from the carried frames plus the new ones
 //   pv_frame_carry_kernel        the last n_fft / hop synthesised frames, into the other buffer of the pair
 // with pv_polar_kernel, the two convs (always in batch-invariant mode) and an fv_resample_stream between and behind them.
 //
@@ -31,30 +32,6 @@ namespace fv {
 namespace {
 
 constexpr int64_t kPvMaxLen = 1LL << 30;
-
-// yp[b][r][tp] = wave[b][tp hop + r - pad] inside [0, L), else 0.  The address is clamped and the value selected: no sample at or past L is loaded.
-__global__ __launch_bounds__(256) void pv_frame_kernel(const float* __restrict__ wave, float* __restrict__ yp, long long x_stride, long long L,
-                                                       int hop, int TP, int pad) {
-    __shared__ float tile[32][33];
-    const int b = blockIdx.z;
-    const int r0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const float* wb = wave + (long long)b * x_stride;
-    for (int i = ty; i < 32; i += 8) {   // read: consecutive lanes = consecutive samples (r) of frame slot t0 + i
-        const int tp = t0 + i, r = r0 + tx;
-        const long long idx = (long long)tp * hop + r - pad;
-        const bool in = tp < TP && r < hop && idx >= 0 && idx < L;
-        const long long at = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
-        const float v = wb[at];
-        tile[i][tx] = in ? v : 0.f;
-    }
-    __syncthreads();
-    float* yb = yp + (long long)b * hop * TP;
-    for (int i = ty; i < 32; i += 8) {   // write: consecutive lanes = consecutive frame slots
-        const int r = r0 + i, tp = t0 + tx;
-        if (r < hop && tp < TP) yb[(long long)r * TP + tp] = tile[tx][i];
-    }
-}
 
 // mag = |D| (no epsilon: silence stays exact zero), theta = angle(D) in turns as uint32; columns T and T + 1 are zero
 __global__ __launch_bounds__(256) void pv_polar_kernel(const float* __restrict__ spec, float* __restrict__ mag, uint32_t* __restrict__ theta,
@@ -76,35 +53,33 @@ __global__ __launch_bounds__(256) void pv_polar_kernel(const float* __restrict__
     theta[(long long)b * nb * T2 + i] = th;
 }
 
-// One wave per (b, k) row walks the T' output columns 64 at a time, kPvUnroll chunks per trip.  Column s: q = s n, j = q / o, alpha = (q % o) / o;
-// Phi[s] = Theta[0] + sum_{u < s} (Theta[j_u + 1] - Theta[j_u]): a wave-level exclusive scan (six __shfl_up steps) plus the carried total, all in
-// wrapping uint32.  Lanes read and write consecutive columns; no LDS, no atomics, Phi is never stored.
+// One wave walks the dS output columns [start, start + dS) of one (b, k) row 64 at a time, kPvUnroll chunks per trip.  Column s: q = s n, j = q / o,
+// alpha = (q % o) / o; Phi[s] = Theta[0] + sum_{u < s} (Theta[j_u + 1] - Theta[j_u]): a wave-level exclusive scan (six __shfl_up steps) plus the
+// carried total, all in wrapping uint32.  `carry` is Phi[start] on entry and Phi[start + dS] on return.  cols(j, m, th) fetches column j of |D| and
+// Theta; its Index type is the width j is kept in.  Lanes read and write consecutive columns; no LDS, no atomics, Phi is never stored.
 // Each column pays one 64-bit division (q / o) beside the sincospif, and alpha = rem * (1 / o) rounds twice where rem / o would round once
-// (within 2^-23, far inside the parity bar).  The kernel has not been timed (profiles/LOG.md R15.1), so stepping j and the remainder from column
-// to column (as resample_body steps ph and base) is an untried option, not a known gain.
+// (within 2^-23, far inside the parity bar).  Stepping j and the remainder from column to column (as resample_body steps ph and base) is an
+// untried option, not a known gain.
 constexpr int kPvUnroll = 2;
 
-__global__ __launch_bounds__(256) void pv_scan_synth_kernel(const float* __restrict__ mag, const uint32_t* __restrict__ theta,
-                                                            float* __restrict__ spec, int rows, int nb, int T, int Tout, int o, int n) {
+template <class Cols>
+__device__ __forceinline__ void pv_scan_row(const Cols& cols, float* __restrict__ re, float* __restrict__ im, long long start, int dS,
+                                            uint32_t& carry, int o, int n) {
+    using Index = typename Cols::Index;
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;   // (whole waves leave: the shuffles below always see 64 lanes)
-    const int b = row / nb, k = row - b * nb;
-    const float* mr = mag + (long long)row * (T + 2);
-    const uint32_t* tr = theta + (long long)row * (T + 2);
-    float* re = spec + ((long long)b * 2 * nb + k) * Tout;
-    float* im = re + (long long)nb * Tout;
     const float inv_o = 1.0f / (float)o;
-    uint32_t carry = tr[0];
-    for (int s0 = 0; s0 < Tout; s0 += 64 * kPvUnroll) {
+    for (int s0 = 0; s0 < dS; s0 += 64 * kPvUnroll) {
 #pragma unroll
         for (int u = 0; u < kPvUnroll; ++u) {
             const int s = s0 + u * 64 + lane;
-            const bool live = s < Tout;
-            const long long q = (long long)(live ? s : 0) * n;
-            const int j = (int)(q / o), rem = (int)(q - (long long)j * o);   // j <= T - 1: columns j and j + 1 exist
-            const uint32_t th0 = tr[j], th1 = tr[j + 1];
-            const float m0 = mr[j], m1 = mr[j + 1];
+            const bool live = s < dS;
+            const long long q = (start + (live ? s : 0)) * n;
+            const Index j = (Index)(q / o);
+            const int rem = (int)(q - (long long)j * o);
+            float m0, m1;
+            uint32_t th0, th1;
+            cols(j, m0, th0);
+            cols(j + 1, m1, th1);
             const uint32_t d = live ? th1 - th0 : 0u;
             uint32_t inc = d;
 #pragma unroll
@@ -126,66 +101,37 @@ __global__ __launch_bounds__(256) void pv_scan_synth_kernel(const float* __restr
     }
 }
 
-__global__ void pv_zero_tail_kernel(float* y, long long y_stride, long long from, long long to) {
-    const long long i = from + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < to) y[(long long)blockIdx.y * y_stride + i] = 0.f;
-}
+// the whole row: columns [0, T + 2) in place, j <= T - 1 so that columns j and j + 1 exist; the scan starts from Theta[0]
+struct PvRowCols {
+    using Index = int;
+    const float* mr;
+    const uint32_t* tr;
+    __device__ __forceinline__ void operator()(int j, float& m, uint32_t& th) const { m = mr[j], th = tr[j]; }
+};
 
-
-// The stream's pv_frame_kernel: slot (tp, r) is sample idx = (f0 + tp) hop + r - pad of row b.  The carry holds the samples [N - H, N), the chunk
-// [N, N + c); zeros stand before sample 0 and from `end` on (a push: N + c, no frame of the launch reaches it; the flush: N).  A slot that takes a
-// sample selects its piece and clamps the address into it: nothing outside the chunk and the carry is loaded.  Neither piece is written here.
-__global__ __launch_bounds__(256) void pv_frame_window_kernel(const float* __restrict__ carry, const float* __restrict__ chunk,
-                                                              float* __restrict__ yp, long long carry_stride, long long chunk_stride, long long N,
-                                                              int H, int c, long long end, long long f0, int hop, int TP, int pad) {
-    __shared__ float tile[32][33];
-    const int b = blockIdx.z;
-    const int r0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int i = ty; i < 32; i += 8) {   // read: consecutive lanes = consecutive samples (r) of frame slot t0 + i
-        const int tp = t0 + i, r = r0 + tx;
-        const long long idx = (f0 + tp) * hop + r - pad;
-        float v = 0.f;
-        if (tp < TP && r < hop && idx >= 0 && idx >= N - H && idx < end) {
-            if (idx >= N) {
-                const long long at = idx - N;
-                v = chunk[(long long)b * chunk_stride + (at > c - 1 ? c - 1 : at)];
-            } else {
-                v = carry[(long long)b * carry_stride + (idx - (N - H))];
-            }
-        }
-        tile[i][tx] = v;
-    }
-    __syncthreads();
-    float* yb = yp + (long long)b * hop * TP;
-    for (int i = ty; i < 32; i += 8) {   // write: consecutive lanes = consecutive frame slots
-        const int r = r0 + i, tp = t0 + tx;
-        if (r < hop && tp < TP) yb[(long long)r * TP + tp] = tile[tx][i];
-    }
-}
-
-// pv_scan_synth_kernel over the stretched frames [S, S + dS).  mag / theta: (rows, dA + 2), the analysed columns [A, A + dA) and two zero columns
-// behind them (read at the flush only, where they are the columns T and T + 1); column A - 1 is the carried (cmag, ctheta).  The scan starts from
-// the carried total cphi — Theta[k][0] plus the increments of the frames [0, S) — or, at S = 0, from Theta[k][0] itself, and lane 0 stores the new
-// total and the new last column into the other buffers of the pairs.  q, j, alpha, the fmaf and the sincospif are pv_scan_synth_kernel's statements,
-// and the wrapping sum is associative: the bits are the whole row's.
-__global__ __launch_bounds__(256) void pv_scan_synth_stream_kernel(const float* __restrict__ mag, const uint32_t* __restrict__ theta,
-                                                                   const float* __restrict__ cmag, const uint32_t* __restrict__ ctheta,
-                                                                   const uint32_t* __restrict__ cphi, float* __restrict__ nmag,
-                                                                   uint32_t* __restrict__ ntheta, uint32_t* __restrict__ nphi,
-                                                                   float* __restrict__ spec, int rows, int nb, long long A, int dA, long long S,
-                                                                   int dS, int o, int n) {
-    const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(256) void pv_scan_synth_kernel(const float* __restrict__ mag, const uint32_t* __restrict__ theta,
+                                                            float* __restrict__ spec, int rows, int nb, int T, int Tout, int o, int n) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;   // (whole waves leave: the shuffles below always see 64 lanes)
+    if (row >= rows) return;   // (whole waves leave: the shuffles of the scan always see 64 lanes)
     const int b = row / nb, k = row - b * nb;
-    const int W = dA + 2;
-    const float* mr = mag + (long long)row * W;
-    const uint32_t* tr = theta + (long long)row * W;
-    const float cm = cmag[row];
-    const uint32_t ct = ctheta[row];
-    // column j of the row: w = j - A in [-1, dA + 1] by the rule (clamped, so that no address leaves the window)
-    auto col = [&](long long j, float& m, uint32_t& th) {
+    const PvRowCols cols{mag + (long long)row * (T + 2), theta + (long long)row * (T + 2)};
+    float* re = spec + ((long long)b * 2 * nb + k) * Tout;
+    uint32_t carry = cols.tr[0];
+    pv_scan_row(cols, re, re + (long long)nb * Tout, 0, Tout, carry, o, n);
+}
+
+// The stream's window: mr / tr hold the analysed columns [A, A + dA) and two zero columns behind them (read at the flush only, where they are
+// the columns T and T + 1); column A - 1 is the carried (cm, ct).  w = j - A lies in [-1, dA + 1] by the rule and is clamped, so that no address
+// leaves the window.
+struct PvWindowCols {
+    using Index = long long;
+    const float* mr;
+    const uint32_t* tr;
+    float cm;
+    uint32_t ct;
+    long long A;
+    int dA;
+    __device__ __forceinline__ void operator()(long long j, float& m, uint32_t& th) const {
         long long w = j - A;
         w = w > dA + 1 ? dA + 1 : w;
         const int at = w < 0 ? 0 : (int)w;
@@ -193,112 +139,41 @@ __global__ __launch_bounds__(256) void pv_scan_synth_stream_kernel(const float* 
         const uint32_t tw = tr[at];
         m = w < 0 ? cm : mw;
         th = w < 0 ? ct : tw;
-    };
+    }
+};
+
+// pv_scan_synth_kernel over the stretched frames [S, S + dS), mag / theta: (rows, dA + 2).  The scan starts from the carried total cphi —
+// Theta[k][0] plus the increments of the frames [0, S) — or, at S = 0, from Theta[k][0] itself, and lane 0 stores the new total and the new last
+// column into the other buffers of the pairs.  The wrapping sum is associative: the bits are the whole row's.
+__global__ __launch_bounds__(256) void pv_scan_synth_stream_kernel(const float* __restrict__ mag, const uint32_t* __restrict__ theta,
+                                                                   const float* __restrict__ cmag, const uint32_t* __restrict__ ctheta,
+                                                                   const uint32_t* __restrict__ cphi, float* __restrict__ nmag,
+                                                                   uint32_t* __restrict__ ntheta, uint32_t* __restrict__ nphi,
+                                                                   float* __restrict__ spec, int rows, int nb, long long A, int dA, long long S,
+                                                                   int dS, int o, int n) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;   // (whole waves leave: the shuffles of the scan always see 64 lanes)
+    const int b = row / nb, k = row - b * nb;
+    const PvWindowCols cols{mag + (long long)row * (dA + 2), theta + (long long)row * (dA + 2), cmag[row], ctheta[row], A, dA};
     float* re = spec + ((long long)b * 2 * nb + k) * dS;
-    float* im = re + (long long)nb * dS;
-    const float inv_o = 1.0f / (float)o;
     uint32_t carry;
     {
         float m0;
         uint32_t t0;
-        col(0, m0, t0);   // (S = 0 means A <= 1: column 0 is in the window or is the carried one)
+        cols(0, m0, t0);   // (S = 0 means A <= 1: column 0 is in the window or is the carried one)
         carry = S == 0 ? t0 : cphi[row];
     }
-    for (int s0 = 0; s0 < dS; s0 += 64 * kPvUnroll) {
-#pragma unroll
-        for (int u = 0; u < kPvUnroll; ++u) {
-            const int sl = s0 + u * 64 + lane;
-            const bool live = sl < dS;
-            const long long q = (S + (live ? sl : 0)) * n;
-            const long long j = q / o;
-            const int rem = (int)(q - j * o);
-            float m0, m1;
-            uint32_t th0, th1;
-            col(j, m0, th0);
-            col(j + 1, m1, th1);
-            const uint32_t d = live ? th1 - th0 : 0u;
-            uint32_t inc = d;
-#pragma unroll
-            for (int sh = 1; sh < 64; sh <<= 1) {
-                const uint32_t v = __shfl_up(inc, sh, 64);
-                if (lane >= sh) inc += v;
-            }
-            const uint32_t phi = carry + (inc - d);
-            carry += __shfl(inc, 63, 64);
-            if (live) {
-                const float alpha = (float)rem * inv_o;
-                const float m = fmaf(alpha, m1, (1.0f - alpha) * m0);
-                float sn, cs;
-                sincospif((float)(int32_t)phi * (1.0f / 2147483648.0f), &sn, &cs);
-                re[sl] = m * cs;
-                im[sl] = m * sn;
-            }
-        }
-    }
-    if (lane == 0) {
+    pv_scan_row(cols, re, re + (long long)nb * dS, S, dS, carry, o, n);
+    if ((threadIdx.x & 63) == 0) {
         nphi[row] = carry;
-        nmag[row] = dA > 0 ? mr[dA - 1] : cm;
-        ntheta[row] = dA > 0 ? tr[dA - 1] : ct;
+        nmag[row] = dA > 0 ? cols.mr[dA - 1] : cols.cm;
+        ntheta[row] = dA > 0 ? cols.tr[dA - 1] : cols.ct;
     }
 }
 
-// istft_ola_kernel on the stretched samples [Y, Y2): sample tau hop + r - pad sums the frames t = tau - g in ascending g, t a GLOBAL frame index
-// that must lie in [0, Tend) — frames [S, S + dS) from `frames` (B, n_fft, dS), frames [S - G, S) from the carried `cfr` (B, n_fft, G).  During
-// pushes Tend = S + dS cannot bind (every frame that covers a sample below Y2 exists); at the flush it is T'.  Reads run along tau, the write is
-// transposed through LDS so that it runs along r, as in istft_ola_kernel.
-__global__ __launch_bounds__(256) void istft_ola_window_kernel(const float* __restrict__ frames, const float* __restrict__ cfr,
-                                                               const float* __restrict__ win2, float* __restrict__ y, int n_fft, int hop, int pad,
-                                                               int G, long long S, int dS, long long Tend, long long Y, long long Y2,
-                                                               long long y_stride, long long tau0, int n_tau, int r_tiles, int tau_tiles) {
-    __shared__ float tile[32][33];
-    int bid = blockIdx.x;
-    const int tt = bid % tau_tiles;
-    bid /= tau_tiles;
-    const int rt = bid % r_tiles;
-    const int b = bid / r_tiles;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    const float* fb = frames + (long long)b * n_fft * dS;
-    const float* cb = cfr + (long long)b * n_fft * G;
-    for (int rr = ty; rr < 32; rr += 8) {
-        const int r = rt * 32 + rr, ti = tt * 32 + tx;
-        float acc = 0.f, env = 0.f;
-        if (r < hop && ti < n_tau) {
-            const long long tau = tau0 + ti;
-            for (int g = 0; g * hop + r < n_fft; ++g) {
-                const long long t = tau - g;
-                if (t >= 0 && t < Tend) {
-                    float v = 0.f;   // (a frame below S - G is never reached: fv_pv_stream_create's note on G)
-                    if (t >= S) v = fb[(long long)(g * hop + r) * dS + (t - S)];
-                    else if (t >= S - G) v = cb[(long long)(g * hop + r) * G + (t - (S - G))];
-                    acc += v;
-                    env += win2[g * hop + r];
-                }
-            }
-        }
-        tile[rr][tx] = env > 0.f ? acc / env : 0.f;
-    }
-    __syncthreads();
-    for (int cc = ty; cc < 32; cc += 8) {
-        const int ti = tt * 32 + cc, r = rt * 32 + tx;
-        if (r < hop && ti < n_tau) {
-            const long long sidx = (tau0 + ti) * hop + r - pad;
-            if (sidx >= Y && sidx < Y2) y[(long long)b * y_stride + (sidx - Y)] = tile[tx][cc];
-        }
-    }
-}
-
-// nfr[b][f][i] = frame S + dS - G + i: from the new frames at or after S, from the carried ones below it, 0 before frame 0
-__global__ __launch_bounds__(256) void pv_frame_carry_kernel(const float* __restrict__ frames, const float* __restrict__ cfr,
-                                                             float* __restrict__ nfr, int n_fft, int G, long long S, int dS) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long long)n_fft * G) return;
-    const int b = blockIdx.y;
-    const int f = (int)(e / G), i = (int)(e - (long long)f * G);
-    const long long t = S + dS - G + i;
-    float v = 0.f;
-    if (t >= S) v = frames[((long long)b * n_fft + f) * dS + (t - S)];
-    else if (t >= 0) v = cfr[((long long)b * n_fft + f) * G + (t - (S - G))];
-    nfr[((long long)b * n_fft + f) * G + i] = v;
+__global__ void pv_zero_tail_kernel(float* y, long long y_stride, long long from, long long to) {
+    const long long i = from + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < to) y[(long long)blockIdx.y * y_stride + i] = 0.f;
 }
 
 struct Plan {
@@ -407,33 +282,47 @@ struct fv_pitch_shift {
     }
     bool identity() const { return plan.orig_freq == cfg.sample_rate; }
 
-    // [Yp (B, hop, T + taps - 1) | Sp (B, 2 nb, T) | Mg (B, nb, T + 2) | Th (same, uint32) | S2 (B, 2 nb, T') | Fr (B, N, T') | St (B, Ls)], each
-    // part rounded up to 64 floats
+    // The workspace of a launch over nA analysis frames, nS stretched frames, nY stretched samples and nR resampled ones per row:
+    // [Yp (B, hop, nA + taps - 1) | Sp (B, 2 nb, nA) | Mg (B, nb, nA + 2) | Th (same, uint32) | S2 (B, 2 nb, nS) | Fr (B, N, nS) | St (B, nY) |
+    //  Rs (B, nR)], each part rounded up to 64 floats.  A whole-row call: (T, T', Ls, 0); a stream: the most of one call (maxA, maxS, maxY, maxR).
     struct Parts {
-        float *Yp, *Sp, *Mg, *S2, *Fr, *St;
+        float *Yp, *Sp, *Mg, *S2, *Fr, *St, *Rs;
         uint32_t* Th;
         size_t elems;
     };
-    Parts carve(float* ws, int B, const Lengths& l) const {
+    Parts carve(float* ws, int B, size_t nA, size_t nS, size_t nY, size_t nR) const {
         auto up = [](size_t v) { return (v + 63) / 64 * 64; };
         const size_t b = (size_t)B;
-        const size_t n_yp = up(b * plan.hop * (size_t)(l.T + taps - 1)), n_sp = up(b * 2 * nb * (size_t)l.T), n_mg = up(b * nb * (size_t)(l.T + 2));
-        const size_t n_s2 = up(b * 2 * nb * (size_t)l.Tout), n_fr = up(b * plan.N * (size_t)l.Tout), n_st = up(b * (size_t)l.Ls);
-        Parts p;
-        p.Yp = ws, p.Sp = p.Yp + n_yp, p.Mg = p.Sp + n_sp, p.Th = (uint32_t*)(p.Mg + n_mg);
-        p.S2 = p.Mg + 2 * n_mg, p.Fr = p.S2 + n_s2, p.St = p.Fr + n_fr;
-        p.elems = n_yp + n_sp + 2 * n_mg + n_s2 + n_fr + n_st;
-        return p;
+        const size_t n_yp = up(b * plan.hop * (nA + taps - 1)), n_sp = up(b * 2 * nb * nA), n_mg = up(b * nb * (nA + 2));
+        const size_t n_s2 = up(b * 2 * nb * nS), n_fr = up(b * plan.N * nS), n_st = up(b * nY), n_rs = up(b * nR);
+        Parts w;
+        w.Yp = ws, w.Sp = w.Yp + n_yp, w.Mg = w.Sp + n_sp, w.Th = (uint32_t*)(w.Mg + n_mg);
+        w.S2 = w.Mg + 2 * n_mg, w.Fr = w.S2 + n_s2, w.St = w.Fr + n_fr, w.Rs = w.St + n_st;
+        w.elems = n_yp + n_sp + 2 * n_mg + n_s2 + n_fr + n_st + n_rs;
+        return w;
     }
+    Parts carve(float* ws, int B, const Lengths& l) const { return carve(ws, B, (size_t)l.T, (size_t)l.Tout, (size_t)l.Ls, 0); }
 };
+
+// What every call refuses of its output rows (ny samples each, y_stride apart) against its input rows (nx each): the callers word the errors
+enum class OutFault { none, null_out, short_stride, overlap };
+static OutFault out_fault(const float* d_x, int64_t x_stride, int64_t nx, const float* d_y, int64_t y_stride, int64_t ny, int B) {
+    if (ny <= 0) return OutFault::none;
+    if (!d_y) return OutFault::null_out;
+    if (y_stride < ny) return OutFault::short_stride;
+    if (nx > 0 && d_x) {
+        const float *x_end = d_x + (int64_t)(B - 1) * x_stride + nx, *y_end = d_y + (int64_t)(B - 1) * y_stride + ny;
+        if (d_x < y_end && d_y < x_end) return OutFault::overlap;
+    }
+    return OutFault::none;
+}
 
 // the time stretch of `B` rows into rows of Ls samples at y (stride y_stride >= Ls)
 static fv_status pv_stretch(fv_pitch_shift* p, const float* d_x, long long x_stride, float* y, long long y_stride, int B, long long L,
                             const Lengths& l, const fv_pitch_shift::Parts& w, hipStream_t s) {
     const Plan& pl = p->plan;
     const int hop = pl.hop, N = pl.N, nb = p->nb, T = (int)l.T, Tout = (int)l.Tout, TP = T + p->taps - 1;
-    hipLaunchKernelGGL(pv_frame_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, B), dim3(256), 0, s, d_x, w.Yp, x_stride, L, hop, TP, N / 2);
-    FV_HIP_CHECK(hipGetLastError());
+    if (const fv_status st = launch_pv_frame(d_x, x_stride, w.Yp, B, L, hop, TP, N / 2, s)) return st;
     // (the default leaves the calling thread's mode alone: the calls keep the kernels, and the bits, they have always had)
     std::optional<AlgoScope> scope;
     if (p->invariant) scope.emplace(FV_CONV_ALGO_AUTO, true);
@@ -472,17 +361,17 @@ static fv_status pv_call(fv_pitch_shift* p, const char* fn, bool whole, const fl
     const Lengths l = lengths_of(p->plan, L);
     const int64_t out = whole ? L : l.Ls;
     if (out == 0) return FV_OK;   // (a stretch of a row so short that round(L o / n) = 0)
-    if (!d_x || !d_y) {
+    const OutFault of = out_fault(d_x, x_row_stride, L, d_y, y_row_stride, out, batch);
+    if (!d_x || of == OutFault::null_out) {
         set_error("%s: null %s", fn, d_x ? "d_y" : "d_x");
         return FV_ERR_INVALID;
     }
-    if (x_row_stride < L || y_row_stride < out) {
+    if (x_row_stride < L || of == OutFault::short_stride) {
         set_error("%s: row strides (%lld, %lld) are shorter than the rows (L = %lld, %lld outputs)", fn, (long long)x_row_stride,
                   (long long)y_row_stride, (long long)L, (long long)out);
         return FV_ERR_INVALID;
     }
-    const float *x_end = d_x + (int64_t)(batch - 1) * x_row_stride + L, *y_end = d_y + (int64_t)(batch - 1) * y_row_stride + out;
-    if (d_x < y_end && d_y < x_end) {
+    if (of == OutFault::overlap) {
         set_error("%s: d_y overlaps d_x; the pitch shift does not run in place (every frame reads n_fft input samples)", fn);
         return FV_ERR_INVALID;
     }
@@ -538,25 +427,7 @@ struct fv_pv_stream : SampleStream {
     uint32_t* theta(int h) const { return (uint32_t*)(pol[h] + (size_t)B * p->nb); }
     uint32_t* phi(int h) const { return (uint32_t*)(pol[h] + 2 * (size_t)B * p->nb); }
 
-    // [Yp (B, hop, maxA + taps - 1) | Sp (B, 2 nb, maxA) | Mg (B, nb, maxA + 2) | Th (same, uint32) | S2 (B, 2 nb, maxS) | Fr (B, N, maxS) |
-    //  St (B, maxY) | Rs (B, maxR)], each part rounded up to 64 floats
-    struct Parts {
-        float *Yp, *Sp, *Mg, *S2, *Fr, *St, *Rs;
-        uint32_t* Th;
-        size_t elems;
-    };
-    Parts carve(float* ws) const {
-        auto up = [](size_t v) { return (v + 63) / 64 * 64; };
-        const size_t b = (size_t)B, nb = (size_t)p->nb;
-        const size_t n_yp = up(b * p->plan.hop * (size_t)(maxA + p->taps - 1)), n_sp = up(b * 2 * nb * (size_t)maxA);
-        const size_t n_mg = up(b * nb * (size_t)(maxA + 2)), n_s2 = up(b * 2 * nb * (size_t)maxS), n_fr = up(b * p->plan.N * (size_t)maxS);
-        const size_t n_st = up(b * (size_t)maxY), n_rs = up(b * (size_t)maxR);
-        Parts w;
-        w.Yp = ws, w.Sp = w.Yp + n_yp, w.Mg = w.Sp + n_sp, w.Th = (uint32_t*)(w.Mg + n_mg);
-        w.S2 = w.Mg + 2 * n_mg, w.Fr = w.S2 + n_s2, w.St = w.Fr + n_fr, w.Rs = w.St + n_st;
-        w.elems = n_yp + n_sp + 2 * n_mg + n_s2 + n_fr + n_st + n_rs;
-        return w;
-    }
+    fv_pitch_shift::Parts carve(float* ws) const { return p->carve(ws, B, (size_t)maxA, (size_t)maxS, (size_t)maxY, (size_t)maxR); }
     size_t ws_bytes() const { return p->identity() ? 0 : align_up(carve(nullptr).elems * sizeof(float), 256); }
 };
 
@@ -586,16 +457,14 @@ static fv_status pv_stream_step(fv_pv_stream* st, const float* d_x, int64_t x_ro
     const long long N = st->N;
     hipStream_t s = (hipStream_t)stream;
     const auto check_out = [&](long long k) -> fv_status {
-        if (k > 0 && (!d_y || y_row_stride < k)) {
+        const OutFault of = out_fault(d_x, x_row_stride, c, d_y, y_row_stride, k, B);
+        if (of == OutFault::null_out || of == OutFault::short_stride) {
             set_error("%s: %s (this call emits %lld outputs per row)", fn, d_y ? "y_row_stride is shorter than the output" : "null output", k);
             return FV_ERR_INVALID;
         }
-        if (k > 0 && c > 0) {
-            const float *x_end = d_x + (int64_t)(B - 1) * x_row_stride + c, *y_end = d_y + (int64_t)(B - 1) * y_row_stride + k;
-            if (d_x < y_end && d_y < x_end) {
-                set_error("%s: d_y overlaps d_x; the stream does not run in place", fn);
-                return FV_ERR_INVALID;
-            }
+        if (of == OutFault::overlap) {
+            set_error("%s: d_y overlaps d_x; the stream does not run in place", fn);
+            return FV_ERR_INVALID;
         }
         return FV_OK;
     };
@@ -635,15 +504,14 @@ static fv_status pv_stream_step(fv_pv_stream* st, const float* d_x, int64_t x_ro
         set_error("%s: workspace too small (%zu < %zu bytes, fv_pv_stream_workspace_bytes)", fn, ws ? ws_bytes : (size_t)0, st->ws_bytes());
         return FV_ERR_INVALID;
     }
-    const fv_pv_stream::Parts w = st->carve((float*)ws);
+    const fv_pitch_shift::Parts w = st->carve((float*)ws);
     const int hop = pl.hop, F = pl.N, nb = p->nb, G = st->G, H = st->H;
     {
         const AlgoScope scope(FV_CONV_ALGO_AUTO, true);   // every column one fixed-order sum, whatever the launch holds
         if (dA > 0) {
             const int TP = (int)dA + p->taps - 1;
-            hipLaunchKernelGGL(pv_frame_window_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, B), dim3(256), 0, s, st->buf[st->cur], d_x, w.Yp,
-                               st->stride, (long long)x_row_stride, N, H, (int)c, (long long)N2, (long long)r1.A, hop, TP, F / 2);
-            FV_HIP_CHECK(hipGetLastError());
+            if (const fv_status rs = launch_pv_frame_window(st->buf[st->cur], st->stride, d_x, x_row_stride, w.Yp, B, N, H, N2, r1.A, hop, TP, F / 2, s))
+                return rs;
             ConvRun r;
             r.batch = B, r.t_in = TP, r.x = w.Yp, r.y = w.Sp;
             if (const fv_status rs = conv_layer_run(p->stft, r, s)) return rs;
@@ -671,18 +539,12 @@ static fv_status pv_stream_step(fv_pv_stream* st, const float* d_x, int64_t x_ro
         }
     }
     if (dY > 0) {
-        const long long tau0 = (r1.Y + F / 2) / hop;
-        const int n_tau = (int)((r2.Y - 1 + F / 2) / hop - tau0 + 1);
-        const int r_tiles = (hop + 31) / 32, tau_tiles = (n_tau + 31) / 32;
-        hipLaunchKernelGGL(istft_ola_window_kernel, dim3((unsigned)((long long)B * r_tiles * tau_tiles)), dim3(256), 0, s, w.Fr, st->fr[st->fcur],
-                           p->d_win2, w.St, F, hop, F / 2, G, (long long)r1.S, (int)dS, (long long)r2.S, (long long)r1.Y, (long long)r2.Y, dY, tau0,
-                           n_tau, r_tiles, tau_tiles);
-        FV_HIP_CHECK(hipGetLastError());
+        if (const fv_status rs = launch_istft_ola_window(w.Fr, st->fr[st->fcur], p->d_win2, w.St, B, F, hop, F / 2, G, r1.S, (int)dS, r2.S, r1.Y,
+                                                         r2.Y, s))
+            return rs;
     }
     if (dS > 0) {
-        hipLaunchKernelGGL(pv_frame_carry_kernel, dim3((unsigned)(((long long)F * G + 255) / 256), B), dim3(256), 0, s, w.Fr, st->fr[st->fcur],
-                           st->fr[st->fcur ^ 1], F, G, (long long)r1.S, (int)dS);
-        FV_HIP_CHECK(hipGetLastError());
+        if (const fv_status rs = launch_pv_frame_carry(w.Fr, st->fr[st->fcur], st->fr[st->fcur ^ 1], B, F, G, r1.S, (int)dS, s)) return rs;
         st->fcur ^= 1;
     }
     // the resampler: a push writes the caller's rows; the flush goes through Rs, because its last outputs may lie past L

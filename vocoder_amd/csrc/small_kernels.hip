@@ -1,6 +1,6 @@
 // HBM-bound helper kernels around the MFMA conv: narrow-output conv (conv_post), anti-aliased SnakeBeta,
-// depthwise-conv + LayerNorm, ISTFT spectrum / overlap-add.  All are coalesced along T (the contiguous axis of
-// the reference's (B, C, T) layout) and stage their reuse windows in LDS.
+// depthwise-conv + LayerNorm, ISTFT spectrum (its overlap-add is frame_kernels.hip's).  All are coalesced along T (the
+// contiguous axis of the reference's (B, C, T) layout) and stage their reuse windows in LDS.
 
 #include "conv_mfma_impl.h"
 
@@ -971,57 +971,6 @@ fv_status launch_istft_spec(const float* h, float* spec, int B, int n_fft, int T
     return FV_OK;
 }
 
-// Overlap-add + crop + envelope normalisation of vocos ISTFT("same").  frames: (B, n_fft, T), already multiplied by the
-// hann window (folded into the inverse-DFT basis).  Output sample s = tau*hop + r - pad collects
-// frames[g*hop + r][tau - g]; reads are coalesced along tau, the write is transposed through LDS so it is coalesced
-// along r.  win2 = window^2 (n_fft).
-__global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ win2,
-                                                        float* __restrict__ y, int n_fft, int T, int hop, int pad,
-                                                        long long out_len, int r_tiles, int tau_tiles) {
-    __shared__ float tile[32][33];
-    int bid = blockIdx.x;
-    const int tt = bid % tau_tiles;
-    bid /= tau_tiles;
-    const int rt = bid % r_tiles;
-    const int b = bid / r_tiles;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    const float* fb = frames + (long long)b * n_fft * T;
-    const int n_tau = T + (n_fft + hop - 1) / hop;  // hop-frames touched by any analysis frame
-    for (int rr = ty; rr < 32; rr += 8) {
-        const int r = rt * 32 + rr, tau = tt * 32 + tx;
-        float acc = 0.f, env = 0.f;
-        if (r < hop && tau < n_tau) {
-            for (int g = 0; g * hop + r < n_fft; ++g) {
-                const int t = tau - g;
-                if (t >= 0 && t < T) {
-                    acc += fb[(long long)(g * hop + r) * T + t];
-                    env += win2[g * hop + r];
-                }
-            }
-        }
-        tile[rr][tx] = env > 0.f ? acc / env : 0.f;
-    }
-    __syncthreads();
-    for (int cc = ty; cc < 32; cc += 8) {
-        const int tau = tt * 32 + cc, r = rt * 32 + tx;
-        if (r < hop && tau < n_tau) {
-            const long long sidx = (long long)tau * hop + r - pad;
-            if (sidx >= 0 && sidx < out_len) y[(long long)b * out_len + sidx] = tile[tx][cc];
-        }
-    }
-}
-
-fv_status launch_istft_ola(const float* frames, const float* win2, float* y, int B, int n_fft, int T, int hop, int pad,
-                           long long out_len, hipStream_t s) {
-    const int r_tiles = (hop + 31) / 32;
-    const int n_tau = T + (n_fft + hop - 1) / hop;
-    const int tau_tiles = (n_tau + 31) / 32;
-    hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)((long long)B * r_tiles * tau_tiles)), dim3(256), 0, s, frames,
-                       win2, y, n_fft, T, hop, pad, out_len, r_tiles, tau_tiles);
-    FV_HIP_CHECK(hipGetLastError());
-    return FV_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Pitch-template branch of the up-sampling stages (use_template=True, fish_vocoder/modules/generators/hifigan.py:192-204,
 // 233-234):  x[b][c][t] += bias[c] + sum_j w[c][j] * template[b][t*stride + j - pad]   — a strided Conv1d(1 -> C).
@@ -1069,44 +1018,8 @@ fv_status launch_noise_conv_add(const float* tmpl, const float* w, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Log-mel front-end (fish_vocoder/data/transforms/spectrogram.py:25-56): reflect padding + polyphase re-layout, magnitude.
+// Log-mel front-end (fish_vocoder/data/transforms/spectrogram.py:25-56): magnitude (the polyphase re-layout is frame_kernels.hip's).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void polyphase_reflect_kernel(const float* __restrict__ wave, float* __restrict__ yp,
-                                                                int L, int hop, int TP, int pad_l, int pad_r) {
-    __shared__ float tile[32][33];
-    const int b = blockIdx.z;
-    const int r0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const float* wb = wave + (long long)b * L;
-    const long long lpad = (long long)L + pad_l + pad_r;
-    for (int i = ty; i < 32; i += 8) {   // read: consecutive lanes = consecutive samples (r) of frame slot t0 + i
-        const int tp = t0 + i, r = r0 + tx;
-        float v = 0.f;
-        const long long pos = (long long)tp * hop + r;
-        if (tp < TP && r < hop && pos < lpad) {
-            long long idx = pos - pad_l;
-            if (idx < 0) idx = -idx;
-            if (idx >= L) idx = 2LL * (L - 1) - idx;
-            idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
-            v = wb[idx];
-        }
-        tile[i][tx] = v;
-    }
-    __syncthreads();
-    float* yb = yp + (long long)b * hop * TP;
-    for (int i = ty; i < 32; i += 8) {   // write: consecutive lanes = consecutive frame slots
-        const int r = r0 + i, tp = t0 + tx;
-        if (r < hop && tp < TP) yb[(long long)r * TP + tp] = tile[tx][i];
-    }
-}
-
-fv_status launch_polyphase_reflect(const float* wave, float* yp, int B, int L, int hop, int TP, int pad_l, int pad_r, hipStream_t s) {
-    hipLaunchKernelGGL(polyphase_reflect_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, B), dim3(256), 0, s, wave, yp, L, hop, TP,
-                       pad_l, pad_r);
-    FV_HIP_CHECK(hipGetLastError());
-    return FV_OK;
-}
-
 __global__ __launch_bounds__(256) void magnitude_kernel(const float* __restrict__ spec, float* __restrict__ mag, int nb, int T) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long per = (long long)nb * T;
