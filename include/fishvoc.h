@@ -60,7 +60,8 @@ typedef enum fv_model_kind {
     FV_MODEL_LOGMEL = 7,     /* LogMelSpectrogram: (B, 1, L) wave -> (B, n_mels, frames) (data/transforms/spectrogram.py:59-104);
                                 the step right before the generator in test.py:71 */
     FV_MODEL_REFINEGAN = 8   /* fish_vocoder.modules.generators.refinegan.RefineGANGenerator (refinegan.py:182): forward(mel, template)
-                                with AdaIN noise supplied by the caller (fv_forward_refinegan) */
+                                with AdaIN noise supplied by the caller (fv_forward_refinegan) or seeded and computed in the AdaIN kernels
+                                (fv_refinegan_set_noise_seed, fv_forward_refinegan_seeded) */
 } fv_model_kind;
 
 #define FV_MAX_STAGES 8
@@ -274,6 +275,37 @@ FV_API fv_status fv_forward_refinegan(fv_engine* e, const float* d_mel, const fl
                                       float* d_out, int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes,
                                       void* stream);
 
+/* Seeded AdaIN noise.  With a seed set, the standard-normal sample that stands in for torch.randn_like (refinegan.py:125) is computed inside
+ * the AdaIN kernel as a pure function of (seed s, noise row r, AdaIN layer l, channel c of C, absolute position p >= 0 at that layer's rate):
+ *   q = p >> 2, lane = p & 3;
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter = (q & 0xffffffff, q >> 32, r * C + c, l), key = (s & 0xffffffff, s >> 32))  (Random123:
+ *   multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds);
+ *   Box-Muller per pair: u1 = ((xa >> 8) + 1) 2^-24 in (0, 1], u2 = (xb >> 8) 2^-24 in [0, 1), rad = sqrt(-2 ln u1); lanes 0 / 1 are
+ *   rad cos(2 pi u2) / rad sin(2 pi u2) of (x0, x1), lanes 2 / 3 the same of (x2, x3)  (logf, sqrtf, sincospif(2 u2)).
+ * l counts the AdaIN layers in the order of fv_forward_refinegan's d_noise (stage, branch k = 3 / 7 / 11, first / second AdaIN); p is counted
+ * from the utterance's first sample; r = first_row + b for batch row b, so that a shard, or a clip run alone, reproduces row b of the global
+ * batch.  No noise tensor exists, and a window of an utterance regenerates exactly the samples the whole utterance has at those positions: a
+ * seeded engine has a finite reach (fv_reach_frames), runs clips of any length as time tiles and streams (fv_stream_*: a stream's pushes run
+ * eagerly — the window's origin is a kernel scalar, which a captured graph would bake in; a push after the engine's seed was cleared or changed
+ * is refused with FV_ERR_STATE before anything moves).  fv_ragged_* and fv_pool_* stay refused for RefineGAN: their rows start at per-row
+ * origins, which the per-launch (origin, stride) does not express.  vocoder_amd/refinegan_noise.py restates the rule in numpy.
+ *
+ * fv_refinegan_set_noise_seed puts the engine in seeded mode (refinegan.py:125's draw becomes reproducible), fv_refinegan_clear_noise_seed
+ * takes it out (refinegan.py:125 needs the caller's d_noise again); both drop the engine's captured graphs.  first_row >= 0. */
+FV_API fv_status fv_refinegan_set_noise_seed(fv_engine* e, uint64_t seed, int32_t first_row);
+FV_API fv_status fv_refinegan_clear_noise_seed(fv_engine* e);
+/* fv_forward_refinegan with refinegan.py:125's draws computed in the kernels: the input is the frames [origin_frame, origin_frame + t_in) of
+ * its utterance (0 for a whole clip).  FV_ERR_STATE on an engine without a seed.  Clips past the addressing span run as time tiles, each tile
+ * with its clip's noise row at its own origin; at most 65535 clips x tiles per call.  fv_forward_refinegan with explicit d_noise keeps working
+ * on a seeded engine for lengths that run whole; at a tiled length it is refused with FV_ERR_UNSUPPORTED (the explicit layout has no tiled
+ * form). */
+FV_API fv_status fv_forward_refinegan_seeded(fv_engine* e, const float* d_mel, const float* d_template, float* d_out, int32_t batch,
+                                             int32_t t_in, int64_t origin_frame, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The draws of refinegan.py:125 that fv_forward_refinegan_seeded(batch, t_in, origin_frame) computes in its kernels, written in
+ * fv_forward_refinegan's d_noise layout (fv_refinegan_noise_elems floats): the two paths then agree bit for bit.  Needs a seed
+ * (FV_ERR_STATE). */
+FV_API fv_status fv_refinegan_fill_noise(fv_engine* e, float* d_noise, int32_t batch, int32_t t_in, int64_t origin_frame, void* stream);
+
 /* -------- streaming synthesis: push mel chunks, get audio after a fixed lookahead.  No reference counterpart: the reference has no
  *          streaming — its only caller (test.py:88-90) runs whole utterances through `self.generator(input_spec)`; this replaces cutting
  *          windows by hand around that call.  --------
@@ -289,7 +321,8 @@ FV_API fv_status fv_forward_refinegan(fv_engine* e, const float* d_mel, const fl
  *     windows anchor the Winograd lattices elsewhere, as the time tiles do); an utterance of T <= A frames comes out of the flush alone, as
  *     the single window [0, T): bit-identical to fv_forward.
  * Models stream exactly when they are frame-aligned (what the time tiles need): HiFiGAN / BigVGAN (with or without use_template), Firefly,
- * Vocos and ISTFT heads with padding "same", the ConvNeXt encoder alone (hop = 1).  RefineGAN, LOGMEL, the "center" ISTFT head and upsamplers
+ * Vocos and ISTFT heads with padding "same", the ConvNeXt encoder alone (hop = 1), RefineGAN once a noise seed is set
+ * (fv_refinegan_set_noise_seed).  RefineGAN without a seed, LOGMEL, the "center" ISTFT head and upsamplers
  * whose output is not hop x frames get FV_ERR_UNSUPPORTED at fv_stream_create, with the reason in fv_last_error. */
 
 /* R, the engine's one-sided reach in input frames (the halo of the time tiles); -1: this model cannot stream. */
@@ -843,7 +876,7 @@ FV_API fv_status fv_template_forward(fv_template* p, const float* d_f0, int64_t 
  * bit-identical to fv_template_forward over the whole rows.
  *
  * Every call validates everything before it enqueues anything, enqueues eagerly on `stream` and never synchronises; a refused call changes
- * nothing.  Not built: per-session (non-lockstep) template streams for fv_pool_step, a streaming RefineGAN. */
+ * nothing.  Not built: per-session (non-lockstep) template streams for fv_pool_step. */
 typedef struct fv_yin_stream fv_yin_stream;
 typedef struct fv_osc_stream fv_osc_stream;
 

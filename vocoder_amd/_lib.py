@@ -42,6 +42,7 @@ EXPORTS = (
     "fv_conv_forward", "fv_conv_destroy", "fv_last_error", "fv_abi_version", "fv_last_kernel",
     "fv_profile_begin", "fv_profile_end", "fv_conv_pair_forward", "fv_forward_template",
     "fv_set_precision", "fv_conv_set_precision", "fv_refinegan_noise_elems", "fv_forward_refinegan",
+    "fv_refinegan_set_noise_seed", "fv_refinegan_clear_noise_seed", "fv_forward_refinegan_seeded", "fv_refinegan_fill_noise",
     "fv_set_graph_replay", "fv_get_graph_replay", "fv_reload_env", "fv_set_conv_algorithm", "fv_set_batch_invariant", "fv_conv_set_algorithm",
     "fv_reach_frames", "fv_stream_create", "fv_stream_workspace_bytes", "fv_stream_pending_frames", "fv_stream_push", "fv_stream_flush",
     "fv_stream_reset", "fv_stream_destroy",
@@ -205,6 +206,14 @@ def lib() -> ctypes.CDLL:
     L.fv_refinegan_noise_elems.restype = ctypes.c_int64
     L.fv_forward_refinegan.argtypes = [vp, vp, vp, vp, vp, _i32, _i32, vp, ctypes.c_size_t, vp]
     L.fv_forward_refinegan.restype = _i32
+    L.fv_refinegan_set_noise_seed.argtypes = [vp, ctypes.c_uint64, _i32]
+    L.fv_refinegan_set_noise_seed.restype = _i32
+    L.fv_refinegan_clear_noise_seed.argtypes = [vp]
+    L.fv_refinegan_clear_noise_seed.restype = _i32
+    L.fv_forward_refinegan_seeded.argtypes = [vp, vp, vp, vp, _i32, _i32, ctypes.c_int64, vp, ctypes.c_size_t, vp]
+    L.fv_forward_refinegan_seeded.restype = _i32
+    L.fv_refinegan_fill_noise.argtypes = [vp, vp, _i32, _i32, ctypes.c_int64, vp]
+    L.fv_refinegan_fill_noise.restype = _i32
     L.fv_conv_create.argtypes = [ctypes.POINTER(ConvDesc), fp, fp, ctypes.POINTER(vp)]
     L.fv_conv_create.restype = _i32
     L.fv_conv_output_length.argtypes = [vp, _i32]

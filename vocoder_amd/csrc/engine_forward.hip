@@ -629,9 +629,10 @@ fv_status check_forward(fv_engine* e, const float* d_in, const float* d_template
 }
 
 fv_status forward_common(fv_engine* e, const float* d_in, const float* d_template, const float* d_noise, float* d_out,
-                         int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes, void* stream) {
+                         int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes, void* stream, bool seeded,
+                         int64_t origin_frame) {
     if (const fv_status st = check_forward(e, d_in, d_template, d_out, batch, t_in, d_workspace, workspace_bytes)) return st;
-    const ForwardScope scope(e, d_template, d_noise);
+    const ForwardScope scope(e, d_template, d_noise, seeded, origin_frame);
     hipStream_t s = (hipStream_t)stream;
     float* ws = (float*)d_workspace;
 
@@ -641,7 +642,8 @@ fv_status forward_common(fv_engine* e, const float* d_in, const float* d_templat
     // The legacy default stream (0: where the reference's own call runs, test.py:88-90) cannot be captured, but an instantiated graph can be launched on
     // it: the sequence is captured on an engine-owned stream and replayed on stream 0 — without the two cross-stream waits a redirect through a side
     // stream costs every call (single clip: ~0.04 ms of 0.75).
-    fv_engine::GraphKey key{d_in, d_out, d_workspace, d_template, d_noise, batch, t_in, s};
+    fv_engine::GraphKey key{d_in, d_out, d_workspace, d_template, d_noise, batch, t_in, s, seeded, seeded ? e->noise_seed : 0,
+                            seeded ? e->noise_first_row : 0, seeded ? origin_frame : 0};
     const bool graphable = e->opt.use_graph && !e->profiling;
     if (graphable) {
         for (auto& g : e->graphs)

@@ -333,9 +333,14 @@ struct fv_engine {
         const void* noise;
         int batch, t_in;
         hipStream_t stream;
+        // seeded RefineGAN: kernel scalars are baked into a captured graph, so a replay under another seed, row or origin would draw other noise
+        bool seeded;
+        uint64_t seed;
+        int32_t first_row;
+        int64_t origin_frame;
         bool operator==(const GraphKey& o) const {
             return in == o.in && out == o.out && ws == o.ws && tmpl == o.tmpl && noise == o.noise && batch == o.batch && t_in == o.t_in &&
-                   stream == o.stream;
+                   stream == o.stream && seeded == o.seeded && seed == o.seed && first_row == o.first_row && origin_frame == o.origin_frame;
         }
     };
     struct GraphEntry {
@@ -516,6 +521,15 @@ struct fv_engine {
     fv_status build_refinegan();
     fv_status run_refinegan(const float* d_mel, float* d_out, int B, int T, float* ws, hipStream_t s);
     const float* cur_noise = nullptr;      // set by fv_forward_refinegan for the duration of one call
+    // Seeded AdaIN noise (fv_refinegan_set_noise_seed): engine state, then what one call sets for its duration — cur_seeded: this call's AdaIN
+    // launches compute their noise (no cur_noise); cur_origin_frame: the utterance frame its input starts at; cur_tile: run_model's tile plan
+    // (n tiles per clip, stride and the pulled-back last start in frames)
+    bool noise_seeded = false;
+    uint64_t noise_seed = 0;
+    int32_t noise_first_row = 0;
+    bool cur_seeded = false;
+    int64_t cur_origin_frame = 0;
+    int cur_tile_n = 1, cur_tile_stride = 0, cur_tile_last = 0;
     fv_status run_model(const float* d_in, float* d_out, int batch, int t_in, float* ws, hipStream_t s);
     fv_status run_model_whole(const float* d_in, float* d_out, int batch, int t_in, float* ws, hipStream_t s);
     // Long clips: time tiles with halo recompute, run as a BATCH of tiles (SURVEY §5 long-context row; VERDICT r4 missing 3)
@@ -575,9 +589,12 @@ struct ProfScope {
 struct ForwardScope {
     AlgoScope algo;
     ProfScope prof;
-    ForwardScope(fv_engine* e, const float* d_template, const float* d_noise) : algo(e->algo, e->invariant), prof(e) {
+    ForwardScope(fv_engine* e, const float* d_template, const float* d_noise, bool seeded = false, int64_t origin_frame = 0)
+        : algo(e->algo, e->invariant), prof(e) {
         e->cur_template = d_template;
         e->cur_noise = d_noise;
+        e->cur_seeded = seeded;
+        e->cur_origin_frame = origin_frame;
     }
 };
 
@@ -585,7 +602,11 @@ struct ForwardScope {
 fv_status check_template(const fv_engine* e, const float* d_template);
 fv_status check_forward(fv_engine* e, const float* d_in, const float* d_template, float* d_out, int32_t batch, int32_t t_in,
                         void* d_workspace, size_t workspace_bytes);
+// seeded: a RefineGAN forward whose AdaIN noise is computed in the kernels, for an input that starts at frame origin_frame of its utterance
 fv_status forward_common(fv_engine* e, const float* d_in, const float* d_template, const float* d_noise, float* d_out,
-                         int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes, void* stream);
+                         int32_t batch, int32_t t_in, void* d_workspace, size_t workspace_bytes, void* stream, bool seeded = false,
+                         int64_t origin_frame = 0);
 // engine_refinegan.hip
 size_t refine_ws_elems(const fv_engine* e, int B, int T);
+int64_t refine_reach(const RefineModel& m);               // one-sided reach in input frames (reach_frames)
+int64_t refine_max_elems_per_frame(const RefineModel& m);   // largest per-item tensor per input frame; 0: the lengths do not line up (tile_frame_limit)

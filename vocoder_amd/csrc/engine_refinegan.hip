@@ -1,4 +1,5 @@
-// RefineGAN: builder, workspace sizing, forward and its two ABI entries (template + AdaIN noise).
+// RefineGAN: builder, workspace sizing, reach, forward and its ABI entries (template + AdaIN noise, given by the caller or seeded and computed in
+// the AdaIN kernels).
 #include "engine_internal.h"
 
 // RefineGAN builds AdaIN(channels=...) without forwarding the generator's slope (refinegan.py:157,165): always 0.2
@@ -96,6 +97,38 @@ size_t refine_ws_elems(const fv_engine* e, int B, int T) {
     return skips + 7 * ((refine_max_elems(e->refine, down, up) * B + 63) / 64 * 64);
 }
 
+int64_t refine_max_elems_per_frame(const RefineModel& m) {
+    std::vector<int64_t> down, up;
+    if (!m.lengths(1 << 10, down, up)) return 0;
+    return (int64_t)(refine_max_elems(m, down, up) >> 10);
+}
+
+// One-sided reach in input frames (vocoder_amd/refinegan_noise.py refinegan_reach restates it): an upper bound on how far an output sample's
+// inputs, mel and template, lie from it.  Walked backwards from the output in samples at each layer's own rate: a conv adds (k - 1) / 2 *
+// dilation, a ResBlock's six convs 2 * (k - 1) / 2 * (1 + 3 + 5); the up-sampling interpolation divides by its rate and adds its two taps, the
+// down-sampling one multiplies by its rate and adds rate + 1; AdaIN is pointwise (refinegan.py:124-127: no normalisation).  Every skip tensor
+// is needed as far as its farther consumer reaches: the up stage that concatenates it, or the rest of the down path.
+int64_t refine_reach(const RefineModel& m) {
+    const fv_refinegan_config& c = m.cfg;
+    const int S = c.num_stages;
+    int64_t R = 3;   // output_conv (k = 7)
+    std::vector<int64_t> at_skip((size_t)S, 0);
+    for (int i = S - 1; i >= 0; --i) {
+        R += 2 * 5 * 9 + 3;   // the widest branch (k = 11) and input_conv (k = 7)
+        at_skip[(size_t)(S - 1 - i)] = R;
+        const int u = c.upsample_rates[i];
+        R = (R + u - 1) / u + 2;
+    }
+    const int64_t mel = R + 3;   // mel_conv (k = 7), at the frame rate
+    int64_t need = R;
+    for (int k = S - 1; k >= 0; --k) {
+        const int d = c.downsample_rates[k];
+        need = std::max(at_skip[(size_t)k], (need + 2 * 3 * 9) * d + d + 1);
+    }
+    const int64_t tmpl = need + 3;   // template_conv (k = 7), in samples
+    return std::max(mel, (tmpl + c.hop_length - 1) / c.hop_length + 1);
+}
+
 fv_status fv_engine::run_refinegan(const float* d_mel, float* d_out, int B, int T, float* ws, hipStream_t s) {
     const RefineModel& m = refine;
     const int S = m.cfg.num_stages;
@@ -107,6 +140,14 @@ fv_status fv_engine::run_refinegan(const float* d_mel, float* d_out, int B, int 
     }
     if (down[0] >= (1LL << 31)) {
         set_error("refinegan: clip too long");
+        return FV_ERR_UNSUPPORTED;
+    }
+    if (!cur_noise && !(cur_seeded && noise_seeded)) {
+        set_error("refinegan: no AdaIN noise for this forward (fv_forward_refinegan's d_noise, or fv_refinegan_set_noise_seed)");
+        return FV_ERR_STATE;
+    }
+    if (!cur_noise && B > 65535) {
+        set_error("refinegan: %d rows (clips x time tiles) in one seeded forward, more than 65535: split the batch", B);
         return FV_ERR_UNSUPPORTED;
     }
     // ---- workspace ----
@@ -193,9 +234,28 @@ fv_status fv_engine::run_refinegan(const float* d_mel, float* d_out, int B, int 
     // ---- up path ----
     const float* xcur = cat0;
     const float* noise = cur_noise;
+    int layer = 0;             // AdaIN layers in order of use: the seeded noise's `l`
+    int64_t spf = 1;           // samples per frame at stage i
+    // v = leaky_relu(x + noise * weight[c]): the noise from the caller's tensor, or computed in the kernel (seeded: refinegan.py:125's draw
+    // becomes a function of the absolute position, so a window of an utterance sees the whole utterance's samples)
+    auto adain = [&](const float* x, const float* w, float* y, int C, int t, int accumulate, float scale) -> fv_status {
+        const size_t nelem = (size_t)B * C * t;
+        if (noise) {
+            FV_PROF(s, "adain", (accumulate ? 4.0 : 3.0) * nelem, (accumulate ? 16.0 : 12.0) * nelem,
+                    launch_adain(x, noise, w, y, B, C, t, kAdaINSlope, accumulate, scale, s));
+            noise += nelem;
+        } else {
+            const SeededNoise sn{noise_seed, noise_first_row, cur_tile_n, cur_origin_frame * spf, cur_tile_stride * spf, cur_tile_last * spf};
+            FV_PROF(s, "adain_seeded", (accumulate ? 4.0 : 3.0) * nelem, (accumulate ? 12.0 : 8.0) * nelem,
+                    launch_adain_seeded(x, w, y, B, C, t, kAdaINSlope, accumulate, scale, sn, layer, s));
+        }
+        ++layer;
+        return FV_OK;
+    };
     for (int i = 0; i < S; ++i) {
         const RefineUp& u = *m.ups[i];
         const int t = (int)up[i + 1];
+        spf *= u.rate;
         float* CAT = P[0];
         float* XI = P[1];
         float* XA = P[2];
@@ -214,14 +274,10 @@ fv_status fv_engine::run_refinegan(const float* d_mel, float* d_out, int B, int 
         r.x = CAT;
         r.y = XI;
         if ((st = conv_layer_run(u.input_conv, r, s))) return st;
-        const size_t nelem = (size_t)B * u.cout * t;
         for (int j = 0; j < 3; ++j) {
-            FV_PROF(s, "adain", 3.0 * nelem, 12.0 * nelem, launch_adain(XI, noise, u.d_w1[j], XA, B, u.cout, t, kAdaINSlope, 0, 1.0f, s));
-            noise += nelem;
+            if ((st = adain(XI, u.d_w1[j], XA, u.cout, t, 0, 1.0f))) return st;
             if ((st = resblock(u.rb[j], XA, CAT, XT, XB, t, /*post_leaky=*/false))) return st;   // CAT is free again: branch output
-            FV_PROF(s, "adain", 4.0 * nelem, 16.0 * nelem,
-                    launch_adain(CAT, noise, u.d_w2[j], Y, B, u.cout, t, kAdaINSlope, j > 0, j == 2 ? 1.0f / 3.0f : 1.0f, s));
-            noise += nelem;
+            if ((st = adain(CAT, u.d_w2[j], Y, u.cout, t, j > 0, j == 2 ? 1.0f / 3.0f : 1.0f))) return st;
         }
         xcur = Y;
     }
@@ -255,7 +311,103 @@ FV_API fv_status fv_forward_refinegan(fv_engine* e, const float* d_mel, const fl
         set_error("fv_forward_refinegan: template (B, 1, T*hop) and noise (fv_refinegan_noise_elems floats) are required");
         return FV_ERR_INVALID;
     }
+    if (e->noise_seeded && e->finalized && t_in >= 1 && e->tile_plan(t_in).n > 1) {
+        set_error("fv_forward_refinegan: RefineGAN with explicit noise runs whole clips only and %d frames run as time tiles on this seeded "
+                  "engine (the explicit noise layout has no tiled form): use fv_forward_refinegan_seeded", t_in);
+        return FV_ERR_UNSUPPORTED;
+    }
     return forward_common(e, d_mel, d_template, d_noise, d_out, batch, t_in, d_workspace, workspace_bytes, stream);
+}
+
+static fv_status seeded_preamble(const fv_engine* e, const char* fn, int64_t origin_frame) {
+    if (!e || e->cfg.model != FV_MODEL_REFINEGAN) {
+        set_error("%s: not a RefineGAN engine", fn);
+        return FV_ERR_INVALID;
+    }
+    if (!e->finalized) {
+        set_error("%s: call fv_finalize first", fn);
+        return FV_ERR_STATE;
+    }
+    if (!e->noise_seeded) {
+        set_error("%s: the engine has no noise seed (fv_refinegan_set_noise_seed)", fn);
+        return FV_ERR_STATE;
+    }
+    if (origin_frame < 0 || origin_frame > (1LL << 40)) {
+        set_error("%s: origin_frame = %lld, outside [0, 2^40]", fn, (long long)origin_frame);
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+
+FV_API fv_status fv_refinegan_set_noise_seed(fv_engine* e, uint64_t seed, int32_t first_row) {
+    if (!e || e->cfg.model != FV_MODEL_REFINEGAN) {
+        set_error("fv_refinegan_set_noise_seed: not a RefineGAN engine");
+        return FV_ERR_INVALID;
+    }
+    if (first_row < 0) {
+        set_error("fv_refinegan_set_noise_seed: first_row = %d must be >= 0", first_row);
+        return FV_ERR_INVALID;
+    }
+    e->noise_seeded = true;
+    e->noise_seed = seed;
+    e->noise_first_row = first_row;
+    e->drop_graphs();
+    return FV_OK;
+}
+
+FV_API fv_status fv_refinegan_clear_noise_seed(fv_engine* e) {
+    if (!e || e->cfg.model != FV_MODEL_REFINEGAN) {
+        set_error("fv_refinegan_clear_noise_seed: not a RefineGAN engine");
+        return FV_ERR_INVALID;
+    }
+    e->noise_seeded = false;
+    e->noise_seed = 0;
+    e->noise_first_row = 0;
+    e->drop_graphs();
+    return FV_OK;
+}
+
+FV_API fv_status fv_forward_refinegan_seeded(fv_engine* e, const float* d_mel, const float* d_template, float* d_out, int32_t batch,
+                                             int32_t t_in, int64_t origin_frame, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (const fv_status st = seeded_preamble(e, "fv_forward_refinegan_seeded", origin_frame)) return st;
+    if (!d_template) {
+        set_error("fv_forward_refinegan_seeded: the template (B, 1, T*hop) is required");
+        return FV_ERR_INVALID;
+    }
+    if (batch >= 1 && t_in >= 1 && (int64_t)batch * e->tile_plan(t_in).n > 65535) {
+        set_error("fv_forward_refinegan_seeded: %d clips x %d time tiles exceed 65535 rows per call: split the batch", batch, e->tile_plan(t_in).n);
+        return FV_ERR_UNSUPPORTED;
+    }
+    return forward_common(e, d_mel, d_template, nullptr, d_out, batch, t_in, d_workspace, workspace_bytes, stream, true, origin_frame);
+}
+
+FV_API fv_status fv_refinegan_fill_noise(fv_engine* e, float* d_noise, int32_t batch, int32_t t_in, int64_t origin_frame, void* stream) {
+    if (const fv_status st = seeded_preamble(e, "fv_refinegan_fill_noise", origin_frame)) return st;
+    if (!d_noise || batch < 1 || batch > 65535 || t_in < 1) {
+        set_error("fv_refinegan_fill_noise: null noise buffer, or batch (%d) outside [1, 65535], or t_in (%d) < 1", batch, t_in);
+        return FV_ERR_INVALID;
+    }
+    int64_t t = t_in, spf = 1;
+    for (auto& u : e->refine.ups) {
+        t *= u->rate;
+        if (t >= (1LL << 31)) {
+            set_error("fv_refinegan_fill_noise: clip too long");
+            return FV_ERR_UNSUPPORTED;
+        }
+    }
+    const ProfScope prof(e);
+    hipStream_t s = (hipStream_t)stream;
+    int layer = 0;
+    t = t_in;
+    for (auto& u : e->refine.ups) {
+        t *= u->rate;
+        spf *= u->rate;
+        const SeededNoise sn{e->noise_seed, e->noise_first_row, 1, origin_frame * spf, 0, 0};
+        const size_t nelem = (size_t)batch * u->cout * (size_t)t;
+        for (int j = 0; j < 6; ++j, ++layer, d_noise += nelem)
+            FV_PROF(s, "refinegan_fill_noise", 0.0, 4.0 * nelem, launch_refinegan_fill_noise(d_noise, batch, u->cout, (int)t, sn, layer, s));
+    }
+    return FV_OK;
 }
 
 }  // extern "C"

@@ -40,7 +40,11 @@ int fv_engine::reach_frames() const {
         case FV_MODEL_ISTFT_HEAD: R = (cfg.head.n_fft + cfg.head.hop_length - 1) / cfg.head.hop_length; break;
         case FV_MODEL_VOCOS: R = cnx_reach(cnx) + (cfg.head.n_fft + cfg.head.hop_length - 1) / cfg.head.hop_length; break;
         case FV_MODEL_FIREFLY: R = cnx_reach(cnx) + ups_reach(ups); break;
-        default: return -1;   // LOGMEL / REFINEGAN: not tiled
+        case FV_MODEL_REFINEGAN:
+            if (!noise_seeded) return -1;   // its AdaIN noise exists per call only: no window can reproduce it
+            R = refine_reach(refine);
+            break;
+        default: return -1;   // LOGMEL: not tiled
     }
     return (int)std::min<int64_t>(R + 2, 1 << 20);
 }
@@ -51,8 +55,8 @@ int fv_engine::frame_hop(int t_a, int t_b, const char** why) const {
     const char* r = nullptr;
     if (cfg.model == FV_MODEL_LOGMEL)
         r = "the log-mel front-end (wave -> mel) is not frame-windowed";
-    else if (cfg.model == FV_MODEL_REFINEGAN)
-        r = "RefineGAN cannot be windowed (its U-Net spans the whole clip and its AdaIN noise is drawn per call)";
+    else if (cfg.model == FV_MODEL_REFINEGAN && !noise_seeded)
+        r = "RefineGAN cannot be windowed without a noise seed (its AdaIN noise is drawn per call: fv_refinegan_set_noise_seed)";
     else if (reach_frames() < 0)
         r = "the model has no finite reach";
     else if ((cfg.model == FV_MODEL_VOCOS || cfg.model == FV_MODEL_ISTFT_HEAD) && head.center())
@@ -77,6 +81,10 @@ int fv_engine::tile_frame_limit() const {
         case FV_MODEL_ISTFT_HEAD: per_frame = std::max<int64_t>(2 * head.nb, cfg.head.n_fft); break;
         case FV_MODEL_VOCOS: per_frame = std::max<int64_t>(4LL * cnx.max_dim(), std::max<int64_t>(2 * head.nb, cfg.head.n_fft)); break;
         case FV_MODEL_FIREFLY: per_frame = std::max<int64_t>(4LL * cnx.max_dim(), ups.max_elems(1 << 10) >> 10); break;
+        case FV_MODEL_REFINEGAN:   // tiled only with seeded noise (reach_frames); cat([x, skip]) at the output rate is the largest tensor
+            per_frame = noise_seeded ? refine_max_elems_per_frame(refine) : 0;
+            if (per_frame < 1) return 0;
+            break;
         default: return 0;
     }
     return (int)std::min<int64_t>((1LL << 29) / std::max<int64_t>(per_frame, 1), 1 << 30);
@@ -84,7 +92,7 @@ int fv_engine::tile_frame_limit() const {
 fv_engine::TilePlan fv_engine::tile_plan(int t_in) const {
     TilePlan p;
     const int reach = reach_frames();
-    int limit = tile_frame_limit();   // 0 for the models that are never tiled (LOGMEL / REFINEGAN)
+    int limit = tile_frame_limit();   // 0 for the models that are never tiled (LOGMEL, RefineGAN without a noise seed)
     if (opt.tile_frames_override > 0) limit = std::min(limit, std::max(opt.tile_frames_override, 4 * reach));
     if (limit <= 0 || t_in <= limit) return p;
     if (limit < 4 * reach) return p;   // (a model whose reach does not fit the span: the per-layer check reports it)
@@ -190,7 +198,13 @@ fv_status fv_engine::run_model(const float* d_in, float* d_out, int batch, int t
         FV_PROF(s, "gather_tiles", 0.0, 8.0 * bn * lout, launch_gather_tiles(cur_template, w.tmpl, batch, 1, t_in, tp.n, tp.L, tp.stride, hop, s));
         cur_template = w.tmpl;
     }
+    // seeded RefineGAN: tile i of a clip draws the clip's noise row at the tile's own start (TilePlan::start), not at a plain multiple
+    cur_tile_n = tp.n;
+    cur_tile_stride = tp.stride;
+    cur_tile_last = t_in - tp.L;
     st = run_model_whole(w.in, w.out, bn, tp.L, w.model, s);
+    cur_tile_n = 1;
+    cur_tile_stride = cur_tile_last = 0;
     cur_template = clip_template;
     if (st) return st;
     FV_PROF(s, "scatter_tiles", 0.0, 8.0 * batch * cout * clip_out,
@@ -266,6 +280,11 @@ static inline Emission emission(int64_t F, int64_t E, int64_t n, int K, int A, b
 struct fv_stream : RingWindows {
     int64_t F = 0, E = 0;
     bool flushed = false;
+    // RefineGAN: the noise seed the stream was created under — its reach, ring and workspace were sized for a seeded engine, and every window
+    // draws the noise of its own position in the utterance
+    bool seeded = false;
+    uint64_t seed = 0;
+    int32_t first_row = 0;
 };
 
 static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_template, int32_t n, bool flush, float* d_out,
@@ -299,6 +318,10 @@ static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_t
             return FV_ERR_INVALID;
         }
     }
+    if (st->seeded && !(st->e->noise_seeded && st->e->noise_seed == st->seed && st->e->noise_first_row == st->first_row)) {
+        set_error("%s: the engine's noise seed was cleared or changed since this RefineGAN stream was created: create a new stream", fn);
+        return FV_ERR_STATE;
+    }
     if (const fv_status r = st->ws.check(fn, "fv_stream_workspace_bytes", d_workspace, workspace_bytes)) return r;
     const Emission em = emission(st->F, st->E, flush ? 0 : n, st->K, st->A, flush);
     const int64_t F = em.F2, E2 = em.E2;
@@ -324,7 +347,8 @@ static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_t
     }
     if (emit) {
         const int W = (int)(F - w);
-        const fv_status r = forward_common(e, win.in, win.tmpl, nullptr, win.out, B, W, win.model, st->ws.model_bytes, stream);
+        // seeded RefineGAN: the window [w, F) draws the utterance's noise at w (the key of a captured graph holds w: steady-state pushes run eagerly)
+        const fv_status r = forward_common(e, win.in, win.tmpl, nullptr, win.out, B, W, win.model, st->ws.model_bytes, stream, st->seeded, w);
         if (r) return r;
         const int64_t len = (E2 - st->E) * hop;
         FV_PROF(s, "stream_crop", 0.0, 8.0 * B * st->cout * len,
@@ -349,6 +373,11 @@ FV_API fv_status fv_stream_create(fv_engine* e, const fv_stream_config* cfg, fv_
     if (const fv_status r = create_preamble(e, cfg, out, "fv_stream_create", "stream", &st->hop)) return r;
     if (const fv_status r = st->create(e, "fv_stream_create", "batch", cfg->batch, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames))
         return r;
+    if (e->cfg.model == FV_MODEL_REFINEGAN) {
+        st->seeded = true;
+        st->seed = e->noise_seed;
+        st->first_row = e->noise_first_row;
+    }
     *out = st.release();
     return FV_OK;
 }
@@ -498,6 +527,11 @@ FV_API fv_status fv_ragged_create(fv_engine* e, const int32_t* host_lengths, int
                                   int32_t max_groups, fv_ragged** out) {
     int hop = 0;
     if (const fv_status st = create_preamble(e, host_lengths, out, "fv_ragged_create", "run ragged batches", &hop)) return st;
+    if (e->cfg.model == FV_MODEL_REFINEGAN) {
+        set_error("fv_ragged_create: this model cannot run ragged batches: the windows of a RefineGAN batch start at per-row origins, and its "
+                  "seeded AdaIN noise takes one (origin, stride) per launch");
+        return FV_ERR_UNSUPPORTED;
+    }
     if (batch < 1 || t_max < 1) {
         set_error("fv_ragged_create: batch (%d) and t_max (%d) must be >= 1", batch, t_max);
         return FV_ERR_INVALID;
@@ -739,6 +773,11 @@ FV_API int32_t fv_pool_plan(const fv_pool_config* cfg, const int64_t* received, 
 FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool** out) {
     std::unique_ptr<fv_pool> p(new fv_pool());
     if (const fv_status r = create_preamble(e, cfg, out, "fv_pool_create", "stream", &p->hop)) return r;
+    if (e->cfg.model == FV_MODEL_REFINEGAN) {
+        set_error("fv_pool_create: this model cannot run session pools: the sessions of a RefineGAN pool advance to per-row origins, and its "
+                  "seeded AdaIN noise takes one (origin, stride) per launch");
+        return FV_ERR_UNSUPPORTED;
+    }
     if (const fv_status r = p->create(e, "fv_pool_create", "sessions", cfg->sessions, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames))
         return r;
     const size_t S = (size_t)p->rows;

@@ -472,5 +472,16 @@ fv_status launch_copy_channels(const float* x, float* y, int B, int C, int T, in
 fv_status launch_mean_of_three(const float* a, const float* b, const float* c, float* y, long long n, hipStream_t s);   // ((a + b) + c) / 3
 fv_status launch_adain(const float* x, const float* noise, const float* w, float* y, int B, int C, int T, float slope,
                        int accumulate, float scale, hipStream_t s);
+// Seeded AdaIN noise (fv_refinegan_set_noise_seed): the sample is computed in the kernel from (seed, noise row, layer, channel, absolute position).
+// Tensor row i is clip i / n (noise row first_row + i / n) at sample origin origin0 + min((i % n) * stride, last), all in samples at the
+// launch's own rate (TilePlan::start's rule; n = 1 for a whole forward and a stream window).
+struct SeededNoise {
+    unsigned long long seed = 0;
+    int first_row = 0, n = 1;
+    long long origin0 = 0, stride = 0, last = 0;
+};
+fv_status launch_adain_seeded(const float* x, const float* w, float* y, int B, int C, int T, float slope, int accumulate, float scale,
+                              const SeededNoise& sn, int layer, hipStream_t s);
+fv_status launch_refinegan_fill_noise(float* out, int B, int C, int T, const SeededNoise& sn, int layer, hipStream_t s);   // the explicit layout
 
 }  // namespace fv

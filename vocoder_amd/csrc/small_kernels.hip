@@ -1122,6 +1122,131 @@ fv_status launch_adain(const float* x, const float* noise, const float* w, float
     return FV_OK;
 }
 
+// Seeded AdaIN noise (fv_refinegan_set_noise_seed; vocoder_amd/refinegan_noise.py states the rule in numpy): the standard-normal sample that
+// stands in for torch.randn_like (refinegan.py:125) is a pure function of (seed, noise row, AdaIN layer, channel, absolute sample position p):
+// Philox4x32-10 (Random123) on the counter (q lo, q hi, row * C + channel, layer), q = p >> 2, under the key (seed lo, seed hi), then Box-Muller on
+// (x0, x1) for lanes p & 3 = 0, 1 and on (x2, x3) for lanes 2, 3.  One call serves the four positions of an absolute quad.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned x[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    x[0] = c0;
+    x[1] = c1;
+    x[2] = c2;
+    x[3] = c3;
+}
+// The precise logf / sqrtf / sincospif and explicitly rounded products: the fill kernel and the fused AdaIN kernel share this function and agree
+// bit for bit.  u1 = ((xa >> 8) + 1) 2^-24 in (0, 1], u2 = (xb >> 8) 2^-24 in [0, 1): both exact in fp32, and so is 2 u2.
+__device__ __forceinline__ void seeded_normal4(unsigned long long seed, long long q, unsigned row_channel, unsigned layer, float z[4]) {
+    unsigned x[4];
+    philox4x32_10((unsigned)q, (unsigned)((unsigned long long)q >> 32), row_channel, layer, (unsigned)seed, (unsigned)(seed >> 32), x);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = __fmul_rn((float)((x[2 * h] >> 8) + 1u), 5.9604644775390625e-8f);
+        const float u2x2 = __fmul_rn((float)(x[2 * h + 1] >> 8), 1.1920928955078125e-7f);
+        const float rad = sqrtf(__fmul_rn(-2.0f, logf(u1)));
+        float sn, cs;
+        sincospif(u2x2, &sn, &cs);
+        z[2 * h] = __fmul_rn(rad, cs);
+        z[2 * h + 1] = __fmul_rn(rad, sn);
+    }
+}
+// Where tensor row `i` of a seeded launch sits in its utterance: clip i / n (noise row first_row + i / n), sample origin origin0 + min((i % n)
+// * stride, last) — TilePlan::start's rule in samples at this layer's rate (the last time tile is pulled back to end at the clip's end).  A whole
+// forward and a stream window are n = 1: every row starts at origin0.
+struct SeededRows {
+    unsigned long long seed;
+    int layer, first_row, n;
+    long long origin0, stride, last;
+};
+__device__ __forceinline__ long long seeded_origin(const SeededRows& r, int i) {
+    const long long a = (long long)(i % r.n) * r.stride;
+    return r.origin0 + (a < r.last ? a : r.last);
+}
+
+// adain_kernel with the noise operand computed in place of loaded.  A thread owns one absolute-aligned quad of one (row, channel): the first and the
+// last quad of a row may be partial (an origin off the quad grid, a length that is no multiple of 4) — those lanes are computed and not stored.
+// 16-byte accesses where the quad is whole and its address lines up, scalar ones at the ragged ends.
+__global__ __launch_bounds__(256) void adain_seeded_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, int C,
+                                                           int T, float slope, int accumulate, float scale, SeededRows rows) {
+    const int c = blockIdx.y, i = blockIdx.z;
+    const long long o = seeded_origin(rows, i);
+    const long long q = (o >> 2) + ((long long)blockIdx.x * 256 + threadIdx.x);
+    const long long t0 = q * 4 - o;   // the quad's first position within the row: -3 ... T - 1 for the quads that touch it
+    if (t0 >= T) return;
+    float z[4];
+    seeded_normal4(rows.seed, q, (unsigned)(rows.first_row + i / rows.n) * (unsigned)C + (unsigned)c, (unsigned)rows.layer, z);
+    const long long base = ((long long)i * C + c) * T + t0;
+    const float wc = w[c];
+    const bool whole = t0 >= 0 && t0 + 3 < T;
+    if (whole && (((unsigned long long)(x + base) | (unsigned long long)(y + base)) & 15ull) == 0) {
+        const float4 xv = *reinterpret_cast<const float4*>(x + base);
+        float4 yv = accumulate ? *reinterpret_cast<const float4*>(y + base) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+        float ys[4] = {yv.x, yv.y, yv.z, yv.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float v = __fadd_rn(xs[k], __fmul_rn(z[k], wc));
+            v = v >= 0.f ? v : v * slope;
+            ys[k] = accumulate ? (ys[k] + v) * scale : v;
+        }
+        *reinterpret_cast<float4*>(y + base) = make_float4(ys[0], ys[1], ys[2], ys[3]);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long long t = t0 + k;
+        if (t < 0 || t >= T) continue;
+        float v = __fadd_rn(x[base + k], __fmul_rn(z[k], wc));
+        v = v >= 0.f ? v : v * slope;
+        y[base + k] = accumulate ? (y[base + k] + v) * scale : v;
+    }
+}
+
+// The same samples into the explicit-noise layout of fv_forward_refinegan: one (B, C, T) tensor of one AdaIN layer per launch
+__global__ __launch_bounds__(256) void refinegan_fill_noise_kernel(float* __restrict__ out, int C, int T, SeededRows rows) {
+    const int c = blockIdx.y, i = blockIdx.z;
+    const long long o = seeded_origin(rows, i);
+    const long long q = (o >> 2) + ((long long)blockIdx.x * 256 + threadIdx.x);
+    const long long t0 = q * 4 - o;
+    if (t0 >= T) return;
+    float z[4];
+    seeded_normal4(rows.seed, q, (unsigned)(rows.first_row + i / rows.n) * (unsigned)C + (unsigned)c, (unsigned)rows.layer, z);
+    const long long base = ((long long)i * C + c) * T + t0;
+    if (t0 >= 0 && t0 + 3 < T && ((unsigned long long)(out + base) & 15ull) == 0) {
+        *reinterpret_cast<float4*>(out + base) = make_float4(z[0], z[1], z[2], z[3]);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (t0 + k >= 0 && t0 + k < T) out[base + k] = z[k];
+}
+
+// rows of T samples hold at most T / 4 + 2 absolute quads, whatever the origin's alignment
+static SeededRows seeded_rows(const SeededNoise& sn, int layer) {
+    return SeededRows{sn.seed, layer, sn.first_row, sn.n, sn.origin0, sn.stride, sn.last};
+}
+fv_status launch_adain_seeded(const float* x, const float* w, float* y, int B, int C, int T, float slope, int accumulate, float scale,
+                              const SeededNoise& sn, int layer, hipStream_t s) {
+    hipLaunchKernelGGL(adain_seeded_kernel, dim3((T / 4 + 2 + 255) / 256, C, B), dim3(256), 0, s, x, w, y, C, T, slope, accumulate, scale,
+                       seeded_rows(sn, layer));
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+}
+fv_status launch_refinegan_fill_noise(float* out, int B, int C, int T, const SeededNoise& sn, int layer, hipStream_t s) {
+    hipLaunchKernelGGL(refinegan_fill_noise_kernel, dim3((T / 4 + 2 + 255) / 256, C, B), dim3(256), 0, s, out, C, T, seeded_rows(sn, layer));
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+}
+
 #ifdef FV_DEBUG_HOOKS   // not in the product library: `make BUILD=build_dbg LIB=libfishvoc_dbg.so EXTRA=-DFV_DEBUG_HOOKS`, then FV_LIB_PATH
 // Debug aid (tools/probe_lds_poison.py): fills the LDS of every CU with signalling garbage (NaN bit patterns) so that a kernel
 // which reads LDS it never wrote shows up as a changed / non-finite result instead of silently inheriting whatever the previous

@@ -253,6 +253,7 @@ class Engine(_Handle):
         self._last_stream = None
         self._streams: weakref.WeakSet = weakref.WeakSet()   # live Streams and RaggedPlans: closed before the engine is destroyed
         self._ragged_last: RaggedPlan | None = None          # the plan forward_ragged made for the last (lengths, t_max) it saw
+        self.noise_seed: "tuple[int, int] | None" = None     # RefineGAN: (seed, first_row) of set_noise_seed, None without one
 
     def close(self) -> None:
         """Destroys the engine; its live streams are closed first (their pushes then raise)."""
@@ -292,10 +293,39 @@ class Engine(_Handle):
         """RefineGAN only: number of standard-normal samples one forward consumes (fv_refinegan_noise_elems)."""
         return int(self._lib.fv_refinegan_noise_elems(self._h, int(batch), int(t_in)))
 
+    def set_noise_seed(self, seed: int, first_row: int = 0) -> None:
+        """RefineGAN only: AdaIN's draws (reference refinegan.py:125) become a pure function of (seed, noise row, layer, channel, absolute sample
+        position), computed inside the AdaIN kernels (fv_refinegan_set_noise_seed; the rule: ``vocoder_amd.refinegan_noise``).  Batch row ``b``
+        draws noise row ``first_row + b``.  A seeded engine has a reach, runs clips of any length and streams; ``forward`` without ``noise``
+        then needs no noise tensor."""
+        seed, first_row = int(seed), int(first_row)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"the noise seed is an unsigned 64-bit integer, got {seed}")
+        with self._lock:
+            check(self._lib.fv_refinegan_set_noise_seed(self._h, seed, first_row))
+            self.noise_seed = (seed, first_row)
+
+    def clear_noise_seed(self) -> None:
+        """Back to explicit noise (fv_refinegan_clear_noise_seed): ``forward`` needs ``noise`` again, and streams made under the seed refuse their
+        next push."""
+        with self._lock:
+            check(self._lib.fv_refinegan_clear_noise_seed(self._h))
+            self.noise_seed = None
+
+    def fill_noise(self, batch: int, frames: int, origin_frame: int = 0) -> torch.Tensor:
+        """The draws a seeded ``forward`` of ``batch`` x ``frames`` frames at ``origin_frame`` computes in its kernels, as the flat tensor of
+        ``noise_elems(batch, frames)`` samples that ``forward(noise=...)`` takes (fv_refinegan_fill_noise): the two forwards agree bit for bit."""
+        n = self.noise_elems(batch, frames)
+        out = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+        self._enqueue(self.device, lambda stream: self._lib.fv_refinegan_fill_noise(self._h, out.data_ptr(), int(batch), int(frames),
+                                                                                    int(origin_frame), stream), eager=True)
+        return out[:n]
+
     def forward(self, x: torch.Tensor, out: torch.Tensor | None = None, template: torch.Tensor | None = None,
-                noise: torch.Tensor | None = None) -> torch.Tensor:
+                noise: torch.Tensor | None = None, *, origin_frame: int = 0) -> torch.Tensor:
         """``noise`` (RefineGAN engines only): flat fp32 tensor of ``noise_elems(B, T)`` standard-normal samples standing in
-        for AdaIN's torch.randn_like draws (reference refinegan.py:125), in order of use."""
+        for AdaIN's torch.randn_like draws (reference refinegan.py:125), in order of use.  Without it, an engine under ``set_noise_seed``
+        computes the draws in its kernels; ``origin_frame``: the utterance frame ``x`` starts at (a window of a longer utterance)."""
         x, B, T = self._input(x, "Engine.forward")
         if T == 0:   # the reference fails here too: conv_pre's kernel is wider than the padded input
             raise ValueError(f"empty input {tuple(x.shape)}")
@@ -316,8 +346,15 @@ class Engine(_Handle):
             nptr = noise.data_ptr()
         need = self.workspace_bytes(B, T)
 
+        seeded = nptr is None and self.noise_seed is not None
+        if origin_frame and not seeded:
+            raise ValueError("origin_frame belongs to a RefineGAN forward under set_noise_seed without explicit noise")
+
         def launch(stream: int) -> int:
             self._grow_workspace(need, x.device)
+            if seeded:
+                return self._lib.fv_forward_refinegan_seeded(self._h, x.data_ptr(), tptr, out.data_ptr(), B, T, int(origin_frame),
+                                                             self._ws.data_ptr(), self._ws.numel() * 4, stream)
             return self._launch(x, tptr, nptr, out, B, T, stream)
         self._enqueue(x.device, launch)
         return out
@@ -505,8 +542,8 @@ class Engine(_Handle):
         return self._lib.fv_forward_template(self._h, x.data_ptr(), tptr, out.data_ptr(), B, T, self._ws.data_ptr(),
                                              self._ws.numel() * 4, stream)
 
-    def __call__(self, x, out=None, template=None, noise=None):
-        return self.forward(x, out, template, noise)
+    def __call__(self, x, out=None, template=None, noise=None, **kw):
+        return self.forward(x, out, template, noise, **kw)
 
     def profile(self, x: torch.Tensor, repeats: int = 3, lengths=None) -> list[dict]:
         """Per-kernel hipEvent timings of `repeats` forwards (fv_profile_begin/end): a list of

@@ -19,6 +19,8 @@
   (``RefineGANGenerator``, ``use_template=True``; refinegan.py:287, hifigan.py:226) gets one: for a ``.wav`` it is made on the GPU from the
   samples the mel is made from (``vocoder_amd.f0``: YIN, then an exact-phase oscillator; ``--f0-min`` / ``--f0-max`` / ``--f0-threshold`` /
   ``--template-kind``), for a mel from the sidecar ``<stem>.f0.npy`` (Hz per mel frame, 0 = unvoiced); whole files and ``--batch-size``.
+  ``--noise-seed N`` (RefineGAN): the AdaIN noise (refinegan.py:125) is computed inside the kernels from the seed instead of drawn with
+  ``torch.randn`` per call (``RefineGANGenerator.set_noise_seed``): the same file twice, no noise tensor, whole files of any length.
 """
 from __future__ import annotations
 
@@ -611,7 +613,12 @@ def main(argv=None):
     ap.add_argument("--f0-max", type=float, default=1100.0, metavar="HZ", help="highest F0 the tracker searches")
     ap.add_argument("--f0-threshold", type=float, default=0.1, help="YIN's voicing threshold on the normalised difference function, in (0, 1]")
     ap.add_argument("--template-kind", choices=("sine", "sawtooth"), default="sine", help="waveform of the pitch template")
+    ap.add_argument("--noise-seed", type=int, default=None, metavar="N",
+                    help="RefineGAN: AdaIN's noise (refinegan.py:125) is computed inside the kernels from this seed instead of drawn with "
+                         "torch.randn per call: reproducible output, no noise tensor, whole files of any length")
     a = ap.parse_args(argv)
+    if a.noise_seed is not None and not 0 <= a.noise_seed < 1 << 64:
+        ap.error("--noise-seed is an unsigned 64-bit integer")
     if a.pitch_shift and (a.chunk_frames is not None or a.sessions is not None):
         raise ValueError("--pitch-shift is not available with --chunk-frames / --sessions on the command line: run the files whole or under "
                          "--batch-size, or call stream_wav_synthesis(pitch_shift=PitchShift(...)), which shifts chunk by chunk")
@@ -627,6 +634,10 @@ def main(argv=None):
         ap.error("--batch-size must be >= 1 and cannot be combined with --chunk-frames")
     model = build_model(a.generator, a.resolution, {"num_mels": a.num_mels} if a.num_mels else None, a.config_root,
                         a.ckpt_path, device="cpu", trust_checkpoint=a.trust_checkpoint)      # (on the host first: the refusal below needs no GPU)
+    if a.noise_seed is not None:
+        if not hasattr(model.generator, "set_noise_seed"):
+            raise ValueError(f"--noise-seed: {type(model.generator).__name__} draws no noise (RefineGAN's AdaIN layers do)")
+        model.generator.set_noise_seed(a.noise_seed)
     with_template = takes_template(model.generator)
     if with_template and (a.chunk_frames is not None or a.sessions is not None):
         raise ValueError(f"{type(model.generator).__name__} takes a pitch template, and the template has no streaming form yet (it would carry "

@@ -9,6 +9,9 @@ variable.  Here the normal samples are an explicit input: ``forward(mel, templat
 ``torch.randn`` on the input's device when ``noise`` is None (same distribution, different stream than the reference's),
 or uses the given flat tensor of ``noise_elems(B, T)`` samples — which is what makes parity with the reference testable
 (tests/golden/refinegan_*.npz were captured with torch.randn_like replaced by the same seeded samples).
+
+``set_noise_seed(seed)`` switches the module to in-kernel noise (``vocoder_amd.refinegan_noise``): no noise tensor is drawn, the output is a
+function of the seed, clips of any length run as time tiles, and ``stream()`` works like a ``use_template`` HiFiGAN's.
 """
 from __future__ import annotations
 
@@ -110,9 +113,25 @@ class RefineGANGenerator(_base.EngineModule):
             n += 6 * batch * ch * t
         return n
 
+    def set_noise_seed(self, seed: "int | None", first_row: int = 0) -> None:
+        """AdaIN's draws (refinegan.py:125) computed inside the kernels from ``seed`` (``Engine.set_noise_seed``); ``None``: back to
+        ``torch.randn`` per call.  Survives the engine rebuilds of ``load_state_dict`` / ``.to()``."""
+        object.__setattr__(self, "_noise_seed", None if seed is None else (int(seed), int(first_row)))
+        eng = self.__dict__.get("_engine")
+        if eng is not None:
+            eng.clear_noise_seed() if seed is None else eng.set_noise_seed(int(seed), int(first_row))
+
+    def engine(self, device):
+        eng = super().engine(device)
+        seed = self.__dict__.get("_noise_seed")
+        if seed is not None and eng.noise_seed != seed:
+            eng.set_noise_seed(*seed)
+        return eng
+
     def forward(self, mel: torch.Tensor, template: torch.Tensor, noise: torch.Tensor | None = None) -> torch.Tensor:
         if template is None:
             raise TypeError("RefineGANGenerator.forward(mel, template): the pitch template is required (refinegan.py:287)")
-        if noise is None and isinstance(mel, torch.Tensor) and mel.is_cuda:
+        seeded = self.__dict__.get("_noise_seed") is not None
+        if noise is None and not seeded and isinstance(mel, torch.Tensor) and mel.is_cuda:
             noise = torch.randn(self.noise_elems(mel.shape[0], mel.shape[2]), dtype=torch.float32, device=mel.device)
         return self._run(mel, template, noise)
