@@ -991,6 +991,15 @@ FV_API fv_status fv_conv_forward(fv_conv* c, const float* d_x, float* d_y, const
  * dilation in {1, 3, 5} (else FV_ERR_UNSUPPORTED).  d_y must not alias d_x. */
 FV_API fv_status fv_conv_pair_forward(fv_conv* c1, fv_conv* c2, const float* d_x, float* d_y, int32_t batch, int32_t t,
                                       void* stream);
+/* The wide k = 3 pairs (C in {64, 128}, dilation in {1, 3, 5}) also have a Winograd F(4,3) quad-lattice kernel, "pair_wino4<k=3 d C>": 6 matrix
+ * products per four outputs instead of F(2,3)'s 8.  An engine's pair branches take it on launches that fill the chip, outside batch-invariant mode;
+ * fv_conv_pair_forward takes it only under FV_PAIR_WINO4=2 (FV_PAIR_WINO4=0: nobody does).  Host helpers, no GPU: the kernel's tile width in final
+ * samples (0 for a shape it has no instance for), exported for the tests' shapes, and the weight packer — w: one layer's (c, c, 3) weights; returns the
+ * packed size in floats (0: unsupported c) and fills out[0 .. size) when cap >= size.  Fragment order: float4 [(m_tile * c / 8 + chunk) * 6 + plane] * 64
+ * + lane, component pp = U[32 m_tile + (lane & 31)][8 chunk + 2 pp + (lane >> 5)][plane], U = G w at the points 0, +1, -1, +2, -2, inf; then 8 zero
+ * fragments. */
+FV_API int32_t fv_pair_wino4_tile(int32_t c, int32_t dilation);
+FV_API int64_t fv_pair_wino4_pack(const float* w, int32_t c, float* out, int64_t cap);
 /* fv_precision for the following fv_conv_forward calls on this layer; layers the split-fp16 kernels do not cover
  * (transposed, C_in < 32, kernel size not in {3, 7, 11}) keep running in fp32. */
 FV_API fv_status fv_conv_set_precision(fv_conv* c, int32_t precision);

@@ -66,6 +66,7 @@ EXPORTS = (
     "fv_yin_stream_reset", "fv_yin_stream_destroy",
     "fv_osc_stream_create", "fv_osc_stream_pending_frames", "fv_osc_stream_push", "fv_osc_stream_flush", "fv_osc_stream_reset",
     "fv_osc_stream_destroy",
+    "fv_pair_wino4_tile", "fv_pair_wino4_pack",
 )
 
 _i32 = ctypes.c_int32
@@ -427,6 +428,10 @@ def lib() -> ctypes.CDLL:
     L.fv_osc_stream_reset.restype = _i32
     L.fv_osc_stream_destroy.argtypes = [vp]
     L.fv_osc_stream_destroy.restype = None
+    L.fv_pair_wino4_tile.argtypes = [_i32, _i32]
+    L.fv_pair_wino4_tile.restype = _i32
+    L.fv_pair_wino4_pack.argtypes = [fp, _i32, fp, i64]
+    L.fv_pair_wino4_pack.restype = i64
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

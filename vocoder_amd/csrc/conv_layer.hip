@@ -32,7 +32,7 @@ static bool f16x3_per_layer_ok(const ConvLayer& L) { return L.M >= 32; }
 // tools/ab_wino.sh do); a layer whose form is missing falls back to the direct kernel.  Footprint at k = 11 per (c_out, c_in): direct 11 floats
 // + F(4,4) 10 + latency / pair fragments 16 (was 11 + 16 + 10 + 26 + 16 + 16).
 struct LayerForms {
-    bool wino, f23, f44, f43, lat, q16, pair16, plain16, f16x3, pair16_f16x3;   // wino: ConvLayer::wino; the others: the layer keeps d_wpw, d_wpw44, d_wpw4, d_wpwl, d_wpq16, d_wpw16, d_wp16, d_wph, d_wph16
+    bool wino, f23, f44, f43, lat, q16, pair16, pairq3, plain16, f16x3, pair16_f16x3;   // wino: ConvLayer::wino; the others: the layer keeps d_wpw, d_wpw44, d_wpw4, d_wpwl, d_wpq16, d_wpw16, d_wpq3, d_wp16, d_wph, d_wph16
 };
 static LayerForms layer_forms(const ConvLayer& L, int stride, bool with_f16x3, const Knobs& kn, bool have_wino4) {
     const bool transposed = L.transposed;
@@ -47,6 +47,7 @@ static LayerForms layer_forms(const ConvLayer& L, int stride, bool with_f16x3, c
     f.lat = f.wino && c_in >= 32 && c_in % 32 == 0;
     f.q16 = f.wino && (c_in == 16 || c_in == 32 || c_in % 32 == 0) && k >= 7;
     f.pair16 = f.wino && (c_in == 16 || c_in == 32);
+    f.pairq3 = f.wino && (c_in == 64 || c_in == 128) && k == 3;   // the wide k = 3 pairs' F(4,3) group: 6 floats per (c_out, c_in) next to F(2,3)'s 4
     f.plain16 = !transposed && c_in == 16 && c_out == 16;
     f.f16x3 = with_f16x3 && f16x3_eligible(transposed, c_in, L.M, L.ks, L.dil);
     f.pair16_f16x3 = with_f16x3 && f.plain16 && (k == 3 || k == 7 || k == 11);
@@ -119,6 +120,7 @@ fv_status conv_layer_create(ConvLayer& L, bool transposed, int c_in, int c_out, 
         if (f.lat && (st = upload(pack_wino_lat(ww, c_out, c_in, L.nv), L.d_wpwl))) return st;
         if (f.q16 && (st = upload(pack_wino44_16(wc, c_in, k), L.d_wpq16))) return st;
         if (f.pair16 && (st = upload(pack_pair_wino16(ww, c_in, L.nv), L.d_wpw16))) return st;
+        if (f.pairq3 && (st = upload(pack_pair_wino4(wc, c_in), L.d_wpq3))) return st;
     }
     if (f.f16x3) {
         L.nch16 = (c_in + 15) / 16;

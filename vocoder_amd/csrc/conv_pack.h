@@ -27,6 +27,8 @@ std::vector<float> pack_wino_lat(const std::vector<float>& ww, int c_out, int c_
 std::vector<float> pack_wino44_16(const std::vector<float>& wc, int c_in, int k);                       // 16x16x4 F(4,4) fragments
 std::vector<float> pack_pair_wino16(const std::vector<float>& ww, int c_in, int nv);                    // C = 16 / 32 pair fragments of wino_taps()
 std::vector<float> pack_conv16(const float* host_w, int k);                                             // plain 16x16x4 fragments, 16 -> 16 channels
+std::vector<float> pair_wino4_taps(const std::vector<float>& wc, int c);                                // k = 3, C -> C: the F(4,3) group U = G w, (c, c, 6)
+std::vector<float> pack_pair_wino4(const std::vector<float>& wc, int c);                                // ... as 32x32x2 fragments (pair_wino4_impl.h)
 
 // f16x3 precision mode: s_w, and the (wh, wl) planes of w * s_w
 float f16x3_weight_scale(const float* w, size_t n);

@@ -188,6 +188,22 @@ std::vector<float> pack_pair_wino16(const std::vector<float>& ww, int c_in, int 
     return p16;
 }
 
+// pair_wino4_impl.h (C = 64 / 128, k = 3): ONE F(4,3) tap group per (c_out, c_in), points 0, +-1, +-2, inf — wino4_rows' transform, all six planes in
+// one row: U = g0 / 4, -(g0 + g1 + g2) / 6, -(g0 - g1 + g2) / 6, g0 / 24 + g1 / 12 + g2 / 6, g0 / 24 - g1 / 12 + g2 / 6, g2
+std::vector<float> pair_wino4_taps(const std::vector<float>& wc, int c) {
+    std::vector<float> u6((size_t)c * c * 6);
+    for (size_t oc = 0; oc < (size_t)c * c; ++oc) {
+        const double g0 = wc[oc * 3], g1 = wc[oc * 3 + 1], g2 = wc[oc * 3 + 2];
+        const double U[6] = {g0 / 4, -(g0 + g1 + g2) / 6, -(g0 - g1 + g2) / 6, g0 / 24 + g1 / 12 + g2 / 6, g0 / 24 - g1 / 12 + g2 / 6, g2};
+        for (int v = 0; v < 6; ++v) u6[oc * 6 + v] = (float)U[v];
+    }
+    return u6;
+}
+
+// ... in pack_conv_weights' fragment order with the six planes as taps: float4 [(m_tile * (c / 8) + chunk) * 6 + plane] * 64 + lane,
+// .{x,y,z,w}[pp] = U[32 m_tile + (lane & 31)][8 chunk + 2 pp + (lane >> 5)][plane]; + 8 zero fragments of prefetch overrun
+std::vector<float> pack_pair_wino4(const std::vector<float>& wc, int c) { return pack_conv_weights(pair_wino4_taps(wc, c), c, c, 6, c, c / kChunk); }
+
 // v_mfma_f32_16x16x4_f32 A fragments: [tap][lane] float4, .q = W[lane & 15][4q + (lane >> 4)][tap]
 std::vector<float> pack_conv16(const float* host_w, int k) {
     std::vector<float> p16((size_t)k * 64 * 4);

@@ -128,7 +128,7 @@ bool pair_wino_supported(int C, int ks, int dil) {
 }
 
 fv_status conv_pair_run(const ConvLayer& c1, const ConvLayer& c2, const float* x, float* y, int batch, int t, int out_mode,
-                        float out_scale, hipStream_t stream) {
+                        float out_scale, hipStream_t stream, bool quad) {
     const int C = c1.c_in;
     if (pair_f16x3_supported(c1, c2)) return conv_pair_run_f16x3(c1, c2, x, y, batch, t, out_mode, out_scale, stream);
     if (pair16_f16x3_usable(c1, c2, x, y, t)) return conv_pair16_run_f16x3(c1, c2, x, y, batch, t, out_mode, out_scale, stream);
@@ -151,6 +151,16 @@ fv_status conv_pair_run(const ConvLayer& c1, const ConvLayer& c2, const float* x
         const int nbq = 16 * (4 / (C / 16));
         const int tt = 4 * (nbq / c1.dil * c1.dil) - (c1.k - 1);   // PQGeom::TT
         return finish_pair_launch(ok, "pair_wino44", "F(4,4) pair kernel", tt, 2.0, c1, t, batch, out_mode, stream, prof_idx);
+    }
+    // the wide stages at k = 3: ONE F(4,3) tap group in both convs (pair_wino4_impl.h; round 26) — 6 products per four outputs against F(2,3)'s 8.  Only where
+    // the caller asks (the engine's pair branches, on launches that fill the chip) or FV_PAIR_WINO4=2, and never in batch-invariant mode: a clip's bits
+    // must not depend on the size of the launch it is part of, so everything below that gate, and every direct call, keeps F(2,3)
+    if (knobs().pair_wino && knobs().pair_wino4 != 0 && (quad || knobs().pair_wino4 == 2) && !cur_invariant() && effective_algo() != FV_CONV_ALGO_DIRECT &&
+        c1.precision == FV_PRECISION_F32 && c2.precision == FV_PRECISION_F32 && c1.d_wpq3 && c2.d_wpq3 && (C == 64 || C == 128) && c1.k == 3 && (long long)C * t < (1LL << 30)) {
+        const PairParams p = pair_params(c1, c2, c1.d_wpq3, c2.d_wpq3, x, y, t, out_mode, out_scale);
+        const int prof_idx = prof_begin(stream);
+        const bool ok = launch_pair_wino4_k3(p, C, c1.dil, batch, stream);
+        return finish_pair_launch(ok, "pair_wino4", "F(4,3) pair kernel", pair_wino4_tile(c1.dil, C), 2.0, c1, t, batch, out_mode, stream, prof_idx);
     }
     const bool wide = C >= 64;   // 32x32x2 kernels on the layers' d_wpw; C <= 32: 16x16x4 kernels on d_wpw16
     if (knobs().pair_wino && effective_algo() != FV_CONV_ALGO_DIRECT && (wide ? (c1.d_wpw && c2.d_wpw) : (c1.d_wpw16 && c2.d_wpw16)) &&

@@ -68,6 +68,17 @@ FV_API fv_status fv_conv_pair_forward(fv_conv* c1, fv_conv* c2, const float* d_x
     return conv_pair_run(c1->L, c2->L, d_x, d_y, batch, t, OUT_SET, 1.0f, (hipStream_t)stream);
 }
 
+FV_API int32_t fv_pair_wino4_tile(int32_t c, int32_t dilation) {
+    return ((c == 64 || c == 128) && (dilation == 1 || dilation == 3 || dilation == 5)) ? pair_wino4_tile(dilation, c) : 0;
+}
+
+FV_API int64_t fv_pair_wino4_pack(const float* w, int32_t c, float* out, int64_t cap) {
+    if (!w || (c != 64 && c != 128)) return 0;
+    const std::vector<float> packed = pack_pair_wino4(std::vector<float>(w, w + (size_t)c * c * 3), c);
+    if (out && cap >= (int64_t)packed.size()) std::copy(packed.begin(), packed.end(), out);
+    return (int64_t)packed.size();
+}
+
 FV_API fv_status fv_conv_set_precision(fv_conv* c, int32_t precision) {
     if (!c || (precision != FV_PRECISION_F32 && precision != FV_PRECISION_F16X3)) {
         set_error("fv_conv_set_precision: invalid argument");

@@ -74,6 +74,9 @@ struct StagePlan {
     BranchPlan br[FV_MAX_KERNELS];   // in the order the host enqueues them
 };
 
+// the chip-filling gate of the wide (C = 64 / 128) fused pairs: two workgroups per CU in the F(2,3) C = 128 tiling
+static bool pair_fills_chip(int B, int t) { return (long long)B * ((t + 125) / 126) >= 2LL * num_cus(); }
+
 BranchForm plan_branch_form(const fv_engine& e, const ResBranch& br, bool dbg_here, int B, int t, int ch) {
     const EngineOptions& o = e.opt;
     // HiFiGAN narrow stages: the whole (c1, c2) pair in one kernel, intermediate kept in LDS.  Not in place
@@ -81,7 +84,7 @@ BranchForm plan_branch_form(const fv_engine& e, const ResBranch& br, bool dbg_he
     // (C = 64 / 128 pairs — k = 3 only — fuse when the launch fills the chip; a single clip's 44 - 88 tiles are better served by the
     //  per-layer latency kernels: conv_wino_lat_impl.h)
     const bool fuse_narrow = ch <= o.pair_max_c && pair_supported(ch, br.k, br.dil[0]) && pair_supported(ch, br.k, br.dil[1]) &&
-                             pair_supported(ch, br.k, br.dil[2]) && (ch < 64 || cur_invariant() || (long long)B * ((t + 125) / 126) >= 2LL * num_cus());
+                             pair_supported(ch, br.k, br.dil[2]) && (ch < 64 || cur_invariant() || pair_fills_chip(B, t) || knobs().pair_wino4 == 2);   // (FV_PAIR_WINO4=2, tests: the wide pairs at any size)
     // f16x3 precision mode: the wide stages (C = 128 / 64) fuse too (pair_f16x3_impl.h)
     const bool fuse_wide = pair_f16x3_supported(br.c1[0], br.c2[0]) && pair_f16x3_supported(br.c1[1], br.c2[1]) &&
                            pair_f16x3_supported(br.c1[2], br.c2[2]);
@@ -212,11 +215,14 @@ fv_status run_branch_pairs(const ResBranch& br, const UpsWorkspace& w, const Sta
     const hipStream_t bs = ord.stream(bp.stream);
     fv_status st;
     const float* src = w.S;
+    // wide k = 3 pairs of a launch that fills the chip: the F(4,3) family (conv_pair_run keeps F(2,3) in batch-invariant mode, for DIRECT and under
+    // FV_PAIR_WINO4=0) — streams, session pools, ragged rows and single clips run below the gate or batch-invariant, and keep their bits
+    const bool quad = sp.ch >= 64 && !cur_invariant() && pair_fills_chip(sp.B, sp.t);
     for (int n = 0; n < FV_MAX_DILATIONS; ++n) {
         const bool last = n == FV_MAX_DILATIONS - 1;
         float* dst = last ? bp.y_last : (n == 0 ? w.XB(bp.bj) : w.XT(bp.bj));
         if (last && (st = ord.before_last(bp))) return st;
-        if ((st = conv_pair_run(br.c1[n], br.c2[n], src, dst, sp.B, sp.t, last ? bp.mode_last : OUT_SET, last ? bp.scale_last : 1.0f, bs)))
+        if ((st = conv_pair_run(br.c1[n], br.c2[n], src, dst, sp.B, sp.t, last ? bp.mode_last : OUT_SET, last ? bp.scale_last : 1.0f, bs, quad)))
             return st;
         src = dst;
     }

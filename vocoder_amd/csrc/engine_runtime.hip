@@ -68,6 +68,7 @@ static const Knobs* load_knobs() {
     if (const char* v = std::getenv("FV_WINO44_FLAT")) k->wino44_flat = std::atoi(v);
     if (const char* v = std::getenv("FV_VEC_STORE")) k->vec_store = std::atoi(v);
     if (const char* v = std::getenv("FV_PAIR_WINO44")) k->pair_wino44 = std::atoi(v);
+    if (const char* v = std::getenv("FV_PAIR_WINO4")) k->pair_wino4 = std::atoi(v);
     if (const char* v = std::getenv("FV_CONV_TILE")) {
         k->conv_tile = conv_tile_by_name(v);
         if (k->conv_tile < 0 && v[0]) std::fprintf(stderr, "fishvoc: FV_CONV_TILE=%s names no conv tile; ignored\n", v);

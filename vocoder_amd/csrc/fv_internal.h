@@ -42,6 +42,8 @@ struct Knobs {
     int splitk_direct = 1;   // FV_SPLITK_DIRECT: 1 = the few-tap split-K launches (conv_pre, the upsamplers of a single clip) load their B operands straight from global memory (conv_mfma_splitk_direct_kernel), 0 = staged through LDS
     int wino44_flat = 1;  // FV_WINO44_FLAT: 1 = conv_wino44 tiles a flattened (clip, quad column) axis where that needs fewer 32-column tiles than tiling every clip on its own (T = 688: 5.4 tiles per clip), 0 = per clip
     int wino_lat = 1;     // FV_WINO_LAT: 0 = launches below the Winograd gate run the direct split-K kernels, 1 = the Winograd latency kernel
+    int pair_wino4 = -1;  // FV_PAIR_WINO4: the fused wide k = 3 pairs (C = 64 / 128) on one F(4,3) tap group (pair_wino4_impl.h) — unset = where the engine's pair
+                          //   branches ask for it (launches that fill the chip, not in batch-invariant mode), 0 = never, 2 = every conv_pair_run (tests)
     int pair_wino = 1;    // FV_PAIR_WINO: 0 = the fused (c1, c2) pairs run direct sums (resblock_pair.hip), 1 = Winograd tap groups where a kernel exists
     int conv_tile = -1;   // FV_CONV_TILE: a TileCfg name ("128x64", "splitK32x32", ...) forced on every conv_mfma launch that has that tile instantiated
                           //   (after all the shape remaps; tests pin the kernel instance by instance), -1 = by shape
@@ -185,6 +187,7 @@ struct ConvLayer {
     float4* d_wpwl = nullptr;  // Winograd-transformed weights of the latency kernel: 16-row tiles, 8-channel blocks, tap pairs (conv_wino_lat_impl.h); optional
     float4* d_wpq16 = nullptr; // Winograd F(4,4)-transformed weights in 16x16x4 fragment order, C -> C, k in {7, 11}: C in {16, 32} for pair_wino44_impl.h, whole 32-row blocks for conv_wino_lat44_impl.h; optional
     float4* d_wpw16 = nullptr; // Winograd-transformed weights in 16x16x4 fragment order, C -> C with C in {16, 32} (pair_wino_impl.h); optional
+    float4* d_wpq3 = nullptr;  // Winograd F(4,3)-transformed weights of the wide k = 3 pairs, C -> C with C in {64, 128}: (32-row tile) x chunk x 6 fragments (pair_wino4_impl.h); optional
     void* d_wph16 = nullptr;   // f16x3 mode, 16 -> 16 channel Conv1d: (wh, wl) planes of the two-samples-per-row layout (pair16_f16x3.hip)
     void* d_wph = nullptr;     // f16x3 mode: (wh, wl, wh * 2^-11) fp16 planes in 32x32x16 fragment order (optional)
     float w_scale = 1.f;       // s_w: power of two folded into those planes
@@ -197,7 +200,7 @@ struct ConvLayer {
     // every device allocation of the layer, in one place: conv_layer_destroy walks this list (a buffer added above is added here too)
     template <class F>
     void for_each_buffer(F&& f) {
-        f(d_wp), f(d_bias), f(d_wp16), f(d_wpw), f(d_wpw16), f(d_wpq16), f(d_wpw44), f(d_wpw4), f(d_wpwl), f(d_wph), f(d_wph16);
+        f(d_wp), f(d_bias), f(d_wp16), f(d_wpw), f(d_wpw16), f(d_wpq16), f(d_wpw44), f(d_wpw4), f(d_wpwl), f(d_wpq3), f(d_wph), f(d_wph16);
     }
 
     int64_t out_len(int t_in) const {
@@ -290,8 +293,13 @@ bool pair_wino_supported(int C, int ks, int dil);
 bool launch_pair_wino_k3(const PairParams& p, int C, int dil, int batch, hipStream_t s);
 bool launch_pair_wino_k7(const PairParams& p, int C, int dil, int batch, hipStream_t s);
 bool launch_pair_wino_k11(const PairParams& p, int C, int dil, int batch, hipStream_t s);
+// Winograd F(4,3) form of the wide k = 3 pairs (pair_wino4_impl.h): p.w1 / p.w2 = the layers' d_wpq3; C in {64, 128}, dil in {1, 3, 5}
+bool launch_pair_wino4_k3(const PairParams& p, int C, int dil, int batch, hipStream_t s);
+// ... and its tile width (final samples per workgroup): 32 (C = 128) or 64 (C = 64) quad columns of whole 4 D-sample blocks, less c2's halo
+constexpr int pair_wino4_tile(int dil, int C) { return 4 * ((C == 128 ? 32 : 64) / dil * dil) - 2; }
+// quad: the caller (the engine's pair branches, on launches that fill the chip) lets the wide k = 3 pairs take the F(4,3) family
 fv_status conv_pair_run(const ConvLayer& c1, const ConvLayer& c2, const float* x, float* y, int batch, int t, int out_mode,
-                        float out_scale, hipStream_t stream);
+                        float out_scale, hipStream_t stream, bool quad = false);
 
 // BigVGAN AMPBlock conv with its anti-aliased SnakeBeta fused in front (amp_conv.hip): y = conv(Activation1d(x)) + bias [+ res]
 // for C_in = C_out in {32, 64}, k in {3, 7, 11}, 'same' padding; alpha / inv_beta / taps as for launch_aa_snake
