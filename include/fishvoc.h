@@ -654,6 +654,77 @@ FV_API fv_status fv_logmel_stream_reset(fv_logmel_stream* s);
  * nothing to free. */
 FV_API void fv_logmel_stream_destroy(fv_logmel_stream* s);
 
+/* -------- audio in, per session: the log-mel front-end as a pool of sessions that advance independently — what fv_pool_* is to fv_stream_*,
+ *          for samples.  No reference counterpart: spectrogram.py:25-104 / test.py:64-71 take one whole file at a time.  --------
+ *
+ * A wav pool holds S slots on a FV_MODEL_LOGMEL engine.  Each slot has its own counters N (samples received) and E (frames emitted), its own
+ * flushed flag and its own n_fft carried samples.  A step is a list of items (session, samples, flush): any subset of the slots, each at
+ * most once, each with its own chunk size.  Per item, the stream's push and flush folded into one call:
+ *   N' = N + samples;  E' = max(E, flush ? fv_logmel_frames(N') : fv_logmel_frames_ready(N'));  the item emits the frames [E, E').
+ * With flush the frames reflect at the true end N' and the slot refuses items (FV_ERR_STATE) until fv_wavpool_reset.  A flush at N' = 0
+ * emits nothing; a flush of an utterance that fv_forward alone would refuse (no frame, or not longer than the reflect padding) refuses the
+ * whole step with FV_ERR_INVALID and names the session.  The whole step is checked before any counter moves or anything is enqueued: a
+ * refused step leaves every slot as it was.  One step is one window launch for all its rows (a table entry per row: chunk row, slot and
+ * carry buffer, origins, end, first frame), the forward's own STFT conv, magnitude and filterbank conv on (rows, max k) columns, one crop
+ * launch and one carry launch; the tables travel in the kernel arguments, 32 entries per launch.  With fv_set_batch_invariant(e, 1) every
+ * frame has the bits of fv_forward over the session's whole utterance, whatever the other sessions do.  The entries enqueue eagerly and leave
+ * the captured graphs of fv_forward alone.  fv_pool_create keeps refusing a log-mel engine; vocoder_amd/framing.py (PoolCounters) states
+ * the same plan in Python. */
+typedef struct fv_wavpool_item {
+    int32_t session;           /* slot in [0, S); at most once per step */
+    int32_t samples;           /* in [0, max_chunk_samples] */
+    int32_t flush;             /* 1: the utterance ends with these samples */
+} fv_wavpool_item;
+
+typedef struct fv_wavpool fv_wavpool;
+
+/* The pool's only device allocation, made here on the current HIP device (spectrogram.py:25-104 / test.py:64-71 keep no state) and freed by
+ * fv_wavpool_destroy: two (S, n_fft) carry buffers; every slot has its own bit saying which of the two holds its samples, and only a slot
+ * that pushed samples flips it, so no launch writes a slot's carry and reads it back and an idle slot's carry stays where it is read.
+ * Engines other than FV_MODEL_LOGMEL: FV_ERR_UNSUPPORTED, by name; sessions outside [1, 65535] or max_chunk_samples outside [1, 2^28]:
+ * FV_ERR_INVALID. */
+FV_API fv_status fv_wavpool_create(fv_engine* logmel_engine, int32_t sessions, int32_t max_chunk_samples, fv_wavpool** out);
+/* Bytes of device scratch every step needs (256-byte aligned): the front-end's workspace (spectrogram.py:25-104 / test.py:64-71 allocate theirs
+ * per call) for S rows of fv_wavpool_max_frames frames, and the rows' result before the crop. */
+FV_API size_t fv_wavpool_workspace_bytes(const fv_wavpool* p);
+/* The most frames one item emits in one step — a first emission plus a flush: (n_fft + max_chunk_samples) / hop + 2 (the frame count that
+ * spectrogram.py:25-104 / test.py:64-71 get for a whole file never enters).  An out_frames of this size serves every step. */
+FV_API int32_t fv_wavpool_max_frames(const fv_wavpool* p);
+/* N of one slot: the samples of the current utterance (the file of test.py:64-71 / spectrogram.py:25-104) received so far; 0 for a session
+ * outside [0, S). */
+FV_API int64_t fv_wavpool_received_samples(const fv_wavpool* p, int32_t session);
+/* E of one slot: the frames (columns of spectrogram.py:25-104 / test.py:64-71's result) emitted so far; 0 for a session outside [0, S). */
+FV_API int64_t fv_wavpool_emitted_frames(const fv_wavpool* p, int32_t session);
+/* N - max(0, E hop - pad_l) of one slot: samples received that frames not yet emitted still read (what spectrogram.py:25-104 / test.py:64-71
+ * would hold as the file's tail); 0 for a session outside [0, S). */
+FV_API int64_t fv_wavpool_pending_samples(const fv_wavpool* p, int32_t session);
+/* Pure host (no engine, no GPU), as fv_pool_plan is: what a step would emit, from the framing of spectrogram.py:25-104 / test.py:64-71 alone.
+ * received / emitted / flushed: the S counters and flags (flushed may be NULL: none is).  Writes E' - E of every item to frames_out (count
+ * entries) and returns the largest of them; nothing is changed: the caller moves the counters.  Refuses what fv_wavpool_step refuses of the
+ * items, each named in fv_last_error, with the status as the (negative) result: a session outside [0, S), a duplicate session, samples
+ * outside [0, max_chunk_samples], more than 2^40 samples, a flush of an utterance too short for the reflect padding or for one frame
+ * (FV_ERR_INVALID); an item for a flushed session (FV_ERR_STATE); an unusable config or sessions outside [1, 65535] (FV_ERR_INVALID). */
+FV_API int32_t fv_wavpool_plan(const fv_logmel_config* cfg, int32_t sessions, int32_t max_chunk_samples, const int64_t* received,
+                               const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
+                               int64_t* frames_out);
+/* One step (replaces one spectrogram.py:25-104 call per file, test.py:64-71, for sessions whose audio arrives at different times).  d_chunks:
+ * (count, chunk_stride) fp32, row i holding item i's samples first — the rest of the row (NaN included) is never loaded; NULL when no item
+ * has samples.  d_out: (count, C_out, out_frames) fp32 with out_frames >= the largest E' - E of the step (NULL when out_frames is 0): row i
+ * receives item i's frames first and exactly 0.0f after them, an item that emits nothing a row of zeros; every element is written.
+ * frames_out (may be NULL): count entries, E' - E of every item.  Refusals, checked for the whole step before anything moves: those of
+ * fv_wavpool_plan, a NULL chunk buffer although an item has samples, chunk_stride shorter than the longest chunk, out_frames too small, a
+ * workspace below fv_wavpool_workspace_bytes (FV_ERR_INVALID).  No device allocation, no copy, no host synchronisation.  Asynchronous on
+ * `stream`; ordered like fv_forward on its engine. */
+FV_API fv_status fv_wavpool_step(fv_wavpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                 float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace, size_t workspace_bytes,
+                                 void* stream);
+/* N = E = 0 and not flushed for one slot: its next utterance (the next file of test.py:64-71 / spectrogram.py:25-104).  The carry is kept:
+ * samples before 0 are zeros by index, whatever it holds.  A session outside [0, S): FV_ERR_INVALID. */
+FV_API fv_status fv_wavpool_reset(fv_wavpool* p, int32_t session);
+/* Frees the carry (call it before fv_destroy of its engine, once the pool's work has finished); spectrogram.py:25-104 / test.py:64-71 have
+ * nothing to free. */
+FV_API void fv_wavpool_destroy(fv_wavpool* p);
+
 /* -------- the resampler with its table in global memory: any rate pair.  fv_resample_create keeps the whole table in LDS and refuses the
  *          pairs whose table does not fit (44101 -> 48000; the 52400 -> 44100 of a pitch shift at lowpass_filter_width 64); this entry takes them.
  *          Same object, same design (fv_resample_design), same functions: fv_resample_forward with or without d_lengths and

@@ -54,6 +54,8 @@ EXPORTS = (
     "fv_resample_stream_flush", "fv_resample_stream_reset", "fv_resample_stream_destroy",
     "fv_logmel_frames", "fv_logmel_frames_ready", "fv_logmel_ragged_forward", "fv_logmel_stream_create", "fv_logmel_stream_workspace_bytes",
     "fv_logmel_stream_pending_samples", "fv_logmel_stream_push", "fv_logmel_stream_flush", "fv_logmel_stream_reset", "fv_logmel_stream_destroy",
+    "fv_wavpool_create", "fv_wavpool_workspace_bytes", "fv_wavpool_max_frames", "fv_wavpool_received_samples", "fv_wavpool_emitted_frames",
+    "fv_wavpool_pending_samples", "fv_wavpool_plan", "fv_wavpool_step", "fv_wavpool_reset", "fv_wavpool_destroy",
     "fv_global_resample_create",
     "fv_pitch_shift_plan", "fv_pitch_shift_lengths", "fv_pitch_shift_create", "fv_pitch_shift_destroy", "fv_pitch_shift_workspace_bytes",
     "fv_pitch_shift_stretch", "fv_pitch_shift_forward",
@@ -129,6 +131,10 @@ class PoolConfig(ctypes.Structure):
 
 class PoolItem(ctypes.Structure):
     _fields_ = [("session", _i32), ("frames", _i32), ("flush", _i32)]
+
+
+class WavPoolItem(ctypes.Structure):
+    _fields_ = [("session", _i32), ("samples", _i32), ("flush", _i32)]
 
 
 class PoolRow(ctypes.Structure):
@@ -342,6 +348,27 @@ def lib() -> ctypes.CDLL:
     L.fv_logmel_stream_reset.restype = _i32
     L.fv_logmel_stream_destroy.argtypes = [vp]
     L.fv_logmel_stream_destroy.restype = None
+    wip = ctypes.POINTER(WavPoolItem)
+    L.fv_wavpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_wavpool_create.restype = _i32
+    L.fv_wavpool_workspace_bytes.argtypes = [vp]
+    L.fv_wavpool_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_wavpool_max_frames.argtypes = [vp]
+    L.fv_wavpool_max_frames.restype = _i32
+    L.fv_wavpool_received_samples.argtypes = [vp, _i32]
+    L.fv_wavpool_received_samples.restype = i64
+    L.fv_wavpool_emitted_frames.argtypes = [vp, _i32]
+    L.fv_wavpool_emitted_frames.restype = i64
+    L.fv_wavpool_pending_samples.argtypes = [vp, _i32]
+    L.fv_wavpool_pending_samples.restype = i64
+    L.fv_wavpool_plan.argtypes = [lcp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
+    L.fv_wavpool_plan.restype = _i32
+    L.fv_wavpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, _i32, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_wavpool_step.restype = _i32
+    L.fv_wavpool_reset.argtypes = [vp, _i32]
+    L.fv_wavpool_reset.restype = _i32
+    L.fv_wavpool_destroy.argtypes = [vp]
+    L.fv_wavpool_destroy.restype = None
     L.fv_global_resample_create.argtypes = [rcp, ctypes.POINTER(vp)]
     L.fv_global_resample_create.restype = _i32
     pcp = ctypes.POINTER(PitchShiftConfig)

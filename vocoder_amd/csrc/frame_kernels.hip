@@ -3,6 +3,7 @@
 //   polyphase_tile        wave -> the polyphase signal Yp[row][r][tp] = sample((f0 + tp) hop + r - pad): a 32 x 33 LDS transpose around a sample rule
 //     polyphase_reflect_kernel   one row, reflect edges (the log-mel front-end of fv_forward)
 //     logmel_window_kernel       carry + chunk, reflect edges, per-row ends (fv_logmel_ragged_forward, fv_logmel_stream_*)
+//     logmel_pool_window_kernel  carry + chunk per table entry: sessions that advance independently (fv_wavpool_step)
 //     pv_frame_kernel            one row, zero edges (the whole-row pitch shift)
 //     pv_frame_window_kernel     carry + chunk, zero edges (fv_pv_stream_*)
 //   ola_tile              frames -> samples: overlap-add in ascending g, envelope, crop, around a frame fetch over the global frame index
@@ -126,6 +127,48 @@ fv_status launch_logmel_window(const float* carry, long long carry_stride, long 
         for (int i = 0; i < nz; ++i) blk.len[i] = row_len ? row_len[b0 + i] : -1;
         hipLaunchKernelGGL(logmel_window_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, nz), dim3(256), 0, s, carry, chunk, yp, blk,
                            carry_stride, chunk_stride, carry_origin, chunk_origin, avail, f0, hop, TP, pad_l, pad_r, b0);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+
+// The same for sessions that advance independently (fv_wavpool_step; spectrogram.py:25-56 per session): tensor row k0 + blockIdx.z is one table
+// entry — its own chunk row, its slot's carry in buf[bit], its own origins, end and first frame.  A row emits `count` frames out of the
+// launch's T: the slots its frames read, tp < count + taps - 1, follow logmel_window_kernel's rule; the others load nothing and are exact zeros.
+__global__ __launch_bounds__(256) void logmel_pool_window_kernel(const float* __restrict__ buf0, const float* __restrict__ buf1,
+                                                                 const float* __restrict__ chunk, float* __restrict__ yp,
+                                                                 const SamplePoolBlock tab, long long H, long long chunk_stride, int hop, int TP,
+                                                                 int taps, int pad_l, int pad_r, int k0) {
+    const SamplePoolEntry e = tab.e[blockIdx.z];
+    const long long lpad = e.end >= 0 ? e.end + pad_l + pad_r : 0;    // the padded row's extent (known end only)
+    const int used = e.count > 0 ? e.count + taps - 1 : 0;
+    const SamplePieces p{(e.bit ? buf1 : buf0) + (long long)e.slot * H, chunk + (long long)e.item * chunk_stride, e.carry_origin,
+                         e.chunk_origin, e.end >= 0 ? e.end : e.avail};
+    polyphase_tile(yp + (long long)(k0 + blockIdx.z) * hop * TP, hop, TP, [&](int tp, int r) {
+        if (tp >= used) return 0.f;
+        const long long pos = (e.first + tp) * hop + r;
+        return e.end >= 0 && pos >= lpad ? 0.f : piece_sample(p, reflect_index(pos - pad_l, e.end));
+    });
+}
+
+fv_status launch_logmel_pool_window(const float* buf0, const float* buf1, long long H, const float* chunk, long long chunk_stride,
+                                    const SamplePoolEntry* tab, int rows, float* yp, int hop, int TP, int taps, int pad_l, int pad_r,
+                                    hipStream_t s) {
+    if (rows <= 0 || TP <= 0) return FV_OK;
+    for (int k = 0; k < rows; ++k) {
+        const SamplePoolEntry& e = tab[k];
+        if (e.count > TP - taps + 1 || e.chunk_origin - e.carry_origin != H || e.avail < e.chunk_origin ||
+            (!chunk && e.avail > e.chunk_origin) || (chunk && e.avail - e.chunk_origin > chunk_stride)) {
+            set_error("logmel_pool_window: internal: entry %d (session %d) does not fit its pieces", k, e.slot);
+            return FV_ERR_INVALID;
+        }
+    }
+    for (int k0 = 0; k0 < rows; k0 += kSamplePoolBlock) {
+        const int nz = std::min(kSamplePoolBlock, rows - k0);
+        SamplePoolBlock blk{};
+        for (int i = 0; i < nz; ++i) blk.e[i] = tab[k0 + i];
+        hipLaunchKernelGGL(logmel_pool_window_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, nz), dim3(256), 0, s, buf0, buf1, chunk, yp, blk, H,
+                           chunk_stride, hop, TP, taps, pad_l, pad_r, k0);
         FV_HIP_CHECK(hipGetLastError());
     }
     return FV_OK;

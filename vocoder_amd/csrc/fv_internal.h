@@ -440,6 +440,32 @@ struct LogmelRowBlock {
 fv_status launch_logmel_window(const float* carry, long long carry_stride, long long carry_origin, const float* chunk, long long chunk_stride,
                                long long chunk_origin, const long long* row_len, long long avail, float* yp, int B, long long f0, int hop,
                                int TP, int pad_l, int pad_r, hipStream_t s);
+// Per-session sample pools (sample_pool.h; fv_wavpool_step): every slot advances on its own, so origins, ends and the slot's carry buffer are
+// per table entry; the tables travel BY VALUE, kSamplePoolBlock entries per launch, as the session pool's do.
+static constexpr int kSamplePoolBlock = 32;
+struct SamplePoolEntry {
+    int item, slot;            // row of the chunk buffer; the slot's row in both carry buffers
+    int bit;                   // the carried samples are in buf[bit]; a push writes buf[bit ^ 1]
+    int count;                 // outputs (frames) of this row; slots past what they read are exact zeros
+    long long carry_origin;    // N - H: the carry holds the samples [N - H, N)
+    long long chunk_origin;    // N: the chunk holds the samples [N, avail)
+    long long end;             // the utterance's end N2 when the item flushes, else -1
+    long long avail;           // N2 = N + the item's samples
+    long long first;           // E: the first output (frame) of this row
+};
+struct SamplePoolBlock {
+    SamplePoolEntry e[kSamplePoolBlock];
+};
+// yp[k][r][tp] = sample (first_k + tp) hop + r - pad_l of entry k's session for the tp < count_k + taps - 1 slots its frames read, 0.0f in the
+// other slots (nothing is loaded for them); reflected and cut off as launch_logmel_window does, per entry.  buf0 / buf1: the pool's two
+// (S, H) carry buffers; chunk (., chunk_stride) may be NULL when no entry's chunk holds a sample.
+fv_status launch_logmel_pool_window(const float* buf0, const float* buf1, long long H, const float* chunk, long long chunk_stride,
+                                    const SamplePoolEntry* tab, int rows, float* yp, int hop, int TP, int taps, int pad_l, int pad_r,
+                                    hipStream_t s);
+// sample_carry per entry: buf[bit ^ 1][slot][i] = sample avail - H + i of the slot, i < H — from the chunk at or after chunk_origin, from
+// buf[bit][slot] before it, 0.0f before the utterance's start.  Only the entries' slots are touched.
+fv_status launch_sample_pool_carry(float* buf0, float* buf1, long long H, const float* chunk, long long chunk_stride,
+                                   const SamplePoolEntry* tab, int count, hipStream_t s);
 // y (B, C, T): columns >= row_cols[b] of row b set to 0.0f
 fv_status launch_zero_columns(float* y, const long long* row_cols, int B, int C, long long T, hipStream_t s);
 // rows [0,nb) = Re, [nbp, nbp+nb) = Im, zero padded to nbp = round_up(nb, 8)

@@ -1,5 +1,6 @@
 // The device half of engine_windows.hip: the copy kernels between the caller's tensors, the rings and the window workspace of the time
-// tiles, streams, ragged batches and session pools; and the carry copy of the sample streams (sample_stream.h).  HBM-bound: each lane moves
+// tiles, streams, ragged batches and session pools; and the carry copies of the sample streams (sample_stream.h) and of the sample pools
+// (sample_pool.h).  HBM-bound: each lane moves
 // one fp32, coalesced along T.
 #include <algorithm>
 
@@ -294,6 +295,49 @@ fv_status launch_sample_carry(const float* prev, float* next, const float* chunk
     hipLaunchKernelGGL(sample_carry_kernel, dim3((unsigned)((count + 255) / 256), B), dim3(256), 0, s, prev, next, chunk, stride, chunk_stride, N,
                        next_origin, prev_origin, count);
     FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sample pools (sample_pool.h: fv_wavpool_*).  Every slot has its own counters and its own ping-pong bit; the entries of one step arrive by
+// value (SamplePoolBlock: blockIdx.y picks the entry).
+//   sample_pool_carry: sample_carry's rule per entry — buf[bit ^ 1][slot][i] = sample idx = avail - H + i of the slot: chunk[item][idx - N] for
+//                      idx >= N (= chunk_origin), buf[bit][slot][idx - (N - H)] for 0 <= idx < N, 0.0f for idx < 0.  An entry reads buffer `bit`
+//                      and writes buffer `bit ^ 1` of its own slot only: no launch reads and writes the same buffer of a slot, and the slots
+//                      that take no part in the step keep their carry where their own bit says it is.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sample_pool_carry_kernel(float* buf0, float* buf1, const float* __restrict__ chunk,
+                                                                const SamplePoolBlock tab, long long H, long long chunk_stride) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= H) return;
+    const SamplePoolEntry e = tab.e[blockIdx.y];
+    const float* prev = (e.bit ? buf1 : buf0) + (long long)e.slot * H;
+    float* next = (e.bit ? buf0 : buf1) + (long long)e.slot * H;
+    const long long idx = e.avail - H + i;
+    float v = 0.0f;
+    if (idx >= e.chunk_origin) v = chunk[(long long)e.item * chunk_stride + (idx - e.chunk_origin)];
+    else if (idx >= 0) v = prev[idx - e.carry_origin];
+    next[i] = v;
+}
+fv_status launch_sample_pool_carry(float* buf0, float* buf1, long long H, const float* chunk, long long chunk_stride,
+                                   const SamplePoolEntry* tab, int count, hipStream_t s) {
+    if (count <= 0 || H <= 0) return FV_OK;
+    for (int k = 0; k < count; ++k) {
+        const SamplePoolEntry& e = tab[k];
+        const long long c = e.avail - e.chunk_origin;
+        if (c < 0 || e.chunk_origin - e.carry_origin != H || (c > 0 && (!chunk || c > chunk_stride))) {
+            set_error("sample_pool_carry: internal: entry %d (session %d) does not fit its pieces", k, e.slot);
+            return FV_ERR_INVALID;
+        }
+    }
+    for (int k0 = 0; k0 < count; k0 += kSamplePoolBlock) {
+        const int nz = std::min(kSamplePoolBlock, count - k0);
+        SamplePoolBlock blk{};
+        for (int i = 0; i < nz; ++i) blk.e[i] = tab[k0 + i];
+        hipLaunchKernelGGL(sample_pool_carry_kernel, dim3((unsigned)((H + 255) / 256), nz), dim3(256), 0, s, buf0, buf1, chunk, blk, H,
+                           chunk_stride);
+        FV_HIP_CHECK(hipGetLastError());
+    }
     return FV_OK;
 }
 }  // namespace fv

@@ -40,7 +40,8 @@ def melscale_fbanks_slaney(n_freqs: int, f_min: float, f_max: float, n_mels: int
 class _FrontEnd(_base.EngineModule):
     """What both transforms add to the whole-tensor ``forward``: rows of different lengths and chunks of a stream (include/fishvoc.h
     ``fv_logmel_*``; the framing rule: ``vocoder_amd.framing``).  They replace the frame-windowed ``forward_ragged`` / ``forward_list`` /
-    ``stream`` of the generators, which a front-end cannot have: it windows samples, not frames.  A session pool is not built: ``session_pool`` is the base's, and the engine refuses it."""
+    ``stream`` of the generators, which a front-end cannot have: it windows samples, not frames.  Its pool of independent sessions is
+    ``wav_pool`` (``fv_wavpool_*``); ``session_pool`` is the base's, and the engine refuses it."""
 
     def frames(self, L: int) -> int:
         """Frames of a whole row of ``L`` samples."""
@@ -87,6 +88,13 @@ class _FrontEnd(_base.EngineModule):
         """The front-end chunk by chunk (``vocoder_amd.engine.LogMelStream``): ``push`` at most ``max_chunk_samples`` samples per row, ``flush``
         at the utterance's end.  Reloading the weights or moving the module rebuilds the engine and closes its streams: create a new one then."""
         return self._ragged_engine("stream").logmel_stream(batch, max_chunk_samples)
+
+
+    def wav_pool(self, sessions: int = 1, max_chunk_samples: int = 4096):
+        """The front-end as a pool of sessions that advance independently (``vocoder_amd.engine.WavPool``): every ``step`` serves any subset of
+        the ``sessions`` slots, each with its own chunk of at most ``max_chunk_samples`` samples, each ending at its own length.  Lives and
+        dies with the engine like ``stream()``."""
+        return self._ragged_engine("wav_pool").wav_pool(sessions, max_chunk_samples)
 
 
 class LinearSpectrogram(_FrontEnd):

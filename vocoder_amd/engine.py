@@ -535,6 +535,15 @@ class Engine(_Handle):
         self._streams.add(st)
         return st
 
+    def wav_pool(self, sessions: int, max_chunk_samples: int = 4096) -> "WavPool":
+        """The front-end as a pool of ``sessions`` sessions that advance independently (``WavPool``; the plan of a step:
+        ``vocoder_amd.framing.PoolCounters``): one ``step`` serves any subset of them, each with its own chunk size, each ending at its own
+        length.  ``session_pool()`` keeps refusing a log-mel engine: it windows frames, this one samples."""
+        self._require_logmel("Engine.wav_pool")
+        p = WavPool(self, sessions, max_chunk_samples)
+        self._streams.add(p)
+        return p
+
     def _launch(self, x, tptr, nptr, out, B, T, stream: int) -> int:
         if nptr is not None:
             return self._lib.fv_forward_refinegan(self._h, x.data_ptr(), tptr, nptr, out.data_ptr(), B, T, self._ws.data_ptr(),
@@ -712,6 +721,102 @@ class LogMelStream(_EngineHandle):
         self._check_open()
         check(self._lib.fv_logmel_stream_reset(self._h))
         self._c.reset()
+
+
+class WavPool(_EngineHandle):
+    """Log-mel sessions that advance independently on a log-mel ``Engine`` (``fv_wavpool``, include/fishvoc.h).  ``step(items)`` takes
+    ``(session, samples, flush)`` tuples — ``samples``: a 1-D tensor of at most ``max_chunk_samples`` samples, or ``None`` for none; ``flush``:
+    the utterance ends with these samples — and returns one ``(C_out, k)`` tensor per item (``k`` may be 0): the frames that session emits in
+    this step, ``[E, frames_ready(N'))``, or ``[E, frames(N'))`` against the true end with ``flush``.  A session appears at most once per
+    step; after its flush it refuses items until ``reset(session)``.  The whole step is checked before anything moves: a refused step leaves
+    every session as it was.  Calls are ordered like ``LogMelStream.push``; the pool owns its workspace and dies with its engine."""
+    _destroy, _ws_getter = "fv_wavpool_destroy", "fv_wavpool_workspace_bytes"
+    _closed = ("this wav pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
+               "the module): create a new pool")
+
+    def __init__(self, engine: Engine, sessions: int, max_chunk_samples: int):
+        self._attach(engine, "Engine.wav_pool")
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_wavpool_create(engine._h, int(sessions), int(max_chunk_samples), ctypes.byref(self._h)))
+            self._alloc_workspace()
+        self.sessions, self.max_chunk_samples = int(sessions), int(max_chunk_samples)
+        self.framing = engine.framing
+        self.hop = self.framing.hop_length
+        self.out_channels = engine.out_channels
+        self.max_frames = int(self._lib.fv_wavpool_max_frames(self._h))
+        self.counters = _framing.PoolCounters(self.framing, self.sessions, self.max_chunk_samples)
+
+    # -- counters (host-side: reading them never synchronises) --
+    def received_samples(self, session: int) -> int:
+        return self.counters.received[session]
+
+    def emitted_frames(self, session: int) -> int:
+        return self.counters.emitted[session]
+
+    def pending_samples(self, session: int) -> int:
+        """Samples of one session that frames not yet emitted still read, as the library counts them (fv_wavpool_pending_samples)."""
+        self._check_open()
+        return int(self._lib.fv_wavpool_pending_samples(self._h, int(session)))
+
+    def step(self, items) -> list[torch.Tensor]:
+        """One step for ``items`` (see the class); returns each item's frames ``(C_out, k)``, views of one output buffer."""
+        self._check_open()
+        meta, rows = [], []
+        for it in map(tuple, items):
+            s, x, flush = it[0], it[1], it[2] if len(it) > 2 else False
+            if x is not None:
+                _require_cuda(x, "WavPool.step")
+                if x.dim() != 1:
+                    raise ValueError(f"expected a 1-D chunk of samples, got {tuple(x.shape)}")
+            rows.append(x)
+            meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(flush)))
+        longest = max((c for _, c, _ in meta), default=0)
+        chunks = None
+        if longest:
+            chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=self._engine.device)
+            for i, x in enumerate(rows):
+                if x is not None and x.shape[0]:
+                    chunks[i, :x.shape[0]] = x
+        out, emit = self.step_padded(meta, chunks)
+        return [out[i, :, :k] for i, k in enumerate(emit)]
+
+    def step_padded(self, items, chunks: torch.Tensor | None, out: torch.Tensor | None = None) -> tuple[torch.Tensor, list[int]]:
+        """The step on the caller's padded buffers, as ``fv_wavpool_step`` takes them: ``items``: ``(session, samples, flush)`` integers;
+        ``chunks``: ``(count, chunk_stride)`` with item i's samples first in row i (the rest, NaN included, is never read), ``None`` when no
+        item has samples; ``out``: ``(count, C_out, out_frames)``, sized from the Python plan when not given.  Returns ``(out, frames emitted
+        per item)``: row i holds item i's frames first and zeros after them."""
+        self._check_open()
+        items = [(int(s), int(c), bool(f)) for s, c, f in items]
+        count = len(items)
+        stride = 0
+        if chunks is not None:
+            _require_cuda(chunks, "WavPool.step_padded")
+            if chunks.dim() != 2 or chunks.shape[0] != count or not chunks.is_contiguous():
+                raise ValueError(f"expected contiguous chunks of shape ({count}, chunk_stride), got {tuple(chunks.shape)}")
+            stride = int(chunks.shape[1])
+        plan = self.counters.plan(items)                          # sizes the output before anything is launched; refuses what the library would
+        dev = self._engine.device
+        if out is None:
+            out = torch.empty((count, self.out_channels, max(plan, default=0)), dtype=torch.float32, device=dev)
+        elif out.dim() != 3 or out.shape[0] != count or out.shape[1] != self.out_channels or not out.is_contiguous():
+            raise ValueError(f"expected a contiguous out of shape ({count}, {self.out_channels}, out_frames), got {tuple(out.shape)}")
+        arr = (_lib.WavPoolItem * max(count, 1))(*[_lib.WavPoolItem(s, c, int(f)) for s, c, f in items])
+        got = (ctypes.c_int64 * max(count, 1))()
+        self._engine._enqueue(dev, lambda stream: self._lib.fv_wavpool_step(
+            self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None, stride,
+            out.data_ptr() if out.numel() else None, int(out.shape[2]), got, self._ws.data_ptr(), self._ws.numel() * 4, stream),
+            owner=self, eager=True)
+        emit = [int(got[i]) for i in range(count)]
+        self.counters.apply(items, plan)                          # the Python counters move as the library's did
+        if plan != emit:
+            raise RuntimeError(f"the wav pool emitted {emit} frames where the framing rule says {plan}")
+        return out, emit
+
+    def reset(self, session: int) -> None:
+        """Start the next utterance in one slot: N = E = 0; its carry is kept."""
+        self._check_open()
+        check(self._lib.fv_wavpool_reset(self._h, int(session)))
+        self.counters.reset(int(session))
 
 
 class SessionPool(_EngineHandle):

@@ -378,6 +378,78 @@ def stream_wav_synthesis(model: InferenceModel, chunks, total_samples: int, chun
     return (torch.cat(collected, dim=-1) if collected else None), stats
 
 
+class WavSessionPool:
+    """wav -> wav for live sources that advance independently: the front-end's ``WavPool`` (``vocoder_amd.engine``) feeding the generator's
+    ``SessionPool`` on the device.  ``step([(session, samples, end), ...])`` — ``samples``: a 1-D tensor of at most ``max_chunk_samples``
+    samples or ``None``; ``end``: the utterance ends with them — runs one ``WavPool.step_padded`` and hands its ``(count, n_mels, out_frames)``
+    buffer and the per-item frame counts straight to ``SessionPool.step_padded``: the counts are known on the host (``framing.PoolCounters``),
+    so nothing synchronises and nothing is copied.  Returns each item's audio ``(C_out, k * hop)``; a session's audio trails its samples by the
+    front-end's ``pad_r`` samples plus the generator's lookahead.  Both plans are checked before anything is launched: a refused step leaves
+    both pools as they were.  A generator that takes a pitch template is refused: its F0 and template streams advance in lockstep, and their
+    pool is not built."""
+
+    def __init__(self, frontend: nn.Module, generator: nn.Module, sessions: int, max_chunk_samples: int):
+        if takes_template(generator):
+            raise ValueError(f"WavSessionPool: {type(generator).__name__} takes a pitch template next to the mel; the per-session F0 / template "
+                             "pool it would need is not built (the template streams advance in lockstep)")
+        if not hasattr(frontend, "wav_pool") or not hasattr(generator, "session_pool"):
+            raise ValueError(f"WavSessionPool needs a front-end with wav_pool() and a generator with session_pool(), got "
+                             f"{type(frontend).__name__} and {type(generator).__name__}")
+        self.wav_pool = frontend.wav_pool(sessions, max_chunk_samples)
+        try:
+            self.gen_pool = generator.session_pool(sessions, max_chunk_frames=self.wav_pool.max_frames)
+        except Exception:
+            self.wav_pool.close()
+            raise
+        if self.gen_pool.in_channels != self.wav_pool.out_channels:
+            self.close()
+            raise ValueError(f"the front-end emits {self.wav_pool.out_channels} channels, the generator takes {self.gen_pool.in_channels}")
+        self.sessions, self.max_chunk_samples, self.hop = int(sessions), int(max_chunk_samples), self.gen_pool.hop
+
+    @torch.no_grad()
+    def step(self, items) -> list:
+        """One step for ``items`` (see the class); returns each item's audio, views of one output buffer."""
+        wp, gp = self.wav_pool, self.gen_pool
+        wp._check_open()
+        gp._check_open()
+        meta, rows = [], []
+        for it in map(tuple, items):
+            s, x, end = it[0], it[1], it[2] if len(it) > 2 else False
+            if x is not None and x.dim() != 1:
+                raise ValueError(f"expected a 1-D chunk of samples, got {tuple(x.shape)}")
+            rows.append(x)
+            meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(end)))
+        frames = wp.counters.plan(meta)                                    # both plans before anything moves: each refuses what its library would
+        gen_items = [(s, k, end) for (s, _, end), k in zip(meta, frames)]
+        gp.state.plan(gen_items)
+        longest = max((c for _, c, _ in meta), default=0)
+        chunks = None
+        if longest:
+            chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=wp._engine.device)
+            for i, x in enumerate(rows):
+                if x is not None and x.shape[0]:
+                    chunks[i, :x.shape[0]] = x
+        mel, _ = wp.step_padded(meta, chunks)
+        audio, out_frames = gp.step_padded(gen_items, mel if mel.shape[2] else None)
+        return [audio[i, :, :k * self.hop] for i, k in enumerate(out_frames)]
+
+    def reset(self, session: int) -> None:
+        """The next utterance of one slot, in both pools."""
+        self.wav_pool.reset(session)
+        self.gen_pool.reset(session)
+
+    def close(self) -> None:
+        self.wav_pool.close()
+        if getattr(self, "gen_pool", None) is not None:
+            self.gen_pool.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
 def _wav_chunks(path, chunk: int):
     """A PCM wav (every width ``read_wav`` takes) ``chunk`` frames at a time: yields ``(channels, c)`` float32 tensors, read as the loop asks
     for them; together they are ``read_wav``'s samples."""
