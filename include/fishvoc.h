@@ -1078,6 +1078,49 @@ FV_API fv_status fv_conv_set_precision(fv_conv* c, int32_t precision);
 FV_API fv_status fv_conv_set_algorithm(fv_conv* c, int32_t algo);
 FV_API void fv_conv_destroy(fv_conv* c);
 
+/* -------- vector quantiser: VQ / residual VQ, encode and decode --------
+ * The stage between generator.encoder and generator.decoder of VQVAEModel (vae.py:66-87: encodec's VectorQuantization for
+ * num_quantizers == 1, ResidualVectorQuantization above) and the `vq` slot of UnifyGenerator (unify.py:21-53), inference arithmetic only
+ * (no EMA, k-means init, dead-code expiry, straight-through or commitment loss; no project_in / project_out: codebook_dim == dim):
+ *   search(x, embed) = argmax_j (x . e_j - h_j), h_j = |e_j|^2 / 2 formed in fp64 at load and rounded to fp32; the lowest index wins on
+ *   equal scores, a NaN score never wins and a frame whose scores are all NaN takes code 0;
+ *   r_0 = x, c_q = search(r_q, embed_q), r_{q+1} = r_q - e_{c_q}, z = ((e_{c_0} + e_{c_1}) + ...): fp32, one rounding per operation.
+ * A frame's scores are formed in an order that depends on dim alone, so its codes and z have the same bits alone, in any batch, under
+ * any chunking along T and any slice count (fv_vq_set_slices).
+ * Limits: dim in [1, 4096], codebook_size in [1, 65536], num_quantizers in [1, 32]; batch in [0, 65535], batch * T at most 2^30 frames.
+ * Every entry validates all a host can see before it enqueues anything, and names the offending field; encode and decode are
+ * asynchronous on `stream`. */
+typedef struct fv_vq_config {
+    int32_t dim;            /* D: channels of a frame (vae.py:68 latent_size) */
+    int32_t codebook_size;  /* K (vae.py:69) */
+    int32_t num_quantizers; /* n_q (vae.py:70); 1 = VectorQuantization */
+} fv_vq_config;
+
+typedef struct fv_vq fv_vq;
+
+/* vae.py:66-78: no device memory yet; FV_ERR_INVALID names the field outside its limits. */
+FV_API fv_status fv_vq_create(const fv_vq_config* cfg, fv_vq** out);
+FV_API void fv_vq_destroy(fv_vq* vq);
+/* vae.py:66-78 (`layers.{layer}._codebook.embed`): host_embed (codebook_size, dim) row-major, copied (synchronously), packed into MFMA
+ * fragment order and h formed.  May be called again to replace a layer's codebook once the device is idle. */
+FV_API fv_status fv_vq_load_codebook(fv_vq* vq, int32_t layer, const float* host_embed);
+/* Codebook slices of the search's grid: 0 (default) = by launch size.  Results do not depend on it; fv_vq_workspace_bytes does.
+ * No reference counterpart (vae.py:82 is one torch call). */
+FV_API fv_status fv_vq_set_slices(fv_vq* vq, int32_t slices);
+/* Bytes of device scratch fv_vq_encode needs for (batch, T): the residual (num_quantizers > 1) and the per-slice partials (vae.py:82
+ * allocates the N x K distance matrix instead).  0 for an invalid shape. */
+FV_API size_t fv_vq_workspace_bytes(const fv_vq* vq, int32_t batch, int64_t T);
+/* vae.py:82 / unify.py:21-23,39-41: d_x is a (batch, dim, T) activation, x_row_stride >= T the distance in floats between its channels
+ * (batch rows are dim * x_row_stride apart: a slice along T of a contiguous tensor passes as it is).  host_frames: NULL, or `batch` frame
+ * counts in [0, T]; frames at or past a row's count are never loaded, get code -1 and exact zeros in z.  d_codes: (num_quantizers,
+ * batch, T) int32; d_z: NULL (codes only) or (batch, dim, T) contiguous.  2 * num_quantizers launches per 256 batch rows. */
+FV_API fv_status fv_vq_encode(fv_vq* vq, const float* d_x, int64_t x_row_stride, const int32_t* host_frames, int32_t* d_codes, float* d_z,
+                              int32_t batch, int64_t T, void* d_workspace, size_t workspace_bytes, void* stream);
+/* unify.py:47 (vq.from_codes) / vae.py:87: d_codes (num_quantizers, batch, T) int32 -> d_z (batch, dim, T), the same layer-ordered sum.
+ * A negative code contributes nothing (an all-negative frame is exact zeros), and so does one >= codebook_size, which the caller is
+ * expected to have refused; frames at or past host_frames[b] are zeros. */
+FV_API fv_status fv_vq_decode(fv_vq* vq, const int32_t* d_codes, const int32_t* host_frames, float* d_z, int32_t batch, int64_t T, void* stream);
+
 /* -------- per-launch timing (measurement aid; bench.py's roofline leg) --------
  * Between fv_profile_begin and fv_profile_end every kernel that fv_forward enqueues is bracketed by hipEvents recorded
  * on the launch stream.  fv_profile_end synchronises them and writes a JSON array

@@ -69,6 +69,7 @@ EXPORTS = (
     "fv_osc_stream_create", "fv_osc_stream_pending_frames", "fv_osc_stream_push", "fv_osc_stream_flush", "fv_osc_stream_reset",
     "fv_osc_stream_destroy",
     "fv_pair_wino4_tile", "fv_pair_wino4_pack",
+    "fv_vq_create", "fv_vq_destroy", "fv_vq_load_codebook", "fv_vq_set_slices", "fv_vq_workspace_bytes", "fv_vq_encode", "fv_vq_decode",
 )
 
 _i32 = ctypes.c_int32
@@ -160,6 +161,10 @@ class F0Config(ctypes.Structure):
 
 class TemplateConfig(ctypes.Structure):
     _fields_ = [("sample_rate", _i32), ("hop_length", _i32), ("kind", _i32), ("amplitude", ctypes.c_float)]
+
+
+class VQConfig(ctypes.Structure):
+    _fields_ = [("dim", _i32), ("codebook_size", _i32), ("num_quantizers", _i32)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -459,6 +464,20 @@ def lib() -> ctypes.CDLL:
     L.fv_pair_wino4_tile.restype = _i32
     L.fv_pair_wino4_pack.argtypes = [fp, _i32, fp, i64]
     L.fv_pair_wino4_pack.restype = i64
+    L.fv_vq_create.argtypes = [ctypes.POINTER(VQConfig), ctypes.POINTER(vp)]
+    L.fv_vq_create.restype = _i32
+    L.fv_vq_destroy.argtypes = [vp]
+    L.fv_vq_destroy.restype = None
+    L.fv_vq_load_codebook.argtypes = [vp, _i32, fp]
+    L.fv_vq_load_codebook.restype = _i32
+    L.fv_vq_set_slices.argtypes = [vp, _i32]
+    L.fv_vq_set_slices.restype = _i32
+    L.fv_vq_workspace_bytes.argtypes = [vp, _i32, i64]
+    L.fv_vq_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_vq_encode.argtypes = [vp, vp, i64, i32p, vp, vp, _i32, i64, vp, ctypes.c_size_t, vp]
+    L.fv_vq_encode.restype = _i32
+    L.fv_vq_decode.argtypes = [vp, vp, i32p, vp, _i32, i64, vp]
+    L.fv_vq_decode.restype = _i32
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

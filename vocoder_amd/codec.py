@@ -1,0 +1,155 @@
+"""The inference face of the reference's ``VQVAEModel`` (fish_vocoder/models/vae.py:51-109): audio -> codes, codes -> audio.
+
+``VQVAECodec(encoder, decoder, vq, frontend=None)`` runs ``generator.encoder`` -> ``vq`` -> ``generator.decoder`` (vae.py:81-87) on the
+drop-in modules, every stage on the HIP engine; the quantiser is ``modules.quantizers`` (``fv_vq_*``).  A Lightning checkpoint's
+``generator.encoder.*``, ``generator.decoder.*`` and ``vq.*`` keys are the module's own ``encoder.*``, ``decoder.*`` and ``vq.*``
+(``load_checkpoint``).  Command line::
+
+    python -m vocoder_amd.codec encode -i a.wav -o out/ [--checkpoint ckpt]      # writes out/a.codes.npy, int64 (n_q, T) or (T,)
+    python -m vocoder_amd.codec decode -i out/a.codes.npy -o out/                 # writes out/a.wav
+
+The architecture defaults to configs/model/vqvae.yaml's (vocos-small-vae at 24000_2048_3072, 512 latent channels, 4096 codes, one
+quantiser); ``vocoder_amd.inference``'s command line is untouched.
+"""
+from __future__ import annotations
+
+import argparse
+from pathlib import Path
+
+import numpy as np
+import torch
+from torch import nn
+
+
+class VQVAECodec(nn.Module):
+    def __init__(self, encoder: nn.Module, decoder: nn.Module, vq: nn.Module, frontend: nn.Module | None = None, hop_length: int | None = None):
+        super().__init__()
+        self.encoder, self.decoder, self.vq, self.frontend = encoder, decoder, vq, frontend
+        hop = hop_length if hop_length is not None else getattr(frontend, "hop_length", None)
+        self.hop_length = None if hop is None else int(hop)
+
+    def _latent(self, x: torch.Tensor) -> torch.Tensor:
+        """Audio ``(B, 1, L)`` / ``(B, L)`` goes through the front-end first (vae.py:14 ``mel_transforms.input``); a spectrogram
+        ``(B, C, T)`` with more than one channel goes straight into the encoder."""
+        if self.frontend is not None and (x.dim() == 2 or x.shape[1] == 1):
+            x = self.frontend(x if x.dim() == 3 else x[:, None, :])
+        elif x.dim() != 3:
+            raise ValueError(f"VQVAECodec: expected audio (B, 1, L) with a front-end, or a spectrogram (B, C, T); got {tuple(x.shape)}")
+        return self.encoder(x)
+
+    def encode(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
+        """``codes``: int64 ``(B, T)`` for one quantiser, ``(n_q, B, T)`` for the residual form; ``lengths`` are latent frames per row."""
+        return self.vq.encode(self._latent(x), lengths)
+
+    def decode(self, codes: torch.Tensor) -> torch.Tensor:
+        y = self.decoder(self.vq.from_codes(codes)[0])
+        return y[:, None, :] if y.ndim == 2 else y
+
+    def forward(self, audio: torch.Tensor, mask=None):
+        """vae.py:80-109: ``(fake_audio, 0)``, trimmed / zero-padded to the input's length, which it may miss by a hop at most."""
+        if audio.dim() == 2:
+            audio = audio[:, None, :]
+        quantize, _, _ = self.vq(self._latent(audio))
+        fake = self.decoder(quantize)
+        fake = fake[:, None, :] if fake.ndim == 2 else fake
+        if self.hop_length is not None:
+            assert abs(fake.size(2) - audio.size(2)) <= self.hop_length, (fake.size(2), audio.size(2), self.hop_length)   # vae.py:89
+        if fake.size(2) > audio.size(2):
+            fake = fake[:, :, : audio.size(2)]
+        else:
+            fake = torch.nn.functional.pad(fake, (0, audio.size(2) - fake.size(2)))
+        return fake, 0
+
+    def load_checkpoint(self, ckpt, trust_checkpoint: bool = False):
+        """A path or dict; Lightning's ``state_dict`` wrapper and its ``generator.`` prefix are taken off, other prefixes
+        (discriminators, mel_transforms) dropped; loads strictly."""
+        if isinstance(ckpt, (str, Path)):
+            try:
+                ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
+            except Exception:
+                if not trust_checkpoint:
+                    raise
+                ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
+        sd = ckpt.get("state_dict", ckpt)
+        own = {}
+        for k, v in sd.items():
+            if k.startswith("generator.encoder.") or k.startswith("generator.decoder."):
+                own[k[len("generator."):]] = v
+            elif k.startswith(("vq.", "encoder.", "decoder.", "frontend.")):
+                own[k] = v
+        for k, v in self.state_dict().items():          # the front-end's window is a constant, not a checkpoint key
+            if k.startswith("frontend."):
+                own.setdefault(k, v)
+        return self.load_state_dict(own, strict=True)
+
+
+def build_vqvae(n_fft: int = 3072, hop_length: int = 2048, win_length: int = 3072, latent_size: int = 512, codebook_size: int = 4096,
+                num_quantizers: int = 1, encoder_depths=(6,), encoder_dims=(512,), decoder_depths=(6, 3), decoder_dims=(512, 1024),
+                kernel_size: int = 7) -> VQVAECodec:
+    """configs/model/vqvae.yaml + generator/vocos-small-vae.yaml with the drop-in modules."""
+    from .data.transforms.spectrogram import LinearSpectrogram
+    from .modules.encoders.convnext import ConvNeXtEncoder
+    from .modules.generators.unify import UnifyGenerator
+    from .modules.generators.vocos import ISTFTHead
+    from .modules.quantizers import ResidualVectorQuantization, VectorQuantization
+    if encoder_dims[-1] != latent_size:
+        raise ValueError(f"latent_size ({latent_size}) must equal the encoder's last width ({encoder_dims[-1]})")
+    encoder = ConvNeXtEncoder(input_channels=n_fft // 2 + 1, depths=list(encoder_depths), dims=list(encoder_dims), kernel_size=kernel_size)
+    decoder = UnifyGenerator(
+        backbone=ConvNeXtEncoder(input_channels=latent_size, depths=list(decoder_depths), dims=list(decoder_dims), kernel_size=kernel_size),
+        head=ISTFTHead(dim=decoder_dims[-1], n_fft=n_fft, hop_length=hop_length, win_length=win_length, padding="same"))
+    if num_quantizers > 1:      # vae.py:66-78
+        vq = ResidualVectorQuantization(dim=latent_size, codebook_size=codebook_size, num_quantizers=num_quantizers, kmeans_init=False)
+    else:
+        vq = VectorQuantization(dim=latent_size, codebook_size=codebook_size, kmeans_init=False)
+    return VQVAECodec(encoder, decoder, vq, frontend=LinearSpectrogram(n_fft, win_length, hop_length), hop_length=hop_length)
+
+
+def main(argv=None):
+    from .inference import read_wav, write_wav
+    ap = argparse.ArgumentParser(prog="python -m vocoder_amd.codec", description=__doc__.split("\n")[0])
+    ap.add_argument("mode", choices=("encode", "decode"))
+    ap.add_argument("-i", "--input", required=True, help="encode: a PCM .wav; decode: a .codes.npy")
+    ap.add_argument("-o", "--output-dir", default="generated")
+    ap.add_argument("--checkpoint", default=None, help="Lightning checkpoint or state dict (default: the untrained initialisation)")
+    ap.add_argument("--trust-checkpoint", action="store_true")
+    ap.add_argument("--sample-rate", type=int, default=24000)
+    ap.add_argument("--n-fft", type=int, default=3072)
+    ap.add_argument("--hop-length", type=int, default=2048)
+    ap.add_argument("--win-length", type=int, default=3072)
+    ap.add_argument("--latent-size", type=int, default=512)
+    ap.add_argument("--codebook-size", type=int, default=4096)
+    ap.add_argument("--num-quantizers", type=int, default=1)
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("vocoder_amd.codec needs a HIP device: there is no CPU path")
+    model = build_vqvae(a.n_fft, a.hop_length, a.win_length, a.latent_size, a.codebook_size, a.num_quantizers,
+                        encoder_dims=(a.latent_size,), decoder_dims=(a.latent_size, 2 * a.latent_size))
+    if a.checkpoint:
+        model.load_checkpoint(a.checkpoint, a.trust_checkpoint)
+    model = model.eval().cuda()
+    out = Path(a.output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    src = Path(a.input)
+    if a.mode == "encode":
+        wav, sr = read_wav(src)
+        if sr != a.sample_rate:
+            raise SystemExit(f"{src}: {sr} Hz, the model runs at {a.sample_rate} Hz (resample with vocoder_amd.inference --resample first)")
+        audio = torch.from_numpy(wav.mean(0, keepdims=True))[None].cuda()
+        codes = model.encode(audio)
+        codes = codes[:, 0] if codes.dim() == 3 else codes[0]
+        dst = out / f"{src.stem}.codes.npy"
+        np.save(dst, codes.cpu().numpy())
+    else:
+        codes = torch.from_numpy(np.load(src)).to(torch.int64).cuda()
+        codes = codes[:, None, :] if codes.dim() == 2 else codes[None, :]
+        audio = model.decode(codes)
+        stem = src.name[: -len(".codes.npy")] if src.name.endswith(".codes.npy") else src.stem
+        dst = out / f"{stem}.wav"
+        write_wav(dst, audio[0, 0].cpu().numpy(), a.sample_rate)
+    print(dst)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

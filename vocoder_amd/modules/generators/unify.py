@@ -1,6 +1,7 @@
 """Drop-in for ``fish_vocoder.modules.generators.unify.UnifyGenerator`` (reference unify.py:5-60):
-``head(backbone(x), template=template)``, channel dim added for 2-D heads.  ``vq`` is out of scope (no shipped
-config wires one) and must be None."""
+``head(backbone(x), template=template)``, channel dim added for 2-D heads.  With ``vq`` (a ``modules.quantizers`` quantiser) the backbone's
+output is quantised on the way (unify.py:21-23), ``forward`` returns ``(audio, vq_result)`` (unify.py:30-31), ``encode`` gives the codes and
+``decode`` turns codes into audio (unify.py:35-53)."""
 from __future__ import annotations
 
 import torch
@@ -10,19 +11,27 @@ from torch import nn
 class UnifyGenerator(nn.Module):
     def __init__(self, backbone: nn.Module, head: nn.Module, vq: nn.Module | None = None):
         super().__init__()
-        if vq is not None:
-            raise NotImplementedError("UnifyGenerator(vq=...) is out of scope: no shipped generator config sets vq")
-        self.backbone, self.head, self.vq = backbone, head, None
+        self.backbone, self.head, self.vq = backbone, head, vq
 
-    def forward(self, x: torch.Tensor, template=None) -> torch.Tensor:
-        x = self.head(self.backbone(x), template=template)
-        return x[:, None, :] if x.ndim == 2 else x
+    def forward(self, x: torch.Tensor, template=None):
+        x = self.backbone(x)
+        if self.vq is not None:
+            vq_result = self.vq(x)
+            x = vq_result.z
+        x = self.head(x, template=template)
+        x = x[:, None, :] if x.ndim == 2 else x
+        return (x, vq_result) if self.vq is not None else x
 
     def encode(self, x):
-        raise ValueError("VQ module is not present in the model.")  # unify.py:36-37
+        if self.vq is None:
+            raise ValueError("VQ module is not present in the model.")  # unify.py:36-37
+        return self.vq(self.backbone(x)).codes
 
     def decode(self, codes, template=None):
-        raise ValueError("VQ module is not present in the model.")  # unify.py:44-45
+        if self.vq is None:
+            raise ValueError("VQ module is not present in the model.")  # unify.py:44-45
+        x = self.head(self.vq.from_codes(codes)[0], template=template)
+        return x[:, None, :] if x.ndim == 2 else x
 
     def remove_parametrizations(self):
         for m in (self.backbone, self.head):
