@@ -192,6 +192,33 @@ def test_oscillator_stream_equals_the_whole_row_forward_bit_for_bit(kind, name):
     assert unvoiced.any() and not _bits(got[:, 0])[unvoiced].any()          # +0.0, not -0.0
 
 
+def test_streams_of_thirty_four_rows_pass_one_launchs_lengths():
+    """Batch 34, more than the 32 lengths one launch carries, two pushes and a flush: rows 32 and 33 ride a second launch with the input of
+    rows 0 and 1 and give their bits, in the tracker stream and in the oscillator stream; rows 0 ... 2 are the whole-row result of _case."""
+    sr, W, hop, fmin, fmax, L = CONFIGS[0]
+    rows3, mod, f0_bits, ap_bits = _case(0)
+    x = rows3[0].cpu().numpy()
+    wide = np.stack([np.roll(x, 37 * b) for b in list(range(32)) + [0, 1]])
+    with mod.stream(34, 1501) as st:
+        f0, ap = _track(st, torch.from_numpy(wide).cuda(), [1500, 1501], W, hop)
+    f0b, apb = _bits(f0), _bits(ap)
+    assert f0b.shape == (34, L // hop) and np.array_equal(f0b[:3], f0_bits) and np.array_equal(apb[:3], ap_bits)
+    assert np.array_equal(f0b[32:], f0b[:2]) and np.array_equal(apb[32:], apb[:2])
+    assert not np.array_equal(f0b[31], f0b[0]) and not np.array_equal(f0b[0], f0b[1])          # the rows differ
+
+    T = 64
+    track = _osc_f0()[:, :T]
+    fw = np.stack([np.roll(track[b % 2], 5 * b) for b in list(range(32)) + [0, 1]])
+    osc = f0mod.PitchTemplate(OSC_SR, OSC_HOP, amplitude=0.5)
+    xw = torch.from_numpy(fw).cuda()
+    with osc.stream(34, 34) as st:
+        y = torch.cat([st.push(_strided(xw[:, :30])), st.push(_strided(xw[:, 30:])), st.flush()], dim=-1)
+    yb = _bits(y[:, 0])
+    assert yb.shape == (34, T * OSC_HOP) and np.array_equal(yb[:2], _bits(osc(_strided(xw[:2]))[:, 0]))
+    assert np.array_equal(yb[32:], yb[:2]) and float(y[32:].abs().max()) > 0.49
+    assert not np.array_equal(yb[31], yb[1]) and not np.array_equal(yb[0], yb[1])
+
+
 def test_template_stream_equals_template_from_audio_bit_for_bit():
     sr, W, hop, fmin, fmax, L = CONFIGS[0]
     rows, _, _, _ = _case(0)

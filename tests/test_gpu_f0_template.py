@@ -112,6 +112,51 @@ def test_ragged_rows_equal_the_rows_alone_bit_for_bit(i):
     assert frames[0] == T and (f0d[0] > 0).any() and tn[0].abs().max() > 0.9
 
 
+WIDE_LENGTHS = {0: 16000, 1: 9001, 31: 4000, 32: 700, 33: 2613}      # the other rows of the 34: a few frames each
+
+
+def test_thirty_four_ragged_rows_pass_one_launchs_lengths():
+    """34 rows, more than the 32 lengths one launch carries, so rows 32 and 33 ride a second launch of every kernel; their lengths differ
+    from those of rows 0 and 1.  Rows 31, 32 and 33 are the bits of the rows run alone and meet the float64 restatement within the file's bars."""
+    sr, W, hop, fmin, fmax, L = CONFIGS[0]
+    x, _, _, mod = _case(0)
+    lengths = [WIDE_LENGTHS.get(b, (130, 0, 515, 1300, 127)[b % 5]) for b in range(34)]
+    rows = np.stack([np.roll(x, 37 * b) for b in range(34)])
+    dirty = rows.copy()
+    for b, n in enumerate(lengths):
+        dirty[b, n:] = np.nan
+    frames = [n // hop for n in lengths]
+    assert (frames[32], frames[33]) != (frames[0], frames[1]) and min(frames[31:]) >= 5 and 0 < max(frames[2:31]) <= 10
+    osc = f0mod.PitchTemplate(sr, hop)
+    f0, ap = mod.forward_ragged(_strided(dirty), lengths)
+    f0n = f0.clone()
+    for b, k in enumerate(frames):
+        f0n[b, k:] = float("nan")
+    tmpl = osc.forward_ragged(f0n, frames)
+    assert tuple(f0.shape) == tuple(ap.shape) == (34, L // hop) and tuple(tmpl.shape) == (34, 1, L)
+    total = left_out = voiced_frames = 0
+    for b in (31, 32, 33):
+        n, k = lengths[b], frames[b]
+        f0a, apa = mod(_strided(rows[b:b + 1, :n]))
+        ta = osc(f0a)
+        assert np.array_equal(_bits(f0a[0]), _bits(f0[b, :k])) and np.array_equal(_bits(apa[0]), _bits(ap[b, :k])), b
+        assert np.array_equal(_bits(ta[0, 0]), _bits(tmpl[b, 0, :k * hop])), b
+        assert _bits(f0[b, k:]).sum() == 0 and _bits(ap[b, k:]).sum() == 0 and _bits(tmpl[b, 0, k * hop:]).sum() == 0
+        ref = fref.yin(rows[b, :n], sr, hop, W, fmin, fmax)
+        g0, g1 = f0[b, :k].cpu().numpy().astype(np.float64), ap[b, :k].cpu().numpy().astype(np.float64)
+        compared, voiced = ref["stable"], ref["lag"] > 0
+        both = compared & voiced
+        d_ap = float(np.abs(g1 - ref["aperiodicity"]).max())
+        d_f0 = float(np.abs(g0[both] / ref["f0"][both] - 1.0).max()) if both.any() else 0.0
+        d_t = float(np.abs(tmpl[b, 0, :k * hop].cpu().numpy().astype(np.float64) - fref.template(g0.astype(np.float32), sr, hop, "sine", 1.0)).max())
+        print(f"row {b} ({n} samples, {k} frames, {int(both.sum())} voiced and compared): max|d aperiodicity| = {d_ap:.2e}, "
+              f"max rel|d f0| = {d_f0:.2e}, template max|d| = {d_t:.2e}")
+        assert np.array_equal(g0[compared] > 0, voiced[compared]), b
+        assert d_ap <= BAR and d_f0 <= BAR and d_t <= TEMPLATE_BAR, b
+        total, left_out, voiced_frames = total + k, left_out + int((~compared).sum()), voiced_frames + int(both.sum())
+    assert left_out <= 0.02 * total and voiced_frames >= 6
+
+
 def _template_error(sr, hop, f0, kind, amplitude=1.0, tail=None):
     """max |GPU - oscillator on the restatement's exact integer phase|, and the GPU output."""
     y = f0mod.PitchTemplate(sr, hop, kind=kind, amplitude=amplitude)(_strided(f0[None].astype(np.float32)))

@@ -151,6 +151,40 @@ def test_lockstep_steps_are_the_streams_pushes_bit_for_bit(model):
     eng.close()
 
 
+def test_lockstep_past_one_launchs_table_entries():
+    """34 sessions on the smallest engine, more than the 32 entries one launch carries: a step in which no session has its lookahead yet
+    (34 ring-only gather entries, 34 zero crop rows), a step in which all 34 emit (34 rows), a flush.  Every step is the push of a Stream of
+    34 rows bit for bit; sessions 0, 31, 32 and 33 — either side of the edge between the first and the second launch — are named."""
+    mk, cin, _, _ = _model("istft_head")
+    dev = _dev()
+    eng = mk()
+    hop, S, R = eng.output_length(1), 34, eng.reach_frames
+    sizes = [R - 1, MAX_CHUNK]
+    assert 1 <= sizes[0] < R < sum(sizes)
+    x = torch.from_numpy(np.random.default_rng(12).standard_normal((S, cin, sum(sizes))).astype(np.float32)).to(dev)
+    with eng.stream(S, MAX_CHUNK) as st:
+        want = [st.push(x[:, :, :sizes[0]]).clone(), st.push(x[:, :, sizes[0]:]).clone(), st.flush().clone()]
+    assert want[0].shape[2] == 0 and want[1].shape[2] > 0 and sum(w.shape[2] for w in want) == sum(sizes) * hop
+    with eng.session_pool(S, MAX_CHUNK) as pool:
+        f = 0
+        for k, n in enumerate(sizes + [0]):
+            items = [(s, n, k == 2) for s in range(S)]
+            pad = torch.full((S, cin, MAX_CHUNK), float("nan"), device=dev)
+            pad[:, :, :n] = x[:, :, f:f + n]
+            plan = pool.state.plan(items)
+            assert len(plan.rows) == (0 if k == 0 else S) and len(plan.groups) == min(k, 1)
+            out = torch.full((S, pool.out_channels, MAX_CHUNK * hop), float("nan"), device=dev)      # (an output with columns: step 0 crops too)
+            y, emit = pool.step_padded(items, pad, None, out)
+            f += n
+            cols = want[k].shape[2]
+            assert emit == [cols // hop] * S
+            for s in (0, 31, 32, 33):
+                assert torch.equal(y[s, :, :cols], want[k][s]) and bool((y[s, :, cols:] == 0.0).all()), (k, s)
+            assert torch.equal(y[:, :, :cols], want[k]) and bool((y[:, :, cols:] == 0.0).all()), k
+    assert not torch.equal(want[1][32], want[1][0]) and not torch.equal(want[1][33], want[1][1])      # every session has its own data
+    eng.close()
+
+
 @pytest.mark.parametrize("model", MODELS)
 def test_independent_sessions_equal_each_utterance_alone_and_the_oracle(model):
     mk, cin, oracle, tmpl = _model(model)

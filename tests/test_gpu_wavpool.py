@@ -172,6 +172,26 @@ def test_sessions_equal_each_utterance_alone(cfg, invariant):
         assert ref.shape == tuple(got[s].shape) and err <= TOL, (cfg, s, err)
 
 
+def test_thirty_four_sessions_pass_one_launchs_table_entries():
+    """34 sessions, more than the 32 entries one launch carries: a step in which every session pushes less than a hop (34 carry entries, no
+    frame), a step in which all 34 push the rest and emit (34 rows), a flush of all.  Sessions 0, 31, 32 and 33 — either side of the edge
+    between the first and the second launch — are the whole-row forward of their utterance bit for bit; so are the others."""
+    cfg = CONFIGS[0]
+    m = _module(cfg, True)
+    S, hop = 34, cfg[1]
+    rng = np.random.default_rng(34)
+    waves = [(0.2 * rng.normal(size=300 + 11 * s)).astype(np.float32) for s in range(S)]
+    first = [1 + s % (hop - 1) for s in range(S)]
+    steps = [[(s, first[s], False) for s in range(S)], [(s, len(waves[s]) - first[s], False) for s in range(S)],
+             [(s, 0, True) for s in range(S)]]
+    with m.wav_pool(S, MAX_CHUNK) as pool:
+        assert pool.counters.plan(steps[0]) == [0] * S
+        got = _serve(pool, waves, steps)
+        assert pool.emitted_frames(33) == m.frames(len(waves[33])) > m.frames_ready(len(waves[33])) > 0      # steps 1 and 2 both emit
+    for s in [0, 31, 32, 33] + list(range(1, 31)):
+        assert torch.equal(got[s], _whole(cfg, True, waves[s])), s
+
+
 @pytest.mark.parametrize("cfg", CONFIGS)
 def test_lockstep_sessions_equal_a_batched_stream(cfg):
     m = _module(cfg)

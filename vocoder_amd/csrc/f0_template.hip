@@ -27,15 +27,13 @@ namespace {
 
 constexpr int kF0MaxFrame = 4096;       // W: the staged frame, d, its scan and the chunk totals stay under 64 KiB of LDS
 constexpr int64_t kF0MaxLen = 1LL << 30;
-constexpr int kF0Rows = 32;             // per-row lengths travel by value, kF0Rows rows per launch (as LogmelRowBlock's do)
+constexpr int kF0Rows = 32;             // rows per launch: their lengths are a LaunchTable (fv_internal.h)
 constexpr int kYinLags = 4;             // consecutive lags per lane: one 16-byte LDS read feeds sixteen subtract-and-FMAs
 constexpr int kYinMaxThreads = 512;
 constexpr int kTmplItems = 8;           // consecutive samples per thread
 constexpr int kTmplChunk = 256 * kTmplItems;
 
-struct F0RowBlock {
-    int len[kF0Rows];
-};
+using F0RowBlock = LaunchTable<int, kF0Rows>;
 
 struct YinPlan {
     int sr = 0, W = 0, hop = 0, tau_min = 0, tau_max = 0, Wi = 0;
@@ -108,7 +106,7 @@ __device__ __forceinline__ float wave_scan_add(float v, int lane) {   // inclusi
 
 // grid (frames, rows); block pl.threads().  LDS: xs[W + 8] (the frame, then zeros) | dl[d_elems] (d, then d') | cs[d_elems] (the prefix inside
 // a 64-lag chunk) | ct[d_elems / 64] (chunk totals) | red[32].  Workgroup x computes frame t0 + x into column x.  x[b] holds the samples
-// [origin, origin + rows.len) of row b (the whole row: origin 0, t0 0, len the row's length; a stream: its carried samples and the chunk), the
+// [origin, origin + rows.e[row]) of row b (the whole row: origin 0, t0 0, len the row's length; a stream: its carried samples and the chunk), the
 // frame's global indices map to index - origin.  Samples before 0 or at or past limit = origin + len are zeros by index: the address is clamped
 // and the value selected, so no sample outside [origin, limit) is loaded.
 __global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __restrict__ x, long long x_stride, F0RowBlock rows, int row0,
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __r
     extern __shared__ __align__(16) float lds[];
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
     const int col = blockIdx.x, b = row0 + blockIdx.y;
-    const long long t = t0 + col, limit = origin + rows.len[blockIdx.y], first = origin > 0 ? origin : 0;
+    const long long t = t0 + col, limit = origin + rows.e[blockIdx.y], first = origin > 0 ? origin : 0;
     float* f0r = f0 + (long long)b * out_stride;
     float* apr = ap + (long long)b * out_stride;
     if (t >= limit / pl.hop) {   // (the whole workgroup leaves: no barrier below is reached by a part of it)
@@ -237,7 +235,7 @@ __global__ __launch_bounds__(256) void f0_increment_kernel(const float* __restri
     if (t >= T) return;
     const int b = row0 + blockIdx.y;
     uint32_t v = 0u;
-    if (t < rows.len[blockIdx.y]) {
+    if (t < rows.e[blockIdx.y]) {
         const float f = f0[(long long)b * f0_stride + t];
         if (f > 0.f && f < (float)sr) v = (uint32_t)__double2ll_rn((double)f / (double)sr * 4294967296.0);
     }
@@ -322,7 +320,7 @@ __device__ __forceinline__ void tmpl_chunk_emit(const uint32_t* __restrict__ Fr,
 // grid (chunks, rows): sums[b][chunk] = the sum of the chunk's increments, wrapping
 __global__ __launch_bounds__(256) void f0_template_sums_kernel(const uint32_t* __restrict__ F, F0RowBlock rows, int row0,
                                                                uint32_t* __restrict__ sums, int T, int hop, int nchunk) {
-    const int b = row0 + blockIdx.y, Ti = rows.len[blockIdx.y];
+    const int b = row0 + blockIdx.y, Ti = rows.e[blockIdx.y];
     const uint32_t s = tmpl_chunk_sum(F + (long long)b * T, 0, Ti - 1, hop, blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, Ti * hop);
     if (threadIdx.x == 0) sums[(long long)b * nchunk + blockIdx.x] = s;
 }
@@ -331,7 +329,7 @@ __global__ __launch_bounds__(256) void f0_template_sums_kernel(const uint32_t* _
 __global__ __launch_bounds__(256) void f0_template_kernel(const uint32_t* __restrict__ F, const uint32_t* __restrict__ sums, F0RowBlock rows,
                                                           int row0, float* __restrict__ out, long long out_stride, int T, int hop, int nchunk,
                                                           int kind, float amplitude) {
-    const int b = row0 + blockIdx.y, Ti = rows.len[blockIdx.y];
+    const int b = row0 + blockIdx.y, Ti = rows.e[blockIdx.y];
     uint32_t carry = 0u;
     for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) carry += sums[(long long)b * nchunk + c];
     tmpl_chunk_emit(F + (long long)b * T, 0, Ti - 1, hop, blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, Ti * hop, T * hop, carry,
@@ -360,16 +358,13 @@ __global__ __launch_bounds__(256) void osc_stream_kernel(const uint32_t* __restr
                     out + (long long)b * out_stride, n_lo, kind, amplitude, (int)blockIdx.x == nchunk - 1 ? phase_out + b : nullptr);
 }
 
-// the lengths of the rows [row0, row0 + count) by value; host == NULL: every row has `whole`
-fv_status row_block(const char* fn, const char* what, const int32_t* host, int row0, int count, int whole, F0RowBlock& rb) {
-    for (int i = 0; i < kF0Rows; ++i) {
-        const int v = i < count ? (host ? host[row0 + i] : whole) : 0;
-        if (v < 0 || v > whole) {
-            set_error("%s: row %d has %s = %d, outside [0, %d]", fn, row0 + i, what, v, whole);
+// the rows' lengths, checked before anything is enqueued; host == NULL: every row has `whole`
+fv_status check_rows(const char* fn, const char* what, const int32_t* host, int batch, int whole) {
+    for (int b = 0; host && b < batch; ++b)
+        if (host[b] < 0 || host[b] > whole) {
+            set_error("%s: row %d has %s = %d, outside [0, %d]", fn, b, what, host[b], whole);
             return FV_ERR_INVALID;
         }
-        rb.len[i] = v;
-    }
     return FV_OK;
 }
 
@@ -480,20 +475,16 @@ FV_API fv_status fv_f0_forward(fv_f0* p, const float* d_x, int64_t x_row_stride,
                   (long long)out_row_stride, (long long)L, (long long)T);
         return FV_ERR_INVALID;
     }
-    std::vector<F0RowBlock> blocks((batch + kF0Rows - 1) / kF0Rows);   // everything is validated before anything is enqueued
-    for (size_t i = 0; i < blocks.size(); ++i)
-        if (const fv_status st = row_block(fn, "length", host_lengths, (int)i * kF0Rows, std::min(kF0Rows, batch - (int)i * kF0Rows), (int)L,
-                                           blocks[i]))
-            return st;
+    if (const fv_status st = check_rows(fn, "length", host_lengths, batch, (int)L)) return st;
     hipStream_t s = (hipStream_t)stream;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-        const int row0 = (int)i * kF0Rows, count = std::min(kF0Rows, batch - row0);
-        hipLaunchKernelGGL(yin_f0_kernel, dim3((unsigned)T, count), dim3(pl.threads()), pl.lds_bytes(), s, d_x, (long long)x_row_stride,
-                           blocks[i], row0, d_f0, d_aperiodicity, (long long)out_row_stride, 0LL, 0LL, pl);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    set_last_kernel("yin_f0_kernel");
-    return FV_OK;
+    const fv_status st = for_each_launch_table<F0RowBlock>(batch, [&](int b) { return host_lengths ? host_lengths[b] : (int)L; },
+                                                           [&](const F0RowBlock& rows, int row0, int count) {
+        hipLaunchKernelGGL(yin_f0_kernel, dim3((unsigned)T, count), dim3(pl.threads()), pl.lds_bytes(), s, d_x, (long long)x_row_stride, rows,
+                           row0, d_f0, d_aperiodicity, (long long)out_row_stride, 0LL, 0LL, pl);
+        return FV_OK;
+    });
+    if (st == FV_OK) set_last_kernel("yin_f0_kernel");
+    return st;
 }
 
 FV_API fv_status fv_template_create(const fv_template_config* cfg, fv_template** out) {
@@ -543,30 +534,26 @@ FV_API fv_status fv_template_forward(fv_template* p, const float* d_f0, int64_t 
         set_error("%s: workspace too small (%zu < %zu bytes, fv_template_workspace_bytes)", fn, d_workspace ? workspace_bytes : (size_t)0, need);
         return FV_ERR_INVALID;
     }
-    std::vector<F0RowBlock> blocks((batch + kF0Rows - 1) / kF0Rows);
-    for (size_t i = 0; i < blocks.size(); ++i)
-        if (const fv_status st = row_block(fn, "frames", host_frames, (int)i * kF0Rows, std::min(kF0Rows, batch - (int)i * kF0Rows), (int)T,
-                                           blocks[i]))
-            return st;
+    if (const fv_status st = check_rows(fn, "frames", host_frames, batch, (int)T)) return st;
     size_t f_words = 0;
     (void)template_words(batch, T, hop, &f_words);
     uint32_t* F = (uint32_t*)d_workspace;
     uint32_t* sums = F + f_words;
     const int nchunk = (int)((T * hop + kTmplChunk - 1) / kTmplChunk);
     hipStream_t s = (hipStream_t)stream;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-        const int row0 = (int)i * kF0Rows, count = std::min(kF0Rows, batch - row0);
-        hipLaunchKernelGGL(f0_increment_kernel, dim3((unsigned)((T + 255) / 256), count), dim3(256), 0, s, d_f0, (long long)f0_row_stride,
-                           blocks[i], row0, F, (int)T, p->cfg.sample_rate);
+    const fv_status st = for_each_launch_table<F0RowBlock>(batch, [&](int b) { return host_frames ? host_frames[b] : (int)T; },
+                                                           [&](const F0RowBlock& rows, int row0, int count) -> fv_status {
+        hipLaunchKernelGGL(f0_increment_kernel, dim3((unsigned)((T + 255) / 256), count), dim3(256), 0, s, d_f0, (long long)f0_row_stride, rows,
+                           row0, F, (int)T, p->cfg.sample_rate);
         FV_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(f0_template_sums_kernel, dim3(nchunk, count), dim3(256), 0, s, F, blocks[i], row0, sums, (int)T, hop, nchunk);
+        hipLaunchKernelGGL(f0_template_sums_kernel, dim3(nchunk, count), dim3(256), 0, s, F, rows, row0, sums, (int)T, hop, nchunk);
         FV_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(f0_template_kernel, dim3(nchunk, count), dim3(256), 0, s, F, sums, blocks[i], row0, d_out,
-                           (long long)out_row_stride, (int)T, hop, nchunk, p->cfg.kind, p->cfg.amplitude);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    set_last_kernel("f0_template_kernel");
-    return FV_OK;
+        hipLaunchKernelGGL(f0_template_kernel, dim3(nchunk, count), dim3(256), 0, s, F, sums, rows, row0, d_out, (long long)out_row_stride,
+                           (int)T, hop, nchunk, p->cfg.kind, p->cfg.amplitude);
+        return FV_OK;
+    });
+    if (st == FV_OK) set_last_kernel("f0_template_kernel");
+    return st;
 }
 
 }  // extern "C"
@@ -631,14 +618,13 @@ static fv_status yin_stream_step(fv_yin_stream* st, const float* d_wave, int64_t
         st->prev_c = c;
     }
     if (k > 0) {
-        F0RowBlock rb;
-        for (int row0 = 0; row0 < st->B; row0 += kF0Rows) {
-            const int count = std::min(kF0Rows, st->B - row0);
-            for (int i = 0; i < kF0Rows; ++i) rb.len[i] = i < count ? (int)(N2 - origin) : 0;
-            hipLaunchKernelGGL(yin_f0_kernel, dim3((unsigned)k, count), dim3(pl.threads()), pl.lds_bytes(), s, x, st->stride, rb, row0, d_f0, d_ap,
-                               (long long)out_row_stride, origin, st->E, pl);
-            FV_HIP_CHECK(hipGetLastError());
-        }
+        const fv_status rs = for_each_launch_table<F0RowBlock>(st->B, [&](int) { return (int)(N2 - origin); },
+                                                               [&](const F0RowBlock& rows, int row0, int count) {
+            hipLaunchKernelGGL(yin_f0_kernel, dim3((unsigned)k, count), dim3(pl.threads()), pl.lds_bytes(), s, x, st->stride, rows, row0, d_f0,
+                               d_ap, (long long)out_row_stride, origin, st->E, pl);
+            return FV_OK;
+        });
+        if (rs) return rs;
         set_last_kernel("yin_f0_kernel");
     }
     *frames_out = k;
@@ -679,14 +665,13 @@ static fv_status osc_stream_step(fv_osc_stream* st, const float* d_f0, int64_t r
         st->prev_c = c;
     }
     if (k > 0) {
-        F0RowBlock rb;
-        for (int row0 = 0; row0 < st->B; row0 += kF0Rows) {
-            const int count = std::min(kF0Rows, st->B - row0);
-            for (int i = 0; i < kF0Rows; ++i) rb.len[i] = i < count ? fcount : 0;
-            hipLaunchKernelGGL(f0_increment_kernel, dim3((unsigned)((fcount + 255) / 256), count), dim3(256), 0, s, x, st->stride, rb, row0, st->F,
-                               fcount, cfg.sample_rate);
-            FV_HIP_CHECK(hipGetLastError());
-        }
+        const fv_status rs = for_each_launch_table<F0RowBlock>(st->B, [&](int) { return fcount; },
+                                                               [&](const F0RowBlock& rows, int row0, int count) {
+            hipLaunchKernelGGL(f0_increment_kernel, dim3((unsigned)((fcount + 255) / 256), count), dim3(256), 0, s, x, st->stride, rows, row0,
+                               st->F, fcount, cfg.sample_rate);
+            return FV_OK;
+        });
+        if (rs) return rs;
         const int n_lo = (int)((st->E - o) * hop), n_hi = (int)((E2 - o) * hop);
         const int nchunk = (n_hi - n_lo + kTmplChunk - 1) / kTmplChunk;
         const int lo_c = o < 0 ? (int)-o : 0, hi_c = (int)(T2 - 1 - o);

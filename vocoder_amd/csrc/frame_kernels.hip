@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void logmel_window_kernel(const float* __restr
                                                             long long chunk_stride, long long carry_origin, long long chunk_origin,
                                                             long long avail, long long f0, int hop, int TP, int pad_l, int pad_r, int b0) {
     const int b = b0 + blockIdx.z;
-    const long long end = rows.len[blockIdx.z];
+    const long long end = rows.e[blockIdx.z];
     const long long lpad = end >= 0 ? end + pad_l + pad_r : 0;    // the padded row's extent (known end only)
     const SamplePieces p{carry + (long long)b * carry_stride, chunk + (long long)b * chunk_stride, carry_origin, chunk_origin,
                          end >= 0 ? end : avail};
@@ -121,15 +121,12 @@ fv_status launch_logmel_window(const float* carry, long long carry_stride, long 
         set_error("logmel_window: internal: a piece that holds samples is NULL (%s)", chunk ? "carry" : "chunk");
         return FV_ERR_INVALID;
     }
-    for (int b0 = 0; b0 < B; b0 += kLogmelRows) {
-        const int nz = std::min(kLogmelRows, B - b0);
-        LogmelRowBlock blk{};
-        for (int i = 0; i < nz; ++i) blk.len[i] = row_len ? row_len[b0 + i] : -1;
+    return for_each_launch_table<LogmelRowBlock>(B, [&](int b) { return row_len ? row_len[b] : -1LL; },
+                                                 [&](const LogmelRowBlock& blk, int b0, int nz) {
         hipLaunchKernelGGL(logmel_window_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, nz), dim3(256), 0, s, carry, chunk, yp, blk,
                            carry_stride, chunk_stride, carry_origin, chunk_origin, avail, f0, hop, TP, pad_l, pad_r, b0);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    return FV_OK;
+        return FV_OK;
+    });
 }
 
 // The same for sessions that advance independently (fv_wavpool_step; spectrogram.py:25-56 per session): tensor row k0 + blockIdx.z is one table
@@ -163,15 +160,11 @@ fv_status launch_logmel_pool_window(const float* buf0, const float* buf1, long l
             return FV_ERR_INVALID;
         }
     }
-    for (int k0 = 0; k0 < rows; k0 += kSamplePoolBlock) {
-        const int nz = std::min(kSamplePoolBlock, rows - k0);
-        SamplePoolBlock blk{};
-        for (int i = 0; i < nz; ++i) blk.e[i] = tab[k0 + i];
+    return for_each_launch_table<SamplePoolBlock>(rows, tab, [&](const SamplePoolBlock& blk, int k0, int nz) {
         hipLaunchKernelGGL(logmel_pool_window_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, nz), dim3(256), 0, s, buf0, buf1, chunk, yp, blk, H,
                            chunk_stride, hop, TP, taps, pad_l, pad_r, k0);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    return FV_OK;
+        return FV_OK;
+    });
 }
 
 // The pitch shift's centred frames (pitch_shift.hip), zero edges: yp[b][r][tp] = wave[b][tp hop + r - pad] inside [0, L), else 0
@@ -319,27 +312,21 @@ fv_status launch_pv_frame_carry(const float* frames, const float* cfr, float* nf
     return FV_OK;
 }
 
-// y[b][c][T_b ...) = 0.0f up to the row's end; T_b travels by value (rows.len), `span` = columns of the longest tail
+// y[b][c][T_b ...) = 0.0f up to the row's end; T_b travels by value (rows.e), `span` = columns of the longest tail
 __global__ __launch_bounds__(256) void zero_columns_kernel(float* __restrict__ y, const LogmelRowBlock rows, int C, long long T, int b0) {
-    const long long j = rows.len[blockIdx.z] + (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long j = rows.e[blockIdx.z] + (long long)blockIdx.x * 256 + threadIdx.x;
     if (j >= T) return;
     y[((long long)(b0 + blockIdx.z) * C + blockIdx.y) * T + j] = 0.0f;
 }
 
 fv_status launch_zero_columns(float* y, const long long* row_cols, int B, int C, long long T, hipStream_t s) {
-    for (int b0 = 0; b0 < B; b0 += kLogmelRows) {
-        const int nz = std::min(kLogmelRows, B - b0);
-        LogmelRowBlock blk{};
+    return for_each_launch_table<LogmelRowBlock>(B, [&](int b) { return std::min(std::max(row_cols[b], 0LL), T); },
+                                                 [&](const LogmelRowBlock& blk, int b0, int nz) {
         long long span = 0;
-        for (int i = 0; i < nz; ++i) {
-            blk.len[i] = std::min(std::max(row_cols[b0 + i], 0LL), T);
-            span = std::max(span, T - blk.len[i]);
-        }
-        if (span <= 0) continue;
-        hipLaunchKernelGGL(zero_columns_kernel, dim3((unsigned)((span + 255) / 256), C, nz), dim3(256), 0, s, y, blk, C, T, b0);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    return FV_OK;
+        for (int i = 0; i < nz; ++i) span = std::max(span, T - blk.e[i]);
+        if (span > 0) hipLaunchKernelGGL(zero_columns_kernel, dim3((unsigned)((span + 255) / 256), C, nz), dim3(256), 0, s, y, blk, C, T, b0);
+        return FV_OK;
+    });
 }
 
 }  // namespace fv

@@ -108,6 +108,34 @@ void prof_end(hipStream_t s, int idx, const char* label, double flops, double by
         }                                                                                        \
     } while (0)
 
+// Per-row values that change with every call (a step's session tables, the lengths of a ragged batch) travel BY VALUE in the kernel
+// arguments, N entries per launch: no device table, and no async copy that could read a host buffer after the next call has rewritten it.
+// The kernel indexes `e` with the block index that runs over the launch's rows.  HIP's kernel-argument segment is 4 KiB; a table may take
+// half of it, which leaves 2 KiB for the pointers and scalars beside it (the largest table holds 1792 bytes, the fullest kernel 1336).
+template <class T, int N>
+struct LaunchTable {
+    static_assert(sizeof(T) * N <= 2048, "a by-value table takes at most half of the 4 KiB kernel-argument segment");
+    static constexpr int size = N;
+    T e[N];
+};
+// The one blocking loop over such tables: entries [first, first + nz) of `src` — a pointer to the entries, or a callable int -> entry — go
+// into a zeroed Table, launch(table, first, nz) -> fv_status enqueues that block's kernels (per-block reductions and the launches they
+// skip are its business), and the launch error is checked here.  Stops at the first status that is not FV_OK; count <= 0 launches nothing.
+template <class Table, class Src, class Launch>
+fv_status for_each_launch_table(int count, const Src& src, Launch&& launch) {
+    for (int first = 0; first < count; first += Table::size) {
+        const int nz = count - first < Table::size ? count - first : Table::size;
+        Table blk{};
+        for (int i = 0; i < nz; ++i) {
+            if constexpr (std::is_pointer_v<Src>) blk.e[i] = src[first + i];
+            else blk.e[i] = src(first + i);
+        }
+        if (const fv_status st = launch(blk, first, nz)) return st;
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+
 // Opt a kernel in to more than 64 KiB of dynamic LDS (gfx950: 160 KiB per CU).  The attribute is PER DEVICE, so the
 // "already done" state is a bit per device ordinal (one mask per call site), set with an atomic OR: a process that drives
 // several GPUs, or several host threads, gets every (kernel, device) pair opted in exactly once.  Returns false and sets
@@ -397,9 +425,8 @@ fv_status launch_ragged_gather(const float* x, float* win, const fv_ragged_windo
 fv_status launch_ragged_scatter(const float* win, float* y, const fv_ragged_window* tab, int first, int count, int C, long long T,
                                 long long L, int hop, hipStream_t s);
 fv_status launch_ragged_zero_tail(float* y, const int* lens, int B, int C, long long T, long long span, int hop, hipStream_t s);
-// session pool (fv_pool_step): the step's tables change every call, so they travel BY VALUE in the kernel arguments, kPoolBlock entries per
-// launch — no device table, no copy that could read a host buffer after the next step has rewritten it.  Entries count in frames; the
-// launchers take `hop` (1 for the mel, the generator's hop for the pitch template and the waveform) and scale to columns.
+// session pool (fv_pool_step): the step's tables are LaunchTables of kPoolBlock entries.  Entries count in frames; the launchers take `hop`
+// (1 for the mel, the generator's hop for the pitch template and the waveform) and scale to columns.
 static constexpr int kPoolBlock = 32;
 struct PoolGatherEntry {
     int item, slot;       // row of the chunk buffer, row of the ring
@@ -411,12 +438,8 @@ struct PoolCropEntry {
     int item, row;        // row of the caller's output; row of the group's output, -1: the item emits nothing (a row of zeros)
     long long src, len;   // out[item][c][j] = j < len ? y[row][c][src + j] : 0
 };
-struct PoolGatherBlock {
-    PoolGatherEntry e[kPoolBlock];
-};
-struct PoolCropBlock {
-    PoolCropEntry e[kPoolBlock];
-};
+using PoolGatherBlock = LaunchTable<PoolGatherEntry, kPoolBlock>;
+using PoolCropBlock = LaunchTable<PoolCropEntry, kPoolBlock>;
 // chunk (., C, in_frames) -> ring (., C, cap) at F mod cap, and ring + chunk -> win (rows, C, Wg), zero outside [col0, col0 + W)
 fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const PoolGatherEntry* tab, int count, int C, long long cap,
                              long long in_frames, long long Wg, int hop, hipStream_t s);
@@ -428,12 +451,10 @@ fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab,
 // of row stride `stride`
 fv_status launch_sample_carry(const float* prev, float* next, const float* chunk, long long stride, long long chunk_stride, int B, long long N,
                               long long next_origin, long long prev_origin, long long count, hipStream_t s);
-// log-mel front-end on ragged rows and stream chunks (frame_kernels.hip; fv_logmel_ragged_forward, fv_logmel_stream_*): per-row values travel
-// BY VALUE, kLogmelRows rows per launch, as the session pool's tables do
+// log-mel front-end on ragged rows and stream chunks (frame_kernels.hip; fv_logmel_ragged_forward, fv_logmel_stream_*): a LaunchTable of the
+// rows' lengths or column counts, kLogmelRows rows per launch
 static constexpr int kLogmelRows = 32;
-struct LogmelRowBlock {
-    long long len[kLogmelRows];
-};
+using LogmelRowBlock = LaunchTable<long long, kLogmelRows>;
 // yp[b][r][tp] = sample (f0 + tp) hop + r - pad_l of row b, reflected at 0 and — where row_len[b] >= 0 (row_len NULL: no row's end is known) — at
 // the row's end, 0 past the padded row / from `avail` on; the sample is read from `chunk` (samples [chunk_origin, ...)) or from `carry`
 // (samples [carry_origin, chunk_origin)); either may be NULL only when it holds no sample of any row (refused otherwise)
@@ -441,7 +462,7 @@ fv_status launch_logmel_window(const float* carry, long long carry_stride, long 
                                long long chunk_origin, const long long* row_len, long long avail, float* yp, int B, long long f0, int hop,
                                int TP, int pad_l, int pad_r, hipStream_t s);
 // Per-session sample pools (sample_pool.h; fv_wavpool_step): every slot advances on its own, so origins, ends and the slot's carry buffer are
-// per table entry; the tables travel BY VALUE, kSamplePoolBlock entries per launch, as the session pool's do.
+// per table entry of a LaunchTable, kSamplePoolBlock entries per launch.
 static constexpr int kSamplePoolBlock = 32;
 struct SamplePoolEntry {
     int item, slot;            // row of the chunk buffer; the slot's row in both carry buffers
@@ -453,9 +474,7 @@ struct SamplePoolEntry {
     long long avail;           // N2 = N + the item's samples
     long long first;           // E: the first output (frame) of this row
 };
-struct SamplePoolBlock {
-    SamplePoolEntry e[kSamplePoolBlock];
-};
+using SamplePoolBlock = LaunchTable<SamplePoolEntry, kSamplePoolBlock>;
 // yp[k][r][tp] = sample (first_k + tp) hop + r - pad_l of entry k's session for the tp < count_k + taps - 1 slots its frames read, 0.0f in the
 // other slots (nothing is loaded for them); reflected and cut off as launch_logmel_window does, per entry.  buf0 / buf1: the pool's two
 // (S, H) carry buffers; chunk (., chunk_stride) may be NULL when no entry's chunk holds a sample.

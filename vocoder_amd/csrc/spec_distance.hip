@@ -26,20 +26,18 @@ namespace fv {
 constexpr int kSdTile = 64;                          // columns per tile (fv_spec_distance_tile): one wave's lanes
 constexpr int kSdThreads = 256;
 constexpr int kSdWaves = kSdThreads / 64;            // channels per step
-constexpr int kSdRows = 64;                          // rows per launch: their frame counts travel BY VALUE, as LogmelRowBlock's lengths do
+constexpr int kSdRows = 64;                          // rows per launch: their frame counts are a LaunchTable (fv_internal.h)
 static_assert(kSdTile == 64, "a lane is a column");
 static_assert(kSdRows * 4 == kSdThreads, "the finish kernel gives a row four threads, one per sum");
 
-struct SdRowBlock {
-    int frames[kSdRows];
-};
+using SdRowBlock = LaunchTable<int, kSdRows>;
 
 template <bool LOG>
 __global__ __launch_bounds__(kSdThreads) void spec_distance_tile_kernel(const float* __restrict__ est, const float* __restrict__ ref,
                                                                         double* __restrict__ partial, const SdRowBlock rows,
                                                                         long long row_stride, long long ld, int C, long long tiles, int b0) {
     __shared__ double red[kSdWaves][4];
-    const int frames = rows.frames[blockIdx.y];
+    const int frames = rows.e[blockIdx.y];
     const long long col0 = (long long)blockIdx.x * kSdTile;
     if (col0 >= frames) return;                                  // (the whole workgroup: nothing of this tile is loaded or written)
     const long long b = b0 + (long long)blockIdx.y;
@@ -86,7 +84,7 @@ __global__ __launch_bounds__(kSdThreads) void spec_distance_finish_kernel(const 
     const int i = threadIdx.x >> 2, k = threadIdx.x & 3;
     if (i >= nrows) return;
     const long long b = b0 + (long long)i;
-    const int nt = (rows.frames[i] + kSdTile - 1) / kSdTile;
+    const int nt = (rows.e[i] + kSdTile - 1) / kSdTile;
     const double* p = partial + b * tiles * 4 + k;
     double s = 0.0;
     for (int t = 0; t < nt; ++t) s += p[(long long)t * 4];
@@ -154,23 +152,16 @@ FV_API fv_status fv_spec_distance(const float* d_est, const float* d_ref, int64_
     auto tile_kernel = (flags & FV_SPEC_DISTANCE_LOG) ? spec_distance_tile_kernel<true> : spec_distance_tile_kernel<false>;
     const long long tiles = sd_tiles(T);
     double* partial = static_cast<double*>(d_workspace);
-    for (int b0 = 0; b0 < batch; b0 += kSdRows) {
-        const int nz = std::min(kSdRows, batch - b0);
-        SdRowBlock blk{};
-        int longest = 0;
-        for (int i = 0; i < nz; ++i) {
-            blk.frames[i] = host_frames[b0 + i];
-            longest = std::max(longest, blk.frames[i]);
-        }
+    return for_each_launch_table<SdRowBlock>(batch, host_frames, [&](const SdRowBlock& blk, int b0, int nz) -> fv_status {
+        const int longest = *std::max_element(blk.e, blk.e + nz);
         if (longest > 0) {
             hipLaunchKernelGGL(tile_kernel, dim3((unsigned)sd_tiles(longest), nz), dim3(kSdThreads), 0, s, d_est, d_ref, partial, blk,
                                (long long)row_stride, (long long)ld, (int)channels, tiles, b0);
             FV_HIP_CHECK(hipGetLastError());
         }
         hipLaunchKernelGGL(spec_distance_finish_kernel, dim3(1), dim3(kSdThreads), 0, s, partial, d_out, blk, tiles, b0, nz);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    return FV_OK;
+        return FV_OK;
+    });
 }
 
 }  // extern "C"

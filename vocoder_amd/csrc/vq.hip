@@ -29,7 +29,7 @@ namespace {
 typedef float vq_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kVqMaxDim = 4096, kVqMaxCodes = 65536, kVqMaxLayers = 32;
-constexpr int kVqRows = 256;                 // batch rows whose lengths travel by value with one launch
+constexpr int kVqRows = 256;                 // rows per launch: their lengths are a LaunchTable (fv_internal.h)
 constexpr int kVqMT = 2;                     // 32-code tiles per wave and pass
 constexpr int kVqGroup = 4;                  // chunks of 8 channels a wave requests at once (vq_search_kernel)
 constexpr int kVqUnit = 4 * kVqMT;           // code tiles one pass of a workgroup's four waves covers: the slicing granule
@@ -37,9 +37,7 @@ constexpr int kVqSelFrames = 32, kVqSelD = 64;
 constexpr int kNoCode = 0x7fffffff;          // "no score won yet": every NaN-free score beats it, a frame left with it takes code 0
 constexpr long long kVqMaxFrames = 1LL << 30;
 
-struct VqRowBlock {
-    int len[kVqRows];
-};
+using VqRowBlock = LaunchTable<int, kVqRows>;
 
 // Where the frames of a launch live: element (b, d, t) at b * bstride + d * dstride + t; rows [row0, row0 + rows) of the batch
 struct VqFrames {
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(256) void vq_search_kernel(const float* __restrict_
         off[j] = 0;
         if (n < count) {
             const int bl = (int)(n / fr.T), t = (int)(n - (long long)bl * fr.T);
-            const int len = fr.uniform >= 0 ? fr.uniform : rows.len[bl];
+            const int len = fr.uniform >= 0 ? fr.uniform : rows.e[bl];
             ok[j] = t < len;                                           // frames at or past the row's length are never loaded
             off[j] = (long long)(fr.row0 + bl) * fr.bstride + t + (long long)half * fr.dstride;
         }
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(256) void vq_select_kernel(const float* in, VqFrame
         int code = -2;                                                  // -2: no such frame; -1: past the row's length
         if (n < count) {
             const int bl = (int)(n / fr.T), t = (int)(n - (long long)bl * fr.T);
-            const int len = fr.uniform >= 0 ? fr.uniform : rows.len[bl];
+            const int len = fr.uniform >= 0 ? fr.uniform : rows.e[bl];
             if (t < len) {
                 float bs = -INFINITY;
                 int bi = kNoCode;
@@ -265,7 +263,7 @@ __global__ __launch_bounds__(256) void vq_gather_kernel(const int* __restrict__ 
     auto frame_ok = [&](long long n) {
         if (n >= count) return false;
         const int bl = (int)(n / T), t = (int)(n - (long long)bl * T);
-        return t < (uniform >= 0 ? uniform : rows.len[bl]);
+        return t < (uniform >= 0 ? uniform : rows.e[bl]);
     };
     const long long n = nloc0 + f;
     const bool exists = n < count;
@@ -375,16 +373,24 @@ fv_status vq_check_shape(const char* fn, const fv_vq* p, int32_t batch, int64_t 
     return FV_OK;
 }
 
-fv_status vq_row_blocks(const char* fn, const int32_t* host_frames, int batch, int T, std::vector<VqRowBlock>& blocks) {
-    if (!host_frames) return FV_OK;
-    blocks.resize((batch + kVqRows - 1) / kVqRows);
-    for (int b = 0; b < batch; ++b) {
+fv_status vq_check_frames(const char* fn, const int32_t* host_frames, int batch, int T) {
+    for (int b = 0; host_frames && b < batch; ++b)
         if (host_frames[b] < 0 || host_frames[b] > T) {
             set_error("%s: host_frames[%d] = %d lies outside [0, T = %d]", fn, b, host_frames[b], T);
             return FV_ERR_INVALID;
         }
-        blocks[b / kVqRows].len[b % kVqRows] = host_frames[b];
-    }
+    return FV_OK;
+}
+
+// launch(rows, row0, nrows, uniform) over the batch: kVqRows rows per call with their lengths, or — host_frames == NULL, every row holds T
+// frames — one call over all rows with uniform = T and a zeroed table that is never read
+template <class Launch>
+fv_status vq_for_rows(const int32_t* host_frames, int batch, int T, Launch&& launch) {
+    if (host_frames)
+        return for_each_launch_table<VqRowBlock>(batch, host_frames,
+                                                 [&](const VqRowBlock& rows, int row0, int nrows) { return launch(rows, row0, nrows, -1); });
+    if (const fv_status st = launch(VqRowBlock{}, 0, batch, T)) return st;
+    FV_HIP_CHECK(hipGetLastError());
     return FV_OK;
 }
 
@@ -503,8 +509,7 @@ FV_API fv_status fv_vq_encode(fv_vq* p, const float* d_x, int64_t x_row_stride, 
                   d_workspace ? workspace_bytes : (size_t)0, pl.total, batch, (long long)T);
         return FV_ERR_INVALID;
     }
-    std::vector<VqRowBlock> blocks;   // everything is validated before anything is enqueued
-    if (const fv_status st = vq_row_blocks(fn, host_frames, batch, (int)T, blocks)) return st;
+    if (const fv_status st = vq_check_frames(fn, host_frames, batch, (int)T)) return st;   // everything is validated before anything is enqueued
 
     const int D = p->cfg.dim, K = p->cfg.codebook_size, nq = p->cfg.num_quantizers;
     char* ws = (char*)d_workspace;
@@ -512,20 +517,17 @@ FV_API fv_status fv_vq_encode(fv_vq* p, const float* d_x, int64_t x_row_stride, 
     float* part_s = (float*)(ws + pl.r_bytes);
     int* part_i = (int*)(ws + pl.r_bytes + pl.part_bytes);
     hipStream_t s = (hipStream_t)stream;
-    static const VqRowBlock no_rows{};
-    const int nblocks = host_frames ? (int)blocks.size() : 1;
     for (int q = 0; q < nq; ++q) {
         const bool last = q == nq - 1;
-        for (int bi = 0; bi < nblocks; ++bi) {
+        const float* in = q == 0 ? d_x : r;
+        const fv_status st = vq_for_rows(host_frames, batch, (int)T, [&](const VqRowBlock& rb, int row0, int nrows, int uniform) -> fv_status {
             VqFrames fr;
             fr.T = (int)T;
-            fr.row0 = host_frames ? bi * kVqRows : 0;
-            fr.rows = host_frames ? std::min(kVqRows, batch - fr.row0) : batch;
-            fr.uniform = host_frames ? -1 : (int)T;
+            fr.row0 = row0;
+            fr.rows = nrows;
+            fr.uniform = uniform;
             fr.bstride = q == 0 ? (long long)D * x_row_stride : (long long)D * T;
             fr.dstride = q == 0 ? (long long)x_row_stride : (long long)T;
-            const float* in = q == 0 ? d_x : r;
-            const VqRowBlock& rb = host_frames ? blocks[bi] : no_rows;
             const long long count = (long long)fr.rows * T, n_first = (long long)fr.row0 * T;
             const dim3 grid((unsigned)((count + 32 * pl.nt - 1) / (32 * pl.nt)), (unsigned)pl.slices);
             const auto kernel = pl.nt == 2 ? vq_search_kernel<2> : vq_search_kernel<1>;
@@ -535,8 +537,9 @@ FV_API fv_status fv_vq_encode(fv_vq* p, const float* d_x, int64_t x_row_stride, 
             hipLaunchKernelGGL(vq_select_kernel, dim3((unsigned)((count + kVqSelFrames - 1) / kVqSelFrames), (unsigned)((D + kVqSelD - 1) / kVqSelD)), dim3(256), 0, s, in, fr, rb,
                                p->d_embed[q], D, K, pl.slices, part_s, part_i, n_first, pl.n_pad, d_codes + (size_t)q * pl.N, last ? nullptr : r, d_z,
                                q == 0 ? 1 : 0);
-            FV_HIP_CHECK(hipGetLastError());
-        }
+            return FV_OK;
+        });
+        if (st) return st;
     }
     set_last_kernel(pl.nt == 2 ? "vq_search_kernel<2>" : "vq_search_kernel<1>");
     return FV_OK;
@@ -551,22 +554,18 @@ FV_API fv_status fv_vq_decode(fv_vq* p, const int32_t* d_codes, const int32_t* h
         set_error("%s: null %s", fn, !d_codes ? "d_codes" : "d_z");
         return FV_ERR_INVALID;
     }
-    std::vector<VqRowBlock> blocks;
-    if (const fv_status st = vq_row_blocks(fn, host_frames, batch, (int)T, blocks)) return st;
+    if (const fv_status st = vq_check_frames(fn, host_frames, batch, (int)T)) return st;
     VqLayerPtrs lp{};
     for (int q = 0; q < p->cfg.num_quantizers; ++q) lp.embed[q] = p->d_embed[q];
-    static const VqRowBlock no_rows{};
-    const int nblocks = host_frames ? (int)blocks.size() : 1;
-    for (int bi = 0; bi < nblocks; ++bi) {
-        const int row0 = host_frames ? bi * kVqRows : 0, nrows = host_frames ? std::min(kVqRows, batch - row0) : batch;
+    const fv_status st = vq_for_rows(host_frames, batch, (int)T, [&](const VqRowBlock& rb, int row0, int nrows, int uniform) {
         const long long count = (long long)nrows * T;
         hipLaunchKernelGGL(vq_gather_kernel, dim3((unsigned)((count + kVqSelFrames - 1) / kVqSelFrames)), dim3(256), 0, (hipStream_t)stream, d_codes,
-                           lp, p->cfg.num_quantizers, p->cfg.dim, p->cfg.codebook_size, (int)T, row0, nrows, host_frames ? -1 : (int)T,
-                           host_frames ? blocks[bi] : no_rows, (long long)batch * T, d_z);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    set_last_kernel("vq_gather_kernel");
-    return FV_OK;
+                           lp, p->cfg.num_quantizers, p->cfg.dim, p->cfg.codebook_size, (int)T, row0, nrows, uniform, rb, (long long)batch * T,
+                           d_z);
+        return FV_OK;
+    });
+    if (st == FV_OK) set_last_kernel("vq_gather_kernel");
+    return st;
 }
 
 }  // extern "C"

@@ -231,20 +231,14 @@ __global__ __launch_bounds__(256) void pool_gather_kernel(const float* __restric
 }
 fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const PoolGatherEntry* tab, int count, int C, long long cap,
                              long long in_frames, long long Wg, int hop, hipStream_t s) {
-    for (int i0 = 0; i0 < count; i0 += kPoolBlock) {
-        const int nz = std::min(kPoolBlock, count - i0);
-        PoolGatherBlock blk{};
+    return for_each_launch_table<PoolGatherBlock>(count, tab, [&](const PoolGatherBlock& blk, int, int nz) {
         long long X = 0;   // columns this launch spans: the group's tensor for a row, the chunk for a ring-only entry
-        for (int i = 0; i < nz; ++i) {
-            blk.e[i] = tab[i0 + i];
-            X = std::max(X, tab[i0 + i].row >= 0 ? Wg * hop : (long long)tab[i0 + i].n * hop);
-        }
-        if (X <= 0) continue;
-        hipLaunchKernelGGL(pool_gather_kernel, dim3((unsigned)((X + 255) / 256), C, nz), dim3(256), 0, s, chunk, ring, win, blk, C, cap * hop,
-                           in_frames * hop, Wg * hop, hop);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    return FV_OK;
+        for (int i = 0; i < nz; ++i) X = std::max(X, blk.e[i].row >= 0 ? Wg * hop : (long long)blk.e[i].n * hop);
+        if (X > 0)
+            hipLaunchKernelGGL(pool_gather_kernel, dim3((unsigned)((X + 255) / 256), C, nz), dim3(256), 0, s, chunk, ring, win, blk, C, cap * hop,
+                               in_frames * hop, Wg * hop, hop);
+        return FV_OK;
+    });
 }
 __global__ __launch_bounds__(256) void pool_crop_kernel(const float* __restrict__ y, float* __restrict__ out, const PoolCropBlock tab, int C,
                                                         long long Ly, long long out_cols, int hop) {
@@ -259,15 +253,11 @@ __global__ __launch_bounds__(256) void pool_crop_kernel(const float* __restrict_
 fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames, int hop,
                            hipStream_t s) {
     if (out_frames <= 0) return FV_OK;
-    for (int i0 = 0; i0 < count; i0 += kPoolBlock) {
-        const int nz = std::min(kPoolBlock, count - i0);
-        PoolCropBlock blk{};
-        for (int i = 0; i < nz; ++i) blk.e[i] = tab[i0 + i];
+    return for_each_launch_table<PoolCropBlock>(count, tab, [&](const PoolCropBlock& blk, int, int nz) {
         hipLaunchKernelGGL(pool_crop_kernel, dim3((unsigned)((out_frames * hop + 255) / 256), C, nz), dim3(256), 0, s, y, out, blk, C, Ly * hop,
                            out_frames * hop, hop);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    return FV_OK;
+        return FV_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -330,14 +320,10 @@ fv_status launch_sample_pool_carry(float* buf0, float* buf1, long long H, const 
             return FV_ERR_INVALID;
         }
     }
-    for (int k0 = 0; k0 < count; k0 += kSamplePoolBlock) {
-        const int nz = std::min(kSamplePoolBlock, count - k0);
-        SamplePoolBlock blk{};
-        for (int i = 0; i < nz; ++i) blk.e[i] = tab[k0 + i];
+    return for_each_launch_table<SamplePoolBlock>(count, tab, [&](const SamplePoolBlock& blk, int, int nz) {
         hipLaunchKernelGGL(sample_pool_carry_kernel, dim3((unsigned)((H + 255) / 256), nz), dim3(256), 0, s, buf0, buf1, chunk, blk, H,
                            chunk_stride);
-        FV_HIP_CHECK(hipGetLastError());
-    }
-    return FV_OK;
+        return FV_OK;
+    });
 }
 }  // namespace fv
