@@ -1121,6 +1121,64 @@ FV_API fv_status fv_vq_encode(fv_vq* vq, const float* d_x, int64_t x_row_stride,
  * expected to have refused; frames at or past host_frames[b] are zeros. */
 FV_API fv_status fv_vq_decode(fv_vq* vq, const int32_t* d_codes, const int32_t* host_frames, float* d_z, int32_t batch, int64_t T, void* stream);
 
+/* -------- posterior encoder: the WaveNet encoder of VITS / RVC (modules/encoders/posterior_encoder.py) --------
+ * PosteriorEncoder in eval mode, the fourth encoder of the reference's modules/encoders package and one that VQVAEModel's generator.encoder
+ * slot can take (vae.py:81).  With C = hidden_channels, k = kernel_size, m[b][t] = t < lengths[b], d_i = dilation_rate ** (i % dilation_cycle):
+ *   h = pre(x) m;  out = 0
+ *   layer i:  a = in_i(h)  (C -> 2C, k taps, dilation d_i, zero padding (k - 1) d_i / 2);  g = tanh(a[:C]) sigmoid(a[C:]);  r = rs_i(g)
+ *             i < n_layers - 1 (rs_i: C -> 2C):  h = (h + r[:C]) m,  out = out + r[C:];   the last layer (rs_i: C -> C):  out = out + r
+ *   y = proj(out m) m;  vqvae: z = y;  vae: mean, logvar = y[:out], clamp(y[out:], -30, 20), z = mean m;  bnvae: mean = BatchNorm1d_eval(mean)
+ *   before z (the mean of a padded frame is BN(0), a per-channel constant; z is zero there).
+ * Exact fp32 on v_mfma_f32_32x32x2_f32; weight norm (weight_g, weight_v) and the BatchNorm are folded in fp64 at finalize and rounded once.
+ * `a` never reaches memory; the padding of x, and every frame at or past a row's length, is never loaded.  Every output element's sum is
+ * formed in an order fixed by the layer's shape alone (8-channel chunk, tap, channel pair), so a row has the same bits alone, in any batch
+ * and padded to any T.  Training-mode draws, dropout and f16x3 are not built: fp32 only.
+ * Limits: hidden_channels in [1, 1024]; in_channels, out_channels in [1, 4096]; kernel_size odd in [1, 11]; n_layers in [1, 64];
+ * dilation_rate >= 1, dilation_cycle >= 1 with (kernel_size - 1) * the largest dilation at most 896 frames (the staged window's LDS budget;
+ * above: FV_ERR_UNSUPPORTED); batch in [0, 65535], batch * T at most 2^30 frames, lengths in [0, T].
+ * Every entry validates all a host can see before it enqueues anything, and names the offending field. */
+typedef struct fv_posterior_config {
+    int32_t in_channels;     /* posterior_encoder.py:94 */
+    int32_t out_channels;    /* :95 — proj has 2 * out_channels rows in the vae modes (:124-126) */
+    int32_t hidden_channels; /* :96 */
+    int32_t kernel_size;     /* :97, reference default 5 */
+    int32_t dilation_rate;   /* :98, 1 */
+    int32_t dilation_cycle;  /* :99, 1 */
+    int32_t n_layers;        /* :100, 16 */
+    int32_t mode;            /* :101 — 0 = "vqvae", 1 = "vae", 2 = "bnvae" */
+} fv_posterior_config;
+
+typedef struct fv_posterior fv_posterior;
+
+/* posterior_encoder.py:92-131 (the constructor): validates on the host, no device work.  FV_ERR_INVALID / FV_ERR_UNSUPPORTED name the field. */
+FV_API fv_status fv_posterior_create(const fv_posterior_config* cfg, fv_posterior** out);
+/* `load_state_dict` on posterior_encoder.py:116-131,30-55: the reference's key names — pre.{weight,bias}, enc.in_layers.{i}.{bias,weight_g,
+ * weight_v}, enc.res_skip_layers.{i}.{bias,weight_g,weight_v}, proj.{weight,bias} and, in bnvae mode, mu_bn.{weight,bias,running_mean,
+ * running_var,num_batches_tracked} (the last is accepted, carries no eval arithmetic and is not required).  host: fp32, torch layout, copied.
+ * An unknown key -> FV_ERR_INVALID, a wrong shape -> FV_ERR_SHAPE, both by name; after fv_posterior_finalize -> FV_ERR_STATE. */
+FV_API fv_status fv_posterior_load_weight(fv_posterior* p, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+/* Strict load: FV_ERR_MISSING_WEIGHT names the first absent key (before any device work).  Folds g v / |v| per output channel
+ * (posterior_encoder.py:44,54) and the BatchNorm (:129) in fp64, packs MFMA fragments with a gate pair's halves adjacent, uploads. */
+FV_API fv_status fv_posterior_finalize(fv_posterior* p);
+/* R = sum_i (kernel_size - 1) d_i / 2 (posterior_encoder.py:35-36): output frame t depends on the input frames [t - R, t + R] only. */
+FV_API int32_t fv_posterior_reach_frames(const fv_posterior* p);
+/* Rows of z (and of mean / logvar): out_channels (posterior_encoder.py:124-126,146). */
+FV_API int32_t fv_posterior_output_channels(const fv_posterior* p);
+/* Bytes of device scratch fv_posterior_forward needs: h, g and out of posterior_encoder.py:57-80, 3 * batch * hidden_channels * T floats.
+ * 0 for an invalid shape (fv_last_error says which) and for batch = 0 or T = 0. */
+FV_API size_t fv_posterior_workspace_bytes(const fv_posterior* p, int32_t batch, int64_t T);
+/* posterior_encoder.py:133-160 in eval mode.  d_x: (batch, in_channels, T) fp32, x_row_stride >= T the distance in floats between its
+ * channels (batch rows are in_channels * x_row_stride apart: a slice along T of a contiguous tensor passes as it is).  host_lengths: NULL
+ * (every row holds T frames) or `batch` values in [0, T], read before the call returns.  d_z: (batch, out_channels, T), every element
+ * written, exact zeros at and past a row's length.  d_mean / d_logvar: must be NULL in vqvae mode; in the vae modes each is NULL (not
+ * wanted) or (batch, out_channels, T), where padded frames hold 0 — in bnvae mode the mean there is BN(0).  The fourth value of :157, the
+ * mask, is lengths again and is not written.  2 * n_layers + 2 launches per 256 batch rows, whatever batch and T are; batch = 0 or T = 0 is
+ * FV_OK and does nothing.  Asynchronous on `stream`. */
+FV_API fv_status fv_posterior_forward(fv_posterior* p, const float* d_x, int64_t x_row_stride, const int32_t* host_lengths, float* d_z,
+                                      float* d_mean, float* d_logvar, int32_t batch, int64_t T, void* d_workspace, size_t workspace_bytes,
+                                      void* stream);
+FV_API void fv_posterior_destroy(fv_posterior* p);
+
 /* -------- per-launch timing (measurement aid; bench.py's roofline leg) --------
  * Between fv_profile_begin and fv_profile_end every kernel that fv_forward enqueues is bracketed by hipEvents recorded
  * on the launch stream.  fv_profile_end synchronises them and writes a JSON array

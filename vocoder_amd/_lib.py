@@ -70,6 +70,8 @@ EXPORTS = (
     "fv_osc_stream_destroy",
     "fv_pair_wino4_tile", "fv_pair_wino4_pack",
     "fv_vq_create", "fv_vq_destroy", "fv_vq_load_codebook", "fv_vq_set_slices", "fv_vq_workspace_bytes", "fv_vq_encode", "fv_vq_decode",
+    "fv_posterior_create", "fv_posterior_load_weight", "fv_posterior_finalize", "fv_posterior_reach_frames", "fv_posterior_output_channels",
+    "fv_posterior_workspace_bytes", "fv_posterior_forward", "fv_posterior_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -165,6 +167,14 @@ class TemplateConfig(ctypes.Structure):
 
 class VQConfig(ctypes.Structure):
     _fields_ = [("dim", _i32), ("codebook_size", _i32), ("num_quantizers", _i32)]
+
+
+POSTERIOR_MODES = {"vqvae": 0, "vae": 1, "bnvae": 2}
+
+
+class PosteriorConfig(ctypes.Structure):
+    _fields_ = [("in_channels", _i32), ("out_channels", _i32), ("hidden_channels", _i32), ("kernel_size", _i32), ("dilation_rate", _i32),
+                ("dilation_cycle", _i32), ("n_layers", _i32), ("mode", _i32)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -478,6 +488,22 @@ def lib() -> ctypes.CDLL:
     L.fv_vq_encode.restype = _i32
     L.fv_vq_decode.argtypes = [vp, vp, i32p, vp, _i32, i64, vp]
     L.fv_vq_decode.restype = _i32
+    L.fv_posterior_create.argtypes = [ctypes.POINTER(PosteriorConfig), ctypes.POINTER(vp)]
+    L.fv_posterior_create.restype = _i32
+    L.fv_posterior_load_weight.argtypes = [vp, cp, fp, i64p, _i32]
+    L.fv_posterior_load_weight.restype = _i32
+    L.fv_posterior_finalize.argtypes = [vp]
+    L.fv_posterior_finalize.restype = _i32
+    L.fv_posterior_reach_frames.argtypes = [vp]
+    L.fv_posterior_reach_frames.restype = _i32
+    L.fv_posterior_output_channels.argtypes = [vp]
+    L.fv_posterior_output_channels.restype = _i32
+    L.fv_posterior_workspace_bytes.argtypes = [vp, _i32, i64]
+    L.fv_posterior_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_posterior_forward.argtypes = [vp, vp, i64, i32p, vp, vp, vp, _i32, i64, vp, ctypes.c_size_t, vp]
+    L.fv_posterior_forward.restype = _i32
+    L.fv_posterior_destroy.argtypes = [vp]
+    L.fv_posterior_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

@@ -28,18 +28,21 @@ class VQVAECodec(nn.Module):
         hop = hop_length if hop_length is not None else getattr(frontend, "hop_length", None)
         self.hop_length = None if hop is None else int(hop)
 
-    def _latent(self, x: torch.Tensor) -> torch.Tensor:
+    def _latent(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
         """Audio ``(B, 1, L)`` / ``(B, L)`` goes through the front-end first (vae.py:14 ``mel_transforms.input``); a spectrogram
         ``(B, C, T)`` with more than one channel goes straight into the encoder."""
         if self.frontend is not None and (x.dim() == 2 or x.shape[1] == 1):
             x = self.frontend(x if x.dim() == 3 else x[:, None, :])
         elif x.dim() != 3:
             raise ValueError(f"VQVAECodec: expected audio (B, 1, L) with a front-end, or a spectrogram (B, C, T); got {tuple(x.shape)}")
+        if lengths is not None and getattr(self.encoder, "takes_lengths", False):
+            return self.encoder(x, lengths)
         return self.encoder(x)
 
     def encode(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
-        """``codes``: int64 ``(B, T)`` for one quantiser, ``(n_q, B, T)`` for the residual form; ``lengths`` are latent frames per row."""
-        return self.vq.encode(self._latent(x), lengths)
+        """``codes``: int64 ``(B, T)`` for one quantiser, ``(n_q, B, T)`` for the residual form; ``lengths`` are latent frames per row, handed
+        to an encoder that takes them (``PosteriorEncoder``: a row's latent then has the bits of the row alone)."""
+        return self.vq.encode(self._latent(x, lengths), lengths)
 
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
         y = self.decoder(self.vq.from_codes(codes)[0])
@@ -85,16 +88,25 @@ class VQVAECodec(nn.Module):
 
 def build_vqvae(n_fft: int = 3072, hop_length: int = 2048, win_length: int = 3072, latent_size: int = 512, codebook_size: int = 4096,
                 num_quantizers: int = 1, encoder_depths=(6,), encoder_dims=(512,), decoder_depths=(6, 3), decoder_dims=(512, 1024),
-                kernel_size: int = 7) -> VQVAECodec:
-    """configs/model/vqvae.yaml + generator/vocos-small-vae.yaml with the drop-in modules."""
+                kernel_size: int = 7, encoder: str = "convnext", hidden_channels: int = 192, posterior_layers: int = 16,
+                posterior_kernel_size: int = 5) -> VQVAECodec:
+    """configs/model/vqvae.yaml + generator/vocos-small-vae.yaml with the drop-in modules.  ``encoder="posterior"`` puts the reference's
+    ``PosteriorEncoder(mode="vqvae", out_channels=latent_size)`` into the encoder slot instead of the ConvNeXt one."""
     from .data.transforms.spectrogram import LinearSpectrogram
     from .modules.encoders.convnext import ConvNeXtEncoder
     from .modules.generators.unify import UnifyGenerator
     from .modules.generators.vocos import ISTFTHead
     from .modules.quantizers import ResidualVectorQuantization, VectorQuantization
-    if encoder_dims[-1] != latent_size:
-        raise ValueError(f"latent_size ({latent_size}) must equal the encoder's last width ({encoder_dims[-1]})")
-    encoder = ConvNeXtEncoder(input_channels=n_fft // 2 + 1, depths=list(encoder_depths), dims=list(encoder_dims), kernel_size=kernel_size)
+    if encoder == "posterior":
+        from .modules.encoders.posterior_encoder import PosteriorEncoder
+        enc = PosteriorEncoder(in_channels=n_fft // 2 + 1, out_channels=latent_size, hidden_channels=hidden_channels,
+                               kernel_size=posterior_kernel_size, n_layers=posterior_layers, mode="vqvae")
+    elif encoder == "convnext":
+        if encoder_dims[-1] != latent_size:
+            raise ValueError(f"latent_size ({latent_size}) must equal the encoder's last width ({encoder_dims[-1]})")
+        enc = ConvNeXtEncoder(input_channels=n_fft // 2 + 1, depths=list(encoder_depths), dims=list(encoder_dims), kernel_size=kernel_size)
+    else:
+        raise ValueError(f"encoder must be 'convnext' or 'posterior', got {encoder!r}")
     decoder = UnifyGenerator(
         backbone=ConvNeXtEncoder(input_channels=latent_size, depths=list(decoder_depths), dims=list(decoder_dims), kernel_size=kernel_size),
         head=ISTFTHead(dim=decoder_dims[-1], n_fft=n_fft, hop_length=hop_length, win_length=win_length, padding="same"))
@@ -102,7 +114,7 @@ def build_vqvae(n_fft: int = 3072, hop_length: int = 2048, win_length: int = 307
         vq = ResidualVectorQuantization(dim=latent_size, codebook_size=codebook_size, num_quantizers=num_quantizers, kmeans_init=False)
     else:
         vq = VectorQuantization(dim=latent_size, codebook_size=codebook_size, kmeans_init=False)
-    return VQVAECodec(encoder, decoder, vq, frontend=LinearSpectrogram(n_fft, win_length, hop_length), hop_length=hop_length)
+    return VQVAECodec(enc, decoder, vq, frontend=LinearSpectrogram(n_fft, win_length, hop_length), hop_length=hop_length)
 
 
 def main(argv=None):
@@ -120,11 +132,14 @@ def main(argv=None):
     ap.add_argument("--latent-size", type=int, default=512)
     ap.add_argument("--codebook-size", type=int, default=4096)
     ap.add_argument("--num-quantizers", type=int, default=1)
+    ap.add_argument("--encoder", choices=("convnext", "posterior"), default="convnext", help="the encoder slot: ConvNeXtEncoder or PosteriorEncoder")
+    ap.add_argument("--hidden-channels", type=int, default=192, help="--encoder posterior: the WaveNet's width")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("vocoder_amd.codec needs a HIP device: there is no CPU path")
     model = build_vqvae(a.n_fft, a.hop_length, a.win_length, a.latent_size, a.codebook_size, a.num_quantizers,
-                        encoder_dims=(a.latent_size,), decoder_dims=(a.latent_size, 2 * a.latent_size))
+                        encoder_dims=(a.latent_size,), decoder_dims=(a.latent_size, 2 * a.latent_size), encoder=a.encoder,
+                        hidden_channels=a.hidden_channels)
     if a.checkpoint:
         model.load_checkpoint(a.checkpoint, a.trust_checkpoint)
     model = model.eval().cuda()

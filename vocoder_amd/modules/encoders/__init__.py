@@ -1,1 +1,2 @@
 from .convnext import ConvNeXtEncoder  # noqa: F401
+from .posterior_encoder import PosteriorEncoder  # noqa: F401

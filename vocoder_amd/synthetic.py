@@ -161,6 +161,44 @@ def convnext_state_dict(cfg: dict, seed: int = 0, prefix: str = "") -> dict:
     return sd
 
 
+POSTERIOR_DEFAULT = dict(in_channels=513, out_channels=512, hidden_channels=192, kernel_size=5, dilation_rate=1, dilation_cycle=1,
+                         n_layers=16, mode="vqvae")
+
+
+def posterior_state_dict(cfg: dict, seed: int = 0) -> dict:
+    """State dict of PosteriorEncoder(**cfg), reference key order (posterior_encoder.py:116-131,30-55): the old weight-norm naming
+    ``weight_g`` / ``weight_v`` with g near |v| but not equal to it, non-zero biases, and for ``mode="bnvae"`` non-trivial ``mu_bn``
+    running statistics and bias."""
+    rng = np.random.default_rng(seed)
+    sd: dict = {}
+    cin, out, c = cfg["in_channels"], cfg["out_channels"], cfg["hidden_channels"]
+    k, nl, mode = cfg.get("kernel_size", 5), cfg.get("n_layers", 16), cfg.get("mode", "vqvae")
+
+    def wn(prefix, shape):
+        v = rng.normal(0.0, 1.0 / sqrt(shape[1] * shape[2]), size=shape)
+        norm = np.sqrt((v.reshape(shape[0], -1) ** 2).sum(1))
+        sd[f"{prefix}.bias"] = rng.normal(0.0, 0.05, size=shape[0]).astype(np.float32)
+        sd[f"{prefix}.weight_g"] = (norm * rng.uniform(0.8, 1.25, size=shape[0])).reshape(shape[0], 1, 1).astype(np.float32)
+        sd[f"{prefix}.weight_v"] = v.astype(np.float32)
+
+    sd["pre.weight"] = rng.normal(0.0, 1.0 / sqrt(cin), size=(c, cin, 1)).astype(np.float32)
+    sd["pre.bias"] = rng.normal(0.0, 0.05, size=c).astype(np.float32)
+    for i in range(nl):
+        wn(f"enc.in_layers.{i}", (2 * c, c, k))
+    for i in range(nl):
+        wn(f"enc.res_skip_layers.{i}", (2 * c if i < nl - 1 else c, c, 1))
+    rows = out if mode == "vqvae" else 2 * out
+    sd["proj.weight"] = rng.normal(0.0, 1.0 / sqrt(c), size=(rows, c, 1)).astype(np.float32)
+    sd["proj.bias"] = rng.normal(0.0, 0.05, size=rows).astype(np.float32)
+    if mode == "bnvae":
+        sd["mu_bn.weight"] = np.full(out, 0.5, np.float32)
+        sd["mu_bn.bias"] = rng.normal(0.0, 0.3, size=out).astype(np.float32)
+        sd["mu_bn.running_mean"] = rng.normal(0.0, 0.5, size=out).astype(np.float32)
+        sd["mu_bn.running_var"] = rng.uniform(0.3, 2.0, size=out).astype(np.float32)
+        sd["mu_bn.num_batches_tracked"] = np.array(100, np.int64)
+    return sd
+
+
 def istft_head_state_dict(cfg: dict, seed: int = 0, prefix: str = "") -> dict:
     """State dict for ISTFTHead(**cfg): ``out`` = Conv1d(dim, 2*n_fft, 1), ``istft.window`` = hann
     (/root/reference/fish_vocoder/modules/generators/vocos.py:33-41)."""
