@@ -1179,6 +1179,67 @@ FV_API fv_status fv_posterior_forward(fv_posterior* p, const float* d_x, int64_t
                                       void* stream);
 FV_API void fv_posterior_destroy(fv_posterior* p);
 
+/* -------- wav2vec2 / HuBERT encoder (modules/encoders/hubert.py: HubertModel in its "stable layer norm" form, then `post`) --------
+ * Eval-mode fp32 forward of the family feat_extract_norm = "layer", do_stable_layer_norm, conv_bias, feat_proj_layer_norm, GELU, eps 1e-5
+ * (facebook/hubert-large-ll60k, facebook/mms-300m).  Activations are time major, (row, frame, channel).  With len_0 = the row's samples and
+ * len_l = floor((len_{l-1} - kernel_l) / stride_l) + 1 (0 where that is not positive) — HF's _get_feat_extract_output_lengths:
+ *   conv layer l:   c = GELU(LN_channels(conv_l(c) + bias)), no padding: a valid frame reads valid samples only
+ *   projection:     h = W LN(c) + b
+ *   pos conv:       h = h + GELU(conv_grouped(h)), k = pos_conv_kernel taps, zero padding k / 2 (an even k drops the last sample: SamePad);
+ *                   weight norm over dim 2, w[:, :, j] = g[j] v[:, :, j] / |v[:, :, j]|, folded in fp64 at finalize
+ *   layer i:        h = h + out(attn(LN(h)));  h = h + W2 GELU(W1 LN(h))     attn: softmax(Q K' / 8) V per head over the row's own frames
+ *   last:           y = LN(h)
+ *   post (post_channels > 0): Conv1d(hidden, O, 3, pad 1), SiLU, Conv1d(O, O, 3, stride 2, pad 1), SiLU, Conv1d(O, O, 1)
+ * Every matrix product, the convs included, is one implicit GEMM on v_mfma_f32_32x32x2_f32; an output element's sum runs over k in
+ * ascending order from one accumulator, then the bias is added.  The attention keeps a running maximum and sum over tiles of 32 keys: no
+ * frames x frames tensor exists.  Keys, frames and samples at or past a row's own count are never loaded, and every output and hidden
+ * state holds exact zeros there, so a row has the same bits alone, in any batch and padded to any T.
+ * Limits: head size hidden / heads = 64; hidden, conv_dim in [1, 1024] (a LayerNorm row lives in one wave's registers) and multiples of 4;
+ * intermediate, post_channels at most 8192 and multiples of 4; layers in [1, 64]; n_conv in [1, 8] with kernel[0] at most 32; kernel,
+ * stride in [1, 64]; pos_conv_kernel in [1, 256], pos_conv_groups dividing hidden; batch in [0, 65535], batch * T at most 2^30 samples.
+ * Every entry validates all a host can see before it enqueues anything, and names the offending field. */
+typedef struct fv_w2v_config {
+    int32_t hidden;            /* HF hidden_size */
+    int32_t layers;            /* num_hidden_layers */
+    int32_t heads;             /* num_attention_heads */
+    int32_t intermediate;      /* intermediate_size */
+    int32_t n_conv;            /* len(conv_dim) */
+    int32_t conv_dim[8];
+    int32_t conv_kernel[8];
+    int32_t conv_stride[8];
+    int32_t pos_conv_kernel;   /* num_conv_pos_embeddings */
+    int32_t pos_conv_groups;   /* num_conv_pos_embedding_groups */
+    int32_t post_channels;     /* hubert.py's output_size; 0 = the backbone alone (last_hidden_state) */
+} fv_w2v_config;
+
+typedef struct fv_w2v fv_w2v;
+
+/* Validates on the host, no device work.  FV_ERR_INVALID / FV_ERR_UNSUPPORTED name the field. */
+FV_API fv_status fv_w2v_create(const fv_w2v_config* cfg, fv_w2v** out);
+/* The reference module's state-dict keys: "model." + HF's (feature_extractor.conv_layers.{l}.{conv,layer_norm}.{weight,bias},
+ * feature_projection.{layer_norm,projection}.*, encoder.pos_conv_embed.conv.{bias,parametrizations.weight.original0,original1},
+ * encoder.layers.{i}.{attention.{k,v,q,out}_proj,layer_norm,feed_forward.{intermediate,output}_dense,final_layer_norm}.*,
+ * encoder.layer_norm.*) and post.{0,2,4}.{weight,bias}.  The legacy ...conv.weight_g / weight_v are taken for original0 / original1;
+ * model.masked_spec_embed is accepted and ignored.  host: fp32, torch layout, copied.  An unknown key -> FV_ERR_INVALID, a wrong shape ->
+ * FV_ERR_SHAPE, both by name; after fv_w2v_finalize -> FV_ERR_STATE. */
+FV_API fv_status fv_w2v_load_weight(fv_w2v* w, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+/* Strict load: FV_ERR_MISSING_WEIGHT names the first absent key (before any device work).  Folds the weight norm, reorders conv weights
+ * to (out, tap, in), fuses q | k | v into one matrix, uploads. */
+FV_API fv_status fv_w2v_finalize(fv_w2v* w);
+/* Frames that `samples` samples give: stage 0 after the backbone, stage 1 after `post` (floor((F - 1) / 2) + 1; 0 for F = 0).  -1: bad argument. */
+FV_API int64_t fv_w2v_frames(const fv_w2v* w, int64_t samples, int32_t stage);
+/* Bytes of device scratch fv_w2v_forward needs; 0 for an invalid shape (fv_last_error says which) and where no frame comes out. */
+FV_API size_t fv_w2v_workspace_bytes(const fv_w2v* w, int32_t batch, int64_t T);
+/* d_x: (batch, T) fp32 samples.  host_lengths: NULL (every row holds T samples) or `batch` sample counts in [0, T], read before the call
+ * returns.  With F = fv_w2v_frames(T, 0), F2 = fv_w2v_frames(T, 1):  d_out is (batch, post_channels, F2), the reference's layout — or, with
+ * post_channels = 0, last_hidden_state (batch, F, hidden); d_hidden_states: NULL or (layers + 1, batch, F, hidden), the input of layer 0
+ * and every layer's output (HF's output_hidden_states without the final norm).  Every element is written, exact zeros at and past a row's
+ * own frame count.  d_workspace, d_out and d_hidden_states must be 16-byte aligned.  batch = 0 or F = 0 is FV_OK and launches nothing.
+ * Asynchronous on `stream`. */
+FV_API fv_status fv_w2v_forward(fv_w2v* w, const float* d_x, int64_t T, const int32_t* host_lengths, int32_t batch, float* d_out,
+                                float* d_hidden_states, void* d_workspace, size_t workspace_bytes, void* stream);
+FV_API void fv_w2v_destroy(fv_w2v* w);
+
 /* -------- per-launch timing (measurement aid; bench.py's roofline leg) --------
  * Between fv_profile_begin and fv_profile_end every kernel that fv_forward enqueues is bracketed by hipEvents recorded
  * on the launch stream.  fv_profile_end synchronises them and writes a JSON array

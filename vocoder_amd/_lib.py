@@ -72,6 +72,7 @@ EXPORTS = (
     "fv_vq_create", "fv_vq_destroy", "fv_vq_load_codebook", "fv_vq_set_slices", "fv_vq_workspace_bytes", "fv_vq_encode", "fv_vq_decode",
     "fv_posterior_create", "fv_posterior_load_weight", "fv_posterior_finalize", "fv_posterior_reach_frames", "fv_posterior_output_channels",
     "fv_posterior_workspace_bytes", "fv_posterior_forward", "fv_posterior_destroy",
+    "fv_w2v_create", "fv_w2v_load_weight", "fv_w2v_finalize", "fv_w2v_frames", "fv_w2v_workspace_bytes", "fv_w2v_forward", "fv_w2v_destroy",
 )
 
 _i32 = ctypes.c_int32
@@ -175,6 +176,16 @@ POSTERIOR_MODES = {"vqvae": 0, "vae": 1, "bnvae": 2}
 class PosteriorConfig(ctypes.Structure):
     _fields_ = [("in_channels", _i32), ("out_channels", _i32), ("hidden_channels", _i32), ("kernel_size", _i32), ("dilation_rate", _i32),
                 ("dilation_cycle", _i32), ("n_layers", _i32), ("mode", _i32)]
+
+
+W2V_MAX_CONV = 8
+
+
+class W2VConfig(ctypes.Structure):
+    """fv_w2v_config, field for field (include/fishvoc.h)."""
+    _fields_ = [("hidden", _i32), ("layers", _i32), ("heads", _i32), ("intermediate", _i32), ("n_conv", _i32),
+                ("conv_dim", _i32 * W2V_MAX_CONV), ("conv_kernel", _i32 * W2V_MAX_CONV), ("conv_stride", _i32 * W2V_MAX_CONV),
+                ("pos_conv_kernel", _i32), ("pos_conv_groups", _i32), ("post_channels", _i32)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -504,6 +515,20 @@ def lib() -> ctypes.CDLL:
     L.fv_posterior_forward.restype = _i32
     L.fv_posterior_destroy.argtypes = [vp]
     L.fv_posterior_destroy.restype = None
+    L.fv_w2v_create.argtypes = [ctypes.POINTER(W2VConfig), ctypes.POINTER(vp)]
+    L.fv_w2v_create.restype = _i32
+    L.fv_w2v_load_weight.argtypes = [vp, cp, fp, i64p, _i32]
+    L.fv_w2v_load_weight.restype = _i32
+    L.fv_w2v_finalize.argtypes = [vp]
+    L.fv_w2v_finalize.restype = _i32
+    L.fv_w2v_frames.argtypes = [vp, i64, _i32]
+    L.fv_w2v_frames.restype = i64
+    L.fv_w2v_workspace_bytes.argtypes = [vp, _i32, i64]
+    L.fv_w2v_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_w2v_forward.argtypes = [vp, vp, i64, i32p, _i32, vp, vp, vp, ctypes.c_size_t, vp]
+    L.fv_w2v_forward.restype = _i32
+    L.fv_w2v_destroy.argtypes = [vp]
+    L.fv_w2v_destroy.restype = None
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

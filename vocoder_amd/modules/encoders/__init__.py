@@ -1,2 +1,3 @@
 from .convnext import ConvNeXtEncoder  # noqa: F401
+from .hubert import HubertEncoder  # noqa: F401
 from .posterior_encoder import PosteriorEncoder  # noqa: F401

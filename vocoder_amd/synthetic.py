@@ -199,6 +199,57 @@ def posterior_state_dict(cfg: dict, seed: int = 0) -> dict:
     return sd
 
 
+HUBERT_TINY = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, conv_dim=[32, 64], conv_kernel=[10, 3],
+                   conv_stride=[5, 2], num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4, output_size=96)
+
+
+def hubert_state_dict(cfg: dict, seed: int = 0) -> dict:
+    """State dict of the reference's HubertEncoder over ``HubertModel(HubertConfig(**cfg))`` in the stable-layer-norm family, in the
+    reference's key order: ``model.`` + HF's keys (the positional conv under ``parametrizations.weight.original0`` / ``original1``), then
+    ``post.{0,2,4}``.  ``cfg`` holds HF's field names and ``output_size``.  Weights are scaled for O(1) activations; biases are non-zero, the
+    LayerNorm weights lie away from 1 and ``original0`` away from |v|."""
+    rng = np.random.default_rng(seed)
+    sd: dict = {}
+    H, I, O = cfg["hidden_size"], cfg["intermediate_size"], cfg["output_size"]
+    dims, kernels = list(cfg["conv_dim"]), list(cfg["conv_kernel"])
+    k, g = cfg["num_conv_pos_embeddings"], cfg["num_conv_pos_embedding_groups"]
+
+    def dense(prefix, shape, gain=1.0):
+        fan_in = int(np.prod(shape[1:]))
+        sd[f"{prefix}.weight"] = rng.normal(0.0, gain / sqrt(fan_in), size=shape).astype(np.float32)
+        sd[f"{prefix}.bias"] = rng.normal(0.0, 0.05, size=shape[0]).astype(np.float32)
+
+    def norm(prefix, c):
+        sd[f"{prefix}.weight"] = rng.uniform(0.6, 1.5, size=c).astype(np.float32)
+        sd[f"{prefix}.bias"] = rng.normal(0.0, 0.1, size=c).astype(np.float32)
+
+    sd["model.masked_spec_embed"] = rng.uniform(0.0, 1.0, size=H).astype(np.float32)
+    for i, (c, kk) in enumerate(zip(dims, kernels)):
+        dense(f"model.feature_extractor.conv_layers.{i}.conv", (c, dims[i - 1] if i else 1, kk), gain=1.4)
+        norm(f"model.feature_extractor.conv_layers.{i}.layer_norm", c)
+    norm("model.feature_projection.layer_norm", dims[-1])
+    dense("model.feature_projection.projection", (H, dims[-1]))
+    sd["model.encoder.pos_conv_embed.conv.bias"] = rng.normal(0.0, 0.05, size=H).astype(np.float32)
+    v = rng.normal(0.0, 1.0 / sqrt(k * H // g), size=(H, H // g, k))
+    tap_norm = np.sqrt((v ** 2).sum((0, 1)))
+    sd["model.encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = (
+        tap_norm * rng.uniform(0.7, 1.4, size=k)).reshape(1, 1, k).astype(np.float32)
+    sd["model.encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = v.astype(np.float32)
+    norm("model.encoder.layer_norm", H)
+    for i in range(cfg["num_hidden_layers"]):
+        p = f"model.encoder.layers.{i}"
+        for name in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            dense(f"{p}.attention.{name}", (H, H), gain=2.0 if name in ("k_proj", "q_proj") else 1.0)
+        norm(f"{p}.layer_norm", H)
+        dense(f"{p}.feed_forward.intermediate_dense", (I, H))
+        dense(f"{p}.feed_forward.output_dense", (H, I))
+        norm(f"{p}.final_layer_norm", H)
+    dense("post.0", (O, H, 3))
+    dense("post.2", (O, O, 3))
+    dense("post.4", (O, O, 1))
+    return sd
+
+
 def istft_head_state_dict(cfg: dict, seed: int = 0, prefix: str = "") -> dict:
     """State dict for ISTFTHead(**cfg): ``out`` = Conv1d(dim, 2*n_fft, 1), ``istft.window`` = hann
     (/root/reference/fish_vocoder/modules/generators/vocos.py:33-41)."""
