@@ -1240,6 +1240,38 @@ FV_API fv_status fv_w2v_forward(fv_w2v* w, const float* d_x, int64_t T, const in
                                 float* d_hidden_states, void* d_workspace, size_t workspace_bytes, void* stream);
 FV_API void fv_w2v_destroy(fv_w2v* w);
 
+/* -------- MMSEncoder's front and back (modules/encoders/mms.py) --------
+ * The reference resamples to 16 kHz (mms.py:20-22), moves every row through numpy into HF's Wav2Vec2FeatureExtractor (mms.py:23-27), runs
+ * Wav2Vec2Model (mms.py:29) and maps the backbone's frames to L / hop_length frames (mms.py:30-31).  The resampler is fv_global_resample_*,
+ * the backbone fv_w2v_forward on a post_channels = 0 encoder; the two steps between and after them are the entries below.  Both take ragged
+ * rows: per-row counts are host arrays read before the call returns, nothing at or past a row's count is read, the outputs hold exact
+ * zeros there, and a row has the same bits alone, in any batch, in any row order and padded to any width.  Every entry validates all a
+ * host can see, and names the offending argument, before it enqueues anything.  batch in [0, 65535]; batch * T, batch * F and batch * N at
+ * most 2^30. */
+/* Bytes of device scratch fv_mms_normalize needs for the sums behind mms.py:23-27 (16 per row and segment of 4096 samples); 0 for an
+ * invalid shape (fv_last_error says which) and for batch = 0 or T = 0. */
+FV_API size_t fv_mms_normalize_workspace_bytes(int32_t batch, int64_t T);
+/* mms.py:23-27, the processor's do_normalize (HF's zero_mean_unit_var_norm): y = (x - mean) / sqrt(var + 1e-7) with the population
+ * variance, each row over its own length.  d_x, d_y: (batch, T) fp32, d_y may be d_x.  host_lengths: NULL (every row holds T samples) or
+ * `batch` counts in [0, T].  The sums of x and x^2 are fp64, over segments of 4096 samples and then over the segments in ascending order —
+ * an order fixed by the row's length alone, no atomics; mean and 1 / sqrt(var + 1e-7) are rounded to fp32 once, and an output is one
+ * rounded subtraction and one rounded product.  A row of length 0 gives zeros; a constant row gives zeros, as numpy does.  d_workspace
+ * must be 16-byte aligned; 16-byte accesses are used where T is a multiple of 4 and d_x, d_y are 16-byte aligned, with the same bits
+ * either way.  Asynchronous on `stream`. */
+FV_API fv_status fv_mms_normalize(const float* d_x, int64_t T, const int32_t* host_lengths, int32_t batch, float* d_y, void* d_workspace,
+                                  size_t workspace_bytes, void* stream);
+/* mms.py:30-31, x.transpose(1, 2) then F.interpolate(size = N, mode = "nearest"): d_x (batch, F, H) time major, fv_w2v_forward's
+ * last_hidden_state -> d_y (batch, H, N) channel major.  host_frames / host_out_frames: NULL (every row holds F source frames / N output
+ * frames) or `batch` counts in [0, F] / [0, N].  y[b][h][j] = x[b][src][h] for j < N_b with PyTorch's legacy rule in fp32,
+ * src = min((int)floorf(j * scale), F_b - 1), scale = (float)F_b / (float)N_b, the product one rounded multiply; exact zeros for
+ * j >= N_b.  A row with F_b = 0 and N_b > 0 has nothing to read and is refused.  H in [4, 8192], a multiple of 4; d_x 16-byte aligned;
+ * 16-byte stores where N is a multiple of 4 and d_y is 16-byte aligned, with the same bits either way.  Asynchronous on `stream`. */
+FV_API fv_status fv_mms_interpolate(const float* d_x, int64_t F, int32_t H, const int32_t* host_frames, const int32_t* host_out_frames,
+                                    int32_t batch, float* d_y, int64_t N, void* stream);
+/* Pure host: the source frame fv_mms_interpolate takes for output frame j of a row with F source and N output frames (mms.py:31); -1 for
+ * F < 1, N < 1 or j outside [0, N). */
+FV_API int64_t fv_mms_nearest_index(int64_t F, int64_t N, int64_t j);
+
 /* -------- per-launch timing (measurement aid; bench.py's roofline leg) --------
  * Between fv_profile_begin and fv_profile_end every kernel that fv_forward enqueues is bracketed by hipEvents recorded
  * on the launch stream.  fv_profile_end synchronises them and writes a JSON array

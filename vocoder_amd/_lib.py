@@ -73,6 +73,7 @@ EXPORTS = (
     "fv_posterior_create", "fv_posterior_load_weight", "fv_posterior_finalize", "fv_posterior_reach_frames", "fv_posterior_output_channels",
     "fv_posterior_workspace_bytes", "fv_posterior_forward", "fv_posterior_destroy",
     "fv_w2v_create", "fv_w2v_load_weight", "fv_w2v_finalize", "fv_w2v_frames", "fv_w2v_workspace_bytes", "fv_w2v_forward", "fv_w2v_destroy",
+    "fv_mms_normalize_workspace_bytes", "fv_mms_normalize", "fv_mms_interpolate", "fv_mms_nearest_index",
 )
 
 _i32 = ctypes.c_int32
@@ -529,6 +530,14 @@ def lib() -> ctypes.CDLL:
     L.fv_w2v_forward.restype = _i32
     L.fv_w2v_destroy.argtypes = [vp]
     L.fv_w2v_destroy.restype = None
+    L.fv_mms_normalize_workspace_bytes.argtypes = [_i32, i64]
+    L.fv_mms_normalize_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_mms_normalize.argtypes = [vp, i64, i32p, _i32, vp, vp, ctypes.c_size_t, vp]
+    L.fv_mms_normalize.restype = _i32
+    L.fv_mms_interpolate.argtypes = [vp, i64, _i32, i32p, i32p, _i32, vp, i64, vp]
+    L.fv_mms_interpolate.restype = _i32
+    L.fv_mms_nearest_index.argtypes = [i64, i64, i64]
+    L.fv_mms_nearest_index.restype = i64
     L.fv_last_error.restype = cp
     L.fv_abi_version.restype = _i32
     L.fv_last_kernel.restype = cp

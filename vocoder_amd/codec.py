@@ -30,7 +30,14 @@ class VQVAECodec(nn.Module):
 
     def _latent(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
         """Audio ``(B, 1, L)`` / ``(B, L)`` goes through the front-end first (vae.py:14 ``mel_transforms.input``); a spectrogram
-        ``(B, C, T)`` with more than one channel goes straight into the encoder."""
+        ``(B, C, T)`` with more than one channel goes straight into the encoder.  An encoder that declares ``takes_audio`` receives the audio
+        itself, without the front-end; ``lengths`` (latent frames) do not reach such an encoder, which counts in samples, so it runs every
+        row over its whole width, padding included — for ragged audio call the encoder with its own ``lengths=`` (samples) and quantise its
+        output with ``vq.encode(z, frames)``."""
+        if getattr(self.encoder, "takes_audio", False):        # vae.py:81 generator.encoder(audio, mask): an encoder of raw audio (MMSEncoder)
+            if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+                raise ValueError(f"VQVAECodec: an encoder that takes audio expects (B, 1, L) or (B, L); got {tuple(x.shape)}")
+            return self.encoder(x)
         if self.frontend is not None and (x.dim() == 2 or x.shape[1] == 1):
             x = self.frontend(x if x.dim() == 3 else x[:, None, :])
         elif x.dim() != 3:
@@ -41,7 +48,8 @@ class VQVAECodec(nn.Module):
 
     def encode(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
         """``codes``: int64 ``(B, T)`` for one quantiser, ``(n_q, B, T)`` for the residual form; ``lengths`` are latent frames per row, handed
-        to an encoder that takes them (``PosteriorEncoder``: a row's latent then has the bits of the row alone)."""
+        to an encoder that takes them (``PosteriorEncoder``: a row's latent then has the bits of the row alone).  Ragged encoding
+        is not supported through an encoder of raw audio (``takes_audio``, ``MMSEncoder``): see ``_latent``."""
         return self.vq.encode(self._latent(x, lengths), lengths)
 
     def decode(self, codes: torch.Tensor) -> torch.Tensor:

@@ -30,6 +30,7 @@ TARGET_ALIASES = {
     "fish_vocoder.modules.encoders.convnext": "vocoder_amd.modules.encoders.convnext",
     "fish_vocoder.modules.encoders.posterior_encoder": "vocoder_amd.modules.encoders.posterior_encoder",
     "fish_vocoder.modules.encoders.hubert": "vocoder_amd.modules.encoders.hubert",
+    "fish_vocoder.modules.encoders.mms": "vocoder_amd.modules.encoders.mms",
     "fish_vocoder.data.transforms.spectrogram": "vocoder_amd.data.transforms.spectrogram",
 }
 

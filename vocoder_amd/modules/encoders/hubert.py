@@ -40,13 +40,14 @@ _POS = "model.encoder.pos_conv_embed.conv."
 _LEGACY = {_POS + "weight_g": _POS + "parametrizations.weight.original0", _POS + "weight_v": _POS + "parametrizations.weight.original1"}
 
 
-def resolve_config(config, model_name: str) -> dict:
-    """HF's fields as a dict, defaults filled in; from ``config`` or from ``model_name``/config.json.  Never touches the network."""
+def resolve_config(config, model_name: str, who: str = "HubertEncoder") -> dict:
+    """HF's fields as a dict, defaults filled in; from ``config`` or from ``model_name``/config.json.  Never touches the network.  ``who``
+    names the module in the refusals."""
     if config is None:
         path = os.path.join(str(model_name), "config.json")
         if not os.path.isdir(str(model_name)) or not os.path.isfile(path):
             raise ValueError(
-                f"HubertEncoder: model_name = {model_name!r} is not a local directory holding a config.json, and this module never downloads "
+                f"{who}: model_name = {model_name!r} is not a local directory holding a config.json, and this module never downloads "
                 "from the hub; pass config= (a dict or an object with HF's field names) or a local directory, then load_state_dict the weights")
         with open(path, "r", encoding="utf-8") as fh:
             config = json.load(fh)
@@ -54,15 +55,15 @@ def resolve_config(config, model_name: str) -> dict:
     cfg = {k: get(k, d) for k, d in _HF_DEFAULTS.items()}
     for field, want in _FAMILY.items():
         if cfg[field] != want:
-            raise ValueError(f"HubertEncoder: {field} = {cfg[field]!r} is not supported: only the stable-layer-norm family "
+            raise ValueError(f"{who}: {field} = {cfg[field]!r} is not supported: only the stable-layer-norm family "
                              f"({field} = {want!r}) has kernels")
     for field in ("conv_dim", "conv_kernel", "conv_stride"):
         cfg[field] = [int(v) for v in cfg[field]]
     n = len(cfg["conv_dim"])
     if len(cfg["conv_kernel"]) != n or len(cfg["conv_stride"]) != n:
-        raise ValueError(f"HubertEncoder: conv_kernel and conv_stride must have len(conv_dim) = {n} entries")
+        raise ValueError(f"{who}: conv_kernel and conv_stride must have len(conv_dim) = {n} entries")
     if not 1 <= n <= _lib.W2V_MAX_CONV:
-        raise ValueError(f"HubertEncoder: conv_dim has {n} layers; the library takes 1 to {_lib.W2V_MAX_CONV}")
+        raise ValueError(f"{who}: conv_dim has {n} layers; the library takes 1 to {_lib.W2V_MAX_CONV}")
     return cfg
 
 
@@ -130,22 +131,17 @@ def _backbone(cfg: dict) -> nn.Module:
     return model
 
 
-class HubertEncoder(nn.Module):
-    def __init__(self, model_name: str = "facebook/hubert-large-ll60k", freeze_backbone: bool = True, output_size: int = 1024, config=None):
-        super().__init__()
-        if not freeze_backbone:
-            raise ValueError("HubertEncoder: freeze_backbone = False needs gradients through the backbone; the kernels are inference-only")
-        self.model_name, self.freeze_backbone, self.output_size = model_name, True, int(output_size)
-        self.hf_config = resolve_config(config, model_name)
-        if self.output_size < 1:
-            raise ValueError(f"HubertEncoder: output_size = {output_size} must be >= 1")
+class _BackboneModule(nn.Module):
+    """What the encoders over the wav2vec2 backbone share: the parameter holder under ``model.``, the key hooks of its state dict, the
+    fp32-only precision switch, the conv stack's frame count and the cache of one finalized ``fv_w2v`` engine."""
+    post_channels = 0       # fv_w2v_config.post_channels of the engine: 0 = the backbone alone
+
+    def _init_backbone(self, config, model_name: str) -> None:
+        self.hf_config = resolve_config(config, model_name, type(self).__name__)
         self._config()                  # the library's limits, by name, before any parameter is allocated
-        H, O = self.hf_config["hidden_size"], self.output_size
         self.model = _backbone(self.hf_config)
         for p in self.model.parameters():
             p.requires_grad = False
-        self.post = nn.Sequential(nn.Conv1d(H, O, kernel_size=3, padding=1), nn.SiLU(), nn.Conv1d(O, O, stride=2, kernel_size=3, padding=1), nn.SiLU(),
-                                  nn.Conv1d(O, O, kernel_size=1))
         object.__setattr__(self, "_engine", None)
         self._register_load_state_dict_pre_hook(self._legacy_keys)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate_engine())
@@ -166,7 +162,7 @@ class HubertEncoder(nn.Module):
         arr = ctypes.c_int32 * _lib.W2V_MAX_CONV
         cfg = _lib.W2VConfig(int(c["hidden_size"]), int(c["num_hidden_layers"]), int(c["num_attention_heads"]), int(c["intermediate_size"]), n,
                              arr(*c["conv_dim"], *pad), arr(*c["conv_kernel"], *pad), arr(*c["conv_stride"], *pad),
-                             int(c["num_conv_pos_embeddings"]), int(c["num_conv_pos_embedding_groups"]), self.output_size)
+                             int(c["num_conv_pos_embeddings"]), int(c["num_conv_pos_embedding_groups"]), int(self.post_channels))
         h = ctypes.c_void_p()
         L = _lib.lib()
         if L.fv_w2v_create(ctypes.byref(cfg), ctypes.byref(h)) != 0:
@@ -182,17 +178,16 @@ class HubertEncoder(nn.Module):
     @precision.setter
     def precision(self, value: str) -> None:
         if value == "f16x3":
-            raise ValueError("HubertEncoder is fp32 only: there is no f16x3 form of the wav2vec2 kernels")
+            raise ValueError(f"{type(self).__name__} is fp32 only: there is no f16x3 form of the wav2vec2 kernels")
         if value != "f32":
             raise ValueError(f"precision must be 'f32', got {value!r}")
 
-    def frames(self, samples: int, backbone: bool = False) -> int:
-        """Frames that ``samples`` samples give after ``post`` (or after the backbone): HF's ``_get_feat_extract_output_lengths``, then
-        ``floor((F - 1) / 2) + 1``."""
+    def conv_frames(self, samples: int) -> int:
+        """Frames the backbone gives for ``samples`` samples at its own rate: HF's ``_get_feat_extract_output_lengths``."""
         f = int(samples)
         for k, s in zip(self.hf_config["conv_kernel"], self.hf_config["conv_stride"]):
             f = (f - k) // s + 1 if f >= k else 0
-        return f if backbone else ((f - 1) // 2 + 1 if f > 0 else 0)
+        return f
 
     # -- engine cache (as PosteriorEncoder keeps its own) -------------------------------------------
     def invalidate_engine(self) -> None:
@@ -212,6 +207,30 @@ class HubertEncoder(nn.Module):
             eng = _W2VEngine(self._config(), self.state_dict(), device)
             object.__setattr__(self, "_engine", eng)
         return eng
+
+
+class HubertEncoder(_BackboneModule):
+    def __init__(self, model_name: str = "facebook/hubert-large-ll60k", freeze_backbone: bool = True, output_size: int = 1024, config=None):
+        super().__init__()
+        if not freeze_backbone:
+            raise ValueError("HubertEncoder: freeze_backbone = False needs gradients through the backbone; the kernels are inference-only")
+        self.model_name, self.freeze_backbone, self.output_size = model_name, True, int(output_size)
+        if self.output_size < 1:
+            raise ValueError(f"HubertEncoder: output_size = {output_size} must be >= 1")
+        self._init_backbone(config, model_name)
+        H, O = self.hf_config["hidden_size"], self.output_size
+        self.post = nn.Sequential(nn.Conv1d(H, O, kernel_size=3, padding=1), nn.SiLU(), nn.Conv1d(O, O, stride=2, kernel_size=3, padding=1), nn.SiLU(),
+                                  nn.Conv1d(O, O, kernel_size=1))
+
+    @property
+    def post_channels(self) -> int:
+        return self.output_size
+
+    def frames(self, samples: int, backbone: bool = False) -> int:
+        """Frames that ``samples`` samples give after ``post`` (or after the backbone): HF's ``_get_feat_extract_output_lengths``, then
+        ``floor((F - 1) / 2) + 1``."""
+        f = self.conv_frames(samples)
+        return f if backbone else ((f - 1) // 2 + 1 if f > 0 else 0)
 
     # -- calls ---------------------------------------------------------------------------------
     def _run(self, x: torch.Tensor, lengths, want_hidden: bool, what: str):

@@ -250,6 +250,14 @@ def hubert_state_dict(cfg: dict, seed: int = 0) -> dict:
     return sd
 
 
+def mms_state_dict(cfg: dict, seed: int = 0) -> dict:
+    """State dict of the reference's MMSEncoder over ``Wav2Vec2Model(Wav2Vec2Config(**cfg))`` in the stable-layer-norm family, in the
+    reference's key order: ``model.`` + HF's keys and nothing else (the processor holds no tensor).  The backbone's weights are those of
+    ``hubert_state_dict(cfg, seed)``, whose ``post`` convs are drawn last and left out here."""
+    sd = hubert_state_dict(dict(cfg, output_size=cfg.get("output_size", 4)), seed)
+    return {k: v for k, v in sd.items() if not k.startswith("post.")}
+
+
 def istft_head_state_dict(cfg: dict, seed: int = 0, prefix: str = "") -> dict:
     """State dict for ISTFTHead(**cfg): ``out`` = Conv1d(dim, 2*n_fft, 1), ``istft.window`` = hann
     (/root/reference/fish_vocoder/modules/generators/vocos.py:33-41)."""
