@@ -18,22 +18,13 @@ import w2v_reference as wref
 from vocoder_amd import _lib
 from vocoder_amd import synthetic as syn
 from vocoder_amd.modules.encoders import HubertEncoder
+from w2v_cases import BAR, Handle, bits, mask_of, parity, same     # noqa: F401  (shared with test_gpu_w2v_shapes.py)
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = ("tiny", "shape")
-BAR = 1e-4
 EDGE_FRAMES = (1, 31, 32, 33, 127, 128, 129)       # around the attention's key tile (32) and query block (128)
-
-
-def bits(a) -> np.ndarray:
-    a = a.cpu().numpy() if torch.is_tensor(a) else a
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def same(a, b) -> bool:
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
 @functools.lru_cache(maxsize=None)
@@ -55,61 +46,6 @@ def module(name):
 def restated(name, row):
     cfg, sd, g = golden(name)
     return wref.forward(sd, cfg, g["waves"][row, : int(g["lengths"][row])])
-
-
-def mask_of(lengths, T):
-    return (torch.arange(T)[None, :] < torch.tensor(lengths)[:, None]).to(torch.int64).cuda()
-
-
-class Handle:
-    """A finalized fv_w2v with the calls the tests make on the C ABI."""
-
-    def __init__(self, cfg, sd, post):
-        self.cfg, self.post, self.L, self.h = cfg, post, _lib.lib(), ctypes.c_void_p()
-        n = len(cfg["conv_dim"])
-        arr = lambda v: (ctypes.c_int32 * 8)(*v, *([0] * (8 - n)))      # noqa: E731
-        c = _lib.W2VConfig(cfg["hidden_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"], cfg["intermediate_size"], n,
-                           arr(cfg["conv_dim"]), arr(cfg["conv_kernel"]), arr(cfg["conv_stride"]), cfg["num_conv_pos_embeddings"],
-                           cfg["num_conv_pos_embedding_groups"], post)
-        _lib.check(self.L.fv_w2v_create(ctypes.byref(c), ctypes.byref(self.h)))
-        for k, v in sd.items():
-            if not post and k.startswith("post."):
-                continue
-            a = np.ascontiguousarray(v, np.float32)
-            _lib.check(self.L.fv_w2v_load_weight(self.h, k.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                 (ctypes.c_int64 * max(a.ndim, 1))(*a.shape), a.ndim))
-        _lib.check(self.L.fv_w2v_finalize(self.h))
-
-    def frames(self, n, stage):
-        return int(self.L.fv_w2v_frames(self.h, n, stage))
-
-    def run(self, x, lengths, hidden=False, guard=0):
-        """x: (B, T) device tensor -> (out, hidden states or None, the workspace tensor with `guard` extra bytes after it)."""
-        B, T = x.shape
-        F, F2 = self.frames(T, 0), self.frames(T, 1)
-        H, nl = self.cfg["hidden_size"], self.cfg["num_hidden_layers"]
-        out = torch.full((B, self.post, F2) if self.post else (B, F, H), float("nan"), device="cuda")
-        hs = torch.full((nl + 1, B, F, H), float("nan"), device="cuda") if hidden else None
-        need = int(self.L.fv_w2v_workspace_bytes(self.h, B, T))
-        assert need > 0 and need % 4 == 0
-        ws = torch.full((need + guard,), 0xA5, dtype=torch.uint8, device="cuda")
-        lp = None if lengths is None else (ctypes.c_int32 * B)(*lengths)
-        _lib.check(self.L.fv_w2v_forward(self.h, x.data_ptr(), T, lp, B, out.data_ptr(), hs.data_ptr() if hidden else None, ws.data_ptr(), need,
-                                         int(torch.cuda.current_stream().cuda_stream)))
-        torch.cuda.synchronize()
-        return out, hs, ws
-
-    def close(self):
-        torch.cuda.synchronize()
-        self.L.fv_w2v_destroy(self.h)
-
-
-def parity(tag, got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    err = np.abs(got - want).max() / max(np.abs(want).max(), 1e-30)
-    print(f"{tag}: max |d| / peak = {err:.2e} (peak {np.abs(want).max():.3g})")
-    assert got.shape == want.shape and np.isfinite(got).all() and err <= BAR, (tag, err)
-    return err
 
 
 @pytest.mark.parametrize("name", FIXTURES)

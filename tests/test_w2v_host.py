@@ -1,6 +1,8 @@
 """Host (no GPU): the wav2vec2 / HuBERT encoder's surface (include/fishvoc.h fv_w2v_*, vocoder_amd/modules/encoders/hubert.py) — the declared
 entry points and the config mirror, the state dict's keys against the reference's recorded ones, the refusals that name their field, that
 nothing reaches for the network, the frame formula, and the float64 restatement (w2v_reference.py) against the reference's goldens.
+For the configs of the shape sweep (w2v_cases.py, run on the GPU by test_gpu_w2v_shapes.py), which have no golden: float32 arithmetic alone
+stays a factor of 10 under the parity bar, and the faults the sweep is there to catch move the restatement a factor of 10 above it.
 
 The 30-sample row of ``hubert_tiny`` gives TWO frames ((30 - 10) // 5 + 1 = 5, then (5 - 3) // 2 + 1 = 2), not the one frame its place in
 the fixture list was meant for; the fixture keeps it and carries a 24-sample row, which gives exactly one."""
@@ -16,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import w2v_cases as wc
 import w2v_reference as wref
 from vocoder_amd import _lib
 from vocoder_amd import synthetic as syn
@@ -25,7 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden")
 FIXTURES = ("tiny", "shape")
 ENTRIES = ("fv_w2v_create", "fv_w2v_load_weight", "fv_w2v_finalize", "fv_w2v_frames", "fv_w2v_workspace_bytes", "fv_w2v_forward", "fv_w2v_destroy")
-BAR = 1e-4      # the project's parity bar: max |d| over the expected tensor's own peak
+BAR = wc.BAR     # the project's parity bar: max |d| over the expected tensor's own peak
 POS = "model.encoder.pos_conv_embed.conv."
 
 
@@ -308,3 +311,76 @@ def test_restatement_against_the_references_goldens(name):
             err = np.abs(got - want).max() / np.abs(want).max()
             print(f"hubert_{name} row {b} {key}: fp64 restatement vs the reference's fp32, max |d| / peak = {err:.2e}")
             assert got.shape == want.shape and err <= BAR
+
+
+def moved(want, got) -> float:
+    return float(np.abs(got - want).max() / np.abs(want).max())
+
+
+@pytest.mark.parametrize("name,F", wc.SWEEP_CASES)
+def test_float32_arithmetic_alone_stays_a_tenth_of_the_bar_at_every_sweep_config(name, F):
+    """A condition on the sweep's inputs: the restatement evaluated in float32 lies within BAR / 10 of the float64 one's peak in every hidden
+    state, the normed state and the output, so a kernel in exact fp32 has a factor of 10 of room under the bar.  A config that breaks it gets
+    another seed or scale, not another condition."""
+    cfg = wc.SWEEP[name][0]
+    want = wc.sweep_restated(name, F)
+    got = wref.forward(wc.sweep_state_dict(name), cfg, wc.sweep_wave(name, F), dtype=np.float32)
+    assert want["hidden_states"].dtype == np.float64 and want["hidden_states"].shape == (cfg["num_hidden_layers"] + 1, F, cfg["hidden_size"])
+    assert want["out"].shape == (cfg["output_size"], (F - 1) // 2 + 1)
+    pairs = [(f"hidden state {i}", got["hidden_states"][i], want["hidden_states"][i]) for i in range(cfg["num_hidden_layers"] + 1)]
+    pairs += [(k, got[k], want[k]) for k in ("last_hidden_state", "out")]
+    for key, g, w in pairs:
+        err = moved(w, g)
+        print(f"{name} {F} frames {key}: float32 restatement vs float64, max |d| / peak = {err:.2e}")
+        assert g.dtype == np.float32 and g.shape == w.shape and err <= BAR / 10, (key, err)
+
+
+def altered(name, key, index):
+    """The restatement of the sweep's first row of `name` with sd[key][index] zeroed."""
+    cfg, Fs = wc.SWEEP[name]
+    sd = wc.sweep_state_dict(name)
+    w = sd[key].copy()
+    assert np.abs(w[index]).min() > 0
+    w[index] = 0
+    return wc.sweep_restated(name, Fs[0]), wref.forward(dict(sd, **{key: w}), cfg, wc.sweep_wave(name, Fs[0]))
+
+
+@pytest.mark.parametrize("name", ("large", "base", "odd"))
+def test_a_dropped_k_tail_tap_or_quad_moves_the_next_state_ten_bars(name):
+    """What a kernel that drops the last four k of a product, one tap of a conv or the last quad of a LayerNorm row would compute, stated as
+    altered weights of the float64 restatement: the first state downstream moves by more than 10 BAR of its peak, so a sweep case that passes
+    at the bar has excluded it."""
+    cfg = wc.SWEEP[name][0]
+    last, nc = cfg["num_hidden_layers"] - 1, len(cfg["conv_dim"])
+    tail = (slice(None), slice(-4, None))
+    cases = [("the projection's last four k", "model.feature_projection.projection.weight", tail, lambda o: o["hidden_states"][0]),
+             ("the second FFN product's last four k", f"model.encoder.layers.{last}.feed_forward.output_dense.weight", tail,
+              lambda o: o["hidden_states"][last + 1]),
+             ("the final LayerNorm's last four gammas", "model.encoder.layer_norm.weight", slice(-4, None), lambda o: o["last_hidden_state"])]
+    for l in range(nc):
+        cases.append((f"the last tap of channel 5 of conv layer {l}", f"model.feature_extractor.conv_layers.{l}.conv.weight",
+                      (5, slice(None), cfg["conv_kernel"][l] - 1), lambda o: o["hidden_states"][0]))
+    for what, key, index, state in cases:
+        want, got = altered(name, key, index)
+        err = moved(state(want), state(got))
+        print(f"{name}: {what} zeroed moves the next state by {err:.2e} of its peak")
+        assert err > 10 * BAR, (what, err)
+
+
+@pytest.mark.parametrize("name", ("large", "base"))
+def test_one_zeroed_element_of_q_proj_moves_the_output_a_bar(name):
+    cfg = wc.SWEEP[name][0]
+    for layer in (0, cfg["num_hidden_layers"] - 1):
+        want, got = altered(name, f"model.encoder.layers.{layer}.attention.q_proj.weight", (0, 0))
+        err = moved(want["out"], got["out"])
+        print(f"{name}: q_proj.weight[0, 0] of layer {layer} zeroed moves the output by {err:.2e} of its peak")
+        assert err > BAR, (layer, err)
+
+
+def test_the_restatement_in_float64_is_the_default_and_float32_is_float32_throughout():
+    cfg, seed, g = golden("tiny")
+    sd, wave = syn.hubert_state_dict(cfg, seed), g["waves"][1, : int(g["lengths"][1])]
+    a, b = restated("tiny", 1), wref.forward(sd, cfg, wave, dtype=np.float64)
+    assert all(v.dtype == np.float64 and np.array_equal(v, b[k]) for k, v in a.items())
+    c = wref.forward(sd, cfg, wave, dtype=np.float32)
+    assert all(v.dtype == np.float32 for v in c.values()) and 0 < moved(a["out"], c["out"]) <= BAR / 10

@@ -1,5 +1,7 @@
 """Float64 numpy restatement of the reference's HubertEncoder (modules/encoders/hubert.py over HF's HubertModel, stable-layer-norm family) for
-ONE unpadded row, with every hidden state.  The host tests pin it to the goldens; the GPU tests hold the kernels to it where no golden exists."""
+ONE unpadded row, with every hidden state.  The host tests pin it to the goldens; the GPU tests hold the kernels to it where no golden exists.
+``forward(..., dtype=np.float32)`` evaluates the same statements in float32 (erf and the fold of the positional conv's weight norm included,
+each rounded to float32): the host tests use it to show how far float32 arithmetic alone moves a result."""
 from __future__ import annotations
 
 from math import erf
@@ -11,7 +13,7 @@ _POS = "model.encoder.pos_conv_embed.conv."
 
 
 def gelu(x):
-    return 0.5 * x * (1.0 + _erf(x / np.sqrt(2.0)))
+    return 0.5 * x * (1.0 + _erf(x / x.dtype.type(np.sqrt(2.0))).astype(x.dtype, copy=False))
 
 
 def silu(x):
@@ -31,10 +33,10 @@ def conv1d(x, w, b, stride=1, pad=0, groups=1):
     x = np.pad(x, ((0, 0), (pad, pad)))
     n = (x.shape[1] - k) // stride + 1
     if n <= 0:
-        return np.zeros((cout, 0))
+        return np.zeros((cout, 0), x.dtype)
     idx = np.arange(n)[:, None] * stride + np.arange(k)[None, :]
     og = cout // groups
-    out = np.empty((cout, n))
+    out = np.empty((cout, n), x.dtype)
     for g in range(groups):
         win = x[g * cg:(g + 1) * cg][:, idx]                    # (cg, n, k)
         out[g * og:(g + 1) * og] = np.einsum("cnk,ock->on", win, w[g * og:(g + 1) * og])
@@ -48,17 +50,17 @@ def frames(cfg: dict, samples: int, backbone: bool = False) -> int:
     return f if backbone else ((f - 1) // 2 + 1 if f > 0 else 0)
 
 
-def pos_conv_weight(sd: dict) -> np.ndarray:
-    g = np.asarray(sd[_POS + "parametrizations.weight.original0"], np.float64)
-    v = np.asarray(sd[_POS + "parametrizations.weight.original1"], np.float64)
+def pos_conv_weight(sd: dict, dtype=np.float64) -> np.ndarray:
+    g = np.asarray(sd[_POS + "parametrizations.weight.original0"], dtype)
+    v = np.asarray(sd[_POS + "parametrizations.weight.original1"], dtype)
     return g * v / np.sqrt((v ** 2).sum((0, 1), keepdims=True))
 
 
-def forward(sd: dict, cfg: dict, wave: np.ndarray) -> dict:
-    """wave: (T,) -> dict(hidden_states (L + 1, F, H), last_hidden_state (F, H), out (O, F_post))."""
-    p = {k: np.asarray(v, np.float64) for k, v in sd.items()}
+def forward(sd: dict, cfg: dict, wave: np.ndarray, dtype=np.float64) -> dict:
+    """wave: (T,) -> dict(hidden_states (L + 1, F, H), last_hidden_state (F, H), out (O, F_post)), every statement evaluated in ``dtype``."""
+    p = {k: np.asarray(v, dtype) for k, v in sd.items()}
     heads = cfg["num_attention_heads"]
-    x = np.asarray(wave, np.float64)[None, :]
+    x = np.asarray(wave, dtype)[None, :]
     for i in range(len(cfg["conv_dim"])):
         pfx = f"model.feature_extractor.conv_layers.{i}."
         x = conv1d(x, p[pfx + "conv.weight"], p[pfx + "conv.bias"], stride=cfg["conv_stride"][i])
@@ -67,7 +69,7 @@ def forward(sd: dict, cfg: dict, wave: np.ndarray) -> dict:
     h = h @ p["model.feature_projection.projection.weight"].T + p["model.feature_projection.projection.bias"]
     F, H = h.shape
     k = cfg["num_conv_pos_embeddings"]
-    pos = conv1d(h.T, pos_conv_weight(sd), p[_POS + "bias"], pad=k // 2, groups=cfg["num_conv_pos_embedding_groups"])[:, :F]   # SamePad
+    pos = conv1d(h.T, pos_conv_weight(sd, dtype), p[_POS + "bias"], pad=k // 2, groups=cfg["num_conv_pos_embedding_groups"])[:, :F]   # SamePad
     h = h + gelu(pos).T
     hidden = [h]
     d = H // heads
