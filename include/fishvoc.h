@@ -737,6 +737,70 @@ FV_API void fv_wavpool_destroy(fv_wavpool* p);
  *          pinned by its host test.) -------- */
 FV_API fv_status fv_global_resample_create(const fv_resample_config* cfg, fv_resample** out);
 
+/* -------- sample-rate conversion, per session: the resampler as a pool of sessions that advance independently — what fv_wavpool_* is to
+ *          fv_logmel_stream_*, for fv_resample_stream_*.  No reference counterpart: test.py:54 / hq_pitch_shift.py:33 resample whole clips and
+ *          keep no per-session state.  (Named fv_respool_*, outside the fv_resample_ prefix: that family's list of entries is pinned by its
+ *          host test.)  --------
+ *
+ * A resample pool holds S slots on one fv_resample (either table form; one pool is one rate pair).  Each slot has its own counters N (input
+ * samples received) and E (outputs emitted), its own flushed flag and its own H = Kp rounded up to 4 carried samples.  A step is a list of
+ * fv_wavpool_item (session, samples, flush): any subset of the slots, each at most once, each with its own chunk size.  Per item, the
+ * stream's push and flush folded into one call, with M(N) the emission rule of fv_resample_stream_push:
+ *   N' = N + samples;  E' = flush ? ceil(n N' / o) : max(E, M(N'));  the item emits the outputs [E, E').
+ * With flush the rest comes out against zeros and the slot refuses items (FV_ERR_STATE) until fv_respool_reset; a flush at N' = 0 emits
+ * nothing.  The whole step is checked before any counter moves or anything is enqueued: a refused step leaves every slot as it was.  One step
+ * is one FIR launch and one carry launch per 32 items; the items' table entries (chunk row, slot and carry buffer, origins, first output,
+ * count) travel in the kernel arguments.  An item's workgroups stage their input tiles from the slot's carried samples and from its chunk
+ * row, and every output is the sum fv_resample_forward forms — ascending taps, one fp32 accumulator, fused multiply-adds — so a session's
+ * concatenated outputs are bit-identical to fv_resample_forward over its whole utterance and to an fv_resample_stream fed the same chunks,
+ * whatever the other sessions do.  The entries enqueue eagerly. */
+typedef struct fv_respool fv_respool;
+
+/* The pool's only device allocation, made here on the current HIP device (test.py:54 / hq_pitch_shift.py:33 keep no state) and freed by
+ * fv_respool_destroy: two (S, H) carry buffers; every slot has its own bit saying which of the two holds its samples, and only a slot that
+ * pushed samples flips it.  sessions outside [1, 65535] or max_chunk outside [1, 2^28]: FV_ERR_INVALID. */
+FV_API fv_status fv_respool_create(fv_resample* r, int32_t sessions, int32_t max_chunk, fv_respool** out);
+/* The most one item can emit in one step (the length that test.py:54 / hq_pitch_shift.py:33 get for a whole clip never enters): a push of
+ * max_chunk samples that also flushes.  Between flushes E = M(N), so such a step emits g(N) = ceil(n (N + max_chunk) / o) - M(N).  M jumps at
+ * the N at which a band ends, N = f o + first[p] + count[p] - width, n times per o samples, and ceil() never falls: g is largest just before
+ * a jump.  From N >= first[n - 1] + count[n - 1] - width - o on, M(N + o) = M(N) + n, and before that M is clamped at 0 from below, so g is
+ * periodic there and no larger before: the result is the largest g(f o + first[p] + count[p] - width - 1) over the n phases of one frame f
+ * past that point.  Exact: some state attains it.  An out_cols of this size serves every step.  0 for a NULL pool. */
+FV_API int64_t fv_respool_max_outputs(const fv_respool* p);
+/* N of one slot: the input samples of the current utterance (the clip of test.py:54 / hq_pitch_shift.py:33) received so far; 0 for a session
+ * outside [0, S). */
+FV_API int64_t fv_respool_received(const fv_respool* p, int32_t session);
+/* E of one slot: the outputs (samples of what test.py:54 / hq_pitch_shift.py:33 return) emitted so far; 0 for a session outside [0, S). */
+FV_API int64_t fv_respool_emitted(const fv_respool* p, int32_t session);
+/* ceil(n N / o) - E of one slot: the outputs a flush would emit now (the tail of test.py:54 / hq_pitch_shift.py:33's result); 0 for a session
+ * outside [0, S). */
+FV_API int64_t fv_respool_pending(const fv_respool* p, int32_t session);
+/* Pure host (no GPU), as fv_wavpool_plan is: what a step would emit, from the filter design alone (what test.py:54 / hq_pitch_shift.py:33
+ * leave to their libraries).  received / emitted / flushed: the S counters and flags (flushed may be NULL: none is).  Designs the filter,
+ * writes E' - E of every item to outputs_out (count entries) and returns the largest of them; nothing is changed: the caller moves the
+ * counters.  Refuses what fv_respool_step refuses of the items, each named in fv_last_error, with the status as the (negative) result: a
+ * session outside [0, S), a duplicate session, samples outside [0, max_chunk], more than 2^40 samples (FV_ERR_INVALID); an item for a flushed
+ * session (FV_ERR_STATE); a config that fv_resample_design refuses, sessions outside [1, 65535] or max_chunk outside [1, 2^28]. */
+FV_API int64_t fv_respool_plan(const fv_resample_config* cfg, int32_t sessions, int32_t max_chunk, const int64_t* received,
+                               const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
+                               int64_t* outputs_out);
+/* One step (replaces one test.py:54 / hq_pitch_shift.py:33 call per clip, for sessions whose audio arrives at different times).  d_chunks:
+ * (count, chunk_stride) fp32, row i holding item i's samples first — the rest of the row (NaN included) is never loaded; NULL when no item
+ * has samples.  d_out: (count, out_stride) fp32 with out_stride >= out_cols >= the largest E' - E of the step (NULL when out_cols is 0): the
+ * first out_cols columns of row i receive item i's outputs and exactly 0.0f after them, an item that emits nothing a row of zeros; every one
+ * of them is written.  outputs_out (may be NULL): count entries, E' - E of every item.  Refusals, checked for the whole step before anything
+ * moves, each naming the item and the session: those of fv_respool_plan, a NULL chunk buffer although an item has samples, chunk_stride
+ * shorter than the longest chunk, out_cols below the largest E' - E, out_stride < out_cols, a NULL d_out although an item emits
+ * (FV_ERR_INVALID).  No device allocation, no copy, no host synchronisation.  Asynchronous on `stream`; steps of one pool must be ordered. */
+FV_API fv_status fv_respool_step(fv_respool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                 float* d_out, int64_t out_stride, int32_t out_cols, int64_t* outputs_out, void* stream);
+/* N = E = 0 and not flushed for one slot: its next utterance (the next clip of test.py:54 / hq_pitch_shift.py:33).  The carry is kept:
+ * samples before 0 are zeros by index, whatever it holds.  A session outside [0, S): FV_ERR_INVALID. */
+FV_API fv_status fv_respool_reset(fv_respool* p, int32_t session);
+/* Frees the carry (call it before fv_resample_destroy of its resampler, once the pool's work has finished); test.py:54 /
+ * hq_pitch_shift.py:33 have nothing to free. */
+FV_API void fv_respool_destroy(fv_respool* p);
+
 /* -------- pitch shift: `librosa.effects.pitch_shift(gt_y, sr=sr, n_steps=cfg.pitch_shift)` (test.py:61-62), the step between loading /
  *          resampling a file and the mel front-end.  librosa is not a dependency; its arithmetic is restated: a time stretch by
  *          rate = 2^(-n_steps / bins_per_octave) with a phase vocoder (stft, n_fft 2048, hop n_fft / 4, periodic hann, center=True with zero

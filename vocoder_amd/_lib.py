@@ -57,6 +57,8 @@ EXPORTS = (
     "fv_wavpool_create", "fv_wavpool_workspace_bytes", "fv_wavpool_max_frames", "fv_wavpool_received_samples", "fv_wavpool_emitted_frames",
     "fv_wavpool_pending_samples", "fv_wavpool_plan", "fv_wavpool_step", "fv_wavpool_reset", "fv_wavpool_destroy",
     "fv_global_resample_create",
+    "fv_respool_create", "fv_respool_max_outputs", "fv_respool_received", "fv_respool_emitted", "fv_respool_pending", "fv_respool_plan",
+    "fv_respool_step", "fv_respool_reset", "fv_respool_destroy",
     "fv_pitch_shift_plan", "fv_pitch_shift_lengths", "fv_pitch_shift_create", "fv_pitch_shift_destroy", "fv_pitch_shift_workspace_bytes",
     "fv_pitch_shift_stretch", "fv_pitch_shift_forward",
     "fv_pv_stream_ready", "fv_pv_set_batch_invariant", "fv_pv_stream_create", "fv_pv_stream_workspace_bytes", "fv_pv_stream_pending",
@@ -398,6 +400,21 @@ def lib() -> ctypes.CDLL:
     L.fv_wavpool_destroy.restype = None
     L.fv_global_resample_create.argtypes = [rcp, ctypes.POINTER(vp)]
     L.fv_global_resample_create.restype = _i32
+    L.fv_respool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_respool_create.restype = _i32
+    L.fv_respool_max_outputs.argtypes = [vp]
+    L.fv_respool_max_outputs.restype = i64
+    for name in ("fv_respool_received", "fv_respool_emitted", "fv_respool_pending"):
+        getattr(L, name).argtypes = [vp, _i32]
+        getattr(L, name).restype = i64
+    L.fv_respool_plan.argtypes = [rcp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
+    L.fv_respool_plan.restype = i64
+    L.fv_respool_step.argtypes = [vp, wip, _i32, vp, i64, vp, i64, _i32, i64p, vp]
+    L.fv_respool_step.restype = _i32
+    L.fv_respool_reset.argtypes = [vp, _i32]
+    L.fv_respool_reset.restype = _i32
+    L.fv_respool_destroy.argtypes = [vp]
+    L.fv_respool_destroy.restype = None
     pcp = ctypes.POINTER(PitchShiftConfig)
     L.fv_pitch_shift_plan.argtypes = [pcp, i32p, i32p, i32p]
     L.fv_pitch_shift_plan.restype = _i32

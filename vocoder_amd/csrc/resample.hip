@@ -1,6 +1,7 @@
 // Sample-rate conversion (fv_resample_*, include/fishvoc.h): the polyphase windowed-sinc resampler of torchaudio.transforms.Resample as a banded
-// FIR on the vector ALU.  Host: the filter design in float64 (fv_resample_design, no GPU), the object, the stream.  Device: one kernel body in two forms
-// (table staged in LDS / read from global memory).
+// FIR on the vector ALU.  Host: the filter design in float64 (fv_resample_design, no GPU), the object, the stream, the pool of sessions
+// (fv_respool_*).  Device: one kernel body for whole rows and one for a pool's items, each in two forms (table staged in LDS / read from global
+// memory), around one output loop.
 //
 // Output m = f n + p reads x[f o + first[p] - width + i], i < count[p] (count <= Kp: 13 taps for 44100 -> 48000, 73 for 48000 -> 8000), where the
 // dense form of the reference holds 2 width + o = 161 ... 475 taps per output, all but the band zero: an MFMA GEMM over the dense form would do
@@ -21,7 +22,7 @@
 #include <numeric>
 #include <vector>
 
-#include "sample_stream.h"
+#include "sample_pool.h"
 
 namespace fv {
 namespace {
@@ -78,6 +79,38 @@ struct TablePtr<true> {
     using F = const float* __restrict__;
 };
 
+// The outputs [m_lo, m_hi) of one tile, lane `tid` taking every kResThreads-th: the sum of every kernel in this file, whole rows and pools alike.
+// s_x[0] is the input sample X - width - shift of the row; outputs from M_b on are zeros (a ragged row's tail); yr[m] is where output m goes.
+template <bool kGlobalTable>
+__device__ __forceinline__ void resample_tile_outputs(typename TablePtr<kGlobalTable>::I s_first, typename TablePtr<kGlobalTable>::I s_count,
+                                                      typename TablePtr<kGlobalTable>::F s_taps, const float* s_x, int n, int o, int kpad,
+                                                      long long X, int shift, long long m_lo, long long m_hi, long long M_b, float* yr, int tid) {
+    long long m = m_lo + tid;
+    if (m >= m_hi) return;
+    const long long f0 = m / n;
+    int ph = (int)(m - f0 * n);
+    int base = (int)(f0 * o - X) + shift;             // LDS index of the sample f o - width
+    const int dp = kResThreads % n, db = (kResThreads / n) * o;
+    for (; m < m_hi; m += kResThreads) {
+        float acc = 0.f;
+        if (m < M_b) {
+            const float* xs = s_x + base + s_first[ph];
+            const float* tp = s_taps + ph * kpad;
+            const int cnt = s_count[ph];
+            // (unrolled by four so that the LDS reads of four taps are in flight together; the sum stays one ascending chain)
+#pragma unroll 4
+            for (int i = 0; i < cnt; ++i) acc = fmaf(tp[i], xs[i], acc);
+        }
+        yr[m] = acc;
+        ph += dp;
+        base += db;
+        if (ph >= n) {
+            ph -= n;
+            base += o;
+        }
+    }
+}
+
 // kGlobalTable: first[], count[] and the taps are read where they lie, in global memory (fv_global_resample_create: a table of any size, served
 // by L2), and LDS holds the input tile alone.  Tiling, indices and the sum of an output are the same statements in both forms.
 template <bool kGlobalTable>
@@ -124,35 +157,100 @@ __device__ __forceinline__ void resample_body(const ResampleParams& p) {
 
     const long long m_lo = tile == 0 ? p.m_begin : max(p.m_begin, count_below(s_first, p.n, p.o, X));
     const long long m_hi = tile == p.ntiles - 1 ? p.m_end : min(p.m_end, count_below(s_first, p.n, p.o, X + kResTile));
-    long long m = m_lo + tid;
-    if (m >= m_hi) return;
-    const long long f0 = m / p.n;
-    int ph = (int)(m - f0 * p.n);
-    int base = (int)(f0 * p.o - X) + shift;           // LDS index of the sample f o - width
-    const int dp = kResThreads % p.n, db = (kResThreads / p.n) * p.o;
-    float* yr = p.y + row * p.y_stride - p.m_begin;
-    for (; m < m_hi; m += kResThreads) {
-        float acc = 0.f;
-        if (m < M_b) {
-            const float* xs = s_x + base + s_first[ph];
-            const float* tp = s_taps + ph * p.kpad;
-            const int cnt = s_count[ph];
-            // (unrolled by four so that the LDS reads of four taps are in flight together; the sum stays one ascending chain)
-#pragma unroll 4
-            for (int i = 0; i < cnt; ++i) acc = fmaf(tp[i], xs[i], acc);
-        }
-        yr[m] = acc;
-        ph += dp;
-        base += db;
-        if (ph >= p.n) {
-            ph -= p.n;
-            base += p.o;
-        }
-    }
+    resample_tile_outputs<kGlobalTable>(s_first, s_count, s_taps, s_x, p.n, p.o, p.kpad, X, shift, m_lo, m_hi, M_b,
+                                        p.y + row * p.y_stride - p.m_begin, tid);
 }
 
 __global__ __launch_bounds__(kResThreads) void resample_kernel(const ResampleParams p) { resample_body<false>(p); }
 __global__ __launch_bounds__(kResThreads) void resample_global_kernel(const ResampleParams p) { resample_body<true>(p); }
+
+// ---------------------------------------------------------------------------------------------
+// The pool form (fv_respool_step): one launch serves up to kSamplePoolBlock items, each a session with its own counters.  blockIdx.y picks the
+// item's entry (by value, fv_internal.h: first = E, count = E' - E, carry_origin = N - H, chunk_origin = N, avail = N'), blockIdx.x its tile:
+// entry k owns the tiles of [s(E), s(E' - 1)], split as resample_run splits a row's, and finds X0 = s(first) and its own tile count from first[]
+// (read from global memory: the LDS copy is not staged yet).  The grid is as wide as the block's largest tile count; a workgroup past its
+// entry's last tile only stores its share of the zero tail.  A tile's samples come from two places: sample j >= chunk_origin from
+// chunk[item][j - chunk_origin], 0 <= j < chunk_origin from the slot's carry buf[bit][slot][j - carry_origin], and j < 0 or j >= avail is 0.0f and
+// never loaded.  fv_respool_step has checked that no output of the step reads below carry_origin; the up to three samples that only the
+// 16-byte alignment puts in front of the first tile are staged as zeros rather than loaded.
+// ---------------------------------------------------------------------------------------------
+struct ResamplePoolParams {
+    const float* chunk;        // (items, chunk_stride); NULL when no entry's chunk holds a sample
+    const float* buf0;         // the pool's two (S, H) carry buffers
+    const float* buf1;
+    float* y;                  // (items, y_stride): columns [0, out_cols) of an entry's row are written
+    const uint32_t* table;
+    long long chunk_stride, y_stride, H;
+    int out_cols, max_tiles;
+    int o, n, width, kpad, table_dwords, sx;
+};
+
+template <bool kGlobalTable>
+__device__ __forceinline__ void resample_pool_body(const ResamplePoolParams& p, const SamplePoolBlock& tab) {
+    extern __shared__ __align__(16) uint32_t smem[];
+    const uint32_t* table = kGlobalTable ? p.table : smem;
+    const typename TablePtr<kGlobalTable>::I s_first = (const int*)table;
+    const typename TablePtr<kGlobalTable>::I s_count = s_first + p.n;
+    const typename TablePtr<kGlobalTable>::F s_taps = (const float*)(s_count + p.n);
+    float* s_x = (float*)(smem + (kGlobalTable ? 0 : p.table_dwords));
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x;
+    const SamplePoolEntry e = tab.e[blockIdx.y];
+    float* yrow = p.y + (long long)e.item * p.y_stride;
+
+    // the zero tail [count, out_cols) of the row, shared among the max_tiles workgroups of the entry
+    for (long long c = e.count + (long long)tile * kResThreads + tid; c < p.out_cols; c += (long long)p.max_tiles * kResThreads) yrow[c] = 0.f;
+    if (e.count <= 0) return;
+
+    const int* g_first = (const int*)p.table;
+    const long long m_begin = e.first, m_end = e.first + e.count;
+    const long long X0 = (m_begin / p.n) * p.o + g_first[m_begin % p.n];
+    const long long X_last = ((m_end - 1) / p.n) * p.o + g_first[(m_end - 1) % p.n];
+    const int ntiles = (int)((X_last - X0) / kResTile) + 1;
+    if (tile >= ntiles) return;
+
+    if (!kGlobalTable)
+        for (int q = tid; q < p.table_dwords / 4; q += kResThreads) ((uint4*)smem)[q] = ((const uint4*)p.table)[q];
+
+    const long long X = X0 + (long long)tile * kResTile;
+    const long long j0 = X - p.width;                 // the first sample this tile reads
+    const long long chunk_len = e.avail - e.chunk_origin;
+    const float* cr = chunk_len > 0 ? p.chunk + (long long)e.item * p.chunk_stride : nullptr;
+    const float* carry = (e.bit ? p.buf1 : p.buf0) + (long long)e.slot * p.H;
+    const int mis = (int)((reinterpret_cast<uintptr_t>(cr) >> 2) & 3);   // the chunk row's own offset from a 16-byte boundary, in floats
+    const int shift = (int)((j0 - e.chunk_origin + mis) & 3);
+    const long long js = j0 - shift;                  // ... moved down so that cr + (js - chunk_origin) lies on a 16-byte boundary of memory
+    const long long lo = max(0LL, e.carry_origin);    // samples [lo, chunk_origin) are carried, [chunk_origin, avail) lie in the chunk
+    auto sample = [&](long long j) -> float {
+        if (j < lo || j >= e.avail) return 0.f;
+        return j >= e.chunk_origin ? cr[j - e.chunk_origin] : carry[j - e.carry_origin];
+    };
+    for (int q = tid; q < p.sx / 4; q += kResThreads) {
+        const long long j = js + 4 * q;
+        float4 v;
+        if (j >= e.chunk_origin && j + 4 <= e.avail) {
+            v = *(const float4*)(cr + (j - e.chunk_origin));
+        } else {
+            v.x = sample(j);
+            v.y = sample(j + 1);
+            v.z = sample(j + 2);
+            v.w = sample(j + 3);
+        }
+        ((float4*)s_x)[q] = v;
+    }
+    __syncthreads();
+
+    const long long m_lo = tile == 0 ? m_begin : max(m_begin, count_below(s_first, p.n, p.o, X));
+    const long long m_hi = tile == ntiles - 1 ? m_end : min(m_end, count_below(s_first, p.n, p.o, X + kResTile));
+    resample_tile_outputs<kGlobalTable>(s_first, s_count, s_taps, s_x, p.n, p.o, p.kpad, X, shift, m_lo, m_hi, m_end, yrow - m_begin, tid);
+}
+
+__global__ __launch_bounds__(kResThreads) void resample_pool_kernel(const ResamplePoolParams p, const SamplePoolBlock tab) {
+    resample_pool_body<false>(p, tab);
+}
+__global__ __launch_bounds__(kResThreads) void resample_pool_global_kernel(const ResamplePoolParams p, const SamplePoolBlock tab) {
+    resample_pool_body<true>(p, tab);
+}
 
 constexpr double kKaiserBeta = 14.769656459379492;
 
@@ -545,5 +643,192 @@ FV_API fv_status fv_resample_stream_reset(fv_resample_stream* s) {
 }
 
 FV_API void fv_resample_stream_destroy(fv_resample_stream* s) { delete s; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// The pool (fv_respool_*): the sample pool's counters and carry (sample_pool.h) around resample_pool_kernel.
+// ---------------------------------------------------------------------------------------------
+struct fv_respool : SamplePool {
+    fv_resample* r = nullptr;
+    long long max_out = 0;      // fv_respool_max_outputs
+};
+
+// the host half of resample_create: the design's sizes and end[], enough for out_len / emit_count / s_of (fv_respool_plan)
+static fv_status resample_rule(const fv_resample_config* cfg, const char* fn, fv_resample& r) {
+    if (const fv_status st = design(cfg, fn, r.d, false)) return st;
+    r.cfg = *cfg;
+    r.end.resize((size_t)r.d.n);
+    for (int p = 0; p < r.d.n; ++p) r.end[(size_t)p] = r.d.first[(size_t)p] + r.d.count[(size_t)p];
+    return FV_OK;
+}
+
+// The emission rule of one step, after the pool's admit: E2[i] = flush ? out_len(N2) : max(E, emit_count(N2)).
+static void respool_emission(const fv_resample& r, const int64_t* emitted, const fv_wavpool_item* items, int count, const long long* N2,
+                             long long* E2) {
+    for (int i = 0; i < count; ++i) {
+        const long long E = emitted[items[i].session];
+        E2[i] = items[i].flush ? std::max(E, r.out_len(N2[i])) : std::max(E, r.emit_count(N2[i]));
+    }
+}
+
+// The most one item emits in one step (the derivation: include/fishvoc.h): g(N) = out_len(N + max_chunk) - emit_count(N) just before each of
+// the n jumps of emit_count in one period of o samples, past the point from which emit_count is periodic.
+static long long respool_max_outputs(const fv_resample& r, int max_chunk) {
+    const Design& d = r.d;
+    long long best = 0;
+    for (int p = 0; p < d.n; ++p) {
+        const long long N = 2LL * d.o + r.end[(size_t)p] - d.width - 1;   // frame 2: end[0] >= end[n - 1] - o, so N >= end[n - 1] - width - o
+        best = std::max(best, r.out_len(N + max_chunk) - r.emit_count(N));
+    }
+    return best;
+}
+
+static fv_status respool_range(const char* fn, int sessions, int max_chunk) {
+    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
+        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+
+extern "C" {
+
+FV_API fv_status fv_respool_create(fv_resample* r, int32_t sessions, int32_t max_chunk, fv_respool** out) {
+    const char* fn = "fv_respool_create";
+    if (out) *out = nullptr;
+    if (!r || !out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::unique_ptr<fv_respool> p(new fv_respool());
+    p->r = r;
+    const int H = (r->d.kp + 3) / 4 * 4;   // an output not yet emitted starts less than Kp samples before N (fv_resample_stream_create)
+    if (const fv_status rs = p->create(fn, sessions, max_chunk, H)) return rs;
+    p->max_out = respool_max_outputs(*r, max_chunk);
+    *out = p.release();
+    return FV_OK;
+}
+
+FV_API int64_t fv_respool_max_outputs(const fv_respool* p) { return p ? p->max_out : 0; }
+
+FV_API int64_t fv_respool_received(const fv_respool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+
+FV_API int64_t fv_respool_emitted(const fv_respool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+
+FV_API int64_t fv_respool_pending(const fv_respool* p, int32_t s) {
+    return p && s >= 0 && s < p->S ? p->r->out_len(p->N[(size_t)s]) - p->E[(size_t)s] : 0;
+}
+
+FV_API int64_t fv_respool_plan(const fv_resample_config* cfg, int32_t sessions, int32_t max_chunk, const int64_t* received,
+                               const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
+                               int64_t* outputs_out) {
+    const char* fn = "fv_respool_plan";
+    fv_resample r;
+    if (const fv_status st = resample_rule(cfg, fn, r)) return st;
+    if (const fv_status st = respool_range(fn, sessions, max_chunk)) return st;
+    if (!received || !emitted || (count > 0 && !outputs_out)) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk, received, flushed, items, count, false, nullptr, 0, N2.data()))
+        return rs;
+    respool_emission(r, emitted, items, count, N2.data(), E2.data());
+    int64_t k_max = 0;
+    for (int i = 0; i < count; ++i) {
+        outputs_out[i] = E2[(size_t)i] - emitted[items[i].session];
+        k_max = std::max(k_max, outputs_out[i]);
+    }
+    return k_max;
+}
+
+FV_API fv_status fv_respool_step(fv_respool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                 float* d_out, int64_t out_stride, int32_t out_cols, int64_t* outputs_out, void* stream) {
+    const char* fn = "fv_respool_step";
+    if (!p) {
+        set_error("%s: null pool", fn);
+        return FV_ERR_INVALID;
+    }
+    for (int i = 0; outputs_out && i < count; ++i) outputs_out[i] = 0;
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status rs = p->admit(fn, "fv_respool_reset", items, count, d_chunks, chunk_stride, N2.data())) return rs;
+    const fv_resample* r = p->r;
+    respool_emission(*r, p->E.data(), items, count, N2.data(), E2.data());
+    long long k_max = 0;
+    int k_item = 0;
+    for (int i = 0; i < count; ++i) {
+        const long long k = E2[(size_t)i] - p->E[(size_t)items[i].session];
+        if (k > k_max) k_max = k, k_item = i;
+    }
+    const int k_session = count > 0 ? items[k_item].session : -1;
+    if (out_cols < k_max || out_cols < 0) {
+        set_error("%s: out_cols = %d, but item %d (session %d) emits %lld outputs in this step", fn, out_cols, k_item, k_session, k_max);
+        return FV_ERR_INVALID;
+    }
+    if (out_stride < out_cols) {
+        set_error("%s: out_stride = %lld is shorter than out_cols = %d (item %d, session %d, emits %lld outputs)", fn, (long long)out_stride,
+                  out_cols, k_item, k_session, k_max);
+        return FV_ERR_INVALID;
+    }
+    if (k_max > 0 && !d_out) {
+        set_error("%s: null output although item %d (session %d) emits %lld outputs", fn, k_item, k_session, k_max);
+        return FV_ERR_INVALID;
+    }
+    // one table entry per item, in item order: every row of d_out is written; `carry` the items that push samples
+    std::vector<SamplePoolEntry> fir((size_t)count), carry;
+    std::vector<int> tiles((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+        const size_t s = (size_t)items[i].session;
+        const long long N = p->N[s], E = p->E[s], k = E2[(size_t)i] - E;      // k <= out_cols: it fits an int
+        const SamplePoolEntry en{i, items[i].session, (int)p->cur[s], (int)k, N - p->H, N, items[i].flush ? N2[(size_t)i] : -1, N2[(size_t)i], E};
+        fir[(size_t)i] = en;
+        if (items[i].samples > 0) carry.push_back(en);
+        if (k > 0) {
+            const long long X0 = r->s_of(E), j0 = X0 - r->d.width;
+            if (en.carry_origin > 0 && j0 < en.carry_origin) {   // (cannot happen: an output not yet emitted starts less than Kp <= H samples before N)
+                set_error("%s: internal: output %lld of session %d reads sample %lld, before the %d carried samples that end at %lld", fn, E,
+                          items[i].session, j0, p->H, N);
+                return FV_ERR_INVALID;
+            }
+            tiles[(size_t)i] = (int)((r->s_of(E2[(size_t)i] - 1) - X0) / kResTile + 1);
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (count > 0 && out_cols > 0 && d_out) {
+        ResamplePoolParams q{};
+        q.chunk = d_chunks, q.buf0 = p->buf[0], q.buf1 = p->buf[1], q.y = d_out, q.table = r->d_table;
+        q.chunk_stride = chunk_stride, q.y_stride = out_stride, q.H = p->H, q.out_cols = out_cols;
+        q.o = r->d.o, q.n = r->d.n, q.width = r->d.width, q.kpad = r->kpad, q.table_dwords = r->table_dwords, q.sx = r->sx;
+        const fv_status rs = for_each_launch_table<SamplePoolBlock>(count, fir.data(), [&](const SamplePoolBlock& blk, int k0, int nz) {
+            q.max_tiles = std::max(1, *std::max_element(tiles.begin() + k0, tiles.begin() + k0 + nz));
+            const dim3 grid((unsigned)q.max_tiles, (unsigned)nz);
+            if (r->global_table) {
+                hipLaunchKernelGGL(resample_pool_global_kernel, grid, dim3(kResThreads), (size_t)r->sx * 4, s, q, blk);
+                set_last_kernel("resample_pool_global_kernel");
+            } else {
+                hipLaunchKernelGGL(resample_pool_kernel, grid, dim3(kResThreads), ((size_t)r->table_dwords + r->sx) * 4, s, q, blk);
+                set_last_kernel("resample_pool_kernel");
+            }
+            return FV_OK;
+        });
+        if (rs) return rs;
+    }
+    if (const fv_status rs = launch_sample_pool_carry(p->buf[0], p->buf[1], p->H, d_chunks, chunk_stride, carry.data(), (int)carry.size(), s))
+        return rs;
+    for (int i = 0; outputs_out && i < count; ++i) outputs_out[i] = E2[(size_t)i] - p->E[(size_t)items[i].session];
+    p->commit(items, count, N2.data(), E2.data());
+    return FV_OK;
+}
+
+FV_API fv_status fv_respool_reset(fv_respool* p, int32_t session) {
+    if (!p) {
+        set_error("fv_respool_reset: null pool");
+        return FV_ERR_INVALID;
+    }
+    return p->reset("fv_respool_reset", session);
+}
+
+FV_API void fv_respool_destroy(fv_respool* p) { delete p; }
 
 }  // extern "C"

@@ -384,22 +384,52 @@ class WavSessionPool:
     samples or ``None``; ``end``: the utterance ends with them — runs one ``WavPool.step_padded`` and hands its ``(count, n_mels, out_frames)``
     buffer and the per-item frame counts straight to ``SessionPool.step_padded``: the counts are known on the host (``framing.PoolCounters``),
     so nothing synchronises and nothing is copied.  Returns each item's audio ``(C_out, k * hop)``; a session's audio trails its samples by the
-    front-end's ``pad_r`` samples plus the generator's lookahead.  Both plans are checked before anything is launched: a refused step leaves
-    both pools as they were.  A generator that takes a pitch template is refused: its F0 and template streams advance in lockstep, and their
-    pool is not built."""
+    front-end's ``pad_r`` samples plus the generator's lookahead.  All plans are checked before anything is launched: a refused step leaves
+    every pool as it was.  A generator that takes a pitch template is refused: its F0 and template streams advance in lockstep, and their
+    pool is not built.
 
-    def __init__(self, frontend: nn.Module, generator: nn.Module, sessions: int, max_chunk_samples: int):
+    ``input_resample`` (a ``Resample`` from the client's rate to the model's) puts a ``ResamplePool`` in front: ``max_chunk_samples`` and the
+    items' samples then count the client's samples.  ``output_resample`` (from the model's rate to the client's) puts one behind, a slot per
+    session and output channel, and the audio comes back at its ``new_freq``: ``(C_out, k)`` with the ``k`` outputs whose bands have
+    arrived.  ``end`` flushes every stage in the same step."""
+
+    def __init__(self, frontend: nn.Module, generator: nn.Module, sessions: int, max_chunk_samples: int, input_resample=None,
+                 output_resample=None):
         if takes_template(generator):
             raise ValueError(f"WavSessionPool: {type(generator).__name__} takes a pitch template next to the mel; the per-session F0 / template "
                              "pool it would need is not built (the template streams advance in lockstep)")
         if not hasattr(frontend, "wav_pool") or not hasattr(generator, "session_pool"):
             raise ValueError(f"WavSessionPool needs a front-end with wav_pool() and a generator with session_pool(), got "
                              f"{type(frontend).__name__} and {type(generator).__name__}")
-        self.wav_pool = frontend.wav_pool(sessions, max_chunk_samples)
+        self.in_pool = self.out_pool = self.wav_pool = self.gen_pool = None
+        if input_resample is None and output_resample is None:
+            self.wav_pool = frontend.wav_pool(sessions, max_chunk_samples)
+        else:
+            sr = getattr(frontend, "sampling_rate", None) or getattr(frontend, "sample_rate", None)
+            for name, r, end, what in (("input_resample", input_resample, "new_freq", "feeds"),
+                                       ("output_resample", output_resample, "orig_freq", "takes the audio of")):
+                if r is None:
+                    continue
+                if not hasattr(r, "pool") or not hasattr(r, end):
+                    raise ValueError(f"WavSessionPool: {name} must be a vocoder_amd.resample.Resample, got {type(r).__name__}")
+                if sr is not None and int(getattr(r, end)) != int(sr):
+                    raise ValueError(f"WavSessionPool: {name} has {end} = {getattr(r, end)} Hz, but it {what} a front-end that runs at {sr} Hz")
+            try:
+                wav_chunk = max_chunk_samples
+                if input_resample is not None:
+                    self.in_pool = input_resample.pool(sessions, max_chunk_samples)
+                    wav_chunk = max(self.in_pool.max_outputs, 1)
+                self.wav_pool = frontend.wav_pool(sessions, wav_chunk)
+            except Exception:
+                self.close()
+                raise
         try:
             self.gen_pool = generator.session_pool(sessions, max_chunk_frames=self.wav_pool.max_frames)
+            if output_resample is not None:    # a flush emits at most the chunk's frames plus the lookahead the pool still held back
+                gp = self.gen_pool
+                self.out_pool = output_resample.pool(sessions * gp.out_channels, (gp.max_chunk_frames + gp.lookahead_frames) * gp.hop)
         except Exception:
-            self.wav_pool.close()
+            self.close()
             raise
         if self.gen_pool.in_channels != self.wav_pool.out_channels:
             self.close()
@@ -419,29 +449,55 @@ class WavSessionPool:
                 raise ValueError(f"expected a 1-D chunk of samples, got {tuple(x.shape)}")
             rows.append(x)
             meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(end)))
-        frames = wp.counters.plan(meta)                                    # both plans before anything moves: each refuses what its library would
+        ip, op, C = self.in_pool, self.out_pool, gp.out_channels
+        for pool in (ip, op):
+            if pool is not None:
+                pool._check_open()
+        # every stage's plan before anything moves (each refuses what its library would); the counts pass from stage to stage as host integers
+        wav_items = meta if ip is None else [(s, k, end) for (s, _, end), k in zip(meta, ip.counters.plan(meta))]
+        frames = wp.counters.plan(wav_items)
         gen_items = [(s, k, end) for (s, _, end), k in zip(meta, frames)]
-        gp.state.plan(gen_items)
-        longest = max((c for _, c, _ in meta), default=0)
-        chunks = None
-        if longest:
-            chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=wp._engine.device)
-            for i, x in enumerate(rows):
-                if x is not None and x.shape[0]:
-                    chunks[i, :x.shape[0]] = x
-        mel, _ = wp.step_padded(meta, chunks)
+        emit = gp.state.plan(gen_items).emit_frames
+        if op is not None:
+            out_items = [(s * C + ch, k * self.hop, end) for (s, _, end), k in zip(meta, emit) for ch in range(C)]
+            op.counters.plan(out_items)
+        chunks = self._chunks(meta, rows)
+        if ip is not None:
+            chunks, _ = ip.step_padded(meta, chunks)
+            chunks = chunks if chunks.shape[1] else None
+        mel, _ = wp.step_padded(wav_items, chunks)
         audio, out_frames = gp.step_padded(gen_items, mel if mel.shape[2] else None)
-        return [audio[i, :, :k * self.hop] for i, k in enumerate(out_frames)]
+        if op is None:
+            return [audio[i, :, :k * self.hop] for i, k in enumerate(out_frames)]
+        flat = audio.reshape(len(meta) * C, audio.shape[2])
+        out, got = op.step_padded(out_items, flat if flat.shape[1] else None)
+        return [out[i * C:(i + 1) * C, :got[i * C]] for i in range(len(meta))]
+
+    def _chunks(self, meta, rows):
+        """The items' samples as the padded ``(count, longest)`` buffer the first pool takes; ``None`` when no item has any."""
+        longest = max((c for _, c, _ in meta), default=0)
+        if not longest:
+            return None
+        chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=self.wav_pool._engine.device)
+        for i, x in enumerate(rows):
+            if x is not None and x.shape[0]:
+                chunks[i, :x.shape[0]] = x
+        return chunks
 
     def reset(self, session: int) -> None:
-        """The next utterance of one slot, in both pools."""
+        """The next utterance of one slot, in every pool."""
+        if self.in_pool is not None:
+            self.in_pool.reset(session)
         self.wav_pool.reset(session)
         self.gen_pool.reset(session)
+        if self.out_pool is not None:
+            for ch in range(self.gen_pool.out_channels):
+                self.out_pool.reset(int(session) * self.gen_pool.out_channels + ch)
 
     def close(self) -> None:
-        self.wav_pool.close()
-        if getattr(self, "gen_pool", None) is not None:
-            self.gen_pool.close()
+        for name in ("in_pool", "wav_pool", "gen_pool", "out_pool"):
+            if getattr(self, name, None) is not None:
+                getattr(self, name).close()
 
     def __enter__(self):
         return self
