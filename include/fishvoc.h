@@ -934,8 +934,8 @@ FV_API void fv_pv_stream_destroy(fv_pv_stream* s);
  * inc[n] = (F_a (hop - k) + F_b k) / hop in 64-bit integers, an unvoiced neighbour taking the other one's value; the phase
  * phi[n] = sum_{m <= n} inc[m] mod 2^32 is an integer prefix sum, exact in any order (an fp32 accumulator drifts audibly within seconds).
  * Output amplitude sin(2 pi phi / 2^32) or amplitude (2 phi / 2^32 - 1), exactly 0 where frame n / hop is unvoiced.
- * The streaming form (fv_yin_stream_*, fv_osc_stream_*) follows the whole-row entries.  Not built: pYIN / Viterbi smoothing, octave-error
- * correction. */
+ * The streaming form (fv_yin_stream_*, fv_osc_stream_*) and the pool form (fv_yinpool_*, fv_oscpool_*) follow the whole-row entries.  Not
+ * built: pYIN / Viterbi smoothing, octave-error correction. */
 typedef struct fv_f0_config {
     int32_t sample_rate;   /* the model's rate: the tracker runs on the samples the mel is made from */
     int32_t frame_length;  /* W, even; 2048 */
@@ -1011,7 +1011,8 @@ FV_API fv_status fv_template_forward(fv_template* p, const float* d_f0, int64_t 
  * bit-identical to fv_template_forward over the whole rows.
  *
  * Every call validates everything before it enqueues anything, enqueues eagerly on `stream` and never synchronises; a refused call changes
- * nothing.  Not built: per-session (non-lockstep) template streams for fv_pool_step. */
+ * nothing.  Sessions that do not advance in lockstep — what fv_pool_step's d_templates needs — have the pool form below (fv_yinpool_*,
+ * fv_oscpool_*). */
 typedef struct fv_yin_stream fv_yin_stream;
 typedef struct fv_osc_stream fv_osc_stream;
 
@@ -1065,6 +1066,118 @@ FV_API fv_status fv_osc_stream_reset(fv_osc_stream* s);
 /* Call it before fv_template_destroy of its synthesiser, once the stream's work has finished (refinegan.py:287 / hifigan.py:226's users free
  * nothing). */
 FV_API void fv_osc_stream_destroy(fv_osc_stream* s);
+
+/* Pool form of both steps: S sessions that advance independently, what fv_wavpool_* is to fv_logmel_stream_* and fv_respool_* to
+ * fv_resample_stream_*, for fv_yin_stream_* and fv_osc_stream_* (no reference counterpart: the CPU trackers in front of refinegan.py:287 /
+ * hifigan.py:226 take whole files).  What the two pools emit per session is what fv_pool_step takes as d_templates.  (Named fv_yinpool_* /
+ * fv_oscpool_*, outside the fv_yin_ / fv_osc_ prefixes: those families' lists of entries are pinned by their host test.)
+ *
+ * Both pools hold S slots on the per-session carry core: each slot has its own counters, its own flushed flag and its own bit saying which of
+ * two carry buffers holds its history.  A step is a list of fv_wavpool_item (session, samples, flush): any subset of the slots, each at most
+ * once, each with its own chunk size; the stream's push and flush folded into one call.  With flush the slot then refuses items (FV_ERR_STATE)
+ * until its reset.  The whole step is checked before any counter moves or anything is enqueued: a refused step leaves every slot as it was.
+ * The items' table entries travel in the kernel arguments, 32 per launch.  The entries enqueue eagerly and never synchronise.
+ *
+ * Tracker pool.  Per slot N samples received, E frames emitted and the last H = W / 2 + max(W / 2, (hop + 1) / 2) samples, as the stream.
+ *   N' = N + samples;  E' = flush ? N' / hop : max(E, ready(N'));  the item emits the frames [E, E')      (ready: fv_yin_frames_ready)
+ * A flush at N' = 0 emits nothing.  One workgroup per (item, frame) stages the frame from the slot's carried samples and the item's chunk row —
+ * samples before 0 and at or past N' are zeros by index and never loaded — and then runs the device code fv_f0_forward runs, so a session's
+ * concatenated values are bit-identical to fv_f0_forward over its whole utterance, whatever the other sessions do.  One step is one tracker
+ * launch and one carry launch per 32 items.
+ *
+ * Oscillator pool.  An item's `samples` counts F0 frames.  Per slot Tn frames received, E emitted, the F0 of the last two frames received (the
+ * frames [E - 1, Tn) among them) and the phase at the start of frame E, a wrapping uint32 in one of two (S) arrays picked by a second bit of
+ * the slot: an item that emits reads one and writes the other, so no launch reads and writes the same buffer of a slot.
+ *   Tn' = Tn + samples;  E' = flush ? Tn' : max(E, Tn' - 1);  the item emits the samples of the frames [E, E'), hop each
+ * The flush clamps the last centre to Tn' - 1, as fv_template_forward clamps to the row's last frame.  At E = 0 the phase is 0 by index, not
+ * from memory: a slot's first utterance, a slot after its reset, a slot whose first push was one frame and emitted nothing.  A session's
+ * concatenated samples are bit-identical to fv_template_forward over its whole track.  One step is three launches (increments, chunk sums,
+ * samples) and one carry launch per 32 items, whatever the number of sessions. */
+typedef struct fv_yinpool fv_yinpool;
+typedef struct fv_oscpool fv_oscpool;
+
+/* The tracker pool's only device allocation (a CPU tracker in front of refinegan.py:287 / hifigan.py:226 keeps no state), made on the current
+ * HIP device and freed by fv_yinpool_destroy: two (S, H) carry buffers.  sessions outside [1, 65535] or max_chunk outside [1, 2^28]:
+ * FV_ERR_INVALID.  `p` must outlive the pool. */
+FV_API fv_status fv_yinpool_create(fv_f0* p, int32_t sessions, int32_t max_chunk, fv_yinpool** out);
+/* The most frames one item can emit in one step (a whole-file tracker in front of refinegan.py:287 / hifigan.py:226 has no such bound): a push
+ * of max_chunk samples that also flushes, the largest (N + max_chunk) / hop - ready(N) over one period of N.  Exact: some state attains it.
+ * An out_cols of this size serves every step.  0 for a NULL pool. */
+FV_API int64_t fv_yinpool_max_frames(const fv_yinpool* p);
+/* N of one slot: the samples of the current utterance (the file of a tracker in front of refinegan.py:287 / hifigan.py:226) received so far;
+ * 0 for a session outside [0, S). */
+FV_API int64_t fv_yinpool_received(const fv_yinpool* p, int32_t session);
+/* E of one slot: the frames (values of what a tracker in front of refinegan.py:287 / hifigan.py:226 returns) emitted so far; 0 for a session
+ * outside [0, S). */
+FV_API int64_t fv_yinpool_emitted(const fv_yinpool* p, int32_t session);
+/* N - max(0, E hop + hop / 2 - W / 2) of one slot, never negative: samples received that frames not yet emitted still read (the file's tail
+ * of a tracker in front of refinegan.py:287 / hifigan.py:226); 0 for a session outside [0, S). */
+FV_API int64_t fv_yinpool_pending(const fv_yinpool* p, int32_t session);
+/* Pure host (no GPU): what a step would emit (a whole-file tracker in front of refinegan.py:287 / hifigan.py:226 has nothing to plan).
+ * received / emitted / flushed: the S counters and flags (flushed may be NULL: none is).  Writes E' - E of every item to frames_out (count
+ * entries) and returns the largest of them; nothing is changed: the caller moves the counters.  Refuses what fv_yinpool_step refuses of the
+ * items, each named in fv_last_error, with the status as the (negative) result: a session outside [0, S), a duplicate session, samples
+ * outside [0, max_chunk], more than 2^40 samples (FV_ERR_INVALID); an item for a flushed session (FV_ERR_STATE); a config that fv_f0_plan
+ * refuses, sessions outside [1, 65535] or max_chunk outside [1, 2^28]. */
+FV_API int64_t fv_yinpool_plan(const fv_f0_config* cfg, int32_t sessions, int32_t max_chunk, const int64_t* received, const int64_t* emitted,
+                               const int32_t* flushed, const fv_wavpool_item* items, int32_t count, int64_t* frames_out);
+/* One step (replaces one run of the tracker in front of refinegan.py:287 / hifigan.py:226 per file, for sessions whose audio arrives at
+ * different times).  d_chunks: (count, chunk_stride) fp32, row i holding item i's samples first — the rest of the row (NaN included) is never
+ * loaded; NULL when no item has samples.  d_f0 / d_aperiodicity: (count, out_stride) fp32 with out_stride >= out_cols >= the largest E' - E
+ * of the step (d_f0 NULL when out_cols is 0; d_aperiodicity may always be NULL: it is then not stored): the first out_cols columns of row i
+ * receive item i's frames and exactly 0.0f after them, an item that emits nothing a row of zeros; every one of them is written.  frames_out
+ * (may be NULL): count entries, E' - E of every item.  Refusals, checked for the whole step before anything moves, each naming the item and
+ * the session: those of fv_yinpool_plan, a NULL chunk buffer although an item has samples, chunk_stride shorter than the longest chunk,
+ * out_cols below the largest E' - E, out_stride < out_cols, a NULL d_f0 although an item emits (FV_ERR_INVALID).  No device allocation, no
+ * copy, no host synchronisation.  Asynchronous on `stream`; steps of one pool must be ordered. */
+FV_API fv_status fv_yinpool_step(fv_yinpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                 float* d_f0, float* d_aperiodicity, int64_t out_stride, int32_t out_cols, int64_t* frames_out, void* stream);
+/* N = E = 0 and not flushed for one slot: its next utterance (the next file of a tracker in front of refinegan.py:287 / hifigan.py:226).  The
+ * carry is kept: samples before 0 are zeros by index, whatever it holds.  A session outside [0, S): FV_ERR_INVALID. */
+FV_API fv_status fv_yinpool_reset(fv_yinpool* p, int32_t session);
+/* Frees the carry (call it before fv_f0_destroy of its tracker, once the pool's work has finished); a CPU tracker in front of
+ * refinegan.py:287 / hifigan.py:226 has nothing to free. */
+FV_API void fv_yinpool_destroy(fv_yinpool* p);
+
+/* The oscillator pool's device allocations (a CPU oscillator in front of refinegan.py:287 / hifigan.py:226 keeps its phase in a host float),
+ * made on the current HIP device and freed by fv_oscpool_destroy: two (S, 2) carry buffers, the increments and chunk sums of one step — sized
+ * for S items of 2 + max_chunk_frames frames — and two (S) uint32 phases.  (2 + max_chunk_frames) * hop <= 2^30; sessions outside [1, 65535]
+ * or max_chunk_frames outside [1, 2^28]: FV_ERR_INVALID.  `p` must outlive the pool. */
+FV_API fv_status fv_oscpool_create(fv_template* p, int32_t sessions, int32_t max_chunk_frames, fv_oscpool** out);
+/* The most frames one item can emit in one step (refinegan.py:287 / hifigan.py:226 take the whole template at once): max_chunk_frames + 1, a
+ * push of max_chunk_frames that also flushes while one frame waits.  An out_cols of hop times this serves every step.  0 for a NULL pool. */
+FV_API int64_t fv_oscpool_max_frames(const fv_oscpool* p);
+/* Tn of one slot: the F0 frames of the current utterance (the track a user of refinegan.py:287 / hifigan.py:226 brings whole) received so far;
+ * 0 for a session outside [0, S). */
+FV_API int64_t fv_oscpool_received(const fv_oscpool* p, int32_t session);
+/* E of one slot: the frames whose samples (of the template refinegan.py:287 / hifigan.py:226 take) have been emitted; 0 for a session outside
+ * [0, S). */
+FV_API int64_t fv_oscpool_emitted(const fv_oscpool* p, int32_t session);
+/* Tn - E of one slot: F0 frames received whose samples have not left, 0 or 1 between steps (a CPU oscillator in front of refinegan.py:287 /
+ * hifigan.py:226 waits for the whole track); 0 for a session outside [0, S). */
+FV_API int64_t fv_oscpool_pending(const fv_oscpool* p, int32_t session);
+/* Pure host (no GPU), as fv_yinpool_plan: what a step would emit, in frames (a CPU oscillator in front of refinegan.py:287 / hifigan.py:226
+ * has nothing to plan).  The items' `samples` count F0 frames.  Writes E' - E of every item to frames_out and returns the largest; refuses
+ * what fv_oscpool_step refuses of the items, a config that fv_template_create refuses, sessions outside [1, 65535] or max_chunk_frames
+ * outside [1, 2^28], with the status as the (negative) result. */
+FV_API int64_t fv_oscpool_plan(const fv_template_config* cfg, int32_t sessions, int32_t max_chunk_frames, const int64_t* received,
+                               const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
+                               int64_t* frames_out);
+/* One step (the next pieces of the template refinegan.py:287 / hifigan.py:226 take, for sessions whose F0 arrives at different times).
+ * d_chunks: (count, chunk_stride) fp32 in Hz (0, negative, NaN or >= sr: unvoiced), row i holding item i's frames first — the rest of the row
+ * is never loaded; NULL when no item has frames; an fv_yinpool_step's d_f0 serves as it is.  d_out: (count, out_stride) fp32, out_stride >=
+ * out_cols >= hop times the largest E' - E of the step, counted in samples (NULL when out_cols is 0): the first out_cols columns of row i
+ * receive the (E' - E) hop samples of item i and exactly 0.0f after them; every one of them is written.  frames_out (may be NULL): E' - E of
+ * every item, in frames.  Refusals as fv_yinpool_step's, the output's counted in samples.  No device allocation, no copy, no host
+ * synchronisation.  Asynchronous on `stream`; steps of one pool must be ordered. */
+FV_API fv_status fv_oscpool_step(fv_oscpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                 float* d_out, int64_t out_stride, int32_t out_cols, int64_t* frames_out, void* stream);
+/* Tn = E = 0 and not flushed for one slot: its next utterance (the next track of refinegan.py:287 / hifigan.py:226's user).  The buffers are
+ * kept: the first emission of an utterance takes phase 0 by index, not from memory.  A session outside [0, S): FV_ERR_INVALID. */
+FV_API fv_status fv_oscpool_reset(fv_oscpool* p, int32_t session);
+/* Call it before fv_template_destroy of its synthesiser, once the pool's work has finished (refinegan.py:287 / hifigan.py:226's users free
+ * nothing). */
+FV_API void fv_oscpool_destroy(fv_oscpool* p);
 
 /* -------- scoring generated audio: the distances eval.py and the STFT loss compute between a source and a generated waveform, as metrics.
  *          eval.py:29-33's spec_diff is mean |LogMelSpectrogram(target) - LogMelSpectrogram(preds)|; stft.py:55 is the spectral convergence

@@ -12,14 +12,16 @@ Public surface (mirrors /root/reference/fish_vocoder for the generator hot path 
   formulas as GPU metrics; ``python -m vocoder_amd.eval SOURCE GENERATED`` scores a directory;
 * ``vocoder_amd.f0`` — ``YinF0``, ``PitchTemplate`` and ``template_from_audio``: the F0 track and the pitch template that
   ``RefineGANGenerator`` and the ``use_template=True`` generators take next to the mel, made on the GPU from the audio, whole rows, ragged rows and
-  chunk by chunk (``YinF0Stream``, ``PitchTemplateStream``, ``TemplateStream``; exported here);
+  chunk by chunk (``YinF0Stream``, ``PitchTemplateStream``, ``TemplateStream``) and per session (``YinF0Pool``, ``PitchTemplatePool``,
+  ``TemplatePool``); exported here;
 * ``vocoder_amd.sharding`` — utterance-batch sharding helpers for one process per GPU.
 
 The compute path is hand-written HIP only; importing works on a CPU-only box (for config/host logic), running does not.
 """
 __version__ = "0.1.0"
 
-__all__ = ["PitchTemplate", "PitchTemplateStream", "TemplateStream", "YinF0", "YinF0Stream", "frames_ready", "template_from_audio"]
+__all__ = ["PitchTemplate", "PitchTemplatePool", "PitchTemplateStream", "TemplatePool", "TemplateStream", "YinF0", "YinF0Pool", "YinF0Stream",
+           "frames_ready", "template_from_audio"]
 
 
 def __getattr__(name: str):

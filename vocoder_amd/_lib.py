@@ -70,6 +70,10 @@ EXPORTS = (
     "fv_yin_stream_reset", "fv_yin_stream_destroy",
     "fv_osc_stream_create", "fv_osc_stream_pending_frames", "fv_osc_stream_push", "fv_osc_stream_flush", "fv_osc_stream_reset",
     "fv_osc_stream_destroy",
+    "fv_yinpool_create", "fv_yinpool_max_frames", "fv_yinpool_received", "fv_yinpool_emitted", "fv_yinpool_pending", "fv_yinpool_plan",
+    "fv_yinpool_step", "fv_yinpool_reset", "fv_yinpool_destroy",
+    "fv_oscpool_create", "fv_oscpool_max_frames", "fv_oscpool_received", "fv_oscpool_emitted", "fv_oscpool_pending", "fv_oscpool_plan",
+    "fv_oscpool_step", "fv_oscpool_reset", "fv_oscpool_destroy",
     "fv_pair_wino4_tile", "fv_pair_wino4_pack",
     "fv_vq_create", "fv_vq_destroy", "fv_vq_load_codebook", "fv_vq_set_slices", "fv_vq_workspace_bytes", "fv_vq_encode", "fv_vq_decode",
     "fv_posterior_create", "fv_posterior_load_weight", "fv_posterior_finalize", "fv_posterior_reach_frames", "fv_posterior_output_channels",
@@ -499,6 +503,24 @@ def lib() -> ctypes.CDLL:
     L.fv_osc_stream_reset.restype = _i32
     L.fv_osc_stream_destroy.argtypes = [vp]
     L.fv_osc_stream_destroy.restype = None
+    for pre, cfgp in (("fv_yinpool", fcp), ("fv_oscpool", tcp)):
+        getattr(L, pre + "_create").argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+        getattr(L, pre + "_create").restype = _i32
+        getattr(L, pre + "_max_frames").argtypes = [vp]
+        getattr(L, pre + "_max_frames").restype = i64
+        for name in ("_received", "_emitted", "_pending"):
+            getattr(L, pre + name).argtypes = [vp, _i32]
+            getattr(L, pre + name).restype = i64
+        getattr(L, pre + "_plan").argtypes = [cfgp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
+        getattr(L, pre + "_plan").restype = i64
+        getattr(L, pre + "_reset").argtypes = [vp, _i32]
+        getattr(L, pre + "_reset").restype = _i32
+        getattr(L, pre + "_destroy").argtypes = [vp]
+        getattr(L, pre + "_destroy").restype = None
+    L.fv_yinpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, vp, i64, _i32, i64p, vp]
+    L.fv_yinpool_step.restype = _i32
+    L.fv_oscpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, i64, _i32, i64p, vp]
+    L.fv_oscpool_step.restype = _i32
     L.fv_pair_wino4_tile.argtypes = [_i32, _i32]
     L.fv_pair_wino4_tile.restype = _i32
     L.fv_pair_wino4_pack.argtypes = [fp, _i32, fp, i64]

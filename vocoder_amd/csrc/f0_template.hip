@@ -9,6 +9,11 @@
 //   f0_template_kernel         carry = the sums of the chunks before this one; a workgroup scan inside the chunk; sin / sawtooth of the phase
 //   osc_stream_sums_kernel,    the same two levels on the frames a stream has staged (fv_osc_stream_*), the carry started from the phase the
 //   osc_stream_kernel          call before left on the device
+//   yin_pool_kernel            yin_f0_kernel's frame (one body, yin_frame_body) per item of a pool of sessions that advance independently
+//                              (fv_yinpool_*): the frame staged from the slot's carry and the item's chunk row
+//   osc_pool_increment_kernel, the oscillator's levels per item of such a pool (fv_oscpool_*): increments from the slot's two carried frames and
+//   osc_pool_sums_kernel,      the item's F0 row, chunk sums, and the samples with the slot's own carried phase.  One fv_oscpool_step is these
+//   osc_pool_kernel            three launches and one carry launch per 32 items, whatever the number of sessions
 // The streams (fv_yin_stream_*, fv_osc_stream_*) sit on the sample streams' carry core (sample_stream.h): the tracker carries the last samples of
 // every row and runs yin_f0_kernel on [carried | chunk]; the oscillator carries the last two F0 frames, as its "samples", and the phase.
 //
@@ -16,10 +21,12 @@
 // over ascending j with fused multiply-adds, and the running sum is scanned in chunks of 64 lags whatever the launch: a frame's bits depend on
 // the plan alone.  Why integers for the phase: the same reason as pv_scan_synth_kernel's accumulator (pitch_shift.hip) — the sum never grows
 // and is exact in any order.  The sample streams' carry core (sample_stream.h) carries the last H samples of a row from call to call; a prefix
-// sum has no such history, so the two-level scan here is its own.
+// sum has no such history, so the two-level scan here is its own.  The pools sit on the per-session form of that core (sample_pool.h), with a
+// ping-pong bit per slot for the carry and another for the oscillator's phase.
 #include <memory>
 
 #include "engine_internal.h"
+#include "sample_pool.h"
 #include "sample_stream.h"
 
 namespace fv {
@@ -104,39 +111,18 @@ __device__ __forceinline__ float wave_scan_add(float v, int lane) {   // inclusi
     return v;
 }
 
-// grid (frames, rows); block pl.threads().  LDS: xs[W + 8] (the frame, then zeros) | dl[d_elems] (d, then d') | cs[d_elems] (the prefix inside
-// a 64-lag chunk) | ct[d_elems / 64] (chunk totals) | red[32].  Workgroup x computes frame t0 + x into column x.  x[b] holds the samples
-// [origin, origin + rows.e[row]) of row b (the whole row: origin 0, t0 0, len the row's length; a stream: its carried samples and the chunk), the
-// frame's global indices map to index - origin.  Samples before 0 or at or past limit = origin + len are zeros by index: the address is clamped
-// and the value selected, so no sample outside [origin, limit) is loaded.
-__global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __restrict__ x, long long x_stride, F0RowBlock rows, int row0,
-                                                                float* __restrict__ f0, float* __restrict__ ap, long long out_stride,
-                                                                long long origin, long long t0, YinPlan pl) {
-    extern __shared__ __align__(16) float lds[];
+// One frame, staged by the caller in xs = lds[0 .. W + 8) (the frame, then zeros): the difference function, the cumulative-mean normalisation,
+// the threshold search and the parabolic step, by the whole workgroup of pl.threads(); thread 0 stores the frame's values (ap_out may be NULL).
+// LDS: xs[W + 8] | dl[d_elems] (d, then d') | cs[d_elems] (the prefix inside a 64-lag chunk) | ct[d_elems / 64] (chunk totals) | red[32].
+// The one body of yin_f0_kernel (whole rows, lockstep streams) and yin_pool_kernel (per-session items): a frame's bits depend on the plan alone.
+__device__ __forceinline__ void yin_frame_body(float* lds, const YinPlan& pl, float* __restrict__ f0_out, float* __restrict__ ap_out) {
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
-    const int col = blockIdx.x, b = row0 + blockIdx.y;
-    const long long t = t0 + col, limit = origin + rows.e[blockIdx.y], first = origin > 0 ? origin : 0;
-    float* f0r = f0 + (long long)b * out_stride;
-    float* apr = ap + (long long)b * out_stride;
-    if (t >= limit / pl.hop) {   // (the whole workgroup leaves: no barrier below is reached by a part of it)
-        if (tid == 0) f0r[col] = 0.f, apr[col] = 0.f;
-        return;
-    }
     const int W = pl.W, Wi = pl.Wi, NL = pl.lags(), DE = pl.d_elems();
     float* xs = lds;
     float* dl = xs + W + 8;
     float* cs = dl + DE;
     float* ct = cs + DE;
     float* red = ct + DE / 64;
-    const float* xr = x + (long long)b * x_stride;
-    const long long lo = t * pl.hop + pl.hop / 2 - W / 2;
-    for (int i = tid; i < W + 8; i += nthr) {
-        const long long idx = lo + i;
-        const bool in = i < W && idx >= first && idx < limit;
-        const long long at = idx < first ? first : (idx >= limit ? limit - 1 : idx);
-        const float v = xr[at - origin];
-        xs[i] = in ? v : 0.f;
-    }
     for (int i = tid; i < DE; i += nthr) dl[i] = 0.f;
     __syncthreads();
 
@@ -223,9 +209,78 @@ __global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __r
             f = (float)pl.sr / ((float)best + delta);
             aper = bb;
         }
-        f0r[col] = f;
-        apr[col] = aper;
+        *f0_out = f;
+        if (ap_out) *ap_out = aper;
     }
+}
+
+// grid (frames, rows); block pl.threads().  LDS as yin_frame_body lays it out.  Workgroup x computes frame t0 + x into column x.  x[b] holds the
+// samples [origin, origin + rows.e[row]) of row b (the whole row: origin 0, t0 0, len the row's length; a stream: its carried samples and the
+// chunk), the frame's global indices map to index - origin.  Samples before 0 or at or past limit = origin + len are zeros by index: the
+// address is clamped and the value selected, so no sample outside [origin, limit) is loaded.
+__global__ __launch_bounds__(kYinMaxThreads) void yin_f0_kernel(const float* __restrict__ x, long long x_stride, F0RowBlock rows, int row0,
+                                                                float* __restrict__ f0, float* __restrict__ ap, long long out_stride,
+                                                                long long origin, long long t0, YinPlan pl) {
+    extern __shared__ __align__(16) float lds[];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int col = blockIdx.x, b = row0 + blockIdx.y;
+    const long long t = t0 + col, limit = origin + rows.e[blockIdx.y], first = origin > 0 ? origin : 0;
+    float* f0r = f0 + (long long)b * out_stride;
+    float* apr = ap + (long long)b * out_stride;
+    if (t >= limit / pl.hop) {   // (the whole workgroup leaves: no barrier below is reached by a part of it)
+        if (tid == 0) f0r[col] = 0.f, apr[col] = 0.f;
+        return;
+    }
+    const int W = pl.W;
+    float* xs = lds;
+    const float* xr = x + (long long)b * x_stride;
+    const long long lo = t * pl.hop + pl.hop / 2 - W / 2;
+    for (int i = tid; i < W + 8; i += nthr) {
+        const long long idx = lo + i;
+        const bool in = i < W && idx >= first && idx < limit;
+        const long long at = idx < first ? first : (idx >= limit ? limit - 1 : idx);
+        const float v = xr[at - origin];
+        xs[i] = in ? v : 0.f;
+    }
+    yin_frame_body(lds, pl, f0r + col, apr + col);
+}
+
+// The pool form (fv_yinpool_step): grid (out_cols, entries); block pl.threads(); at most kSamplePoolBlock entries per launch, by value
+// (fv_internal.h: first = E, count = E' - E, carry_origin = N - H, chunk_origin = N, avail = N').  Workgroup (x, k) computes frame first + x of
+// entry k into column x of row `item` and stages it from two places, as resample_pool_body's sample() maps them: sample j in
+// [chunk_origin, avail) from the item's chunk row, j in [max(0, carry_origin), chunk_origin) from the slot's carry buf[bit][slot], anything
+// else — j < 0, and j >= avail, which only a flushing item's frames ask for — is 0.0f and never loaded.  A column at or past the entry's count
+// is an exact zero; ap == NULL: the aperiodicity is not stored.
+__global__ __launch_bounds__(kYinMaxThreads) void yin_pool_kernel(const float* __restrict__ chunk, long long chunk_stride,
+                                                                  const float* __restrict__ buf0, const float* __restrict__ buf1, long long H,
+                                                                  const SamplePoolBlock tab, float* __restrict__ f0, float* __restrict__ ap,
+                                                                  long long out_stride, YinPlan pl) {
+    extern __shared__ __align__(16) float lds[];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int col = blockIdx.x;
+    const SamplePoolEntry e = tab.e[blockIdx.y];
+    float* f0r = f0 + (long long)e.item * out_stride;
+    float* apr = ap ? ap + (long long)e.item * out_stride : nullptr;
+    if (col >= e.count) {   // (the whole workgroup leaves: no barrier below is reached by a part of it)
+        if (tid == 0) {
+            f0r[col] = 0.f;
+            if (apr) apr[col] = 0.f;
+        }
+        return;
+    }
+    const int W = pl.W;
+    float* xs = lds;
+    const float* cr = e.avail > e.chunk_origin ? chunk + (long long)e.item * chunk_stride : nullptr;
+    const float* carry = (e.bit ? buf1 : buf0) + (long long)e.slot * H;
+    const long long held = e.carry_origin > 0 ? e.carry_origin : 0;   // samples [held, chunk_origin) are carried
+    const long long lo = (e.first + col) * pl.hop + pl.hop / 2 - W / 2;
+    for (int i = tid; i < W + 8; i += nthr) {
+        const long long idx = lo + i;
+        float v = 0.f;
+        if (i < W && idx >= held && idx < e.avail) v = idx >= e.chunk_origin ? cr[idx - e.chunk_origin] : carry[idx - e.carry_origin];
+        xs[i] = v;
+    }
+    yin_frame_body(lds, pl, f0r + col, apr ? apr + col : nullptr);
 }
 
 // F[b][t] = rint(f0 / sr * 2^32) in double for 0 < f0 < sr and t < frames[b], else 0 (unvoiced; NaN and padded frames included)
@@ -356,6 +411,74 @@ __global__ __launch_bounds__(256) void osc_stream_kernel(const uint32_t* __restr
     for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) carry += sums[(long long)b * nchunk + c];
     tmpl_chunk_emit(F + (long long)b * fcount, lo_c, hi_c, hop, n_lo + blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, n_hi, n_hi, carry,
                     out + (long long)b * out_stride, n_lo, kind, amplitude, (int)blockIdx.x == nchunk - 1 ? phase_out + b : nullptr);
+}
+
+// The oscillator pool's three levels (fv_oscpool_step), each grid (., entries) with at most kOscPoolBlock entries per launch, by value.  Entry k
+// is one item: its slot has received Tn frames, the item brings `fcount - 2` more, and row `item` of F holds the increments of the frames
+// [Tn - 2, Tn + c) — the first two from the slot's carry buf[bit][slot], the rest from the item's chunk row — so column 0 is frame o = Tn - 2 of
+// the utterance and everything below counts from there, as in the stream: clamp bounds lo_c / hi_c, the emitted samples [n_lo, n_hi) in
+// `nchunk` chunks of kTmplChunk.  phase_in: the array (0 / 1) that holds the phase at the start of frame E, -1: E = 0, phase 0 by index; the
+// phase after the last emitted sample goes into the array phase_out, the other one.
+struct OscPoolEntry {
+    int item, slot, bit;
+    int phase_in, phase_out;
+    int fcount, lo_c, hi_c;
+    int n_lo, n_hi, nchunk;
+};
+constexpr int kOscPoolBlock = 32;
+using OscPoolBlock = LaunchTable<OscPoolEntry, kOscPoolBlock>;
+
+// grid (ceil(f_cols / 256), entries), f_cols the block's largest fcount: F[item][t] = the increment of frame o + t, f0_increment_kernel's
+// conversion; 0 before the utterance's first frame (t < lo_c: the carry may hold an earlier utterance) and from fcount on
+__global__ __launch_bounds__(256) void osc_pool_increment_kernel(const float* __restrict__ chunk, long long chunk_stride,
+                                                                 const float* __restrict__ buf0, const float* __restrict__ buf1,
+                                                                 const OscPoolBlock tab, uint32_t* __restrict__ F, int f_stride, int f_cols,
+                                                                 int sr) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= f_cols) return;
+    const OscPoolEntry e = tab.e[blockIdx.y];
+    uint32_t v = 0u;
+    if (t >= e.lo_c && t < e.fcount) {
+        const float f = t < 2 ? ((e.bit ? buf1 : buf0) + 2LL * e.slot)[t] : chunk[(long long)e.item * chunk_stride + (t - 2)];
+        if (f > 0.f && f < (float)sr) v = (uint32_t)__double2ll_rn((double)f / (double)sr * 4294967296.0);
+    }
+    F[(long long)e.item * f_stride + t] = v;
+}
+
+// grid (the block's largest nchunk, entries): sums[item][chunk], wrapping; a workgroup past its entry's chunks leaves whole
+__global__ __launch_bounds__(256) void osc_pool_sums_kernel(const uint32_t* __restrict__ F, int f_stride, uint32_t* __restrict__ sums,
+                                                            int sums_stride, const OscPoolBlock tab, int hop) {
+    const OscPoolEntry e = tab.e[blockIdx.y];
+    if ((int)blockIdx.x >= e.nchunk) return;
+    const uint32_t s = tmpl_chunk_sum(F + (long long)e.item * f_stride, e.lo_c, e.hi_c, hop,
+                                      e.n_lo + blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems, e.n_hi);
+    if (threadIdx.x == 0) sums[(long long)e.item * sums_stride + blockIdx.x] = s;
+}
+
+// grid (ceil(out_cols / kTmplChunk), entries): the samples [n_lo, n_hi) of the entry into the columns [0, n_hi - n_lo) of row `item`, exact
+// zeros up to out_cols.  A workgroup past its entry's chunks stores its zeros and leaves whole, before any barrier.
+__global__ __launch_bounds__(256) void osc_pool_kernel(const uint32_t* __restrict__ F, int f_stride, const uint32_t* __restrict__ sums,
+                                                       int sums_stride, const OscPoolBlock tab, uint32_t* phase0, uint32_t* phase1,
+                                                       float* __restrict__ out, long long out_stride, int out_cols, int hop, int kind,
+                                                       float amplitude) {
+    const OscPoolEntry e = tab.e[blockIdx.y];
+    float* orow = out + (long long)e.item * out_stride;
+    if ((int)blockIdx.x >= e.nchunk) {
+        const long long c0 = (long long)blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems;   // this thread's first column
+#pragma unroll
+        for (int i = 0; i < kTmplItems; ++i)
+            if (c0 + i < out_cols) orow[c0 + i] = 0.f;
+        return;
+    }
+    const int c0 = blockIdx.x * kTmplChunk + threadIdx.x * kTmplItems;   // (inside the entry's chunks: below 2^30)
+    const uint32_t* pin = e.phase_in < 0 ? nullptr : (e.phase_in ? phase1 : phase0);
+    uint32_t* pout = e.phase_out ? phase1 : phase0;
+    const uint32_t* srow = sums + (long long)e.item * sums_stride;
+    uint32_t carry = threadIdx.x == 0 && pin ? pin[e.slot] : 0u;
+    for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) carry += srow[c];
+    const int n_out = e.n_lo + (int)min((long long)out_cols, ((long long)blockIdx.x + 1) * kTmplChunk);
+    tmpl_chunk_emit(F + (long long)e.item * f_stride, e.lo_c, e.hi_c, hop, e.n_lo + c0, e.n_hi, n_out, carry, orow, e.n_lo, kind, amplitude,
+                    (int)blockIdx.x == e.nchunk - 1 ? pout + e.slot : nullptr);
 }
 
 // the rows' lengths, checked before anything is enqueued; host == NULL: every row has `whole`
@@ -786,5 +909,326 @@ FV_API fv_status fv_osc_stream_reset(fv_osc_stream* s) {
 }
 
 FV_API void fv_osc_stream_destroy(fv_osc_stream* s) { delete s; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Pools (fv_yinpool_*, fv_oscpool_*): the streams' rules per session on the per-session carry core (sample_pool.h).  Slot s carries its last H
+// samples (tracker) or its last two F0 frames (oscillator) in buf[cur[s]] row s; the oscillator's phase at the start of frame E lies in
+// phase[pcur[s]][s], and an item that emits writes the other array and flips that slot's bit alone.
+// ---------------------------------------------------------------------------------------------
+struct fv_yinpool : SamplePool {
+    fv_f0* p = nullptr;
+    long long max_frames = 0;   // fv_yinpool_max_frames
+};
+
+struct fv_oscpool : SamplePool {
+    fv_template* p = nullptr;
+    std::vector<unsigned char> pcur;   // the slot's phase is in phase[pcur[s]][s]
+    uint32_t* aux = nullptr;           // one allocation: F (S, f_stride) | sums (S, sums_stride) | phase[2] (S)
+    uint32_t *F = nullptr, *sums = nullptr, *phase[2] = {nullptr, nullptr};
+    int f_stride = 0, sums_stride = 0;
+    ~fv_oscpool() {
+        if (aux) (void)hipFree(aux);
+    }
+};
+
+static fv_status f0_pool_range(const char* fn, int sessions, int max_chunk) {
+    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
+        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+
+// The most one tracker item emits: a push of max_chunk samples that also flushes, from a state with E = ready(N):
+// g(N) = (N + max_chunk) / hop - ready(N).  From N = hop / 2 + W / 2 on, ready(N + hop) = ready(N) + 1, so g has the period hop there.
+static long long yinpool_max_frames(const YinPlan& pl, int max_chunk) {
+    long long best = 0;
+    for (long long N = 0; N < pl.hop / 2 + pl.W / 2 + 2LL * pl.hop; ++N) best = std::max(best, (N + max_chunk) / pl.hop - yin_ready(pl, N));
+    return best;
+}
+
+// The emission rules of one step, after the pool's admit
+static void yinpool_emission(const YinPlan& pl, const int64_t* emitted, const fv_wavpool_item* items, int count, const long long* N2,
+                             long long* E2) {
+    for (int i = 0; i < count; ++i) {
+        const long long E = emitted[items[i].session];
+        E2[i] = std::max(E, items[i].flush ? N2[i] / pl.hop : yin_ready(pl, N2[i]));
+    }
+}
+
+static void oscpool_emission(const int64_t* emitted, const fv_wavpool_item* items, int count, const long long* T2, long long* E2) {
+    for (int i = 0; i < count; ++i) E2[i] = std::max((long long)emitted[items[i].session], items[i].flush ? T2[i] : T2[i] - 1);
+}
+
+// What both plans return: E' - E per item and the largest of them
+static int64_t f0_pool_counts(const int64_t* emitted, const fv_wavpool_item* items, int count, const long long* E2, int64_t* frames_out) {
+    int64_t k_max = 0;
+    for (int i = 0; i < count; ++i) {
+        frames_out[i] = E2[i] - emitted[items[i].session];
+        k_max = std::max(k_max, frames_out[i]);
+    }
+    return k_max;
+}
+
+// The refusals of a step's output buffer (fv_respool_step's): `need` columns for the item that emits most, `what` names a column
+static fv_status f0_pool_output(const char* fn, const char* what, const fv_wavpool_item* items, int count, const int64_t* emitted,
+                                const long long* E2, long long per_frame, bool have_out, long long out_stride, int out_cols) {
+    long long k_max = 0;
+    int k_item = 0;
+    for (int i = 0; i < count; ++i) {
+        const long long k = (E2[i] - emitted[items[i].session]) * per_frame;
+        if (k > k_max) k_max = k, k_item = i;
+    }
+    const int k_session = count > 0 ? items[k_item].session : -1;
+    if (out_cols < k_max || out_cols < 0) {
+        set_error("%s: out_cols = %d, but item %d (session %d) emits %lld %s in this step", fn, out_cols, k_item, k_session, k_max, what);
+        return FV_ERR_INVALID;
+    }
+    if (out_stride < out_cols) {
+        set_error("%s: out_stride = %lld is shorter than out_cols = %d (item %d, session %d, emits %lld %s)", fn, out_stride, out_cols, k_item,
+                  k_session, k_max, what);
+        return FV_ERR_INVALID;
+    }
+    if (k_max > 0 && !have_out) {
+        set_error("%s: null output although item %d (session %d) emits %lld %s", fn, k_item, k_session, k_max, what);
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+
+extern "C" {
+
+FV_API fv_status fv_yinpool_create(fv_f0* f, int32_t sessions, int32_t max_chunk, fv_yinpool** out) {
+    const char* fn = "fv_yinpool_create";
+    if (out) *out = nullptr;
+    if (!f || !out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::unique_ptr<fv_yinpool> p(new fv_yinpool());
+    p->p = f;
+    const int H = f->plan.W / 2 + std::max(f->plan.W / 2, (f->plan.hop + 1) / 2);   // what fv_yin_stream_create carries
+    if (const fv_status rs = p->create(fn, sessions, max_chunk, H)) return rs;
+    p->max_frames = yinpool_max_frames(f->plan, max_chunk);
+    *out = p.release();
+    return FV_OK;
+}
+
+FV_API int64_t fv_yinpool_max_frames(const fv_yinpool* p) { return p ? p->max_frames : 0; }
+
+FV_API int64_t fv_yinpool_received(const fv_yinpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+
+FV_API int64_t fv_yinpool_emitted(const fv_yinpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+
+FV_API int64_t fv_yinpool_pending(const fv_yinpool* p, int32_t s) {
+    return p && s >= 0 && s < p->S ? yin_pending(p->p->plan, p->N[(size_t)s], p->E[(size_t)s]) : 0;
+}
+
+FV_API int64_t fv_yinpool_plan(const fv_f0_config* cfg, int32_t sessions, int32_t max_chunk, const int64_t* received, const int64_t* emitted,
+                               const int32_t* flushed, const fv_wavpool_item* items, int32_t count, int64_t* frames_out) {
+    const char* fn = "fv_yinpool_plan";
+    YinPlan pl;
+    if (const fv_status st = make_yin_plan(cfg, fn, pl)) return st;
+    if (const fv_status st = f0_pool_range(fn, sessions, max_chunk)) return st;
+    if (!received || !emitted || (count > 0 && !frames_out)) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk, received, flushed, items, count, false, nullptr, 0, N2.data()))
+        return rs;
+    yinpool_emission(pl, emitted, items, count, N2.data(), E2.data());
+    return f0_pool_counts(emitted, items, count, E2.data(), frames_out);
+}
+
+FV_API fv_status fv_yinpool_step(fv_yinpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                 float* d_f0, float* d_aperiodicity, int64_t out_stride, int32_t out_cols, int64_t* frames_out, void* stream) {
+    const char* fn = "fv_yinpool_step";
+    if (!p) {
+        set_error("%s: null pool", fn);
+        return FV_ERR_INVALID;
+    }
+    for (int i = 0; frames_out && i < count; ++i) frames_out[i] = 0;
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status rs = p->admit(fn, "fv_yinpool_reset", items, count, d_chunks, chunk_stride, N2.data())) return rs;
+    const YinPlan& pl = p->p->plan;
+    yinpool_emission(pl, p->E.data(), items, count, N2.data(), E2.data());
+    if (const fv_status rs = f0_pool_output(fn, "frames", items, count, p->E.data(), E2.data(), 1, d_f0 != nullptr, out_stride, out_cols))
+        return rs;
+    // one table entry per item, in item order: every row of the outputs is written; `carry` the items that push samples
+    std::vector<SamplePoolEntry> rows((size_t)count), carry;
+    for (int i = 0; i < count; ++i) {
+        const size_t s = (size_t)items[i].session;
+        const long long N = p->N[s], E = p->E[s], k = E2[(size_t)i] - E;      // k <= out_cols: it fits an int
+        const SamplePoolEntry en{i, items[i].session, (int)p->cur[s], (int)k, N - p->H, N, items[i].flush ? N2[(size_t)i] : -1, N2[(size_t)i], E};
+        rows[(size_t)i] = en;
+        if (items[i].samples > 0) carry.push_back(en);
+        const long long lo = E * pl.hop + pl.hop / 2 - pl.W / 2;
+        if (k > 0 && en.carry_origin > 0 && lo < en.carry_origin) {   // (cannot happen: a frame not yet emitted starts less than H samples before N)
+            set_error("%s: internal: frame %lld of session %d reads sample %lld, before the %d carried samples that end at %lld", fn, E,
+                      items[i].session, lo, p->H, N);
+            return FV_ERR_INVALID;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (count > 0 && out_cols > 0 && d_f0) {
+        const fv_status rs = for_each_launch_table<SamplePoolBlock>(count, rows.data(), [&](const SamplePoolBlock& blk, int, int nz) {
+            hipLaunchKernelGGL(yin_pool_kernel, dim3((unsigned)out_cols, (unsigned)nz), dim3(pl.threads()), pl.lds_bytes(), s, d_chunks,
+                               (long long)chunk_stride, p->buf[0], p->buf[1], (long long)p->H, blk, d_f0, d_aperiodicity, (long long)out_stride, pl);
+            return FV_OK;
+        });
+        if (rs) return rs;
+        set_last_kernel("yin_pool_kernel");
+    }
+    if (const fv_status rs = launch_sample_pool_carry(p->buf[0], p->buf[1], p->H, d_chunks, chunk_stride, carry.data(), (int)carry.size(), s))
+        return rs;
+    for (int i = 0; frames_out && i < count; ++i) frames_out[i] = E2[(size_t)i] - p->E[(size_t)items[i].session];
+    p->commit(items, count, N2.data(), E2.data());
+    return FV_OK;
+}
+
+FV_API fv_status fv_yinpool_reset(fv_yinpool* p, int32_t session) {
+    if (!p) {
+        set_error("fv_yinpool_reset: null pool");
+        return FV_ERR_INVALID;
+    }
+    return p->reset("fv_yinpool_reset", session);
+}
+
+FV_API void fv_yinpool_destroy(fv_yinpool* p) { delete p; }
+
+FV_API fv_status fv_oscpool_create(fv_template* t, int32_t sessions, int32_t max_chunk_frames, fv_oscpool** out) {
+    const char* fn = "fv_oscpool_create";
+    if (out) *out = nullptr;
+    if (!t || !out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    const int hop = t->cfg.hop_length;
+    if (max_chunk_frames >= 1 && (2LL + max_chunk_frames) * hop > kF0MaxLen) {
+        set_error("%s: max_chunk_frames = %d frames of %d samples, with the two carried frames, pass 2^30 samples", fn, max_chunk_frames, hop);
+        return FV_ERR_INVALID;
+    }
+    std::unique_ptr<fv_oscpool> p(new fv_oscpool());
+    p->p = t;
+    if (const fv_status rs = p->create(fn, sessions, max_chunk_frames, 2)) return rs;
+    p->pcur.assign((size_t)sessions, 0);
+    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+    p->f_stride = (int)((2LL + max_chunk_frames + 3) / 4 * 4);
+    p->sums_stride = (int)(((1LL + max_chunk_frames) * hop + kTmplChunk - 1) / kTmplChunk);   // a flushing item emits at most max_chunk + 1 frames
+    const size_t nf = up((size_t)sessions * (size_t)p->f_stride), ns = up((size_t)sessions * (size_t)p->sums_stride), np = up((size_t)sessions);
+    FV_HIP_CHECK(hipMalloc((void**)&p->aux, (nf + ns + 2 * np) * sizeof(uint32_t)));
+    p->F = p->aux, p->sums = p->F + nf, p->phase[0] = p->sums + ns, p->phase[1] = p->phase[0] + np;
+    *out = p.release();
+    return FV_OK;
+}
+
+FV_API int64_t fv_oscpool_max_frames(const fv_oscpool* p) { return p ? (int64_t)p->max_chunk + 1 : 0; }
+
+FV_API int64_t fv_oscpool_received(const fv_oscpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+
+FV_API int64_t fv_oscpool_emitted(const fv_oscpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+
+FV_API int64_t fv_oscpool_pending(const fv_oscpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] - p->E[(size_t)s] : 0; }
+
+FV_API int64_t fv_oscpool_plan(const fv_template_config* cfg, int32_t sessions, int32_t max_chunk_frames, const int64_t* received,
+                               const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
+                               int64_t* frames_out) {
+    const char* fn = "fv_oscpool_plan";
+    if (const fv_status st = check_template_config(cfg, fn)) return st;
+    if (const fv_status st = f0_pool_range(fn, sessions, max_chunk_frames)) return st;
+    if (!received || !emitted || (count > 0 && !frames_out)) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::vector<long long> T2((size_t)std::max(count, 0)), E2(T2.size());
+    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk_frames, received, flushed, items, count, false, nullptr, 0,
+                                               T2.data()))
+        return rs;
+    oscpool_emission(emitted, items, count, T2.data(), E2.data());
+    return f0_pool_counts(emitted, items, count, E2.data(), frames_out);
+}
+
+FV_API fv_status fv_oscpool_step(fv_oscpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                 float* d_out, int64_t out_stride, int32_t out_cols, int64_t* frames_out, void* stream) {
+    const char* fn = "fv_oscpool_step";
+    if (!p) {
+        set_error("%s: null pool", fn);
+        return FV_ERR_INVALID;
+    }
+    for (int i = 0; frames_out && i < count; ++i) frames_out[i] = 0;
+    std::vector<long long> T2((size_t)std::max(count, 0)), E2(T2.size());
+    if (const fv_status rs = p->admit(fn, "fv_oscpool_reset", items, count, d_chunks, chunk_stride, T2.data())) return rs;
+    const fv_template_config& cfg = p->p->cfg;
+    const int hop = cfg.hop_length;
+    oscpool_emission(p->E.data(), items, count, T2.data(), E2.data());
+    if (const fv_status rs = f0_pool_output(fn, "samples", items, count, p->E.data(), E2.data(), hop, d_out != nullptr, out_stride, out_cols))
+        return rs;
+    std::vector<OscPoolEntry> rows((size_t)count);
+    std::vector<SamplePoolEntry> carry;
+    for (int i = 0; i < count; ++i) {
+        const size_t s = (size_t)items[i].session;
+        const long long Tn = p->N[s], E = p->E[s], k = E2[(size_t)i] - E, o = Tn - 2;   // column 0 of the item's F row is frame o
+        const int c = items[i].samples;
+        if (E - o < 1 || E - o > 2) {   // (cannot happen: between calls Tn - E is 0 or 1)
+            set_error("%s: internal: session %d has received %lld frames and emitted %lld", fn, items[i].session, Tn, E);
+            return FV_ERR_INVALID;
+        }
+        OscPoolEntry en{};
+        en.item = i, en.slot = items[i].session, en.bit = (int)p->cur[s];
+        en.phase_in = E > 0 ? (int)p->pcur[s] : -1, en.phase_out = (int)p->pcur[s] ^ 1;
+        en.fcount = 2 + c, en.lo_c = o < 0 ? (int)-o : 0, en.hi_c = (int)(T2[(size_t)i] - 1 - o);
+        en.n_lo = (int)((E - o) * hop), en.n_hi = (int)((E2[(size_t)i] - o) * hop);
+        en.nchunk = (en.n_hi - en.n_lo + kTmplChunk - 1) / kTmplChunk;
+        rows[(size_t)i] = en;
+        if (c > 0)
+            carry.push_back(SamplePoolEntry{i, items[i].session, (int)p->cur[s], (int)k, o, Tn, items[i].flush ? T2[(size_t)i] : -1,
+                                            T2[(size_t)i], E});
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (count > 0 && out_cols > 0 && d_out) {
+        const unsigned out_chunks = (unsigned)(((long long)out_cols + kTmplChunk - 1) / kTmplChunk);
+        const fv_status rs = for_each_launch_table<OscPoolBlock>(count, rows.data(), [&](const OscPoolBlock& blk, int, int nz) -> fv_status {
+            int nchunk = 0, fcols = 0;
+            for (int k = 0; k < nz; ++k)
+                if (blk.e[k].nchunk > 0) nchunk = std::max(nchunk, blk.e[k].nchunk), fcols = std::max(fcols, blk.e[k].fcount);
+            if (nchunk > 0) {   // (an entry that emits nothing needs no increments: its workgroups only store zeros)
+                hipLaunchKernelGGL(osc_pool_increment_kernel, dim3((unsigned)((fcols + 255) / 256), (unsigned)nz), dim3(256), 0, s, d_chunks,
+                                   (long long)chunk_stride, p->buf[0], p->buf[1], blk, p->F, p->f_stride, fcols, cfg.sample_rate);
+                FV_HIP_CHECK(hipGetLastError());
+                hipLaunchKernelGGL(osc_pool_sums_kernel, dim3((unsigned)nchunk, (unsigned)nz), dim3(256), 0, s, p->F, p->f_stride, p->sums,
+                                   p->sums_stride, blk, hop);
+                FV_HIP_CHECK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(osc_pool_kernel, dim3(out_chunks, (unsigned)nz), dim3(256), 0, s, p->F, p->f_stride, p->sums, p->sums_stride, blk,
+                               p->phase[0], p->phase[1], d_out, (long long)out_stride, out_cols, hop, cfg.kind, cfg.amplitude);
+            return FV_OK;
+        });
+        if (rs) return rs;
+        set_last_kernel("osc_pool_kernel");
+    }
+    if (const fv_status rs = launch_sample_pool_carry(p->buf[0], p->buf[1], p->H, d_chunks, chunk_stride, carry.data(), (int)carry.size(), s))
+        return rs;
+    for (int i = 0; i < count; ++i) {
+        const size_t sl = (size_t)items[i].session;
+        const long long k = E2[(size_t)i] - p->E[sl];
+        if (frames_out) frames_out[i] = k;
+        if (k > 0) p->pcur[sl] ^= 1;   // the step wrote the slot's other phase
+    }
+    p->commit(items, count, T2.data(), E2.data());
+    return FV_OK;
+}
+
+FV_API fv_status fv_oscpool_reset(fv_oscpool* p, int32_t session) {
+    if (!p) {
+        set_error("fv_oscpool_reset: null pool");
+        return FV_ERR_INVALID;
+    }
+    return p->reset("fv_oscpool_reset", session);
+}
+
+FV_API void fv_oscpool_destroy(fv_oscpool* p) { delete p; }
 
 }  // extern "C"

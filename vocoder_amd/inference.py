@@ -385,23 +385,40 @@ class WavSessionPool:
     buffer and the per-item frame counts straight to ``SessionPool.step_padded``: the counts are known on the host (``framing.PoolCounters``),
     so nothing synchronises and nothing is copied.  Returns each item's audio ``(C_out, k * hop)``; a session's audio trails its samples by the
     front-end's ``pad_r`` samples plus the generator's lookahead.  All plans are checked before anything is launched: a refused step leaves
-    every pool as it was.  A generator that takes a pitch template is refused: its F0 and template streams advance in lockstep, and their
-    pool is not built.
+    every pool as it was.
+
+    ``template`` (for a generator that takes a pitch template; such a generator is refused without it): the keyword arguments of a
+    ``vocoder_amd.f0.TemplatePool`` after its sizes, the keys ``stream_wav_synthesis(template=...)`` takes (``frame_length``, ``fmin``, ``fmax``,
+    ``threshold``, ``kind``, ``amplitude``).  A ``TemplatePool`` then stands beside the wav pool on the same model-rate samples.  Per session,
+    what one branch has emitted ahead of the other waits on the device (what ``_TemplateJoin`` does for rows in lockstep), and the generator
+    pool gets the ``n`` frames both have emitted with their ``n * hop`` template samples; ``n`` comes from the host counters.  With ``end``
+    both branches flush in the same step, and a session whose two branches made different numbers of frames raises a ValueError that names it,
+    before anything is launched.
 
     ``input_resample`` (a ``Resample`` from the client's rate to the model's) puts a ``ResamplePool`` in front: ``max_chunk_samples`` and the
     items' samples then count the client's samples.  ``output_resample`` (from the model's rate to the client's) puts one behind, a slot per
     session and output channel, and the audio comes back at its ``new_freq``: ``(C_out, k)`` with the ``k`` outputs whose bands have
     arrived.  ``end`` flushes every stage in the same step."""
 
+    _TEMPLATE_KEYS = ("frame_length", "fmin", "fmax", "threshold", "kind", "amplitude")
+
     def __init__(self, frontend: nn.Module, generator: nn.Module, sessions: int, max_chunk_samples: int, input_resample=None,
-                 output_resample=None):
-        if takes_template(generator):
+                 output_resample=None, template: dict | None = None):
+        if takes_template(generator) and template is None:
             raise ValueError(f"WavSessionPool: {type(generator).__name__} takes a pitch template next to the mel; the per-session F0 / template "
-                             "pool it would need is not built (the template streams advance in lockstep)")
+                             "pool it would need is not built (the template streams advance in lockstep) unless template= is passed: a dict "
+                             "of the tracker's and the oscillator's keyword arguments, empty for the defaults")
+        if template is not None:
+            if not takes_template(generator):
+                raise ValueError(f"WavSessionPool: template= was given, but {type(generator).__name__} takes no pitch template")
+            unknown = sorted(set(template) - set(self._TEMPLATE_KEYS))
+            if unknown:
+                raise ValueError(f"WavSessionPool: template= has unknown keys {unknown}; it takes {list(self._TEMPLATE_KEYS)}")
         if not hasattr(frontend, "wav_pool") or not hasattr(generator, "session_pool"):
             raise ValueError(f"WavSessionPool needs a front-end with wav_pool() and a generator with session_pool(), got "
                              f"{type(frontend).__name__} and {type(generator).__name__}")
-        self.in_pool = self.out_pool = self.wav_pool = self.gen_pool = None
+        self.in_pool = self.out_pool = self.wav_pool = self.gen_pool = self.template_pool = None
+        wav_chunk = max_chunk_samples
         if input_resample is None and output_resample is None:
             self.wav_pool = frontend.wav_pool(sessions, max_chunk_samples)
         else:
@@ -424,7 +441,16 @@ class WavSessionPool:
                 self.close()
                 raise
         try:
-            self.gen_pool = generator.session_pool(sessions, max_chunk_frames=self.wav_pool.max_frames)
+            release = self.wav_pool.max_frames
+            if template is not None:
+                from .f0 import TemplatePool
+                sr = getattr(frontend, "sampling_rate", None) or getattr(frontend, "sample_rate", None)
+                if sr is None:
+                    raise ValueError("WavSessionPool: template= needs a front-end that declares its sample rate")
+                self.template_pool = TemplatePool(int(sr), self.wav_pool.hop, sessions, wav_chunk, **template)
+                # after a step one of a session's two waiting lists is empty, so the join releases at most what one branch emits in one step
+                release = max(release, self.template_pool.max_frames)
+            self.gen_pool = generator.session_pool(sessions, max_chunk_frames=release)
             if output_resample is not None:    # a flush emits at most the chunk's frames plus the lookahead the pool still held back
                 gp = self.gen_pool
                 self.out_pool = output_resample.pool(sessions * gp.out_channels, (gp.max_chunk_frames + gp.lookahead_frames) * gp.hop)
@@ -435,11 +461,17 @@ class WavSessionPool:
             self.close()
             raise ValueError(f"the front-end emits {self.wav_pool.out_channels} channels, the generator takes {self.gen_pool.in_channels}")
         self.sessions, self.max_chunk_samples, self.hop = int(sessions), int(max_chunk_samples), self.gen_pool.hop
+        if self.template_pool is not None and self.wav_pool.hop != self.hop:
+            self.close()
+            raise ValueError(f"the front-end's hop is {self.wav_pool.hop} samples, the generator's {self.hop}")
+        # per session: mel frames (C, r) / template samples (r * hop,) one branch has emitted ahead of the other; None: nothing waits
+        self._mel_wait = [None] * self.sessions
+        self._template_wait = [None] * self.sessions
 
     @torch.no_grad()
     def step(self, items) -> list:
         """One step for ``items`` (see the class); returns each item's audio, views of one output buffer."""
-        wp, gp = self.wav_pool, self.gen_pool
+        wp, gp, tp = self.wav_pool, self.gen_pool, self.template_pool
         wp._check_open()
         gp._check_open()
         meta, rows = [], []
@@ -450,13 +482,14 @@ class WavSessionPool:
             rows.append(x)
             meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(end)))
         ip, op, C = self.in_pool, self.out_pool, gp.out_channels
-        for pool in (ip, op):
+        for pool in (ip, op) + ((tp.tracker, tp.template) if tp is not None else ()):
             if pool is not None:
                 pool._check_open()
         # every stage's plan before anything moves (each refuses what its library would); the counts pass from stage to stage as host integers
         wav_items = meta if ip is None else [(s, k, end) for (s, _, end), k in zip(meta, ip.counters.plan(meta))]
         frames = wp.counters.plan(wav_items)
-        gen_items = [(s, k, end) for (s, _, end), k in zip(meta, frames)]
+        release = frames if tp is None else self._plan_join(wav_items, frames, tp.counters.plan(wav_items)[1])
+        gen_items = [(s, k, end) for (s, _, end), k in zip(meta, release)]
         emit = gp.state.plan(gen_items).emit_frames
         if op is not None:
             out_items = [(s * C + ch, k * self.hop, end) for (s, _, end), k in zip(meta, emit) for ch in range(C)]
@@ -466,12 +499,56 @@ class WavSessionPool:
             chunks, _ = ip.step_padded(meta, chunks)
             chunks = chunks if chunks.shape[1] else None
         mel, _ = wp.step_padded(wav_items, chunks)
-        audio, out_frames = gp.step_padded(gen_items, mel if mel.shape[2] else None)
+        if tp is None:
+            audio, out_frames = gp.step_padded(gen_items, mel if mel.shape[2] else None)
+        else:
+            tmpl, tframes = tp.step_padded(wav_items, chunks)
+            audio, out_frames = gp.step_padded(gen_items, *self._join(gen_items, mel, frames, tmpl, tframes))
         if op is None:
             return [audio[i, :, :k * self.hop] for i, k in enumerate(out_frames)]
         flat = audio.reshape(len(meta) * C, audio.shape[2])
         out, got = op.step_padded(out_items, flat if flat.shape[1] else None)
         return [out[i * C:(i + 1) * C, :got[i * C]] for i in range(len(meta))]
+
+    def _waiting(self, s: int) -> tuple:
+        """Frames of session ``s`` that wait in the mel branch and in the template branch (one of the two is 0)."""
+        m, t = self._mel_wait[s], self._template_wait[s]
+        return (0 if m is None else int(m.shape[1])), (0 if t is None else int(t.shape[0]) // self.hop)
+
+    def _plan_join(self, items, mel_frames, template_frames) -> list:
+        """Frames every item releases into the generator pool: what both branches have emitted, waiting frames included.  Host only."""
+        release = []
+        for i, ((s, _, end), fm, ft) in enumerate(zip(items, mel_frames, template_frames)):
+            wm, wt = self._waiting(s)
+            if end and wm + fm != wt + ft:
+                raise ValueError(f"session {s} (item {i}) ends with {wm + fm} frames from the log-mel front-end and {wt + ft} from the pitch "
+                                 f"template: the generator takes one template frame of {self.hop} samples per mel frame")
+            release.append(min(wm + fm, wt + ft))
+        return release
+
+    def _join(self, gen_items, mel, mel_frames, tmpl, template_frames) -> tuple:
+        """``(chunks, templates)`` for ``SessionPool.step_padded``: per item the waiting frames, then this step's, cut at what the item
+        releases; the rest waits.  Device copies only; every count is a host integer."""
+        hop, count = self.hop, len(gen_items)
+        width = max((n for _, n, _ in gen_items), default=0)
+        if not any(self._mel_wait[s] is not None or self._template_wait[s] is not None for s, _, _ in gen_items) \
+                and all(n == fm == ft for (_, n, _), fm, ft in zip(gen_items, mel_frames, template_frames)) \
+                and mel.shape[2] == width and tmpl.shape[1] == width * hop:
+            return (mel, tmpl[:, None, :]) if width else (None, None)      # nothing waits and nothing will: the two buffers as they stand
+        chunks = torch.zeros((count, mel.shape[1], width), dtype=torch.float32, device=mel.device) if width else None
+        templates = torch.zeros((count, 1, width * hop), dtype=torch.float32, device=mel.device) if width else None
+        for i, ((s, n, _), fm, ft) in enumerate(zip(gen_items, mel_frames, template_frames)):
+            m, t = mel[i, :, :fm], tmpl[i, :ft * hop]
+            if self._mel_wait[s] is not None:
+                m = torch.cat([self._mel_wait[s], m], dim=1)
+            if self._template_wait[s] is not None:
+                t = torch.cat([self._template_wait[s], t])
+            if n:
+                chunks[i, :, :n] = m[:, :n]
+                templates[i, 0, :n * hop] = t[:n * hop]
+            self._mel_wait[s] = m[:, n:].clone() if m.shape[1] > n else None
+            self._template_wait[s] = t[n * hop:].clone() if t.shape[0] > n * hop else None
+        return chunks, templates
 
     def _chunks(self, meta, rows):
         """The items' samples as the padded ``(count, longest)`` buffer the first pool takes; ``None`` when no item has any."""
@@ -490,12 +567,15 @@ class WavSessionPool:
             self.in_pool.reset(session)
         self.wav_pool.reset(session)
         self.gen_pool.reset(session)
+        if self.template_pool is not None:
+            self.template_pool.reset(session)
+            self._mel_wait[int(session)] = self._template_wait[int(session)] = None
         if self.out_pool is not None:
             for ch in range(self.gen_pool.out_channels):
                 self.out_pool.reset(int(session) * self.gen_pool.out_channels + ch)
 
     def close(self) -> None:
-        for name in ("in_pool", "wav_pool", "gen_pool", "out_pool"):
+        for name in ("in_pool", "wav_pool", "template_pool", "gen_pool", "out_pool"):
             if getattr(self, name, None) is not None:
                 getattr(self, name).close()
 
