@@ -820,8 +820,8 @@ FV_API void fv_respool_destroy(fv_respool* p);
  * Synthesis: irfft(S[:, s]) times the window, overlap-added, divided by the overlap-added window^2 where that is positive, n_fft / 2 samples
  * cropped from the front, cut or zero-padded to Ls = (2 L o + n) / (2 n) (round(L o / n), halves up).
  * Resample: orig_freq -> sr with fv_resample_design's filter (table in global memory): ceil(n Ls / o) samples, cut or zero-padded to L.
- * The streaming form (fv_pv_stream_*) follows the whole-row entries.  Not built: ragged rows in one call, a chunk-parallel scan for very long
- * single rows, per-session (non-lockstep) shift streams for fv_pool_step, the command line's --pitch-shift with --chunk-frames. */
+ * The streaming form (fv_pv_stream_*) and the per-session pool (fv_pvpool_*) follow the whole-row entries.  Not built: ragged rows in one call,
+ * a chunk-parallel scan for very long single rows, a per-session n_steps, the command line's --pitch-shift with --sessions / --chunk-frames. */
 typedef struct fv_pitch_shift_config {
     int32_t sample_rate;           /* sr of test.py:61-62 */
     double n_steps;                /* cfg.pitch_shift (configs/train.yaml), in steps of an octave / bins_per_octave */
@@ -914,6 +914,76 @@ FV_API fv_status fv_pv_stream_flush(fv_pv_stream* s, float* d_y, int64_t y_row_s
 FV_API fv_status fv_pv_stream_reset(fv_pv_stream* s);
 /* Call it before fv_pitch_shift_destroy of its shifter, once the stream's work has finished (test.py:61-62 has nothing to free). */
 FV_API void fv_pv_stream_destroy(fv_pv_stream* s);
+
+/* -------- pitch shift, per session: test.py:61-62 for a pool of sessions that advance independently — what fv_respool_* is to
+ *          fv_resample_stream_*, for fv_pv_stream_*.  No reference counterpart: librosa shifts whole files and keeps no state.  (Named
+ *          fv_pvpool_*, outside the fv_pv_ and fv_pitch_shift_ prefixes: those families' lists of entries are pinned by their host tests.)
+ *          --------
+ *
+ * One pool is one fv_pitch_shift: one n_steps, so one rate n / o and one resampler table for all S slots.  Each slot has its own N and E, its
+ * flushed flag, its n_fft carried samples, the polar carry (|D| and Theta of column A - 1, Phi after the frames [0, S)) and the last
+ * n_fft / hop synthesised frames.  All three carries are pairs of buffers with one bit per slot; a bit flips only when the step's launch wrote
+ * that slot's other half: samples > 0 for the sample carry, dA > 0 or dS > 0 for the polar pair, dS > 0 for the frames.  A, S, Y and the
+ * resampler's count follow from N alone (fv_pv_stream_ready).  A step is a list of fv_wavpool_item (session, samples, flush); per item
+ *   N' = N + samples;  E' = flush ? N' : max(E, min(M(Y(N')), N'));  the item emits the outputs [E, E').
+ * A flush at N' = 0 emits nothing; a flushed slot refuses items (FV_ERR_STATE) until fv_pvpool_reset; an utterance holds at most 2^30 samples.
+ * The whole step — the pool's plan, the inner resample pool's, every check of the output and the workspace — is made on the host before
+ * anything is enqueued or any counter moves: a refused step leaves every slot as it was.  The items that have work form the rows of one set of
+ * tensors: one window launch, the STFT conv over (rows, largest dA), the polar and scan launches, the inverse-DFT conv over (rows, largest dS),
+ * the overlap-add, the frame carry, one step of an inner fv_respool on the shifter's resampler, the sample carry and one crop into the
+ * caller's rows, each launch serving 32 rows; a row's columns past its own dA / dS are written as zeros.  Both convs run in batch-invariant
+ * mode, so a session's concatenated outputs are bit-identical to fv_pitch_shift_forward over its whole utterance after
+ * fv_pv_set_batch_invariant(p, 1) and to an fv_pv_stream fed the same chunks, whatever the other sessions do.  orig_freq == sr: every item's
+ * samples come back bit for bit and nothing is carried.  Not built: a per-session n_steps (it needs a per-slot rate and resampler table). */
+typedef struct fv_pvpool fv_pvpool;
+
+/* All device state of the pool is allocated here on the current HIP device (test.py:61-62 keeps none) and freed by fv_pvpool_destroy: the three
+ * pairs of carries and an fv_respool on the shifter's resampler.  sessions outside [1, 65535] or max_chunk outside [1, 2^28]: FV_ERR_INVALID; a
+ * max_chunk whose one step passes 2^31 elements per row: FV_ERR_UNSUPPORTED. */
+FV_API fv_status fv_pvpool_create(fv_pitch_shift* p, int32_t sessions, int32_t max_chunk, fv_pvpool** out);
+/* Bytes of device scratch a step of up to `sessions` items needs (256-byte aligned; test.py:61-62 allocates per call); 0 for NULL and for the
+ * identity shift. */
+FV_API size_t fv_pvpool_workspace_bytes(const fv_pvpool* p);
+/* The most one item can emit in one step (test.py:61-62's file length never enters): a push of max_chunk samples that also flushes, from any
+ * state.  Such a step emits N + max_chunk - E(N), and N - E(N) grows by one per sample and falls only where A(N) steps, at N = F / 2 + a h: its
+ * largest value stands at some N_a = F / 2 + a h - 1.  Moving a by n moves S by o, Y by o h, the resampler's count by n h and N by n h, so past
+ * the start-up N_a - E(N_a) has period n in a; in the start-up every clamp (A, S, Y and the resampler's count at 0) only raises E.  The result
+ * is max_chunk + the largest N_a - E(N_a) over n consecutive a past the start-up.  Exact: some state attains it.  The per-step sizes inside
+ * the pool (fv_pvpool_bounds) cover the same step and are upper estimates.  An out_cols of this size serves every step.  0 for NULL. */
+FV_API int64_t fv_pvpool_max_outputs(const fv_pvpool* p);
+/* N of one slot: the samples of the current utterance (test.py:61-62's gt_y) received so far; 0 for a session outside [0, S). */
+FV_API int64_t fv_pvpool_received(const fv_pvpool* p, int32_t session);
+/* E of one slot: the shifted samples (what test.py:61-62 returns) emitted so far; 0 for a session outside [0, S). */
+FV_API int64_t fv_pvpool_emitted(const fv_pvpool* p, int32_t session);
+/* N - E of one slot: what its flush would emit now (the rest of test.py:61-62's file); 0 for a session outside [0, S). */
+FV_API int64_t fv_pvpool_pending(const fv_pvpool* p, int32_t session);
+/* Pure host (no GPU): the sizes a pool of this config and max_chunk is built with (test.py:61-62 sizes nothing), five entries: the most
+ * analysis frames, stretched frames and stretched samples one item makes ready in one step, the most its resampler emits, and
+ * fv_pvpool_max_outputs.  The first four are upper estimates: (max_chunk + F / 2) / h + 2; ceil((maxA + 1) o / n) + 2;
+ * max(maxS h + F, ceil(max_chunk o / n) + 2); fv_respool_max_outputs of a pool of maxY.  Zeros but the last for the identity shift. */
+FV_API fv_status fv_pvpool_bounds(const fv_pitch_shift_config* cfg, int32_t max_chunk, int64_t* bounds);
+/* Pure host, as fv_respool_plan is: what a step would emit, from the config alone (what test.py:61-62 leaves to librosa).  received / emitted
+ * / flushed: the S counters and flags (flushed may be NULL: none is).  Writes E' - E of every item to outputs_out (count entries) and returns
+ * the largest; nothing is changed.  Refuses what fv_pvpool_step refuses of the items, each named in fv_last_error, with the status as the
+ * (negative) result: those of fv_respool_plan, in its order, then more than 2^30 samples in one utterance, then an item that passes the
+ * pool's own bounds or counters that no sequence of steps gives (FV_ERR_INVALID, "internal"). */
+FV_API int64_t fv_pvpool_plan(const fv_pitch_shift_config* cfg, int32_t sessions, int32_t max_chunk, const int64_t* received,
+                              const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
+                              int64_t* outputs_out);
+/* One step (replaces one test.py:61-62 call per file, for sessions whose audio arrives at different times).  d_chunks, d_out, out_stride,
+ * out_cols and outputs_out as in fv_respool_step: the first out_cols columns of row i receive item i's outputs and exactly 0.0f after them,
+ * every one of them is written.  d_workspace: fv_pvpool_workspace_bytes.  Refusals, for the whole step before anything moves, each naming the
+ * item and the session: those of the items in fv_respool_plan's order, a NULL chunk buffer although an item has samples, chunk_stride shorter
+ * than the longest chunk; then the pool's own of fv_pvpool_plan; then out_cols below the largest E' - E, out_stride < out_cols, a NULL d_out
+ * although an item emits; then a workspace that is NULL or too small although an item has work.  No device allocation, no host synchronisation.  Asynchronous on `stream`; steps of one pool must be ordered. */
+FV_API fv_status fv_pvpool_step(fv_pvpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                float* d_out, int64_t out_stride, int32_t out_cols, int64_t* outputs_out, void* d_workspace,
+                                size_t workspace_bytes, void* stream);
+/* N = E = 0 and not flushed for one slot, and the same for its slot of the inner resample pool: the next file of test.py:61-62.  The carries
+ * are kept: what lies before sample, column and frame 0 is zero by index.  A session outside [0, S): FV_ERR_INVALID. */
+FV_API fv_status fv_pvpool_reset(fv_pvpool* p, int32_t session);
+/* Call it before fv_pitch_shift_destroy of its shifter, once the pool's work has finished (test.py:61-62 has nothing to free). */
+FV_API void fv_pvpool_destroy(fv_pvpool* p);
 
 /* -------- pitch template: the `template (B, 1, T * hop)` that refinegan.py:287 / hifigan.py:226 take next to the mel.  The reference does not
  *          make one: its users bring an F0 track from a CPU tracker (pyworld, parselmouth, librosa.yin) and synthesise the template from it.

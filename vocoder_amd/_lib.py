@@ -63,6 +63,8 @@ EXPORTS = (
     "fv_pitch_shift_stretch", "fv_pitch_shift_forward",
     "fv_pv_stream_ready", "fv_pv_set_batch_invariant", "fv_pv_stream_create", "fv_pv_stream_workspace_bytes", "fv_pv_stream_pending",
     "fv_pv_stream_push", "fv_pv_stream_flush", "fv_pv_stream_reset", "fv_pv_stream_destroy",
+    "fv_pvpool_create", "fv_pvpool_workspace_bytes", "fv_pvpool_max_outputs", "fv_pvpool_received", "fv_pvpool_emitted", "fv_pvpool_pending",
+    "fv_pvpool_bounds", "fv_pvpool_plan", "fv_pvpool_step", "fv_pvpool_reset", "fv_pvpool_destroy",
     "fv_spec_distance_tile", "fv_spec_distance_workspace_bytes", "fv_spec_distance",
     "fv_f0_plan", "fv_f0_create", "fv_f0_destroy", "fv_f0_workspace_bytes", "fv_f0_forward",
     "fv_template_create", "fv_template_destroy", "fv_template_workspace_bytes", "fv_template_forward",
@@ -452,6 +454,25 @@ def lib() -> ctypes.CDLL:
     L.fv_pv_stream_reset.restype = _i32
     L.fv_pv_stream_destroy.argtypes = [vp]
     L.fv_pv_stream_destroy.restype = None
+    L.fv_pvpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_pvpool_create.restype = _i32
+    L.fv_pvpool_workspace_bytes.argtypes = [vp]
+    L.fv_pvpool_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_pvpool_max_outputs.argtypes = [vp]
+    L.fv_pvpool_max_outputs.restype = i64
+    for name in ("fv_pvpool_received", "fv_pvpool_emitted", "fv_pvpool_pending"):
+        getattr(L, name).argtypes = [vp, _i32]
+        getattr(L, name).restype = i64
+    L.fv_pvpool_bounds.argtypes = [pcp, _i32, i64p]
+    L.fv_pvpool_bounds.restype = _i32
+    L.fv_pvpool_plan.argtypes = [pcp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
+    L.fv_pvpool_plan.restype = i64
+    L.fv_pvpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, i64, _i32, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_pvpool_step.restype = _i32
+    L.fv_pvpool_reset.argtypes = [vp, _i32]
+    L.fv_pvpool_reset.restype = _i32
+    L.fv_pvpool_destroy.argtypes = [vp]
+    L.fv_pvpool_destroy.restype = None
     L.fv_spec_distance_tile.argtypes = []
     L.fv_spec_distance_tile.restype = _i32
     L.fv_spec_distance_workspace_bytes.argtypes = [_i32, i64]

@@ -6,10 +6,12 @@
 //     logmel_pool_window_kernel  carry + chunk per table entry: sessions that advance independently (fv_wavpool_step)
 //     pv_frame_kernel            one row, zero edges (the whole-row pitch shift)
 //     pv_frame_window_kernel     carry + chunk, zero edges (fv_pv_stream_*)
+//     pv_frame_pool_window_kernel  carry + chunk per table entry, zero edges (fv_pvpool_step)
 //   ola_tile              frames -> samples: overlap-add in ascending g, envelope, crop, around a frame fetch over the global frame index
 //     istft_ola_kernel           one piece of T frames (the vocos head, the whole-row pitch shift)
 //     istft_ola_window_kernel    the carried frames plus the new ones, an output window [Y, Y2) (fv_pv_stream_*)
-//   pv_frame_carry        the last G synthesised frames, into the other buffer of the pair
+//     istft_ola_pool_window_kernel  the same per table entry: the slot's carried frames, its own S, dS, Tend and [Y, Y2) (fv_pvpool_step)
+//   pv_frame_carry        the last G synthesised frames, into the other buffer of the pair; per table entry in pv_frame_pool_carry_kernel
 //   zero_columns          columns >= T_b of a (B, C, T) result set to 0.0f
 // HBM-bound copies: each lane moves one fp32.
 #include <algorithm>
@@ -203,6 +205,41 @@ fv_status launch_pv_frame_window(const float* carry, long long carry_stride, con
     return FV_OK;
 }
 
+// The pool's (fv_pvpool_step): tensor row k0 + blockIdx.z is one table entry — its own chunk row, its slot's carry in buf[bit], first frame A
+// (first) and dA frames (count) out of the launch's TP - taps + 1.  What logmel_pool_window_kernel is to logmel_window_kernel, without the
+// reflection: zeros before sample 0 and from `avail` on; the slots past tp = count + taps - 1 load nothing and are exact zeros.
+__global__ __launch_bounds__(256) void pv_frame_pool_window_kernel(const float* __restrict__ buf0, const float* __restrict__ buf1,
+                                                                   const float* __restrict__ chunk, float* __restrict__ yp,
+                                                                   const SamplePoolBlock tab, long long H, long long chunk_stride, int hop, int TP,
+                                                                   int taps, int pad, int k0) {
+    const SamplePoolEntry e = tab.e[blockIdx.z];
+    const int used = e.count > 0 ? e.count + taps - 1 : 0;
+    const SamplePieces p{(e.bit ? buf1 : buf0) + (long long)e.slot * H, chunk + (long long)e.item * chunk_stride, e.carry_origin,
+                         e.chunk_origin, e.avail};
+    polyphase_tile(yp + (long long)(k0 + blockIdx.z) * hop * TP, hop, TP, [&](int tp, int r) {
+        if (tp >= used) return 0.f;
+        return piece_sample(p, (e.first + tp) * hop + r - pad);
+    });
+}
+
+fv_status launch_pv_frame_pool_window(const float* buf0, const float* buf1, long long H, const float* chunk, long long chunk_stride,
+                                      const SamplePoolEntry* tab, int rows, float* yp, int hop, int TP, int taps, int pad, hipStream_t s) {
+    if (rows <= 0 || TP <= 0) return FV_OK;
+    for (int k = 0; k < rows; ++k) {
+        const SamplePoolEntry& e = tab[k];
+        if (e.count < 0 || e.count > TP - taps + 1 || e.chunk_origin - e.carry_origin != H || e.avail < e.chunk_origin ||
+            (!chunk && e.avail > e.chunk_origin) || (chunk && e.avail - e.chunk_origin > chunk_stride)) {
+            set_error("pv_frame_pool_window: internal: entry %d (session %d) does not fit its pieces", k, e.slot);
+            return FV_ERR_INVALID;
+        }
+    }
+    return for_each_launch_table<SamplePoolBlock>(rows, tab, [&](const SamplePoolBlock& blk, int k0, int nz) {
+        hipLaunchKernelGGL(pv_frame_pool_window_kernel, dim3((TP + 31) / 32, (hop + 31) / 32, nz), dim3(256), 0, s, buf0, buf1, chunk, yp, blk, H,
+                           chunk_stride, hop, TP, taps, pad, k0);
+        return FV_OK;
+    });
+}
+
 // ---------------------------------------------------------------------------------------------
 // Overlap-add + crop + envelope normalisation of vocos ISTFT("same").  The frames are already multiplied by the hann window (folded into the
 // inverse-DFT basis); win2 = window^2 (n_fft).  Sample tau hop + r - pad sums frame(g hop + r, tau - g) in ascending g over the frames
@@ -262,6 +299,15 @@ fv_status launch_istft_ola(const float* frames, const float* win2, float* y, int
     return FV_OK;
 }
 
+// Element f of frame t from two pieces: the frames [S, ...) in `fb` (n_fft, ld), the frames [S - G, S) in the carried `cb` (n_fft, G)
+__device__ __forceinline__ float two_piece_frame(const float* __restrict__ fb, long long ld, const float* __restrict__ cb, int G, long long S,
+                                                 int f, long long t) {
+    float v = 0.f;   // (a frame below S - G is never reached: fv_pv_stream_create's note on G)
+    if (t >= S) v = fb[(long long)f * ld + (t - S)];
+    else if (t >= S - G) v = cb[(long long)f * G + (t - (S - G))];
+    return v;
+}
+
 // Two pieces, the stretched samples [Y, Y2) of a stream: frames [S, S + dS) from `frames` (B, n_fft, dS), frames [S - G, S) from the carried `cfr`
 // (B, n_fft, G); the frames [0, Tend) exist.  During pushes Tend = S + dS cannot bind (every frame that covers a sample below Y2 exists); at
 // the flush it is T'.
@@ -272,12 +318,8 @@ __global__ __launch_bounds__(256) void istft_ola_window_kernel(const float* __re
     const int tt = blockIdx.x % tau_tiles, rt = blockIdx.x / tau_tiles % r_tiles, b = blockIdx.x / tau_tiles / r_tiles;
     const float* fb = frames + (long long)b * n_fft * dS;
     const float* cb = cfr + (long long)b * n_fft * G;
-    ola_tile<long long>(win2, y + (long long)b * y_stride, n_fft, hop, pad, tau0, n_tau, Tend, Y, Y2, rt, tt, [&](int f, long long t) {
-        float v = 0.f;   // (a frame below S - G is never reached: fv_pv_stream_create's note on G)
-        if (t >= S) v = fb[(long long)f * dS + (t - S)];
-        else if (t >= S - G) v = cb[(long long)f * G + (t - (S - G))];
-        return v;
-    });
+    ola_tile<long long>(win2, y + (long long)b * y_stride, n_fft, hop, pad, tau0, n_tau, Tend, Y, Y2, rt, tt,
+                        [&](int f, long long t) { return two_piece_frame(fb, dS, cb, G, S, f, t); });
 }
 
 fv_status launch_istft_ola_window(const float* frames, const float* cfr, const float* win2, float* y, int B, int n_fft, int hop, int pad, int G,
@@ -291,18 +333,25 @@ fv_status launch_istft_ola_window(const float* frames, const float* cfr, const f
     return FV_OK;
 }
 
+// Element e = f G + i of one row's next carry, frame S + dS - G + i: from the new frames `fb` (n_fft, ld) at or after S, from the carried
+// `cb` (n_fft, G) below it, 0 before frame 0
+__device__ __forceinline__ float frame_carry_value(const float* __restrict__ fb, long long ld, const float* __restrict__ cb, int G, long long S,
+                                                   int dS, long long e) {
+    const int f = (int)(e / G), i = (int)(e - (long long)f * G);
+    const long long t = S + dS - G + i;
+    float v = 0.f;
+    if (t >= S) v = fb[(long long)f * ld + (t - S)];
+    else if (t >= 0) v = cb[(long long)f * G + (t - (S - G))];
+    return v;
+}
+
 // nfr[b][f][i] = frame S + dS - G + i: from the new frames at or after S, from the carried ones below it, 0 before frame 0
 __global__ __launch_bounds__(256) void pv_frame_carry_kernel(const float* __restrict__ frames, const float* __restrict__ cfr,
                                                              float* __restrict__ nfr, int n_fft, int G, long long S, int dS) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)n_fft * G) return;
-    const int b = blockIdx.y;
-    const int f = (int)(e / G), i = (int)(e - (long long)f * G);
-    const long long t = S + dS - G + i;
-    float v = 0.f;
-    if (t >= S) v = frames[((long long)b * n_fft + f) * dS + (t - S)];
-    else if (t >= 0) v = cfr[((long long)b * n_fft + f) * G + (t - (S - G))];
-    nfr[((long long)b * n_fft + f) * G + i] = v;
+    const long long b = blockIdx.y;
+    nfr[b * n_fft * G + e] = frame_carry_value(frames + b * n_fft * dS, dS, cfr + b * n_fft * G, G, S, dS, e);
 }
 
 fv_status launch_pv_frame_carry(const float* frames, const float* cfr, float* nfr, int B, int n_fft, int G, long long S, int dS, hipStream_t s) {
@@ -310,6 +359,67 @@ fv_status launch_pv_frame_carry(const float* frames, const float* cfr, float* nf
                        S, dS);
     FV_HIP_CHECK(hipGetLastError());
     return FV_OK;
+}
+
+// The pool's two (fv_pvpool_step): tensor row k0 + blockIdx.z is one table entry with its own S, dS, Tend and window [Y, Y2); the new frames
+// are (rows, n_fft, ld) with ld the step's largest dS, the carried ones fr[fbit][slot].  An entry's n_tau follows from its own window; the grid
+// spans the launch's largest, and a block past its entry's tiles leaves whole.
+__global__ __launch_bounds__(256) void istft_ola_pool_window_kernel(const float* __restrict__ frames, const float* __restrict__ fr0,
+                                                                    const float* __restrict__ fr1, const float* __restrict__ win2,
+                                                                    float* __restrict__ y, const PvOlaBlock tab, int n_fft, int hop, int pad,
+                                                                    int G, int ld, long long y_stride, int tau_tiles, int k0) {
+    const PvOlaEntry e = tab.e[blockIdx.z];
+    if (e.Y2 <= e.Y) return;
+    const long long tau0 = (e.Y + pad) / hop;
+    const int n_tau = (int)((e.Y2 - 1 + pad) / hop - tau0 + 1);
+    const int tt = blockIdx.x % tau_tiles, rt = blockIdx.x / tau_tiles;
+    if (tt * 32 >= n_tau) return;
+    const long long row = k0 + blockIdx.z;
+    const float* fb = frames + row * n_fft * ld;
+    const float* cb = (e.fbit ? fr1 : fr0) + (long long)e.slot * n_fft * G;
+    ola_tile<long long>(win2, y + row * y_stride, n_fft, hop, pad, tau0, n_tau, e.Tend, e.Y, e.Y2, rt, tt,
+                        [&](int f, long long t) { return two_piece_frame(fb, ld, cb, G, e.S, f, t); });
+}
+
+__global__ __launch_bounds__(256) void pv_frame_pool_carry_kernel(const float* __restrict__ frames, float* fr0, float* fr1, const PvOlaBlock tab,
+                                                                  int n_fft, int G, int ld, int k0) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const PvOlaEntry e = tab.e[blockIdx.y];
+    if (i >= (long long)n_fft * G || e.dS <= 0) return;   // (a slot that synthesised no frame keeps its half and its bit)
+    const long long slot = (long long)e.slot * n_fft * G;
+    (e.fbit ? fr0 : fr1)[slot + i] = frame_carry_value(frames + (long long)(k0 + blockIdx.y) * n_fft * ld, ld, (e.fbit ? fr1 : fr0) + slot, G, e.S,
+                                                       e.dS, i);
+}
+
+fv_status launch_pv_pool_ola(const float* frames, float* fr0, float* fr1, const float* win2, float* y, const PvOlaEntry* tab, int rows, int n_fft,
+                             int hop, int pad, int G, int ld, long long y_stride, hipStream_t s) {
+    if (rows <= 0) return FV_OK;
+    for (int k = 0; k < rows; ++k) {
+        const PvOlaEntry& e = tab[k];
+        if (e.dS < 0 || e.dS > ld || e.Y2 < e.Y || e.Y2 - e.Y > y_stride || e.Tend > e.S + e.dS) {
+            set_error("pv_pool_ola: internal: entry %d (session %d) does not fit its pieces", k, e.slot);
+            return FV_ERR_INVALID;
+        }
+    }
+    const int r_tiles = (hop + 31) / 32;
+    return for_each_launch_table<PvOlaBlock>(rows, tab, [&](const PvOlaBlock& blk, int k0, int nz) {
+        long long span = 0;
+        bool carry = false;
+        for (int i = 0; i < nz; ++i) {
+            const PvOlaEntry& e = blk.e[i];
+            if (e.Y2 > e.Y) span = std::max(span, (e.Y2 - 1 + pad) / hop - (e.Y + pad) / hop + 1);
+            carry = carry || e.dS > 0;
+        }
+        if (span > 0) {
+            const int tau_tiles = (int)((span + 31) / 32);
+            hipLaunchKernelGGL(istft_ola_pool_window_kernel, dim3((unsigned)(r_tiles * tau_tiles), 1, nz), dim3(256), 0, s, frames, fr0, fr1, win2, y,
+                               blk, n_fft, hop, pad, G, ld, y_stride, tau_tiles, k0);
+        }
+        if (carry)   // after the overlap-add in stream order; it writes the halves that one does not read
+            hipLaunchKernelGGL(pv_frame_pool_carry_kernel, dim3((unsigned)(((long long)n_fft * G + 255) / 256), nz), dim3(256), 0, s, frames, fr0,
+                               fr1, blk, n_fft, G, ld, k0);
+        return FV_OK;
+    });
 }
 
 // y[b][c][T_b ...) = 0.0f up to the row's end; T_b travels by value (rows.e), `span` = columns of the longest tail

@@ -444,8 +444,9 @@ using PoolCropBlock = LaunchTable<PoolCropEntry, kPoolBlock>;
 fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const PoolGatherEntry* tab, int count, int C, long long cap,
                              long long in_frames, long long Wg, int hop, hipStream_t s);
 // y (rows, C, Ly) -> out (., C, out_frames): each entry's samples, then zeros to the row's end
+// out_stride: columns between the rows of `out` (0: out_frames * hop, rows back to back)
 fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames,
-                           int hop, hipStream_t s);
+                           int hop, hipStream_t s, long long out_stride = 0);
 // sample streams (sample_stream.h): next[b][i] = sample next_origin + i of row b, i < count, where `N` samples have arrived before this call — from
 // chunk[b][idx - N] at or after N, from prev[b][idx - prev_origin] before it, 0.0f before the utterance's start; prev and next are two buffers
 // of row stride `stride`
@@ -505,6 +506,23 @@ fv_status launch_pv_frame(const float* wave, long long x_stride, float* yp, int 
 fv_status launch_pv_frame_window(const float* carry, long long carry_stride, const float* chunk, long long chunk_stride, float* yp, int B,
                                  long long N, int H, long long end, long long f0, int hop, int TP, int pad, hipStream_t s);
 
+// The pitch-shift pool's forms (fv_pvpool_step): tensor row k of each launch is one table entry.  The window takes SamplePoolEntry with
+// first = A and count = dA: yp[k][r][tp] = sample (A_k + tp) hop + r - pad of the entry's session for tp < dA_k + taps - 1, zeros before sample 0
+// and from avail on, 0.0f in the other slots.
+fv_status launch_pv_frame_pool_window(const float* buf0, const float* buf1, long long H, const float* chunk, long long chunk_stride,
+                                      const SamplePoolEntry* tab, int rows, float* yp, int hop, int TP, int taps, int pad, hipStream_t s);
+struct PvOlaEntry {
+    int slot, fbit;            // the slot's carried frames [S - G, S) are in fr[fbit]; an entry with dS > 0 writes fr[fbit ^ 1]
+    int dS, pad_;              // frames [S, S + dS) of this row are new
+    long long S, Tend;         // only frames in [0, Tend) exist
+    long long Y, Y2;           // the stretched samples this row emits
+};
+using PvOlaBlock = LaunchTable<PvOlaEntry, kSamplePoolBlock>;
+// launch_istft_ola_window and launch_pv_frame_carry per entry: frames (rows, n_fft, ld), y (rows, y_stride) receives the samples [Y, Y2) of each
+// entry; fr0 / fr1: the pool's two (S, n_fft, G) frame carries
+fv_status launch_pv_pool_ola(const float* frames, float* fr0, float* fr1, const float* win2, float* y, const PvOlaEntry* tab, int rows, int n_fft,
+                             int hop, int pad, int G, int ld, long long y_stride, hipStream_t s);
+
 // The DFT bases the STFT / ISTFT convs are built from (engine_build.hip): the log-mel front-end, the ISTFT head and the pitch shift share them.
 // stft_basis: the window-folded real DFT in polyphase form, a (2 nb, hop, taps) conv weight — rows [0, nb) win[n] cos, [nb, 2 nb) -win[n] sin at
 // n = q hop + r, zero for n >= N.  istft_basis: the windowed inverse real DFT, an (N, 2 nb) pointwise weight — c_k cos / N win[n] | -c_k sin / N win[n].
@@ -516,6 +534,10 @@ fv_status resample_rows(const fv_resample* r, const char* fn, const float* x, lo
 // resample.hip: what a stream on r has emitted once N input samples have arrived (fv_resample_stream_push's rule), and Kp, the longest band
 long long resample_emit_count(const fv_resample* r, long long N);
 int resample_band_taps(const fv_resample* r);
+// resample.hip: the host half of a resampler — the design's sizes and the emission rule, no device table (fv_pvpool_plan); freed by
+// fv_resample_destroy.  And fv_respool_max_outputs for a pool of `max_chunk` on r.
+fv_status resample_rule_create(const fv_resample_config* cfg, const char* fn, fv_resample** out);
+long long resample_pool_max_outputs(const fv_resample* r, int max_chunk);
 
 // RefineGAN glue (small_kernels.hip): linear interpolation (nn.Upsample(mode="linear")) with optional leaky_relu, written into
 // a channel slice of a wider tensor; channel-slice copy; AdaIN with caller-supplied noise

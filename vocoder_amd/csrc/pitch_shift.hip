@@ -19,6 +19,13 @@
 //   pv_frame_carry_kernel        the last n_fft / hop synthesised frames, into the other buffer of the pair
 // with pv_polar_kernel, the two convs (always in batch-invariant mode) and an fv_resample_stream between and behind them.
 //
+// The pool (fv_pvpool_*) runs it for sessions that advance independently: the same bodies behind a third fetch, one table entry per item,
+//   pv_frame_pool_window_kernel   the window from the slot's carried samples plus the item's chunk row (frame_kernels.hip)
+//   pv_polar_pool_kernel          rows padded to the step's largest dA; every column from an entry's own dA on is written as zero
+//   pv_scan_synth_pool_kernel     the scan per (entry, k) row, the slot's polar carry in, its other half out
+//   istft_ola_pool_window_kernel, pv_frame_pool_carry_kernel   per-entry (S, dS, Tend, Y, Y2) and the slot's frame carry (frame_kernels.hip)
+// with the two convs once per step over all rows and an inner fv_respool behind them.
+//
 // Why integers: librosa's accumulator grows by about pi per hop and bin — 1e6 rad after 200 000 samples, where fp32 resolves 0.06 rad.  In
 // turns modulo 1 the sum never grows: a uint32 holds it to 2^-32 turns, exactly, in any summation order.
 #include <memory>
@@ -26,6 +33,7 @@
 #include <optional>
 
 #include "engine_internal.h"
+#include "sample_pool.h"
 #include "sample_stream.h"
 
 namespace fv {
@@ -33,7 +41,14 @@ namespace {
 
 constexpr int64_t kPvMaxLen = 1LL << 30;
 
-// mag = |D| (no epsilon: silence stays exact zero), theta = angle(D) in turns as uint32; columns T and T + 1 are zero
+// one bin of one column: |D| (no epsilon: silence stays exact zero) and angle(D) in turns as uint32
+__device__ __forceinline__ void pv_polar(float re, float im, float& m, uint32_t& th) {
+    m = sqrtf(fmaf(re, re, im * im));
+    th = 0u;
+    if (re != 0.f || im != 0.f) th = (uint32_t)__double2ll_rn((double)atan2f(im, re) * (4294967296.0 / (2.0 * M_PI)));
+}
+
+// mag = |D|, theta = angle(D); columns T and T + 1 are zero
 __global__ __launch_bounds__(256) void pv_polar_kernel(const float* __restrict__ spec, float* __restrict__ mag, uint32_t* __restrict__ theta,
                                                        int nb, int T) {
     const int T2 = T + 2;
@@ -45,12 +60,39 @@ __global__ __launch_bounds__(256) void pv_polar_kernel(const float* __restrict__
     uint32_t th = 0u;
     if (t < T) {
         const float* sb = spec + (long long)b * 2 * nb * T;
-        const float re = sb[(long long)k * T + t], im = sb[(long long)(nb + k) * T + t];
-        m = sqrtf(fmaf(re, re, im * im));
-        if (re != 0.f || im != 0.f) th = (uint32_t)__double2ll_rn((double)atan2f(im, re) * (4294967296.0 / (2.0 * M_PI)));
+        pv_polar(sb[(long long)k * T + t], sb[(long long)(nb + k) * T + t], m, th);
     }
     mag[(long long)b * nb * T2 + i] = m;
     theta[(long long)b * nb * T2 + i] = th;
+}
+
+// The pool's tables (fv_pvpool_step): tensor row k0 + (block index) is one entry, at most kSamplePoolBlock per launch, by value
+struct PvScanEntry {
+    int slot, pbit;        // the slot's polar carry is in pol[pbit]; an entry with dA > 0 or dS > 0 writes pol[pbit ^ 1]
+    int dA, dS;            // analysed columns [A, A + dA) and stretched frames [S, S + dS) of this row
+    long long A, S;
+};
+using PvScanBlock = LaunchTable<PvScanEntry, kSamplePoolBlock>;
+
+// pv_polar_kernel per entry: spec (rows, 2 nb, T) is the conv over rows padded to the launch's largest dA = T, mag / theta (rows, nb, T + 2).
+// Entry i owns the columns below dA_i; every column from dA_i on is WRITTEN as zero — column dA_i of the conv reads taps - 1 real polyphase
+// slots and is not zero on its own, and a flushing entry reads its columns dA_i and dA_i + 1 as the row's columns T and T + 1.
+__global__ __launch_bounds__(256) void pv_polar_pool_kernel(const float* __restrict__ spec, float* __restrict__ mag, uint32_t* __restrict__ theta,
+                                                            const PvScanBlock tab, int nb, int T, int k0) {
+    const int T2 = T + 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)nb * T2) return;
+    const long long row = k0 + blockIdx.y;
+    const int dA = tab.e[blockIdx.y].dA;
+    const int k = (int)(i / T2), t = (int)(i - (long long)k * T2);
+    float m = 0.f;
+    uint32_t th = 0u;
+    if (t < dA) {
+        const float* sb = spec + row * 2 * nb * T;
+        pv_polar(sb[(long long)k * T + t], sb[(long long)(nb + k) * T + t], m, th);
+    }
+    mag[row * nb * T2 + i] = m;
+    theta[row * nb * T2 + i] = th;
 }
 
 // One wave walks the dS output columns [start, start + dS) of one (b, k) row 64 at a time, kPvUnroll chunks per trip.  Column s: q = s n, j = q / o,
@@ -168,6 +210,39 @@ __global__ __launch_bounds__(256) void pv_scan_synth_stream_kernel(const float* 
         nphi[row] = carry;
         nmag[row] = dA > 0 ? cols.mr[dA - 1] : cols.cm;
         ntheta[row] = dA > 0 ? cols.tr[dA - 1] : cols.ct;
+    }
+}
+
+// pv_scan_synth_stream_kernel per entry: grid (groups of 4 bins, entries), so a wave is one (entry, k) row and the scan's shuffles see 64
+// lanes of one row.  mag / theta: (rows, nb, T + 2) and spec (rows, 2 nb, ld), T / ld the launch's largest dA / dS; the entry's window has its
+// own dA, and the columns [dS, ld) of its spec rows are written as zeros.  pol0 / pol1: the pool's two polar carries, each
+// [mag (S, nb) | theta (S, nb) | phi (S, nb)] with `sn` = S nb; the entry reads half pbit and, if it analysed or synthesised, writes the other.
+__global__ __launch_bounds__(256) void pv_scan_synth_pool_kernel(const float* __restrict__ mag, const uint32_t* __restrict__ theta,
+                                                                 const float* pol0, const float* pol1, float* __restrict__ spec,
+                                                                 const PvScanBlock tab, long long sn, int nb, int T, int ld, int o, int n, int k0) {
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= nb) return;   // (whole waves leave: the shuffles of the scan always see 64 lanes)
+    const PvScanEntry e = tab.e[blockIdx.y];
+    const long long row = (long long)(k0 + blockIdx.y) * nb + k, cr = (long long)e.slot * nb + k;
+    const float* cur = e.pbit ? pol1 : pol0;
+    float* next = (float*)(e.pbit ? pol0 : pol1);
+    float* re = spec + ((long long)(k0 + blockIdx.y) * 2 * nb + k) * ld;
+    float* im = re + (long long)nb * ld;
+    for (int c = e.dS + (threadIdx.x & 63); c < ld; c += 64) re[c] = 0.f, im[c] = 0.f;
+    if (e.dA <= 0 && e.dS <= 0) return;
+    const PvWindowCols cols{mag + row * (T + 2), theta + row * (T + 2), cur[cr], ((const uint32_t*)cur)[sn + cr], e.A, e.dA};
+    uint32_t carry;
+    {
+        float m0;
+        uint32_t t0;
+        cols(0, m0, t0);   // (S = 0 means A <= 1: column 0 is in the window or is the carried one)
+        carry = e.S == 0 ? t0 : ((const uint32_t*)cur)[2 * sn + cr];
+    }
+    pv_scan_row(cols, re, im, e.S, e.dS, carry, o, n);
+    if ((threadIdx.x & 63) == 0) {
+        ((uint32_t*)next)[2 * sn + cr] = carry;
+        next[cr] = e.dA > 0 ? cols.mr[e.dA - 1] : cols.cm;
+        ((uint32_t*)next)[sn + cr] = e.dA > 0 ? cols.tr[e.dA - 1] : cols.ct;
     }
 }
 
@@ -577,7 +652,400 @@ static fv_status pv_stream_step(fv_pv_stream* st, const float* d_x, int64_t x_ro
     return FV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The pool (fv_pvpool_*): the sample pool's counters and sample carry (sample_pool.h) around the stream's chain, every stage behind a per-entry
+// fetch.  Per slot two more ping-pong pairs with a bit each: the polar carry (pbit flips when the step analysed or synthesised for the slot)
+// and the last G frames (fbit flips when it synthesised).  The resampler stage is an inner fv_respool on the shifter's own resampler.
+// ---------------------------------------------------------------------------------------------
+// The host rule of one pool: everything fv_pvpool_plan needs.  rs: the resampler's rule (NULL for the identity shift).
+struct PvPoolRule {
+    Plan pl;
+    const fv_resample* rs = nullptr;
+    int max_chunk = 0;
+    long long maxA = 0, maxS = 0, maxY = 0, maxR = 0, max_out = 0;
+    bool identity() const { return rs == nullptr; }
+    long long emitted_after(long long N) const {   // E(N) between flushes
+        return std::min(resample_emit_count(rs, stream_ready(pl, N).Y), N);
+    }
+};
+
+// The bounds of one step, for a push of max_chunk = c samples that also flushes, from any state N (N2 = N + c):
+//   dA = T(N2) - A(N) <= (c + F / 2) / h + 1: T = 1 + N2 / h, and A(N) = (N - F / 2) / h + 1 (0 below F / 2, where T <= 1 + (c + F / 2 - 1) / h)
+//   dS = T'(N2) - S(N) <= ceil((dA + 1) o / n) + 1: T' = ceil(T o / n), S = ceil((A - 1) o / n) (0 for A < 2, which is that formula's value or above)
+//   dY = Ls(N2) - Y(N) < dS h + F where Y = max(0, S h - F / 2) (Ls < T' h + F / 2), and <= c o / n + 1 where Y = Ls(N)
+//   the resampler: an inner pool item of dY <= maxY samples that flushes, fv_respool_max_outputs of that pool
+//   outputs: N2 - E(N) = c + (N - E(N)).  N - E(N) grows by one per sample and falls only where A(N) steps, at N = F / 2 + a h, so its largest
+//   value stands at some N_a = F / 2 + a h - 1.  A step of a by n moves S by o, Y by o h and the resampler's count by n h = the step of N: past
+//   the start-up (Y beyond the resampler's clamp at 0) N - E(N) has period n in a, and in the start-up every clamp (A, S, Y, the count at 0)
+//   only raises E.  So the bound is the largest N_a - E(N_a) over n consecutive a past the start-up: exact, some state attains it.
+static void pvpool_bounds(PvPoolRule& r) {
+    const Plan& pl = r.pl;
+    const long long c = r.max_chunk;
+    if (r.identity()) {
+        r.max_out = c;
+        return;
+    }
+    const long long F = pl.N, h = pl.hop, o = pl.o, n = pl.n;
+    r.maxA = (c + F / 2) / h + 2;
+    r.maxS = ((r.maxA + 1) * o + n - 1) / n + 2;
+    r.maxY = std::max(r.maxS * h + F, (c * o + n - 1) / n + 2);
+    r.maxR = r.maxY <= (1 << 28) ? resample_pool_max_outputs(r.rs, (int)r.maxY) : 0;
+    const long long need = 4 * o + 2LL * resample_band_taps(r.rs);
+    long long a0 = (((need + F) * n + o - 1) / o + 2 * F + 2 * h) / h + 2;
+    while (stream_ready(pl, F / 2 + a0 * h - 1).Y < need) a0 += n;
+    long long lag = 0;
+    for (long long a = a0; a < a0 + n; ++a) {
+        const long long N = F / 2 + a * h - 1;
+        lag = std::max(lag, N - r.emitted_after(N));
+    }
+    r.max_out = c + lag;
+}
+
+// What one item does in a step; all of it host arithmetic from the slot's N and E
+struct PvPoolMove {
+    long long N = 0, N2 = 0, E2 = 0, k = 0, keep = 0;   // keep: outputs that come from the resampler, the rest of k are zeros
+    Ready r1, r2;
+    long long dA = 0, dS = 0, dY = 0, Er = 0, Er2 = 0;  // the inner pool's emitted count before and after
+    bool active = false;                                // the item runs the chain (a row of the step's tensors)
+};
+
+// The pool's own plan after sample_pool_admit: the 2^30 limit and the step's bounds, each refusal naming item and session.  Changes nothing.
+static fv_status pvpool_moves(const PvPoolRule& r, const char* fn, const int64_t* received, const int64_t* emitted, const fv_wavpool_item* items,
+                              int count, const long long* N2, std::vector<PvPoolMove>& mv) {
+    mv.assign((size_t)std::max(count, 0), PvPoolMove());
+    for (int i = 0; i < count; ++i) {
+        const int s = items[i].session;
+        const bool flush = items[i].flush != 0;
+        PvPoolMove& m = mv[(size_t)i];
+        m.N = received[s], m.N2 = N2[i];
+        const long long E = emitted[s];
+        if (m.N2 > kPvMaxLen) {
+            set_error("%s: item %d takes session %d past 2^30 samples in one utterance (%lld + %d)", fn, i, s, m.N, items[i].samples);
+            return FV_ERR_INVALID;
+        }
+        if (r.identity()) {   // rate 1: the item's own samples
+            m.E2 = E + items[i].samples, m.k = m.keep = items[i].samples;
+            continue;
+        }
+        if (flush && m.N2 == 0) continue;   // an utterance without samples: nothing to analyse, nothing comes out
+        m.r1 = stream_ready(r.pl, m.N), m.r2 = stream_ready(r.pl, m.N2);
+        if (flush) {
+            const Lengths l = lengths_of(r.pl, m.N2);
+            m.r2.A = l.T, m.r2.S = l.Tout, m.r2.Y = l.Ls;
+        }
+        m.dA = m.r2.A - m.r1.A, m.dS = m.r2.S - m.r1.S, m.dY = m.r2.Y - m.r1.Y;
+        m.Er = resample_emit_count(r.rs, m.r1.Y);
+        m.Er2 = flush ? std::max(m.Er, (long long)fv_resample_output_length(r.rs, m.r2.Y)) : std::max(m.Er, resample_emit_count(r.rs, m.r2.Y));
+        if (!flush && m.Er2 > m.N2) {   // (not reached for lowpass_filter_width >= 1: an output's band ends after the samples its own index stands for)
+            set_error("%s: internal: item %d (session %d): the resampler would emit output %lld after %lld input samples", fn, i, s, m.Er2 - 1, m.N2);
+            return FV_ERR_INVALID;
+        }
+        m.E2 = flush ? m.N2 : std::max<long long>(E, std::min(m.Er2, m.N2));
+        m.k = m.E2 - E;
+        m.keep = std::max(0LL, std::min(m.k, std::min(m.Er2, m.N2) - E));
+        if (m.dA < 0 || m.dS < 0 || m.dY < 0 || m.k < 0 || E != std::min(m.Er, m.N) || m.dA > r.maxA || m.dS > r.maxS || m.dY > r.maxY ||
+            m.Er2 - m.Er > r.maxR || m.k > r.max_out) {
+            set_error("%s: internal: item %d (session %d): %lld frames, %lld stretched frames, %lld stretched samples, %lld resampled, %lld outputs in "
+                      "one step from N = %lld, E = %lld; the pool was sized for %lld, %lld, %lld, %lld, %lld", fn, i, s, m.dA, m.dS, m.dY,
+                      m.Er2 - m.Er, m.k, m.N, (long long)E, r.maxA, r.maxS, r.maxY, r.maxR, r.max_out);
+            return FV_ERR_INVALID;
+        }
+        m.active = flush || m.dA > 0 || m.dS > 0 || m.dY > 0;
+    }
+    return FV_OK;
+}
+
+static fv_status pvpool_range(const char* fn, int sessions, int max_chunk, const PvPoolRule* r) {
+    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
+        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);
+        return FV_ERR_INVALID;
+    }
+    if (r && !r->identity() && (r->maxY > (1 << 28) || r->maxR > (1LL << 30) || (long long)r->pl.N * r->maxS >= (1LL << 31))) {
+        set_error("%s: max_chunk = %d gives %lld stretched frames of %d samples in one step, more than 2^31 elements per row or 2^28 stretched "
+                  "samples; push smaller chunks", fn, max_chunk, r->maxS, r->pl.N);
+        return FV_ERR_UNSUPPORTED;
+    }
+    return FV_OK;
+}
+
+struct fv_pvpool : SamplePool {
+    fv_pitch_shift* p = nullptr;
+    fv_respool* rs = nullptr;            // NULL for the pass-through
+    PvPoolRule rule;
+    int G = 0;
+    float* pol[2] = {nullptr, nullptr};  // one allocation: per half [mag (S, nb) | theta (S, nb) | phi (S, nb)]
+    float* fr[2] = {nullptr, nullptr};   // one allocation: (S, n_fft, G) each
+    std::vector<unsigned char> pbit, fbit;
+    ~fv_pvpool() {
+        fv_respool_destroy(rs);
+        if (pol[0]) (void)hipFree(pol[0]);
+        if (fr[0]) (void)hipFree(fr[0]);
+    }
+    fv_pitch_shift::Parts carve(float* ws) const {
+        return p->carve(ws, S, (size_t)rule.maxA, (size_t)rule.maxS, (size_t)rule.maxY, (size_t)rule.maxR);
+    }
+    size_t ws_bytes() const { return rule.identity() ? 0 : align_up(carve(nullptr).elems * sizeof(float), 256); }
+};
+
 extern "C" {
+
+FV_API fv_status fv_pvpool_create(fv_pitch_shift* p, int32_t sessions, int32_t max_chunk, fv_pvpool** out) {
+    const char* fn = "fv_pvpool_create";
+    if (out) *out = nullptr;
+    if (!p || !out) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    if (const fv_status rs = pvpool_range(fn, sessions, max_chunk, nullptr)) return rs;
+    std::unique_ptr<fv_pvpool> q(new fv_pvpool());
+    q->p = p;
+    q->rule.pl = p->plan, q->rule.rs = p->identity() ? nullptr : p->rs, q->rule.max_chunk = max_chunk;
+    pvpool_bounds(q->rule);
+    if (const fv_status rs = pvpool_range(fn, sessions, max_chunk, &q->rule)) return rs;
+    q->pbit.assign((size_t)sessions, 0), q->fbit.assign((size_t)sessions, 0);
+    if (p->identity()) {   // the pass-through carries nothing
+        q->init(sessions, max_chunk, 0);
+        *out = q.release();
+        return FV_OK;
+    }
+    const int F = p->plan.N;
+    if (const fv_status rs = q->create(fn, sessions, max_chunk, F)) return rs;
+    q->G = F / p->plan.hop;   // (fv_pv_stream_create's note on G)
+    const size_t pol = 3 * (size_t)sessions * p->nb, frm = (size_t)sessions * F * q->G;
+    FV_HIP_CHECK(hipMalloc((void**)&q->pol[0], 2 * pol * sizeof(float)));
+    q->pol[1] = q->pol[0] + pol;
+    FV_HIP_CHECK(hipMemset(q->pol[0], 0, 2 * pol * sizeof(float)));
+    FV_HIP_CHECK(hipMalloc((void**)&q->fr[0], 2 * frm * sizeof(float)));
+    q->fr[1] = q->fr[0] + frm;
+    FV_HIP_CHECK(hipMemset(q->fr[0], 0, 2 * frm * sizeof(float)));
+    if (const fv_status rs = fv_respool_create(p->rs, sessions, (int32_t)q->rule.maxY, &q->rs)) return rs;
+    *out = q.release();
+    return FV_OK;
+}
+
+FV_API size_t fv_pvpool_workspace_bytes(const fv_pvpool* p) { return p ? p->ws_bytes() : 0; }
+
+FV_API int64_t fv_pvpool_max_outputs(const fv_pvpool* p) { return p ? p->rule.max_out : 0; }
+
+FV_API int64_t fv_pvpool_received(const fv_pvpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+
+FV_API int64_t fv_pvpool_emitted(const fv_pvpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+
+FV_API int64_t fv_pvpool_pending(const fv_pvpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] - p->E[(size_t)s] : 0; }
+
+struct RuleHold {
+    fv_resample* r = nullptr;
+    ~RuleHold() { fv_resample_destroy(r); }
+};
+// the host rule of a config: the plan, the resampler's rule (owned by `hold`) and the bounds
+static fv_status pvpool_rule(const fv_pitch_shift_config* cfg, const char* fn, int max_chunk, PvPoolRule& r, RuleHold& hold) {
+    if (const fv_status st = make_plan(cfg, fn, r.pl)) return st;
+    r.max_chunk = max_chunk;
+    const fv_resample_config rc = resample_config(*cfg, r.pl);
+    fv_resample* rs = nullptr;
+    if (const fv_status st = resample_rule_create(&rc, fn, &rs)) return st;
+    hold.r = rs;
+    r.rs = r.pl.orig_freq == cfg->sample_rate ? nullptr : rs;
+    pvpool_bounds(r);
+    return FV_OK;
+}
+
+FV_API fv_status fv_pvpool_bounds(const fv_pitch_shift_config* cfg, int32_t max_chunk, int64_t* bounds) {
+    const char* fn = "fv_pvpool_bounds";
+    if (!bounds) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    if (const fv_status st = pvpool_range(fn, 1, max_chunk, nullptr)) return st;
+    PvPoolRule r;
+    RuleHold hold;
+    if (const fv_status st = pvpool_rule(cfg, fn, max_chunk, r, hold)) return st;
+    if (const fv_status st = pvpool_range(fn, 1, max_chunk, &r)) return st;
+    bounds[0] = r.maxA, bounds[1] = r.maxS, bounds[2] = r.maxY, bounds[3] = r.maxR, bounds[4] = r.max_out;
+    return FV_OK;
+}
+
+FV_API int64_t fv_pvpool_plan(const fv_pitch_shift_config* cfg, int32_t sessions, int32_t max_chunk, const int64_t* received,
+                              const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
+                              int64_t* outputs_out) {
+    const char* fn = "fv_pvpool_plan";
+    if (const fv_status st = pvpool_range(fn, sessions, max_chunk, nullptr)) return st;
+    PvPoolRule r;
+    RuleHold hold;
+    if (const fv_status st = pvpool_rule(cfg, fn, max_chunk, r, hold)) return st;
+    if (const fv_status st = pvpool_range(fn, sessions, max_chunk, &r)) return st;
+    if (!received || !emitted || (count > 0 && !outputs_out)) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::vector<long long> N2((size_t)std::max(count, 0));
+    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk, received, flushed, items, count, false, nullptr, 0, N2.data()))
+        return rs;
+    std::vector<PvPoolMove> mv;
+    if (const fv_status rs = pvpool_moves(r, fn, received, emitted, items, count, N2.data(), mv)) return rs;
+    int64_t k_max = 0;
+    for (int i = 0; i < count; ++i) {
+        outputs_out[i] = mv[(size_t)i].k;
+        k_max = std::max<int64_t>(k_max, outputs_out[i]);
+    }
+    return k_max;
+}
+
+FV_API fv_status fv_pvpool_step(fv_pvpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
+                                float* d_out, int64_t out_stride, int32_t out_cols, int64_t* outputs_out, void* d_workspace,
+                                size_t workspace_bytes, void* stream) {
+    const char* fn = "fv_pvpool_step";
+    if (!p) {
+        set_error("%s: null pool", fn);
+        return FV_ERR_INVALID;
+    }
+    for (int i = 0; outputs_out && i < count; ++i) outputs_out[i] = 0;
+    // the whole step on the host first: the core's refusals, the pool's own plan, the inner pool's state, the output and the workspace
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status rs = p->admit(fn, "fv_pvpool_reset", items, count, d_chunks, chunk_stride, N2.data())) return rs;
+    std::vector<PvPoolMove> mv;
+    if (const fv_status rs = pvpool_moves(p->rule, fn, p->N.data(), p->E.data(), items, count, N2.data(), mv)) return rs;
+    long long k_max = 0;
+    int k_item = 0, nact = 0;
+    for (int i = 0; i < count; ++i) {
+        const PvPoolMove& m = mv[(size_t)i];
+        E2[(size_t)i] = m.E2;
+        if (m.k > k_max) k_max = m.k, k_item = i;
+        if (!m.active) continue;
+        ++nact;
+        const int s = items[i].session;
+        if (fv_respool_received(p->rs, s) != m.r1.Y || fv_respool_emitted(p->rs, s) != m.Er) {
+            set_error("%s: internal: item %d (session %d): the inner resample pool stands at (%lld, %lld) where the rule says (%lld, %lld)", fn, i, s,
+                      (long long)fv_respool_received(p->rs, s), (long long)fv_respool_emitted(p->rs, s), m.r1.Y, m.Er);
+            return FV_ERR_INVALID;
+        }
+    }
+    const int k_session = count > 0 ? items[k_item].session : -1;
+    if (out_cols < k_max || out_cols < 0) {
+        set_error("%s: out_cols = %d, but item %d (session %d) emits %lld outputs in this step", fn, out_cols, k_item, k_session, k_max);
+        return FV_ERR_INVALID;
+    }
+    if (out_stride < out_cols) {
+        set_error("%s: out_stride = %lld is shorter than out_cols = %d (item %d, session %d, emits %lld outputs)", fn, (long long)out_stride,
+                  out_cols, k_item, k_session, k_max);
+        return FV_ERR_INVALID;
+    }
+    if (k_max > 0 && !d_out) {
+        set_error("%s: null output although item %d (session %d) emits %lld outputs", fn, k_item, k_session, k_max);
+        return FV_ERR_INVALID;
+    }
+    if (nact > 0 && (!d_workspace || workspace_bytes < p->ws_bytes())) {
+        int a = 0;
+        while (!mv[(size_t)a].active) ++a;
+        set_error("%s: workspace too small (%zu < %zu bytes, fv_pvpool_workspace_bytes) for item %d (session %d)", fn,
+                  d_workspace ? workspace_bytes : (size_t)0, p->ws_bytes(), a, items[a].session);
+        return FV_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const auto done = [&]() {
+        for (int i = 0; outputs_out && i < count; ++i) outputs_out[i] = mv[(size_t)i].k;
+        for (int i = 0; i < count; ++i) {
+            const PvPoolMove& m = mv[(size_t)i];
+            const size_t sl = (size_t)items[i].session;
+            if (m.dA > 0 || m.dS > 0) p->pbit[sl] ^= 1;
+            if (m.dS > 0) p->fbit[sl] ^= 1;
+        }
+        p->commit(items, count, N2.data(), E2.data());
+        return FV_OK;
+    };
+    std::vector<PoolCropEntry> crop((size_t)count);
+    if (p->rule.identity()) {   // rate 1: every item's samples back bit for bit, zeros behind them
+        for (int i = 0; i < count; ++i) crop[(size_t)i] = PoolCropEntry{i, items[i].samples > 0 ? i : -1, 0, items[i].samples};
+        if (d_out && out_cols > 0)
+            if (const fv_status rs = launch_pool_crop(d_chunks, d_out, crop.data(), count, 1, chunk_stride, out_cols, 1, s, out_stride)) return rs;
+        return done();
+    }
+    // the step's tables: one row of the workspace tensors per active item, in item order
+    const fv_pitch_shift* ps = p->p;
+    const Plan& pl = ps->plan;
+    const int hop = pl.hop, F = pl.N, nb = ps->nb, H = p->H;
+    std::vector<SamplePoolEntry> win, carry;
+    std::vector<PvScanEntry> scan;
+    std::vector<PvOlaEntry> ola;
+    std::vector<fv_wavpool_item> inner;
+    long long dA_max = 0, dS_max = 0, ki_max = 0;
+    bool any_scan = false;
+    for (int i = 0; i < count; ++i) {
+        const PvPoolMove& m = mv[(size_t)i];
+        const int sl = items[i].session;
+        const SamplePoolEntry en{i, sl, (int)p->cur[(size_t)sl], (int)m.dA, m.N - H, m.N, items[i].flush ? m.N2 : -1, m.N2, m.r1.A};
+        if (items[i].samples > 0) carry.push_back(en);
+        crop[(size_t)i] = PoolCropEntry{i, m.active && m.keep > 0 ? (int)win.size() : -1, 0, m.keep};
+        if (!m.active) continue;
+        win.push_back(en);
+        scan.push_back(PvScanEntry{sl, (int)p->pbit[(size_t)sl], (int)m.dA, (int)m.dS, m.r1.A, m.r1.S});
+        ola.push_back(PvOlaEntry{sl, (int)p->fbit[(size_t)sl], (int)m.dS, 0, m.r1.S, m.r2.S, m.r1.Y, m.r2.Y});
+        inner.push_back(fv_wavpool_item{sl, (int32_t)m.dY, items[i].flush});
+        dA_max = std::max(dA_max, m.dA), dS_max = std::max(dS_max, m.dS), ki_max = std::max(ki_max, m.Er2 - m.Er);
+        any_scan = any_scan || m.dA > 0 || m.dS > 0;
+    }
+    if (nact > 0) {
+        const fv_pitch_shift::Parts w = p->carve((float*)d_workspace);
+        const int T = (int)dA_max, ld = (int)dS_max;
+        {
+            const AlgoScope scope(FV_CONV_ALGO_AUTO, true);   // every column one fixed-order sum, whatever the launch holds
+            if (T > 0) {
+                const int TP = T + ps->taps - 1;
+                if (const fv_status rs = launch_pv_frame_pool_window(p->buf[0], p->buf[1], H, d_chunks, chunk_stride, win.data(), nact, w.Yp, hop, TP,
+                                                                     ps->taps, F / 2, s))
+                    return rs;
+                ConvRun r;
+                r.batch = nact, r.t_in = TP, r.x = w.Yp, r.y = w.Sp;
+                if (const fv_status rs = conv_layer_run(ps->stft, r, s)) return rs;
+            }
+            if (any_scan) {
+                const long long per = (long long)nb * (T + 2), sn = (long long)p->S * nb;
+                const fv_status rs = for_each_launch_table<PvScanBlock>(nact, scan.data(), [&](const PvScanBlock& blk, int k0, int nz) {
+                    hipLaunchKernelGGL(pv_polar_pool_kernel, dim3((unsigned)((per + 255) / 256), nz), dim3(256), 0, s, w.Sp, w.Mg, w.Th, blk, nb, T, k0);
+                    hipLaunchKernelGGL(pv_scan_synth_pool_kernel, dim3((nb + 3) / 4, nz), dim3(256), 0, s, w.Mg, w.Th, p->pol[0], p->pol[1], w.S2, blk,
+                                       sn, nb, T, ld, pl.o, pl.n, k0);
+                    return FV_OK;
+                });
+                if (rs) return rs;
+                set_last_kernel("pv_scan_synth_pool_kernel");
+            }
+            if (ld > 0) {
+                ConvRun r;
+                r.batch = nact, r.t_in = ld, r.x = w.S2, r.y = w.Fr;
+                if (const fv_status rs = conv_layer_run(ps->idft, r, s)) return rs;
+            }
+        }
+        if (const fv_status rs = launch_pv_pool_ola(w.Fr, p->fr[0], p->fr[1], ps->d_win2, w.St, ola.data(), nact, F, hop, F / 2, p->G, std::max(ld, 1),
+                                                    p->rule.maxY, s))
+            return rs;
+        // the resampler: the inner pool takes this step's stretched samples and writes Rs; a flush's surplus past N' is cut by the crop below
+        if (const fv_status rs = fv_respool_step(p->rs, inner.data(), nact, w.St, p->rule.maxY, w.Rs, p->rule.maxR, (int32_t)ki_max, nullptr, stream))
+            return rs;
+        for (int i = 0; i < count; ++i)   // an item flushed at N' > 0 leaves its inner slot flushed too; fv_pvpool_reset resets both
+            if (mv[(size_t)i].active && fv_respool_emitted(p->rs, items[i].session) != mv[(size_t)i].Er2) {
+                set_error("%s: internal: the inner resample pool emitted up to %lld for session %d where the rule says %lld", fn,
+                          (long long)fv_respool_emitted(p->rs, items[i].session), items[i].session, mv[(size_t)i].Er2);
+                return FV_ERR_INVALID;
+            }
+    }
+    if (const fv_status rs = launch_sample_pool_carry(p->buf[0], p->buf[1], H, d_chunks, chunk_stride, carry.data(), (int)carry.size(), s)) return rs;
+    if (d_out && out_cols > 0)
+        if (const fv_status rs = launch_pool_crop(nact > 0 ? p->carve((float*)d_workspace).Rs : nullptr, d_out, crop.data(), count, 1, p->rule.maxR,
+                                                  out_cols, 1, s, out_stride))
+            return rs;
+    return done();
+}
+
+FV_API fv_status fv_pvpool_reset(fv_pvpool* p, int32_t session) {
+    if (!p) {
+        set_error("fv_pvpool_reset: null pool");
+        return FV_ERR_INVALID;
+    }
+    if (const fv_status rs = p->reset("fv_pvpool_reset", session)) return rs;
+    return p->rs ? fv_respool_reset(p->rs, session) : FV_OK;
+}
+
+FV_API void fv_pvpool_destroy(fv_pvpool* p) { delete p; }
 
 FV_API fv_status fv_pitch_shift_plan(const fv_pitch_shift_config* cfg, int32_t* orig_freq, int32_t* o, int32_t* n) {
     Plan p;

@@ -684,6 +684,14 @@ static long long respool_max_outputs(const fv_resample& r, int max_chunk) {
     return best;
 }
 
+fv_status fv::resample_rule_create(const fv_resample_config* cfg, const char* fn, fv_resample** out) {
+    std::unique_ptr<fv_resample> r(new fv_resample());
+    if (const fv_status st = resample_rule(cfg, fn, *r)) return st;
+    *out = r.release();
+    return FV_OK;
+}
+long long fv::resample_pool_max_outputs(const fv_resample* r, int max_chunk) { return respool_max_outputs(*r, max_chunk); }
+
 static fv_status respool_range(const char* fn, int sessions, int max_chunk) {
     if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
         set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);

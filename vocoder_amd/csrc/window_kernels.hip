@@ -241,21 +241,22 @@ fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const 
     });
 }
 __global__ __launch_bounds__(256) void pool_crop_kernel(const float* __restrict__ y, float* __restrict__ out, const PoolCropBlock tab, int C,
-                                                        long long Ly, long long out_cols, int hop) {
+                                                        long long Ly, long long out_cols, int hop, long long out_stride) {
     const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
     if (j >= out_cols) return;
     const PoolCropEntry e = tab.e[blockIdx.z];
     const int c = blockIdx.y;
     float v = 0.0f;
     if (e.row >= 0 && j < e.len * hop) v = y[((long long)e.row * C + c) * Ly + e.src * hop + j];
-    out[((long long)e.item * C + c) * out_cols + j] = v;
+    out[((long long)e.item * C + c) * out_stride + j] = v;
 }
 fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames, int hop,
-                           hipStream_t s) {
+                           hipStream_t s, long long out_stride) {
     if (out_frames <= 0) return FV_OK;
+    if (out_stride <= 0) out_stride = out_frames * hop;
     return for_each_launch_table<PoolCropBlock>(count, tab, [&](const PoolCropBlock& blk, int, int nz) {
         hipLaunchKernelGGL(pool_crop_kernel, dim3((unsigned)((out_frames * hop + 255) / 256), C, nz), dim3(256), 0, s, y, out, blk, C, Ly * hop,
-                           out_frames * hop, hop);
+                           out_frames * hop, hop, out_stride);
         return FV_OK;
     });
 }

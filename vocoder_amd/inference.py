@@ -398,12 +398,17 @@ class WavSessionPool:
     ``input_resample`` (a ``Resample`` from the client's rate to the model's) puts a ``ResamplePool`` in front: ``max_chunk_samples`` and the
     items' samples then count the client's samples.  ``output_resample`` (from the model's rate to the client's) puts one behind, a slot per
     session and output channel, and the audio comes back at its ``new_freq``: ``(C_out, k)`` with the ``k`` outputs whose bands have
-    arrived.  ``end`` flushes every stage in the same step."""
+    arrived.  ``end`` flushes every stage in the same step.
+
+    ``pitch_shift`` (a ``vocoder_amd.pitch_shift.PitchShift`` at the front-end's rate; ``batch_invariant=True`` for bits that do not depend on
+    the chunking) puts a ``PitchShiftPool`` behind ``input_resample``, if any, and in front of both the wav pool and the template pool — where
+    ``stream_wav_synthesis`` puts its stream: the mel and the template are made from the shifted audio.  One ``n_steps`` serves every session.
+    The shifter hands back as many samples as it takes, so utterance lengths and the join's frame check hold as without it."""
 
     _TEMPLATE_KEYS = ("frame_length", "fmin", "fmax", "threshold", "kind", "amplitude")
 
     def __init__(self, frontend: nn.Module, generator: nn.Module, sessions: int, max_chunk_samples: int, input_resample=None,
-                 output_resample=None, template: dict | None = None):
+                 output_resample=None, template: dict | None = None, pitch_shift=None):
         if takes_template(generator) and template is None:
             raise ValueError(f"WavSessionPool: {type(generator).__name__} takes a pitch template next to the mel; the per-session F0 / template "
                              "pool it would need is not built (the template streams advance in lockstep) unless template= is passed: a dict "
@@ -417,12 +422,18 @@ class WavSessionPool:
         if not hasattr(frontend, "wav_pool") or not hasattr(generator, "session_pool"):
             raise ValueError(f"WavSessionPool needs a front-end with wav_pool() and a generator with session_pool(), got "
                              f"{type(frontend).__name__} and {type(generator).__name__}")
-        self.in_pool = self.out_pool = self.wav_pool = self.gen_pool = self.template_pool = None
+        self.in_pool = self.out_pool = self.wav_pool = self.gen_pool = self.template_pool = self.shift_pool = None
         wav_chunk = max_chunk_samples
-        if input_resample is None and output_resample is None:
+        if input_resample is None and output_resample is None and pitch_shift is None:
             self.wav_pool = frontend.wav_pool(sessions, max_chunk_samples)
         else:
             sr = getattr(frontend, "sampling_rate", None) or getattr(frontend, "sample_rate", None)
+            if pitch_shift is not None:
+                if not hasattr(pitch_shift, "pool") or not hasattr(pitch_shift, "sample_rate"):
+                    raise ValueError(f"WavSessionPool: pitch_shift must be a vocoder_amd.pitch_shift.PitchShift, got {type(pitch_shift).__name__}")
+                if sr is not None and int(pitch_shift.sample_rate) != int(sr):
+                    raise ValueError(f"WavSessionPool: pitch_shift has sample_rate = {pitch_shift.sample_rate} Hz, but it feeds a front-end that "
+                                     f"runs at {sr} Hz")
             for name, r, end, what in (("input_resample", input_resample, "new_freq", "feeds"),
                                        ("output_resample", output_resample, "orig_freq", "takes the audio of")):
                 if r is None:
@@ -436,6 +447,9 @@ class WavSessionPool:
                 if input_resample is not None:
                     self.in_pool = input_resample.pool(sessions, max_chunk_samples)
                     wav_chunk = max(self.in_pool.max_outputs, 1)
+                if pitch_shift is not None:    # the wav and template pools are sized by what one shifter item can emit
+                    self.shift_pool = pitch_shift.pool(sessions, wav_chunk)
+                    wav_chunk = max(self.shift_pool.max_outputs, 1)
                 self.wav_pool = frontend.wav_pool(sessions, wav_chunk)
             except Exception:
                 self.close()
@@ -481,12 +495,13 @@ class WavSessionPool:
                 raise ValueError(f"expected a 1-D chunk of samples, got {tuple(x.shape)}")
             rows.append(x)
             meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(end)))
-        ip, op, C = self.in_pool, self.out_pool, gp.out_channels
-        for pool in (ip, op) + ((tp.tracker, tp.template) if tp is not None else ()):
+        ip, sp, op, C = self.in_pool, self.shift_pool, self.out_pool, gp.out_channels
+        for pool in (ip, sp, op) + ((tp.tracker, tp.template) if tp is not None else ()):
             if pool is not None:
                 pool._check_open()
         # every stage's plan before anything moves (each refuses what its library would); the counts pass from stage to stage as host integers
-        wav_items = meta if ip is None else [(s, k, end) for (s, _, end), k in zip(meta, ip.counters.plan(meta))]
+        shift_items = meta if ip is None else [(s, k, end) for (s, _, end), k in zip(meta, ip.counters.plan(meta))]
+        wav_items = shift_items if sp is None else [(s, k, end) for (s, _, end), k in zip(meta, sp.counters.plan(shift_items))]
         frames = wp.counters.plan(wav_items)
         release = frames if tp is None else self._plan_join(wav_items, frames, tp.counters.plan(wav_items)[1])
         gen_items = [(s, k, end) for (s, _, end), k in zip(meta, release)]
@@ -497,6 +512,9 @@ class WavSessionPool:
         chunks = self._chunks(meta, rows)
         if ip is not None:
             chunks, _ = ip.step_padded(meta, chunks)
+            chunks = chunks if chunks.shape[1] else None
+        if sp is not None:
+            chunks, _ = sp.step_padded(shift_items, chunks)
             chunks = chunks if chunks.shape[1] else None
         mel, _ = wp.step_padded(wav_items, chunks)
         if tp is None:
@@ -565,6 +583,8 @@ class WavSessionPool:
         """The next utterance of one slot, in every pool."""
         if self.in_pool is not None:
             self.in_pool.reset(session)
+        if self.shift_pool is not None:
+            self.shift_pool.reset(session)
         self.wav_pool.reset(session)
         self.gen_pool.reset(session)
         if self.template_pool is not None:
@@ -575,7 +595,7 @@ class WavSessionPool:
                 self.out_pool.reset(int(session) * self.gen_pool.out_channels + ch)
 
     def close(self) -> None:
-        for name in ("in_pool", "wav_pool", "template_pool", "gen_pool", "out_pool"):
+        for name in ("in_pool", "shift_pool", "wav_pool", "template_pool", "gen_pool", "out_pool"):
             if getattr(self, name, None) is not None:
                 getattr(self, name).close()
 
