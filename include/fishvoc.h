@@ -1426,6 +1426,38 @@ FV_API fv_status fv_posterior_forward(fv_posterior* p, const float* d_x, int64_t
                                       void* stream);
 FV_API void fv_posterior_destroy(fv_posterior* p);
 
+/* -------- posterior encoder, chunk by chunk (fv_wnstream_*) --------
+ * `batch` rows advance in lockstep, as in fv_logmel_stream_* and fv_pv_stream_*.  With R = fv_posterior_reach_frames, N frames received and
+ * E emitted: a push of c frames sets N += c, E' = max(E, N - R) and writes the latent frames [E, E'); the flush sets E' = N — the utterance
+ * ends at N and zero padding follows it — and writes the rest, at most R frames.  After the flush pushes are refused (FV_ERR_STATE) until
+ * fv_wnstream_reset.  The concatenated frames are BIT-identical to fv_posterior_forward over the whole utterance, under any chunking:
+ * with p_i = (kernel_size - 1) d_i / 2, every layer keeps a ring of its input whose frontier lies p_0 + ... + p_{i-1} frames behind N, a
+ * call runs each layer's gate and res / skip GEMM over the new columns only (the kernels are the whole-row body, addressed through the
+ * rings), and an element's sum order is fixed by the layer's shape alone.  A ring position at or past a frontier is never read: the flush
+ * stages zeros there.  A call enqueues at most 2 * n_layers + 2 launches, none when it has nothing to compute; it neither synchronises nor
+ * allocates.  All device state is allocated by fv_wnstream_create:
+ *   batch * hidden_channels * (sum_i pow2(2 p_i + S) + pow2(R + S) + S) floats, S = max(max_chunk, R), pow2 = the next power of two.
+ * The stream reads the encoder's weights: destroy it before the encoder.  Every entry validates all a host can see before it enqueues
+ * anything and names what it refuses; a refused call changes no counter. */
+typedef struct fv_wnstream fv_wnstream;
+/* p must be finalized (FV_ERR_STATE otherwise); batch in [1, 65535], max_chunk in [1, 2^20]. */
+FV_API fv_status fv_wnstream_create(fv_posterior* p, int32_t batch, int32_t max_chunk, fv_wnstream** out);
+/* d_x: frame t of channel ch of row b at d_x[b * x_batch_stride + ch * x_row_stride + t], x_row_stride >= c (a slice along T passes as it
+ * is); c in [0, max_chunk], d_x may be NULL when c = 0.  d_z, d_mean, d_logvar: (batch, out_channels, y_row_stride) with
+ * y_row_stride >= E' - E, frame E + j in column j; d_mean / d_logvar must be NULL in vqvae mode and may be NULL in the vae modes; d_z may
+ * be NULL when the call emits nothing.  *emitted (may be NULL) receives E' - E.  At most 2^30 frames per utterance. */
+FV_API fv_status fv_wnstream_push(fv_wnstream* s, const float* d_x, int64_t x_batch_stride, int64_t x_row_stride, int32_t c, float* d_z,
+                                  float* d_mean, float* d_logvar, int64_t y_row_stride, int64_t* emitted, void* stream);
+FV_API fv_status fv_wnstream_flush(fv_wnstream* s, float* d_z, float* d_mean, float* d_logvar, int64_t y_row_stride, int64_t* emitted,
+                                   void* stream);
+/* N = E = 0 for the next utterance; no device work (nothing a ring holds from the last one is read). */
+FV_API fv_status fv_wnstream_reset(fv_wnstream* s);
+/* N - E; -1 for NULL. */
+FV_API int64_t fv_wnstream_pending(const fv_wnstream* s);
+/* R; -1 for NULL. */
+FV_API int32_t fv_wnstream_lookahead(const fv_wnstream* s);
+FV_API void fv_wnstream_destroy(fv_wnstream* s);
+
 /* -------- wav2vec2 / HuBERT encoder (modules/encoders/hubert.py: HubertModel in its "stable layer norm" form, then `post`) --------
  * Eval-mode fp32 forward of the family feat_extract_norm = "layer", do_stable_layer_norm, conv_bias, feat_proj_layer_norm, GELU, eps 1e-5
  * (facebook/hubert-large-ll60k, facebook/mms-300m).  Activations are time major, (row, frame, channel).  With len_0 = the row's samples and

@@ -80,6 +80,8 @@ EXPORTS = (
     "fv_vq_create", "fv_vq_destroy", "fv_vq_load_codebook", "fv_vq_set_slices", "fv_vq_workspace_bytes", "fv_vq_encode", "fv_vq_decode",
     "fv_posterior_create", "fv_posterior_load_weight", "fv_posterior_finalize", "fv_posterior_reach_frames", "fv_posterior_output_channels",
     "fv_posterior_workspace_bytes", "fv_posterior_forward", "fv_posterior_destroy",
+    "fv_wnstream_create", "fv_wnstream_push", "fv_wnstream_flush", "fv_wnstream_reset", "fv_wnstream_pending", "fv_wnstream_lookahead",
+    "fv_wnstream_destroy",
     "fv_w2v_create", "fv_w2v_load_weight", "fv_w2v_finalize", "fv_w2v_frames", "fv_w2v_workspace_bytes", "fv_w2v_forward", "fv_w2v_destroy",
     "fv_mms_normalize_workspace_bytes", "fv_mms_normalize", "fv_mms_interpolate", "fv_mms_nearest_index",
 )
@@ -576,6 +578,20 @@ def lib() -> ctypes.CDLL:
     L.fv_posterior_forward.restype = _i32
     L.fv_posterior_destroy.argtypes = [vp]
     L.fv_posterior_destroy.restype = None
+    L.fv_wnstream_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_wnstream_create.restype = _i32
+    L.fv_wnstream_push.argtypes = [vp, vp, i64, i64, _i32, vp, vp, vp, i64, i64p, vp]
+    L.fv_wnstream_push.restype = _i32
+    L.fv_wnstream_flush.argtypes = [vp, vp, vp, vp, i64, i64p, vp]
+    L.fv_wnstream_flush.restype = _i32
+    L.fv_wnstream_reset.argtypes = [vp]
+    L.fv_wnstream_reset.restype = _i32
+    L.fv_wnstream_pending.argtypes = [vp]
+    L.fv_wnstream_pending.restype = i64
+    L.fv_wnstream_lookahead.argtypes = [vp]
+    L.fv_wnstream_lookahead.restype = _i32
+    L.fv_wnstream_destroy.argtypes = [vp]
+    L.fv_wnstream_destroy.restype = None
     L.fv_w2v_create.argtypes = [ctypes.POINTER(W2VConfig), ctypes.POINTER(vp)]
     L.fv_w2v_create.restype = _i32
     L.fv_w2v_load_weight.argtypes = [vp, cp, fp, i64p, _i32]

@@ -52,6 +52,12 @@ class VQVAECodec(nn.Module):
         is not supported through an encoder of raw audio (``takes_audio``, ``MMSEncoder``): see ``_latent``."""
         return self.vq.encode(self._latent(x, lengths), lengths)
 
+    def encode_stream(self, batch: int = 1, max_chunk_samples: int = 4096) -> "CodecEncodeStream":
+        """``encode`` chunk by chunk (``CodecEncodeStream``): audio in, codes out after the front-end's and the encoder's lookahead.  For an
+        encoder of spectrograms whose own ``stream()`` has ``forward``'s bits (``PosteriorEncoder``); with the front-end in its
+        batch-invariant mode the concatenated codes are ``encode``'s."""
+        return CodecEncodeStream(self, batch, max_chunk_samples)
+
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
         y = self.decoder(self.vq.from_codes(codes)[0])
         return y[:, None, :] if y.ndim == 2 else y
@@ -92,6 +98,63 @@ class VQVAECodec(nn.Module):
             if k.startswith("frontend."):
                 own.setdefault(k, v)
         return self.load_state_dict(own, strict=True)
+
+
+class CodecEncodeStream:
+    """``VQVAECodec.encode`` on a live source: ``frontend.stream()`` -> ``encoder.stream()`` -> ``vq.encode``, every stage on the device.
+    ``push(wave (B, c) or (B, 1, c))``, ``c <= max_chunk_samples``, returns the codes of the latent frames that are final — ``(B, k)``, or
+    ``(n_q, B, k)`` for the residual form, ``k`` possibly 0; ``flush()`` ends the utterance and returns the rest; ``reset()`` starts the next
+    one.  The quantiser is frame-independent, so the concatenated codes are ``encode``'s whenever both streams have their whole-row bits."""
+
+    def __init__(self, codec: VQVAECodec, batch: int = 1, max_chunk_samples: int = 4096):
+        enc, name = codec.encoder, type(codec.encoder).__name__
+        if getattr(enc, "takes_audio", False):
+            raise ValueError(f"encode_stream: {name} takes raw audio (takes_audio), not a streamed spectrogram: it has no streaming encode")
+        if not getattr(enc, "stream_is_bit_exact", False):
+            raise ValueError(f"encode_stream: {name}.stream() is not bit-exact — a windowed engine stream promises 2e-5, not forward's bits, so "
+                             "codes could differ from encode(); use a PosteriorEncoder (build_vqvae(encoder='posterior'))")
+        if codec.frontend is None:
+            raise ValueError("encode_stream: the codec has no front-end to turn the audio chunks into spectrogram frames")
+        self._vq = codec.vq
+        self._fe = codec.frontend.stream(batch, max_chunk_samples)
+        self.batch, self.max_chunk_samples = int(batch), int(max_chunk_samples)
+        self._max_frames = self.max_chunk_samples // int(codec.frontend.hop_length) + 2      # per encoder push; longer runs go in pieces
+        self._enc = enc.stream(batch, self._max_frames)
+
+    @property
+    def received_samples(self) -> int:
+        return self._fe.received_samples
+
+    @property
+    def emitted_frames(self) -> int:
+        return self._enc.emitted_frames
+
+    def _latents(self, spec: torch.Tensor) -> list:
+        return [self._enc.push(spec[:, :, a:a + self._max_frames]) for a in range(0, int(spec.shape[2]), self._max_frames)]
+
+    def _codes(self, zs: list) -> torch.Tensor:
+        return self._vq.encode(zs[0] if len(zs) == 1 else torch.cat(zs, dim=2))
+
+    def push(self, wave: torch.Tensor) -> torch.Tensor:
+        spec = self._fe.push(wave)
+        return self._codes(self._latents(spec) or [self._enc.push(spec)])
+
+    def flush(self) -> torch.Tensor:
+        return self._codes(self._latents(self._fe.flush()) + [self._enc.flush()])
+
+    def reset(self) -> None:
+        self._fe.reset()
+        self._enc.reset()
+
+    def close(self) -> None:
+        self._fe.close()
+        self._enc.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
 
 
 def build_vqvae(n_fft: int = 3072, hop_length: int = 2048, win_length: int = 3072, latent_size: int = 512, codebook_size: int = 4096,
@@ -142,7 +205,17 @@ def main(argv=None):
     ap.add_argument("--num-quantizers", type=int, default=1)
     ap.add_argument("--encoder", choices=("convnext", "posterior"), default="convnext", help="the encoder slot: ConvNeXtEncoder or PosteriorEncoder")
     ap.add_argument("--hidden-channels", type=int, default=192, help="--encoder posterior: the WaveNet's width")
+    ap.add_argument("--chunk-samples", type=int, default=None,
+                    help="encode: run the file through encode_stream in chunks of this many samples (same codes; needs --encoder posterior)")
     a = ap.parse_args(argv)
+    if a.chunk_samples is not None:
+        if a.mode != "encode":
+            ap.error("--chunk-samples belongs to encode: there is no decode stream")
+        if a.encoder != "posterior":
+            ap.error("--chunk-samples needs --encoder posterior: the ConvNeXt encoder's stream is not bit-exact, so its codes could differ "
+                     "from a whole-file encode")
+        if a.chunk_samples < 1:
+            ap.error(f"--chunk-samples = {a.chunk_samples} must be at least 1")
     if not torch.cuda.is_available():
         raise SystemExit("vocoder_amd.codec needs a HIP device: there is no CPU path")
     model = build_vqvae(a.n_fft, a.hop_length, a.win_length, a.latent_size, a.codebook_size, a.num_quantizers,
@@ -159,7 +232,13 @@ def main(argv=None):
         if sr != a.sample_rate:
             raise SystemExit(f"{src}: {sr} Hz, the model runs at {a.sample_rate} Hz (resample with vocoder_amd.inference --resample first)")
         audio = torch.from_numpy(wav.mean(0, keepdims=True))[None].cuda()
-        codes = model.encode(audio)
+        if a.chunk_samples is None:
+            codes = model.encode(audio)
+        else:
+            model.frontend.batch_invariant = True       # the mode in which the front-end's stream has its whole-row bits
+            with model.encode_stream(1, a.chunk_samples) as st:
+                parts = [st.push(audio[:, :, n:n + a.chunk_samples]) for n in range(0, audio.shape[2], a.chunk_samples)]
+                codes = torch.cat(parts + [st.flush()], dim=-1)
         codes = codes[:, 0] if codes.dim() == 3 else codes[0]
         dst = out / f"{src.stem}.codes.npy"
         np.save(dst, codes.cpu().numpy())

@@ -18,6 +18,9 @@
 // addition of the bias: an order fixed by the layer's shape alone.  It does not depend on the batch, the column's tile or place in it, the
 // tile width (WN) or the other rows' lengths (masked frames and padded channels add exact zeros in the same places), so a row has the same
 // bits alone, in any batch and padded to any T.
+// The stream (fv_wnstream_*): the same body instantiated with STREAM — a column origin, input and output addresses through a WnSpan (a ring
+// or a linear buffer) and the input's valid range [lo, frontier) — runs every layer over a push's new columns only, out of one ring per
+// layer input.  Nothing above depends on where a column sits, so a stream has the whole row's bits under any chunking.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -48,6 +51,14 @@ using WnRowBlock = LaunchTable<int, kWnRows>;
 
 enum WnMode : int { WN_GATE = 0, WN_RES_SKIP = 1, WN_PRE = 2, WN_PROJ = 3 };
 
+// Frame t of channel row r is element r * stride + ((t - org) & mask): a ring of `stride` = mask + 1 frames (org 0), or a linear buffer
+// whose first frame is org (mask -1)
+struct WnSpan {
+    long long stride;
+    int org, mask;
+    __host__ __device__ long long at(long long r, int t) const { return r * stride + ((t - org) & mask); }
+};
+
 struct WnParams {
     const float* x;                 // (., Cin, .): element (b, c, t) at b * x_bstride + c * x_cstride + t
     long long x_bstride, x_cstride;
@@ -64,10 +75,16 @@ struct WnParams {
     const float* bn_shift;
     int first;                      // res_skip: the first layer writes out
     int G;                          // chunks staged per barrier (wn_stage_chunks)
+    // The stream instantiations only (fv_wnstream_*).  A launch covers the frames [col0, T) of every row; `uniform` is the input's frontier
+    // (frames at or past it stage as zero, whatever a ring holds there) and `lo` its first frame in memory.  A WnSpan is where a frame lives.
+    int col0, lo;
+    WnSpan xs, y0s, y1s, rs;        // of x, of y0 (and z), of y1, of res
+    const float* res;               // res_skip: the residual input h_i (its own ring; y0 is the ring of h_{i + 1})
 };
 
 // WN waves side by side along time (32 columns each) x 4 / WN pairs; KS = 0: taps and dilation at run time
-template <int MODE, int WN, int KS, int DIL>
+// STREAM: the tile's columns are the frames col0 + ..., and every address goes through a WnSpan; the sums are the whole-row ones
+template <int MODE, int WN, int KS, int DIL, bool STREAM = false>
 __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& rows) {
     constexpr int WM = 4 / WN, N_BLK = 32 * WN;
     extern __shared__ __attribute__((aligned(16))) float wn_xs[];
@@ -78,9 +95,9 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
     const int wn = wave % WN, wm = wave / WN;
     const int bl = blockIdx.z;
     const long long b = p.row0 + bl;
-    const int len = p.uniform >= 0 ? p.uniform : rows.e[bl];
-    const int n0 = blockIdx.x * N_BLK;
-    if (MODE != WN_PROJ && n0 >= len) return;       // nothing of this tile is ever read (block-uniform); proj still writes its zeros
+    const int len = STREAM || p.uniform >= 0 ? p.uniform : rows.e[bl];
+    const int n0 = (STREAM ? p.col0 : 0) + blockIdx.x * N_BLK;
+    if ((STREAM || MODE != WN_PROJ) && n0 >= len) return;       // nothing of this tile is ever read (block-uniform); proj still writes its zeros
     const int pair = blockIdx.y * WM + wm;
     const bool do0 = pair < p.npairs && pair * 32 < p.M0, do1 = pair < p.npairs && pair * 32 < p.M1;      // wave-uniform
 
@@ -106,7 +123,11 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
                 float v = 0.f;
                 if (tid + 256 * i < total) {
                     const int ci = s * G * kChunk + r, t = tbase + col;
-                    if (ci < p.Cin && t >= 0 && t < len) v = xb[(long long)ci * p.x_cstride + t];     // the conv's zero padding and the row's length
+                    if constexpr (STREAM) {
+                        if (ci < p.Cin && t >= p.lo && t < len) v = xb[(long long)ci * p.x_cstride + ((t - p.xs.org) & p.xs.mask)];
+                    } else {
+                        if (ci < p.Cin && t >= 0 && t < len) v = xb[(long long)ci * p.x_cstride + t];     // the conv's zero padding and the row's length
+                    }
                 }
                 pf[i] = v;
                 r += rq, col += cq;
@@ -174,7 +195,8 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = pair * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const long long o0 = (b * p.M0 + m) * p.T + n, o1 = (b * p.M1 + m) * p.T + n;
+        const long long o0 = STREAM ? p.y0s.at(b * p.M0 + m, n) : (b * p.M0 + m) * p.T + n;
+        const long long o1 = STREAM ? p.y1s.at(b * p.M1 + m, n) : (b * p.M1 + m) * p.T + n;
         if (MODE == WN_GATE) {
             if (valid && m < p.M0) {
                 const float t = tanhf(acc0[r] + bias0[m]);
@@ -183,7 +205,11 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
             }
         } else if (MODE == WN_RES_SKIP) {
             if (!valid) continue;
-            if (m < p.M0) p.y0[o0] = p.y0[o0] + (acc0[r] + bias0[m]);           // the same lane reads and writes the element
+            if constexpr (STREAM) {
+                if (m < p.M0) p.y0[o0] = p.res[p.rs.at(b * p.M0 + m, n)] + (acc0[r] + bias0[m]);     // h_{i + 1} = h_i + r, from ring to ring
+            } else {
+                if (m < p.M0) p.y0[o0] = p.y0[o0] + (acc0[r] + bias0[m]);           // the same lane reads and writes the element
+            }
             if (m < p.M1) {
                 const float v = acc1[r] + bias1[m];
                 p.y1[o1] = p.first ? v : p.y1[o1] + v;
@@ -217,6 +243,9 @@ template <int WN>
 __global__ __launch_bounds__(256) void wn_pre_kernel(const WnParams p, const WnRowBlock rows) { wn_body<WN_PRE, WN, 1, 1>(p, rows); }
 template <int WN>
 __global__ __launch_bounds__(256) void wn_proj_kernel(const WnParams p, const WnRowBlock rows) { wn_body<WN_PROJ, WN, 1, 1>(p, rows); }
+// The stream forms take no row table: every row of a stream holds the same frames
+template <int MODE, int WN, int KS, int DIL>
+__global__ __launch_bounds__(256) void wn_stream_kernel(const WnParams p) { wn_body<MODE, WN, KS, DIL, true>(p, WnRowBlock{}); }
 
 // Chunks per stage: as many as keep a stage inside the threads' kWnSlots registers, which is also half the LDS budget (two stages)
 int wn_stage_chunks(int cols, int ks, int dil) {
@@ -238,6 +267,19 @@ void wn_launch(WnParams p, const WnRowBlock& rows, int nrows, hipStream_t s) {
     else if (MODE == WN_RES_SKIP) narrow ? go(wn_res_skip_kernel<1>) : go(wn_res_skip_kernel<4>);
     else if (MODE == WN_PRE) narrow ? go(wn_pre_kernel<1>) : go(wn_pre_kernel<4>);
     else narrow ? go(wn_proj_kernel<1>) : go(wn_proj_kernel<4>);
+}
+
+// The frames [p.col0, p.T) of `nrows` rows; the tile is chosen by their count as wn_launch chooses it by T
+template <int MODE, int KS, int DIL>
+void wn_stream_launch(WnParams p, int nrows, hipStream_t s) {
+    const int ncols = p.T - p.col0;
+    const bool narrow = ncols <= kWnNarrowMaxT;
+    const int cols = narrow ? 32 : kWnWideCols, wm = narrow ? 4 : 1;
+    const dim3 grid((unsigned)((ncols + cols - 1) / cols), (unsigned)((p.npairs + wm - 1) / wm), (unsigned)nrows);
+    p.G = wn_stage_chunks(cols, p.ks, p.dil);
+    const size_t lds = wn_lds_bytes(cols, p.ks, p.dil, p.G);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, p); };
+    narrow ? go(wn_stream_kernel<MODE, 1, KS, DIL>) : go(wn_stream_kernel<MODE, 4, KS, DIL>);
 }
 
 // One GEMM of the stack on the host side: the folded rows of its two halves, packed
@@ -306,6 +348,28 @@ struct fv_posterior {
         for (auto& g : in_layers) drop(g);
         for (auto& g : rs_layers) drop(g);
         if (d_bn) (void)hipFree(d_bn);
+    }
+};
+
+// The encoder chunk by chunk (fv_wnstream_*).  With p_i = (k - 1) d_i / 2 and lam[i] = p_0 + ... + p_{i - 1} (lam[n_layers] = R), layer i's
+// input h_i is known up to frame N - lam[i] after N frames have arrived, and a push computes only the new columns of every layer.  h_i lives
+// in a ring of its own: its next outputs still read the last 2 p_i frames below the frontier, and one call adds max(max_chunk, R) at the
+// most (R: a flush takes every layer up to N), so nothing is copied between pushes.  `out`, the running skip sum, is a ring of the R frames
+// that wait for their later layers plus one call's; g is linear, one call's columns.
+struct fv_wnstream {
+    fv_posterior* enc = nullptr;
+    int batch = 0, max_chunk = 0;
+    long long N = 0, E = 0;
+    bool flushed = false;
+    std::vector<int> lam;               // n_layers + 1
+    std::vector<float*> h;              // ring of h_i, (batch, C, hW[i])
+    std::vector<int> hW;
+    float* out = nullptr;               // (batch, C, outW)
+    float* g = nullptr;                 // (batch, C, gW)
+    int outW = 0, gW = 0;
+    float* slab = nullptr;
+    ~fv_wnstream() {
+        if (slab) (void)hipFree(slab);
     }
 };
 
@@ -611,5 +675,187 @@ FV_API fv_status fv_posterior_forward(fv_posterior* p, const float* d_x, int64_t
     if (st == FV_OK) set_last_kernel(Ti <= kWnNarrowMaxT ? "wn_gate_kernel<1>" : "wn_gate_kernel<4>");
     return st;
 }
+
+}  // extern "C"
+
+namespace {
+
+int wn_pow2_at_least(long long v) {
+    int w = 1;
+    while (w < v) w <<= 1;
+    return w;
+}
+
+// One push (c frames of d_x) or the flush: validates, then enqueues at most 2 n_layers + 2 launches and moves the counters
+fv_status wn_stream_advance(const char* fn, fv_wnstream* s, const float* d_x, int64_t x_batch_stride, int64_t x_row_stride, int32_t c, bool flush,
+                            float* d_z, float* d_mean, float* d_logvar, int64_t y_row_stride, int64_t* emitted, void* stream) {
+    if (!s) {
+        set_error("%s: null stream", fn);
+        return FV_ERR_INVALID;
+    }
+    const fv_posterior* p = s->enc;
+    const fv_posterior_config& cfg = p->cfg;
+    if (s->flushed) {
+        set_error("%s: the stream was flushed at %lld frames: fv_wnstream_reset starts the next utterance", fn, s->N);
+        return FV_ERR_STATE;
+    }
+    if (c < 0 || c > s->max_chunk) {
+        set_error("%s: c = %d must lie in [0, max_chunk = %d]", fn, c, s->max_chunk);
+        return FV_ERR_INVALID;
+    }
+    if (s->N + c > kWnMaxFrames) {
+        set_error("%s: %lld + %d frames are more than the 2^30 a stream counts", fn, s->N, c);
+        return FV_ERR_INVALID;
+    }
+    if (cfg.mode == 0 && (d_mean || d_logvar)) {
+        set_error("%s: %s must be NULL in vqvae mode (posterior_encoder.py:159-160 returns one tensor)", fn, d_mean ? "d_mean" : "d_logvar");
+        return FV_ERR_INVALID;
+    }
+    if (c > 0 && !d_x) {
+        set_error("%s: null d_x with c = %d", fn, c);
+        return FV_ERR_INVALID;
+    }
+    if (c > 0 && (x_row_stride < c || x_batch_stride < 0)) {
+        set_error("%s: x_row_stride = %lld (the stride between channels) is shorter than a chunk of c = %d frames, or x_batch_stride = %lld is "
+                  "negative", fn, (long long)x_row_stride, c, (long long)x_batch_stride);
+        return FV_ERR_INVALID;
+    }
+    const int R = p->reach, nl = cfg.n_layers, C = cfg.hidden_channels, B = s->batch;
+    const long long N0 = s->N, N1 = N0 + c, E0 = s->E, E1 = flush ? N1 : std::max(E0, N1 - R);
+    const long long k = E1 - E0;
+    if (k > 0 && !d_z) {
+        set_error("%s: null d_z for the %lld frames this call emits", fn, k);
+        return FV_ERR_INVALID;
+    }
+    if (k > 0 && y_row_stride < k) {
+        set_error("%s: y_row_stride = %lld is shorter than the %lld frames this call emits", fn, (long long)y_row_stride, k);
+        return FV_ERR_INVALID;
+    }
+    // everything is validated: enqueue
+
+    hipStream_t st = (hipStream_t)stream;
+    const bool k5 = cfg.kernel_size == 5;
+    auto ring = [](int W) { return WnSpan{W, 0, W - 1}; };
+    auto linear = [](long long stride, long long org) { return WnSpan{stride, (int)org, -1}; };
+    auto clamp0 = [](long long v) { return (int)std::max(0LL, v); };
+    bool any = false;
+    if (c > 0) {        // h_0 = pre(x) over the new frames
+        WnParams q = wn_params(p->pre, d_x, x_batch_stride, x_row_stride, (int)N1, 1);
+        q.col0 = q.lo = (int)N0, q.uniform = (int)N1, q.xs = linear(x_row_stride, N0);
+        q.y0 = s->h[0], q.y0s = ring(s->hW[0]);
+        wn_stream_launch<WN_PRE, 1, 1>(q, B, st);
+        any = true;
+    }
+    for (int i = 0; i < nl; ++i) {
+        // the new columns of h_{i + 1} and skip_i; the flush takes every layer up to N, reading zeros from there on
+        const int n0 = clamp0(N0 - s->lam[i + 1]), n1 = flush ? (int)N1 : clamp0(N1 - s->lam[i + 1]);
+        if (n1 <= n0) continue;
+        const int front = flush ? (int)N1 : clamp0(N1 - s->lam[i]);         // h_i's frontier: a ring holds an earlier lap's frame past it
+        WnParams q = wn_params(p->in_layers[i], s->h[i], (long long)C * s->hW[i], s->hW[i], n1, p->dil[i]);
+        q.col0 = n0, q.lo = 0, q.uniform = front, q.xs = ring(s->hW[i]);
+        q.y0 = s->g, q.y0s = linear(s->gW, n0);
+        if (k5 && p->dil[i] == 1) wn_stream_launch<WN_GATE, 5, 1>(q, B, st);
+        else wn_stream_launch<WN_GATE, 0, 0>(q, B, st);
+        WnParams r = wn_params(p->rs_layers[i], s->g, (long long)C * s->gW, s->gW, n1, 1);
+        r.col0 = r.lo = n0, r.uniform = n1, r.xs = linear(s->gW, n0);
+        r.res = s->h[i], r.rs = ring(s->hW[i]);
+        if (i + 1 < nl) r.y0 = s->h[i + 1], r.y0s = ring(s->hW[i + 1]);
+        r.y1 = s->out, r.y1s = ring(s->outW), r.first = i == 0;
+        wn_stream_launch<WN_RES_SKIP, 1, 1>(r, B, st);
+        any = true;
+    }
+    if (k > 0) {
+        WnParams q = wn_params(p->proj, s->out, (long long)C * s->outW, s->outW, (int)E1, 1);
+        q.col0 = (int)E0, q.lo = 0, q.uniform = (int)E1, q.xs = ring(s->outW);
+        q.y0s = q.y1s = linear(y_row_stride, E0);
+        if (cfg.mode == 0) {
+            q.y0 = d_z;
+        } else {
+            q.y0 = d_mean, q.y1 = d_logvar, q.z = d_z;
+            if (cfg.mode == 2) q.bn_scale = p->d_bn, q.bn_shift = p->d_bn + cfg.out_channels;
+        }
+        wn_stream_launch<WN_PROJ, 1, 1>(q, B, st);
+        any = true;
+    }
+    if (any) {
+        FV_HIP_CHECK(hipGetLastError());
+        set_last_kernel("wn_stream_kernel");
+    }
+    s->N = N1, s->E = E1, s->flushed = flush;
+    if (emitted) *emitted = k;
+    return FV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+FV_API fv_status fv_wnstream_create(fv_posterior* p, int32_t batch, int32_t max_chunk, fv_wnstream** out) {
+    const char* fn = "fv_wnstream_create";
+    if (!out || !p) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!p->finalized) {
+        set_error("%s: the encoder has not been finalized (fv_posterior_finalize)", fn);
+        return FV_ERR_STATE;
+    }
+    if (batch < 1 || batch > 65535) {
+        set_error("%s: batch = %d must lie in [1, 65535]", fn, batch);
+        return FV_ERR_INVALID;
+    }
+    if (max_chunk < 1 || max_chunk > (1 << 20)) {
+        set_error("%s: max_chunk = %d must lie in [1, 2^20]", fn, max_chunk);
+        return FV_ERR_INVALID;
+    }
+    std::unique_ptr<fv_wnstream> s(new fv_wnstream());
+    s->enc = p, s->batch = batch, s->max_chunk = max_chunk;
+    const int nl = p->cfg.n_layers, k = p->cfg.kernel_size, R = p->reach;
+    const long long step = std::max(max_chunk, R);            // the most frames one call adds to a frontier
+    s->lam.assign(nl + 1, 0);
+    size_t frames = 0;                                         // per (row, channel)
+    for (int i = 0; i < nl; ++i) {
+        const int pad = (k - 1) * p->dil[i] / 2;
+        s->lam[i + 1] = s->lam[i] + pad;
+        s->hW.push_back(wn_pow2_at_least(2LL * pad + step));
+        frames += (size_t)s->hW.back();
+    }
+    s->outW = wn_pow2_at_least(R + step), s->gW = (int)step;
+    frames += (size_t)s->outW + (size_t)s->gW;
+    const size_t plane = (size_t)batch * (size_t)p->cfg.hidden_channels;
+    FV_HIP_CHECK(hipMalloc(&s->slab, plane * frames * sizeof(float)));
+    float* at = s->slab;
+    for (int i = 0; i < nl; ++i) s->h.push_back(at), at += plane * (size_t)s->hW[i];
+    s->out = at, at += plane * (size_t)s->outW;
+    s->g = at;
+    *out = s.release();
+    return FV_OK;
+}
+
+FV_API fv_status fv_wnstream_push(fv_wnstream* s, const float* d_x, int64_t x_batch_stride, int64_t x_row_stride, int32_t c, float* d_z,
+                                  float* d_mean, float* d_logvar, int64_t y_row_stride, int64_t* emitted, void* stream) {
+    return wn_stream_advance("fv_wnstream_push", s, d_x, x_batch_stride, x_row_stride, c, false, d_z, d_mean, d_logvar, y_row_stride, emitted, stream);
+}
+
+FV_API fv_status fv_wnstream_flush(fv_wnstream* s, float* d_z, float* d_mean, float* d_logvar, int64_t y_row_stride, int64_t* emitted,
+                                   void* stream) {
+    return wn_stream_advance("fv_wnstream_flush", s, nullptr, 0, 0, 0, true, d_z, d_mean, d_logvar, y_row_stride, emitted, stream);
+}
+
+FV_API fv_status fv_wnstream_reset(fv_wnstream* s) {
+    if (!s) {
+        set_error("fv_wnstream_reset: null stream");
+        return FV_ERR_INVALID;
+    }
+    s->N = s->E = 0, s->flushed = false;        // the rings keep their frames: nothing at or past a frontier, or before frame 0, is ever read
+    return FV_OK;
+}
+
+FV_API int64_t fv_wnstream_pending(const fv_wnstream* s) { return s ? s->N - s->E : -1; }
+
+FV_API int32_t fv_wnstream_lookahead(const fv_wnstream* s) { return s ? s->enc->reach : -1; }
+
+FV_API void fv_wnstream_destroy(fv_wnstream* s) { delete s; }
 
 }  // extern "C"

@@ -5,20 +5,38 @@ Parameters are ordinary torch parameters under the reference's keys and order â€
 weight_v}``, ``enc.res_skip_layers.{i}.{bias,weight_g,weight_v}`` (the old ``nn.utils.weight_norm(name="weight")`` naming), ``proj.{weight,
 bias}`` and, for ``mode="bnvae"``, ``mu_bn.*`` â€” so a checkpoint loads strictly; the holders are never called.  ``forward(x, x_lengths)``
 returns what the reference's eval forward returns: ``y`` for ``"vqvae"``, ``(z, mean, logvar, x_mask)`` for ``"vae"`` / ``"bnvae"``.  A row has
-the same bits alone, in any batch and padded to any T; frames at or past a row's length, and the padding of ``x``, are never read.  Not
-built: the training-mode draw, dropout, f16x3.  No CPU fallback.
+the same bits alone, in any batch and padded to any T; frames at or past a row's length, and the padding of ``x``, are never read.
+``stream(batch, max_chunk_frames)`` is the encoder chunk by chunk (``PosteriorStream``, ``fv_wnstream_*``): the whole utterance's bits under
+any chunking, ``reach_frames`` frames behind the input.  Not built: the training-mode draw, dropout, f16x3.  No CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import torch
 from torch import nn
 
 from ... import _lib
+from ..._handle import _Handle
 from ..._lib import check
 
 _MSG_INFERENCE = "{} is inference-only: call .eval() first"
+_MSG_DEVICE = ("{} needs a CUDA/HIP tensor (got {}); vocoder_amd has no CPU path â€” move the model and "
+               "input to the GPU")
+
+
+def schedule(chunks, R: int) -> list:
+    """The frames a stream of reach ``R`` emits: ``(E, E')`` for every push of ``chunks`` (frame counts, zeros allowed) â€” the push emits the
+    frames ``[E, E')``, ``E' = max(E, N - R)`` â€” and last ``(E, N)`` for the flush."""
+    out, N, E = [], 0, 0
+    for c in chunks:
+        N += int(c)
+        E2 = max(E, N - int(R))
+        out.append((E, E2))
+        E = E2
+    out.append((E, N))
+    return out
 
 
 class _PosteriorEngine:
@@ -26,6 +44,7 @@ class _PosteriorEngine:
 
     def __init__(self, cfg: "_lib.PosteriorConfig", state_dict, device: torch.device):
         self.device, self._h = device, ctypes.c_void_p()
+        self._streams: weakref.WeakSet = weakref.WeakSet()      # live PosteriorStreams: closed before the handle is destroyed
         L = _lib.lib()
         check(L.fv_posterior_create(ctypes.byref(cfg), ctypes.byref(self._h)))
         try:
@@ -45,6 +64,8 @@ class _PosteriorEngine:
         return self._h
 
     def close(self) -> None:
+        for st in list(getattr(self, "_streams", ())):
+            st.close()
         if self._h is not None and self._h.value:
             if torch.cuda.is_available():
                 torch.cuda.synchronize(self.device)     # kernels that read the weights may still be running
@@ -56,6 +77,108 @@ class _PosteriorEngine:
             self.close()
         except Exception:
             pass
+
+
+class PosteriorStream(_Handle):
+    """``PosteriorEncoder`` chunk by chunk (``fv_wnstream_*``, include/fishvoc.h): ``push`` a ``(B, in_channels, c)`` chunk, ``c <=
+    max_chunk_frames``, and get what ``forward`` returns for the frames that need no later input â€” ``[E, max(E, N - R))``, ``R =
+    lookahead_frames``, possibly none; ``flush`` ends the utterance at ``N`` and returns the rest, then pushes raise until ``reset()``.  The
+    concatenation has the bits of ``forward`` over the whole utterance under any chunking (``schedule`` gives the counts).  The ``batch`` rows
+    advance in lockstep.  A stream dies with the module's engine: ``load_state_dict`` or ``.to()`` closes it, create a new one then."""
+    _destroy = "fv_wnstream_destroy"
+    _closed = ("this posterior stream is closed (its engine was closed or rebuilt â€” e.g. load_state_dict or .to() on "
+               "the module): create a new stream")
+
+    def __init__(self, module: "PosteriorEncoder", engine: _PosteriorEngine, batch: int, max_chunk_frames: int):
+        self._lib, self._h = _lib.lib(), ctypes.c_void_p()
+        self._module, self._engine = module, engine
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_wnstream_create(engine.handle, int(batch), int(max_chunk_frames), ctypes.byref(self._h)))
+        engine._streams.add(self)
+        self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
+        self.in_channels, self.out_channels = module.in_channels, module.out_channels
+        self._R = int(self._lib.fv_wnstream_lookahead(self._h))
+        self._N = self._E = 0
+        self._flushed = False
+        self._last_stream = None
+
+    # -- counters (host-side: reading them never synchronises) --
+    @property
+    def received_frames(self) -> int:
+        return self._N
+
+    @property
+    def emitted_frames(self) -> int:
+        return self._E
+
+    @property
+    def pending_frames(self) -> int:
+        """Frames received and not yet emitted, as the library counts them (``fv_wnstream_pending``)."""
+        self._check_open()
+        return int(self._lib.fv_wnstream_pending(self._h))
+
+    @property
+    def lookahead_frames(self) -> int:
+        return self._R
+
+    def push(self, x: torch.Tensor):
+        self._check_open()
+        what = f"{type(self).__name__}.push"
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError(_MSG_DEVICE.format(what, getattr(x, "device", type(x))))
+        if x.dim() != 3 or x.shape[0] != self.batch or x.shape[1] != self.in_channels:
+            raise ValueError(f"{what}: expected ({self.batch}, {self.in_channels}, c), got {tuple(x.shape)}")
+        x = x.detach().to(torch.float32)
+        c = int(x.shape[2])
+        # a slice along T passes as it is (fv_wnstream_push's strides)
+        if c and not ((c == 1 or x.stride(2) == 1) and x.stride(1) >= c and x.stride(0) >= 0):
+            x = x.contiguous()
+        return self._call(x, c, flush=False)
+
+    def flush(self):
+        """The frames ``[E, N)`` against the utterance's end; pushes raise afterwards until ``reset()``."""
+        self._check_open()
+        return self._call(None, 0, flush=True)
+
+    def _call(self, x, c: int, flush: bool):
+        m, dev = self._module, self._engine.device
+        if m.training:
+            raise RuntimeError(_MSG_INFERENCE.format(type(m).__name__))
+        if x is not None and x.device != dev:
+            raise RuntimeError(f"{type(self).__name__}.push: the chunk is on {x.device}, the stream on {dev}")
+        refused = self._flushed or c > self.max_chunk_frames      # a refused call emits nothing; the library says why
+        k = 0 if refused else (self._N - self._E if flush else max(self._E, self._N + c - self._R) - self._E)
+        vae = m.mode != "vqvae"
+        new = lambda: torch.empty((self.batch, self.out_channels, k), dtype=torch.float32, device=dev)      # noqa: E731
+        z, mean, logvar = new(), (new() if vae else None), (new() if vae else None)
+        ptr = lambda t: t.data_ptr() if t is not None and k else None      # noqa: E731
+        got = ctypes.c_int64(0)
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            if self._done is not None and self._last_stream != cur.cuda_stream:
+                cur.wait_event(self._done)       # the rings are the stream's own: order after the previous call when it ran on another stream
+            tail = (ptr(z), ptr(mean), ptr(logvar), max(k, 1), ctypes.byref(got), int(cur.cuda_stream))
+            if flush:
+                check(self._lib.fv_wnstream_flush(self._h, *tail))
+            else:
+                check(self._lib.fv_wnstream_push(self._h, x.data_ptr() if c else None, x.stride(0) if c else 0, x.stride(1) if c else 0, c, *tail))
+            self._record_done(cur)
+            self._last_stream = cur.cuda_stream
+        if got.value != k:
+            raise RuntimeError(f"posterior stream emitted {got.value} frames where the rule says {k}")
+        self._N += c
+        self._E += k
+        self._flushed = flush
+        if not vae:
+            return z
+        return z, mean, logvar, torch.ones(self.batch, 1, k, dtype=torch.float32, device=dev)
+
+    def reset(self) -> None:
+        """Start the next utterance: N = E = 0; the rings are kept (nothing they hold is read again)."""
+        self._check_open()
+        check(self._lib.fv_wnstream_reset(self._h))
+        self._N = self._E = 0
+        self._flushed = False
 
 
 class WaveNet(nn.Module):
@@ -213,6 +336,22 @@ class PosteriorEncoder(nn.Module):
         res = self._run(padded, lengths, what)
         z = res if self.mode == "vqvae" else res[0]
         return [z[b, :, :n] for b, n in enumerate(lengths)]
+
+    stream_is_bit_exact = True      # codec.VQVAECodec.encode_stream: a stream's latents are forward's own bits, so its codes are encode's
+
+    def stream(self, batch: int = 1, max_chunk_frames: int = 64) -> PosteriorStream:
+        """The encoder chunk by chunk (``PosteriorStream``): ``push`` at most ``max_chunk_frames`` frames per row, ``flush`` at the utterance's
+        end; a latent frame comes out ``reach_frames`` frames after its own input.  Reloading the weights or moving the module rebuilds the
+        engine and closes its streams: create a new one then."""
+        what = f"{type(self).__name__}.stream"
+        dev = self.pre.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError(_MSG_DEVICE.format(what, dev).replace("a CUDA/HIP tensor", "the module on a CUDA/HIP device"))
+        if self.training:
+            raise RuntimeError(_MSG_INFERENCE.format(type(self).__name__))
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return PosteriorStream(self, self.engine(dev), batch, max_chunk_frames)
 
     def remove_weight_norm(self):
         """Kept for API compatibility (posterior_encoder.py:162-163, which raises AttributeError on ``gin_channels``): weight norm is folded
