@@ -398,7 +398,7 @@ def test_wav_session_pool_equals_the_generator_pool_fed_by_hand():
         for items in steps:
             ks = pc.plan(items)
             hand = [(s, mels[s][:, pc.emitted[s]:pc.emitted[s] + k] if k else None, f) for (s, _, f), k in zip(items, ks)]
-            pc.apply(items, ks)
+            pc.commit(items, ks)
             for (s, _, _), y in zip(items, pool.step(hand)):
                 want[s].append(y.clone())
     for s in range(S):

@@ -81,7 +81,7 @@ def test_c_plan_and_python_plan_agree_over_random_schedules(n_fft, hop):
         want = pc.plan(items)
         assert r == max(want, default=0) and got == want, (step, items, got, want, msg)
         before = (list(pc.received), list(pc.emitted))
-        pc.apply(items, want)
+        pc.commit(items, want)
         for (s, c, flush), k in zip(items, want):
             lo = before[1][s]
             rng_frames = list(lone[s].push(c)) + (list(lone[s].flush()) if flush else [])

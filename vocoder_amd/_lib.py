@@ -386,43 +386,35 @@ def lib() -> ctypes.CDLL:
     L.fv_logmel_stream_destroy.argtypes = [vp]
     L.fv_logmel_stream_destroy.restype = None
     wip = ctypes.POINTER(WavPoolItem)
-    L.fv_wavpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
-    L.fv_wavpool_create.restype = _i32
+    # the sample pools (csrc/sample_pool.h): create, the counters, reset and destroy have one signature; the wav pool's counters have longer names
+    for pre, received, emitted, pending in (("fv_wavpool", "_received_samples", "_emitted_frames", "_pending_samples"),
+                                            ("fv_respool", "_received", "_emitted", "_pending"), ("fv_pvpool", "_received", "_emitted", "_pending"),
+                                            ("fv_yinpool", "_received", "_emitted", "_pending"), ("fv_oscpool", "_received", "_emitted", "_pending")):
+        getattr(L, pre + "_create").argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+        getattr(L, pre + "_create").restype = _i32
+        for name in (received, emitted, pending):
+            getattr(L, pre + name).argtypes = [vp, _i32]
+            getattr(L, pre + name).restype = i64
+        getattr(L, pre + "_reset").argtypes = [vp, _i32]
+        getattr(L, pre + "_reset").restype = _i32
+        getattr(L, pre + "_destroy").argtypes = [vp]
+        getattr(L, pre + "_destroy").restype = None
     L.fv_wavpool_workspace_bytes.argtypes = [vp]
     L.fv_wavpool_workspace_bytes.restype = ctypes.c_size_t
     L.fv_wavpool_max_frames.argtypes = [vp]
     L.fv_wavpool_max_frames.restype = _i32
-    L.fv_wavpool_received_samples.argtypes = [vp, _i32]
-    L.fv_wavpool_received_samples.restype = i64
-    L.fv_wavpool_emitted_frames.argtypes = [vp, _i32]
-    L.fv_wavpool_emitted_frames.restype = i64
-    L.fv_wavpool_pending_samples.argtypes = [vp, _i32]
-    L.fv_wavpool_pending_samples.restype = i64
     L.fv_wavpool_plan.argtypes = [lcp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
     L.fv_wavpool_plan.restype = _i32
     L.fv_wavpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, _i32, i64p, vp, ctypes.c_size_t, vp]
     L.fv_wavpool_step.restype = _i32
-    L.fv_wavpool_reset.argtypes = [vp, _i32]
-    L.fv_wavpool_reset.restype = _i32
-    L.fv_wavpool_destroy.argtypes = [vp]
-    L.fv_wavpool_destroy.restype = None
     L.fv_global_resample_create.argtypes = [rcp, ctypes.POINTER(vp)]
     L.fv_global_resample_create.restype = _i32
-    L.fv_respool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
-    L.fv_respool_create.restype = _i32
     L.fv_respool_max_outputs.argtypes = [vp]
     L.fv_respool_max_outputs.restype = i64
-    for name in ("fv_respool_received", "fv_respool_emitted", "fv_respool_pending"):
-        getattr(L, name).argtypes = [vp, _i32]
-        getattr(L, name).restype = i64
     L.fv_respool_plan.argtypes = [rcp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
     L.fv_respool_plan.restype = i64
     L.fv_respool_step.argtypes = [vp, wip, _i32, vp, i64, vp, i64, _i32, i64p, vp]
     L.fv_respool_step.restype = _i32
-    L.fv_respool_reset.argtypes = [vp, _i32]
-    L.fv_respool_reset.restype = _i32
-    L.fv_respool_destroy.argtypes = [vp]
-    L.fv_respool_destroy.restype = None
     pcp = ctypes.POINTER(PitchShiftConfig)
     L.fv_pitch_shift_plan.argtypes = [pcp, i32p, i32p, i32p]
     L.fv_pitch_shift_plan.restype = _i32
@@ -456,25 +448,16 @@ def lib() -> ctypes.CDLL:
     L.fv_pv_stream_reset.restype = _i32
     L.fv_pv_stream_destroy.argtypes = [vp]
     L.fv_pv_stream_destroy.restype = None
-    L.fv_pvpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
-    L.fv_pvpool_create.restype = _i32
     L.fv_pvpool_workspace_bytes.argtypes = [vp]
     L.fv_pvpool_workspace_bytes.restype = ctypes.c_size_t
     L.fv_pvpool_max_outputs.argtypes = [vp]
     L.fv_pvpool_max_outputs.restype = i64
-    for name in ("fv_pvpool_received", "fv_pvpool_emitted", "fv_pvpool_pending"):
-        getattr(L, name).argtypes = [vp, _i32]
-        getattr(L, name).restype = i64
     L.fv_pvpool_bounds.argtypes = [pcp, _i32, i64p]
     L.fv_pvpool_bounds.restype = _i32
     L.fv_pvpool_plan.argtypes = [pcp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
     L.fv_pvpool_plan.restype = i64
     L.fv_pvpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, i64, _i32, i64p, vp, ctypes.c_size_t, vp]
     L.fv_pvpool_step.restype = _i32
-    L.fv_pvpool_reset.argtypes = [vp, _i32]
-    L.fv_pvpool_reset.restype = _i32
-    L.fv_pvpool_destroy.argtypes = [vp]
-    L.fv_pvpool_destroy.restype = None
     L.fv_spec_distance_tile.argtypes = []
     L.fv_spec_distance_tile.restype = _i32
     L.fv_spec_distance_workspace_bytes.argtypes = [_i32, i64]
@@ -527,19 +510,10 @@ def lib() -> ctypes.CDLL:
     L.fv_osc_stream_destroy.argtypes = [vp]
     L.fv_osc_stream_destroy.restype = None
     for pre, cfgp in (("fv_yinpool", fcp), ("fv_oscpool", tcp)):
-        getattr(L, pre + "_create").argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
-        getattr(L, pre + "_create").restype = _i32
         getattr(L, pre + "_max_frames").argtypes = [vp]
         getattr(L, pre + "_max_frames").restype = i64
-        for name in ("_received", "_emitted", "_pending"):
-            getattr(L, pre + name).argtypes = [vp, _i32]
-            getattr(L, pre + name).restype = i64
         getattr(L, pre + "_plan").argtypes = [cfgp, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
         getattr(L, pre + "_plan").restype = i64
-        getattr(L, pre + "_reset").argtypes = [vp, _i32]
-        getattr(L, pre + "_reset").restype = _i32
-        getattr(L, pre + "_destroy").argtypes = [vp]
-        getattr(L, pre + "_destroy").restype = None
     L.fv_yinpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, vp, i64, _i32, i64p, vp]
     L.fv_yinpool_step.restype = _i32
     L.fv_oscpool_step.argtypes = [vp, wip, _i32, vp, i64, vp, i64, _i32, i64p, vp]

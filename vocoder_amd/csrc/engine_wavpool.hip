@@ -75,9 +75,9 @@ FV_API size_t fv_wavpool_workspace_bytes(const fv_wavpool* p) { return p ? p->ws
 
 FV_API int32_t fv_wavpool_max_frames(const fv_wavpool* p) { return p ? p->max_frames : 0; }
 
-FV_API int64_t fv_wavpool_received_samples(const fv_wavpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+FV_API int64_t fv_wavpool_received_samples(const fv_wavpool* p, int32_t s) { return sample_pool_received(p, s); }
 
-FV_API int64_t fv_wavpool_emitted_frames(const fv_wavpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+FV_API int64_t fv_wavpool_emitted_frames(const fv_wavpool* p, int32_t s) { return sample_pool_emitted(p, s); }
 
 FV_API int64_t fv_wavpool_pending_samples(const fv_wavpool* p, int32_t s) {
     if (!p || s < 0 || s >= p->S) return 0;
@@ -92,25 +92,12 @@ FV_API int32_t fv_wavpool_plan(const fv_logmel_config* cfg, int32_t sessions, in
         set_error("%s: unusable config (need n_fft >= 1, 1 <= hop_length <= win_length)", fn);
         return FV_ERR_INVALID;
     }
-    if (sessions < 1 || sessions > 65535 || max_chunk_samples < 1 || max_chunk_samples > (1 << 28)) {
-        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk_samples);
-        return FV_ERR_INVALID;
-    }
-    if (!received || !emitted || (count > 0 && !frames_out)) {
-        set_error("%s: null argument", fn);
-        return FV_ERR_INVALID;
-    }
-    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
-    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk_samples, received, flushed, items, count, false, nullptr, 0,
-                                               N2.data()))
-        return rs;
-    if (const fv_status rs = wavpool_emission(fn, *cfg, emitted, items, count, N2.data(), E2.data())) return rs;
-    int64_t k_max = 0;
-    for (int i = 0; i < count; ++i) {
-        frames_out[i] = E2[(size_t)i] - emitted[items[i].session];
-        k_max = std::max(k_max, frames_out[i]);
-    }
-    return (int32_t)std::min<int64_t>(k_max, INT32_MAX);
+    if (const fv_status st = sample_pool_range(fn, sessions, max_chunk_samples)) return st;
+    const int64_t k_max = sample_pool_plan(fn, sessions, max_chunk_samples, received, emitted, flushed, items, count, frames_out,
+                                           [&](const long long* N2, long long* E2) {
+                                               return wavpool_emission(fn, *cfg, emitted, items, count, N2, E2);
+                                           });
+    return (int32_t)std::min<int64_t>(k_max, INT32_MAX);   // (a refusal is negative and passes as it is)
 }
 
 FV_API fv_status fv_wavpool_step(fv_wavpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
@@ -128,20 +115,18 @@ FV_API fv_status fv_wavpool_step(fv_wavpool* p, const fv_wavpool_item* items, in
     const fv_logmel_config& mc = e->cfg.mel;
     if (const fv_status rs = wavpool_emission(fn, mc, p->E.data(), items, count, N2.data(), E2.data())) return rs;
     // one table entry per item: `win` the rows that emit, in item order; `carry` the items that push samples
-    std::vector<SamplePoolEntry> win, carry;
+    std::vector<SamplePoolEntry> all, win, carry;
+    p->build_entries(items, count, N2.data(), E2.data(), all, carry);
     std::vector<PoolCropEntry> crop((size_t)count);
     long long k_max = 0;
     for (int i = 0; i < count; ++i) {
-        const size_t s = (size_t)items[i].session;
-        const long long N = p->N[s], E = p->E[s], k = E2[(size_t)i] - E;
-        const SamplePoolEntry en{i, items[i].session, (int)p->cur[s], (int)k, N - p->H, N, items[i].flush ? N2[(size_t)i] : -1, N2[(size_t)i], E};
+        const long long k = E2[(size_t)i] - p->E[(size_t)items[i].session];
         if (k > p->max_frames) {   // (cannot happen: max_frames bounds every item's emission)
             set_error("%s: internal: session %d emits %lld frames in one step, the pool was sized for %d", fn, items[i].session, k, p->max_frames);
             return FV_ERR_INVALID;
         }
         crop[(size_t)i] = PoolCropEntry{i, k > 0 ? (int)win.size() : -1, 0, k};
-        if (k > 0) win.push_back(en);
-        if (items[i].samples > 0) carry.push_back(en);
+        if (k > 0) win.push_back(all[(size_t)i]);
         k_max = std::max(k_max, k);
     }
     if (out_frames < k_max || out_frames < 0) {
@@ -180,13 +165,7 @@ FV_API fv_status fv_wavpool_step(fv_wavpool* p, const fv_wavpool_item* items, in
     return FV_OK;
 }
 
-FV_API fv_status fv_wavpool_reset(fv_wavpool* p, int32_t session) {
-    if (!p) {
-        set_error("fv_wavpool_reset: null pool");
-        return FV_ERR_INVALID;
-    }
-    return p->reset("fv_wavpool_reset", session);
-}
+FV_API fv_status fv_wavpool_reset(fv_wavpool* p, int32_t session) { return sample_pool_reset(p, "fv_wavpool_reset", session); }
 
 FV_API void fv_wavpool_destroy(fv_wavpool* p) { delete p; }
 

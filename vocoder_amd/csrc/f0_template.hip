@@ -933,14 +933,6 @@ struct fv_oscpool : SamplePool {
     }
 };
 
-static fv_status f0_pool_range(const char* fn, int sessions, int max_chunk) {
-    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
-        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);
-        return FV_ERR_INVALID;
-    }
-    return FV_OK;
-}
-
 // The most one tracker item emits: a push of max_chunk samples that also flushes, from a state with E = ready(N):
 // g(N) = (N + max_chunk) / hop - ready(N).  From N = hop / 2 + W / 2 on, ready(N + hop) = ready(N) + 1, so g has the period hop there.
 static long long yinpool_max_frames(const YinPlan& pl, int max_chunk) {
@@ -960,42 +952,6 @@ static void yinpool_emission(const YinPlan& pl, const int64_t* emitted, const fv
 
 static void oscpool_emission(const int64_t* emitted, const fv_wavpool_item* items, int count, const long long* T2, long long* E2) {
     for (int i = 0; i < count; ++i) E2[i] = std::max((long long)emitted[items[i].session], items[i].flush ? T2[i] : T2[i] - 1);
-}
-
-// What both plans return: E' - E per item and the largest of them
-static int64_t f0_pool_counts(const int64_t* emitted, const fv_wavpool_item* items, int count, const long long* E2, int64_t* frames_out) {
-    int64_t k_max = 0;
-    for (int i = 0; i < count; ++i) {
-        frames_out[i] = E2[i] - emitted[items[i].session];
-        k_max = std::max(k_max, frames_out[i]);
-    }
-    return k_max;
-}
-
-// The refusals of a step's output buffer (fv_respool_step's): `need` columns for the item that emits most, `what` names a column
-static fv_status f0_pool_output(const char* fn, const char* what, const fv_wavpool_item* items, int count, const int64_t* emitted,
-                                const long long* E2, long long per_frame, bool have_out, long long out_stride, int out_cols) {
-    long long k_max = 0;
-    int k_item = 0;
-    for (int i = 0; i < count; ++i) {
-        const long long k = (E2[i] - emitted[items[i].session]) * per_frame;
-        if (k > k_max) k_max = k, k_item = i;
-    }
-    const int k_session = count > 0 ? items[k_item].session : -1;
-    if (out_cols < k_max || out_cols < 0) {
-        set_error("%s: out_cols = %d, but item %d (session %d) emits %lld %s in this step", fn, out_cols, k_item, k_session, k_max, what);
-        return FV_ERR_INVALID;
-    }
-    if (out_stride < out_cols) {
-        set_error("%s: out_stride = %lld is shorter than out_cols = %d (item %d, session %d, emits %lld %s)", fn, out_stride, out_cols, k_item,
-                  k_session, k_max, what);
-        return FV_ERR_INVALID;
-    }
-    if (k_max > 0 && !have_out) {
-        set_error("%s: null output although item %d (session %d) emits %lld %s", fn, k_item, k_session, k_max, what);
-        return FV_ERR_INVALID;
-    }
-    return FV_OK;
 }
 
 extern "C" {
@@ -1018,9 +974,9 @@ FV_API fv_status fv_yinpool_create(fv_f0* f, int32_t sessions, int32_t max_chunk
 
 FV_API int64_t fv_yinpool_max_frames(const fv_yinpool* p) { return p ? p->max_frames : 0; }
 
-FV_API int64_t fv_yinpool_received(const fv_yinpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+FV_API int64_t fv_yinpool_received(const fv_yinpool* p, int32_t s) { return sample_pool_received(p, s); }
 
-FV_API int64_t fv_yinpool_emitted(const fv_yinpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+FV_API int64_t fv_yinpool_emitted(const fv_yinpool* p, int32_t s) { return sample_pool_emitted(p, s); }
 
 FV_API int64_t fv_yinpool_pending(const fv_yinpool* p, int32_t s) {
     return p && s >= 0 && s < p->S ? yin_pending(p->p->plan, p->N[(size_t)s], p->E[(size_t)s]) : 0;
@@ -1031,16 +987,12 @@ FV_API int64_t fv_yinpool_plan(const fv_f0_config* cfg, int32_t sessions, int32_
     const char* fn = "fv_yinpool_plan";
     YinPlan pl;
     if (const fv_status st = make_yin_plan(cfg, fn, pl)) return st;
-    if (const fv_status st = f0_pool_range(fn, sessions, max_chunk)) return st;
-    if (!received || !emitted || (count > 0 && !frames_out)) {
-        set_error("%s: null argument", fn);
-        return FV_ERR_INVALID;
-    }
-    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
-    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk, received, flushed, items, count, false, nullptr, 0, N2.data()))
-        return rs;
-    yinpool_emission(pl, emitted, items, count, N2.data(), E2.data());
-    return f0_pool_counts(emitted, items, count, E2.data(), frames_out);
+    if (const fv_status st = sample_pool_range(fn, sessions, max_chunk)) return st;
+    return sample_pool_plan(fn, sessions, max_chunk, received, emitted, flushed, items, count, frames_out,
+                            [&](const long long* N2, long long* E2) {
+                                yinpool_emission(pl, emitted, items, count, N2, E2);
+                                return FV_OK;
+                            });
 }
 
 FV_API fv_status fv_yinpool_step(fv_yinpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
@@ -1055,20 +1007,17 @@ FV_API fv_status fv_yinpool_step(fv_yinpool* p, const fv_wavpool_item* items, in
     if (const fv_status rs = p->admit(fn, "fv_yinpool_reset", items, count, d_chunks, chunk_stride, N2.data())) return rs;
     const YinPlan& pl = p->p->plan;
     yinpool_emission(pl, p->E.data(), items, count, N2.data(), E2.data());
-    if (const fv_status rs = f0_pool_output(fn, "frames", items, count, p->E.data(), E2.data(), 1, d_f0 != nullptr, out_stride, out_cols))
+    if (const fv_status rs = sample_pool_output(fn, "frames", items, count, p->E.data(), E2.data(), 1, d_f0 != nullptr, out_stride, out_cols))
         return rs;
     // one table entry per item, in item order: every row of the outputs is written; `carry` the items that push samples
-    std::vector<SamplePoolEntry> rows((size_t)count), carry;
+    std::vector<SamplePoolEntry> rows, carry;
+    p->build_entries(items, count, N2.data(), E2.data(), rows, carry);      // E2 - E <= out_cols: it fits an int
     for (int i = 0; i < count; ++i) {
-        const size_t s = (size_t)items[i].session;
-        const long long N = p->N[s], E = p->E[s], k = E2[(size_t)i] - E;      // k <= out_cols: it fits an int
-        const SamplePoolEntry en{i, items[i].session, (int)p->cur[s], (int)k, N - p->H, N, items[i].flush ? N2[(size_t)i] : -1, N2[(size_t)i], E};
-        rows[(size_t)i] = en;
-        if (items[i].samples > 0) carry.push_back(en);
-        const long long lo = E * pl.hop + pl.hop / 2 - pl.W / 2;
-        if (k > 0 && en.carry_origin > 0 && lo < en.carry_origin) {   // (cannot happen: a frame not yet emitted starts less than H samples before N)
-            set_error("%s: internal: frame %lld of session %d reads sample %lld, before the %d carried samples that end at %lld", fn, E,
-                      items[i].session, lo, p->H, N);
+        const SamplePoolEntry& en = rows[(size_t)i];
+        const long long lo = en.first * pl.hop + pl.hop / 2 - pl.W / 2;
+        if (en.count > 0 && en.carry_origin > 0 && lo < en.carry_origin) {   // (cannot happen: a frame not yet emitted starts less than H samples before N)
+            set_error("%s: internal: frame %lld of session %d reads sample %lld, before the %d carried samples that end at %lld", fn, en.first,
+                      items[i].session, lo, p->H, en.chunk_origin);
             return FV_ERR_INVALID;
         }
     }
@@ -1089,13 +1038,7 @@ FV_API fv_status fv_yinpool_step(fv_yinpool* p, const fv_wavpool_item* items, in
     return FV_OK;
 }
 
-FV_API fv_status fv_yinpool_reset(fv_yinpool* p, int32_t session) {
-    if (!p) {
-        set_error("fv_yinpool_reset: null pool");
-        return FV_ERR_INVALID;
-    }
-    return p->reset("fv_yinpool_reset", session);
-}
+FV_API fv_status fv_yinpool_reset(fv_yinpool* p, int32_t session) { return sample_pool_reset(p, "fv_yinpool_reset", session); }
 
 FV_API void fv_yinpool_destroy(fv_yinpool* p) { delete p; }
 
@@ -1127,9 +1070,9 @@ FV_API fv_status fv_oscpool_create(fv_template* t, int32_t sessions, int32_t max
 
 FV_API int64_t fv_oscpool_max_frames(const fv_oscpool* p) { return p ? (int64_t)p->max_chunk + 1 : 0; }
 
-FV_API int64_t fv_oscpool_received(const fv_oscpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+FV_API int64_t fv_oscpool_received(const fv_oscpool* p, int32_t s) { return sample_pool_received(p, s); }
 
-FV_API int64_t fv_oscpool_emitted(const fv_oscpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+FV_API int64_t fv_oscpool_emitted(const fv_oscpool* p, int32_t s) { return sample_pool_emitted(p, s); }
 
 FV_API int64_t fv_oscpool_pending(const fv_oscpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] - p->E[(size_t)s] : 0; }
 
@@ -1138,17 +1081,12 @@ FV_API int64_t fv_oscpool_plan(const fv_template_config* cfg, int32_t sessions, 
                                int64_t* frames_out) {
     const char* fn = "fv_oscpool_plan";
     if (const fv_status st = check_template_config(cfg, fn)) return st;
-    if (const fv_status st = f0_pool_range(fn, sessions, max_chunk_frames)) return st;
-    if (!received || !emitted || (count > 0 && !frames_out)) {
-        set_error("%s: null argument", fn);
-        return FV_ERR_INVALID;
-    }
-    std::vector<long long> T2((size_t)std::max(count, 0)), E2(T2.size());
-    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk_frames, received, flushed, items, count, false, nullptr, 0,
-                                               T2.data()))
-        return rs;
-    oscpool_emission(emitted, items, count, T2.data(), E2.data());
-    return f0_pool_counts(emitted, items, count, E2.data(), frames_out);
+    if (const fv_status st = sample_pool_range(fn, sessions, max_chunk_frames)) return st;
+    return sample_pool_plan(fn, sessions, max_chunk_frames, received, emitted, flushed, items, count, frames_out,
+                            [&](const long long* T2, long long* E2) {
+                                oscpool_emission(emitted, items, count, T2, E2);
+                                return FV_OK;
+                            });
 }
 
 FV_API fv_status fv_oscpool_step(fv_oscpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
@@ -1164,13 +1102,13 @@ FV_API fv_status fv_oscpool_step(fv_oscpool* p, const fv_wavpool_item* items, in
     const fv_template_config& cfg = p->p->cfg;
     const int hop = cfg.hop_length;
     oscpool_emission(p->E.data(), items, count, T2.data(), E2.data());
-    if (const fv_status rs = f0_pool_output(fn, "samples", items, count, p->E.data(), E2.data(), hop, d_out != nullptr, out_stride, out_cols))
+    if (const fv_status rs = sample_pool_output(fn, "samples", items, count, p->E.data(), E2.data(), hop, d_out != nullptr, out_stride, out_cols))
         return rs;
     std::vector<OscPoolEntry> rows((size_t)count);
     std::vector<SamplePoolEntry> carry;
     for (int i = 0; i < count; ++i) {
         const size_t s = (size_t)items[i].session;
-        const long long Tn = p->N[s], E = p->E[s], k = E2[(size_t)i] - E, o = Tn - 2;   // column 0 of the item's F row is frame o
+        const long long Tn = p->N[s], E = p->E[s], o = Tn - 2;   // column 0 of the item's F row is frame o
         const int c = items[i].samples;
         if (E - o < 1 || E - o > 2) {   // (cannot happen: between calls Tn - E is 0 or 1)
             set_error("%s: internal: session %d has received %lld frames and emitted %lld", fn, items[i].session, Tn, E);
@@ -1183,9 +1121,7 @@ FV_API fv_status fv_oscpool_step(fv_oscpool* p, const fv_wavpool_item* items, in
         en.n_lo = (int)((E - o) * hop), en.n_hi = (int)((E2[(size_t)i] - o) * hop);
         en.nchunk = (en.n_hi - en.n_lo + kTmplChunk - 1) / kTmplChunk;
         rows[(size_t)i] = en;
-        if (c > 0)
-            carry.push_back(SamplePoolEntry{i, items[i].session, (int)p->cur[s], (int)k, o, Tn, items[i].flush ? T2[(size_t)i] : -1,
-                                            T2[(size_t)i], E});
+        if (c > 0) carry.push_back(p->entry(i, items[i], T2[(size_t)i], E2[(size_t)i]));   // H = 2: the carry's origin is o
     }
     hipStream_t s = (hipStream_t)stream;
     if (count > 0 && out_cols > 0 && d_out) {
@@ -1221,13 +1157,7 @@ FV_API fv_status fv_oscpool_step(fv_oscpool* p, const fv_wavpool_item* items, in
     return FV_OK;
 }
 
-FV_API fv_status fv_oscpool_reset(fv_oscpool* p, int32_t session) {
-    if (!p) {
-        set_error("fv_oscpool_reset: null pool");
-        return FV_ERR_INVALID;
-    }
-    return p->reset("fv_oscpool_reset", session);
-}
+FV_API fv_status fv_oscpool_reset(fv_oscpool* p, int32_t session) { return sample_pool_reset(p, "fv_oscpool_reset", session); }
 
 FV_API void fv_oscpool_destroy(fv_oscpool* p) { delete p; }
 

@@ -755,14 +755,11 @@ static fv_status pvpool_moves(const PvPoolRule& r, const char* fn, const int64_t
     return FV_OK;
 }
 
-static fv_status pvpool_range(const char* fn, int sessions, int max_chunk, const PvPoolRule* r) {
-    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
-        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);
-        return FV_ERR_INVALID;
-    }
-    if (r && !r->identity() && (r->maxY > (1 << 28) || r->maxR > (1LL << 30) || (long long)r->pl.N * r->maxS >= (1LL << 31))) {
+// the pool's own range check, once the bounds of `max_chunk` are known: what a step's tensors and the inner resample pool can hold
+static fv_status pvpool_range(const char* fn, int max_chunk, const PvPoolRule& r) {
+    if (!r.identity() && (r.maxY > (1 << 28) || r.maxR > (1LL << 30) || (long long)r.pl.N * r.maxS >= (1LL << 31))) {
         set_error("%s: max_chunk = %d gives %lld stretched frames of %d samples in one step, more than 2^31 elements per row or 2^28 stretched "
-                  "samples; push smaller chunks", fn, max_chunk, r->maxS, r->pl.N);
+                  "samples; push smaller chunks", fn, max_chunk, r.maxS, r.pl.N);
         return FV_ERR_UNSUPPORTED;
     }
     return FV_OK;
@@ -796,12 +793,12 @@ FV_API fv_status fv_pvpool_create(fv_pitch_shift* p, int32_t sessions, int32_t m
         set_error("%s: null argument", fn);
         return FV_ERR_INVALID;
     }
-    if (const fv_status rs = pvpool_range(fn, sessions, max_chunk, nullptr)) return rs;
+    if (const fv_status rs = sample_pool_range(fn, sessions, max_chunk)) return rs;
     std::unique_ptr<fv_pvpool> q(new fv_pvpool());
     q->p = p;
     q->rule.pl = p->plan, q->rule.rs = p->identity() ? nullptr : p->rs, q->rule.max_chunk = max_chunk;
     pvpool_bounds(q->rule);
-    if (const fv_status rs = pvpool_range(fn, sessions, max_chunk, &q->rule)) return rs;
+    if (const fv_status rs = pvpool_range(fn, max_chunk, q->rule)) return rs;
     q->pbit.assign((size_t)sessions, 0), q->fbit.assign((size_t)sessions, 0);
     if (p->identity()) {   // the pass-through carries nothing
         q->init(sessions, max_chunk, 0);
@@ -827,9 +824,9 @@ FV_API size_t fv_pvpool_workspace_bytes(const fv_pvpool* p) { return p ? p->ws_b
 
 FV_API int64_t fv_pvpool_max_outputs(const fv_pvpool* p) { return p ? p->rule.max_out : 0; }
 
-FV_API int64_t fv_pvpool_received(const fv_pvpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+FV_API int64_t fv_pvpool_received(const fv_pvpool* p, int32_t s) { return sample_pool_received(p, s); }
 
-FV_API int64_t fv_pvpool_emitted(const fv_pvpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+FV_API int64_t fv_pvpool_emitted(const fv_pvpool* p, int32_t s) { return sample_pool_emitted(p, s); }
 
 FV_API int64_t fv_pvpool_pending(const fv_pvpool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] - p->E[(size_t)s] : 0; }
 
@@ -856,11 +853,11 @@ FV_API fv_status fv_pvpool_bounds(const fv_pitch_shift_config* cfg, int32_t max_
         set_error("%s: null argument", fn);
         return FV_ERR_INVALID;
     }
-    if (const fv_status st = pvpool_range(fn, 1, max_chunk, nullptr)) return st;
+    if (const fv_status st = sample_pool_range(fn, 1, max_chunk)) return st;
     PvPoolRule r;
     RuleHold hold;
     if (const fv_status st = pvpool_rule(cfg, fn, max_chunk, r, hold)) return st;
-    if (const fv_status st = pvpool_range(fn, 1, max_chunk, &r)) return st;
+    if (const fv_status st = pvpool_range(fn, max_chunk, r)) return st;
     bounds[0] = r.maxA, bounds[1] = r.maxS, bounds[2] = r.maxY, bounds[3] = r.maxR, bounds[4] = r.max_out;
     return FV_OK;
 }
@@ -869,26 +866,18 @@ FV_API int64_t fv_pvpool_plan(const fv_pitch_shift_config* cfg, int32_t sessions
                               const int64_t* emitted, const int32_t* flushed, const fv_wavpool_item* items, int32_t count,
                               int64_t* outputs_out) {
     const char* fn = "fv_pvpool_plan";
-    if (const fv_status st = pvpool_range(fn, sessions, max_chunk, nullptr)) return st;
+    if (const fv_status st = sample_pool_range(fn, sessions, max_chunk)) return st;
     PvPoolRule r;
     RuleHold hold;
     if (const fv_status st = pvpool_rule(cfg, fn, max_chunk, r, hold)) return st;
-    if (const fv_status st = pvpool_range(fn, sessions, max_chunk, &r)) return st;
-    if (!received || !emitted || (count > 0 && !outputs_out)) {
-        set_error("%s: null argument", fn);
-        return FV_ERR_INVALID;
-    }
-    std::vector<long long> N2((size_t)std::max(count, 0));
-    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk, received, flushed, items, count, false, nullptr, 0, N2.data()))
-        return rs;
-    std::vector<PvPoolMove> mv;
-    if (const fv_status rs = pvpool_moves(r, fn, received, emitted, items, count, N2.data(), mv)) return rs;
-    int64_t k_max = 0;
-    for (int i = 0; i < count; ++i) {
-        outputs_out[i] = mv[(size_t)i].k;
-        k_max = std::max<int64_t>(k_max, outputs_out[i]);
-    }
-    return k_max;
+    if (const fv_status st = pvpool_range(fn, max_chunk, r)) return st;
+    return sample_pool_plan(fn, sessions, max_chunk, received, emitted, flushed, items, count, outputs_out,
+                            [&](const long long* N2, long long* E2) -> fv_status {
+                                std::vector<PvPoolMove> mv;
+                                if (const fv_status rs = pvpool_moves(r, fn, received, emitted, items, count, N2, mv)) return rs;
+                                for (int i = 0; i < count; ++i) E2[i] = emitted[items[i].session] + mv[(size_t)i].k;   // the counts are the moves' k
+                                return FV_OK;
+                            });
 }
 
 FV_API fv_status fv_pvpool_step(fv_pvpool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
@@ -905,12 +894,10 @@ FV_API fv_status fv_pvpool_step(fv_pvpool* p, const fv_wavpool_item* items, int3
     if (const fv_status rs = p->admit(fn, "fv_pvpool_reset", items, count, d_chunks, chunk_stride, N2.data())) return rs;
     std::vector<PvPoolMove> mv;
     if (const fv_status rs = pvpool_moves(p->rule, fn, p->N.data(), p->E.data(), items, count, N2.data(), mv)) return rs;
-    long long k_max = 0;
-    int k_item = 0, nact = 0;
+    int nact = 0;
     for (int i = 0; i < count; ++i) {
         const PvPoolMove& m = mv[(size_t)i];
         E2[(size_t)i] = m.E2;
-        if (m.k > k_max) k_max = m.k, k_item = i;
         if (!m.active) continue;
         ++nact;
         const int s = items[i].session;
@@ -920,20 +907,8 @@ FV_API fv_status fv_pvpool_step(fv_pvpool* p, const fv_wavpool_item* items, int3
             return FV_ERR_INVALID;
         }
     }
-    const int k_session = count > 0 ? items[k_item].session : -1;
-    if (out_cols < k_max || out_cols < 0) {
-        set_error("%s: out_cols = %d, but item %d (session %d) emits %lld outputs in this step", fn, out_cols, k_item, k_session, k_max);
-        return FV_ERR_INVALID;
-    }
-    if (out_stride < out_cols) {
-        set_error("%s: out_stride = %lld is shorter than out_cols = %d (item %d, session %d, emits %lld outputs)", fn, (long long)out_stride,
-                  out_cols, k_item, k_session, k_max);
-        return FV_ERR_INVALID;
-    }
-    if (k_max > 0 && !d_out) {
-        set_error("%s: null output although item %d (session %d) emits %lld outputs", fn, k_item, k_session, k_max);
-        return FV_ERR_INVALID;
-    }
+    if (const fv_status rs = sample_pool_output(fn, "outputs", items, count, p->E.data(), E2.data(), 1, d_out != nullptr, out_stride, out_cols))
+        return rs;
     if (nact > 0 && (!d_workspace || workspace_bytes < p->ws_bytes())) {
         int a = 0;
         while (!mv[(size_t)a].active) ++a;
@@ -1037,11 +1012,7 @@ FV_API fv_status fv_pvpool_step(fv_pvpool* p, const fv_wavpool_item* items, int3
 }
 
 FV_API fv_status fv_pvpool_reset(fv_pvpool* p, int32_t session) {
-    if (!p) {
-        set_error("fv_pvpool_reset: null pool");
-        return FV_ERR_INVALID;
-    }
-    if (const fv_status rs = p->reset("fv_pvpool_reset", session)) return rs;
+    if (const fv_status rs = sample_pool_reset(p, "fv_pvpool_reset", session)) return rs;
     return p->rs ? fv_respool_reset(p->rs, session) : FV_OK;
 }
 

@@ -692,14 +692,6 @@ fv_status fv::resample_rule_create(const fv_resample_config* cfg, const char* fn
 }
 long long fv::resample_pool_max_outputs(const fv_resample* r, int max_chunk) { return respool_max_outputs(*r, max_chunk); }
 
-static fv_status respool_range(const char* fn, int sessions, int max_chunk) {
-    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
-        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);
-        return FV_ERR_INVALID;
-    }
-    return FV_OK;
-}
-
 extern "C" {
 
 FV_API fv_status fv_respool_create(fv_resample* r, int32_t sessions, int32_t max_chunk, fv_respool** out) {
@@ -720,9 +712,9 @@ FV_API fv_status fv_respool_create(fv_resample* r, int32_t sessions, int32_t max
 
 FV_API int64_t fv_respool_max_outputs(const fv_respool* p) { return p ? p->max_out : 0; }
 
-FV_API int64_t fv_respool_received(const fv_respool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->N[(size_t)s] : 0; }
+FV_API int64_t fv_respool_received(const fv_respool* p, int32_t s) { return sample_pool_received(p, s); }
 
-FV_API int64_t fv_respool_emitted(const fv_respool* p, int32_t s) { return p && s >= 0 && s < p->S ? p->E[(size_t)s] : 0; }
+FV_API int64_t fv_respool_emitted(const fv_respool* p, int32_t s) { return sample_pool_emitted(p, s); }
 
 FV_API int64_t fv_respool_pending(const fv_respool* p, int32_t s) {
     return p && s >= 0 && s < p->S ? p->r->out_len(p->N[(size_t)s]) - p->E[(size_t)s] : 0;
@@ -734,21 +726,12 @@ FV_API int64_t fv_respool_plan(const fv_resample_config* cfg, int32_t sessions, 
     const char* fn = "fv_respool_plan";
     fv_resample r;
     if (const fv_status st = resample_rule(cfg, fn, r)) return st;
-    if (const fv_status st = respool_range(fn, sessions, max_chunk)) return st;
-    if (!received || !emitted || (count > 0 && !outputs_out)) {
-        set_error("%s: null argument", fn);
-        return FV_ERR_INVALID;
-    }
-    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
-    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk, received, flushed, items, count, false, nullptr, 0, N2.data()))
-        return rs;
-    respool_emission(r, emitted, items, count, N2.data(), E2.data());
-    int64_t k_max = 0;
-    for (int i = 0; i < count; ++i) {
-        outputs_out[i] = E2[(size_t)i] - emitted[items[i].session];
-        k_max = std::max(k_max, outputs_out[i]);
-    }
-    return k_max;
+    if (const fv_status st = sample_pool_range(fn, sessions, max_chunk)) return st;
+    return sample_pool_plan(fn, sessions, max_chunk, received, emitted, flushed, items, count, outputs_out,
+                            [&](const long long* N2, long long* E2) {
+                                respool_emission(r, emitted, items, count, N2, E2);
+                                return FV_OK;
+                            });
 }
 
 FV_API fv_status fv_respool_step(fv_respool* p, const fv_wavpool_item* items, int32_t count, const float* d_chunks, int64_t chunk_stride,
@@ -763,40 +746,20 @@ FV_API fv_status fv_respool_step(fv_respool* p, const fv_wavpool_item* items, in
     if (const fv_status rs = p->admit(fn, "fv_respool_reset", items, count, d_chunks, chunk_stride, N2.data())) return rs;
     const fv_resample* r = p->r;
     respool_emission(*r, p->E.data(), items, count, N2.data(), E2.data());
-    long long k_max = 0;
-    int k_item = 0;
-    for (int i = 0; i < count; ++i) {
-        const long long k = E2[(size_t)i] - p->E[(size_t)items[i].session];
-        if (k > k_max) k_max = k, k_item = i;
-    }
-    const int k_session = count > 0 ? items[k_item].session : -1;
-    if (out_cols < k_max || out_cols < 0) {
-        set_error("%s: out_cols = %d, but item %d (session %d) emits %lld outputs in this step", fn, out_cols, k_item, k_session, k_max);
-        return FV_ERR_INVALID;
-    }
-    if (out_stride < out_cols) {
-        set_error("%s: out_stride = %lld is shorter than out_cols = %d (item %d, session %d, emits %lld outputs)", fn, (long long)out_stride,
-                  out_cols, k_item, k_session, k_max);
-        return FV_ERR_INVALID;
-    }
-    if (k_max > 0 && !d_out) {
-        set_error("%s: null output although item %d (session %d) emits %lld outputs", fn, k_item, k_session, k_max);
-        return FV_ERR_INVALID;
-    }
-    // one table entry per item, in item order: every row of d_out is written; `carry` the items that push samples
-    std::vector<SamplePoolEntry> fir((size_t)count), carry;
+    if (const fv_status rs = sample_pool_output(fn, "outputs", items, count, p->E.data(), E2.data(), 1, d_out != nullptr, out_stride, out_cols))
+        return rs;
+    // one table entry per item, in item order: every row of d_out is written (E2 - E <= out_cols: it fits an int); `carry` the items that push samples
+    std::vector<SamplePoolEntry> fir, carry;
+    p->build_entries(items, count, N2.data(), E2.data(), fir, carry);
     std::vector<int> tiles((size_t)count, 0);
     for (int i = 0; i < count; ++i) {
-        const size_t s = (size_t)items[i].session;
-        const long long N = p->N[s], E = p->E[s], k = E2[(size_t)i] - E;      // k <= out_cols: it fits an int
-        const SamplePoolEntry en{i, items[i].session, (int)p->cur[s], (int)k, N - p->H, N, items[i].flush ? N2[(size_t)i] : -1, N2[(size_t)i], E};
-        fir[(size_t)i] = en;
-        if (items[i].samples > 0) carry.push_back(en);
-        if (k > 0) {
+        const SamplePoolEntry& en = fir[(size_t)i];
+        const long long E = en.first;
+        if (en.count > 0) {
             const long long X0 = r->s_of(E), j0 = X0 - r->d.width;
             if (en.carry_origin > 0 && j0 < en.carry_origin) {   // (cannot happen: an output not yet emitted starts less than Kp <= H samples before N)
                 set_error("%s: internal: output %lld of session %d reads sample %lld, before the %d carried samples that end at %lld", fn, E,
-                          items[i].session, j0, p->H, N);
+                          items[i].session, j0, p->H, en.chunk_origin);
                 return FV_ERR_INVALID;
             }
             tiles[(size_t)i] = (int)((r->s_of(E2[(size_t)i] - 1) - X0) / kResTile + 1);
@@ -829,13 +792,7 @@ FV_API fv_status fv_respool_step(fv_respool* p, const fv_wavpool_item* items, in
     return FV_OK;
 }
 
-FV_API fv_status fv_respool_reset(fv_respool* p, int32_t session) {
-    if (!p) {
-        set_error("fv_respool_reset: null pool");
-        return FV_ERR_INVALID;
-    }
-    return p->reset("fv_respool_reset", session);
-}
+FV_API fv_status fv_respool_reset(fv_respool* p, int32_t session) { return sample_pool_reset(p, "fv_respool_reset", session); }
 
 FV_API void fv_respool_destroy(fv_respool* p) { delete p; }
 

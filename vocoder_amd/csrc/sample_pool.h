@@ -4,7 +4,9 @@
 // and then flips that slot's bit alone.  A step touches only some slots; one toggle for all of them (sample_stream.h) would leave the
 // untouched slots' carry in the buffer the next step no longer reads.  Per slot the streams' rule holds: no launch reads and writes the same
 // buffer.  A step is checked whole before any counter moves (admit), and only its items' counters move (commit).  What a pool emits, and what
-// it runs between admit() and commit(), is its own.  admit / commit / reset make no HIP runtime call: a host program can drive them.
+// it runs between admit() and commit(), is its own.  What the pools state the same way is here too: the range check, the refusals of a step's
+// output buffer, the tail of a *_plan and the table entry of an item.  Only create() and the destructor make a HIP runtime call: a host
+// program can drive everything else.
 #pragma once
 
 #include "sample_stream.h"
@@ -68,6 +70,67 @@ inline fv_status sample_pool_admit(const char* fn, const char* reset_fn, int S, 
     return FV_OK;
 }
 
+// The range check of every *_create and *_plan
+inline fv_status sample_pool_range(const char* fn, int sessions, int max_chunk) {
+    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 28)) {
+        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, max_chunk);
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+
+// The refusals of a step's output buffer: (E2 - E) * per_unit columns for the item that emits most, `what` names a column
+inline fv_status sample_pool_output(const char* fn, const char* what, const SamplePoolItem* items, int count, const int64_t* emitted,
+                                    const long long* E2, long long per_unit, bool have_out, long long out_stride, int out_cols) {
+    long long k_max = 0;
+    int k_item = 0;
+    for (int i = 0; i < count; ++i) {
+        const long long k = (E2[i] - emitted[items[i].session]) * per_unit;
+        if (k > k_max) k_max = k, k_item = i;
+    }
+    const int k_session = count > 0 ? items[k_item].session : -1;
+    if (out_cols < k_max || out_cols < 0) {
+        set_error("%s: out_cols = %d, but item %d (session %d) emits %lld %s in this step", fn, out_cols, k_item, k_session, k_max, what);
+        return FV_ERR_INVALID;
+    }
+    if (out_stride < out_cols) {
+        set_error("%s: out_stride = %lld is shorter than out_cols = %d (item %d, session %d, emits %lld %s)", fn, out_stride, out_cols, k_item,
+                  k_session, k_max, what);
+        return FV_ERR_INVALID;
+    }
+    if (k_max > 0 && !have_out) {
+        set_error("%s: null output although item %d (session %d) emits %lld %s", fn, k_item, k_session, k_max, what);
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+
+// What a plan returns: E' - E per item and the largest of them
+inline int64_t sample_pool_counts(const int64_t* emitted, const SamplePoolItem* items, int count, const long long* E2, int64_t* out) {
+    int64_t k_max = 0;
+    for (int i = 0; i < count; ++i) {
+        out[i] = E2[i] - emitted[items[i].session];
+        k_max = std::max(k_max, out[i]);
+    }
+    return k_max;
+}
+
+// The tail of a *_plan, after the pool's own checks of its config and sample_pool_range: the null arguments, the admit without buffers, the
+// pool's rule `emission(N2, E2) -> fv_status`, which fills E2 and may refuse, and the counts.  A negative fv_status, or the largest count.
+template <class Emission>
+inline int64_t sample_pool_plan(const char* fn, int sessions, int max_chunk, const int64_t* received, const int64_t* emitted,
+                                const int32_t* flushed, const SamplePoolItem* items, int count, int64_t* out, Emission&& emission) {
+    if (!received || !emitted || (count > 0 && !out)) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status rs = sample_pool_admit(fn, "reset", sessions, max_chunk, received, flushed, items, count, false, nullptr, 0, N2.data()))
+        return rs;
+    if (const fv_status rs = emission(N2.data(), E2.data())) return rs;
+    return sample_pool_counts(emitted, items, count, E2.data(), out);
+}
+
 struct SamplePool {
     int S = 0, max_chunk = 0, H = 0;
     float* buf[2] = {nullptr, nullptr};     // two (S, H) buffers of one allocation
@@ -80,10 +143,7 @@ struct SamplePool {
 
     // the range checks of `fn` (a *_create), then two zeroed (sessions, h) buffers
     fv_status create(const char* fn, int sessions, int chunk, int h) {
-        if (sessions < 1 || sessions > 65535 || chunk < 1 || chunk > (1 << 28)) {
-            set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^28]", fn, sessions, chunk);
-            return FV_ERR_INVALID;
-        }
+        if (const fv_status rs = sample_pool_range(fn, sessions, chunk)) return rs;
         init(sessions, chunk, h);
         const size_t elems = (size_t)sessions * (size_t)h;
         FV_HIP_CHECK(hipMalloc((void**)&buf[0], 2 * elems * sizeof(float)));
@@ -102,6 +162,22 @@ struct SamplePool {
         return sample_pool_admit(fn, reset_fn, S, max_chunk, N.data(), flushed.data(), items, count, true, chunks, chunk_stride, N2);
     }
 
+    // The table entry of item i once admit gave N2 and the pool's rule E2: the slot's bit, the E2 - E it emits (its caller bounds that to an
+    // int), the carried samples [N - H, N), the chunk up to N2 and, with a flush, the utterance's end there
+    SamplePoolEntry entry(int i, const SamplePoolItem& item, long long N2, long long E2) const {
+        const size_t s = (size_t)item.session;
+        return SamplePoolEntry{i, item.session, (int)cur[s], (int)(E2 - E[s]), N[s] - H, N[s], item.flush ? N2 : -1, N2, E[s]};
+    }
+    // one entry per item in `rows`, in item order, and in `carry` those of the items that push samples (launch_sample_pool_carry)
+    void build_entries(const SamplePoolItem* items, int count, const long long* N2, const long long* E2, std::vector<SamplePoolEntry>& rows,
+                       std::vector<SamplePoolEntry>& carry) const {
+        rows.resize((size_t)std::max(count, 0)), carry.clear();
+        for (int i = 0; i < count; ++i) {
+            rows[(size_t)i] = entry(i, items[i], N2[i], E2[i]);
+            if (items[i].samples > 0) carry.push_back(rows[(size_t)i]);
+        }
+    }
+
     // the step was enqueued: the items' counters move, and the bit of every slot that pushed samples flips (the step wrote its other buffer)
     void commit(const SamplePoolItem* items, int count, const long long* N2, const long long* E2) {
         for (int i = 0; i < count; ++i) {
@@ -111,6 +187,9 @@ struct SamplePool {
             if (items[i].samples > 0) cur[s] ^= 1;
         }
     }
+
+    int64_t received(int s) const { return s >= 0 && s < S ? N[(size_t)s] : 0; }
+    int64_t emitted(int s) const { return s >= 0 && s < S ? E[(size_t)s] : 0; }
 
     // the next utterance of one slot: samples before 0 are zeros by index, whatever the carried buffer holds
     fv_status reset(const char* fn, int s) {
@@ -123,5 +202,16 @@ struct SamplePool {
         return FV_OK;
     }
 };
+
+// fv_*pool_received / _emitted / _reset on a pool that may be NULL
+inline int64_t sample_pool_received(const SamplePool* p, int s) { return p ? p->received(s) : 0; }
+inline int64_t sample_pool_emitted(const SamplePool* p, int s) { return p ? p->emitted(s) : 0; }
+inline fv_status sample_pool_reset(SamplePool* p, const char* fn, int s) {
+    if (!p) {
+        set_error("%s: null pool", fn);
+        return FV_ERR_INVALID;
+    }
+    return p->reset(fn, s);
+}
 
 }  // namespace fv

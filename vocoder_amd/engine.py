@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib, framing as _framing, sessions as _sessions, streaming
-from ._handle import _Handle, _emit, _require_cuda
+from ._handle import _Handle, _emit, _gather, _pool_items, _pool_moved, _require_cuda
 from ._lib import FishVocError, check  # noqa: F401
 
 _SIDE_STREAM_FOR_DEFAULT = os.environ.get("FV_DEFAULT_STREAM_SIDE", "0") == "1"   # experiments: see Engine.forward
@@ -761,23 +761,7 @@ class WavPool(_EngineHandle):
     def step(self, items) -> list[torch.Tensor]:
         """One step for ``items`` (see the class); returns each item's frames ``(C_out, k)``, views of one output buffer."""
         self._check_open()
-        meta, rows = [], []
-        for it in map(tuple, items):
-            s, x, flush = it[0], it[1], it[2] if len(it) > 2 else False
-            if x is not None:
-                _require_cuda(x, "WavPool.step")
-                if x.dim() != 1:
-                    raise ValueError(f"expected a 1-D chunk of samples, got {tuple(x.shape)}")
-            rows.append(x)
-            meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(flush)))
-        longest = max((c for _, c, _ in meta), default=0)
-        chunks = None
-        if longest:
-            chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=self._engine.device)
-            for i, x in enumerate(rows):
-                if x is not None and x.shape[0]:
-                    chunks[i, :x.shape[0]] = x
-        out, emit = self.step_padded(meta, chunks)
+        out, emit = self.step_padded(*_gather(items, self._engine.device, _require_cuda, "WavPool.step"))
         return [out[i, :, :k] for i, k in enumerate(emit)]
 
     def step_padded(self, items, chunks: torch.Tensor | None, out: torch.Tensor | None = None) -> tuple[torch.Tensor, list[int]]:
@@ -786,7 +770,7 @@ class WavPool(_EngineHandle):
         item has samples; ``out``: ``(count, C_out, out_frames)``, sized from the Python plan when not given.  Returns ``(out, frames emitted
         per item)``: row i holds item i's frames first and zeros after them."""
         self._check_open()
-        items = [(int(s), int(c), bool(f)) for s, c, f in items]
+        items, arr, got = _pool_items(items)
         count = len(items)
         stride = 0
         if chunks is not None:
@@ -800,17 +784,11 @@ class WavPool(_EngineHandle):
             out = torch.empty((count, self.out_channels, max(plan, default=0)), dtype=torch.float32, device=dev)
         elif out.dim() != 3 or out.shape[0] != count or out.shape[1] != self.out_channels or not out.is_contiguous():
             raise ValueError(f"expected a contiguous out of shape ({count}, {self.out_channels}, out_frames), got {tuple(out.shape)}")
-        arr = (_lib.WavPoolItem * max(count, 1))(*[_lib.WavPoolItem(s, c, int(f)) for s, c, f in items])
-        got = (ctypes.c_int64 * max(count, 1))()
         self._engine._enqueue(dev, lambda stream: self._lib.fv_wavpool_step(
             self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None, stride,
             out.data_ptr() if out.numel() else None, int(out.shape[2]), got, self._ws.data_ptr(), self._ws.numel() * 4, stream),
             owner=self, eager=True)
-        emit = [int(got[i]) for i in range(count)]
-        self.counters.apply(items, plan)                          # the Python counters move as the library's did
-        if plan != emit:
-            raise RuntimeError(f"the wav pool emitted {emit} frames where the framing rule says {plan}")
-        return out, emit
+        return out, _pool_moved(self.counters, items, plan, got, "the wav pool emitted {emit} frames where the framing rule says {plan}")
 
     def reset(self, session: int) -> None:
         """Start the next utterance in one slot: N = E = 0; its carry is kept."""

@@ -35,9 +35,10 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._handle import _DeviceHandles, _Handle, _emit
+from ._handle import _DeviceHandles, _Handle, _SamplePoolHandle, _emit, _gather
 from ._lib import check
 from .resample import _require_cuda, _rows
+from .sample_pool import SamplePoolCounters
 
 MAX_FRAME_LENGTH = 4096      # one workgroup stages the frame in LDS (fv_f0_create)
 
@@ -417,72 +418,7 @@ class TemplateStream:
 # ---------------------------------------------------------------------------------------------
 # Pools: sessions that advance independently (fv_yinpool_* / fv_oscpool_*), what the streams above are to rows in lockstep
 # ---------------------------------------------------------------------------------------------
-MAX_SAMPLES = 1 << 40       # samples (or frames) of one utterance, as the library counts (sample_stream.h)
-
-
-class _F0PoolCounters:
-    """The host counters of one of the two pools: ``received[s]``, ``emitted[s]`` and ``flushed[s]`` per slot, and the plan of a step in plain
-    Python.  ``plan(items)`` — items ``(session, samples, flush)`` — says how many frames every item emits and changes nothing; it refuses
-    what the library refuses of the items, in its order per item: ``ValueError`` for a session out of range, a duplicate session and samples
-    outside ``[0, max_chunk]``, ``PoolStateError`` for a flushed slot, ``ValueError`` past 2^40 samples.  ``apply`` moves the counters as a
-    step that emitted the plan does; ``step`` is both."""
-
-    def __init__(self, sessions: int, max_chunk: int):
-        self.S, self.max_chunk = int(sessions), int(max_chunk)
-        if not 1 <= self.S <= 65535 or not 1 <= self.max_chunk <= 1 << 28:
-            raise ValueError(f"sessions ({self.S}) must lie in [1, 65535] and max_chunk ({self.max_chunk}) in [1, 2^28]")
-        self.received = [0] * self.S
-        self.emitted = [0] * self.S
-        self.flushed = [False] * self.S
-
-    def _emitted(self, N2: int, flush: bool) -> int:      # E' before the max with E
-        raise NotImplementedError
-
-    @staticmethod
-    def _items(items) -> list:
-        return [(int(it[0]), int(it[1]), bool(it[2]) if len(it) > 2 else False) for it in items]
-
-    def plan(self, items) -> list:
-        """Frames every item of the step emits, in item order."""
-        from .sessions import PoolStateError
-        seen, out = set(), []
-        for i, (s, c, flush) in enumerate(self._items(items)):
-            if not 0 <= s < self.S:
-                raise ValueError(f"item {i} names session {s}, outside [0, {self.S})")
-            if s in seen:
-                raise ValueError(f"duplicate session {s} (item {i}): a session appears at most once per step")
-            seen.add(s)
-            if not 0 <= c <= self.max_chunk:
-                raise ValueError(f"item {i} (session {s}) has {c} samples, outside [0, max_chunk = {self.max_chunk}]")
-            if self.flushed[s]:
-                raise PoolStateError(f"session {s} was flushed (item {i}); reset it before the next utterance")
-            N2 = self.received[s] + c
-            if N2 > MAX_SAMPLES:
-                raise ValueError(f"item {i} takes session {s} past 2^40 samples in one utterance")
-            out.append(max(self.emitted[s], self._emitted(N2, flush)) - self.emitted[s])
-        return out
-
-    def apply(self, items, plan) -> None:
-        """Move the items' counters as a step that emitted ``plan`` does."""
-        for (s, c, flush), k in zip(self._items(items), plan):
-            self.received[s] += c
-            self.emitted[s] += int(k)
-            if flush:
-                self.flushed[s] = True
-
-    def step(self, items) -> list:
-        k = self.plan(items)
-        self.apply(items, k)
-        return k
-
-    def reset(self, session: int) -> None:
-        if not 0 <= session < self.S:
-            raise ValueError(f"no session {session}")
-        self.received[session] = self.emitted[session] = 0
-        self.flushed[session] = False
-
-
-class YinPoolCounters(_F0PoolCounters):
+class YinPoolCounters(SamplePoolCounters):
     """The tracker pool's rule: ``N' = N + samples``, ``E' = N' // hop`` with flush, else ``max(E, frames_ready(N'))``."""
 
     def __init__(self, frame_length: int, hop_length: int, sessions: int, max_chunk: int):
@@ -492,113 +428,29 @@ class YinPoolCounters(_F0PoolCounters):
         # a push of max_chunk samples that also flushes, from E = frames_ready(N); periodic in N from hop // 2 + W // 2 on (fv_yinpool_max_frames)
         self.max_frames = max((N + self.max_chunk) // hop - frames_ready(N, W, hop) for N in range(hop // 2 + W // 2 + 2 * hop))
 
-    def _emitted(self, N2: int, flush: bool) -> int:
-        return N2 // self.hop_length if flush else frames_ready(N2, self.frame_length, self.hop_length)
+    def _emission(self, i: int, s: int, c: int, flush: bool, N2: int, E: int) -> int:
+        return max(E, N2 // self.hop_length if flush else frames_ready(N2, self.frame_length, self.hop_length))
 
     def pending(self, session: int) -> int:
         N, E, W, hop = self.received[session], self.emitted[session], self.frame_length, self.hop_length
         return max(0, N - max(0, E * hop + hop // 2 - W // 2))
 
 
-class OscPoolCounters(_F0PoolCounters):
+class OscPoolCounters(SamplePoolCounters):
     """The oscillator pool's rule, counted in F0 frames: ``Tn' = Tn + frames``, ``E' = Tn'`` with flush, else ``max(E, Tn' - 1)``."""
 
     def __init__(self, sessions: int, max_chunk_frames: int):
         super().__init__(sessions, max_chunk_frames)
         self.max_frames = self.max_chunk + 1      # a push of max_chunk frames that also flushes while one frame waits
 
-    def _emitted(self, T2: int, flush: bool) -> int:
-        return T2 if flush else T2 - 1
+    def _emission(self, i: int, s: int, c: int, flush: bool, T2: int, E: int) -> int:
+        return max(E, T2 if flush else T2 - 1)
 
     def pending(self, session: int) -> int:
         return self.received[session] - self.emitted[session]
 
 
-class _F0Pool(_Handle):
-    """What the two pools share: the handle on one device, the library's counters, the padded chunk buffer of ``step`` and its check."""
-    _prefix = ""
-
-    def __init__(self, parent, sessions: int, max_chunk: int, counters: _F0PoolCounters, device=None):
-        self._parent, self._lib = parent, _lib.lib()
-        self.sessions, self.max_chunk, self.counters = int(sessions), int(max_chunk), counters
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(getattr(self._lib, self._prefix + "_create")(parent._handle(self.device), self.sessions, self.max_chunk, ctypes.byref(self._h)))
-        self.max_frames = int(getattr(self._lib, self._prefix + "_max_frames")(self._h))
-
-    # -- counters (the library's own; host-side: reading them never synchronises) --
-    def received(self, session: int) -> int:
-        self._check_open()
-        return int(getattr(self._lib, self._prefix + "_received")(self._h, int(session)))
-
-    def emitted(self, session: int) -> int:
-        self._check_open()
-        return int(getattr(self._lib, self._prefix + "_emitted")(self._h, int(session)))
-
-    def pending(self, session: int) -> int:
-        self._check_open()
-        return int(getattr(self._lib, self._prefix + "_pending")(self._h, int(session)))
-
-    def _gather(self, items, what: str):
-        """``(session, 1-D tensor or None, end)`` tuples -> the integer items and the padded ``(count, longest)`` buffer (None: no samples)."""
-        self._check_open()
-        meta, rows = [], []
-        for it in map(tuple, items):
-            s, x, end = it[0], it[1], it[2] if len(it) > 2 else False
-            if x is not None:
-                _require_cuda(x, what)
-                if x.dim() != 1:
-                    raise ValueError(f"expected a 1-D chunk, got {tuple(x.shape)}")
-            rows.append(x)
-            meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(end)))
-        longest = max((c for _, c, _ in meta), default=0)
-        chunks = None
-        if longest:
-            chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=self.device)
-            for i, x in enumerate(rows):
-                if x is not None and x.shape[0]:
-                    chunks[i, :x.shape[0]] = x
-        return meta, chunks
-
-    def _padded(self, items, chunks, what: str):
-        """The checks of ``step_padded``'s inputs -> (items, the C item array, the chunk pointer, the chunk row stride)."""
-        self._check_open()
-        items = [(int(s), int(c), bool(f)) for s, c, f in items]
-        count, stride = len(items), 0
-        if chunks is not None:
-            _require_cuda(chunks, what)
-            if chunks.dim() != 2 or chunks.shape[0] < count or (chunks.shape[1] > 1 and chunks.stride(1) != 1):
-                raise ValueError(f"expected chunks of shape ({count}, chunk_stride) with contiguous rows, got {tuple(chunks.shape)}")
-            stride = int(chunks.stride(0)) if chunks.shape[0] > 1 else int(chunks.shape[1])
-            if stride < chunks.shape[1]:
-                raise ValueError("the rows of chunks overlap")
-        arr = (_lib.WavPoolItem * max(count, 1))(*[_lib.WavPoolItem(s, c, int(f)) for s, c, f in items])
-        return items, arr, chunks.data_ptr() if chunks is not None and chunks.numel() else None, stride
-
-    def _out(self, out, lead: tuple, count: int, cols: int, what: str) -> torch.Tensor:
-        if out is None:
-            return torch.empty(lead + (count, cols), dtype=torch.float32, device=self.device)
-        _require_cuda(out, what)
-        if out.dim() != len(lead) + 2 or tuple(out.shape[:-1]) != lead + (count,) or not out.is_contiguous():
-            raise ValueError(f"expected a contiguous out of shape {lead + (count, 'out_cols')}, got {tuple(out.shape)}")
-        return out
-
-    def _moved(self, items, plan, got, count: int, what: str) -> list:
-        emit = [int(got[i]) for i in range(count)]
-        self.counters.apply(items, plan)                          # the Python counters move as the library's did
-        if plan != emit:
-            raise RuntimeError(f"the {what} pool emitted {emit} frames where the emission rule says {plan}")
-        return emit
-
-    def reset(self, session: int) -> None:
-        """Start the next utterance in one slot: its counters go to 0; its carry is kept."""
-        self._check_open()
-        check(getattr(self._lib, self._prefix + "_reset")(self._h, int(session)))
-        self.counters.reset(int(session))
-
-
-class YinF0Pool(_F0Pool):
+class YinF0Pool(_SamplePoolHandle):
     """Tracker sessions that advance independently (``fv_yinpool``, include/fishvoc.h): what ``YinF0Stream`` is to rows in lockstep, for
     ``sessions`` slots with their own counters.  ``step(items)`` takes ``(session, samples, end)`` tuples — ``samples``: a 1-D tensor of at
     most ``max_chunk_samples`` samples, or ``None`` for none; ``end``: the utterance ends with them — and returns one ``(f0 (k,),
@@ -607,16 +459,17 @@ class YinF0Pool(_F0Pool):
     is checked before anything moves: a refused step leaves every session as it was.  A session's concatenated values have the bits of
     ``YinF0.forward`` on its whole utterance.  One step is one tracker launch and one carry launch per 32 items; work is enqueued on
     torch's current stream, and calls must be ordered."""
-    _destroy, _prefix = "fv_yinpool_destroy", "fv_yinpool"
+    _destroy, _prefix, _bound, _noun = "fv_yinpool_destroy", "fv_yinpool", "max_frames", "chunk"
     _closed = "this F0 pool is closed: create a new one"
+    _mismatch = "the F0 pool emitted {emit} frames where the emission rule says {plan}"
 
     def __init__(self, yin: YinF0, sessions: int, max_chunk_samples: int, device=None):
-        super().__init__(yin, sessions, max_chunk_samples, YinPoolCounters(yin.frame_length, yin.hop_length, sessions, max_chunk_samples), device)
+        self.counters = YinPoolCounters(yin.frame_length, yin.hop_length, sessions, max_chunk_samples)
+        super().__init__(yin, sessions, max_chunk_samples, device)
         self.frame_length, self.hop_length = yin.frame_length, yin.hop_length
 
     def step(self, items) -> list:
-        meta, chunks = self._gather(items, "YinF0Pool.step")
-        f0, ap, emit = self.step_padded(meta, chunks)
+        f0, ap, emit = self.step_padded(*self._gather(items))
         return [(f0[i, :k], ap[i, :k]) for i, k in enumerate(emit)]
 
     def step_padded(self, items, chunks: torch.Tensor | None, out: torch.Tensor | None = None, aperiodicity: bool = True) -> tuple:
@@ -625,38 +478,34 @@ class YinF0Pool(_F0Pool):
         when no item has samples; ``out``: ``(2, count, out_cols)`` — ``(1, count, out_cols)`` with ``aperiodicity=False``, which is then
         not stored — sized from the Python plan when not given.  Returns ``(f0 (count, out_cols), aperiodicity or None, frames per item)``:
         row i holds item i's frames first and zeros after them."""
-        items, arr, cptr, stride = self._padded(items, chunks, "YinF0Pool.step_padded")
-        count = len(items)
+        items, arr, got, cptr, stride = self._padded(items, chunks)
+        count, lead = len(items), 2 if aperiodicity else 1
         plan = self.counters.plan(items)                          # sizes the output before anything is launched; refuses what the library would
-        out = self._out(out, (2 if aperiodicity else 1,), count, max(plan, default=0), "YinF0Pool.step_padded")
+        out = self._out(out, (lead, count), max(plan, default=0), f"{(lead, count, 'out_cols')}")
         cols = int(out.shape[2])
-        got = (ctypes.c_int64 * max(count, 1))()
-        with torch.cuda.device(self.device):
-            run = torch.cuda.current_stream()
-            check(self._lib.fv_yinpool_step(self._h, arr, count, cptr, stride, out[0].data_ptr() if out[0].numel() else None,
-                                            out[1].data_ptr() if aperiodicity and out[1].numel() else None, max(cols, 1), cols, got,
-                                            int(run.cuda_stream)))
-            self._record_done(run)          # the carried buffers are in use on the device until then
-        emit = self._moved(items, plan, got, count, "F0")
-        return out[0], (out[1] if aperiodicity else None), emit
+        self._run(lambda stream: self._lib.fv_yinpool_step(self._h, arr, count, cptr, stride, out[0].data_ptr() if out[0].numel() else None,
+                                                           out[1].data_ptr() if aperiodicity and out[1].numel() else None, max(cols, 1),
+                                                           cols, got, stream))
+        return out[0], (out[1] if aperiodicity else None), self._moved(items, plan, got)
 
 
-class PitchTemplatePool(_F0Pool):
+class PitchTemplatePool(_SamplePoolHandle):
     """Oscillator sessions that advance independently (``fv_oscpool``): what ``PitchTemplateStream`` is to rows in lockstep.  ``step(items)``
     takes ``(session, f0, end)`` tuples — ``f0``: a 1-D tensor of at most ``max_chunk_frames`` F0 frames in Hz, or ``None`` — and returns one
     ``(1, k hop)`` tensor per item: the samples of the frames whose next frame has arrived, or with ``end`` of all that remain.  Sessions,
     refusals and ordering as ``YinF0Pool``.  A session's concatenated samples have the bits of ``PitchTemplate.forward`` on its whole track:
     the phase carried per slot is a wrapping integer.  One step is three launches and one carry launch per 32 items."""
-    _destroy, _prefix = "fv_oscpool_destroy", "fv_oscpool"
+    _destroy, _prefix, _bound, _noun = "fv_oscpool_destroy", "fv_oscpool", "max_frames", "chunk"
     _closed = "this pitch template pool is closed: create a new one"
+    _mismatch = "the pitch template pool emitted {emit} frames where the emission rule says {plan}"
 
     def __init__(self, template: PitchTemplate, sessions: int, max_chunk_frames: int, device=None):
-        super().__init__(template, sessions, max_chunk_frames, OscPoolCounters(sessions, max_chunk_frames), device)
+        self.counters = OscPoolCounters(sessions, max_chunk_frames)
+        super().__init__(template, sessions, max_chunk_frames, device)
         self.hop_length = template.hop_length
 
     def step(self, items) -> list:
-        meta, chunks = self._gather(items, "PitchTemplatePool.step")
-        out, emit = self.step_padded(meta, chunks)
+        out, emit = self.step_padded(*self._gather(items))
         return [out[i:i + 1, :k * self.hop_length] for i, k in enumerate(emit)]
 
     def step_padded(self, items, chunks: torch.Tensor | None, out: torch.Tensor | None = None) -> tuple:
@@ -664,18 +513,14 @@ class PitchTemplatePool(_F0Pool):
         ``chunks``: ``(rows >= count, chunk_stride)`` F0 in Hz with item i's frames first in row i (the rest is never read) — a
         ``YinF0Pool.step_padded``'s f0 buffer serves as it is; ``out``: ``(count, out_cols)`` samples, sized from the Python plan when not
         given.  Returns ``(out, frames per item)``: row i holds the ``k hop`` samples of item i first and zeros after them."""
-        items, arr, cptr, stride = self._padded(items, chunks, "PitchTemplatePool.step_padded")
+        items, arr, got, cptr, stride = self._padded(items, chunks)
         count = len(items)
         plan = self.counters.plan(items)
-        out = self._out(out, (), count, max(plan, default=0) * self.hop_length, "PitchTemplatePool.step_padded")
+        out = self._out(out, (count,), max(plan, default=0) * self.hop_length, f"{(count, 'out_cols')}")
         cols = int(out.shape[1])
-        got = (ctypes.c_int64 * max(count, 1))()
-        with torch.cuda.device(self.device):
-            run = torch.cuda.current_stream()
-            check(self._lib.fv_oscpool_step(self._h, arr, count, cptr, stride, out.data_ptr() if out.numel() else None, max(cols, 1), cols, got,
-                                            int(run.cuda_stream)))
-            self._record_done(run)
-        return out, self._moved(items, plan, got, count, "pitch template")
+        self._run(lambda stream: self._lib.fv_oscpool_step(self._h, arr, count, cptr, stride, out.data_ptr() if out.numel() else None,
+                                                           max(cols, 1), cols, got, stream))
+        return out, self._moved(items, plan, got)
 
 
 class TemplatePoolCounters:
@@ -686,15 +531,15 @@ class TemplatePoolCounters:
         self.tracker, self.template = tracker, template
 
     def plan(self, items) -> tuple:
-        items = _F0PoolCounters._items(items)
+        items = SamplePoolCounters._items(items)
         frames = self.tracker.plan(items)
         return frames, self.template.plan([(s, k, end) for (s, _, end), k in zip(items, frames)])
 
     def step(self, items) -> tuple:
-        items = _F0PoolCounters._items(items)
+        items = SamplePoolCounters._items(items)
         frames, emit = self.plan(items)
-        self.tracker.apply(items, frames)
-        self.template.apply([(s, k, end) for (s, _, end), k in zip(items, frames)], emit)
+        self.tracker.commit(items, frames)
+        self.template.commit([(s, k, end) for (s, _, end), k in zip(items, frames)], emit)
         return frames, emit
 
     def reset(self, session: int) -> None:
@@ -738,8 +583,8 @@ class TemplatePool:
         return self.tracker.received(session) // self.hop_length - self.template.emitted(session)
 
     def step(self, items) -> list:
-        meta, chunks = self.tracker._gather(items, "TemplatePool.step")
-        out, emit = self.step_padded(meta, chunks)
+        self.tracker._check_open()
+        out, emit = self.step_padded(*_gather(items, self.device, _require_cuda, "TemplatePool.step", "chunk"))
         return [out[i:i + 1, :k * self.hop_length] for i, k in enumerate(emit)]
 
     def step_padded(self, items, chunks: torch.Tensor | None, out: torch.Tensor | None = None) -> tuple:
@@ -747,7 +592,7 @@ class TemplatePool:
         samples.  Returns ``(out, template frames per item)``."""
         self.tracker._check_open()
         self.template._check_open()
-        items = _F0PoolCounters._items(items)
+        items = SamplePoolCounters._items(items)
         self.counters.plan(items)                                 # both plans before anything moves
         f0, _, frames = self.tracker.step_padded(items, chunks, aperiodicity=False)
         return self.template.step_padded([(s, k, end) for (s, _, end), k in zip(items, frames)], f0 if f0.shape[1] else None, out)

@@ -16,11 +16,8 @@
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Sequence
 
-from .sessions import PoolStateError
-
-MAX_SAMPLES = 1 << 40      # the longest utterance of a sample stream or pool (kSampleStreamMaxLen)
+from .sample_pool import MAX_SAMPLES, SamplePoolCounters  # noqa: F401
 
 
 @dataclass(frozen=True)
@@ -86,65 +83,21 @@ class Counters:
         self.flushed = False
 
 
-class PoolCounters:
-    """The host counters of a wav pool: ``received[s]`` samples, ``emitted[s]`` frames and ``flushed[s]`` per slot.  ``plan(items)`` says what a
-    step would emit per item and changes nothing; it refuses what ``fv_wavpool_step`` refuses of the items — ``ValueError`` for a session out
-    of range, a duplicate session, samples outside ``[0, max_chunk]``, more than 2^40 samples and a flush that ends an utterance too short for
-    the reflect padding or for one frame; ``PoolStateError`` for a flushed slot — checking the whole step before ``apply`` moves anything."""
+class PoolCounters(SamplePoolCounters):
+    """The host counters of a wav pool (``SamplePoolCounters``) with the framing rule: ``E' = max(E, frames(N') if flush else
+    frames_ready(N'))``.  Beyond the shared refusals, ``ValueError`` for a flush that ends an utterance too short for the reflect padding or
+    for one frame."""
 
     def __init__(self, framing: Framing, sessions: int, max_chunk: int):
-        self.framing, self.S, self.max_chunk = framing, int(sessions), int(max_chunk)
-        if not 1 <= self.S <= 65535 or not 1 <= self.max_chunk <= 1 << 28:
-            raise ValueError(f"sessions ({self.S}) must lie in [1, 65535] and max_chunk ({self.max_chunk}) in [1, 2^28]")
-        self.received = [0] * self.S
-        self.emitted = [0] * self.S
-        self.flushed = [False] * self.S
+        super().__init__(sessions, max_chunk)
+        self.framing = framing
 
-    @staticmethod
-    def _items(items: Sequence) -> list:
-        return [(int(it[0]), int(it[1]), bool(it[2]) if len(it) > 2 else False) for it in items]
-
-    def plan(self, items: Sequence) -> list:
-        """Frames every item of the step emits, in item order."""
-        fr, seen, ends = self.framing, set(), []
-        items = self._items(items)
-        for i, (s, c, flush) in enumerate(items):
-            if not 0 <= s < self.S:
-                raise ValueError(f"item {i} names session {s}, outside [0, {self.S})")
-            if s in seen:
-                raise ValueError(f"duplicate session {s} (item {i}): a session appears at most once per step")
-            seen.add(s)
-            if not 0 <= c <= self.max_chunk:
-                raise ValueError(f"item {i} (session {s}) has {c} samples, outside [0, max_chunk = {self.max_chunk}]")
-            if self.flushed[s]:
-                raise PoolStateError(f"session {s} was flushed (item {i}); reset it before the next utterance")
-            if self.received[s] + c > MAX_SAMPLES:
-                raise ValueError(f"item {i} takes session {s} past 2^40 samples in one utterance")
-            ends.append(self.received[s] + c)
-        for i, ((s, _, flush), N2) in enumerate(zip(items, ends)):
-            if flush and N2 > 0 and fr.too_short(N2):
-                raise ValueError(f"session {s} (item {i}) ends after {N2} samples: too short for reflect padding {fr.pad_l}/{fr.pad_r} and one "
-                                 f"{fr.n_fft}-sample frame")
-        return [max(self.emitted[s], fr.frames(N2) if flush else fr.frames_ready(N2)) - self.emitted[s] for (s, _, flush), N2 in zip(items, ends)]
-
-    def apply(self, items: Sequence, plan: Sequence[int]) -> None:
-        """Move the items' counters as a step that emitted ``plan`` does."""
-        for (s, c, flush), k in zip(self._items(items), plan):
-            self.received[s] += c
-            self.emitted[s] += int(k)
-            if flush:
-                self.flushed[s] = True
-
-    def step(self, items: Sequence) -> list:
-        k = self.plan(items)
-        self.apply(items, k)
-        return k
+    def _emission(self, i: int, s: int, c: int, flush: bool, N2: int, E: int) -> int:
+        fr = self.framing
+        if flush and N2 > 0 and fr.too_short(N2):
+            raise ValueError(f"session {s} (item {i}) ends after {N2} samples: too short for reflect padding {fr.pad_l}/{fr.pad_r} and one "
+                             f"{fr.n_fft}-sample frame")
+        return max(E, fr.frames(N2) if flush else fr.frames_ready(N2))
 
     def pending_samples(self, session: int) -> int:
         return self.framing.pending_samples(self.received[session], self.emitted[session])
-
-    def reset(self, session: int) -> None:
-        if not 0 <= session < self.S:
-            raise ValueError(f"no session {session}")
-        self.received[session] = self.emitted[session] = 0
-        self.flushed[session] = False

@@ -34,11 +34,10 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._handle import _DeviceHandles, _Handle, _emit
+from ._handle import _DeviceHandles, _Handle, _SamplePoolHandle, _emit
 from ._lib import check
-from .framing import MAX_SAMPLES
 from .resample import KAISER_BETA, _require_cuda, _rows, design
-from .sessions import PoolStateError
+from .sample_pool import SamplePoolCounters
 
 MAX_UTTERANCE = 1 << 30                      # samples per utterance of a stream or a pool slot (the library's limit)
 
@@ -253,21 +252,14 @@ class PitchShiftStream(_Handle):
         self._flushed = False
 
 
-class PvPoolCounters:
-    """The host counters of a pitch-shift pool: ``received[s]``, ``emitted[s]`` and ``flushed[s]`` per slot, and the plan of
-    ``fv_pvpool_plan`` in plain Python over ``PitchShift.stream_emitted``.  ``plan(items)`` — items ``(session, samples, flush)`` — says what a
-    step would emit per item and changes nothing; it refuses what ``fv_pvpool_step`` refuses of the items, in the library's order per item:
-    ``ValueError`` for a session out of range, a duplicate session and samples outside ``[0, max_chunk]``, ``PoolStateError`` for a flushed
-    slot, ``ValueError`` past 2^40 samples; then ``ValueError`` past 2^30 samples in one utterance.  ``commit`` moves the counters as a step
-    that emitted the plan does."""
+class PvPoolCounters(SamplePoolCounters):
+    """The host counters of a pitch-shift pool (``SamplePoolCounters``) and the plan of ``fv_pvpool_plan`` in plain Python over
+    ``PitchShift.stream_emitted``: ``E' = N'`` with the flush, else ``max(E, E(N'))``; the identity shift emits the item's own samples.  Beyond
+    the shared refusals, ``ValueError`` past 2^30 samples in one utterance."""
 
     def __init__(self, shift: PitchShift, sessions: int, max_chunk: int):
-        self.shift, self.S, self.max_chunk = shift, int(sessions), int(max_chunk)
-        if not 1 <= self.S <= 65535 or not 1 <= self.max_chunk <= 1 << 28:
-            raise ValueError(f"sessions ({self.S}) must lie in [1, 65535] and max_chunk ({self.max_chunk}) in [1, 2^28]")
-        self.received = [0] * self.S
-        self.emitted = [0] * self.S
-        self.flushed = [False] * self.S
+        super().__init__(sessions, max_chunk)
+        self.shift = shift
         self.max_outputs = self._max_outputs()
 
     def _max_outputs(self) -> int:
@@ -283,61 +275,18 @@ class PvPoolCounters:
             a0 += n
         return self.max_chunk + max(N - sh.stream_emitted(N) for N in (F // 2 + a * h - 1 for a in range(a0, a0 + n)))
 
-    @staticmethod
-    def _items(items) -> list:
-        return [(int(it[0]), int(it[1]), bool(it[2]) if len(it) > 2 else False) for it in items]
-
-    def plan(self, items) -> list:
-        """Outputs every item of the step emits, in item order."""
-        seen, moves = set(), []
-        for i, (s, c, flush) in enumerate(self._items(items)):
-            if not 0 <= s < self.S:
-                raise ValueError(f"item {i} names session {s}, outside [0, {self.S})")
-            if s in seen:
-                raise ValueError(f"duplicate session {s} (item {i}): a session appears at most once per step")
-            seen.add(s)
-            if not 0 <= c <= self.max_chunk:
-                raise ValueError(f"item {i} (session {s}) has {c} samples, outside [0, max_chunk = {self.max_chunk}]")
-            if self.flushed[s]:
-                raise PoolStateError(f"session {s} was flushed (item {i}); reset it before the next utterance")
-            if self.received[s] + c > MAX_SAMPLES:
-                raise ValueError(f"item {i} takes session {s} past 2^40 samples in one utterance")
-            moves.append((i, s, c, flush))
-        out = []
-        for i, s, c, flush in moves:
-            N2 = self.received[s] + c
-            if N2 > MAX_UTTERANCE:
-                raise ValueError(f"item {i} takes session {s} past 2^30 samples in one utterance")
-            if self.shift.orig_freq == self.shift.sample_rate:
-                out.append(c)
-            else:
-                out.append((N2 if flush else max(self.emitted[s], self.shift.stream_emitted(N2))) - self.emitted[s])
-        return out
-
-    def commit(self, items, plan) -> None:
-        """Move the items' counters as a step that emitted ``plan`` does."""
-        for (s, c, flush), k in zip(self._items(items), plan):
-            self.received[s] += c
-            self.emitted[s] += int(k)
-            if flush:
-                self.flushed[s] = True
-
-    def step(self, items) -> list:
-        k = self.plan(items)
-        self.commit(items, k)
-        return k
+    def _emission(self, i: int, s: int, c: int, flush: bool, N2: int, E: int) -> int:
+        if N2 > MAX_UTTERANCE:
+            raise ValueError(f"item {i} takes session {s} past 2^30 samples in one utterance")
+        if self.shift.orig_freq == self.shift.sample_rate:
+            return E + c
+        return N2 if flush else max(E, self.shift.stream_emitted(N2))
 
     def pending(self, session: int) -> int:
         return self.received[session] - self.emitted[session]
 
-    def reset(self, session: int) -> None:
-        if not 0 <= session < self.S:
-            raise ValueError(f"no session {session}")
-        self.received[session] = self.emitted[session] = 0
-        self.flushed[session] = False
 
-
-class PitchShiftPool(_Handle):
+class PitchShiftPool(_SamplePoolHandle):
     """Pitch-shift sessions that advance independently (``fv_pvpool``, include/fishvoc.h): what ``PitchShiftStream`` is to rows in lockstep,
     for ``sessions`` slots with their own counters, all with the shifter's one ``n_steps``.  ``step(items)`` takes ``(session, samples, end)``
     tuples — ``samples``: a 1-D tensor of at most ``max_chunk`` samples, or ``None`` for none; ``end``: the utterance ends with them — and
@@ -346,55 +295,20 @@ class PitchShiftPool(_Handle):
     ``reset(session)``.  The whole step is checked before anything moves: a refused step leaves every session as it was.  With
     ``batch_invariant=True`` on the shifter a session's concatenated outputs are bit-identical to ``PitchShift.forward`` of its whole
     utterance.  Work is enqueued on torch's current stream, and calls must be ordered."""
-    _destroy = "fv_pvpool_destroy"
+    _destroy, _prefix = "fv_pvpool_destroy", "fv_pvpool"
     _closed = "this pitch-shift pool is closed: create a new one"
+    _mismatch = "the pitch-shift pool emitted {emit} outputs where the emission rule says {plan}"
 
     def __init__(self, shift: PitchShift, sessions: int, max_chunk: int, device=None):
-        self._shift, self._lib = shift, _lib.lib()
-        self.sessions, self.max_chunk = int(sessions), int(max_chunk)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = ctypes.c_void_p()
+        super().__init__(shift, sessions, max_chunk, device)
         with torch.cuda.device(self.device):
-            check(self._lib.fv_pvpool_create(shift._handle(self.device), self.sessions, self.max_chunk, ctypes.byref(self._h)))
             self._need = int(self._lib.fv_pvpool_workspace_bytes(self._h))
             self._ws = torch.empty(max(self._need, 1), dtype=torch.uint8, device=self.device)
-        self.max_outputs = int(self._lib.fv_pvpool_max_outputs(self._h))
         self.counters = PvPoolCounters(shift, self.sessions, self.max_chunk)
-
-    # -- counters (the library's own; host-side: reading them never synchronises) --
-    def received(self, session: int) -> int:
-        self._check_open()
-        return int(self._lib.fv_pvpool_received(self._h, int(session)))
-
-    def emitted(self, session: int) -> int:
-        self._check_open()
-        return int(self._lib.fv_pvpool_emitted(self._h, int(session)))
-
-    def pending(self, session: int) -> int:
-        """``N - E`` of one session: what its flush would emit now."""
-        self._check_open()
-        return int(self._lib.fv_pvpool_pending(self._h, int(session)))
 
     def step(self, items) -> list:
         """One step for ``items`` (see the class); returns each item's outputs, views of one output buffer."""
-        self._check_open()
-        meta, rows = [], []
-        for it in map(tuple, items):
-            s, x, end = it[0], it[1], it[2] if len(it) > 2 else False
-            if x is not None:
-                _require_cuda(x, "PitchShiftPool.step")
-                if x.dim() != 1:
-                    raise ValueError(f"expected a 1-D chunk of samples, got {tuple(x.shape)}")
-            rows.append(x)
-            meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(end)))
-        longest = max((c for _, c, _ in meta), default=0)
-        chunks = None
-        if longest:
-            chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=self.device)
-            for i, x in enumerate(rows):
-                if x is not None and x.shape[0]:
-                    chunks[i, :x.shape[0]] = x
-        out, emit = self.step_padded(meta, chunks)
+        out, emit = self.step_padded(*self._gather(items))
         return [out[i, :k] for i, k in enumerate(emit)]
 
     def step_padded(self, items, chunks: torch.Tensor | None, out: torch.Tensor | None = None, workspace_bytes: int | None = None) -> tuple:
@@ -402,41 +316,12 @@ class PitchShiftPool(_Handle):
         ``chunks``: ``(rows >= count, chunk_stride)`` with item i's samples first in row i (the rest, NaN included, is never read), ``None``
         when no item has samples; ``out``: ``(count, out_cols)``, sized from the Python plan when not given.  Returns ``(out, outputs per
         item)``: row i holds item i's outputs first and zeros after them."""
-        self._check_open()
-        items = [(int(s), int(c), bool(f)) for s, c, f in items]
+        items, arr, got, cptr, stride = self._padded(items, chunks)
         count = len(items)
-        stride = 0
-        if chunks is not None:
-            _require_cuda(chunks, "PitchShiftPool.step_padded")
-            if chunks.dim() != 2 or chunks.shape[0] < count or (chunks.shape[1] > 1 and chunks.stride(1) != 1):
-                raise ValueError(f"expected chunks of shape ({count}, chunk_stride) with contiguous rows, got {tuple(chunks.shape)}")
-            stride = int(chunks.stride(0)) if chunks.shape[0] > 1 else int(chunks.shape[1])
-            if stride < chunks.shape[1]:
-                raise ValueError("the rows of chunks overlap")
         plan = self.counters.plan(items)                          # sizes the output before anything is launched; refuses what the library would
-        if out is None:
-            out = torch.empty((count, max(plan, default=0)), dtype=torch.float32, device=self.device)
-        elif out.dim() != 2 or out.shape[0] != count or not out.is_contiguous():
-            raise ValueError(f"expected a contiguous out of shape ({count}, out_cols), got {tuple(out.shape)}")
-        _require_cuda(out, "PitchShiftPool.step_padded")
-        arr = (_lib.WavPoolItem * max(count, 1))(*[_lib.WavPoolItem(s, c, int(f)) for s, c, f in items])
-        got = (ctypes.c_int64 * max(count, 1))()
+        out = self._out(out, (count,), max(plan, default=0), f"({count}, out_cols)")
         cols = int(out.shape[1])
         need = self._need if workspace_bytes is None else int(workspace_bytes)
-        with torch.cuda.device(self.device):
-            run = torch.cuda.current_stream()
-            check(self._lib.fv_pvpool_step(self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None, stride,
-                                           out.data_ptr() if out.numel() else None, max(cols, 1), cols, got, self._ws.data_ptr(), need,
-                                           int(run.cuda_stream)))
-            self._record_done(run)          # the carries and the workspace are in use on the device until then
-        emit = [int(got[i]) for i in range(count)]
-        self.counters.commit(items, plan)                         # the Python counters move as the library's did
-        if plan != emit:
-            raise RuntimeError(f"the pitch-shift pool emitted {emit} outputs where the emission rule says {plan}")
-        return out, emit
-
-    def reset(self, session: int) -> None:
-        """Start the next utterance in one slot: N = E = 0; its carries are kept."""
-        self._check_open()
-        check(self._lib.fv_pvpool_reset(self._h, int(session)))
-        self.counters.reset(int(session))
+        self._run(lambda stream: self._lib.fv_pvpool_step(self._h, arr, count, cptr, stride, out.data_ptr() if out.numel() else None,
+                                                          max(cols, 1), cols, got, self._ws.data_ptr(), need, stream))
+        return out, self._moved(items, plan, got)

@@ -35,10 +35,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._handle import _DeviceHandles, _Handle, _emit, _require_cuda as _require
+from ._handle import _DeviceHandles, _Handle, _SamplePoolHandle, _emit, _require_value as _require_cuda
 from ._lib import check
-from .framing import MAX_SAMPLES
-from .sessions import PoolStateError
+from .sample_pool import SamplePoolCounters
 
 KAISER_BETA = 14.769656459379492
 
@@ -167,10 +166,6 @@ def _config(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_metho
     method = resampling_method if isinstance(resampling_method, int) else _lib.RESAMPLE_METHODS.get(resampling_method, -1)
     return _lib.ResampleConfig(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), int(method),
                                0.0 if beta is None else float(beta))
-
-
-def _require_cuda(t: torch.Tensor, what: str) -> None:
-    _require(t, what, ValueError, ValueError)
 
 
 def _rows(x: torch.Tensor) -> torch.Tensor:
@@ -335,70 +330,23 @@ class ResampleStream(_Handle):
         self._flushed = False
 
 
-class ResamplePoolCounters:
-    """The host counters of a resample pool: ``received[s]`` input samples, ``emitted[s]`` outputs and ``flushed[s]`` per slot, and the plan
-    of ``fv_respool_plan`` in plain Python over ``Design.emit_count`` / ``output_length``.  ``plan(items)`` — items ``(session, samples,
-    flush)`` — says what a step would emit per item and changes nothing; it refuses what ``fv_respool_step`` refuses of the items, in the
-    library's order per item: ``ValueError`` for a session out of range, a duplicate session and samples outside ``[0, max_chunk]``,
-    ``PoolStateError`` for a flushed slot, ``ValueError`` past 2^40 samples.  ``commit`` moves the counters as a step that emitted the plan
-    does."""
+class ResamplePoolCounters(SamplePoolCounters):
+    """The host counters of a resample pool (``SamplePoolCounters``) and the plan of ``fv_respool_plan`` in plain Python over
+    ``Design.emit_count`` / ``output_length``: ``E' = max(E, output_length(N') if flush else emit_count(N'))``."""
 
     def __init__(self, design: Design, sessions: int, max_chunk: int):
-        self.design, self.S, self.max_chunk = design, int(sessions), int(max_chunk)
-        if not 1 <= self.S <= 65535 or not 1 <= self.max_chunk <= 1 << 28:
-            raise ValueError(f"sessions ({self.S}) must lie in [1, 65535] and max_chunk ({self.max_chunk}) in [1, 2^28]")
-        self.received = [0] * self.S
-        self.emitted = [0] * self.S
-        self.flushed = [False] * self.S
+        super().__init__(sessions, max_chunk)
+        self.design = design
         self.max_outputs = design.max_step_outputs(self.max_chunk)
 
-    @staticmethod
-    def _items(items) -> list:
-        return [(int(it[0]), int(it[1]), bool(it[2]) if len(it) > 2 else False) for it in items]
-
-    def plan(self, items) -> list:
-        """Outputs every item of the step emits, in item order."""
-        d, seen, out = self.design, set(), []
-        for i, (s, c, flush) in enumerate(self._items(items)):
-            if not 0 <= s < self.S:
-                raise ValueError(f"item {i} names session {s}, outside [0, {self.S})")
-            if s in seen:
-                raise ValueError(f"duplicate session {s} (item {i}): a session appears at most once per step")
-            seen.add(s)
-            if not 0 <= c <= self.max_chunk:
-                raise ValueError(f"item {i} (session {s}) has {c} samples, outside [0, max_chunk = {self.max_chunk}]")
-            if self.flushed[s]:
-                raise PoolStateError(f"session {s} was flushed (item {i}); reset it before the next utterance")
-            N2 = self.received[s] + c
-            if N2 > MAX_SAMPLES:
-                raise ValueError(f"item {i} takes session {s} past 2^40 samples in one utterance")
-            out.append(max(self.emitted[s], d.output_length(N2) if flush else d.emit_count(N2)) - self.emitted[s])
-        return out
-
-    def commit(self, items, plan) -> None:
-        """Move the items' counters as a step that emitted ``plan`` does."""
-        for (s, c, flush), k in zip(self._items(items), plan):
-            self.received[s] += c
-            self.emitted[s] += int(k)
-            if flush:
-                self.flushed[s] = True
-
-    def step(self, items) -> list:
-        k = self.plan(items)
-        self.commit(items, k)
-        return k
+    def _emission(self, i: int, s: int, c: int, flush: bool, N2: int, E: int) -> int:
+        return max(E, self.design.output_length(N2) if flush else self.design.emit_count(N2))
 
     def pending(self, session: int) -> int:
         return self.design.output_length(self.received[session]) - self.emitted[session]
 
-    def reset(self, session: int) -> None:
-        if not 0 <= session < self.S:
-            raise ValueError(f"no session {session}")
-        self.received[session] = self.emitted[session] = 0
-        self.flushed[session] = False
 
-
-class ResamplePool(_Handle):
+class ResamplePool(_SamplePoolHandle):
     """Resampler sessions that advance independently (``fv_respool``, include/fishvoc.h): what ``ResampleStream`` is to rows in lockstep, for
     ``sessions`` slots with their own counters.  ``step(items)`` takes ``(session, samples, end)`` tuples — ``samples``: a 1-D tensor of at
     most ``max_chunk`` samples, or ``None`` for none; ``end``: the utterance ends with them — and returns one 1-D tensor per item (possibly
@@ -406,54 +354,18 @@ class ResamplePool(_Handle):
     refuses items after its end until ``reset(session)``.  The whole step is checked before anything moves: a refused step leaves every
     session as it was.  A session's concatenated outputs are bit-identical to ``Resample.forward`` of its whole utterance.  One step is one
     FIR launch and one carry launch per 32 items; work is enqueued on torch's current stream, and calls must be ordered."""
-    _destroy = "fv_respool_destroy"
+    _destroy, _prefix = "fv_respool_destroy", "fv_respool"
     _closed = "this resample pool is closed: create a new one"
+    _mismatch = "the resample pool emitted {emit} outputs where the emission rule says {plan}"
 
     def __init__(self, resample: Resample, sessions: int, max_chunk: int, device=None):
-        self._resample, self._lib = resample, _lib.lib()
+        super().__init__(resample, sessions, max_chunk, device)
         self.design = resample.design
-        self.sessions, self.max_chunk = int(sessions), int(max_chunk)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(self._lib.fv_respool_create(resample._handle(self.device), self.sessions, self.max_chunk, ctypes.byref(self._h)))
-        self.max_outputs = int(self._lib.fv_respool_max_outputs(self._h))
         self.counters = ResamplePoolCounters(self.design, self.sessions, self.max_chunk)
-
-    # -- counters (the library's own; host-side: reading them never synchronises) --
-    def received(self, session: int) -> int:
-        self._check_open()
-        return int(self._lib.fv_respool_received(self._h, int(session)))
-
-    def emitted(self, session: int) -> int:
-        self._check_open()
-        return int(self._lib.fv_respool_emitted(self._h, int(session)))
-
-    def pending(self, session: int) -> int:
-        """``ceil(n N / o) - E`` of one session: what its flush would emit now."""
-        self._check_open()
-        return int(self._lib.fv_respool_pending(self._h, int(session)))
 
     def step(self, items) -> list:
         """One step for ``items`` (see the class); returns each item's outputs, views of one output buffer."""
-        self._check_open()
-        meta, rows = [], []
-        for it in map(tuple, items):
-            s, x, end = it[0], it[1], it[2] if len(it) > 2 else False
-            if x is not None:
-                _require_cuda(x, "ResamplePool.step")
-                if x.dim() != 1:
-                    raise ValueError(f"expected a 1-D chunk of samples, got {tuple(x.shape)}")
-            rows.append(x)
-            meta.append((int(s), 0 if x is None else int(x.shape[0]), bool(end)))
-        longest = max((c for _, c, _ in meta), default=0)
-        chunks = None
-        if longest:
-            chunks = torch.zeros((len(meta), longest), dtype=torch.float32, device=self.device)
-            for i, x in enumerate(rows):
-                if x is not None and x.shape[0]:
-                    chunks[i, :x.shape[0]] = x
-        out, emit = self.step_padded(meta, chunks)
+        out, emit = self.step_padded(*self._gather(items))
         return [out[i, :k] for i, k in enumerate(emit)]
 
     def step_padded(self, items, chunks: torch.Tensor | None, out: torch.Tensor | None = None) -> tuple:
@@ -461,39 +373,11 @@ class ResamplePool(_Handle):
         ``chunks``: ``(rows >= count, chunk_stride)`` with item i's samples first in row i (the rest, NaN included, is never read), ``None``
         when no item has samples; ``out``: ``(count, out_cols)``, sized from the Python plan when not given.  Returns ``(out, outputs per
         item)``: row i holds item i's outputs first and zeros after them."""
-        self._check_open()
-        items = [(int(s), int(c), bool(f)) for s, c, f in items]
+        items, arr, got, cptr, stride = self._padded(items, chunks)
         count = len(items)
-        stride = 0
-        if chunks is not None:
-            _require_cuda(chunks, "ResamplePool.step_padded")
-            if chunks.dim() != 2 or chunks.shape[0] < count or (chunks.shape[1] > 1 and chunks.stride(1) != 1):
-                raise ValueError(f"expected chunks of shape ({count}, chunk_stride) with contiguous rows, got {tuple(chunks.shape)}")
-            stride = int(chunks.stride(0)) if chunks.shape[0] > 1 else int(chunks.shape[1])
-            if stride < chunks.shape[1]:
-                raise ValueError("the rows of chunks overlap")
         plan = self.counters.plan(items)                          # sizes the output before anything is launched; refuses what the library would
-        if out is None:
-            out = torch.empty((count, max(plan, default=0)), dtype=torch.float32, device=self.device)
-        elif out.dim() != 2 or out.shape[0] != count or not out.is_contiguous():
-            raise ValueError(f"expected a contiguous out of shape ({count}, out_cols), got {tuple(out.shape)}")
-        _require_cuda(out, "ResamplePool.step_padded")
-        arr = (_lib.WavPoolItem * max(count, 1))(*[_lib.WavPoolItem(s, c, int(f)) for s, c, f in items])
-        got = (ctypes.c_int64 * max(count, 1))()
+        out = self._out(out, (count,), max(plan, default=0), f"({count}, out_cols)")
         cols = int(out.shape[1])
-        with torch.cuda.device(self.device):
-            run = torch.cuda.current_stream()
-            check(self._lib.fv_respool_step(self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None, stride,
-                                            out.data_ptr() if out.numel() else None, max(cols, 1), cols, got, int(run.cuda_stream)))
-            self._record_done(run)          # the carried buffers are in use on the device until then
-        emit = [int(got[i]) for i in range(count)]
-        self.counters.commit(items, plan)                         # the Python counters move as the library's did
-        if plan != emit:
-            raise RuntimeError(f"the resample pool emitted {emit} outputs where the emission rule says {plan}")
-        return out, emit
-
-    def reset(self, session: int) -> None:
-        """Start the next utterance in one slot: N = E = 0; its carry is kept."""
-        self._check_open()
-        check(self._lib.fv_respool_reset(self._h, int(session)))
-        self.counters.reset(int(session))
+        self._run(lambda stream: self._lib.fv_respool_step(self._h, arr, count, cptr, stride, out.data_ptr() if out.numel() else None,
+                                                           max(cols, 1), cols, got, stream))
+        return out, self._moved(items, plan, got)
