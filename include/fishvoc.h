@@ -1458,6 +1458,53 @@ FV_API int64_t fv_wnstream_pending(const fv_wnstream* s);
 FV_API int32_t fv_wnstream_lookahead(const fv_wnstream* s);
 FV_API void fv_wnstream_destroy(fv_wnstream* s);
 
+/* -------- posterior encoder, sessions that advance independently (fv_wnpool_*) --------
+ * What fv_wnstream_* is to rows in lockstep, for `sessions` slots with their own N, E and flushed flag, as fv_wavpool_* / fv_respool_* are to
+ * their streams.  A step is a list of items (fv_wavpool_item: session, `samples` counting FRAMES here, flush: the utterance ends with these
+ * frames), each session at most once.  Per item N' = N + frames and E' = flush ? N' : max(E, N' - R); the item emits the latent frames
+ * [E, E').  A flush at N' = 0 emits nothing.  After its flush a slot refuses items (FV_ERR_STATE) until fv_wnpool_reset.  A session's
+ * concatenated frames are BIT-identical to fv_posterior_forward over its whole utterance, whatever the other sessions do: the kernels are
+ * the stream's (the whole-row body addressed through per-layer rings), with the column origin, the end and the frontier taken per item from
+ * a by-value table of 128 entries, and a slot's state is its own row of every ring.  A step enqueues at most
+ * (2 * n_layers + 2) * ceil(count / 128) launches, each serving every item of its block; a layer in which no item of the block has a new
+ * column is not launched.  A step neither allocates, copies nor synchronises.  All device state is allocated by fv_wnpool_create:
+ *   sessions * hidden_channels * (sum_i pow2(2 p_i + S) + pow2(R + S) + S) floats, S = max_chunk + R, pow2 = the next power of two
+ * (S is max_chunk + R where the stream has max(max_chunk, R): an item may flush together with its last frames, and its layers then advance
+ * by up to max_chunk + R frames in one step).  The pool reads the encoder's weights: destroy it before the encoder.  The whole step is
+ * validated before any counter moves or anything is enqueued, and a refusal names the item and the session: a refused step leaves every
+ * slot as it was. */
+typedef struct fv_wnpool fv_wnpool;
+/* p must be finalized (FV_ERR_STATE otherwise); sessions in [1, 65535], max_chunk in [1, 2^20]. */
+FV_API fv_status fv_wnpool_create(fv_posterior* p, int32_t sessions, int32_t max_chunk, fv_wnpool** out);
+/* Pure host, no GPU: what a step of `items` would emit on slots with the counters received[s], emitted[s], flushed[s] (flushed may be NULL:
+ * none is) of an encoder of reach R.  Writes E' - E per item into frames_out and returns the largest, or the negative fv_status of a refusal:
+ * a session outside [0, sessions), a duplicate session, frames outside [0, max_chunk], more than 2^30 frames in one utterance
+ * (FV_ERR_INVALID), an item for a flushed slot (FV_ERR_STATE).  Changes nothing. */
+FV_API int64_t fv_wnpool_plan(int32_t reach, int32_t sessions, int32_t max_chunk, const int64_t* received, const int64_t* emitted,
+                              const int32_t* flushed, const fv_wavpool_item* items, int32_t count, int64_t* frames_out);
+/* d_x: (count, in_channels, x_row_stride): frame j of channel ch of item i's chunk at d_x[i * x_item_stride + ch * x_row_stride + j],
+ * x_row_stride >= the longest chunk; what follows an item's frames in its row, NaN included, is never loaded; NULL when no item has frames.
+ * d_z, d_mean, d_logvar: (count, out_channels, out_cols), out_cols >= the largest E' - E: row i receives item i's frames first and exactly
+ * 0.0f after them (the mean too, in bnvae mode), every element written.  d_mean / d_logvar must be NULL in vqvae mode and may be NULL in the
+ * vae modes; d_z may be NULL when out_cols = 0.  frames_out (may be NULL) receives E' - E per item.  The plan's refusals apply, and null
+ * buffers, a row stride shorter than a chunk and out_cols below the largest E' - E are refused as well.  Asynchronous on `stream`. */
+FV_API fv_status fv_wnpool_step(fv_wnpool* p, const fv_wavpool_item* items, int32_t count, const float* d_x, int64_t x_item_stride,
+                                int64_t x_row_stride, float* d_z, float* d_mean, float* d_logvar, int32_t out_cols, int64_t* frames_out,
+                                void* stream);
+/* N = E = 0 and the flushed flag cleared for one slot; no device work (nothing at or past a frontier or before frame 0 is ever read). */
+FV_API fv_status fv_wnpool_reset(fv_wnpool* p, int32_t session);
+/* N, E and N - E of one slot; -1 for NULL or a session out of range. */
+FV_API int64_t fv_wnpool_received(const fv_wnpool* p, int32_t session);
+FV_API int64_t fv_wnpool_emitted(const fv_wnpool* p, int32_t session);
+FV_API int64_t fv_wnpool_pending(const fv_wnpool* p, int32_t session);
+/* R; -1 for NULL. */
+FV_API int32_t fv_wnpool_lookahead(const fv_wnpool* p);
+/* The most one item can emit in a step: max_chunk + R (a flush with max_chunk frames after R pending ones); -1 for NULL. */
+FV_API int64_t fv_wnpool_max_frames(const fv_wnpool* p);
+/* Host counter: the kernel launches the last accepted step enqueued; -1 for NULL. */
+FV_API int32_t fv_wnpool_launches(const fv_wnpool* p);
+FV_API void fv_wnpool_destroy(fv_wnpool* p);
+
 /* -------- wav2vec2 / HuBERT encoder (modules/encoders/hubert.py: HubertModel in its "stable layer norm" form, then `post`) --------
  * Eval-mode fp32 forward of the family feat_extract_norm = "layer", do_stable_layer_norm, conv_bias, feat_proj_layer_norm, GELU, eps 1e-5
  * (facebook/hubert-large-ll60k, facebook/mms-300m).  Activations are time major, (row, frame, channel).  With len_0 = the row's samples and

@@ -82,6 +82,8 @@ EXPORTS = (
     "fv_posterior_workspace_bytes", "fv_posterior_forward", "fv_posterior_destroy",
     "fv_wnstream_create", "fv_wnstream_push", "fv_wnstream_flush", "fv_wnstream_reset", "fv_wnstream_pending", "fv_wnstream_lookahead",
     "fv_wnstream_destroy",
+    "fv_wnpool_create", "fv_wnpool_plan", "fv_wnpool_step", "fv_wnpool_reset", "fv_wnpool_received", "fv_wnpool_emitted", "fv_wnpool_pending",
+    "fv_wnpool_lookahead", "fv_wnpool_max_frames", "fv_wnpool_launches", "fv_wnpool_destroy",
     "fv_w2v_create", "fv_w2v_load_weight", "fv_w2v_finalize", "fv_w2v_frames", "fv_w2v_workspace_bytes", "fv_w2v_forward", "fv_w2v_destroy",
     "fv_mms_normalize_workspace_bytes", "fv_mms_normalize", "fv_mms_interpolate", "fv_mms_nearest_index",
 )
@@ -566,6 +568,25 @@ def lib() -> ctypes.CDLL:
     L.fv_wnstream_lookahead.restype = _i32
     L.fv_wnstream_destroy.argtypes = [vp]
     L.fv_wnstream_destroy.restype = None
+    L.fv_wnpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_wnpool_create.restype = _i32
+    L.fv_wnpool_plan.argtypes = [_i32, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
+    L.fv_wnpool_plan.restype = i64
+    L.fv_wnpool_step.argtypes = [vp, wip, _i32, vp, i64, i64, vp, vp, vp, _i32, i64p, vp]
+    L.fv_wnpool_step.restype = _i32
+    L.fv_wnpool_reset.argtypes = [vp, _i32]
+    L.fv_wnpool_reset.restype = _i32
+    for name in ("received", "emitted", "pending"):
+        getattr(L, "fv_wnpool_" + name).argtypes = [vp, _i32]
+        getattr(L, "fv_wnpool_" + name).restype = i64
+    L.fv_wnpool_lookahead.argtypes = [vp]
+    L.fv_wnpool_lookahead.restype = _i32
+    L.fv_wnpool_max_frames.argtypes = [vp]
+    L.fv_wnpool_max_frames.restype = i64
+    L.fv_wnpool_launches.argtypes = [vp]
+    L.fv_wnpool_launches.restype = _i32
+    L.fv_wnpool_destroy.argtypes = [vp]
+    L.fv_wnpool_destroy.restype = None
     L.fv_w2v_create.argtypes = [ctypes.POINTER(W2VConfig), ctypes.POINTER(vp)]
     L.fv_w2v_create.restype = _i32
     L.fv_w2v_load_weight.argtypes = [vp, cp, fp, i64p, _i32]

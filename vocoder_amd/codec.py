@@ -20,6 +20,8 @@ import numpy as np
 import torch
 from torch import nn
 
+from ._handle import _gather, _require_cuda
+
 
 class VQVAECodec(nn.Module):
     def __init__(self, encoder: nn.Module, decoder: nn.Module, vq: nn.Module, frontend: nn.Module | None = None, hop_length: int | None = None):
@@ -57,6 +59,12 @@ class VQVAECodec(nn.Module):
         encoder of spectrograms whose own ``stream()`` has ``forward``'s bits (``PosteriorEncoder``); with the front-end in its
         batch-invariant mode the concatenated codes are ``encode``'s."""
         return CodecEncodeStream(self, batch, max_chunk_samples)
+
+    def encode_pool(self, sessions: int, max_chunk_samples: int = 4096) -> "CodecEncodePool":
+        """``encode`` for ``sessions`` live sources that advance at their own pace (``CodecEncodePool``): one step serves any subset of them in
+        the launches one ``encode_stream`` push takes.  The same encoders as ``encode_stream``; with the front-end in its batch-invariant mode
+        a session's concatenated codes are ``encode``'s of its whole utterance."""
+        return CodecEncodePool(self, sessions, max_chunk_samples)
 
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
         y = self.decoder(self.vq.from_codes(codes)[0])
@@ -100,6 +108,69 @@ class VQVAECodec(nn.Module):
         return self.load_state_dict(own, strict=True)
 
 
+def _streaming_encoder(codec: VQVAECodec, what: str) -> nn.Module:
+    """The encoder of a codec that can encode chunk by chunk with ``encode``'s codes; ``what`` (``encode_stream`` / ``encode_pool``) refuses
+    the others by name."""
+    enc, name = codec.encoder, type(codec.encoder).__name__
+    if getattr(enc, "takes_audio", False):
+        raise ValueError(f"{what}: {name} takes raw audio (takes_audio), not a streamed spectrogram: it has no streaming encode")
+    if not getattr(enc, "stream_is_bit_exact", False):
+        raise ValueError(f"{what}: {name}.stream() is not bit-exact — a windowed engine stream promises 2e-5, not forward's bits, so "
+                         "codes could differ from encode(); use a PosteriorEncoder (build_vqvae(encoder='posterior'))")
+    if codec.frontend is None:
+        raise ValueError(f"{what}: the codec has no front-end to turn the audio chunks into spectrogram frames")
+    return enc
+
+
+class CodecEncodePool:
+    """``VQVAECodec.encode`` for live sources that advance independently: ``frontend.wav_pool()`` -> ``encoder.pool()`` -> ``vq.encode``.  The
+    front-end's padded frames go straight into the encoder pool's ``step_padded`` and its padded latents into the quantiser with the frame
+    counts per item: nothing goes through the host.  ``step(items)`` takes ``(session, wave, flush)`` tuples — ``wave``: 1-D, at most
+    ``max_chunk_samples`` samples, or ``None``; ``flush``: the utterance ends with them — and returns per item the int64 codes of the latent
+    frames that are final, ``(k,)`` or ``(n_q, k)`` for the residual form, ``k`` possibly 0.  Both stages are planned before either is
+    launched, so a refused step moves neither pool.  ``reset(session)`` starts a slot's next utterance."""
+
+    def __init__(self, codec: VQVAECodec, sessions: int, max_chunk_samples: int = 4096):
+        enc = _streaming_encoder(codec, "encode_pool")
+        self._vq = codec.vq
+        self.sessions, self.max_chunk_samples = int(sessions), int(max_chunk_samples)
+        self.wav_pool = codec.frontend.wav_pool(self.sessions, self.max_chunk_samples)
+        self.enc_pool = enc.pool(self.sessions, self.wav_pool.max_frames)
+
+    def received_samples(self, session: int) -> int:
+        return self.wav_pool.received_samples(session)
+
+    def emitted_frames(self, session: int) -> int:
+        return self.enc_pool.emitted_frames(session)
+
+    def step(self, items) -> list:
+        wp, ep = self.wav_pool, self.enc_pool
+        wp._check_open(), ep._check_open()
+        meta, chunks = _gather(items, wp._engine.device, _require_cuda, "CodecEncodePool.step")
+        frames = wp.counters.plan(meta)                         # both plans before either launch: a refusal moves neither pool
+        enc_items = [(s, f, flush) for (s, _, flush), f in zip(meta, frames)]
+        ep.counters.plan(enc_items)
+        spec, _ = wp.step_padded(meta, chunks)
+        z, emit = ep.step_padded(enc_items, spec if spec.numel() else None)
+        z = z[0] if isinstance(z, tuple) else z
+        codes = self._vq.encode(z, emit)
+        return [codes[..., i, :k] for i, k in enumerate(emit)]
+
+    def reset(self, session: int) -> None:
+        self.wav_pool.reset(session)
+        self.enc_pool.reset(session)
+
+    def close(self) -> None:
+        self.wav_pool.close()
+        self.enc_pool.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
 class CodecEncodeStream:
     """``VQVAECodec.encode`` on a live source: ``frontend.stream()`` -> ``encoder.stream()`` -> ``vq.encode``, every stage on the device.
     ``push(wave (B, c) or (B, 1, c))``, ``c <= max_chunk_samples``, returns the codes of the latent frames that are final — ``(B, k)``, or
@@ -107,14 +178,7 @@ class CodecEncodeStream:
     one.  The quantiser is frame-independent, so the concatenated codes are ``encode``'s whenever both streams have their whole-row bits."""
 
     def __init__(self, codec: VQVAECodec, batch: int = 1, max_chunk_samples: int = 4096):
-        enc, name = codec.encoder, type(codec.encoder).__name__
-        if getattr(enc, "takes_audio", False):
-            raise ValueError(f"encode_stream: {name} takes raw audio (takes_audio), not a streamed spectrogram: it has no streaming encode")
-        if not getattr(enc, "stream_is_bit_exact", False):
-            raise ValueError(f"encode_stream: {name}.stream() is not bit-exact — a windowed engine stream promises 2e-5, not forward's bits, so "
-                             "codes could differ from encode(); use a PosteriorEncoder (build_vqvae(encoder='posterior'))")
-        if codec.frontend is None:
-            raise ValueError("encode_stream: the codec has no front-end to turn the audio chunks into spectrogram frames")
+        enc = _streaming_encoder(codec, "encode_stream")
         self._vq = codec.vq
         self._fe = codec.frontend.stream(batch, max_chunk_samples)
         self.batch, self.max_chunk_samples = int(batch), int(max_chunk_samples)

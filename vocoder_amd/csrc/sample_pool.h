@@ -18,10 +18,12 @@ using SamplePoolItem = fv_wavpool_item;   // session, samples, flush: the uttera
 // The refusals every step shares, over the counters `received` / `flushed` of `S` slots (flushed may be NULL: none is), in this order per item:
 // session out of range, duplicate session, samples outside [0, max_chunk], a flushed slot (FV_ERR_STATE), more than 2^40 samples; then, with
 // `buffers`, a NULL chunk buffer although an item has samples and a row stride shorter than the longest chunk.  Each names the item and the
-// session.  FV_OK: N2[i] = the samples slot items[i].session has received once the step commits.  Changes nothing.
+// session.  FV_OK: N2[i] = the samples slot items[i].session has received once the step commits.  Changes nothing.  A pool that counts
+// something else (the posterior pool: frames, 2^30 of them) names its unit and its longest utterance.
 inline fv_status sample_pool_admit(const char* fn, const char* reset_fn, int S, int max_chunk, const int64_t* received, const int32_t* flushed,
                                    const SamplePoolItem* items, int count, bool buffers, const float* chunks, long long chunk_stride,
-                                   long long* N2) {
+                                   long long* N2, const char* unit = "samples", long long max_len = kSampleStreamMaxLen,
+                                   const char* max_name = "2^40") {
     if (count < 0 || (count > 0 && (!items || !N2))) {
         set_error("%s: %d items with a null %s", fn, count, items ? "result" : "item list");
         return FV_ERR_INVALID;
@@ -40,7 +42,7 @@ inline fv_status sample_pool_admit(const char* fn, const char* reset_fn, int S, 
         }
         seen[(size_t)it.session] = 1;
         if (it.samples < 0 || it.samples > max_chunk) {
-            set_error("%s: item %d (session %d) has %d samples, outside [0, max_chunk = %d]", fn, i, it.session, it.samples, max_chunk);
+            set_error("%s: item %d (session %d) has %d %s, outside [0, max_chunk = %d]", fn, i, it.session, it.samples, unit, max_chunk);
             return FV_ERR_INVALID;
         }
         if (flushed && flushed[it.session]) {
@@ -48,8 +50,8 @@ inline fv_status sample_pool_admit(const char* fn, const char* reset_fn, int S, 
             return FV_ERR_STATE;
         }
         const long long N = received[it.session];
-        if (N < 0 || N + it.samples > kSampleStreamMaxLen) {
-            set_error("%s: item %d takes session %d past 2^40 samples in one utterance (%lld + %d)", fn, i, it.session, N, it.samples);
+        if (N < 0 || N + it.samples > max_len) {
+            set_error("%s: item %d takes session %d past %s %s in one utterance (%lld + %d)", fn, i, it.session, max_name, unit, N, it.samples);
             return FV_ERR_INVALID;
         }
         N2[i] = N + it.samples;
@@ -57,13 +59,13 @@ inline fv_status sample_pool_admit(const char* fn, const char* reset_fn, int S, 
     }
     if (buffers && longest > 0) {
         if (!chunks) {
-            set_error("%s: null chunk buffer although item %d (session %d) has %d samples", fn, longest_item, items[longest_item].session,
-                      longest);
+            set_error("%s: null chunk buffer although item %d (session %d) has %d %s", fn, longest_item, items[longest_item].session,
+                      longest, unit);
             return FV_ERR_INVALID;
         }
         if (chunk_stride < longest) {
-            set_error("%s: row stride %lld is shorter than the longest chunk, the %d samples of item %d (session %d)", fn, chunk_stride, longest,
-                      longest_item, items[longest_item].session);
+            set_error("%s: row stride %lld is shorter than the longest chunk, the %d %s of item %d (session %d)", fn, chunk_stride, longest,
+                      unit, longest_item, items[longest_item].session);
             return FV_ERR_INVALID;
         }
     }

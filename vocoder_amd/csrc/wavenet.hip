@@ -21,6 +21,9 @@
 // The stream (fv_wnstream_*): the same body instantiated with STREAM — a column origin, input and output addresses through a WnSpan (a ring
 // or a linear buffer) and the input's valid range [lo, frontier) — runs every layer over a push's new columns only, out of one ring per
 // layer input.  Nothing above depends on where a column sits, so a stream has the whole row's bits under any chunking.
+// The pool (fv_wnpool_*): the body once more, instantiated with WN_POOL — the stream's form with the column origin, the end and the frontier
+// taken per table entry (blockIdx.z), rings addressed by the entry's slot — for sessions that advance independently: one launch serves
+// every item of a step, and a session has the bits of its whole utterance whatever the other sessions do.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -29,6 +32,7 @@
 #include <string>
 
 #include "fv_internal.h"
+#include "sample_pool.h"
 
 namespace fv {
 namespace {
@@ -48,6 +52,16 @@ constexpr int kWnRing = 4;                          // weight fragments in fligh
 constexpr int kWnMaxStageChunks = 8;
 
 using WnRowBlock = LaunchTable<int, kWnRows>;
+
+// The pool form's table (fv_wnpool_*): an entry is one item of a step in one launch — the slot whose ring rows it reads and writes, its first
+// column, its end (what T is to the stream: no column at or past it is written) and its input's frontier (what `uniform` is to the stream)
+struct WnPoolEntry {
+    int slot, col0, end, front;
+};
+constexpr int kWnPoolBlock = 128;                   // entries per launch: 2 KiB, with WnParams well inside the 4 KiB kernel-argument segment
+using WnPoolBlock = LaunchTable<WnPoolEntry, kWnPoolBlock>;
+
+enum WnForm : int { WN_ROWS = 0, WN_STREAM = 1, WN_POOL = 2 };
 
 enum WnMode : int { WN_GATE = 0, WN_RES_SKIP = 1, WN_PRE = 2, WN_PROJ = 3 };
 
@@ -77,15 +91,19 @@ struct WnParams {
     int G;                          // chunks staged per barrier (wn_stage_chunks)
     // The stream instantiations only (fv_wnstream_*).  A launch covers the frames [col0, T) of every row; `uniform` is the input's frontier
     // (frames at or past it stage as zero, whatever a ring holds there) and `lo` its first frame in memory.  A WnSpan is where a frame lives.
+    // The pool instantiations (fv_wnpool_*) take col0, T and the frontier from their entry; `lo` != 0 says the input begins at the entry's
+    // col0 (else at frame 0).  A ring span is indexed by the entry's slot, a linear one by the item's row row0 + blockIdx.z, origin col0.
     int col0, lo;
     WnSpan xs, y0s, y1s, rs;        // of x, of y0 (and z), of y1, of res
     const float* res;               // res_skip: the residual input h_i (its own ring; y0 is the ring of h_{i + 1})
 };
 
 // WN waves side by side along time (32 columns each) x 4 / WN pairs; KS = 0: taps and dilation at run time
-// STREAM: the tile's columns are the frames col0 + ..., and every address goes through a WnSpan; the sums are the whole-row ones
-template <int MODE, int WN, int KS, int DIL, bool STREAM = false>
-__device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& rows) {
+// WN_STREAM: the tile's columns are the frames col0 + ..., and every address goes through a WnSpan; the sums are the whole-row ones
+// WN_POOL: the stream's form with col0, the end and the frontier per table entry (blockIdx.z): sessions that advance independently
+template <int MODE, int WN, int KS, int DIL, int FORM = WN_ROWS, class Rows = WnRowBlock>
+__device__ __forceinline__ void wn_body(const WnParams& p, const Rows& rows) {
+    constexpr bool STREAM = FORM != WN_ROWS, POOL = FORM == WN_POOL;
     constexpr int WM = 4 / WN, N_BLK = 32 * WN;
     extern __shared__ __attribute__((aligned(16))) float wn_xs[];
     const int ks = KS ? KS : p.ks, dil = KS ? DIL : p.dil;
@@ -95,9 +113,22 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
     const int wn = wave % WN, wm = wave / WN;
     const int bl = blockIdx.z;
     const long long b = p.row0 + bl;
-    const int len = STREAM || p.uniform >= 0 ? p.uniform : rows.e[bl];
-    const int n0 = (STREAM ? p.col0 : 0) + blockIdx.x * N_BLK;
-    if ((STREAM || MODE != WN_PROJ) && n0 >= len) return;       // nothing of this tile is ever read (block-uniform); proj still writes its zeros
+    int len, cbase, Tend, lo, slot = 0;
+    if constexpr (POOL) {
+        const WnPoolEntry e = rows.e[bl];
+        len = e.front, cbase = e.col0, Tend = e.end, lo = p.lo ? e.col0 : 0, slot = e.slot;
+    } else {
+        len = STREAM || p.uniform >= 0 ? p.uniform : rows.e[bl];
+        cbase = STREAM ? p.col0 : 0, Tend = p.T, lo = p.lo;
+    }
+    const int n0 = cbase + blockIdx.x * N_BLK;
+    if (POOL && n0 >= Tend) return;                             // the grid is the widest entry's: this one has no column here (block-uniform)
+    if ((FORM == WN_STREAM || MODE != WN_PROJ) && n0 >= len) return;       // nothing of this tile is ever read (block-uniform); proj still writes its zeros
+    // where frame t of row m of a span's tensor lives
+    auto at = [&](const WnSpan& sp, int M, int m, int t) -> long long {
+        if constexpr (POOL) return ((sp.mask < 0 ? b : (long long)slot) * M + m) * sp.stride + ((t - (sp.mask < 0 ? cbase : 0)) & sp.mask);
+        else return sp.at(b * M + m, t);
+    };
     const int pair = blockIdx.y * WM + wm;
     const bool do0 = pair < p.npairs && pair * 32 < p.M0, do1 = pair < p.npairs && pair * 32 < p.M1;      // wave-uniform
 
@@ -106,7 +137,8 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
     for (int r = 0; r < 16; ++r) acc0[r] = 0.f, acc1[r] = 0.f;
 
     if (n0 < len) {
-        const float* __restrict__ xb = p.x + b * p.x_bstride;
+        const float* __restrict__ xb = p.x + (POOL && p.xs.mask >= 0 ? (long long)slot : b) * p.x_bstride;
+        const int xorg = POOL ? (p.xs.mask < 0 ? cbase : 0) : p.xs.org;
         const int tbase = n0 - (ks - 1) * dil / 2;
         const int G = p.G, total = G * kChunk * W;          // a stage: G chunks, G kChunk W <= 256 kWnSlots floats (wn_stage_chunks)
         const int nstage = (p.nchunk + G - 1) / G;
@@ -124,7 +156,7 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
                 if (tid + 256 * i < total) {
                     const int ci = s * G * kChunk + r, t = tbase + col;
                     if constexpr (STREAM) {
-                        if (ci < p.Cin && t >= p.lo && t < len) v = xb[(long long)ci * p.x_cstride + ((t - p.xs.org) & p.xs.mask)];
+                        if (ci < p.Cin && t >= lo && t < len) v = xb[(long long)ci * p.x_cstride + ((t - xorg) & p.xs.mask)];
                     } else {
                         if (ci < p.Cin && t >= 0 && t < len) v = xb[(long long)ci * p.x_cstride + t];     // the conv's zero padding and the row's length
                     }
@@ -188,15 +220,15 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
     }
 
     const int n = n0 + wn * 32 + (lane & 31);
-    if (n >= p.T || pair >= p.npairs) return;
+    if (n >= Tend || pair >= p.npairs) return;
     const bool valid = n < len;
     const float* __restrict__ bias0 = p.bias;
     const float* __restrict__ bias1 = p.bias + 32 * p.npairs;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = pair * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const long long o0 = STREAM ? p.y0s.at(b * p.M0 + m, n) : (b * p.M0 + m) * p.T + n;
-        const long long o1 = STREAM ? p.y1s.at(b * p.M1 + m, n) : (b * p.M1 + m) * p.T + n;
+        const long long o0 = STREAM ? at(p.y0s, p.M0, m, n) : (b * p.M0 + m) * p.T + n;
+        const long long o1 = STREAM ? at(p.y1s, p.M1, m, n) : (b * p.M1 + m) * p.T + n;
         if (MODE == WN_GATE) {
             if (valid && m < p.M0) {
                 const float t = tanhf(acc0[r] + bias0[m]);
@@ -206,7 +238,7 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
         } else if (MODE == WN_RES_SKIP) {
             if (!valid) continue;
             if constexpr (STREAM) {
-                if (m < p.M0) p.y0[o0] = p.res[p.rs.at(b * p.M0 + m, n)] + (acc0[r] + bias0[m]);     // h_{i + 1} = h_i + r, from ring to ring
+                if (m < p.M0) p.y0[o0] = p.res[at(p.rs, p.M0, m, n)] + (acc0[r] + bias0[m]);     // h_{i + 1} = h_i + r, from ring to ring
             } else {
                 if (m < p.M0) p.y0[o0] = p.y0[o0] + (acc0[r] + bias0[m]);           // the same lane reads and writes the element
             }
@@ -221,7 +253,7 @@ __device__ __forceinline__ void wn_body(const WnParams& p, const WnRowBlock& row
                 const float v = valid ? acc0[r] + bias0[m] : 0.f;
                 if (p.z) {
                     const float mean = p.bn_scale ? fmaf(v, p.bn_scale[m], p.bn_shift[m]) : v;     // after the mask: a padded frame holds shift
-                    if (p.y0) p.y0[o0] = mean;
+                    if (p.y0) p.y0[o0] = POOL && !valid ? 0.f : mean;      // a pool's rows hold exact zeros past an item's frames
                     p.z[o0] = valid ? mean : 0.f;
                 } else {
                     p.y0[o0] = v;
@@ -245,7 +277,10 @@ template <int WN>
 __global__ __launch_bounds__(256) void wn_proj_kernel(const WnParams p, const WnRowBlock rows) { wn_body<WN_PROJ, WN, 1, 1>(p, rows); }
 // The stream forms take no row table: every row of a stream holds the same frames
 template <int MODE, int WN, int KS, int DIL>
-__global__ __launch_bounds__(256) void wn_stream_kernel(const WnParams p) { wn_body<MODE, WN, KS, DIL, true>(p, WnRowBlock{}); }
+__global__ __launch_bounds__(256) void wn_stream_kernel(const WnParams p) { wn_body<MODE, WN, KS, DIL, WN_STREAM>(p, WnRowBlock{}); }
+// The pool forms: one table entry per item of the step
+template <int MODE, int WN, int KS, int DIL>
+__global__ __launch_bounds__(256) void wn_pool_kernel(const WnParams p, const WnPoolBlock rows) { wn_body<MODE, WN, KS, DIL, WN_POOL>(p, rows); }
 
 // Chunks per stage: as many as keep a stage inside the threads' kWnSlots registers, which is also half the LDS budget (two stages)
 int wn_stage_chunks(int cols, int ks, int dil) {
@@ -280,6 +315,19 @@ void wn_stream_launch(WnParams p, int nrows, hipStream_t s) {
     const size_t lds = wn_lds_bytes(cols, p.ks, p.dil, p.G);
     auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, p); };
     narrow ? go(wn_stream_kernel<MODE, 1, KS, DIL>) : go(wn_stream_kernel<MODE, 4, KS, DIL>);
+}
+
+// The entries' frames of `nz` items; the grid is the widest entry's and the tile is chosen by its `ncols` columns, as wn_stream_launch does.
+// p.col0, p.T and p.uniform are not read: they are the entries'.
+template <int MODE, int KS, int DIL>
+void wn_pool_launch(WnParams p, const WnPoolBlock& rows, int nz, int ncols, hipStream_t s) {
+    const bool narrow = ncols <= kWnNarrowMaxT;
+    const int cols = narrow ? 32 : kWnWideCols, wm = narrow ? 4 : 1;
+    const dim3 grid((unsigned)((ncols + cols - 1) / cols), (unsigned)((p.npairs + wm - 1) / wm), (unsigned)nz);
+    p.G = wn_stage_chunks(cols, p.ks, p.dil);
+    const size_t lds = wn_lds_bytes(cols, p.ks, p.dil, p.G);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, p, rows); };
+    narrow ? go(wn_pool_kernel<MODE, 1, KS, DIL>) : go(wn_pool_kernel<MODE, 4, KS, DIL>);
 }
 
 // One GEMM of the stack on the host side: the folded rows of its two halves, packed
@@ -355,22 +403,66 @@ struct fv_posterior {
 // input h_i is known up to frame N - lam[i] after N frames have arrived, and a push computes only the new columns of every layer.  h_i lives
 // in a ring of its own: its next outputs still read the last 2 p_i frames below the frontier, and one call adds max(max_chunk, R) at the
 // most (R: a flush takes every layer up to N), so nothing is copied between pushes.  `out`, the running skip sum, is a ring of the R frames
-// that wait for their later layers plus one call's; g is linear, one call's columns.
-struct fv_wnstream {
+// that wait for their later layers plus one call's; g is linear, one call's columns.  One allocation holds them for `rows` rows: a stream's
+// batch rows, or a pool's slots (g: its items).
+namespace {
+struct WnRings {
+    std::vector<int> lam;               // n_layers + 1
+    std::vector<float*> h;              // ring of h_i, (rows, C, hW[i])
+    std::vector<int> hW;
+    float* out = nullptr;               // (rows, C, outW)
+    float* g = nullptr;                 // (rows, C, gW)
+    int outW = 0, gW = 0;
+    float* slab = nullptr;
+    ~WnRings() {
+        if (slab) (void)hipFree(slab);
+    }
+    // step: the most frames one call adds to a frontier
+    fv_status create(const fv_posterior* p, int rows, long long step) {
+        const int nl = p->cfg.n_layers, k = p->cfg.kernel_size, R = p->reach;
+        lam.assign(nl + 1, 0);
+        size_t frames = 0;                                         // per (row, channel)
+        for (int i = 0; i < nl; ++i) {
+            const int pad = (k - 1) * p->dil[i] / 2;
+            lam[i + 1] = lam[i] + pad;
+            int w = 1;
+            while (w < 2LL * pad + step) w <<= 1;
+            hW.push_back(w);
+            frames += (size_t)w;
+        }
+        outW = 1;
+        while (outW < R + step) outW <<= 1;
+        gW = (int)step;
+        frames += (size_t)outW + (size_t)gW;
+        const size_t plane = (size_t)rows * (size_t)p->cfg.hidden_channels;
+        FV_HIP_CHECK(hipMalloc(&slab, plane * frames * sizeof(float)));
+        float* at = slab;
+        for (int i = 0; i < nl; ++i) h.push_back(at), at += plane * (size_t)hW[i];
+        out = at, at += plane * (size_t)outW;
+        g = at;
+        return FV_OK;
+    }
+};
+}  // namespace
+
+struct fv_wnstream : WnRings {
     fv_posterior* enc = nullptr;
     int batch = 0, max_chunk = 0;
     long long N = 0, E = 0;
     bool flushed = false;
-    std::vector<int> lam;               // n_layers + 1
-    std::vector<float*> h;              // ring of h_i, (batch, C, hW[i])
-    std::vector<int> hW;
-    float* out = nullptr;               // (batch, C, outW)
-    float* g = nullptr;                 // (batch, C, gW)
-    int outW = 0, gW = 0;
-    float* slab = nullptr;
-    ~fv_wnstream() {
-        if (slab) (void)hipFree(slab);
-    }
+};
+
+// The encoder for `S` sessions that advance independently (fv_wnpool_*): the stream's rings with one row per slot, addressed by the slot's
+// own absolute frame numbers, so a slot's state is its row of each ring and its counters; g has one row per item of a step.  A step fills
+// one WnPoolEntry per item and launch from the item's (N, N', E, flush) and the layer's lam, wn_stream_advance's arithmetic per item, and a
+// launch serves every item of a block.  An item may flush together with its last frames, so a layer advances by up to max_chunk + R frames
+// in one step, where a stream's advances by max(max_chunk, R): the rings and g are sized for that.
+struct fv_wnpool : WnRings {
+    fv_posterior* enc = nullptr;
+    int S = 0, max_chunk = 0;
+    std::vector<int64_t> N, E;
+    std::vector<int32_t> flushed;
+    int launches = 0;                   // of the last accepted step
 };
 
 namespace {
@@ -680,12 +772,6 @@ FV_API fv_status fv_posterior_forward(fv_posterior* p, const float* d_x, int64_t
 
 namespace {
 
-int wn_pow2_at_least(long long v) {
-    int w = 1;
-    while (w < v) w <<= 1;
-    return w;
-}
-
 // One push (c frames of d_x) or the flush: validates, then enqueues at most 2 n_layers + 2 launches and moves the counters
 fv_status wn_stream_advance(const char* fn, fv_wnstream* s, const float* d_x, int64_t x_batch_stride, int64_t x_row_stride, int32_t c, bool flush,
                             float* d_z, float* d_mean, float* d_logvar, int64_t y_row_stride, int64_t* emitted, void* stream) {
@@ -811,24 +897,7 @@ FV_API fv_status fv_wnstream_create(fv_posterior* p, int32_t batch, int32_t max_
     }
     std::unique_ptr<fv_wnstream> s(new fv_wnstream());
     s->enc = p, s->batch = batch, s->max_chunk = max_chunk;
-    const int nl = p->cfg.n_layers, k = p->cfg.kernel_size, R = p->reach;
-    const long long step = std::max(max_chunk, R);            // the most frames one call adds to a frontier
-    s->lam.assign(nl + 1, 0);
-    size_t frames = 0;                                         // per (row, channel)
-    for (int i = 0; i < nl; ++i) {
-        const int pad = (k - 1) * p->dil[i] / 2;
-        s->lam[i + 1] = s->lam[i] + pad;
-        s->hW.push_back(wn_pow2_at_least(2LL * pad + step));
-        frames += (size_t)s->hW.back();
-    }
-    s->outW = wn_pow2_at_least(R + step), s->gW = (int)step;
-    frames += (size_t)s->outW + (size_t)s->gW;
-    const size_t plane = (size_t)batch * (size_t)p->cfg.hidden_channels;
-    FV_HIP_CHECK(hipMalloc(&s->slab, plane * frames * sizeof(float)));
-    float* at = s->slab;
-    for (int i = 0; i < nl; ++i) s->h.push_back(at), at += plane * (size_t)s->hW[i];
-    s->out = at, at += plane * (size_t)s->outW;
-    s->g = at;
+    if (const fv_status st = s->create(p, batch, std::max(max_chunk, p->reach))) return st;
     *out = s.release();
     return FV_OK;
 }
@@ -857,5 +926,221 @@ FV_API int64_t fv_wnstream_pending(const fv_wnstream* s) { return s ? s->N - s->
 FV_API int32_t fv_wnstream_lookahead(const fv_wnstream* s) { return s ? s->enc->reach : -1; }
 
 FV_API void fv_wnstream_destroy(fv_wnstream* s) { delete s; }
+
+}  // extern "C"
+
+namespace {
+
+// The refusals of a pool step's items (sample_pool_admit, counting frames, 2^30 of them) and the emission rule: N2 and E2 per item
+fv_status wn_pool_admit(const char* fn, int R, int S, int max_chunk, const int64_t* received, const int64_t* emitted, const int32_t* flushed,
+                        const fv_wavpool_item* items, int count, bool buffers, const float* d_x, long long x_row_stride, long long* N2,
+                        long long* E2) {
+    if (const fv_status st = sample_pool_admit(fn, "fv_wnpool_reset", S, max_chunk, received, flushed, items, count, buffers, d_x, x_row_stride, N2,
+                                               "frames", kWnMaxFrames, "2^30"))
+        return st;
+    for (int i = 0; i < count; ++i) E2[i] = items[i].flush ? N2[i] : std::max((long long)emitted[items[i].session], N2[i] - R);
+    return FV_OK;
+}
+
+fv_status wn_pool_range(const char* fn, int sessions, int max_chunk) {
+    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 20)) {
+        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^20]", fn, sessions, max_chunk);
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+FV_API fv_status fv_wnpool_create(fv_posterior* p, int32_t sessions, int32_t max_chunk, fv_wnpool** out) {
+    const char* fn = "fv_wnpool_create";
+    if (!out || !p) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!p->finalized) {
+        set_error("%s: the encoder has not been finalized (fv_posterior_finalize)", fn);
+        return FV_ERR_STATE;
+    }
+    if (const fv_status st = wn_pool_range(fn, sessions, max_chunk)) return st;
+    std::unique_ptr<fv_wnpool> s(new fv_wnpool());
+    s->enc = p, s->S = sessions, s->max_chunk = max_chunk;
+    s->N.assign((size_t)sessions, 0), s->E.assign((size_t)sessions, 0), s->flushed.assign((size_t)sessions, 0);
+    // an item may flush with its last frames: its layers then advance by max_chunk + lam[i + 1] <= max_chunk + R frames in one step
+    if (const fv_status st = s->create(p, sessions, (long long)max_chunk + p->reach)) return st;
+    *out = s.release();
+    return FV_OK;
+}
+
+FV_API int64_t fv_wnpool_plan(int32_t reach, int32_t sessions, int32_t max_chunk, const int64_t* received, const int64_t* emitted,
+                              const int32_t* flushed, const fv_wavpool_item* items, int32_t count, int64_t* frames_out) {
+    const char* fn = "fv_wnpool_plan";
+    if (reach < 0) {
+        set_error("%s: reach = %d must be >= 0", fn, reach);
+        return FV_ERR_INVALID;
+    }
+    if (const fv_status st = wn_pool_range(fn, sessions, max_chunk)) return st;
+    if (!received || !emitted || (count > 0 && !frames_out)) {
+        set_error("%s: null argument", fn);
+        return FV_ERR_INVALID;
+    }
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status st = wn_pool_admit(fn, reach, sessions, max_chunk, received, emitted, flushed, items, count, false, nullptr, 0, N2.data(),
+                                           E2.data()))
+        return st;
+    return sample_pool_counts(emitted, items, count, E2.data(), frames_out);
+}
+
+FV_API fv_status fv_wnpool_step(fv_wnpool* p, const fv_wavpool_item* items, int32_t count, const float* d_x, int64_t x_item_stride,
+                                int64_t x_row_stride, float* d_z, float* d_mean, float* d_logvar, int32_t out_cols, int64_t* frames_out,
+                                void* stream) {
+    const char* fn = "fv_wnpool_step";
+    if (!p) {
+        set_error("%s: null pool", fn);
+        return FV_ERR_INVALID;
+    }
+    const fv_posterior* enc = p->enc;
+    const fv_posterior_config& cfg = enc->cfg;
+    if (cfg.mode == 0 && (d_mean || d_logvar)) {
+        set_error("%s: %s must be NULL in vqvae mode (posterior_encoder.py:159-160 returns one tensor)", fn, d_mean ? "d_mean" : "d_logvar");
+        return FV_ERR_INVALID;
+    }
+    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
+    if (const fv_status st = wn_pool_admit(fn, enc->reach, p->S, p->max_chunk, p->N.data(), p->E.data(), p->flushed.data(), items, count, true, d_x,
+                                           x_row_stride, N2.data(), E2.data()))
+        return st;
+    if (d_x && x_item_stride < 0) {
+        set_error("%s: x_item_stride = %lld is negative", fn, (long long)x_item_stride);
+        return FV_ERR_INVALID;
+    }
+    if (out_cols > kWnMaxFrames) {
+        set_error("%s: out_cols = %d is more than 2^30", fn, out_cols);
+        return FV_ERR_INVALID;
+    }
+    if (const fv_status st = sample_pool_output(fn, "frames", items, count, p->E.data(), E2.data(), 1, d_z != nullptr, out_cols, out_cols)) return st;
+    if (count > 0 && out_cols > 0 && !d_z) {
+        set_error("%s: null d_z although every row's first out_cols = %d columns are written", fn, out_cols);
+        return FV_ERR_INVALID;
+    }
+    // everything is validated: enqueue
+
+    hipStream_t st = (hipStream_t)stream;
+    const int nl = cfg.n_layers, C = cfg.hidden_channels;
+    const bool k5 = cfg.kernel_size == 5;
+    auto ring = [](int W) { return WnSpan{W, 0, W - 1}; };
+    auto linear = [](long long stride) { return WnSpan{stride, 0, -1}; };       // the origin is the entry's col0
+    auto clamp0 = [](long long v) { return (int)std::max(0LL, v); };
+    int launches = 0;
+    const fv_status rs = for_each_launch_table<WnPoolBlock>(
+        count, [&](int i) { return WnPoolEntry{items[i].session, 0, 0, 0}; }, [&](const WnPoolBlock& slots, int first, int nz) -> fv_status {
+            WnPoolBlock t = slots;
+            // the table of one launch: cols(item, N, N', flush) -> {col0, end, frontier}; returns the widest entry's columns
+            auto table = [&](auto&& cols) {
+                int widest = 0;
+                for (int i = 0; i < nz; ++i) {
+                    const int item = first + i;
+                    const WnPoolEntry e = cols(item, (long long)p->N[(size_t)items[item].session], N2[(size_t)item], items[item].flush != 0);
+                    t.e[i].col0 = e.col0, t.e[i].end = e.end, t.e[i].front = e.front;
+                    widest = std::max(widest, e.end - e.col0);
+                }
+                return widest;
+            };
+            auto rows = [&](WnParams q) {
+                q.row0 = first;
+                return q;
+            };
+            // h_0 = pre(x) over every item's new frames
+            if (const int w = table([&](int, long long N0, long long N1, bool) { return WnPoolEntry{0, (int)N0, (int)N1, (int)N1}; })) {
+                WnParams q = rows(wn_params(enc->pre, d_x, x_item_stride, x_row_stride, 0, 1));
+                q.lo = 1, q.xs = linear(x_row_stride);
+                q.y0 = p->h[0], q.y0s = ring(p->hW[0]);
+                wn_pool_launch<WN_PRE, 1, 1>(q, t, nz, w, st);
+                ++launches;
+            }
+            for (int i = 0; i < nl; ++i) {
+                // the new columns of h_{i + 1} and skip_i per item; a flush takes every layer up to N', reading zeros from there on
+                const int lam0 = p->lam[i], lam1 = p->lam[i + 1];
+                const int w = table([&](int, long long N0, long long N1, bool flush) {
+                    return WnPoolEntry{0, clamp0(N0 - lam1), flush ? (int)N1 : clamp0(N1 - lam1), flush ? (int)N1 : clamp0(N1 - lam0)};
+                });
+                if (w == 0) continue;
+                WnParams q = rows(wn_params(enc->in_layers[i], p->h[i], (long long)C * p->hW[i], p->hW[i], 0, enc->dil[i]));
+                q.lo = 0, q.xs = ring(p->hW[i]);
+                q.y0 = p->g, q.y0s = linear(p->gW);
+                if (k5 && enc->dil[i] == 1) wn_pool_launch<WN_GATE, 5, 1>(q, t, nz, w, st);
+                else wn_pool_launch<WN_GATE, 0, 0>(q, t, nz, w, st);
+                for (int e = 0; e < nz; ++e) t.e[e].front = t.e[e].end;         // g holds exactly the new columns
+                WnParams r = rows(wn_params(enc->rs_layers[i], p->g, (long long)C * p->gW, p->gW, 0, 1));
+                r.lo = 1, r.xs = linear(p->gW);
+                r.res = p->h[i], r.rs = ring(p->hW[i]);
+                if (i + 1 < nl) r.y0 = p->h[i + 1], r.y0s = ring(p->hW[i + 1]);
+                r.y1 = p->out, r.y1s = ring(p->outW), r.first = i == 0;
+                wn_pool_launch<WN_RES_SKIP, 1, 1>(r, t, nz, w, st);
+                launches += 2;
+            }
+            if (out_cols > 0) {     // every row's out_cols columns: the item's frames [E, E'), then zeros
+                table([&](int item, long long, long long, bool) {
+                    const long long E0 = p->E[(size_t)items[item].session];
+                    return WnPoolEntry{0, (int)E0, (int)(E0 + out_cols), (int)E2[(size_t)item]};
+                });
+                WnParams q = rows(wn_params(enc->proj, p->out, (long long)C * p->outW, p->outW, 0, 1));
+                q.lo = 0, q.xs = ring(p->outW);
+                q.y0s = q.y1s = linear(out_cols);
+                if (cfg.mode == 0) {
+                    q.y0 = d_z;
+                } else {
+                    q.y0 = d_mean, q.y1 = d_logvar, q.z = d_z;
+                    if (cfg.mode == 2) q.bn_scale = enc->d_bn, q.bn_shift = enc->d_bn + cfg.out_channels;
+                }
+                wn_pool_launch<WN_PROJ, 1, 1>(q, t, nz, out_cols, st);
+                ++launches;
+            }
+            return FV_OK;
+        });
+    if (rs != FV_OK) return rs;
+    if (launches) set_last_kernel("wn_pool_kernel");
+    for (int i = 0; i < count; ++i) {
+        const size_t s = (size_t)items[i].session;
+        if (frames_out) frames_out[i] = E2[(size_t)i] - p->E[s];
+        p->N[s] = N2[(size_t)i], p->E[s] = E2[(size_t)i];
+        if (items[i].flush) p->flushed[s] = 1;
+    }
+    p->launches = launches;
+    return FV_OK;
+}
+
+FV_API fv_status fv_wnpool_reset(fv_wnpool* p, int32_t session) {
+    const char* fn = "fv_wnpool_reset";
+    if (!p) {
+        set_error("%s: null pool", fn);
+        return FV_ERR_INVALID;
+    }
+    if (session < 0 || session >= p->S) {
+        set_error("%s: session %d lies outside [0, %d)", fn, session, p->S);
+        return FV_ERR_INVALID;
+    }
+    // the slot's ring rows keep their frames: nothing at or past a frontier, or before frame 0, is ever read
+    p->N[(size_t)session] = p->E[(size_t)session] = 0, p->flushed[(size_t)session] = 0;
+    return FV_OK;
+}
+
+FV_API int64_t fv_wnpool_received(const fv_wnpool* p, int32_t session) { return p && session >= 0 && session < p->S ? p->N[(size_t)session] : -1; }
+
+FV_API int64_t fv_wnpool_emitted(const fv_wnpool* p, int32_t session) { return p && session >= 0 && session < p->S ? p->E[(size_t)session] : -1; }
+
+FV_API int64_t fv_wnpool_pending(const fv_wnpool* p, int32_t session) {
+    return p && session >= 0 && session < p->S ? p->N[(size_t)session] - p->E[(size_t)session] : -1;
+}
+
+FV_API int32_t fv_wnpool_lookahead(const fv_wnpool* p) { return p ? p->enc->reach : -1; }
+
+FV_API int64_t fv_wnpool_max_frames(const fv_wnpool* p) { return p ? (int64_t)p->max_chunk + p->enc->reach : -1; }
+
+FV_API int32_t fv_wnpool_launches(const fv_wnpool* p) { return p ? p->launches : -1; }
+
+FV_API void fv_wnpool_destroy(fv_wnpool* p) { delete p; }
 
 }  // extern "C"

@@ -18,12 +18,14 @@ class SamplePoolCounters:
     """``plan(items)`` says what a step would emit per item and changes nothing; it refuses what the library refuses of the items, in its
     order per item: ``ValueError`` for a session out of range, a duplicate session and samples outside ``[0, max_chunk]``,
     ``PoolStateError`` for a flushed slot, ``ValueError`` past 2^40 samples; then whatever the pool's own rule refuses.  ``commit`` moves the
-    counters as a step that emitted the plan does; ``step`` is both."""
+    counters as a step that emitted the plan does; ``step`` is both.  A pool that counts something else names its unit and its limits
+    (``PosteriorPoolCounters``: frames, chunks up to 2^20, utterances up to 2^30)."""
+    _unit, _chunk_limit, _chunk_limit_name, _length_limit, _length_limit_name = "samples", 1 << 28, "2^28", MAX_SAMPLES, "2^40"
 
     def __init__(self, sessions: int, max_chunk: int):
         self.S, self.max_chunk = int(sessions), int(max_chunk)
-        if not 1 <= self.S <= 65535 or not 1 <= self.max_chunk <= 1 << 28:
-            raise ValueError(f"sessions ({self.S}) must lie in [1, 65535] and max_chunk ({self.max_chunk}) in [1, 2^28]")
+        if not 1 <= self.S <= 65535 or not 1 <= self.max_chunk <= self._chunk_limit:
+            raise ValueError(f"sessions ({self.S}) must lie in [1, 65535] and max_chunk ({self.max_chunk}) in [1, {self._chunk_limit_name}]")
         self.received = [0] * self.S
         self.emitted = [0] * self.S
         self.flushed = [False] * self.S
@@ -46,11 +48,11 @@ class SamplePoolCounters:
                 raise ValueError(f"duplicate session {s} (item {i}): a session appears at most once per step")
             seen.add(s)
             if not 0 <= c <= self.max_chunk:
-                raise ValueError(f"item {i} (session {s}) has {c} samples, outside [0, max_chunk = {self.max_chunk}]")
+                raise ValueError(f"item {i} (session {s}) has {c} {self._unit}, outside [0, max_chunk = {self.max_chunk}]")
             if self.flushed[s]:
                 raise PoolStateError(f"session {s} was flushed (item {i}); reset it before the next utterance")
-            if self.received[s] + c > MAX_SAMPLES:
-                raise ValueError(f"item {i} takes session {s} past 2^40 samples in one utterance")
+            if self.received[s] + c > self._length_limit:
+                raise ValueError(f"item {i} takes session {s} past {self._length_limit_name} {self._unit} in one utterance")
             ends.append(self.received[s] + c)
         emitted, rule = self.emitted, self._emission
         return [rule(i, s, c, flush, N2, emitted[s]) - emitted[s] for i, ((s, c, flush), N2) in enumerate(zip(items, ends))]
