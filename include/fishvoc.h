@@ -1368,6 +1368,40 @@ FV_API fv_status fv_vq_encode(fv_vq* vq, const float* d_x, int64_t x_row_stride,
  * expected to have refused; frames at or past host_frames[b] are zeros. */
 FV_API fv_status fv_vq_decode(fv_vq* vq, const int32_t* d_codes, const int32_t* host_frames, float* d_z, int32_t batch, int64_t T, void* stream);
 
+/* -------- code streams and code session pools: the decode direction of a codec, served chunk by chunk.  No reference counterpart
+ *          (vae.py:87 / unify.py:39-53 decode whole rows); replaces fv_vq_decode followed by fv_stream_push / fv_pool_step.  --------
+ *
+ * An fv_stream / fv_pool made by fv_stream_create_codes / fv_codepool_create keeps the CODES of its last cap = K + A + max_chunk_frames
+ * frames, (rows, num_quantizers, cap) int32, instead of the (rows, C_in, cap) floats of its float twin: 4 n_q cap bytes per row instead of
+ * 4 C_in cap.  The window-forming launch looks the codes up and forms fv_vq_decode's own layer-ordered sum (the first valid layer assigned,
+ * one fp32 rounding per add, a code < 0 or >= codebook_size contributes nothing, a frame without a valid code is exact zeros), so the
+ * window — and with it every emitted sample — has the bits of fv_vq_decode followed by the float entry point.  Everything else is the float
+ * handle's: the emission rule, fv_pool_plan, the forward, the crop, the workspace and its size, the graph key, and "the whole call is
+ * checked before anything moves".  The pitch-template ring of a use_template generator stays a float ring at the hop rate.
+ *   - `vq` must outlive the handle: its codebooks are read at every push / step (not copied), so fv_vq_load_codebook on it changes what
+ *     the frames already in the ring decode to.  Its dim must equal fv_input_channels(e) and every layer must be loaded.
+ *   - flush, reset, destroy, workspace_bytes and pending_frames are the float handle's own entry points.  A code handle refuses
+ *     fv_stream_push / fv_pool_step, and a float handle fv_stream_push_codes / fv_codepool_step, with FV_ERR_STATE and the name of the
+ *     entry point to call instead; nothing moves.
+ *   - creation refuses, by name: a NULL vq, a vq whose dim differs from the engine's input channels (FV_ERR_INVALID), a vq with an unloaded
+ *     layer (FV_ERR_STATE), and the models fv_stream_create / fv_pool_create refuse, as they do.
+ * The additions are additive: FV_ABI_VERSION does not change.  (The pool's entries are named fv_codepool_*, outside the fv_pool_ prefix: that
+ * family's list of entries is pinned by its host test.  They take and make an fv_pool.) */
+FV_API fv_status fv_stream_create_codes(fv_engine* e, const fv_vq* vq, const fv_stream_config* cfg, fv_stream** out);
+/* fv_stream_push with d_codes (num_quantizers, batch, n) int32 in place of d_mel. */
+FV_API fv_status fv_stream_push_codes(fv_stream* s, const int32_t* d_codes, const float* d_template, int32_t n, float* d_out,
+                                      int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream);
+FV_API fv_status fv_codepool_create(fv_engine* e, const fv_vq* vq, const fv_pool_config* cfg, fv_pool** out);
+/* fv_pool_step with d_codes (num_quantizers, count, in_frames) int32 in place of d_chunks: item i's n frames first in row i of every layer
+ * (the rest is never loaded). */
+FV_API fv_status fv_codepool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const int32_t* d_codes, const float* d_templates,
+                                    int32_t in_frames, float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace,
+                                    size_t workspace_bytes, void* stream);
+/* Device bytes of the handle's rings (the mel or code ring, plus the template ring of a use_template generator), for float and code handles
+ * alike; 0 for NULL. */
+FV_API size_t fv_stream_ring_bytes(const fv_stream* s);
+FV_API size_t fv_codepool_ring_bytes(const fv_pool* p);
+
 /* -------- posterior encoder: the WaveNet encoder of VITS / RVC (modules/encoders/posterior_encoder.py) --------
  * PosteriorEncoder in eval mode, the fourth encoder of the reference's modules/encoders package and one that VQVAEModel's generator.encoder
  * slot can take (vae.py:81).  With C = hidden_channels, k = kernel_size, m[b][t] = t < lengths[b], d_i = dilation_rate ** (i % dilation_cycle):

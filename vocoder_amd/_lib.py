@@ -78,6 +78,7 @@ EXPORTS = (
     "fv_oscpool_step", "fv_oscpool_reset", "fv_oscpool_destroy",
     "fv_pair_wino4_tile", "fv_pair_wino4_pack",
     "fv_vq_create", "fv_vq_destroy", "fv_vq_load_codebook", "fv_vq_set_slices", "fv_vq_workspace_bytes", "fv_vq_encode", "fv_vq_decode",
+    "fv_stream_create_codes", "fv_stream_push_codes", "fv_codepool_create", "fv_codepool_step", "fv_stream_ring_bytes", "fv_codepool_ring_bytes",
     "fv_posterior_create", "fv_posterior_load_weight", "fv_posterior_finalize", "fv_posterior_reach_frames", "fv_posterior_output_channels",
     "fv_posterior_workspace_bytes", "fv_posterior_forward", "fv_posterior_destroy",
     "fv_wnstream_create", "fv_wnstream_push", "fv_wnstream_flush", "fv_wnstream_reset", "fv_wnstream_pending", "fv_wnstream_lookahead",
@@ -538,6 +539,18 @@ def lib() -> ctypes.CDLL:
     L.fv_vq_encode.restype = _i32
     L.fv_vq_decode.argtypes = [vp, vp, i32p, vp, _i32, i64, vp]
     L.fv_vq_decode.restype = _i32
+    L.fv_stream_create_codes.argtypes = [vp, vp, ctypes.POINTER(StreamConfig), ctypes.POINTER(vp)]
+    L.fv_stream_create_codes.restype = _i32
+    L.fv_stream_push_codes.argtypes = [vp, vp, vp, _i32, vp, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_stream_push_codes.restype = _i32
+    L.fv_codepool_create.argtypes = [vp, vp, ctypes.POINTER(PoolConfig), ctypes.POINTER(vp)]
+    L.fv_codepool_create.restype = _i32
+    L.fv_codepool_step.argtypes = [vp, pip, _i32, vp, vp, _i32, vp, _i32, i64p, vp, ctypes.c_size_t, vp]
+    L.fv_codepool_step.restype = _i32
+    L.fv_stream_ring_bytes.argtypes = [vp]
+    L.fv_stream_ring_bytes.restype = ctypes.c_size_t
+    L.fv_codepool_ring_bytes.argtypes = [vp]
+    L.fv_codepool_ring_bytes.restype = ctypes.c_size_t
     L.fv_posterior_create.argtypes = [ctypes.POINTER(PosteriorConfig), ctypes.POINTER(vp)]
     L.fv_posterior_create.restype = _i32
     L.fv_posterior_load_weight.argtypes = [vp, cp, fp, i64p, _i32]

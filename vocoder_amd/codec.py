@@ -7,6 +7,10 @@ drop-in modules, every stage on the HIP engine; the quantiser is ``modules.quant
 
     python -m vocoder_amd.codec encode -i a.wav -o out/ [--checkpoint ckpt]      # writes out/a.codes.npy, int64 (n_q, T) or (T,)
     python -m vocoder_amd.codec decode -i out/a.codes.npy -o out/                 # writes out/a.wav
+    python -m vocoder_amd.codec decode -i out/a.codes.npy -o out/ --chunk-frames 64     # through decode_stream, 64 frames a push
+
+``decode_stream`` / ``decode_pool`` serve the decode direction chunk by chunk (``CodecDecodeStream``, ``CodecDecodePool``): the ring in front of
+the decoder keeps the codes, not the latent.
 
 The architecture defaults to configs/model/vqvae.yaml's (vocos-small-vae at 24000_2048_3072, 512 latent channels, 4096 codes, one
 quantiser); ``vocoder_amd.inference``'s command line is untouched.
@@ -69,6 +73,14 @@ class VQVAECodec(nn.Module):
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
         y = self.decoder(self.vq.from_codes(codes)[0])
         return y[:, None, :] if y.ndim == 2 else y
+
+    def decode_stream(self, batch: int = 1, max_chunk_frames: int = 64) -> "CodecDecodeStream":
+        """``decode`` chunk by chunk (``CodecDecodeStream``): codes in, audio out after the decoder's lookahead; the rings keep codes."""
+        return CodecDecodeStream(self.decoder, self.vq, batch, max_chunk_frames)
+
+    def decode_pool(self, sessions: int, max_chunk_frames: int = 64) -> "CodecDecodePool":
+        """``decode`` for ``sessions`` clients that advance at their own pace (``CodecDecodePool``): one step serves any subset of them."""
+        return CodecDecodePool(self.decoder, self.vq, sessions, max_chunk_frames)
 
     def forward(self, audio: torch.Tensor, mask=None):
         """vae.py:80-109: ``(fake_audio, 0)``, trimmed / zero-padded to the input's length, which it may miss by a hop at most."""
@@ -221,6 +233,152 @@ class CodecEncodeStream:
         self.close()
 
 
+def _decoder_stages(decoder: nn.Module, vq, what: str) -> list:
+    """The engine modules codes pass through on their way to audio: ``[decoder]`` for a single engine (a ``HiFiGANGenerator``, a head alone),
+    ``[backbone, head]`` for a ``UnifyGenerator`` with a backbone; ``what`` (``decode_stream`` / ``decode_pool``) refuses the others by name."""
+    from .modules.generators.unify import UnifyGenerator
+    if vq is None:
+        raise ValueError(f"{what}: there is no quantiser to decode the codes with")
+    if isinstance(decoder, UnifyGenerator):
+        if decoder.vq is not None:
+            raise ValueError(f"{what}: the decoder is a UnifyGenerator with a quantiser of its own; call its own {what}()")
+        stages = [decoder.backbone, decoder.head]
+    else:
+        stages = [decoder]
+    for m in stages:
+        if not (hasattr(m, "code_stream") and hasattr(m, "session_pool")):
+            raise ValueError(f"{what}: {type(m).__name__} has no engine to stream on (it is not one of the package's engine modules)")
+    return stages
+
+
+class CodecDecodeStream:
+    """``VQVAECodec.decode`` for a live client: ``push(codes (B, c) or (n_q, B, c))``, ``c <= max_chunk_frames``, returns the audio
+    ``(B, C_out, k * hop)`` of the frames that are final, ``k`` possibly 0; ``flush()`` ends the utterance and returns the rest; ``reset()``
+    starts the next one.  The first stage is a ``CodeStream``: its ring keeps the codes, and its window is decoded from them in the launch
+    that forms it — no ``from_codes`` launch, no latent tensor.  A two-stage decoder (``UnifyGenerator`` with a backbone) feeds the
+    backbone's frames to ``head.stream()`` on the device; ``lookahead_frames`` is the sum of the stages'.  Every call's output has the bits of
+    the same chain on float streams fed ``vq.from_codes``.  ``template`` (a use_template generator) goes to a single-engine decoder."""
+
+    def __init__(self, decoder: nn.Module, vq, batch: int = 1, max_chunk_frames: int = 64):
+        stages = _decoder_stages(decoder, vq, "decode_stream")
+        self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
+        self.codes = stages[0].code_stream(vq, self.batch, self.max_chunk_frames)
+        self.head = None
+        if len(stages) == 2:
+            # one backbone call emits at most max_chunk_frames frames (a push) or its lookahead (the flush)
+            self._head_chunk = max(self.max_chunk_frames, self.codes.lookahead_frames, 1)
+            self.head = stages[1].stream(self.batch, self._head_chunk)
+        last = self.head or self.codes
+        self.hop, self.out_channels = last.hop * (self.codes.hop if self.head else 1), last.out_channels
+        self.lookahead_frames = self.codes.lookahead_frames + (self.head.lookahead_frames if self.head else 0)
+
+    @property
+    def received_frames(self) -> int:
+        return self.codes.received_frames
+
+    @property
+    def emitted_frames(self) -> int:
+        return (self.head or self.codes).emitted_frames
+
+    @property
+    def ring_bytes(self) -> int:
+        return self.codes.ring_bytes + (self.head.ring_bytes if self.head else 0)
+
+    def push(self, codes: torch.Tensor, template: torch.Tensor | None = None, validate: bool = True) -> torch.Tensor:
+        if self.head is None:
+            return self.codes.push(codes, template, validate)
+        if template is not None:
+            raise ValueError("CodecDecodeStream.push: a template belongs to a single-engine decoder")
+        self.head._check_open()
+        return self.head.push(self.codes.push(codes, validate=validate))
+
+    def flush(self) -> torch.Tensor:
+        if self.head is None:
+            return self.codes.flush()
+        self.head._check_open()
+        rest = self.codes.flush()
+        return torch.cat([self.head.push(rest), self.head.flush()], dim=2)
+
+    def reset(self) -> None:
+        self.codes.reset()
+        if self.head is not None:
+            self.head.reset()
+
+    def close(self) -> None:
+        self.codes.close()
+        if self.head is not None:
+            self.head.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
+class CodecDecodePool:
+    """``VQVAECodec.decode`` for clients that advance independently: ``step(items)`` takes ``(session, codes, flush)`` tuples — ``codes``:
+    ``(n,)`` or ``(n_q, n)`` with ``n <= max_chunk_frames``, or ``None``; ``flush``: the utterance ends with them — and returns one audio
+    tensor ``(C_out, k * hop)`` per item, ``k`` possibly 0.  The first stage is a ``CodeSessionPool``: a slot's ring keeps ``n_q`` int32 per
+    frame, not the latent's channels.  A two-stage decoder hands the backbone pool's padded frames to ``head.session_pool()``'s
+    ``step_padded`` on the device; both stages are planned before either is launched, so a refused step moves neither pool.
+    ``reset(session)`` starts a slot's next utterance."""
+
+    def __init__(self, decoder: nn.Module, vq, sessions: int, max_chunk_frames: int = 64):
+        stages = _decoder_stages(decoder, vq, "decode_pool")
+        self.sessions, self.max_chunk_frames = int(sessions), int(max_chunk_frames)
+        self.codes = stages[0].code_pool(vq, self.sessions, self.max_chunk_frames)
+        self.head = None
+        if len(stages) == 2:
+            # an item that ends its utterance emits its own frames and the backbone's lookahead in one step
+            self.head = stages[1].session_pool(self.sessions, self.max_chunk_frames + self.codes.lookahead_frames)
+        last = self.head or self.codes
+        self.hop, self.out_channels = last.hop * (self.codes.hop if self.head else 1), last.out_channels
+        self.lookahead_frames = self.codes.lookahead_frames + (self.head.lookahead_frames if self.head else 0)
+
+    def received_frames(self, session: int) -> int:
+        return self.codes.received_frames(session)
+
+    def emitted_frames(self, session: int) -> int:
+        return (self.head or self.codes).emitted_frames(session)
+
+    @property
+    def ring_bytes(self) -> int:
+        return self.codes.ring_bytes + (self.head.ring_bytes if self.head else 0)
+
+    def step(self, items, validate: bool = True) -> list:
+        cp, hp = self.codes, self.head
+        cp._check_open()
+        if hp is None:
+            return cp.step(items, validate)
+        hp._check_open()
+        meta, chunks, tmpl = cp.gather(items, validate)
+        if tmpl is not None:
+            raise ValueError("CodecDecodePool.step: a template belongs to a single-engine decoder")
+        frames = cp.state.plan(meta).emit_frames                  # both plans before either launch: a refusal moves neither pool
+        head_items = [(s, k, flush) for (s, _, flush), k in zip(meta, frames)]
+        hp.state.plan(head_items)
+        z, emit = cp.step_padded(meta, chunks)
+        out, emit = hp.step_padded(head_items, z if z.numel() else None)
+        return [out[i, :, :k * hp.hop] for i, k in enumerate(emit)]
+
+    def reset(self, session: int) -> None:
+        self.codes.reset(session)
+        if self.head is not None:
+            self.head.reset(session)
+
+    def close(self) -> None:
+        self.codes.close()
+        if self.head is not None:
+            self.head.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
 def build_vqvae(n_fft: int = 3072, hop_length: int = 2048, win_length: int = 3072, latent_size: int = 512, codebook_size: int = 4096,
                 num_quantizers: int = 1, encoder_depths=(6,), encoder_dims=(512,), decoder_depths=(6, 3), decoder_dims=(512, 1024),
                 kernel_size: int = 7, encoder: str = "convnext", hidden_channels: int = 192, posterior_layers: int = 16,
@@ -271,10 +429,17 @@ def main(argv=None):
     ap.add_argument("--hidden-channels", type=int, default=192, help="--encoder posterior: the WaveNet's width")
     ap.add_argument("--chunk-samples", type=int, default=None,
                     help="encode: run the file through encode_stream in chunks of this many samples (same codes; needs --encoder posterior)")
+    ap.add_argument("--chunk-frames", type=int, default=None,
+                    help="decode: run the codes through decode_stream in chunks of this many frames (the rings keep codes)")
     a = ap.parse_args(argv)
+    if a.chunk_frames is not None:
+        if a.mode != "decode":
+            ap.error("--chunk-frames belongs to decode: encode streams samples (--chunk-samples)")
+        if a.chunk_frames < 1:
+            ap.error(f"--chunk-frames = {a.chunk_frames} must be at least 1")
     if a.chunk_samples is not None:
         if a.mode != "encode":
-            ap.error("--chunk-samples belongs to encode: there is no decode stream")
+            ap.error("--chunk-samples belongs to encode: decode streams frames of codes (--chunk-frames)")
         if a.encoder != "posterior":
             ap.error("--chunk-samples needs --encoder posterior: the ConvNeXt encoder's stream is not bit-exact, so its codes could differ "
                      "from a whole-file encode")
@@ -309,7 +474,12 @@ def main(argv=None):
     else:
         codes = torch.from_numpy(np.load(src)).to(torch.int64).cuda()
         codes = codes[:, None, :] if codes.dim() == 2 else codes[None, :]
-        audio = model.decode(codes)
+        if a.chunk_frames is None:
+            audio = model.decode(codes)
+        else:
+            with model.decode_stream(1, a.chunk_frames) as st:
+                parts = [st.push(codes[..., n:n + a.chunk_frames]) for n in range(0, codes.shape[-1], a.chunk_frames)]
+                audio = torch.cat(parts + [st.flush()], dim=2)
         stem = src.name[: -len(".codes.npy")] if src.name.endswith(".codes.npy") else src.stem
         dst = out / f"{stem}.wav"
         write_wav(dst, audio[0, 0].cpu().numpy(), a.sample_rate)

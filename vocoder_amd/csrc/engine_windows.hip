@@ -222,12 +222,19 @@ struct RingWindows {
     bool tmpl = false;            // use_template generator: a template ring at the hop rate beside the mel ring
     float* ring = nullptr;        // (rows, C_in, cap), then (rows, 1, cap * hop) for the template: the only device allocation
     float* ring_tmpl = nullptr;
+    // The code form (fv_stream_create_codes / fv_codepool_create): the ring holds (rows, n_q, cap) int32 codes in place of the C_in floats
+    // per frame, and the window-forming launch decodes them with `vq`'s codebooks (vq.hip); everything else is the float form's.
+    const fv_vq* vq = nullptr;
+    int n_q = 0;
+    size_t ring_bytes = 0;        // of the rings' contents (the allocation rounds the first ring up to 256 bytes)
+    int32_t* ring_codes() const { return (int32_t*)ring; }
     WindowWorkspace ws;           // sized for rows x cap frames, and the forward's own workspace for the largest window at batch `rows`
     ~RingWindows() {
         if (ring) (void)hipFree(ring);
     }
     // For `fn`, which calls its rows `rows_name`, past its create_preamble (`hop` is set); context / lookahead: -1 = the reach
-    fv_status create(fv_engine* e_, const char* fn, const char* rows_name, int rows_, int max_chunk_, int context, int lookahead) {
+    fv_status create(fv_engine* e_, const char* fn, const char* rows_name, int rows_, int max_chunk_, int context, int lookahead,
+                     const fv_vq* vq_ = nullptr, int n_q_ = 0) {
         const int R = e_->reach_frames();
         if (rows_ < 1 || max_chunk_ < 1 || context < -1 || lookahead < -1) {
             set_error("%s: %s (%d) and max_chunk_frames (%d) must be >= 1, context_frames (%d) and lookahead_frames (%d) >= 0 "
@@ -253,12 +260,37 @@ struct RingWindows {
             if (const fv_status r = admit_window(e, fn, "stream", hop, rows, W, &model_bytes)) return r;
         const size_t n = (size_t)rows * (size_t)cap;
         ws = WindowWorkspace(n, cin, cout, hop, tmpl, model_bytes);
-        const size_t n_ring = align_up(n * cin, 64), n_ring_tmpl = tmpl ? n * hop : 0;
+        vq = vq_;
+        n_q = n_q_;
+        const size_t ring_ch = vq ? (size_t)n_q : (size_t)cin;   // 4-byte entries per frame of the ring
+        const size_t n_ring = align_up(n * ring_ch, 64), n_ring_tmpl = tmpl ? n * hop : 0;
+        ring_bytes = (n * ring_ch + n_ring_tmpl) * sizeof(float);
         FV_HIP_CHECK(hipMalloc((void**)&ring, (n_ring + n_ring_tmpl) * sizeof(float)));
         ring_tmpl = tmpl ? ring + n_ring : nullptr;
         return FV_OK;
     }
 };
+
+// What fv_stream_create_codes / fv_codepool_create (`fn`) check past their create_preamble: the quantiser, and that it decodes to the
+// engine's input channels.
+static fv_status admit_vq(const fv_engine* e, const char* fn, const fv_vq* vq, int* n_q) {
+    int dim = 0;
+    if (const fv_status r = vq_describe(fn, vq, &dim, n_q)) return r;
+    if (dim != fv_input_channels(e)) {
+        set_error("%s: vq decodes to dim = %d channels, but the engine takes %d input channels", fn, dim, fv_input_channels(e));
+        return FV_ERR_INVALID;
+    }
+    return FV_OK;
+}
+// A call of the wrong kind on a handle (`fn` on a ring of codes, or its _codes twin on a ring of floats): refused before anything moves
+static fv_status check_ring_kind(const RingWindows* h, bool codes_call, const char* fn, const char* float_fn, const char* codes_fn) {
+    if ((h->vq != nullptr) == codes_call) return FV_OK;
+    if (h->vq)
+        set_error("%s: this handle keeps a ring of codes (it was made by a _create_codes entry point): call %s", fn, codes_fn);
+    else
+        set_error("%s: this handle keeps a ring of floats, not of codes: call %s", fn, float_fn);
+    return FV_ERR_STATE;
+}
 
 // The emission rule, of a stream and of each session of a pool alike: n more frames arrive at the counters (F, E); the frames [E, E2) are
 // emitted out of one forward over the window [w, F2) (vocoder_amd/streaming.py restates it in Python).
@@ -287,34 +319,37 @@ struct fv_stream : RingWindows {
     int32_t first_row = 0;
 };
 
-static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_template, int32_t n, bool flush, float* d_out,
+// d_in: the chunk — (B, C_in, n) floats, or with `codes` (n_q, B, n) int32 codes for a stream that keeps a ring of codes
+static fv_status stream_step(fv_stream* st, const void* d_in, bool codes, const float* d_template, int32_t n, bool flush, float* d_out,
                              int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = flush ? "fv_stream_flush" : "fv_stream_push";
+    const char* fn = flush ? "fv_stream_flush" : codes ? "fv_stream_push_codes" : "fv_stream_push";
     if (frames_out) *frames_out = 0;
     if (!st || !frames_out) {
         set_error("%s: null argument", fn);
         return FV_ERR_INVALID;
     }
+    if (!flush)
+        if (const fv_status r = check_ring_kind(st, codes, fn, "fv_stream_push", "fv_stream_push_codes")) return r;
     if (st->flushed) {
         set_error("%s: the stream was flushed; fv_stream_reset it before the next utterance", fn);
         return FV_ERR_STATE;
     }
     if (!flush) {
         if (n < 0 || n > st->max_chunk) {
-            set_error("fv_stream_push: %d frames, more than max_chunk_frames = %d of this stream", n, st->max_chunk);
+            set_error("%s: %d frames, more than max_chunk_frames = %d of this stream", fn, n, st->max_chunk);
             return FV_ERR_INVALID;
         }
         if (n == 0) return FV_OK;
-        if (!d_mel) {
-            set_error("fv_stream_push: null mel chunk");
+        if (!d_in) {
+            set_error("%s: null %s chunk", fn, codes ? "code" : "mel");
             return FV_ERR_INVALID;
         }
         if (st->tmpl && !d_template) {
-            set_error("fv_stream_push: the generator was built with use_template=True and every push needs a template chunk (B, 1, n*hop)");
+            set_error("%s: the generator was built with use_template=True and every push needs a template chunk (B, 1, n*hop)", fn);
             return FV_ERR_INVALID;
         }
         if (!st->tmpl && d_template) {
-            set_error("fv_stream_push: template given but the generator was built with use_template=False");
+            set_error("%s: template given but the generator was built with use_template=False", fn);
             return FV_ERR_INVALID;
         }
     }
@@ -339,8 +374,12 @@ static fv_status stream_step(fv_stream* st, const float* d_mel, const float* d_t
     if (!flush || emit) {
         // the chunk into the ring at F mod cap, and the window [w, F) beside it; a flush has no chunk (n = 0: the window comes from the ring alone)
         const int64_t nc = flush ? 0 : n, W = F - w;
-        FV_PROF(s, "stream_window", 0.0, 4.0 * B * st->cin * (2.0 * nc + (emit ? 2.0 * W : 0.0)),
-                launch_stream_window(d_mel, st->ring, emit ? win.in : nullptr, B, st->cin, st->cap, st->F, nc, w, s));
+        if (st->vq)   // the ring holds codes: the window is decoded from them on the way (W x n_q codes in, W x C_in floats out)
+            FV_PROF(s, "stream_window_codes", 0.0, 4.0 * B * (st->n_q * (2.0 * nc + (emit ? 1.0 * W : 0.0)) + (emit ? 1.0 * W * st->cin * (1 + st->n_q) : 0.0)),
+                    launch_stream_window_codes(st->vq, (const int*)d_in, st->ring_codes(), emit ? win.in : nullptr, B, st->cap, st->F, nc, w, s));
+        else
+            FV_PROF(s, "stream_window", 0.0, 4.0 * B * st->cin * (2.0 * nc + (emit ? 2.0 * W : 0.0)),
+                    launch_stream_window((const float*)d_in, st->ring, emit ? win.in : nullptr, B, st->cin, st->cap, st->F, nc, w, s));
         if (st->tmpl)
             FV_PROF(s, "stream_window", 0.0, 4.0 * B * hop * (2.0 * nc + (emit ? 2.0 * W : 0.0)),
                     launch_stream_window(d_template, st->ring_tmpl, emit ? win.tmpl : nullptr, B, 1, st->cap * hop, st->F * hop, nc * hop, w * hop, s));
@@ -368,10 +407,14 @@ FV_API int32_t fv_reach_frames(const fv_engine* e) {
     return e->reach_frames();
 }
 
-FV_API fv_status fv_stream_create(fv_engine* e, const fv_stream_config* cfg, fv_stream** out) {
+static fv_status stream_create(fv_engine* e, const fv_vq* vq, bool codes, const fv_stream_config* cfg, fv_stream** out) {
+    const char* fn = codes ? "fv_stream_create_codes" : "fv_stream_create";
     std::unique_ptr<fv_stream> st(new fv_stream());
-    if (const fv_status r = create_preamble(e, cfg, out, "fv_stream_create", "stream", &st->hop)) return r;
-    if (const fv_status r = st->create(e, "fv_stream_create", "batch", cfg->batch, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames))
+    if (const fv_status r = create_preamble(e, cfg, out, fn, "stream", &st->hop)) return r;
+    int n_q = 0;
+    if (codes)
+        if (const fv_status r = admit_vq(e, fn, vq, &n_q)) return r;
+    if (const fv_status r = st->create(e, fn, "batch", cfg->batch, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames, vq, n_q))
         return r;
     if (e->cfg.model == FV_MODEL_REFINEGAN) {
         st->seeded = true;
@@ -382,17 +425,30 @@ FV_API fv_status fv_stream_create(fv_engine* e, const fv_stream_config* cfg, fv_
     return FV_OK;
 }
 
+FV_API fv_status fv_stream_create(fv_engine* e, const fv_stream_config* cfg, fv_stream** out) { return stream_create(e, nullptr, false, cfg, out); }
+
+FV_API fv_status fv_stream_create_codes(fv_engine* e, const fv_vq* vq, const fv_stream_config* cfg, fv_stream** out) {
+    return stream_create(e, vq, true, cfg, out);
+}
+
+FV_API size_t fv_stream_ring_bytes(const fv_stream* s) { return s ? s->ring_bytes : 0; }
+
 FV_API size_t fv_stream_workspace_bytes(const fv_stream* s) { return s ? s->ws.bytes() : 0; }
 
 FV_API int64_t fv_stream_pending_frames(const fv_stream* s) { return s ? s->F - s->E : 0; }
 
 FV_API fv_status fv_stream_push(fv_stream* s, const float* d_mel, const float* d_template, int32_t n, float* d_out, int64_t* frames_out,
                                 void* d_workspace, size_t workspace_bytes, void* stream) {
-    return stream_step(s, d_mel, d_template, n, false, d_out, frames_out, d_workspace, workspace_bytes, stream);
+    return stream_step(s, d_mel, false, d_template, n, false, d_out, frames_out, d_workspace, workspace_bytes, stream);
+}
+
+FV_API fv_status fv_stream_push_codes(fv_stream* s, const int32_t* d_codes, const float* d_template, int32_t n, float* d_out,
+                                      int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream) {
+    return stream_step(s, d_codes, true, d_template, n, false, d_out, frames_out, d_workspace, workspace_bytes, stream);
 }
 
 FV_API fv_status fv_stream_flush(fv_stream* s, float* d_out, int64_t* frames_out, void* d_workspace, size_t workspace_bytes, void* stream) {
-    return stream_step(s, nullptr, nullptr, 0, true, d_out, frames_out, d_workspace, workspace_bytes, stream);
+    return stream_step(s, nullptr, false, nullptr, 0, true, d_out, frames_out, d_workspace, workspace_bytes, stream);
 }
 
 FV_API fv_status fv_stream_reset(fv_stream* s) {
@@ -770,15 +826,19 @@ FV_API int32_t fv_pool_plan(const fv_pool_config* cfg, const int64_t* received, 
     return (int32_t)p.rows.size();
 }
 
-FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool** out) {
+static fv_status pool_create(fv_engine* e, const fv_vq* vq, bool codes, const fv_pool_config* cfg, fv_pool** out) {
+    const char* fn = codes ? "fv_codepool_create" : "fv_pool_create";
     std::unique_ptr<fv_pool> p(new fv_pool());
-    if (const fv_status r = create_preamble(e, cfg, out, "fv_pool_create", "stream", &p->hop)) return r;
+    if (const fv_status r = create_preamble(e, cfg, out, fn, "stream", &p->hop)) return r;
     if (e->cfg.model == FV_MODEL_REFINEGAN) {
-        set_error("fv_pool_create: this model cannot run session pools: the sessions of a RefineGAN pool advance to per-row origins, and its "
-                  "seeded AdaIN noise takes one (origin, stride) per launch");
+        set_error("%s: this model cannot run session pools: the sessions of a RefineGAN pool advance to per-row origins, and its "
+                  "seeded AdaIN noise takes one (origin, stride) per launch", fn);
         return FV_ERR_UNSUPPORTED;
     }
-    if (const fv_status r = p->create(e, "fv_pool_create", "sessions", cfg->sessions, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames))
+    int n_q = 0;
+    if (codes)
+        if (const fv_status r = admit_vq(e, fn, vq, &n_q)) return r;
+    if (const fv_status r = p->create(e, fn, "sessions", cfg->sessions, cfg->max_chunk_frames, cfg->context_frames, cfg->lookahead_frames, vq, n_q))
         return r;
     const size_t S = (size_t)p->rows;
     p->F.assign(S, 0);
@@ -790,43 +850,54 @@ FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool
     return FV_OK;
 }
 
+FV_API fv_status fv_pool_create(fv_engine* e, const fv_pool_config* cfg, fv_pool** out) { return pool_create(e, nullptr, false, cfg, out); }
+
+FV_API fv_status fv_codepool_create(fv_engine* e, const fv_vq* vq, const fv_pool_config* cfg, fv_pool** out) {
+    return pool_create(e, vq, true, cfg, out);
+}
+
+FV_API size_t fv_codepool_ring_bytes(const fv_pool* p) { return p ? p->ring_bytes : 0; }
+
 FV_API size_t fv_pool_workspace_bytes(const fv_pool* p) { return p ? p->ws.bytes() : 0; }
 
 FV_API int64_t fv_pool_pending_frames(const fv_pool* p, int32_t session) {
     return p && session >= 0 && session < p->rows ? p->F[(size_t)session] - p->E[(size_t)session] : 0;
 }
 
-FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const float* d_chunks, const float* d_templates,
-                              int32_t in_frames, float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace,
-                              size_t workspace_bytes, void* stream) {
+// d_chunks: (count, C_in, in_frames) floats, or with `codes` (n_q, count, in_frames) int32 codes for a pool that keeps rings of codes
+static fv_status pool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const void* d_chunks, bool codes, const float* d_templates,
+                           int32_t in_frames, float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace,
+                           size_t workspace_bytes, void* stream) {
+    const char* fn = codes ? "fv_codepool_step" : "fv_pool_step";
     if (!p || count < 0 || (count > 0 && !items) || in_frames < 0 || out_frames < 0) {
-        set_error("fv_pool_step: null argument, or a negative count, in_frames or out_frames");
+        set_error("%s: null argument, or a negative count, in_frames or out_frames", fn);
         return FV_ERR_INVALID;
     }
     // ---- the whole step is checked before any counter moves or anything is enqueued ----
+    if (const fv_status st = check_ring_kind(p, codes, fn, "fv_pool_step", "fv_codepool_step")) return st;
     PoolPlan& pl = p->plan;
-    if (const fv_status st = pool_plan("fv_pool_step", p->rows, p->max_chunk, p->K, p->A, p->F.data(), p->E.data(), p->flushed.data(), items, count,
+    if (const fv_status st = pool_plan(fn, p->rows, p->max_chunk, p->K, p->A, p->F.data(), p->E.data(), p->flushed.data(), items, count,
                                        in_frames, out_frames, pl))
         return st;
     bool any_frames = false;
     for (int i = 0; i < count; ++i) any_frames |= items[i].frames > 0;
     if (any_frames && !d_chunks) {
-        set_error("fv_pool_step: null chunk buffer, but an item of this step has frames");
+        set_error("%s: null chunk buffer, but an item of this step has frames", fn);
         return FV_ERR_INVALID;
     }
     if (any_frames && p->tmpl && !d_templates) {
-        set_error("fv_pool_step: the generator was built with use_template=True and every chunk needs a template chunk (count, 1, in_frames*hop)");
+        set_error("%s: the generator was built with use_template=True and every chunk needs a template chunk (count, 1, in_frames*hop)", fn);
         return FV_ERR_INVALID;
     }
     if (!p->tmpl && d_templates) {
-        set_error("fv_pool_step: template given but the generator was built with use_template=False");
+        set_error("%s: template given but the generator was built with use_template=False", fn);
         return FV_ERR_INVALID;
     }
     if (count > 0 && out_frames > 0 && !d_out) {
-        set_error("fv_pool_step: null output (out_frames = %d)", out_frames);
+        set_error("%s: null output (out_frames = %d)", fn, out_frames);
         return FV_ERR_INVALID;
     }
-    if (const fv_status st = p->ws.check("fv_pool_step", "fv_pool_workspace_bytes", d_workspace, workspace_bytes)) return st;
+    if (const fv_status st = p->ws.check(fn, "fv_pool_workspace_bytes", d_workspace, workspace_bytes)) return st;
     fv_engine* e = p->e;
     const WindowWorkspace::Parts win = p->ws.carve(d_workspace);
     const int G = (int)pl.group_rows.size();
@@ -860,8 +931,12 @@ FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t cou
                     p->crop.push_back({i, -1, 0, 0});
                 }
         const int ng = (int)p->gather.size(), nc = (int)p->crop.size();
-        FV_PROF(s, "pool_gather", 0.0, 8.0 * rows * p->cin * Wg,
-                launch_pool_gather(d_chunks, p->ring, win.in, p->gather.data(), ng, p->cin, p->cap, in_frames, Wg, 1, s));
+        if (p->vq)   // the rings hold codes: the group's tensor is decoded from them on the way
+            FV_PROF(s, "pool_gather_codes", 0.0, 4.0 * rows * Wg * (p->n_q + (double)p->cin * (1 + p->n_q)),
+                    launch_pool_gather_codes(p->vq, (const int*)d_chunks, p->ring_codes(), win.in, p->gather.data(), ng, count, p->cap, in_frames, Wg, s));
+        else
+            FV_PROF(s, "pool_gather", 0.0, 8.0 * rows * p->cin * Wg,
+                    launch_pool_gather((const float*)d_chunks, p->ring, win.in, p->gather.data(), ng, p->cin, p->cap, in_frames, Wg, 1, s));
         if (p->tmpl)
             FV_PROF(s, "pool_gather", 0.0, 8.0 * rows * Wg * hop,
                     launch_pool_gather(d_templates, p->ring_tmpl, win.tmpl, p->gather.data(), ng, 1, p->cap, in_frames, Wg, hop, s));
@@ -889,6 +964,18 @@ FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t cou
         if (items[i].flush) p->flushed[sess] = 1;
     }
     return FV_OK;
+}
+
+FV_API fv_status fv_pool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const float* d_chunks, const float* d_templates,
+                              int32_t in_frames, float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace,
+                              size_t workspace_bytes, void* stream) {
+    return pool_step(p, items, count, d_chunks, false, d_templates, in_frames, d_out, out_frames, frames_out, d_workspace, workspace_bytes, stream);
+}
+
+FV_API fv_status fv_codepool_step(fv_pool* p, const fv_pool_item* items, int32_t count, const int32_t* d_codes, const float* d_templates,
+                                    int32_t in_frames, float* d_out, int32_t out_frames, int64_t* frames_out, void* d_workspace,
+                                    size_t workspace_bytes, void* stream) {
+    return pool_step(p, items, count, d_codes, true, d_templates, in_frames, d_out, out_frames, frames_out, d_workspace, workspace_bytes, stream);
 }
 
 FV_API fv_status fv_pool_reset(fv_pool* p, int32_t session) {

@@ -447,6 +447,14 @@ fv_status launch_pool_gather(const float* chunk, float* ring, float* win, const 
 // out_stride: columns between the rows of `out` (0: out_frames * hop, rows back to back)
 fv_status launch_pool_crop(const float* y, float* out, const PoolCropEntry* tab, int count, int C, long long Ly, long long out_frames,
                            int hop, hipStream_t s, long long out_stride = 0);
+// code rings (fv_stream_push_codes, fv_codepool_step; vq.hip, beside vq_gather_kernel): the twins of launch_stream_window / launch_pool_gather
+// for a ring of codes — chunk (n_q, rows, n) int32 -> ring (rows, n_q, cap) int32, and win (rows, D, .) = fv_vq_decode's sum of the window's codes.
+// vq_describe: what a code handle checks at creation (`fn` names the caller): a quantiser with every layer loaded -> its dim and n_q.
+fv_status vq_describe(const char* fn, const fv_vq* vq, int* dim, int* n_q);
+fv_status launch_stream_window_codes(const fv_vq* vq, const int* chunk, int* ring, float* win, int B, long long cap, long long c0, long long n,
+                                     long long w, hipStream_t s);
+fv_status launch_pool_gather_codes(const fv_vq* vq, const int* chunk, int* ring, float* win, const PoolGatherEntry* tab, int count, int items,
+                                   long long cap, long long in_frames, long long Wg, hipStream_t s);
 // sample streams (sample_stream.h): next[b][i] = sample next_origin + i of row b, i < count, where `N` samples have arrived before this call — from
 // chunk[b][idx - N] at or after N, from prev[b][idx - prev_origin] before it, 0.0f before the utterance's start; prev and next are two buffers
 // of row stride `stride`

@@ -306,6 +306,124 @@ __global__ __launch_bounds__(256) void vq_gather_kernel(const int* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Code rings (engine_windows.hip fv_stream_push_codes / fv_codepool_step): stream_window_kernel and pool_gather_kernel
+// (window_kernels.hip) for a session that keeps the CODES of its last `cap` frames, (rows, n_q, cap) int32 with frame f at slot f mod cap,
+// and forms the generator's input window by looking them up: win[row][d][j] = ((e_0[c_0][d] + e_1[c_1][d]) + ...) of the window's column j,
+// vq_gather_kernel's sum (layer order, the first valid layer assigned, a code < 0 or >= K contributes nothing, no valid code: exact zeros).
+// A workgroup owns kVqSelFrames window columns x kVqSelD channels (blockIdx.y: the channel slice).  The codes of its columns come from the
+// chunk at or after the old F and from the ring before it; slice 0 alone files the chunk's codes in the ring.  W <= cap, so the slots read and
+// the slots written are distinct and no launch reads a code it wrote.  Every layer's row e_q[c] is read along d (a wave reads 64 consecutive
+// floats of one row) into the padded tile and summed along the columns (lane = column), the direction in which the window is contiguous.
+// ---------------------------------------------------------------------------------------------
+struct CodeTile {
+    float tile[kVqSelFrames][kVqSelD + 1];
+    int code[kVqMaxLayers][kVqSelFrames];     // -1: nothing to add (no such column, or a code outside [0, K))
+};
+
+// The sum of the tile's columns over the layers; sh.code is filled and a barrier has been passed.  out(dd, v): channel d0 + dd of column
+// threadIdx.x & 31 is v.
+template <class Out>
+__device__ __forceinline__ void code_tile_sum(CodeTile& sh, const VqLayerPtrs& layers, int n_q, int D, int d0, Out&& out) {
+    const int f = threadIdx.x & 31, dsub = threadIdx.x >> 5;
+    const int lane = threadIdx.x & 63, lrow = threadIdx.x >> 6;
+    float acc[8];
+    bool has = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+    for (int q = 0; q < n_q; ++q) {
+        if (q) __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int fr = lrow + 4 * i;
+            const int c = sh.code[q][fr];
+            sh.tile[fr][lane] = (c >= 0 && d0 + lane < D) ? layers.embed[q][(long long)c * D + d0 + lane] : 0.f;
+        }
+        __syncthreads();
+        if (sh.code[q][f] >= 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = has ? acc[i] + sh.tile[f][dsub + 8 * i] : sh.tile[f][dsub + 8 * i];
+            has = true;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out(dsub + 8 * i, acc[i]);
+}
+
+__device__ __forceinline__ int code_or_none(int c, int K) { return c >= 0 && c < K ? c : -1; }
+
+// chunk (n_q, B, n): the columns [c0, c0 + n); win (B, D, W): the columns [w, w + W), W = c0 + n - w (NULL: the chunk goes into the ring only)
+__global__ __launch_bounds__(256) void stream_window_codes_kernel(const int* __restrict__ chunk, int* __restrict__ ring, float* __restrict__ win,
+                                                                  VqLayerPtrs layers, int n_q, int D, int K, int B, long long cap,
+                                                                  long long c0, long long n, long long w, long long W, int b0) {
+    __shared__ CodeTile sh;
+    const int b = b0 + blockIdx.z;
+    const long long j0 = (long long)blockIdx.x * kVqSelFrames;
+    for (int idx = threadIdx.x; idx < n_q * kVqSelFrames; idx += 256) {
+        const int q = idx >> 5, fr = idx & 31;
+        const long long j = j0 + fr, f = w + j;
+        int c = -1;
+        if (j < W) {
+            int* slot = ring + ((long long)b * n_q + q) * cap + f % cap;
+            if (f >= c0) {
+                c = chunk[((long long)q * B + b) * n + (f - c0)];
+                if (blockIdx.y == 0) *slot = c;
+            } else {
+                c = *slot;
+            }
+        }
+        sh.code[q][fr] = code_or_none(c, K);
+    }
+    if (!win) return;
+    __syncthreads();
+    const int d0 = blockIdx.y * kVqSelD;
+    const long long j = j0 + (threadIdx.x & 31);
+    code_tile_sum(sh, layers, n_q, D, d0, [&](int dd, float v) {
+        if (j < W && d0 + dd < D) win[((long long)b * D + d0 + dd) * W + j] = v;
+    });
+}
+
+// chunk (n_q, items, in_frames), row e.item of every layer; win (rows, D, Wg): entry e's window at [col0, col0 + W), 0.0f elsewhere; an entry
+// without a row (row < 0) only files its chunk in the ring (pool_gather_kernel's rule, counted in frames: hop = 1)
+__global__ __launch_bounds__(256) void pool_gather_codes_kernel(const int* __restrict__ chunk, int* __restrict__ ring, float* __restrict__ win,
+                                                                const PoolGatherBlock tab, VqLayerPtrs layers, int n_q, int D, int K, int items,
+                                                                long long cap, long long in_frames, long long Wg) {
+    __shared__ CodeTile sh;
+    const PoolGatherEntry e = tab.e[blockIdx.z];
+    const long long j0 = (long long)blockIdx.x * kVqSelFrames;
+    if (e.row < 0) {
+        if (blockIdx.y != 0) return;
+        for (int idx = threadIdx.x; idx < n_q * kVqSelFrames; idx += 256) {
+            const int q = idx >> 5;
+            const long long j = j0 + (idx & 31);
+            if (j < e.n) ring[((long long)e.slot * n_q + q) * cap + (e.F + j) % cap] = chunk[((long long)q * items + e.item) * in_frames + j];
+        }
+        return;
+    }
+    if (j0 >= Wg) return;      // (a launch spans its longest chunk where that is longer than the group's tensor)
+    for (int idx = threadIdx.x; idx < n_q * kVqSelFrames; idx += 256) {
+        const int q = idx >> 5, fr = idx & 31;
+        const long long jj = j0 + fr - e.col0, f = e.w + jj;
+        int c = -1;
+        if (jj >= 0 && jj < e.W) {
+            int* slot = ring + ((long long)e.slot * n_q + q) * cap + f % cap;
+            if (f >= e.F) {
+                c = chunk[((long long)q * items + e.item) * in_frames + (f - e.F)];
+                if (blockIdx.y == 0) *slot = c;
+            } else {
+                c = *slot;
+            }
+        }
+        sh.code[q][fr] = code_or_none(c, K);
+    }
+    __syncthreads();
+    const int d0 = blockIdx.y * kVqSelD;
+    const long long j = j0 + (threadIdx.x & 31);
+    code_tile_sum(sh, layers, n_q, D, d0, [&](int dd, float v) {
+        if (j < Wg && d0 + dd < D) win[((long long)e.row * D + d0 + dd) * Wg + j] = v;      // outside the entry's window: no code, v = 0.0f
+    });
+}
+
 size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
@@ -329,6 +447,65 @@ struct fv_vq {
         }
     }
 };
+
+namespace fv {
+
+fv_status vq_describe(const char* fn, const fv_vq* vq, int* dim, int* n_q) {
+    if (!vq) {
+        set_error("%s: null vq (the quantiser whose codebooks the code ring is decoded with)", fn);
+        return FV_ERR_INVALID;
+    }
+    for (int q = 0; q < vq->cfg.num_quantizers; ++q)
+        if (!vq->loaded[q]) {
+            set_error("%s: the codebook of layer %d of vq has not been loaded (fv_vq_load_codebook)", fn, q);
+            return FV_ERR_STATE;
+        }
+    *dim = vq->cfg.dim;
+    *n_q = vq->cfg.num_quantizers;
+    return FV_OK;
+}
+
+static VqLayerPtrs vq_layer_ptrs(const fv_vq* vq) {
+    VqLayerPtrs lp{};
+    for (int q = 0; q < vq->cfg.num_quantizers; ++q) lp.embed[q] = vq->d_embed[q];
+    return lp;
+}
+
+fv_status launch_stream_window_codes(const fv_vq* vq, const int* chunk, int* ring, float* win, int B, long long cap, long long c0, long long n,
+                                     long long w, hipStream_t s) {
+    const long long W = c0 + n - w;
+    if (W <= 0) return FV_OK;
+    const int D = vq->cfg.dim;
+    const unsigned slices = win ? (unsigned)((D + kVqSelD - 1) / kVqSelD) : 1u;
+    constexpr long long kMaxZ = 65535;
+    for (long long b0 = 0; b0 < B; b0 += kMaxZ) {
+        const unsigned nz = (unsigned)std::min<long long>(kMaxZ, (long long)B - b0);
+        hipLaunchKernelGGL(stream_window_codes_kernel, dim3((unsigned)((W + kVqSelFrames - 1) / kVqSelFrames), slices, nz), dim3(256), 0, s, chunk,
+                           ring, win, vq_layer_ptrs(vq), vq->cfg.num_quantizers, D, vq->cfg.codebook_size, B, cap, c0, n, w, W, (int)b0);
+        FV_HIP_CHECK(hipGetLastError());
+    }
+    return FV_OK;
+}
+
+fv_status launch_pool_gather_codes(const fv_vq* vq, const int* chunk, int* ring, float* win, const PoolGatherEntry* tab, int count, int items,
+                                   long long cap, long long in_frames, long long Wg, hipStream_t s) {
+    const int D = vq->cfg.dim;
+    const VqLayerPtrs lp = vq_layer_ptrs(vq);
+    return for_each_launch_table<PoolGatherBlock>(count, tab, [&](const PoolGatherBlock& blk, int, int nz) {
+        long long X = 0;   // columns this launch spans: the group's tensor for a row, the chunk for a ring-only entry
+        bool rows = false;
+        for (int i = 0; i < nz; ++i) {
+            X = std::max(X, blk.e[i].row >= 0 ? Wg : (long long)blk.e[i].n);
+            rows |= blk.e[i].row >= 0;
+        }
+        if (X > 0)
+            hipLaunchKernelGGL(pool_gather_codes_kernel, dim3((unsigned)((X + kVqSelFrames - 1) / kVqSelFrames), rows ? (unsigned)((D + kVqSelD - 1) / kVqSelD) : 1u, nz),
+                               dim3(256), 0, s, chunk, ring, win, blk, lp, vq->cfg.num_quantizers, D, vq->cfg.codebook_size, items, cap, in_frames, Wg);
+        return FV_OK;
+    });
+}
+
+}  // namespace fv
 
 namespace {
 

@@ -68,6 +68,69 @@ class _EngineHandle(_Handle):
         return int(getattr(self._lib, self._ws_getter)(self._h))
 
 
+def code_chunk(codes, num_quantizers: int, rows: "int | None", max_chunk_frames: int, what: str) -> "tuple[torch.Tensor, int]":
+    """The checks every chunk of codes passes before it reaches a code ring -> ``(codes as (n, rows, c), c)``.  ``codes``: int64 or int32,
+    ``(rows, c)`` or ``(n, rows, c)`` with ``1 <= n <= num_quantizers`` layers (the first ``n``, as ``from_codes`` takes them); ``rows=None``: a
+    pool item's ``(c,)`` or ``(n, c)``, returned as ``(n, 1, c)``.  Dtype, shape and size are refused first, on any device; the device last."""
+    if not isinstance(codes, torch.Tensor):
+        raise TypeError(f"{what}: expected a tensor of codes, got {type(codes).__name__}")
+    if codes.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"{what}: expected int64 or int32 codes, got {codes.dtype}")
+    if rows is None:
+        codes, rows, shape = codes.unsqueeze(-2), 1, "(c,) or (n_q, c)"
+    else:
+        shape = f"({rows}, c) or (n_q, {rows}, c)"
+    if codes.dim() == 2:
+        codes = codes[None]
+    if codes.dim() != 3 or codes.shape[1] != rows:
+        raise ValueError(f"{what}: expected codes of shape {shape}, got {tuple(codes.shape)}")
+    if not 1 <= codes.shape[0] <= num_quantizers:
+        raise ValueError(f"{what}: {codes.shape[0]} layers of codes for a quantiser of {num_quantizers} (n_q leads: {shape})")
+    c = int(codes.shape[2])
+    if c > max_chunk_frames:
+        raise ValueError(f"{what}: a chunk of {c} frames, more than max_chunk_frames = {max_chunk_frames}")
+    if not codes.is_cuda:
+        raise RuntimeError(f"{what}: expected codes on a HIP device, got '{codes.device}'; vocoder_amd has no CPU path")
+    return codes, c
+
+
+def _validate_codes(codes: torch.Tensor, codebook_size: int, what: str) -> None:
+    """The one host check (a synchronisation), as ``from_codes`` makes it: every code lies in ``[-1, codebook_size)``."""
+    if codes.numel():
+        lo, hi = int(codes.min()), int(codes.max())
+        if lo < -1 or hi >= codebook_size:
+            raise IndexError(f"{what}: code {hi if hi >= codebook_size else lo} is out of range for a codebook of {codebook_size} "
+                             "(-1: no code)")
+
+
+class _CodeRing:
+    """What ``CodeStream`` and ``CodeSessionPool`` share: the quantiser's library handle, which the ring reads at every call and which must
+    therefore be alive — reloading or moving the quantiser module rebuilds it, and the handle then refuses its calls."""
+
+    def _attach_vq(self, vq, device, where: str) -> None:
+        if not (hasattr(vq, "engine") and hasattr(vq, "num_quantizers") and hasattr(vq, "codebook_size")):
+            raise TypeError(f"{where}: vq must be a vocoder_amd.modules.quantizers quantiser, got {type(vq).__name__}")
+        if vq.training:
+            raise RuntimeError(f"{type(vq).__name__} is inference-only: call .eval() first")
+        self.num_quantizers, self.codebook_size = int(vq.num_quantizers), int(vq.codebook_size)
+        self._vq_engine = vq.engine(device)
+
+    def _vq_handle(self) -> ctypes.c_void_p:
+        h = self._vq_engine.handle
+        if not h.value:
+            raise FishVocError(_lib.FV_ERR_STATE, f"{type(self).__name__}: the quantiser was reloaded or moved since this handle was made "
+                               "(its codebooks are read at every call): create a new one")
+        return h
+
+    def _int32(self, codes: torch.Tensor, rows: int, c: int) -> torch.Tensor:
+        """``(n, rows, c)`` codes -> contiguous int32 ``(num_quantizers, rows, c)`` on the device, the missing layers -1."""
+        if codes.shape[0] == self.num_quantizers:
+            return codes.to(torch.int32).contiguous()
+        c32 = torch.full((self.num_quantizers, rows, c), -1, dtype=torch.int32, device=codes.device)
+        c32[:codes.shape[0]] = codes
+        return c32
+
+
 def post_activation_to_act(act) -> tuple[int, float]:
     """``post_activation()`` of the reference ctor (hifigan.py:150,213: any nn.Module factory) -> (fv_act, slope).  The element-wise modules
     that have a kernel form map onto ``fv_act``; anything else raises NotImplementedError naming what is accepted."""
@@ -433,6 +496,22 @@ class Engine(_Handle):
         self._streams.add(p)
         return p
 
+    def code_stream(self, vq, batch: int, max_chunk_frames: int, context_frames: int | None = None,
+                    lookahead_frames: int | None = None) -> "CodeStream":
+        """``stream()`` for an engine that follows the quantiser ``vq`` (``CodeStream``): pushes take codes, the ring keeps codes, and the
+        output has the bits of ``stream().push(vq.from_codes(codes)[0])``."""
+        st = CodeStream(self, vq, batch, max_chunk_frames, context_frames, lookahead_frames)
+        self._streams.add(st)
+        return st
+
+    def code_pool(self, vq, sessions: int, max_chunk_frames: int, context_frames: int | None = None,
+                  lookahead_frames: int | None = None) -> "CodeSessionPool":
+        """``session_pool()`` for an engine that follows the quantiser ``vq`` (``CodeSessionPool``): ``num_quantizers`` int32 per frame and
+        slot instead of ``C_in`` floats."""
+        p = CodeSessionPool(self, vq, sessions, max_chunk_frames, context_frames, lookahead_frames)
+        self._streams.add(p)
+        return p
+
     def ragged_plan(self, lengths, t_max: int | None = None, launch_frames: int = 0, max_groups: int = 0) -> "RaggedPlan":
         """The plan of a ragged batch (``RaggedPlan``; the rule: ``vocoder_amd.ragged``) for ``lengths[b]`` valid frames per clip inside a
         ``(B, C_in, t_max)`` input (``t_max`` defaults to the longest clip).  Reuse it for every call with these lengths."""
@@ -578,18 +657,28 @@ class Stream(_EngineHandle):
     _destroy, _ws_getter = "fv_stream_destroy", "fv_stream_workspace_bytes"
     _closed = ("this stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
                "the module): create a new stream")
+    _where, _push_entry = "Engine.stream", "fv_stream_push"
 
     def __init__(self, engine: Engine, batch: int, max_chunk_frames: int, context_frames: int | None = None,
                  lookahead_frames: int | None = None):
-        self._attach(engine, "Engine.stream")
+        self._attach(engine, self._where)
         cfg = _lib.StreamConfig(int(batch), int(max_chunk_frames), -1 if context_frames is None else int(context_frames),
                                 -1 if lookahead_frames is None else int(lookahead_frames))
         with torch.cuda.device(engine.device):
-            check(self._lib.fv_stream_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h)))
+            check(self._create(engine, cfg))
             self._alloc_workspace()
         self.batch = int(batch)
         self._ring_attrs(max_chunk_frames, context_frames, lookahead_frames)
         self._F = self._E = 0
+
+    def _create(self, engine: Engine, cfg) -> int:
+        return self._lib.fv_stream_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h))
+
+    @property
+    def ring_bytes(self) -> int:
+        """Device bytes of the stream's rings (fv_stream_ring_bytes): its only allocation beside the workspace."""
+        self._check_open()
+        return int(self._lib.fv_stream_ring_bytes(self._h))
 
     # -- counters (host-side: reading them never synchronises) --
     @property
@@ -631,7 +720,7 @@ class Stream(_EngineHandle):
             def launch(stream: int) -> int:
                 ws = (self._ws.data_ptr(), self._ws.numel() * 4, stream)
                 return (self._lib.fv_stream_flush(self._h, optr, got, *ws) if flush else
-                        self._lib.fv_stream_push(self._h, mel.data_ptr(), tptr, n, optr, got, *ws))
+                        getattr(self._lib, self._push_entry)(self._h, mel.data_ptr(), tptr, n, optr, got, *ws))
             self._engine._enqueue(dev, launch, owner=self)
         out = _emit((self.batch, self.out_channels, k * self.hop), k, dev, enqueue,
                     "stream emitted {got} frames where the emission rule says {k}")
@@ -643,6 +732,39 @@ class Stream(_EngineHandle):
         self._check_open()
         check(self._lib.fv_stream_reset(self._h))
         self._F = self._E = 0
+
+
+class CodeStream(_CodeRing, Stream):
+    """A ``Stream`` fed with the CODES of a quantiser instead of its decoded frames (``fv_stream_create_codes``, include/fishvoc.h): the ring
+    keeps ``num_quantizers`` int32 per frame in place of ``C_in`` floats, and the launch that forms the generator's window looks the codes up.
+    ``push(codes)`` returns the bits ``Stream.push(vq.from_codes(codes)[0])`` returns.  ``codes``: int64 or int32, ``(B, c)`` or
+    ``(n, B, c)`` with the first ``n <= num_quantizers`` layers; ``validate=True`` raises ``IndexError`` for a code outside
+    ``[-1, codebook_size)`` as ``from_codes`` does, at the price of a synchronisation — with ``validate=False`` such a code contributes nothing.
+    ``flush``, ``reset``, ``close`` and the counters are the stream's.  The quantiser's codebooks are read at every push: reloading or moving
+    the quantiser module closes the handle they live in, and the stream then refuses its calls."""
+    _where, _push_entry = "Engine.code_stream", "fv_stream_push_codes"
+
+    def __init__(self, engine: Engine, vq, batch: int, max_chunk_frames: int, context_frames: int | None = None,
+                 lookahead_frames: int | None = None):
+        self._attach_vq(vq, engine.device, self._where)
+        super().__init__(engine, batch, max_chunk_frames, context_frames, lookahead_frames)
+
+    def _create(self, engine: Engine, cfg) -> int:
+        return self._lib.fv_stream_create_codes(engine._h, self._vq_handle(), ctypes.byref(cfg), ctypes.byref(self._h))
+
+    def push(self, codes: torch.Tensor, template: torch.Tensor | None = None, validate: bool = True) -> torch.Tensor:
+        self._check_open()
+        self._vq_handle()
+        codes, c = code_chunk(codes, self.num_quantizers, self.batch, self.max_chunk_frames, "CodeStream.push")
+        if validate:
+            _validate_codes(codes, self.codebook_size, "CodeStream.push")
+        template, tptr = _exact(template, "CodeStream.push template", "a template chunk", (self.batch, 1, c * self.hop))
+        return self._call(self._int32(codes, self.batch, c), tptr, c, flush=False)
+
+    def flush(self) -> torch.Tensor:
+        self._check_open()
+        self._vq_handle()
+        return super().flush()
 
 
 class LogMelStream(_EngineHandle):
@@ -807,18 +929,37 @@ class SessionPool(_EngineHandle):
     _destroy, _ws_getter = "fv_pool_destroy", "fv_pool_workspace_bytes"
     _closed = ("this session pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or "
                ".to() on the module): create a new pool")
+    _where, _step_entry = "Engine.session_pool", "fv_pool_step"
 
     def __init__(self, engine: Engine, sessions: int, max_chunk_frames: int, context_frames: int | None = None,
                  lookahead_frames: int | None = None):
-        self._attach(engine, "Engine.session_pool")
+        self._attach(engine, self._where)
         cfg = _lib.PoolConfig(int(sessions), int(max_chunk_frames), -1 if context_frames is None else int(context_frames),
                               -1 if lookahead_frames is None else int(lookahead_frames))
         with torch.cuda.device(engine.device):
-            check(self._lib.fv_pool_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h)))
+            check(self._create(engine, cfg))
             self._alloc_workspace()
         self.sessions = int(sessions)
         self._ring_attrs(max_chunk_frames, context_frames, lookahead_frames)
         self.state = _sessions.PoolState(self.sessions, self.max_chunk_frames, self.context_frames, self.lookahead_frames)
+
+    def _create(self, engine: Engine, cfg) -> int:
+        return self._lib.fv_pool_create(engine._h, ctypes.byref(cfg), ctypes.byref(self._h))
+
+    @property
+    def ring_bytes(self) -> int:
+        """Device bytes of the pool's rings (fv_codepool_ring_bytes): its only allocation beside the workspace."""
+        self._check_open()
+        return int(self._lib.fv_codepool_ring_bytes(self._h))
+
+    def _chunk_frames(self, chunks: "torch.Tensor | None", count: int) -> int:
+        """The check of ``step_padded``'s chunk buffer -> its frames per row (0 without one)."""
+        if chunks is None:
+            return 0
+        _require_cuda(chunks, "SessionPool.step_padded")
+        if chunks.dim() != 3 or chunks.shape[0] != count or chunks.shape[1] != self.in_channels or not chunks.is_contiguous():
+            raise ValueError(f"expected contiguous chunks of shape ({count}, {self.in_channels}, in_frames), got {tuple(chunks.shape)}")
+        return int(chunks.shape[2])
 
     # -- counters (host-side: reading them never synchronises) --
     def received_frames(self, session: int) -> int:
@@ -870,12 +1011,7 @@ class SessionPool(_EngineHandle):
         self._check_open()
         items = [(int(s), int(n), bool(f)) for s, n, f in items]
         count = len(items)
-        in_frames = 0
-        if chunks is not None:
-            _require_cuda(chunks, "SessionPool.step_padded")
-            if chunks.dim() != 3 or chunks.shape[0] != count or chunks.shape[1] != self.in_channels or not chunks.is_contiguous():
-                raise ValueError(f"expected contiguous chunks of shape ({count}, {self.in_channels}, in_frames), got {tuple(chunks.shape)}")
-            in_frames = int(chunks.shape[2])
+        in_frames = self._chunk_frames(chunks, count)
         _, tptr = _exact(templates, "SessionPool.step_padded templates", "contiguous templates", (count, 1, in_frames * self.hop),
                          make_contiguous=False)
         plan = self.state.plan(items)                             # sizes the output before anything is launched; refuses what the library would
@@ -887,7 +1023,7 @@ class SessionPool(_EngineHandle):
         out_frames = int(out.shape[2]) // self.hop
         arr = (_lib.PoolItem * max(count, 1))(*[_lib.PoolItem(s, n, int(f)) for s, n, f in items])
         got = (ctypes.c_int64 * max(count, 1))()
-        self._engine._enqueue(dev, lambda stream: self._lib.fv_pool_step(
+        self._engine._enqueue(dev, lambda stream: getattr(self._lib, self._step_entry)(
             self._h, arr, count, chunks.data_ptr() if chunks is not None and chunks.numel() else None,
             tptr if count and in_frames else None, in_frames, out.data_ptr() if out.numel() else None, out_frames, got, self._ws.data_ptr(),
             self._ws.numel() * 4, stream), owner=self)
@@ -902,6 +1038,75 @@ class SessionPool(_EngineHandle):
         self._check_open()
         check(self._lib.fv_pool_reset(self._h, int(session)))
         self.state.reset(int(session))
+
+
+class CodeSessionPool(_CodeRing, SessionPool):
+    """A ``SessionPool`` fed with the CODES of a quantiser (``fv_codepool_create``, include/fishvoc.h): every slot's ring keeps
+    ``num_quantizers`` int32 per frame in place of ``C_in`` floats — the pool's size per slot, which bounds the number of sessions — and the
+    gather launch of a step looks the codes up.  ``step(items)`` takes ``(session, codes, flush)`` or ``(session, codes, flush, template)``
+    tuples, ``codes``: int64 or int32 ``(n,)`` or ``(layers, n)`` with ``n <= max_chunk_frames``, or ``None``; each item's audio has the bits a
+    ``SessionPool`` stepped with ``vq.from_codes`` of the same items gives.  ``validate`` as in ``CodeStream.push``.  The plan, the counters,
+    ``reset`` and ``close`` are the pool's."""
+    _where, _step_entry = "Engine.code_pool", "fv_codepool_step"
+
+    def __init__(self, engine: Engine, vq, sessions: int, max_chunk_frames: int, context_frames: int | None = None,
+                 lookahead_frames: int | None = None):
+        self._attach_vq(vq, engine.device, self._where)
+        super().__init__(engine, sessions, max_chunk_frames, context_frames, lookahead_frames)
+
+    def _create(self, engine: Engine, cfg) -> int:
+        return self._lib.fv_codepool_create(engine._h, self._vq_handle(), ctypes.byref(cfg), ctypes.byref(self._h))
+
+    def _chunk_frames(self, chunks: "torch.Tensor | None", count: int) -> int:
+        if chunks is None:
+            return 0
+        shape = (self.num_quantizers, count)
+        if (not isinstance(chunks, torch.Tensor) or not chunks.is_cuda or chunks.dtype != torch.int32 or chunks.dim() != 3
+                or tuple(chunks.shape[:2]) != shape or not chunks.is_contiguous()):
+            raise ValueError(f"expected contiguous int32 codes of shape {shape + ('in_frames',)} on the device, got "
+                             f"{tuple(chunks.shape) if isinstance(chunks, torch.Tensor) else type(chunks).__name__}")
+        return int(chunks.shape[2])
+
+    def gather(self, items, validate: bool = True):
+        """``step``'s items -> ``(the (session, n, flush) integers, the padded int32 codes (num_quantizers, count, longest) or None, the padded
+        templates or None)``: what ``step_padded`` takes.  Nothing moves."""
+        items = [(it[0], it[1], it[2] if len(it) > 2 else False, it[3] if len(it) > 3 else None) for it in map(tuple, items)]
+        dev = self._engine.device
+        meta, rows = [], []
+        for s, codes, flush, tt in items:
+            n = 0
+            if codes is not None:
+                codes, n = code_chunk(codes, self.num_quantizers, None, self.max_chunk_frames, "CodeSessionPool.step")
+                if validate:
+                    _validate_codes(codes, self.codebook_size, "CodeSessionPool.step")
+                _exact(tt, "CodeSessionPool.step template", "a template chunk", (1, n * self.hop))
+            rows.append(codes)
+            meta.append((int(s), n, bool(flush)))
+        in_frames = max((n for _, n, _ in meta), default=0)
+        chunks = tmpl = None
+        if in_frames:
+            chunks = torch.full((self.num_quantizers, len(items), in_frames), -1, dtype=torch.int32, device=dev)
+            if any(tt is not None for _, codes, _, tt in items if codes is not None):
+                tmpl = torch.zeros((len(items), 1, in_frames * self.hop), dtype=torch.float32, device=dev)
+            for i, ((_, _, _, tt), codes) in enumerate(zip(items, rows)):
+                if codes is not None and codes.shape[2]:
+                    chunks[:codes.shape[0], i, :codes.shape[2]] = codes[:, 0]
+                    if tt is not None:
+                        tmpl[i, :, :tt.shape[1]] = tt
+        return meta, chunks, tmpl
+
+    def step(self, items, validate: bool = True) -> list[torch.Tensor]:
+        self._check_open()
+        out, emit = self.step_padded(*self.gather(items, validate))
+        return [out[i, :, :k * self.hop] for i, k in enumerate(emit)]
+
+    def step_padded(self, items, chunks: torch.Tensor | None, templates: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None) -> tuple[torch.Tensor, list[int]]:
+        """``SessionPool.step_padded`` with ``chunks``: contiguous int32 codes ``(num_quantizers, count, in_frames)``, item i's ``n`` frames
+        first in row i of every layer (the rest is never read).  The codes are not validated here: one outside ``[0, codebook_size)``
+        contributes nothing."""
+        self._vq_handle()
+        return super().step_padded(items, chunks, templates, out)
 
 
 class RaggedPlan(_EngineHandle):

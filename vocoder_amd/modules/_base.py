@@ -121,6 +121,15 @@ class EngineModule(nn.Module):
         the engine like ``stream()``."""
         return self._ragged_engine("session_pool").session_pool(sessions, max_chunk_frames, **kw)
 
+    def code_stream(self, vq, batch: int = 1, max_chunk_frames: int = 64, **kw):
+        """``stream()`` for a module that follows the quantiser ``vq`` (``vocoder_amd.engine.CodeStream``): ``push(codes)`` keeps the codes in
+        the ring and returns the bits of ``stream().push(vq.from_codes(codes)[0])``."""
+        return self._ragged_engine("code_stream").code_stream(vq, batch, max_chunk_frames, **kw)
+
+    def code_pool(self, vq, sessions: int = 1, max_chunk_frames: int = 64, **kw):
+        """``session_pool()`` for a module that follows the quantiser ``vq`` (``vocoder_amd.engine.CodeSessionPool``)."""
+        return self._ragged_engine("code_pool").code_pool(vq, sessions, max_chunk_frames, **kw)
+
     def _ragged_engine(self, what: str):
         p = next(self.parameters(), None)
         if p is None or not p.is_cuda:

@@ -9,7 +9,8 @@ restated from encodec's specification (the package is not a dependency, so parit
     r_0 = x;  c_q = search(r_q, embed_q);  r_{q+1} = r_q - e_{c_q};  z = ((e_{c_0} + e_{c_1}) + ...)
 
 A frame's scores are formed in an order that depends on ``dim`` alone: its codes and ``z`` have the same bits alone, in any batch and under
-any chunking along T, so ``head.stream().push(vq.from_codes(codes[..., a:b])[0])`` streams a decode.  Not built: EMA updates, k-means init,
+any chunking along T, so a decode streams: ``module.code_stream(vq, ...)`` / ``code_pool`` keep the codes in the ring and return the bits of
+``module.stream().push(vq.from_codes(codes[..., a:b])[0])`` (``VQVAECodec.decode_stream`` / ``decode_pool``).  Not built: EMA updates, k-means init,
 dead-code expiry, the straight-through estimator, the commitment loss (returned as zeros) and ``project_in`` / ``project_out``
 (``codebook_dim != dim`` is refused).  No CPU fallback.
 """
