@@ -1632,6 +1632,54 @@ FV_API fv_status fv_mms_interpolate(const float* d_x, int64_t F, int32_t H, cons
  * F < 1, N < 1 or j outside [0, N). */
 FV_API int64_t fv_mms_nearest_index(int64_t F, int64_t N, int64_t j);
 
+/* -------- ConvNeXt backbone, layer by layer and chunk by chunk (fv_cnxstream_*) --------
+ * What fv_wnstream_* is to the posterior encoder, for an FV_MODEL_CONVNEXT engine with kernel_size 7 (p = 3).  `batch` rows advance in
+ * lockstep.  Level 0 is the stem conv, levels 1 .. L the blocks (L = sum of depths); R = p (L + 1) is the lookahead — the backbone's own
+ * reach, fv_reach_frames less the 2 frames of margin that engine's windows keep.  With N frames received and E emitted: a push of c frames
+ * sets N += c, E' = max(E, N - R) and writes the frames [E, E'); the flush sets E' = N and writes the rest, at most R frames; afterwards
+ * pushes are refused (FV_ERR_STATE) until fv_cnxstream_reset.
+ *   After a call level l has produced its output on [0, flush ? N : max(0, N - p (l + 1))), and the call ran every level over the columns
+ * that are new at that level (none: no launch).  A block keeps the last 6 columns of its input in a ring of its own — (batch, dim, cap), cap
+ * the power of two >= 6 + S, S = max(max_chunk, R), slot = frame & (cap - 1) — and its depthwise conv + LayerNorm runs in the stream form of
+ * the whole-row tile kernel: frames below the input's old frontier come from the ring, the call's new frames from the level below, frames
+ * before 0 and past the frontier are zeros by predicate (an uninitialised or stale ring is never read), and the same launch files the new
+ * frames into the ring.  The stem conv runs over the last 6 input frames ++ the chunk; everything per-frame (LayerNorms, the pointwise
+ * convs) runs the whole-row kernels over the new columns.  Every launch takes its kernel from the layer's shape alone.
+ *   The claim: the concatenated frames are BIT-identical to fv_forward over the whole utterance with fv_set_batch_invariant(e, 1), under any
+ * chunking and for any batch, for utterances with max(dims) * T < 2^28 (past that the whole-row forward leaves the tile kernel).  One
+ * narrowing: where input_channels == dims[0] the stem is a C -> C k = 7 conv, which the batch-invariant forward runs as Winograd tap groups
+ * under FV_CONV_ALGO_AUTO; a Winograd output's bits depend on where its pair / quad lies in the launch, so the stream runs the stem as
+ * direct sums and its bits are those of fv_forward with fv_set_conv_algorithm(e, FV_CONV_ALGO_DIRECT) as well (the default decoder backbone,
+ * 512 -> 512; for the default encoder, 513 -> 512, the algorithm setting changes nothing).  The claim is about the shipped whole-row
+ * path, the depthwise tile kernel: the experiment switch FV_OLD_DWLN sends the whole-row forward to the register kernel, which sums the
+ * channels in another order, while the stream always runs the tile body (FV_DWLN_NG8 moves both launches alike, FV_DWLN_RR changes no sum).
+ *   A call neither synchronises nor allocates nor copies to the host.  All device state is allocated at create; fv_cnxstream_state_bytes
+ * reports it.  The stream reads the engine's weights: destroy it before the engine.  A refused call changes no counter. */
+typedef struct fv_cnxstream fv_cnxstream;
+/* Refused by name: an engine that is not finalized or in f16x3 precision (FV_ERR_STATE); a model other than FV_MODEL_CONVNEXT,
+ * kernel_size != 7, a stage wider than 1024 channels, batch outside [1, 65535], max_chunk outside [1, 2^16] (FV_ERR_INVALID). */
+FV_API fv_status fv_cnxstream_create(fv_engine* e, int32_t batch, int32_t max_chunk, fv_cnxstream** out);
+/* d_x: frame t of channel ch of row b at d_x[b * x_batch_stride + ch * x_row_stride + t], x_row_stride >= c (a slice along T passes as it
+ * is); c in [0, max_chunk], d_x may be NULL when c = 0.  d_y: (batch, out_channels, y_row_stride), y_row_stride >= E' - E, frame E + j in
+ * column j; may be NULL when the call emits nothing.  *emitted (may be NULL) receives E' - E.  At most 2^30 frames per utterance. */
+FV_API fv_status fv_cnxstream_push(fv_cnxstream* s, const float* d_x, int64_t x_batch_stride, int64_t x_row_stride, int32_t c, float* d_y,
+                                   int64_t y_row_stride, int64_t* emitted, void* stream);
+FV_API fv_status fv_cnxstream_flush(fv_cnxstream* s, float* d_y, int64_t y_row_stride, int64_t* emitted, void* stream);
+/* N = E = 0 for the next utterance; no device work (nothing a ring holds from the last one is read). */
+FV_API fv_status fv_cnxstream_reset(fv_cnxstream* s);
+/* N - E; -1 for NULL. */
+FV_API int64_t fv_cnxstream_pending(const fv_cnxstream* s);
+/* R; -1 for NULL. */
+FV_API int32_t fv_cnxstream_lookahead(const fv_cnxstream* s);
+/* Bytes of device memory the stream holds; -1 for NULL. */
+FV_API int64_t fv_cnxstream_state_bytes(const fv_cnxstream* s);
+FV_API void fv_cnxstream_destroy(fv_cnxstream* s);
+/* Pure host: the plan of one level of a call that takes a stream of `levels` blocks from N0 to N1 frames (flush: N1 == N0 and the utterance
+ * ends), as the engine computes it.  out[0..5] = in0, in1, out0, out1 and, for level 0 (the stem), the window's width and the column of
+ * out0 in it; for a block, the workgroups per row and the first frame workgroup 1 files (-1 with fewer than two).  Returns the ring's
+ * slots for max_chunk, or -1 for arguments outside 0 <= N0 <= N1, 0 <= level <= levels, max_chunk >= 1, out != NULL. */
+FV_API int32_t fv_cnxstream_plan(int64_t N0, int64_t N1, int32_t flush, int32_t level, int32_t max_chunk, int32_t levels, int64_t* out);
+
 /* -------- per-launch timing (measurement aid; bench.py's roofline leg) --------
  * Between fv_profile_begin and fv_profile_end every kernel that fv_forward enqueues is bracketed by hipEvents recorded
  * on the launch stream.  fv_profile_end synchronises them and writes a JSON array

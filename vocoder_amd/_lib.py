@@ -87,6 +87,8 @@ EXPORTS = (
     "fv_wnpool_lookahead", "fv_wnpool_max_frames", "fv_wnpool_launches", "fv_wnpool_destroy",
     "fv_w2v_create", "fv_w2v_load_weight", "fv_w2v_finalize", "fv_w2v_frames", "fv_w2v_workspace_bytes", "fv_w2v_forward", "fv_w2v_destroy",
     "fv_mms_normalize_workspace_bytes", "fv_mms_normalize", "fv_mms_interpolate", "fv_mms_nearest_index",
+    "fv_cnxstream_create", "fv_cnxstream_push", "fv_cnxstream_flush", "fv_cnxstream_reset", "fv_cnxstream_pending", "fv_cnxstream_lookahead",
+    "fv_cnxstream_state_bytes", "fv_cnxstream_destroy", "fv_cnxstream_plan",
 )
 
 _i32 = ctypes.c_int32
@@ -581,6 +583,24 @@ def lib() -> ctypes.CDLL:
     L.fv_wnstream_lookahead.restype = _i32
     L.fv_wnstream_destroy.argtypes = [vp]
     L.fv_wnstream_destroy.restype = None
+    L.fv_cnxstream_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_cnxstream_create.restype = _i32
+    L.fv_cnxstream_push.argtypes = [vp, vp, i64, i64, _i32, vp, i64, i64p, vp]
+    L.fv_cnxstream_push.restype = _i32
+    L.fv_cnxstream_flush.argtypes = [vp, vp, i64, i64p, vp]
+    L.fv_cnxstream_flush.restype = _i32
+    L.fv_cnxstream_reset.argtypes = [vp]
+    L.fv_cnxstream_reset.restype = _i32
+    L.fv_cnxstream_pending.argtypes = [vp]
+    L.fv_cnxstream_pending.restype = i64
+    L.fv_cnxstream_lookahead.argtypes = [vp]
+    L.fv_cnxstream_lookahead.restype = _i32
+    L.fv_cnxstream_state_bytes.argtypes = [vp]
+    L.fv_cnxstream_state_bytes.restype = i64
+    L.fv_cnxstream_destroy.argtypes = [vp]
+    L.fv_cnxstream_destroy.restype = None
+    L.fv_cnxstream_plan.argtypes = [i64, i64, _i32, _i32, _i32, _i32, i64p]
+    L.fv_cnxstream_plan.restype = _i32
     L.fv_wnpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
     L.fv_wnpool_create.restype = _i32
     L.fv_wnpool_plan.argtypes = [_i32, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]

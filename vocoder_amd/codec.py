@@ -8,6 +8,7 @@ drop-in modules, every stage on the HIP engine; the quantiser is ``modules.quant
     python -m vocoder_amd.codec encode -i a.wav -o out/ [--checkpoint ckpt]      # writes out/a.codes.npy, int64 (n_q, T) or (T,)
     python -m vocoder_amd.codec decode -i out/a.codes.npy -o out/                 # writes out/a.wav
     python -m vocoder_amd.codec decode -i out/a.codes.npy -o out/ --chunk-frames 64     # through decode_stream, 64 frames a push
+    python -m vocoder_amd.codec encode -i a.wav -o out/ --chunk-samples 4096 --batch-invariant    # through encode_stream (ConvNeXt layer stream)
 
 ``decode_stream`` / ``decode_pool`` serve the decode direction chunk by chunk (``CodecDecodeStream``, ``CodecDecodePool``): the ring in front of
 the decoder keeps the codes, not the latent.
@@ -60,8 +61,9 @@ class VQVAECodec(nn.Module):
 
     def encode_stream(self, batch: int = 1, max_chunk_samples: int = 4096) -> "CodecEncodeStream":
         """``encode`` chunk by chunk (``CodecEncodeStream``): audio in, codes out after the front-end's and the encoder's lookahead.  For an
-        encoder of spectrograms whose own ``stream()`` has ``forward``'s bits (``PosteriorEncoder``); with the front-end in its
-        batch-invariant mode the concatenated codes are ``encode``'s."""
+        encoder of spectrograms whose own stream has ``forward``'s bits: a ``PosteriorEncoder``, or a ``ConvNeXtEncoder`` with
+        ``batch_invariant = True`` (its ``layer_stream``); with the front-end in its batch-invariant mode the concatenated codes are
+        ``encode``'s."""
         return CodecEncodeStream(self, batch, max_chunk_samples)
 
     def encode_pool(self, sessions: int, max_chunk_samples: int = 4096) -> "CodecEncodePool":
@@ -74,9 +76,11 @@ class VQVAECodec(nn.Module):
         y = self.decoder(self.vq.from_codes(codes)[0])
         return y[:, None, :] if y.ndim == 2 else y
 
-    def decode_stream(self, batch: int = 1, max_chunk_frames: int = 64) -> "CodecDecodeStream":
-        """``decode`` chunk by chunk (``CodecDecodeStream``): codes in, audio out after the decoder's lookahead; the rings keep codes."""
-        return CodecDecodeStream(self.decoder, self.vq, batch, max_chunk_frames)
+    def decode_stream(self, batch: int = 1, max_chunk_frames: int = 64, backbone: str = "window") -> "CodecDecodeStream":
+        """``decode`` chunk by chunk (``CodecDecodeStream``): codes in, audio out after the decoder's lookahead.  ``backbone="window"``: the
+        rings keep codes and every push recomputes the backbone's window; ``"layers"``: the ConvNeXt backbone of a two-stage decoder runs
+        as its ``layer_stream`` — only the new frames, with the bits of its batch-invariant ``forward``."""
+        return CodecDecodeStream(self.decoder, self.vq, batch, max_chunk_frames, backbone)
 
     def decode_pool(self, sessions: int, max_chunk_frames: int = 64) -> "CodecDecodePool":
         """``decode`` for ``sessions`` clients that advance at their own pace (``CodecDecodePool``): one step serves any subset of them."""
@@ -126,9 +130,16 @@ def _streaming_encoder(codec: VQVAECodec, what: str) -> nn.Module:
     enc, name = codec.encoder, type(codec.encoder).__name__
     if getattr(enc, "takes_audio", False):
         raise ValueError(f"{what}: {name} takes raw audio (takes_audio), not a streamed spectrogram: it has no streaming encode")
+    layered = hasattr(enc, "layer_stream")        # ConvNeXtEncoder: bit-exact through layer_stream, in its batch-invariant mode only
     if not getattr(enc, "stream_is_bit_exact", False):
         raise ValueError(f"{what}: {name}.stream() is not bit-exact — a windowed engine stream promises 2e-5, not forward's bits, so "
-                         "codes could differ from encode(); use a PosteriorEncoder (build_vqvae(encoder='posterior'))")
+                         "codes could differ from encode(); use a PosteriorEncoder (build_vqvae(encoder='posterior'))"
+                         + (" or set encoder.batch_invariant = True" if layered and what == "encode_stream" else "")
+                         + (" and encoder.conv_algorithm = 'direct' (its C -> C stem has a Winograd form, whose bits depend on the launch)"
+                            if layered and what == "encode_stream" and getattr(enc, "stem_has_winograd_form", False) else ""))
+    if layered and what != "encode_stream":
+        raise ValueError(f"{what}: {name} has a layer stream (encode_stream) but its pool form is not built: there is no session pool of "
+                         "layer streams; use encode_stream per source, or a PosteriorEncoder")
     if codec.frontend is None:
         raise ValueError(f"{what}: the codec has no front-end to turn the audio chunks into spectrogram frames")
     return enc
@@ -195,7 +206,8 @@ class CodecEncodeStream:
         self._fe = codec.frontend.stream(batch, max_chunk_samples)
         self.batch, self.max_chunk_samples = int(batch), int(max_chunk_samples)
         self._max_frames = self.max_chunk_samples // int(codec.frontend.hop_length) + 2      # per encoder push; longer runs go in pieces
-        self._enc = enc.stream(batch, self._max_frames)
+        # a ConvNeXtEncoder's stream() is the windowed one; its whole-row bits come from layer_stream
+        self._enc = (enc.layer_stream if hasattr(enc, "layer_stream") else enc.stream)(batch, self._max_frames)
 
     @property
     def received_samples(self) -> int:
@@ -259,10 +271,19 @@ class CodecDecodeStream:
     backbone's frames to ``head.stream()`` on the device; ``lookahead_frames`` is the sum of the stages'.  Every call's output has the bits of
     the same chain on float streams fed ``vq.from_codes``.  ``template`` (a use_template generator) goes to a single-engine decoder."""
 
-    def __init__(self, decoder: nn.Module, vq, batch: int = 1, max_chunk_frames: int = 64):
+    def __init__(self, decoder: nn.Module, vq, batch: int = 1, max_chunk_frames: int = 64, backbone: str = "window"):
         stages = _decoder_stages(decoder, vq, "decode_stream")
         self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
-        self.codes = stages[0].code_stream(vq, self.batch, self.max_chunk_frames)
+        if backbone not in ("window", "layers"):
+            raise ValueError(f"decode_stream: backbone must be 'window' or 'layers', got {backbone!r}")
+        self.backbone = backbone
+        if backbone == "layers":
+            if len(stages) != 2 or not hasattr(stages[0], "layer_stream"):
+                raise ValueError("decode_stream: backbone='layers' needs a two-stage decoder whose backbone has a layer stream "
+                                 f"(a ConvNeXtEncoder); got {[type(m).__name__ for m in stages]}")
+            self.codes = _LayerBackbone(vq, stages[0].layer_stream(self.batch, self.max_chunk_frames))
+        else:
+            self.codes = stages[0].code_stream(vq, self.batch, self.max_chunk_frames)
         self.head = None
         if len(stages) == 2:
             # one backbone call emits at most max_chunk_frames frames (a push) or its lookahead (the flush)
@@ -314,6 +335,55 @@ class CodecDecodeStream:
 
     def __exit__(self, *exc) -> None:
         self.close()
+
+
+class _LayerBackbone:
+    """The first stage of ``CodecDecodeStream(backbone="layers")`` with the face of a ``CodeStream``: ``push(codes)`` runs
+    ``vq.from_codes(chunk)`` -> ``backbone.layer_stream`` on the device.  Nothing is kept of the codes: the backbone's rings hold its
+    blocks' last columns.  ``check`` makes the refusals a host can see before anything is launched; the count a call emits is the
+    stream's host arithmetic (``ConvNeXtStream.plan``).  ``validate`` has no effect here: ``from_codes`` checks the codes itself."""
+    hop = 1
+
+    def __init__(self, vq, stream):
+        self._vq, self.stream = vq, stream
+        self.batch, self.max_chunk_frames, self.out_channels = stream.batch, stream.max_chunk_frames, stream.out_channels
+        self.lookahead_frames = stream.lookahead_frames
+
+    received_frames = property(lambda self: self.stream.received_frames)
+    emitted_frames = property(lambda self: self.stream.emitted_frames)
+    ring_bytes = property(lambda self: self.stream.state_bytes)
+
+    def _check_open(self) -> None:
+        self.stream._check_open()
+
+    def check(self, codes: torch.Tensor) -> int:
+        """The refusals a host can see, before any stage launches; returns the chunk's frames."""
+        self.stream._check_open()
+        if not isinstance(codes, torch.Tensor) or not codes.is_cuda:
+            raise RuntimeError(f"CodecDecodeStream.push needs a CUDA/HIP tensor of codes (got {getattr(codes, 'device', type(codes))})")
+        if codes.dim() not in (2, 3) or codes.shape[-2] != self.batch:
+            raise ValueError(f"CodecDecodeStream.push: expected codes ({self.batch}, c) or (n_q, {self.batch}, c), got {tuple(codes.shape)}")
+        c = int(codes.shape[-1])
+        if c > self.max_chunk_frames:
+            raise ValueError(f"CodecDecodeStream.push: c = {c} is more than max_chunk_frames = {self.max_chunk_frames}")
+        if self.stream._flushed:
+            raise RuntimeError("CodecDecodeStream.push: the stream was flushed: reset() starts the next utterance")
+        return c
+
+    def push(self, codes: torch.Tensor, template=None, validate: bool = True) -> torch.Tensor:
+        c = self.check(codes)
+        if c == 0:
+            return self.stream.push(torch.empty((self.batch, self.stream.in_channels, 0), dtype=torch.float32, device=codes.device))
+        return self.stream.push(self._vq.from_codes(codes)[0])
+
+    def flush(self) -> torch.Tensor:
+        return self.stream.flush()
+
+    def reset(self) -> None:
+        self.stream.reset()
+
+    def close(self) -> None:
+        self.stream.close()
 
 
 class CodecDecodePool:
@@ -428,7 +498,11 @@ def main(argv=None):
     ap.add_argument("--encoder", choices=("convnext", "posterior"), default="convnext", help="the encoder slot: ConvNeXtEncoder or PosteriorEncoder")
     ap.add_argument("--hidden-channels", type=int, default=192, help="--encoder posterior: the WaveNet's width")
     ap.add_argument("--chunk-samples", type=int, default=None,
-                    help="encode: run the file through encode_stream in chunks of this many samples (same codes; needs --encoder posterior)")
+                    help="encode: run the file through encode_stream in chunks of this many samples (same codes; needs --encoder posterior, "
+                         "or --batch-invariant with the ConvNeXt encoder)")
+    ap.add_argument("--batch-invariant", action="store_true",
+                    help="encode: the encoder and the front-end in their batch-invariant mode, whole-file or chunked: the mode in which the "
+                         "ConvNeXt encoder's layer stream gives the whole-file codes")
     ap.add_argument("--chunk-frames", type=int, default=None,
                     help="decode: run the codes through decode_stream in chunks of this many frames (the rings keep codes)")
     a = ap.parse_args(argv)
@@ -440,11 +514,13 @@ def main(argv=None):
     if a.chunk_samples is not None:
         if a.mode != "encode":
             ap.error("--chunk-samples belongs to encode: decode streams frames of codes (--chunk-frames)")
-        if a.encoder != "posterior":
+        if a.encoder != "posterior" and not a.batch_invariant:
             ap.error("--chunk-samples needs --encoder posterior: the ConvNeXt encoder's stream is not bit-exact, so its codes could differ "
-                     "from a whole-file encode")
+                     "from a whole-file encode; or add --batch-invariant, the mode in which its layer stream has the whole file's bits")
         if a.chunk_samples < 1:
             ap.error(f"--chunk-samples = {a.chunk_samples} must be at least 1")
+    if a.batch_invariant and a.mode != "encode":
+        ap.error("--batch-invariant belongs to encode: it sets the encoder's and the front-end's mode")
     if not torch.cuda.is_available():
         raise SystemExit("vocoder_amd.codec needs a HIP device: there is no CPU path")
     model = build_vqvae(a.n_fft, a.hop_length, a.win_length, a.latent_size, a.codebook_size, a.num_quantizers,
@@ -461,6 +537,10 @@ def main(argv=None):
         if sr != a.sample_rate:
             raise SystemExit(f"{src}: {sr} Hz, the model runs at {a.sample_rate} Hz (resample with vocoder_amd.inference --resample first)")
         audio = torch.from_numpy(wav.mean(0, keepdims=True))[None].cuda()
+        if a.batch_invariant:
+            model.encoder.batch_invariant = model.frontend.batch_invariant = True
+            if getattr(model.encoder, "stem_has_winograd_form", False):      # n_fft / 2 + 1 == latent_size: a C -> C stem, direct sums as well
+                model.encoder.conv_algorithm = "direct"
         if a.chunk_samples is None:
             codes = model.encode(audio)
         else:

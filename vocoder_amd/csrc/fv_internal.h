@@ -399,6 +399,24 @@ fv_status launch_aa_snake(const float* x, float* y, const float* alpha_eff, cons
 fv_status launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
                            float* y, int B, int C, int T, int k, float eps, hipStream_t s);
 
+// The k = 7 form chunk by chunk (fv_cnxstream_*, cnx_stream_plan.h): one block's launch of a call.  Staged frames below in0 come from the
+// block's ring (B, C, cap), the frames [in0, in1) from `chunk` (B, C, chunk_stride), frame in0 at column chunk_off, and are filed into the
+// ring; h and xres, (B, C, out1 - out0), take the LayerNorm output and the block's input (its residual) at the columns [out0, out1).  The
+// (CMAX, NG) instantiation for C is the whole-row launch's, and so is every column's arithmetic.  C <= 1024, C * cap < 2^28.
+struct DwStreamRun {
+    float* ring = nullptr;
+    const float* chunk = nullptr;
+    float *h = nullptr, *xres = nullptr;
+    int cap = 0, chunk_stride = 0, chunk_off = 0;
+    int in0 = 0, in1 = 0, out0 = 0, out1 = 0, tiles = 0;
+};
+fv_status launch_dwconv_ln_stream(const DwStreamRun& r, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, int B, int C,
+                                  float eps, hipStream_t s);
+// win (B, C, 6 + c) = the input frames [N0 - 6, N0 + c), zeros below frame 0: six from the input ring (B, C, cap), c from the caller's chunk
+// (element (b, ci, t) at b * x_bstride + ci * x_rstride + t), which is filed into the ring
+fv_status launch_cnx_stem_window(const float* chunk, long long x_bstride, long long x_rstride, float* ring, float* win, int B, int C, int cap,
+                                 long long N0, int c, hipStream_t s);
+
 // x[b][c][t] += bias[c] + sum_j w[c][j] * template[b][t*stride + j - pad]  (use_template branch, hifigan.py:233-234)
 fv_status launch_noise_conv_add(const float* tmpl, const float* w, const float* bias, float* x, int B, int C, int T, int Ta,
                                 int k, int stride, int pad, hipStream_t s);

@@ -2,6 +2,7 @@
 // depthwise-conv + LayerNorm, ISTFT spectrum (its overlap-add is frame_kernels.hip's).  All are coalesced along T (the
 // contiguous axis of the reference's (B, C, T) layout) and stage their reuse windows in LDS.
 
+#include "cnx_stream_plan.h"
 #include "conv_mfma_impl.h"
 
 namespace fv {
@@ -746,12 +747,30 @@ __global__ __launch_bounds__(256) void dwconv_ln_reg_kernel(const float* __restr
 constexpr int DWT_TT = 32, DWT_CH = 64, DWT_PITCH = 40;
 // NG channel groups of 32 columns each = NG x 32 threads: 16 groups (512 threads) for the wide stages halve the rows and the
 // FIR-output registers per thread and double the waves a launch puts on a CU (T = 94: only 1.5 workgroups per CU exist).
-template <int K, int CMAX, int NG>
-__global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __restrict__ x, const float* __restrict__ dw_w,
-                                                             const float* __restrict__ dw_b,
-                                                             const float* __restrict__ ln_w,
-                                                             const float* __restrict__ ln_b, float* __restrict__ y, int C,
-                                                             int T, float eps, int n_tiles, int n_items, int xcd_map) {
+//
+// The stream form (fv_cnxstream_*, STREAM): the same body over the columns [out0, out1) of a block that is fed chunk by chunk.  Columns are
+// absolute frames; a staged frame below the input's old frontier in0 comes from the block's ring (C, cap), slot = frame & (cap - 1), a frame
+// of [in0, in1) from the linear chunk, and a frame below 0 or at / past in1 is 0 by predicate — no slot is read for it, so what an
+// uninitialised or stale ring holds never reaches a sum.  The launch files the chunk into the ring as it stages it (cnx_stream_plan.h: the
+// slots read and written are disjoint), writes H as linear (C, out1 - out0) and beside it the block's residual, its input at the output
+// columns, which it holds in LDS.  Per column the arithmetic is the whole-row kernel's, operation for operation — the TILE kernel's: with the
+// experiment switch FV_OLD_DWLN the whole-row launch leaves it for the register kernel (another channel order), and the stream does not follow.
+struct DwStream {
+    float* ring;                 // (batch, C, cap)
+    const float* chunk;          // (batch, C, chunk_stride): frame in0 at column chunk_off
+    float* xres;                 // (batch, C, out1 - out0)
+    int cap, chunk_stride, chunk_off;
+    int in0, in1, out0, out1;
+};
+struct DwNoStream {};
+__device__ __forceinline__ int sp_out0(const DwStream& sp) { return sp.out0; }
+__device__ __forceinline__ int sp_out0(const DwNoStream&) { return 0; }
+
+template <bool STREAM, int K, int CMAX, int NG, class SP>
+__device__ __forceinline__ void dwconv_ln_tile_body(const float* __restrict__ x, const float* __restrict__ dw_w,
+                                                    const float* __restrict__ dw_b, const float* __restrict__ ln_w,
+                                                    const float* __restrict__ ln_b, float* __restrict__ y, int C, int T, float eps,
+                                                    int n_tiles, int n_items, int xcd_map, const SP& sp) {
     constexpr int WE = DWT_TT + K - 1;                    // staged columns per channel row
     constexpr int NEL = DWT_CH * WE;
     constexpr int NTH = NG * 32;                          // threads per workgroup
@@ -774,9 +793,17 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
     const int lid = xcd_map ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (lid >= n_items * n_tiles) return;
     const int tile = lid % n_tiles, b = lid / n_tiles;
-    const int t0 = tile * DWT_TT;
+    const int t0 = tile * DWT_TT + sp_out0(sp);
     const int t = t0 + col;
-    const __amdgpu_buffer_rsrc_t xrs = uniform_rsrc(x + (long long)b * C * T, (unsigned)((long long)C * T * 4));
+    // whole rows: xrs is x.  STREAM: xrs is the block's ring, xrs2 the chunk
+    const __amdgpu_buffer_rsrc_t xrs = [&] {
+        if constexpr (STREAM) return uniform_rsrc(sp.ring + (long long)b * C * sp.cap, (unsigned)((long long)C * sp.cap * 4));
+        else return uniform_rsrc(x + (long long)b * C * T, (unsigned)((long long)C * T * 4));
+    }();
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xrs2 = [&] {
+        if constexpr (STREAM) return uniform_rsrc(sp.chunk + (long long)b * C * sp.chunk_stride, (unsigned)((long long)C * sp.chunk_stride * 4));
+        else return xrs;
+    }();
     const int nchunk = (C + DWT_CH - 1) / DWT_CH;
 
     for (int c = tid; c < C; c += NTH) {
@@ -786,6 +813,10 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
     // staging plan (same for every chunk): element idx = tid + i*NTH -> (row, column) of the chunk window
     unsigned off[NLD];
     int lds_at[NLD];
+    // STREAM: the element's offset in the chunk (off: in the ring) — one of the two lies outside its descriptor and loads 0 — and the ring
+    // slot this workgroup files it in (-1: not a chunk frame, or another workgroup's)
+    [[maybe_unused]] unsigned off2[STREAM ? NLD : 1];
+    [[maybe_unused]] int file_at[STREAM ? NLD : 1];
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
         int idx = tid + i * NTH;
@@ -793,7 +824,16 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
         idx = in ? idx : NEL - 1;
         const int r = idx / WE, cc = idx - r * WE;
         const int tt = t0 - PAD + cc;
-        off[i] = (in && tt >= 0 && tt < T) ? (unsigned)(r * T + tt) * 4u : 0xC0000000u;   // + chunk row offset below
+        if constexpr (STREAM) {
+            const bool live = in && tt >= 0 && tt < sp.in1;
+            const bool fresh = live && tt >= sp.in0;
+            const int slot = tt & (sp.cap - 1);
+            off[i] = (live && !fresh) ? (unsigned)(r * sp.cap + slot) * 4u : 0xC0000000u;
+            off2[i] = fresh ? (unsigned)(r * sp.chunk_stride + sp.chunk_off + (tt - sp.in0)) * 4u : 0xC0000000u;
+            file_at[i] = (fresh && (tile == 0 || cc >= 2 * PAD)) ? r * sp.cap + slot : -1;
+        } else {
+            off[i] = (in && tt >= 0 && tt < T) ? (unsigned)(r * T + tt) * 4u : 0xC0000000u;   // + chunk row offset below
+        }
         lds_at[i] = in ? r * DWT_PITCH + cc : -1;
     }
     // Requests run PF - 1 chunks ahead of the chunk being computed (register ring st[PF]): a chunk is only 8 rows x K taps of
@@ -805,9 +845,17 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
     constexpr int PF = NCHUNK >= FV_X_DWLN_PF ? FV_X_DWLN_PF : (NCHUNK > 1 ? NCHUNK : 2);
     float st[PF][NLD], stw[PF][NWT];
     auto issue = [&](int SL, int ch) {   // SL: ring slot (a constant after unrolling)
-        const unsigned base = (unsigned)(ch * DWT_CH * T) * 4u;   // rows past C fall outside the descriptor -> 0
+        if constexpr (STREAM) {
+            const unsigned base = (unsigned)(ch * DWT_CH * sp.cap) * 4u, base2 = (unsigned)(ch * DWT_CH * sp.chunk_stride) * 4u;
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) st[SL][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs, off[i] + base, 0, 0));
+            for (int i = 0; i < NLD; ++i)
+                st[SL][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs, off[i] + base, 0, 0) |
+                                            __builtin_amdgcn_raw_buffer_load_b32(xrs2, off2[i] + base2, 0, 0));
+        } else {
+            const unsigned base = (unsigned)(ch * DWT_CH * T) * 4u;   // rows past C fall outside the descriptor -> 0
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) st[SL][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs, off[i] + base, 0, 0));
+        }
         if (K > 1) {
 #pragma unroll
             for (int u = 0; u < NWT; ++u) {
@@ -816,11 +864,17 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
             }
         }
     };
-    auto commit = [&](int SL, int buf) {
+    auto commit = [&](int SL, int buf, [[maybe_unused]] int ch) {
         float* xsb = &xs[buf][0][0];
 #pragma unroll
         for (int i = 0; i < NLD; ++i)
             if (lds_at[i] >= 0) xsb[lds_at[i]] = st[SL][i];
+        if constexpr (STREAM) {   // file this workgroup's chunk frames; rows past C fall outside the descriptor and are dropped
+            const unsigned base = (unsigned)(ch * DWT_CH * sp.cap) * 4u;
+#pragma unroll
+            for (int i = 0; i < NLD; ++i)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(st[SL][i]), xrs, file_at[i] >= 0 ? (unsigned)file_at[i] * 4u + base : 0xFFFFFFFFu, 0, 0);
+        }
         if (K > 1) {
 #pragma unroll
             for (int u = 0; u < NWT; ++u) wsm[buf][(tid + u * NTH) >> 3][tid & 7] = stw[SL][u];
@@ -831,10 +885,16 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
 #pragma unroll
     for (int i = 0; i < CMAX / NG; ++i) h[i] = 0.f;
     float s = 0.f;
+    [[maybe_unused]] int n_out = 0;
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t rrs = xrs;
+    if constexpr (STREAM) {
+        n_out = sp.out1 - sp.out0;
+        rrs = uniform_rsrc(sp.xres + (long long)b * C * n_out, (unsigned)((long long)C * n_out * 4));
+    }
 #pragma unroll
     for (int d = 0; d < PF - 1; ++d)
         if (d < nchunk) issue(d, d);
-    commit(0, 0);
+    commit(0, 0, 0);
     __syncthreads();
 #pragma unroll
     for (int ch = 0; ch < NCHUNK; ++ch) {
@@ -855,8 +915,13 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
                 }
                 h[ch * RPT + qq] = v;
                 s += (ch * DWT_CH + cl < C) ? v : 0.f;
+                if constexpr (STREAM) {   // the block's residual: its input at the output column
+                    const int c = ch * DWT_CH + cl;
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xs[buf][cl][col + PAD]), rrs,
+                                                          (c < C && t < sp.out1) ? (unsigned)(c * n_out + (t - sp.out0)) * 4u : 0xFFFFFFFFu, 0, 0);
+                }
             }
-            if (ch + 1 < nchunk) commit((ch + 1) % PF, buf ^ 1);
+            if (ch + 1 < nchunk) commit((ch + 1) % PF, buf ^ 1, ch + 1);
             __syncthreads();
         }
     }
@@ -885,17 +950,50 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __
     for (int g = 0; g < NG; ++g) var += red[g][col];
     var /= (float)C;
     const float inv = 1.0f / sqrtf(var + eps);
-    const __amdgpu_buffer_rsrc_t yrs = uniform_rsrc(y + (long long)b * C * T, (unsigned)((long long)C * T * 4));
+    // whole rows: (C, T), column t.  STREAM: (C, out1 - out0), column t - out0
+    const int yT = STREAM ? n_out : T, yt = t - sp_out0(sp);
+    const __amdgpu_buffer_rsrc_t yrs = uniform_rsrc(y + (long long)b * C * yT, (unsigned)((long long)C * yT * 4));
 #pragma unroll
     for (int ch = 0; ch < NCHUNK; ++ch)
 #pragma unroll
         for (int qq = 0; qq < RPT; ++qq) {
             const int c = ch * DWT_CH + cg + NG * qq;
-            const bool ok = c < C && t < T;
+            const bool ok = c < C && yt < yT;
             const int cc = c < C ? c : 0;
             const float v = (h[ch * RPT + qq] - mean) * inv * lnp[0][cc] + lnp[1][cc];
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yrs, ok ? (unsigned)(c * T + t) * 4u : 0xFFFFFFFFu, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yrs, ok ? (unsigned)(c * yT + yt) * 4u : 0xFFFFFFFFu, 0, 0);
         }
+}
+
+template <int K, int CMAX, int NG>
+__global__ __launch_bounds__(NG * 32) void dwconv_ln_tile_kernel(const float* __restrict__ x, const float* __restrict__ dw_w,
+                                                             const float* __restrict__ dw_b,
+                                                             const float* __restrict__ ln_w,
+                                                             const float* __restrict__ ln_b, float* __restrict__ y, int C,
+                                                             int T, float eps, int n_tiles, int n_items, int xcd_map) {
+    dwconv_ln_tile_body<false, K, CMAX, NG>(x, dw_w, dw_b, ln_w, ln_b, y, C, T, eps, n_tiles, n_items, xcd_map, DwNoStream{});
+}
+template <int K, int CMAX, int NG>
+__global__ __launch_bounds__(NG * 32) void dwconv_ln_stream_kernel(const float* __restrict__ dw_w, const float* __restrict__ dw_b,
+                                                               const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                               float* __restrict__ y, int C, float eps, int n_tiles, int n_items,
+                                                               int xcd_map, DwStream sp) {
+    dwconv_ln_tile_body<true, K, CMAX, NG>(nullptr, dw_w, dw_b, ln_w, ln_b, y, C, 0, eps, n_tiles, n_items, xcd_map, sp);
+}
+
+// The (CMAX, NG) instantiation for C channels, for the whole-row and the stream launch alike: f(CMAX, NG as integral constants); false: C is
+// outside the tile kernel
+template <class F>
+static bool dwln_tile_dispatch(int C, F&& f) {
+    const bool wide = !knobs().dwln_ng8;   // 16 channel groups (512 threads) for C > 256
+    using std::integral_constant;
+    if (C <= 256) f(integral_constant<int, 256>{}, integral_constant<int, 8>{});
+    else if (C <= 512 && wide) f(integral_constant<int, 512>{}, integral_constant<int, 16>{});
+    else if (C <= 512) f(integral_constant<int, 512>{}, integral_constant<int, 8>{});
+    else if (C <= 1024 && wide) f(integral_constant<int, 1024>{}, integral_constant<int, 16>{});
+    else if (C <= 1024) f(integral_constant<int, 1024>{}, integral_constant<int, 8>{});
+    else return false;
+    return true;
 }
 
 template <int K>
@@ -903,15 +1001,61 @@ static bool launch_dwconv_ln_tile(const float* x, const float* dw_w, const float
                                   float* y, int B, int C, int T, float eps, hipStream_t s) {
     const int n_tiles = (T + DWT_TT - 1) / DWT_TT;
     const dim3 grid((B * n_tiles + 7) / 8 * 8);   // whole groups of 8: see the XCD mapping in the kernel
-    const bool wide = !knobs().dwln_ng8;   // 16 channel groups (512 threads) for C > 256
     const int xcd_map = !knobs().dwln_rr;   // experiments: round-robin tiles (the old mapping)
-    if (C <= 256) hipLaunchKernelGGL((dwconv_ln_tile_kernel<K, 256, 8>), grid, dim3(256), 0, s, x, dw_w, dw_b, ln_w, ln_b, y, C, T, eps, n_tiles, B, xcd_map);
-    else if (C <= 512 && wide) hipLaunchKernelGGL((dwconv_ln_tile_kernel<K, 512, 16>), grid, dim3(512), 0, s, x, dw_w, dw_b, ln_w, ln_b, y, C, T, eps, n_tiles, B, xcd_map);
-    else if (C <= 512) hipLaunchKernelGGL((dwconv_ln_tile_kernel<K, 512, 8>), grid, dim3(256), 0, s, x, dw_w, dw_b, ln_w, ln_b, y, C, T, eps, n_tiles, B, xcd_map);
-    else if (C <= 1024 && wide) hipLaunchKernelGGL((dwconv_ln_tile_kernel<K, 1024, 16>), grid, dim3(512), 0, s, x, dw_w, dw_b, ln_w, ln_b, y, C, T, eps, n_tiles, B, xcd_map);
-    else if (C <= 1024) hipLaunchKernelGGL((dwconv_ln_tile_kernel<K, 1024, 8>), grid, dim3(256), 0, s, x, dw_w, dw_b, ln_w, ln_b, y, C, T, eps, n_tiles, B, xcd_map);
-    else return false;
-    return true;
+    return dwln_tile_dispatch(C, [&](auto cmax, auto ng) {
+        hipLaunchKernelGGL((dwconv_ln_tile_kernel<K, decltype(cmax)::value, decltype(ng)::value>), grid, dim3(decltype(ng)::value * 32), 0, s, x, dw_w,
+                           dw_b, ln_w, ln_b, y, C, T, eps, n_tiles, B, xcd_map);
+    });
+}
+
+fv_status launch_dwconv_ln_stream(const DwStreamRun& r, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, int B, int C,
+                                  float eps, hipStream_t s) {
+    static_assert(DWT_TT == kCnxTile, "the plan's tiles are the kernel's");
+    if (r.tiles < 1) return FV_OK;
+    DwStream sp;
+    sp.ring = r.ring, sp.chunk = r.chunk, sp.xres = r.xres;
+    sp.cap = r.cap, sp.chunk_stride = r.chunk_stride, sp.chunk_off = r.chunk_off;
+    sp.in0 = r.in0, sp.in1 = r.in1, sp.out0 = r.out0, sp.out1 = r.out1;
+    const dim3 grid((B * r.tiles + 7) / 8 * 8);
+    const int xcd_map = !knobs().dwln_rr;
+    if (!dwln_tile_dispatch(C, [&](auto cmax, auto ng) {
+            hipLaunchKernelGGL((dwconv_ln_stream_kernel<7, decltype(cmax)::value, decltype(ng)::value>), grid, dim3(decltype(ng)::value * 32), 0, s,
+                               dw_w, dw_b, ln_w, ln_b, r.h, C, eps, r.tiles, B, xcd_map, sp);
+        })) {
+        set_error("launch_dwconv_ln_stream: C = %d is wider than the tile kernel's 1024 channels", C);
+        return FV_ERR_INVALID;
+    }
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+}
+
+// The stem's window of a ConvNeXt layer stream: win (B, C, 6 + c) = the frames [N0 - 6, N0 + c) of the input, zeros below frame 0, the first
+// six from the input ring (B, C, cap), the rest from the caller's chunk, which is filed into the ring on the way (cnx_stream_plan.h)
+__global__ __launch_bounds__(256) void cnx_stem_window_kernel(const float* __restrict__ chunk, long long x_bstride, long long x_rstride,
+                                                              float* __restrict__ ring, float* __restrict__ win, int C, int cap,
+                                                              long long N0, int c) {
+    const int W = c + kCnxHalo;
+    const long long row = blockIdx.x;   // b * C + ci
+    const long long b = row / C, ci = row - b * C;
+    for (int j = blockIdx.y * 256 + threadIdx.x; j < W; j += gridDim.y * 256) {
+        const long long f = N0 - kCnxHalo + j;
+        float v = 0.f;
+        if (f >= N0) {
+            v = chunk[b * x_bstride + ci * x_rstride + (f - N0)];
+            ring[row * cap + (f & (cap - 1))] = v;
+        } else if (f >= 0) {
+            v = ring[row * cap + (f & (cap - 1))];
+        }
+        win[row * W + j] = v;
+    }
+}
+fv_status launch_cnx_stem_window(const float* chunk, long long x_bstride, long long x_rstride, float* ring, float* win, int B, int C, int cap,
+                                 long long N0, int c, hipStream_t s) {
+    const int W = c + kCnxHalo;
+    hipLaunchKernelGGL(cnx_stem_window_kernel, dim3(B * C, std::min((W + 255) / 256, 64)), dim3(256), 0, s, chunk, x_bstride, x_rstride, ring, win, C,
+                       cap, N0, c);
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
 }
 
 fv_status launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,

@@ -4,15 +4,187 @@ Keys: ``downsample_layers.{i}.{0,1}``, ``stages.{i}.{j}.{dwconv,norm,pwconv1,pwc
 ``stages.{i}.{j}.gamma``, ``norm.{weight,bias}``.  Eval-mode semantics only (DropPath is identity).  Engine side:
 depthwise conv + LayerNorm fused in one kernel, the two pointwise Linear layers run as 1x1 convs on the fp32 MFMA
 kernel with GELU / layer-scale + residual fused into their epilogues.
+
+``stream()`` is the windowed engine stream (every push recomputes a window; 2e-5 of the whole row).  ``layer_stream(batch,
+max_chunk_frames)`` is the encoder layer by layer (``ConvNeXtStream``, ``fv_cnxstream_*``): every block keeps the last 6 columns of its
+input in a ring and a push runs each layer over its new columns only; the concatenated frames have the bits of ``forward`` with
+``batch_invariant = True``, ``3 * (1 + sum(depths))`` frames behind the input.  Where ``input_channels == dims[0]`` the stem is a C -> C
+conv with a Winograd form, whose bits depend on the launch's alignment: the stream runs it as direct sums, and the bits are those of
+``forward`` with ``conv_algorithm = "direct"`` as well (``stem_has_winograd_form``).
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 from torch import nn
 
 from .. import _base
 from ... import _lib
+from ..._handle import _Handle
+from ..._lib import check
 from ...engine import Engine, convnext_config
+
+_MSG_INFERENCE = "{} is inference-only: call .eval() first"
+_MSG_DEVICE = ("{} needs a CUDA/HIP tensor (got {}); vocoder_amd has no CPU path — move the model and "
+               "input to the GPU")
+_PAD = 3        # (7 - 1) / 2: the layer stream serves kernel_size 7
+
+
+def lookahead(depths) -> int:
+    """R of the layer stream: the stem and every block reach 3 frames ahead."""
+    return _PAD * (1 + sum(int(d) for d in depths))
+
+
+def schedule(chunks, R: int) -> list:
+    """The frames a layer stream of lookahead ``R`` emits: ``(E, E')`` for every push of ``chunks`` (frame counts, zeros allowed) — the push
+    emits ``[E, E')``, ``E' = max(E, N - R)`` — and last ``(E, N)`` for the flush."""
+    out, N, E = [], 0, 0
+    for c in chunks:
+        N += int(c)
+        E2 = max(E, N - int(R))
+        out.append((E, E2))
+        E = E2
+    out.append((E, N))
+    return out
+
+
+def front(N: int, level: int, flush: bool = False) -> int:
+    """Where level ``level``'s output ends after ``N`` frames (level 0: the stem, 1 .. L: the blocks); csrc/cnx_stream_plan.h ``cnx_front``."""
+    return N if flush else max(0, N - _PAD * (level + 1))
+
+
+def ring_cap(max_chunk: int, levels: int) -> int:
+    """Slots of a block's ring: the power of two >= 6 + max(max_chunk, R) (``cnx_ring_cap``)."""
+    cap = 1
+    while cap < 2 * _PAD + max(int(max_chunk), _PAD * (levels + 1)):
+        cap <<= 1
+    return cap
+
+
+def level_plan(N0: int, N1: int, flush: bool, level: int) -> dict:
+    """One block's launch of a call that takes the stream from ``N0`` to ``N1`` frames (``cnx_level_plan``): the chunk ``[in0, in1)`` from the
+    level below (the ring serves ``[in0 - 6, in0)``), the output columns ``[out0, out1)`` and the workgroups per row; workgroup ``j`` owns
+    the columns ``[out0 + 32 j, + 32)``, stages the frames 3 below to 3 above them and files the chunk frames from ``file_from(j)`` on."""
+    in0, in1 = front(N0, level - 1), front(N1, level - 1, flush)
+    out0, out1 = front(N0, level), front(N1, level, flush)
+    span = max(out1 - out0, in1 - _PAD - out0)
+    if in1 > in0:
+        span = max(span, 1)
+    tiles = (span + 31) // 32 if span > 0 else 0
+    return dict(in0=in0, in1=in1, out0=out0, out1=out1, tiles=tiles,
+                file_from=lambda j: in0 if j == 0 else out0 + 32 * j + _PAD)
+
+
+class ConvNeXtStream(_Handle):
+    """``ConvNeXtEncoder`` layer by layer and chunk by chunk (``fv_cnxstream_*``, include/fishvoc.h): ``push`` a ``(B, input_channels, c)``
+    chunk, ``c <= max_chunk_frames``, and get the frames that need no later input — ``[E, max(E, N - R))``, ``R = lookahead_frames``,
+    possibly none; ``flush`` ends the utterance at ``N`` and returns the rest, then pushes raise until ``reset()``.  The concatenation has
+    the bits of ``forward`` over the whole utterance with ``batch_invariant = True``, under any chunking (``schedule`` gives the counts).
+    The ``batch`` rows advance in lockstep.  A stream dies with the module's engine: ``load_state_dict`` or ``.to()`` closes it."""
+    _destroy = "fv_cnxstream_destroy"
+    _closed = ("this ConvNeXt layer stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
+               "the module): create a new stream")
+
+    def __init__(self, module: "ConvNeXtEncoder", engine: Engine, batch: int, max_chunk_frames: int):
+        self._lib, self._h = _lib.lib(), ctypes.c_void_p()
+        self._module, self._engine = module, engine
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_cnxstream_create(engine._h, int(batch), int(max_chunk_frames), ctypes.byref(self._h)))
+        engine._streams.add(self)
+        self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
+        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
+        self.hop = 1
+        self._R = int(self._lib.fv_cnxstream_lookahead(self._h))
+        self._N = self._E = 0
+        self._flushed = False
+        self._last_stream = None
+
+    # -- counters (host-side: reading them never synchronises) --
+    @property
+    def received_frames(self) -> int:
+        return self._N
+
+    @property
+    def emitted_frames(self) -> int:
+        return self._E
+
+    @property
+    def pending_frames(self) -> int:
+        """Frames received and not yet emitted, as the library counts them (``fv_cnxstream_pending``)."""
+        self._check_open()
+        return int(self._lib.fv_cnxstream_pending(self._h))
+
+    @property
+    def lookahead_frames(self) -> int:
+        return self._R
+
+    @property
+    def state_bytes(self) -> int:
+        """Device memory the stream holds: the rings and one call's scratch (``fv_cnxstream_state_bytes``)."""
+        self._check_open()
+        return int(self._lib.fv_cnxstream_state_bytes(self._h))
+
+    def schedule(self, chunks) -> list:
+        return schedule(chunks, self._R)
+
+    def plan(self, c: int, flush: bool = False) -> int:
+        """Frames the next ``push`` of ``c`` frames (or the ``flush``) emits: host arithmetic, nothing moves."""
+        return self._N - self._E if flush else max(self._E, self._N + int(c) - self._R) - self._E
+
+    def push(self, x: torch.Tensor) -> torch.Tensor:
+        self._check_open()
+        what = f"{type(self).__name__}.push"
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError(_MSG_DEVICE.format(what, getattr(x, "device", type(x))))
+        if x.dim() != 3 or x.shape[0] != self.batch or x.shape[1] != self.in_channels:
+            raise ValueError(f"{what}: expected ({self.batch}, {self.in_channels}, c), got {tuple(x.shape)}")
+        x = x.detach().to(torch.float32)
+        c = int(x.shape[2])
+        # a slice along T passes as it is (fv_cnxstream_push's strides)
+        if c and not ((c == 1 or x.stride(2) == 1) and x.stride(1) >= c and x.stride(0) >= 0):
+            x = x.contiguous()
+        return self._call(x, c, flush=False)
+
+    def flush(self) -> torch.Tensor:
+        """The frames ``[E, N)`` against the utterance's end; pushes raise afterwards until ``reset()``."""
+        self._check_open()
+        return self._call(None, 0, flush=True)
+
+    def _call(self, x, c: int, flush: bool) -> torch.Tensor:
+        m, dev = self._module, self._engine.device
+        if m.training:
+            raise RuntimeError(_MSG_INFERENCE.format(type(m).__name__))
+        if x is not None and x.device != dev:
+            raise RuntimeError(f"{type(self).__name__}.push: the chunk is on {x.device}, the stream on {dev}")
+        refused = self._flushed or c > self.max_chunk_frames      # a refused call emits nothing; the library says why
+        k = 0 if refused else self.plan(c, flush)
+        y = torch.empty((self.batch, self.out_channels, k), dtype=torch.float32, device=dev)
+        got = ctypes.c_int64(0)
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            if self._done is not None and self._last_stream != cur.cuda_stream:
+                cur.wait_event(self._done)       # the rings are the stream's own: order after the previous call when it ran on another stream
+            tail = (y.data_ptr() if k else None, max(k, 1), ctypes.byref(got), int(cur.cuda_stream))
+            if flush:
+                check(self._lib.fv_cnxstream_flush(self._h, *tail))
+            else:
+                check(self._lib.fv_cnxstream_push(self._h, x.data_ptr() if c else None, x.stride(0) if c else 0, x.stride(1) if c else 0, c, *tail))
+            self._record_done(cur)
+            self._last_stream = cur.cuda_stream
+        if got.value != k:
+            raise RuntimeError(f"ConvNeXt layer stream emitted {got.value} frames where the rule says {k}")
+        self._N += c
+        self._E += k
+        self._flushed = flush
+        return y
+
+    def reset(self) -> None:
+        """Start the next utterance: N = E = 0; the rings are kept (nothing they hold is read again)."""
+        self._check_open()
+        check(self._lib.fv_cnxstream_reset(self._h))
+        self._N = self._E = 0
+        self._flushed = False
 
 
 class LayerNorm(nn.Module):
@@ -65,3 +237,32 @@ class ConvNeXtEncoder(_base.EngineModule):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self._run(x)
+
+    @property
+    def stem_has_winograd_form(self) -> bool:
+        """The stem is a C -> C conv (``input_channels == dims[0]``, at least 16): ``layer_stream`` then has the bits of ``forward`` with
+        ``conv_algorithm = "direct"`` and ``batch_invariant = True``; otherwise ``batch_invariant`` alone decides them."""
+        return self._cfg["input_channels"] == self._cfg["dims"][0] >= 16 and self._cfg["kernel_size"] in (3, 7, 11)
+
+    @property
+    def stream_is_bit_exact(self) -> bool:
+        """Does a stream of this encoder have ``forward``'s bits?  ``layer_stream`` has the bits of the batch-invariant forward (with direct
+        sums in a stem that has a Winograd form), so only in that mode — in which ``forward``'s own bits do not depend on the launch — is
+        that a true sentence."""
+        return self.batch_invariant and (not self.stem_has_winograd_form or self.conv_algorithm == "direct")
+
+    @property
+    def lookahead_frames(self) -> int:
+        """R of ``layer_stream``: ``3 * (1 + sum(depths))``."""
+        return lookahead(self._cfg["depths"])
+
+    def layer_stream(self, batch: int = 1, max_chunk_frames: int = 64) -> ConvNeXtStream:
+        """The encoder layer by layer and chunk by chunk (``ConvNeXtStream``): rings of 6 columns per block instead of a recomputed
+        window, the bits of the batch-invariant ``forward``, ``lookahead_frames`` behind the input.  ``kernel_size`` 7, widths up to 1024,
+        precision f32.  Reloading the weights or moving the module rebuilds the engine and closes its streams: create a new one then."""
+        p = next(self.parameters(), None)
+        if p is None or not p.is_cuda:
+            raise RuntimeError(_MSG_DEVICE.format(f"{type(self).__name__}.layer_stream", getattr(p, "device", None)))
+        if self.training:
+            raise RuntimeError(_MSG_INFERENCE.format(type(self).__name__))
+        return ConvNeXtStream(self, self.engine(p.device), batch, max_chunk_frames)

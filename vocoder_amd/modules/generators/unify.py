@@ -33,13 +33,14 @@ class UnifyGenerator(nn.Module):
         x = self.head(self.vq.from_codes(codes)[0], template=template)
         return x[:, None, :] if x.ndim == 2 else x
 
-    def decode_stream(self, batch: int = 1, max_chunk_frames: int = 64):
+    def decode_stream(self, batch: int = 1, max_chunk_frames: int = 64, backbone: str = "window"):
         """``decode`` chunk by chunk (``vocoder_amd.codec.CodecDecodeStream`` on the head alone, as ``decode`` runs the head alone): codes in,
-        audio out after the head's lookahead; the ring keeps the codes."""
+        audio out after the head's lookahead; the ring keeps the codes.  ``backbone`` is ``CodecDecodeStream``'s option: ``"layers"`` asks
+        for a ConvNeXt backbone stage in front of the head, which this ``decode`` does not run, and is refused by name."""
         from ...codec import CodecDecodeStream
         if self.vq is None:
             raise ValueError("VQ module is not present in the model.")
-        return CodecDecodeStream(self.head, self.vq, batch, max_chunk_frames)
+        return CodecDecodeStream(self.head, self.vq, batch, max_chunk_frames, backbone)
 
     def decode_pool(self, sessions: int, max_chunk_frames: int = 64):
         """``decode`` for ``sessions`` clients that advance independently (``vocoder_amd.codec.CodecDecodePool`` on the head alone)."""
