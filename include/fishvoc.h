@@ -1325,6 +1325,29 @@ FV_API fv_status fv_conv_set_precision(fv_conv* c, int32_t precision);
 FV_API fv_status fv_conv_set_algorithm(fv_conv* c, int32_t algo);
 FV_API void fv_conv_destroy(fv_conv* c);
 
+/* -------- single helper ops (the kernels between the convs on their own; used by the parity tests) --------
+ * All pointers are device pointers to contiguous float32 (batch, channels, T) tensors and per-channel vectors.  Everything is validated before
+ * anything is enqueued: a NULL required pointer, channels < 1, batch < 0, T < 0 or past the launcher's 32-bit span, an even kernel_size, or
+ * d_y overlapping an input (workgroups read their neighbours' halo) -> FV_ERR_INVALID with the argument named in fv_last_error, and nothing is
+ * written.  batch = 0 or T = 0 is a no-op.  Asynchronous on `stream`; never synchronises.  fv_last_kernel names the form that ran.
+ *
+ * fv_aa_snake_forward: BigVGAN's Activation1d(SnakeBeta), y = down2(snake(up2(x))) with replicate padding at both rates (bigvgan.py:121-135,
+ * 226-233).  d_alpha = exp(alpha) and d_inv_beta = 1 / (exp(beta) + 1e-9) per channel; d_up_taps / d_down_taps: 12 floats each.  d_x2 and d_x3
+ * are both NULL or both set: the input is then ((x + x2) + x3) / 3.  Forms: "aa_snake<vec4>" (16-byte accesses: T % 4 == 0, T >= 8, d_x and
+ * d_y 16-byte aligned, one operand, FV_AA_VEC4 not 0) or "aa_snake<pair>", the same bits; " sum3" follows with three operands.
+ *
+ * fv_dwconv_ln_forward: depthwise Conv1d(kernel_size, 'same' zero padding) + LayerNorm over channels (convnext.py:126-129); d_dw_weight is
+ * (channels, kernel_size), d_dw_bias may be NULL.  d_dw_weight == NULL: the channels-first LayerNorm alone (convnext.py:71-74); kernel_size
+ * must then be 1 and d_dw_bias NULL.  Forms: "dwconv_ln_tile<k=7 cmax=512 ng=16>" (LayerNorm alone, k = 1, and k = 7 up to 1024 channels;
+ * cmax in {256, 512, 1024}, ng = 8 for cmax = 256 and under FV_DWLN_NG8), "dwconv_ln_reg<k=3>" (other k up to 1024 channels, every k under
+ * FV_OLD_DWLN), "dwconv_ln<k=7>" (wider). */
+FV_API fv_status fv_aa_snake_forward(const float* d_x, const float* d_x2, const float* d_x3, float* d_y, const float* d_alpha,
+                                     const float* d_inv_beta, const float* d_up_taps, const float* d_down_taps, int32_t batch,
+                                     int32_t channels, int64_t T, void* stream);
+FV_API fv_status fv_dwconv_ln_forward(const float* d_x, const float* d_dw_weight, const float* d_dw_bias, const float* d_ln_weight,
+                                      const float* d_ln_bias, float* d_y, int32_t batch, int32_t channels, int64_t T, int32_t kernel_size,
+                                      float eps, void* stream);
+
 /* -------- vector quantiser: VQ / residual VQ, encode and decode --------
  * The stage between generator.encoder and generator.decoder of VQVAEModel (vae.py:66-87: encodec's VectorQuantization for
  * num_quantizers == 1, ResidualVectorQuantization above) and the `vq` slot of UnifyGenerator (unify.py:21-53), inference arithmetic only
@@ -1692,7 +1715,7 @@ FV_API fv_status fv_profile_end(fv_engine* e, char* json_buf, size_t cap, size_t
 /* -------- misc -------- */
 FV_API const char* fv_last_error(void);
 FV_API int32_t fv_abi_version(void);
-/* Name of the device kernel variant the last fv_conv_forward on this thread dispatched (diagnostics). */
+/* Name of the device kernel variant the last fv_conv_forward / fv_aa_snake_forward / fv_dwconv_ln_forward on this thread dispatched (diagnostics). */
 FV_API const char* fv_last_kernel(void);
 
 #ifdef __cplusplus

@@ -6,7 +6,6 @@ import numpy as np, torch
 from vocoder_amd import _lib
 L = _lib.lib()
 vp = ctypes.c_void_p
-L.fv_debug_aa_snake.argtypes = [vp] * 6 + [ctypes.c_int] * 3 + [vp]
 L.fv_debug_poison_lds.argtypes = [vp]
 torch.manual_seed(0)
 taps = torch.tensor([0.002, -0.01, 0.03, -0.08, 0.2, 0.36, 0.36, 0.2, -0.08, 0.03, -0.01, 0.002], device="cuda")
@@ -17,7 +16,7 @@ for B, C, T in [(1, 128, 6016), (1, 64, 12032), (1, 32, 24064), (2, 128, 6016), 
     ref = []
     for j in range(3):
         y = torch.empty_like(xs[j])
-        L.fv_debug_aa_snake(xs[j].data_ptr(), y.data_ptr(), al[j].data_ptr(), ib[j].data_ptr(), taps.data_ptr(), taps.data_ptr(), B, C, T, vp(torch.cuda.current_stream().cuda_stream))
+        L.fv_aa_snake_forward(xs[j].data_ptr(), None, None, y.data_ptr(), al[j].data_ptr(), ib[j].data_ptr(), taps.data_ptr(), taps.data_ptr(), B, C, T, vp(torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
         ref.append(y)
     streams = [torch.cuda.Stream() for _ in range(3)]
@@ -28,7 +27,7 @@ for B, C, T in [(1, 128, 6016), (1, 64, 12032), (1, 32, 24064), (2, 128, 6016), 
         for j in range(3):
             with torch.cuda.stream(streams[j]):
                 if it % 2: L.fv_debug_poison_lds(vp(streams[j].cuda_stream))
-                L.fv_debug_aa_snake(xs[j].data_ptr(), ys[j].data_ptr(), al[j].data_ptr(), ib[j].data_ptr(), taps.data_ptr(), taps.data_ptr(), B, C, T, vp(streams[j].cuda_stream))
+                L.fv_aa_snake_forward(xs[j].data_ptr(), None, None, ys[j].data_ptr(), al[j].data_ptr(), ib[j].data_ptr(), taps.data_ptr(), taps.data_ptr(), B, C, T, vp(streams[j].cuda_stream))
         torch.cuda.synchronize()
         for j in range(3):
             if not torch.equal(ys[j], ref[j]):

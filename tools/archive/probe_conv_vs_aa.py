@@ -11,7 +11,6 @@ prec = sys.argv[1] if len(sys.argv) > 1 else "f16x3"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 L = _lib.lib()
 vp = ctypes.c_void_p
-L.fv_debug_aa_snake.argtypes = [vp] * 6 + [ctypes.c_int] * 3 + [vp]
 rng = np.random.default_rng(0)
 taps = torch.tensor([0.002, -0.01, 0.03, -0.08, 0.2, 0.36, 0.36, 0.2, -0.08, 0.03, -0.01, 0.002], device="cuda")
 side = [torch.cuda.Stream() for _ in range(2)]
@@ -25,7 +24,7 @@ def noise(C, T):
         al = torch.rand(C, device="cuda") + 0.5
         with torch.cuda.stream(s_):
             for _ in range(3):
-                L.fv_debug_aa_snake(xa.data_ptr(), ya.data_ptr(), al.data_ptr(), al.data_ptr(), taps.data_ptr(), taps.data_ptr(), B, C, T, vp(s_.cuda_stream))
+                L.fv_aa_snake_forward(xa.data_ptr(), None, None, ya.data_ptr(), al.data_ptr(), al.data_ptr(), taps.data_ptr(), taps.data_ptr(), B, C, T, vp(s_.cuda_stream))
 for C, T in stages:
     for k in (3, 7, 11):
         for d in (1, 3, 5):

@@ -89,6 +89,7 @@ EXPORTS = (
     "fv_mms_normalize_workspace_bytes", "fv_mms_normalize", "fv_mms_interpolate", "fv_mms_nearest_index",
     "fv_cnxstream_create", "fv_cnxstream_push", "fv_cnxstream_flush", "fv_cnxstream_reset", "fv_cnxstream_pending", "fv_cnxstream_lookahead",
     "fv_cnxstream_state_bytes", "fv_cnxstream_destroy", "fv_cnxstream_plan",
+    "fv_aa_snake_forward", "fv_dwconv_ln_forward",
 )
 
 _i32 = ctypes.c_int32
@@ -273,6 +274,10 @@ def lib() -> ctypes.CDLL:
     L.fv_conv_destroy.restype = None
     L.fv_conv_pair_forward.argtypes = [vp, vp, vp, vp, _i32, _i32, vp]
     L.fv_conv_pair_forward.restype = _i32
+    L.fv_aa_snake_forward.argtypes = [vp] * 8 + [_i32, _i32, ctypes.c_int64, vp]
+    L.fv_aa_snake_forward.restype = _i32
+    L.fv_dwconv_ln_forward.argtypes = [vp] * 6 + [_i32, _i32, ctypes.c_int64, _i32, ctypes.c_float, vp]
+    L.fv_dwconv_ln_forward.restype = _i32
     L.fv_set_precision.argtypes = [vp, _i32]
     L.fv_set_precision.restype = _i32
     L.fv_reload_env.argtypes = []

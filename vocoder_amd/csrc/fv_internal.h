@@ -393,6 +393,21 @@ bool conv_narrow_sum3_ok(int B, int Cin, int T, int Cout, int k, int pad);
 fv_status launch_aa_snake(const float* x, float* y, const float* alpha_eff, const float* inv_beta, const float* up_taps,
                           const float* down_taps, int B, int C, int T, hipStream_t s, const float* x2 = nullptr,
                           const float* x3 = nullptr);
+// The form launch_aa_snake runs on these tensors: vec4_rows is the kernel's `vec4` argument, vec4 what the kernel then takes
+struct AaSnakeForm {
+    int vec4_rows = 0;
+    bool vec4 = false, sum3 = false;
+};
+AaSnakeForm aa_snake_form(const float* x, const float* y, const float* x2, int T);
+const char* aa_snake_form_name(const AaSnakeForm& f);   // "aa_snake<vec4>" | "aa_snake<pair>" [+ " sum3"]
+
+// The kernel launch_dwconv_ln takes for a shape, and its name: "dwconv_ln_tile<k=7 cmax=512 ng=16>" | "dwconv_ln_reg<k=3>" | "dwconv_ln<k=7>"
+struct DwlnForm {
+    enum Kind { TILE, REG, GENERIC } kind = GENERIC;
+    int k = 1, cmax = 0, ng = 0;
+};
+DwlnForm dwln_form(bool has_dw, int C, int T, int k);
+void dwln_form_name(const DwlnForm& f, char* out, size_t cap);
 
 // Depthwise conv (k taps, zero pad) + LayerNorm over channels, fused: y = LN_c(dwconv(x)) * w + b.
 // With dw_w == NULL: plain channels-first LayerNorm.

@@ -548,6 +548,10 @@ __device__ __forceinline__ void aa_snake4_tile(const AaRegs& regs, float* __rest
     }
 }
 
+// The form a launch runs, for the kernel and for the name fv_aa_snake_forward reports: `vec4_rows` is the host's half (the switch, T % 4 == 0 and
+// 16-byte aligned tensors, so that every row starts aligned); three operands and rows shorter than two quads take the pair form.
+__host__ __device__ __forceinline__ bool aa_vec4_form(int vec4_rows, bool sum3, int T) { return vec4_rows && !sum3 && T >= 8; }
+
 __global__ __launch_bounds__(256) void aa_snake_pk_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                           const float* __restrict__ alpha_eff,
                                                           const float* __restrict__ inv_beta,
@@ -567,7 +571,7 @@ __global__ __launch_bounds__(256) void aa_snake_pk_kernel(const float* __restric
     const float* xr = x + row * T;
     float* yr = y + row * T;
     auto interior = [&](int t0) { return t0 >= 6 && t0 + AA_TT + 6 < T; };
-    if (vec4 && !x2 && T >= 8) {
+    if (aa_vec4_form(vec4, x2 != nullptr, T)) {
         const int t0 = tile * AA_TT, t1 = t0 + AA_TT;
         const bool two = tile + 1 < n_tiles;
         const AaRegs r0 = interior(t0) ? aa4_load<false>(xr, t0, T) : aa4_load<true>(xr, t0, T);
@@ -590,6 +594,19 @@ __global__ __launch_bounds__(256) void aa_snake_pk_kernel(const float* __restric
     }
 }
 
+// What a launch on these tensors runs: the kernel's `vec4` argument and the form it selects (one predicate for the launch and the reported name)
+AaSnakeForm aa_snake_form(const float* x, const float* y, const float* x2, int T) {
+    AaSnakeForm f;
+    // interior tiles move 16 bytes per lane when every row starts 16-byte aligned (aa_snake4_tile); FV_AA_VEC4=0: the pair form
+    f.vec4_rows = knobs().aa_vec4 && T % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    f.vec4 = aa_vec4_form(f.vec4_rows, x2 != nullptr, T);
+    f.sum3 = x2 != nullptr;
+    return f;
+}
+const char* aa_snake_form_name(const AaSnakeForm& f) {
+    return f.vec4 ? "aa_snake<vec4>" : (f.sum3 ? "aa_snake<pair> sum3" : "aa_snake<pair>");
+}
+
 fv_status launch_aa_snake(const float* x, float* y, const float* alpha_eff, const float* inv_beta, const float* up_taps,
                           const float* down_taps, int B, int C, int T, hipStream_t s, const float* x2, const float* x3) {
     if ((x2 == nullptr) != (x3 == nullptr)) {
@@ -597,8 +614,7 @@ fv_status launch_aa_snake(const float* x, float* y, const float* alpha_eff, cons
         return FV_ERR_INVALID;
     }
     const int n_tiles = (T + AA_TT - 1) / AA_TT;
-    // interior tiles move 16 bytes per lane when every row starts 16-byte aligned (aa_snake4_tile); FV_AA_VEC4=0: the pair form
-    const int vec4 = knobs().aa_vec4 && T % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    const int vec4 = aa_snake_form(x, y, x2, T).vec4_rows;
     hipLaunchKernelGGL(aa_snake_pk_kernel, dim3((unsigned)((long long)B * C * ((n_tiles + 1) / 2))), dim3(256), 0, s, x, y, alpha_eff,
                        inv_beta, up_taps, down_taps, C, T, n_tiles, vec4, x2, x3);
     FV_HIP_CHECK(hipGetLastError());
@@ -1058,19 +1074,36 @@ fv_status launch_cnx_stem_window(const float* chunk, long long x_bstride, long l
     return FV_OK;
 }
 
+// The kernel a whole-row launch takes (one choice for the launch and for the name fv_dwconv_ln_forward reports): the tile kernel for LayerNorm
+// alone and k = 7 up to 1024 channels, the register kernel for the other k up to 1024 channels, the generic kernel above
+DwlnForm dwln_form(bool has_dw, int C, int T, int k) {
+    DwlnForm f;
+    f.k = has_dw ? k : 1;
+    // per-item tensors below 1 GiB: 32-bit buffer offsets
+    if ((long long)C * T < (1LL << 28) && !knobs().old_dwln && (!has_dw || k == 7) &&
+        dwln_tile_dispatch(C, [&](auto cmax, auto ng) { f.cmax = decltype(cmax)::value, f.ng = decltype(ng)::value; })) {
+        f.kind = DwlnForm::TILE;
+        return f;
+    }
+    f.cmax = f.ng = 0;
+    f.kind = C <= 16 * DWLN_MAXPER ? DwlnForm::REG : DwlnForm::GENERIC;
+    return f;
+}
+void dwln_form_name(const DwlnForm& f, char* out, size_t cap) {
+    if (f.kind == DwlnForm::TILE) std::snprintf(out, cap, "dwconv_ln_tile<k=%d cmax=%d ng=%d>", f.k, f.cmax, f.ng);
+    else std::snprintf(out, cap, "%s<k=%d>", f.kind == DwlnForm::REG ? "dwconv_ln_reg" : "dwconv_ln", f.k);
+}
+
 fv_status launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
                            float* y, int B, int C, int T, int k, float eps, hipStream_t s) {
-    // per-item tensors below 1 GiB: 32-bit buffer offsets
-    if ((long long)C * T < (1LL << 28) && !knobs().old_dwln) {
-        bool done = false;
-        if (!dw_w) done = launch_dwconv_ln_tile<1>(x, nullptr, nullptr, ln_w, ln_b, y, B, C, T, eps, s);
-        else if (k == 7) done = launch_dwconv_ln_tile<7>(x, dw_w, dw_b, ln_w, ln_b, y, B, C, T, eps, s);
-        if (done) {
-            FV_HIP_CHECK(hipGetLastError());
-            return FV_OK;
-        }
+    const DwlnForm form = dwln_form(dw_w != nullptr, C, T, k);
+    if (form.kind == DwlnForm::TILE) {
+        if (!dw_w) launch_dwconv_ln_tile<1>(x, nullptr, nullptr, ln_w, ln_b, y, B, C, T, eps, s);
+        else launch_dwconv_ln_tile<7>(x, dw_w, dw_b, ln_w, ln_b, y, B, C, T, eps, s);
+        FV_HIP_CHECK(hipGetLastError());
+        return FV_OK;
     }
-    if (C <= 16 * DWLN_MAXPER) {
+    if (form.kind == DwlnForm::REG) {
         const int n16 = (T + 15) / 16;
         hipLaunchKernelGGL(dwconv_ln_reg_kernel, dim3(B * n16), dim3(256), 0, s, x, dw_w, dw_b, ln_w, ln_b, y, C, T, k, eps,
                            n16);
@@ -1400,10 +1433,6 @@ __global__ __launch_bounds__(256) void lds_poison_kernel(float* sink) {
     for (int i = threadIdx.x; i < 16000; i += 256) junk[i] = __uint_as_float(0x7fc00000u | (unsigned)i);
     __syncthreads();
     if (sink && junk[(threadIdx.x * 37 + blockIdx.x) % 16000] == 1.0f) sink[0] = 1.0f;   // keeps the stores alive
-}
-extern "C" __attribute__((visibility("default"))) int fv_debug_aa_snake(const float* x, float* y, const float* alpha, const float* inv_beta,
-                                                                       const float* up, const float* down, int B, int C, int T, void* stream) {
-    return (int)launch_aa_snake(x, y, alpha, inv_beta, up, down, B, C, T, (hipStream_t)stream);
 }
 extern "C" __attribute__((visibility("default"))) void fv_debug_poison_lds(void* stream) {
     hipLaunchKernelGGL(lds_poison_kernel, dim3(num_cus() * 2), dim3(256), 0, (hipStream_t)stream, (float*)nullptr);

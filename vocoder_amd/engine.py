@@ -1218,3 +1218,71 @@ class FusedConv(_Handle):
             check(self._lib.fv_conv_pair_forward(self._h, c2._h, x.data_ptr(), out.data_ptr(), B, T,
                                                  _stream_ptr(x.device)))
         return out
+
+
+def _helper_vec(t: torch.Tensor | None, what: str, n: int):
+    """A per-channel (or tap) vector of n floats -> (tensor kept alive, pointer); None stays None."""
+    if t is None:
+        return None, None
+    _require_cuda(t, what)
+    t = t.contiguous()
+    if t.dtype != torch.float32 or t.numel() != n:
+        raise ValueError(f"{what}: expected {n} float32 values, got {t.numel()} of {t.dtype}")
+    return t, t.data_ptr()
+
+
+def _helper_rows(x: torch.Tensor, what: str, shape=None) -> torch.Tensor:
+    """A (B, C, T) float32 operand as the kernel will read it: a contiguous tensor or view goes in as it is, at its own data_ptr()."""
+    _require_cuda(x, what)
+    if x.dtype != torch.float32 or x.dim() != 3 or (shape is not None and tuple(x.shape) != tuple(shape)):
+        raise ValueError(f"{what}: expected a float32 tensor of shape {tuple(shape) if shape is not None else '(B, C, T)'}, "
+                         f"got {tuple(x.shape)} of {x.dtype}")
+    return x.contiguous()   # (no copy of a contiguous view: its offset and alignment reach the kernel)
+
+
+def _helper_out(out: torch.Tensor | None, x: torch.Tensor, what: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty_like(x)
+    _require_cuda(out, what)
+    if out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous float32 tensor of shape {tuple(x.shape)} on {x.device}")
+    return out
+
+
+def aa_snake(x: torch.Tensor, alpha: torch.Tensor, inv_beta: torch.Tensor, up: torch.Tensor, down: torch.Tensor,
+             x2: torch.Tensor | None = None, x3: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """BigVGAN's Activation1d(SnakeBeta) on its own (``fv_aa_snake_forward``): ``alpha`` = exp(alpha) and ``inv_beta`` = 1 / (exp(beta) + 1e-9)
+    per channel, ``up`` / ``down`` the 12 filter taps; with ``x2`` and ``x3`` the input is ((x + x2) + x3) / 3.  ``out`` must not overlap an
+    input (the library refuses it).  ``_lib.last_kernel()`` names the form that ran."""
+    x = _helper_rows(x, "aa_snake x")
+    B, C, T = x.shape
+    x2 = None if x2 is None else _helper_rows(x2, "aa_snake x2", x.shape)
+    x3 = None if x3 is None else _helper_rows(x3, "aa_snake x3", x.shape)
+    keep = [_helper_vec(alpha, "aa_snake alpha", C), _helper_vec(inv_beta, "aa_snake inv_beta", C), _helper_vec(up, "aa_snake up", 12),
+            _helper_vec(down, "aa_snake down", 12)]
+    out = _helper_out(out, x, "aa_snake")
+    with torch.cuda.device(x.device):
+        check(_lib.lib().fv_aa_snake_forward(x.data_ptr(), None if x2 is None else x2.data_ptr(), None if x3 is None else x3.data_ptr(),
+                                             out.data_ptr(), keep[0][1], keep[1][1], keep[2][1], keep[3][1], B, C, T, _stream_ptr(x.device)))
+    return out
+
+
+def dwconv_layernorm(x: torch.Tensor, dw_w: torch.Tensor | None, dw_b: torch.Tensor | None, ln_w: torch.Tensor, ln_b: torch.Tensor,
+                     eps: float = 1e-6, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Depthwise Conv1d ('same' zero padding) + LayerNorm over channels on its own (``fv_dwconv_ln_forward``): ``dw_w`` is (C, k) or (C, 1, k)
+    with k odd, ``dw_b`` may be None; ``dw_w`` None: the channels-first LayerNorm alone.  ``out`` must not overlap an input (the library
+    refuses it).  ``_lib.last_kernel()`` names the kernel that ran."""
+    x = _helper_rows(x, "dwconv_layernorm x")
+    B, C, T = x.shape
+    k = 1
+    if dw_w is not None:
+        if dw_w.dim() not in (2, 3) or dw_w.shape[0] != C or dw_w.numel() % C:
+            raise ValueError(f"dwconv_layernorm dw_w: expected ({C}, k) or ({C}, 1, k), got {tuple(dw_w.shape)}")
+        k = dw_w.numel() // C
+    keep = [_helper_vec(dw_w, "dwconv_layernorm dw_w", C * k), _helper_vec(dw_b, "dwconv_layernorm dw_b", C),
+            _helper_vec(ln_w, "dwconv_layernorm ln_w", C), _helper_vec(ln_b, "dwconv_layernorm ln_b", C)]
+    out = _helper_out(out, x, "dwconv_layernorm")
+    with torch.cuda.device(x.device):
+        check(_lib.lib().fv_dwconv_ln_forward(x.data_ptr(), keep[0][1], keep[1][1], keep[2][1], keep[3][1], out.data_ptr(), B, C, T, k,
+                                              float(eps), _stream_ptr(x.device)))
+    return out
