@@ -1703,6 +1703,70 @@ FV_API void fv_cnxstream_destroy(fv_cnxstream* s);
  * slots for max_chunk, or -1 for arguments outside 0 <= N0 <= N1, 0 <= level <= levels, max_chunk >= 1, out != NULL. */
 FV_API int32_t fv_cnxstream_plan(int64_t N0, int64_t N1, int32_t flush, int32_t level, int32_t max_chunk, int32_t levels, int64_t* out);
 
+/* -------- ConvNeXt backbone, layer by layer, for sessions that advance independently (fv_cnxpool_*) --------
+ * What fv_cnxstream_* is to rows in lockstep, for `sessions` slots with their own N, E and flushed flag, as fv_wnpool_* is to fv_wnstream_*.
+ * A step is a list of items (fv_wavpool_item: session, `samples` counting FRAMES here, flush: the utterance ends with these frames), each
+ * session at most once.  Per item N' = N + frames and E' = flush ? N' : max(E, N' - R); the item emits the frames [E, E').  A flush at
+ * N' = 0 emits nothing.  After its flush a slot refuses items (FV_ERR_STATE) until fv_cnxpool_reset.
+ *   A slot's state is its own row of the input ring and of every block's ring, (sessions, dim, cap), cap the power of two >= 6 + S,
+ * S = max_chunk + R (where the stream has max(max_chunk, R): an item may flush together with its last frames, and a level's frontier then
+ * moves by up to max_chunk + R frames in one step).  A step plans every item at every level on the host, from its slot's (N, N', flush)
+ * with the stream's plan, and runs per level over the columns that are new at that level: the depthwise conv + LayerNorm as the pool form
+ * of the whole-row tile kernel, one launch per fv_cnxpool_table_size() items, each entry reading and filing into its slot's ring row; H and
+ * the residual are PACKED, (dim, P) with P the sum of the items' new columns at that level, and everything per-frame (the LayerNorms, the
+ * pointwise convs) runs the whole-row kernels over the packed buffer as one row of P columns.  The stem conv runs over (count, C_in, Wmax),
+ * Wmax = 6 + the step's longest chunk: row i holds the last 6 input frames of session i ++ its chunk ++ exact zeros.
+ *   Launches of a step in which every level has work, with T = ceil(count / fv_cnxpool_table_size()):
+ *       stem: T window launches + the conv + its LayerNorm;  every block: T depthwise launches + 2 pointwise launches;
+ *       every stage change: 2;  emission: the final LayerNorm + ceil(count / 32) crop launches
+ *   = T (1 + L) + 2 + 2 L + 2 (num_stages - 1) + 1 + ceil(count / 32).  With T = 1 that is the layer stream's count for the same call — 22
+ * for the default encoder (one stage of 6 blocks), 33 for the default backbone (6 + 3 blocks) — plus the crop, which stands in place of the
+ * stream's optional 2-D copy.  A level at which no item of the step has a new column or chunk frame launches nothing; fv_cnxpool_launches
+ * reports what the last accepted step enqueued.
+ *   The claim: a session's concatenated frames are BIT-identical to fv_forward over its whole utterance with fv_set_batch_invariant(e, 1)
+ * — and, where input_channels == dims[0] (a C -> C stem, which has a Winograd form), with fv_set_conv_algorithm(e, FV_CONV_ALGO_DIRECT)
+ * as well: the pool runs the stem as direct sums, as the stream does — whatever the other sessions do, in any item order, after any
+ * fv_cnxpool_reset(session), for utterances with max(dims) * T < 2^28.
+ *   A step neither allocates device memory, copies to the host nor synchronises.  All device state is allocated by fv_cnxpool_create;
+ * fv_cnxpool_state_bytes reports it.  The whole step is validated before any counter moves or anything is enqueued, and a refusal names
+ * the item and the session: a refused step leaves every slot as it was.  The pool reads the engine's weights: destroy it before the engine. */
+typedef struct fv_cnxpool fv_cnxpool;
+/* Refused by name: what fv_cnxstream_create refuses (an engine that is not finalized or in f16x3 precision: FV_ERR_STATE; a model other
+ * than FV_MODEL_CONVNEXT, kernel_size != 7, a stage wider than 1024 channels, max_chunk outside [1, 2^16]: FV_ERR_INVALID), sessions
+ * outside [1, 65535], and sizes that leave the kernels' 32-bit addressing — 4 max(dims) sessions (max_chunk + R) >= 2^29 floats, a ring row
+ * of max(dims, input_channels) * cap >= 2^28 floats or a stem window of 2^29 floats (FV_ERR_INVALID). */
+FV_API fv_status fv_cnxpool_create(fv_engine* e, int32_t sessions, int32_t max_chunk, fv_cnxpool** out);
+/* Pure host, no GPU: what a step of `items` would emit on slots with the counters received[s], emitted[s], flushed[s] (flushed may be NULL:
+ * none is) of a backbone of lookahead `reach`.  Writes E' - E per item into frames_out and returns the largest, or the negative fv_status of
+ * a refusal: a session outside [0, sessions), a duplicate session, frames outside [0, max_chunk], more than 2^30 frames in one utterance
+ * (FV_ERR_INVALID), an item for a flushed slot (FV_ERR_STATE).  sessions in [1, 65535], max_chunk in [1, 2^20].  Changes nothing. */
+FV_API int64_t fv_cnxpool_plan(int32_t reach, int32_t sessions, int32_t max_chunk, const int64_t* received, const int64_t* emitted,
+                               const int32_t* flushed, const fv_wavpool_item* items, int32_t count, int64_t* frames_out);
+/* d_x: (count, input_channels, x_row_stride): frame j of channel ch of item i's chunk at d_x[i * x_item_stride + ch * x_row_stride + j],
+ * x_row_stride >= the longest chunk; what follows an item's frames in its row, NaN included, is never loaded; NULL when no item has frames.
+ * d_y: (count, out_channels, out_cols), out_cols >= the largest E' - E: row i receives item i's frames first and exactly 0.0f after them,
+ * every element written; may be NULL when out_cols = 0.  frames_out (may be NULL) receives E' - E per item.  The plan's refusals apply, and
+ * null buffers, a row stride shorter than a chunk and out_cols below the largest E' - E are refused as well.  Asynchronous on `stream`. */
+FV_API fv_status fv_cnxpool_step(fv_cnxpool* p, const fv_wavpool_item* items, int32_t count, const float* d_x, int64_t x_item_stride,
+                                 int64_t x_row_stride, float* d_y, int32_t out_cols, int64_t* frames_out, void* stream);
+/* N = E = 0 and the flushed flag cleared for one slot; no device work (nothing at or past a frontier or before frame 0 is ever read). */
+FV_API fv_status fv_cnxpool_reset(fv_cnxpool* p, int32_t session);
+/* N, E and N - E of one slot; -1 for NULL or a session out of range. */
+FV_API int64_t fv_cnxpool_received(const fv_cnxpool* p, int32_t session);
+FV_API int64_t fv_cnxpool_emitted(const fv_cnxpool* p, int32_t session);
+FV_API int64_t fv_cnxpool_pending(const fv_cnxpool* p, int32_t session);
+/* R; -1 for NULL. */
+FV_API int32_t fv_cnxpool_lookahead(const fv_cnxpool* p);
+/* The most one item can emit in a step: max_chunk + R (a flush with max_chunk frames after R pending ones); -1 for NULL. */
+FV_API int64_t fv_cnxpool_max_frames(const fv_cnxpool* p);
+/* Host counter: the kernel launches the last accepted step enqueued (the formula above); -1 for NULL. */
+FV_API int32_t fv_cnxpool_launches(const fv_cnxpool* p);
+/* Bytes of device memory the pool holds; -1 for NULL. */
+FV_API int64_t fv_cnxpool_state_bytes(const fv_cnxpool* p);
+/* Items per by-value launch table of the depthwise and the stem-window kernel. */
+FV_API int32_t fv_cnxpool_table_size(void);
+FV_API void fv_cnxpool_destroy(fv_cnxpool* p);
+
 /* -------- per-launch timing (measurement aid; bench.py's roofline leg) --------
  * Between fv_profile_begin and fv_profile_end every kernel that fv_forward enqueues is bracketed by hipEvents recorded
  * on the launch stream.  fv_profile_end synchronises them and writes a JSON array

@@ -89,6 +89,9 @@ EXPORTS = (
     "fv_mms_normalize_workspace_bytes", "fv_mms_normalize", "fv_mms_interpolate", "fv_mms_nearest_index",
     "fv_cnxstream_create", "fv_cnxstream_push", "fv_cnxstream_flush", "fv_cnxstream_reset", "fv_cnxstream_pending", "fv_cnxstream_lookahead",
     "fv_cnxstream_state_bytes", "fv_cnxstream_destroy", "fv_cnxstream_plan",
+    "fv_cnxpool_create", "fv_cnxpool_plan", "fv_cnxpool_step", "fv_cnxpool_reset", "fv_cnxpool_received", "fv_cnxpool_emitted",
+    "fv_cnxpool_pending", "fv_cnxpool_lookahead", "fv_cnxpool_max_frames", "fv_cnxpool_launches", "fv_cnxpool_state_bytes",
+    "fv_cnxpool_table_size", "fv_cnxpool_destroy",
     "fv_aa_snake_forward", "fv_dwconv_ln_forward",
 )
 
@@ -606,6 +609,29 @@ def lib() -> ctypes.CDLL:
     L.fv_cnxstream_destroy.restype = None
     L.fv_cnxstream_plan.argtypes = [i64, i64, _i32, _i32, _i32, _i32, i64p]
     L.fv_cnxstream_plan.restype = _i32
+    L.fv_cnxpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.fv_cnxpool_create.restype = _i32
+    L.fv_cnxpool_plan.argtypes = [_i32, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]
+    L.fv_cnxpool_plan.restype = i64
+    L.fv_cnxpool_step.argtypes = [vp, wip, _i32, vp, i64, i64, vp, _i32, i64p, vp]
+    L.fv_cnxpool_step.restype = _i32
+    L.fv_cnxpool_reset.argtypes = [vp, _i32]
+    L.fv_cnxpool_reset.restype = _i32
+    for name in ("received", "emitted", "pending"):
+        getattr(L, "fv_cnxpool_" + name).argtypes = [vp, _i32]
+        getattr(L, "fv_cnxpool_" + name).restype = i64
+    L.fv_cnxpool_lookahead.argtypes = [vp]
+    L.fv_cnxpool_lookahead.restype = _i32
+    L.fv_cnxpool_max_frames.argtypes = [vp]
+    L.fv_cnxpool_max_frames.restype = i64
+    L.fv_cnxpool_launches.argtypes = [vp]
+    L.fv_cnxpool_launches.restype = _i32
+    L.fv_cnxpool_state_bytes.argtypes = [vp]
+    L.fv_cnxpool_state_bytes.restype = i64
+    L.fv_cnxpool_table_size.argtypes = []
+    L.fv_cnxpool_table_size.restype = _i32
+    L.fv_cnxpool_destroy.argtypes = [vp]
+    L.fv_cnxpool_destroy.restype = None
     L.fv_wnpool_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
     L.fv_wnpool_create.restype = _i32
     L.fv_wnpool_plan.argtypes = [_i32, _i32, _i32, i64p, i64p, i32p, wip, _i32, i64p]

@@ -11,7 +11,8 @@ drop-in modules, every stage on the HIP engine; the quantiser is ``modules.quant
     python -m vocoder_amd.codec encode -i a.wav -o out/ --chunk-samples 4096 --batch-invariant    # through encode_stream (ConvNeXt layer stream)
 
 ``decode_stream`` / ``decode_pool`` serve the decode direction chunk by chunk (``CodecDecodeStream``, ``CodecDecodePool``): the ring in front of
-the decoder keeps the codes, not the latent.
+the decoder keeps the codes, not the latent.  ``encode_pool(layers=True)`` and ``decode_pool(backbone="layers")`` run a ConvNeXt encoder /
+backbone as its layer pool (``ConvNeXtEncoder.layer_pool``): per-slot rings, only the new frames, the batch-invariant ``forward``'s bits.
 
 The architecture defaults to configs/model/vqvae.yaml's (vocos-small-vae at 24000_2048_3072, 512 latent channels, 4096 codes, one
 quantiser); ``vocoder_amd.inference``'s command line is untouched.
@@ -66,11 +67,12 @@ class VQVAECodec(nn.Module):
         ``encode``'s."""
         return CodecEncodeStream(self, batch, max_chunk_samples)
 
-    def encode_pool(self, sessions: int, max_chunk_samples: int = 4096) -> "CodecEncodePool":
+    def encode_pool(self, sessions: int, max_chunk_samples: int = 4096, layers: bool = False) -> "CodecEncodePool":
         """``encode`` for ``sessions`` live sources that advance at their own pace (``CodecEncodePool``): one step serves any subset of them in
-        the launches one ``encode_stream`` push takes.  The same encoders as ``encode_stream``; with the front-end in its batch-invariant mode
-        a session's concatenated codes are ``encode``'s of its whole utterance."""
-        return CodecEncodePool(self, sessions, max_chunk_samples)
+        the launches one ``encode_stream`` push takes.  A ``PosteriorEncoder`` by default; ``layers=True`` takes a ``ConvNeXtEncoder`` with
+        ``batch_invariant = True`` through its ``layer_pool``.  With the front-end in its batch-invariant mode a session's concatenated codes
+        are ``encode``'s of its whole utterance."""
+        return CodecEncodePool(self, sessions, max_chunk_samples, layers)
 
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
         y = self.decoder(self.vq.from_codes(codes)[0])
@@ -82,9 +84,11 @@ class VQVAECodec(nn.Module):
         as its ``layer_stream`` — only the new frames, with the bits of its batch-invariant ``forward``."""
         return CodecDecodeStream(self.decoder, self.vq, batch, max_chunk_frames, backbone)
 
-    def decode_pool(self, sessions: int, max_chunk_frames: int = 64) -> "CodecDecodePool":
-        """``decode`` for ``sessions`` clients that advance at their own pace (``CodecDecodePool``): one step serves any subset of them."""
-        return CodecDecodePool(self.decoder, self.vq, sessions, max_chunk_frames)
+    def decode_pool(self, sessions: int, max_chunk_frames: int = 64, backbone: str = "window") -> "CodecDecodePool":
+        """``decode`` for ``sessions`` clients that advance at their own pace (``CodecDecodePool``): one step serves any subset of them.
+        ``backbone`` as in ``decode_stream``: ``"window"`` recomputes the backbone's window per session and step, ``"layers"`` runs the ConvNeXt
+        backbone of a two-stage decoder as its ``layer_pool`` — only the new frames, with the bits of its batch-invariant ``forward``."""
+        return CodecDecodePool(self.decoder, self.vq, sessions, max_chunk_frames, backbone)
 
     def forward(self, audio: torch.Tensor, mask=None):
         """vae.py:80-109: ``(fake_audio, 0)``, trimmed / zero-padded to the input's length, which it may miss by a hop at most."""
@@ -124,20 +128,24 @@ class VQVAECodec(nn.Module):
         return self.load_state_dict(own, strict=True)
 
 
-def _streaming_encoder(codec: VQVAECodec, what: str) -> nn.Module:
+def _streaming_encoder(codec: VQVAECodec, what: str, layers: bool = False) -> nn.Module:
     """The encoder of a codec that can encode chunk by chunk with ``encode``'s codes; ``what`` (``encode_stream`` / ``encode_pool``) refuses
-    the others by name."""
+    the others by name.  ``layers`` (``encode_pool(layers=True)``): the pool of a layered encoder is its ``layer_pool``."""
     enc, name = codec.encoder, type(codec.encoder).__name__
     if getattr(enc, "takes_audio", False):
         raise ValueError(f"{what}: {name} takes raw audio (takes_audio), not a streamed spectrogram: it has no streaming encode")
     layered = hasattr(enc, "layer_stream")        # ConvNeXtEncoder: bit-exact through layer_stream, in its batch-invariant mode only
+    hint = layered and (what == "encode_stream" or layers)
     if not getattr(enc, "stream_is_bit_exact", False):
         raise ValueError(f"{what}: {name}.stream() is not bit-exact — a windowed engine stream promises 2e-5, not forward's bits, so "
                          "codes could differ from encode(); use a PosteriorEncoder (build_vqvae(encoder='posterior'))"
-                         + (" or set encoder.batch_invariant = True" if layered and what == "encode_stream" else "")
+                         + (" or set encoder.batch_invariant = True" if hint else "")
                          + (" and encoder.conv_algorithm = 'direct' (its C -> C stem has a Winograd form, whose bits depend on the launch)"
-                            if layered and what == "encode_stream" and getattr(enc, "stem_has_winograd_form", False) else ""))
-    if layered and what != "encode_stream":
+                            if hint and getattr(enc, "stem_has_winograd_form", False) else ""))
+    if layers and not hasattr(enc, "layer_pool"):
+        raise ValueError(f"{what}: layers=True needs an encoder with a layer pool (a ConvNeXtEncoder); {name} has no layer_pool — call "
+                         f"{what}() without it")
+    if layered and what != "encode_stream" and not layers:
         raise ValueError(f"{what}: {name} has a layer stream (encode_stream) but its pool form is not built: there is no session pool of "
                          "layer streams; use encode_stream per source, or a PosteriorEncoder")
     if codec.frontend is None:
@@ -146,19 +154,20 @@ def _streaming_encoder(codec: VQVAECodec, what: str) -> nn.Module:
 
 
 class CodecEncodePool:
-    """``VQVAECodec.encode`` for live sources that advance independently: ``frontend.wav_pool()`` -> ``encoder.pool()`` -> ``vq.encode``.  The
+    """``VQVAECodec.encode`` for live sources that advance independently: ``frontend.wav_pool()`` -> ``encoder.pool()`` (with ``layers``:
+    ``encoder.layer_pool()``, a ``ConvNeXtEncoder`` in its batch-invariant mode) -> ``vq.encode``.  The
     front-end's padded frames go straight into the encoder pool's ``step_padded`` and its padded latents into the quantiser with the frame
     counts per item: nothing goes through the host.  ``step(items)`` takes ``(session, wave, flush)`` tuples — ``wave``: 1-D, at most
     ``max_chunk_samples`` samples, or ``None``; ``flush``: the utterance ends with them — and returns per item the int64 codes of the latent
     frames that are final, ``(k,)`` or ``(n_q, k)`` for the residual form, ``k`` possibly 0.  Both stages are planned before either is
     launched, so a refused step moves neither pool.  ``reset(session)`` starts a slot's next utterance."""
 
-    def __init__(self, codec: VQVAECodec, sessions: int, max_chunk_samples: int = 4096):
-        enc = _streaming_encoder(codec, "encode_pool")
+    def __init__(self, codec: VQVAECodec, sessions: int, max_chunk_samples: int = 4096, layers: bool = False):
+        enc = _streaming_encoder(codec, "encode_pool", bool(layers))
         self._vq = codec.vq
         self.sessions, self.max_chunk_samples = int(sessions), int(max_chunk_samples)
         self.wav_pool = codec.frontend.wav_pool(self.sessions, self.max_chunk_samples)
-        self.enc_pool = enc.pool(self.sessions, self.wav_pool.max_frames)
+        self.enc_pool = (enc.layer_pool if layers else enc.pool)(self.sessions, self.wav_pool.max_frames)
 
     def received_samples(self, session: int) -> int:
         return self.wav_pool.received_samples(session)
@@ -170,14 +179,21 @@ class CodecEncodePool:
         wp, ep = self.wav_pool, self.enc_pool
         wp._check_open(), ep._check_open()
         meta, chunks = _gather(items, wp._engine.device, _require_cuda, "CodecEncodePool.step")
-        frames = wp.counters.plan(meta)                         # both plans before either launch: a refusal moves neither pool
-        enc_items = [(s, f, flush) for (s, _, flush), f in zip(meta, frames)]
+        codes, emit = self.step_padded(meta, chunks)
+        return [codes[..., i, :k] for i, k in enumerate(emit)]
+
+    def step_padded(self, items, chunks: "torch.Tensor | None") -> tuple:
+        """The step on padded buffers: ``items``: ``(session, samples, flush)`` integers; ``chunks``: ``(count, longest)`` samples, item i's
+        first in row i, or ``None`` when no item has samples.  Returns ``(codes (..., count, k_max), latent frames emitted per item)``."""
+        wp, ep = self.wav_pool, self.enc_pool
+        wp._check_open(), ep._check_open()
+        frames = wp.counters.plan(items)                        # both plans before either launch: a refusal moves neither pool
+        enc_items = [(s, f, flush) for (s, _, flush), f in zip(items, frames)]
         ep.counters.plan(enc_items)
-        spec, _ = wp.step_padded(meta, chunks)
+        spec, _ = wp.step_padded(items, chunks)
         z, emit = ep.step_padded(enc_items, spec if spec.numel() else None)
         z = z[0] if isinstance(z, tuple) else z
-        codes = self._vq.encode(z, emit)
-        return [codes[..., i, :k] for i, k in enumerate(emit)]
+        return self._vq.encode(z, emit), emit
 
     def reset(self, session: int) -> None:
         self.wav_pool.reset(session)
@@ -392,12 +408,23 @@ class CodecDecodePool:
     tensor ``(C_out, k * hop)`` per item, ``k`` possibly 0.  The first stage is a ``CodeSessionPool``: a slot's ring keeps ``n_q`` int32 per
     frame, not the latent's channels.  A two-stage decoder hands the backbone pool's padded frames to ``head.session_pool()``'s
     ``step_padded`` on the device; both stages are planned before either is launched, so a refused step moves neither pool.
-    ``reset(session)`` starts a slot's next utterance."""
+    ``reset(session)`` starts a slot's next utterance.  ``backbone="layers"``: the first stage of a two-stage decoder is ``vq.from_codes`` on
+    the step's padded codes and the ConvNeXt backbone's ``layer_pool`` (``_LayerBackbonePool``) — only the frames that are new, with the bits
+    of the backbone's batch-invariant ``forward``; no ring keeps codes, the backbone's rings hold its blocks' last columns."""
 
-    def __init__(self, decoder: nn.Module, vq, sessions: int, max_chunk_frames: int = 64):
+    def __init__(self, decoder: nn.Module, vq, sessions: int, max_chunk_frames: int = 64, backbone: str = "window"):
         stages = _decoder_stages(decoder, vq, "decode_pool")
         self.sessions, self.max_chunk_frames = int(sessions), int(max_chunk_frames)
-        self.codes = stages[0].code_pool(vq, self.sessions, self.max_chunk_frames)
+        if backbone not in ("window", "layers"):
+            raise ValueError(f"decode_pool: backbone must be 'window' or 'layers', got {backbone!r}")
+        self.backbone = backbone
+        if backbone == "layers":
+            if len(stages) != 2 or not hasattr(stages[0], "layer_pool"):
+                raise ValueError("decode_pool: backbone='layers' needs a two-stage decoder whose backbone has a layer pool "
+                                 f"(a ConvNeXtEncoder); got {[type(m).__name__ for m in stages]}")
+            self.codes = _LayerBackbonePool(vq, stages[0].layer_pool(self.sessions, self.max_chunk_frames))
+        else:
+            self.codes = stages[0].code_pool(vq, self.sessions, self.max_chunk_frames)
         self.head = None
         if len(stages) == 2:
             # an item that ends its utterance emits its own frames and the backbone's lookahead in one step
@@ -425,12 +452,23 @@ class CodecDecodePool:
         meta, chunks, tmpl = cp.gather(items, validate)
         if tmpl is not None:
             raise ValueError("CodecDecodePool.step: a template belongs to a single-engine decoder")
-        frames = cp.state.plan(meta).emit_frames                  # both plans before either launch: a refusal moves neither pool
-        head_items = [(s, k, flush) for (s, _, flush), k in zip(meta, frames)]
-        hp.state.plan(head_items)
-        z, emit = cp.step_padded(meta, chunks)
-        out, emit = hp.step_padded(head_items, z if z.numel() else None)
+        out, emit = self.step_padded(meta, chunks)
         return [out[i, :, :k * hp.hop] for i, k in enumerate(emit)]
+
+    def step_padded(self, items, chunks: "torch.Tensor | None") -> tuple:
+        """The step of a two-stage decoder on padded codes: ``items``: ``(session, frames, flush)`` integers; ``chunks``: contiguous int32
+        ``(num_quantizers, count, longest)``, item i's codes first in row i of every layer, or ``None`` when no item has frames.  Returns
+        ``(audio (count, C_out, k_max * hop), frames emitted per item)``.  The codes are not validated here."""
+        cp, hp = self.codes, self.head
+        if hp is None:
+            raise ValueError("CodecDecodePool.step_padded: a single-engine decoder's pool is self.codes: call its step_padded")
+        cp._check_open(), hp._check_open()
+        items = [(int(s), int(n), bool(f)) for s, n, f in items]
+        frames = cp.state.plan(items).emit_frames                 # every plan before the first launch: a refusal moves no pool
+        head_items = [(s, k, flush) for (s, _, flush), k in zip(items, frames)]
+        hp.state.plan(head_items)
+        z, _ = cp.step_padded(items, chunks)
+        return hp.step_padded(head_items, z if z.numel() else None)
 
     def reset(self, session: int) -> None:
         self.codes.reset(session)
@@ -447,6 +485,90 @@ class CodecDecodePool:
 
     def __exit__(self, *exc) -> None:
         self.close()
+
+
+class _PlanFrames:
+    def __init__(self, emit_frames: list):
+        self.emit_frames = emit_frames
+
+
+class _LayerPoolState:
+    """The face of a ``SessionPool``'s ``state`` over a layer pool's counters: ``plan(items).emit_frames``."""
+
+    def __init__(self, counters):
+        self._counters = counters
+
+    def plan(self, items) -> _PlanFrames:
+        return _PlanFrames(self._counters.plan(items))
+
+
+class _LayerBackbonePool:
+    """The first stage of ``CodecDecodePool(backbone="layers")`` with the face of a ``CodeSessionPool``: ``gather`` validates and pads the
+    items' codes — with code 0, a valid code whose frames the pool never reads — and ``step_padded`` runs ``vq.from_codes`` on the padded
+    ``(n_q, count, n_max)`` codes and hands the latents to ``backbone.layer_pool().step_padded``.  Nothing is kept of the codes."""
+    hop = 1
+
+    def __init__(self, vq, pool):
+        if not (hasattr(vq, "from_codes") and hasattr(vq, "num_quantizers") and hasattr(vq, "codebook_size")):
+            raise ValueError("decode_pool: expected one of the package's quantisers (modules.quantizers), got " + type(vq).__name__)
+        self._vq, self.pool = vq, pool
+        self.num_quantizers, self.codebook_size = int(vq.num_quantizers), int(vq.codebook_size)
+        self.sessions, self.max_chunk_frames, self.out_channels = pool.sessions, pool.max_chunk_frames, pool.out_channels
+        self.lookahead_frames = pool.lookahead_frames
+        self.state = _LayerPoolState(pool.counters)
+
+    ring_bytes = property(lambda self: self.pool.state_bytes)
+
+    def received_frames(self, session: int) -> int:
+        return self.pool.received_frames(session)
+
+    def emitted_frames(self, session: int) -> int:
+        return self.pool.emitted_frames(session)
+
+    def _check_open(self) -> None:
+        self.pool._check_open()
+
+    def gather(self, items, validate: bool = True):
+        """``step``'s items -> ``(the (session, n, flush) integers, the padded int32 codes (num_quantizers, count, longest) or None, None)``.
+        Nothing moves."""
+        from .engine import _validate_codes, code_chunk
+        what, dev = "CodecDecodePool.step", self.pool._engine.device
+        meta, rows = [], []
+        for it in map(tuple, items):
+            s, codes, flush = it[0], it[1], it[2] if len(it) > 2 else False
+            if len(it) > 3 and it[3] is not None:
+                raise ValueError(f"{what}: a template belongs to a single-engine decoder")
+            n = 0
+            if codes is not None:
+                codes, n = code_chunk(codes, self.num_quantizers, None, self.max_chunk_frames, what)
+                if validate:
+                    _validate_codes(codes, self.codebook_size, what)
+            rows.append(codes)
+            meta.append((int(s), n, bool(flush)))
+        longest = max((n for _, n, _ in meta), default=0)
+        chunks = None
+        if longest:
+            chunks = torch.zeros((self.num_quantizers, len(meta), longest), dtype=torch.int32, device=dev)
+            for i, codes in enumerate(rows):
+                if codes is not None and codes.shape[2]:
+                    chunks[:codes.shape[0], i, :codes.shape[2]] = codes[:, 0]
+                    chunks[codes.shape[0]:, i, :codes.shape[2]] = -1        # layers the item does not give: no code
+        return meta, chunks, None
+
+    def step_padded(self, items, chunks: "torch.Tensor | None", templates=None, out=None) -> tuple:
+        z = None if chunks is None else self._vq.from_codes(chunks)[0]
+        return self.pool.step_padded(items, z, out)
+
+    def step(self, items, validate: bool = True) -> list:
+        meta, chunks, _ = self.gather(items, validate)
+        out, emit = self.step_padded(meta, chunks)
+        return [out[i, :, :k] for i, k in enumerate(emit)]
+
+    def reset(self, session: int) -> None:
+        self.pool.reset(session)
+
+    def close(self) -> None:
+        self.pool.close()
 
 
 def build_vqvae(n_fft: int = 3072, hop_length: int = 2048, win_length: int = 3072, latent_size: int = 512, codebook_size: int = 4096,

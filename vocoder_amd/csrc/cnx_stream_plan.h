@@ -25,6 +25,8 @@ inline long long cnx_front(long long N, int level, bool flush) {
 inline int cnx_reach(int levels_above_stem) { return kCnxPad * (levels_above_stem + 1); }
 // the most frames one call adds to a frontier
 inline int cnx_step(int max_chunk, int L) { return max_chunk > cnx_reach(L) ? max_chunk : cnx_reach(L); }
+// The session pool (fv_cnxpool_*): an item may carry frames AND flush in one step, so a frontier moves by up to max_chunk + R frames
+inline int cnx_pool_step(int max_chunk, int L) { return max_chunk + cnx_reach(L); }
 inline int cnx_ring_cap(int step) {
     int cap = 1;
     while (cap < kCnxHalo + step) cap <<= 1;

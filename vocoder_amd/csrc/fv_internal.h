@@ -431,6 +431,30 @@ fv_status launch_dwconv_ln_stream(const DwStreamRun& r, const float* dw_w, const
 // (element (b, ci, t) at b * x_bstride + ci * x_rstride + t), which is filed into the ring
 fv_status launch_cnx_stem_window(const float* chunk, long long x_bstride, long long x_rstride, float* ring, float* win, int B, int C, int cap,
                                  long long N0, int c, hipStream_t s);
+// The pool form (fv_cnxpool_*): one block's launches of a step, kCnxPoolBlock entries per launch.  An entry is one item at one level:
+// cnx_level_plan's values for its slot's (N0, N1, flush), the slot whose ring row (ring + slot * C * cap) it reads and files into, where frame
+// in0 of its chunk lies (an element offset into `chunk`; chunk_stride elements between channels) and the column at which its outputs start in
+// the packed (C, ostride) buffers h and xres.  A level-0 entry (launch_cnx_stem_pool_window) states the input frames: in0 = N0, in1 = N1.
+struct CnxPoolEntry {
+    int slot;
+    int in0, in1, out0, out1, tiles;
+    int chunk_base, out_col;
+};
+static constexpr int kCnxPoolBlock = 64;         // 64 entries of 32 bytes: the 2 KiB a table may take
+using CnxPoolBlock = LaunchTable<CnxPoolEntry, kCnxPoolBlock>;
+struct DwPoolRun {
+    float* ring = nullptr;           // (sessions, C, cap)
+    const float* chunk = nullptr;
+    float *h = nullptr, *xres = nullptr;
+    int cap = 0, chunk_stride = 0, ostride = 0;
+};
+// *launches (may be NULL) is incremented per launch; a block of the table in which no entry has a tile launches nothing
+fv_status launch_dwconv_ln_pool(const DwPoolRun& r, const CnxPoolEntry* tab, int count, const float* dw_w, const float* dw_b, const float* ln_w,
+                                const float* ln_b, int C, float eps, hipStream_t s, int* launches);
+// win (count, C, Wmax): row i = the frames [N0_i - 6, N1_i) of entry i's session, then exact zeros to Wmax; the chunk row of item i is at
+// chunk + i * x_istride, channel stride x_rstride, and is filed into the slot's row of ring (sessions, C, cap)
+fv_status launch_cnx_stem_pool_window(const float* chunk, long long x_istride, long long x_rstride, float* ring, float* win, const CnxPoolEntry* tab,
+                                      int count, int C, int cap, int Wmax, hipStream_t s, int* launches);
 
 // x[b][c][t] += bias[c] + sum_j w[c][j] * template[b][t*stride + j - pad]  (use_template branch, hifigan.py:233-234)
 fv_status launch_noise_conv_add(const float* tmpl, const float* w, const float* bias, float* x, int B, int C, int T, int Ta,

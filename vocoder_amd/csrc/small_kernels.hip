@@ -779,8 +779,20 @@ struct DwStream {
     int in0, in1, out0, out1;
 };
 struct DwNoStream {};
+// The pool form (fv_cnxpool_*): one table entry's launch of the stream form.  ring and chunk already point at the entry's slot row and at its
+// frame in0; H and the residual are PACKED (C, ostride) buffers that every entry of the step shares, this entry's columns from ocol on.
+struct DwPool : DwStream {
+    int ostride, ocol;
+};
 __device__ __forceinline__ int sp_out0(const DwStream& sp) { return sp.out0; }
 __device__ __forceinline__ int sp_out0(const DwNoStream&) { return 0; }
+// H and the residual: the row stride and the column of out0 (whole rows: y is (C, T) and the stride is T, no residual)
+__device__ __forceinline__ int sp_ostride(const DwStream& sp) { return sp.out1 - sp.out0; }
+__device__ __forceinline__ int sp_ostride(const DwPool& sp) { return sp.ostride; }
+__device__ __forceinline__ int sp_ostride(const DwNoStream&) { return 0; }
+__device__ __forceinline__ int sp_ocol(const DwStream&) { return 0; }
+__device__ __forceinline__ int sp_ocol(const DwPool& sp) { return sp.ocol; }
+__device__ __forceinline__ int sp_ocol(const DwNoStream&) { return 0; }
 
 template <bool STREAM, int K, int CMAX, int NG, class SP>
 __device__ __forceinline__ void dwconv_ln_tile_body(const float* __restrict__ x, const float* __restrict__ dw_w,
@@ -904,7 +916,7 @@ __device__ __forceinline__ void dwconv_ln_tile_body(const float* __restrict__ x,
     [[maybe_unused]] int n_out = 0;
     [[maybe_unused]] __amdgpu_buffer_rsrc_t rrs = xrs;
     if constexpr (STREAM) {
-        n_out = sp.out1 - sp.out0;
+        n_out = sp_ostride(sp);
         rrs = uniform_rsrc(sp.xres + (long long)b * C * n_out, (unsigned)((long long)C * n_out * 4));
     }
 #pragma unroll
@@ -934,7 +946,7 @@ __device__ __forceinline__ void dwconv_ln_tile_body(const float* __restrict__ x,
                 if constexpr (STREAM) {   // the block's residual: its input at the output column
                     const int c = ch * DWT_CH + cl;
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xs[buf][cl][col + PAD]), rrs,
-                                                          (c < C && t < sp.out1) ? (unsigned)(c * n_out + (t - sp.out0)) * 4u : 0xFFFFFFFFu, 0, 0);
+                                                          (c < C && t < sp.out1) ? (unsigned)(c * n_out + sp_ocol(sp) + (t - sp.out0)) * 4u : 0xFFFFFFFFu, 0, 0);
                 }
             }
             if (ch + 1 < nchunk) commit((ch + 1) % PF, buf ^ 1, ch + 1);
@@ -966,15 +978,17 @@ __device__ __forceinline__ void dwconv_ln_tile_body(const float* __restrict__ x,
     for (int g = 0; g < NG; ++g) var += red[g][col];
     var /= (float)C;
     const float inv = 1.0f / sqrtf(var + eps);
-    // whole rows: (C, T), column t.  STREAM: (C, out1 - out0), column t - out0
-    const int yT = STREAM ? n_out : T, yt = t - sp_out0(sp);
+    // whole rows: (C, T), column t.  STREAM: (C, out1 - out0), column t - out0; the pool: (C, ostride), column ocol + t - out0
+    const int yT = STREAM ? n_out : T, yt = t - sp_out0(sp) + sp_ocol(sp);
+    int yend = T;   // the first column that is not this launch's to write
+    if constexpr (STREAM) yend = sp.out1;
     const __amdgpu_buffer_rsrc_t yrs = uniform_rsrc(y + (long long)b * C * yT, (unsigned)((long long)C * yT * 4));
 #pragma unroll
     for (int ch = 0; ch < NCHUNK; ++ch)
 #pragma unroll
         for (int qq = 0; qq < RPT; ++qq) {
             const int c = ch * DWT_CH + cg + NG * qq;
-            const bool ok = c < C && yt < yT;
+            const bool ok = c < C && t < yend;
             const int cc = c < C ? c : 0;
             const float v = (h[ch * RPT + qq] - mean) * inv * lnp[0][cc] + lnp[1][cc];
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yrs, ok ? (unsigned)(c * yT + yt) * 4u : 0xFFFFFFFFu, 0, 0);
@@ -995,6 +1009,28 @@ __global__ __launch_bounds__(NG * 32) void dwconv_ln_stream_kernel(const float* 
                                                                float* __restrict__ y, int C, float eps, int n_tiles, int n_items,
                                                                int xcd_map, DwStream sp) {
     dwconv_ln_tile_body<true, K, CMAX, NG>(nullptr, dw_w, dw_b, ln_w, ln_b, y, C, 0, eps, n_tiles, n_items, xcd_map, sp);
+}
+
+// The pool form: the launch's entries travel by value; blockIdx.y picks the entry, blockIdx.x its tile (workgroups past the entry's tiles return)
+struct DwPoolArgs {
+    float* ring;                 // (sessions, C, cap)
+    const float* chunk;          // the entries' chunk_base are element offsets into it; chunk_stride elements between channels
+    float* xres;                 // (C, ostride), as y
+    int cap, chunk_stride, ostride;
+};
+template <int K, int CMAX, int NG>
+__global__ __launch_bounds__(NG * 32) void dwconv_ln_pool_kernel(const float* __restrict__ dw_w, const float* __restrict__ dw_b,
+                                                             const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                             float* __restrict__ y, int C, float eps, const DwPoolArgs a,
+                                                             const CnxPoolBlock tab) {
+    const CnxPoolEntry e = tab.e[blockIdx.y];
+    if ((int)blockIdx.x >= e.tiles) return;
+    DwPool sp;
+    sp.ring = a.ring + (long long)e.slot * C * a.cap, sp.chunk = a.chunk + e.chunk_base, sp.xres = a.xres;
+    sp.cap = a.cap, sp.chunk_stride = a.chunk_stride, sp.chunk_off = 0;
+    sp.in0 = e.in0, sp.in1 = e.in1, sp.out0 = e.out0, sp.out1 = e.out1;
+    sp.ostride = a.ostride, sp.ocol = e.out_col;
+    dwconv_ln_tile_body<true, K, CMAX, NG>(nullptr, dw_w, dw_b, ln_w, ln_b, y, C, 0, eps, e.tiles, 1, 0, sp);
 }
 
 // The (CMAX, NG) instantiation for C channels, for the whole-row and the stream launch alike: f(CMAX, NG as integral constants); false: C is
@@ -1045,6 +1081,31 @@ fv_status launch_dwconv_ln_stream(const DwStreamRun& r, const float* dw_w, const
     return FV_OK;
 }
 
+fv_status launch_dwconv_ln_pool(const DwPoolRun& r, const CnxPoolEntry* tab, int count, const float* dw_w, const float* dw_b, const float* ln_w,
+                                const float* ln_b, int C, float eps, hipStream_t s, int* launches) {
+    DwPoolArgs a;
+    a.ring = r.ring, a.chunk = r.chunk, a.xres = r.xres;
+    a.cap = r.cap, a.chunk_stride = r.chunk_stride > 0 ? r.chunk_stride : 1, a.ostride = r.ostride;
+    bool wide = false;
+    const fv_status st = for_each_launch_table<CnxPoolBlock>(count, tab, [&](const CnxPoolBlock& blk, int, int nz) -> fv_status {
+        int tiles = 0;
+        for (int i = 0; i < nz; ++i) tiles = std::max(tiles, blk.e[i].tiles);
+        if (tiles < 1) return FV_OK;   // no entry of this block has a new column or chunk frame at this level
+        const dim3 grid(tiles, nz);
+        if (!dwln_tile_dispatch(C, [&](auto cmax, auto ng) {
+                hipLaunchKernelGGL((dwconv_ln_pool_kernel<7, decltype(cmax)::value, decltype(ng)::value>), grid, dim3(decltype(ng)::value * 32), 0, s,
+                                   dw_w, dw_b, ln_w, ln_b, r.h, C, eps, a, blk);
+            })) {
+            wide = true;
+            return FV_ERR_INVALID;
+        }
+        if (launches) ++*launches;
+        return FV_OK;
+    });
+    if (wide) set_error("launch_dwconv_ln_pool: C = %d is wider than the tile kernel's 1024 channels", C);
+    return st;
+}
+
 // The stem's window of a ConvNeXt layer stream: win (B, C, 6 + c) = the frames [N0 - 6, N0 + c) of the input, zeros below frame 0, the first
 // six from the input ring (B, C, cap), the rest from the caller's chunk, which is filed into the ring on the way (cnx_stream_plan.h)
 __global__ __launch_bounds__(256) void cnx_stem_window_kernel(const float* __restrict__ chunk, long long x_bstride, long long x_rstride,
@@ -1072,6 +1133,41 @@ fv_status launch_cnx_stem_window(const float* chunk, long long x_bstride, long l
                        cap, N0, c);
     FV_HIP_CHECK(hipGetLastError());
     return FV_OK;
+}
+
+// The per-entry form (fv_cnxpool_*): win (count, C, Wmax), row first + blockIdx.z = the frames [N0 - 6, N1) of the entry's session (in0 = N0,
+// in1 = N1) — zeros below frame 0, six from the slot's row of the input ring (sessions, C, cap), the rest from the item's chunk row, filed
+// into the ring — and exact zeros from column 6 + c to Wmax: every element of win is written, and nothing past an item's own frames is loaded.
+__global__ __launch_bounds__(256) void cnx_stem_pool_window_kernel(const float* __restrict__ chunk, long long x_istride, long long x_rstride,
+                                                                   float* __restrict__ ring, float* __restrict__ win, int C, int cap, int Wmax,
+                                                                   int first, const CnxPoolBlock tab) {
+    const CnxPoolEntry e = tab.e[blockIdx.z];
+    const long long item = first + (long long)blockIdx.z, ci = blockIdx.x;
+    const long long N0 = e.in0;
+    const int W = e.in1 - e.in0 + kCnxHalo;
+    float* rg = ring + ((long long)e.slot * C + ci) * cap;
+    for (int j = blockIdx.y * 256 + threadIdx.x; j < Wmax; j += gridDim.y * 256) {
+        const long long f = N0 - kCnxHalo + j;
+        float v = 0.f;
+        if (j < W) {
+            if (f >= N0) {
+                v = chunk[item * x_istride + ci * x_rstride + (f - N0)];
+                rg[f & (cap - 1)] = v;
+            } else if (f >= 0) {
+                v = rg[f & (cap - 1)];
+            }
+        }
+        win[(item * C + ci) * Wmax + j] = v;
+    }
+}
+fv_status launch_cnx_stem_pool_window(const float* chunk, long long x_istride, long long x_rstride, float* ring, float* win, const CnxPoolEntry* tab,
+                                      int count, int C, int cap, int Wmax, hipStream_t s, int* launches) {
+    return for_each_launch_table<CnxPoolBlock>(count, tab, [&](const CnxPoolBlock& blk, int first, int nz) -> fv_status {
+        hipLaunchKernelGGL(cnx_stem_pool_window_kernel, dim3(C, std::min((Wmax + 255) / 256, 64), nz), dim3(256), 0, s, chunk, x_istride, x_rstride,
+                           ring, win, C, cap, Wmax, first, blk);
+        if (launches) ++*launches;
+        return FV_OK;
+    });
 }
 
 // The kernel a whole-row launch takes (one choice for the launch and for the name fv_dwconv_ln_forward reports): the tile kernel for LayerNorm

@@ -10,7 +10,8 @@ max_chunk_frames)`` is the encoder layer by layer (``ConvNeXtStream``, ``fv_cnxs
 input in a ring and a push runs each layer over its new columns only; the concatenated frames have the bits of ``forward`` with
 ``batch_invariant = True``, ``3 * (1 + sum(depths))`` frames behind the input.  Where ``input_channels == dims[0]`` the stem is a C -> C
 conv with a Winograd form, whose bits depend on the launch's alignment: the stream runs it as direct sums, and the bits are those of
-``forward`` with ``conv_algorithm = "direct"`` as well (``stem_has_winograd_form``).
+``forward`` with ``conv_algorithm = "direct"`` as well (``stem_has_winograd_form``).  ``layer_pool(sessions, max_chunk_frames)`` is the
+same for sessions that advance independently (``ConvNeXtPool``, ``fv_cnxpool_*``): per-slot rings and packed per-frame work.
 """
 from __future__ import annotations
 
@@ -21,9 +22,10 @@ from torch import nn
 
 from .. import _base
 from ... import _lib
-from ..._handle import _Handle
+from ..._handle import _Handle, _pool_items, _pool_moved
 from ..._lib import check
 from ...engine import Engine, convnext_config
+from .posterior_encoder import PosteriorPoolCounters
 
 _MSG_INFERENCE = "{} is inference-only: call .eval() first"
 _MSG_DEVICE = ("{} needs a CUDA/HIP tensor (got {}); vocoder_amd has no CPU path — move the model and "
@@ -58,6 +60,15 @@ def ring_cap(max_chunk: int, levels: int) -> int:
     """Slots of a block's ring: the power of two >= 6 + max(max_chunk, R) (``cnx_ring_cap``)."""
     cap = 1
     while cap < 2 * _PAD + max(int(max_chunk), _PAD * (levels + 1)):
+        cap <<= 1
+    return cap
+
+
+def pool_ring_cap(max_chunk: int, levels: int) -> int:
+    """Slots of a ring of the layer pool: the power of two >= 6 + max_chunk + R — an item may flush together with its last frames, and a
+    level's frontier then moves by up to ``max_chunk + R`` frames in one step (``cnx_ring_cap(cnx_pool_step(...))``)."""
+    cap = 1
+    while cap < 2 * _PAD + int(max_chunk) + _PAD * (levels + 1):
         cap <<= 1
     return cap
 
@@ -187,6 +198,134 @@ class ConvNeXtStream(_Handle):
         self._flushed = False
 
 
+class ConvNeXtPoolCounters(PosteriorPoolCounters):
+    """The host counters of a layer pool and the plan of ``fv_cnxpool_plan``: the posterior pool's rule with this backbone's lookahead."""
+
+
+class ConvNeXtPool(_Handle):
+    """``ConvNeXtEncoder`` layer by layer for sessions that advance independently (``fv_cnxpool_*``, include/fishvoc.h): what
+    ``ConvNeXtStream`` is to rows in lockstep, for ``sessions`` slots with their own counters and their own row of every ring.
+    ``step(items)`` takes ``(session, x, flush)`` tuples — ``x``: ``(in_channels, n)`` with ``n <= max_chunk_frames``, or ``None`` for no
+    frames; ``flush``: the utterance ends with these frames — and returns per item the ``(out_channels, k)`` frames that session emits in
+    this step, ``k`` possibly 0.  A session appears at most once per step and refuses items after its flush until ``reset(session)``.  The
+    whole step is checked before anything moves: a refused step leaves every session as it was.  A session's concatenated frames have the
+    bits of ``forward`` over its whole utterance with ``batch_invariant = True`` (and ``conv_algorithm = "direct"`` where the stem has a
+    Winograd form), whatever the other sessions do and in any item order.  Work is enqueued on torch's current stream and calls must be
+    ordered; the pool dies with the module's engine, as a ``ConvNeXtStream`` does."""
+    _destroy = "fv_cnxpool_destroy"
+    _closed = ("this ConvNeXt layer pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
+               "the module): create a new pool")
+
+    def __init__(self, module: "ConvNeXtEncoder", engine: Engine, sessions: int, max_chunk_frames: int):
+        self._lib, self._h = _lib.lib(), ctypes.c_void_p()
+        self._module, self._engine = module, engine
+        with torch.cuda.device(engine.device):
+            check(self._lib.fv_cnxpool_create(engine._h, int(sessions), int(max_chunk_frames), ctypes.byref(self._h)))
+        engine._streams.add(self)
+        self.sessions, self.max_chunk_frames = int(sessions), int(max_chunk_frames)
+        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
+        self.hop = 1
+        self.lookahead_frames = int(self._lib.fv_cnxpool_lookahead(self._h))
+        self.max_frames = int(self._lib.fv_cnxpool_max_frames(self._h))
+        self.counters = ConvNeXtPoolCounters(self.lookahead_frames, self.sessions, self.max_chunk_frames)
+        self._last_stream = None
+
+    # -- counters (host-side: reading them never synchronises) --
+    def received_frames(self, session: int) -> int:
+        return self.counters.received[session]
+
+    def emitted_frames(self, session: int) -> int:
+        return self.counters.emitted[session]
+
+    def pending_frames(self, session: int) -> int:
+        """Frames one session has received and not yet emitted, as the library counts them (``fv_cnxpool_pending``)."""
+        self._check_open()
+        return int(self._lib.fv_cnxpool_pending(self._h, int(session)))
+
+    @property
+    def last_step_launches(self) -> int:
+        """The kernel launches the last accepted step enqueued (``fv_cnxpool_launches``)."""
+        self._check_open()
+        return int(self._lib.fv_cnxpool_launches(self._h))
+
+    @property
+    def state_bytes(self) -> int:
+        """Device memory the pool holds: the slots' rings and one step's scratch (``fv_cnxpool_state_bytes``)."""
+        self._check_open()
+        return int(self._lib.fv_cnxpool_state_bytes(self._h))
+
+    def step(self, items) -> list:
+        """One step for ``items`` (see the class); returns each item's frames, views of the step's output buffer."""
+        self._check_open()
+        what = f"{type(self).__name__}.step"
+        meta, rows = [], []
+        for it in map(tuple, items):
+            s, x, flush = it[0], it[1], it[2] if len(it) > 2 else False
+            if x is not None:
+                if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                    raise RuntimeError(_MSG_DEVICE.format(what, getattr(x, "device", type(x))))
+                if x.dim() != 2 or x.shape[0] != self.in_channels:
+                    raise ValueError(f"{what}: expected ({self.in_channels}, n) or None, got {tuple(x.shape)}")
+            rows.append(x)
+            meta.append((int(s), 0 if x is None else int(x.shape[1]), bool(flush)))
+        longest = max((c for _, c, _ in meta), default=0)
+        chunks = None
+        if longest:
+            chunks = torch.zeros((len(meta), self.in_channels, longest), dtype=torch.float32, device=self._engine.device)
+            for i, x in enumerate(rows):
+                if x is not None and x.shape[1]:
+                    chunks[i, :, :x.shape[1]] = x
+        out, emit = self.step_padded(meta, chunks)
+        return [out[i, :, :k] for i, k in enumerate(emit)]
+
+    def step_padded(self, items, chunks: "torch.Tensor | None", out=None) -> tuple:
+        """The step on the caller's padded buffers, as ``fv_cnxpool_step`` takes them: ``items``: ``(session, frames, flush)`` integers;
+        ``chunks``: ``(count, in_channels, stride)`` with item i's frames first in row i (the rest, NaN included, is never read) — the output
+        of ``WavPool.step_padded`` passes as it is — or ``None`` when no item has frames; ``out``: contiguous ``(count, out_channels,
+        out_cols)``, sized from the Python plan when not given.  Returns ``(out, frames emitted per item)``: row i holds item i's frames
+        first and zeros after them."""
+        self._check_open()
+        m, dev, what = self._module, self._engine.device, f"{type(self).__name__}.step_padded"
+        if m.training:
+            raise RuntimeError(_MSG_INFERENCE.format(type(m).__name__))
+        items, arr, got = _pool_items(items)
+        count, xptr, istride, rstride = len(items), None, 0, 0
+        if chunks is not None:
+            if not isinstance(chunks, torch.Tensor) or not chunks.is_cuda:
+                raise RuntimeError(_MSG_DEVICE.format(what, getattr(chunks, "device", type(chunks))))
+            if chunks.device != dev:
+                raise RuntimeError(f"{what}: the chunks are on {chunks.device}, the pool on {dev}")
+            if chunks.dim() != 3 or chunks.shape[0] != count or chunks.shape[1] != self.in_channels or chunks.dtype != torch.float32:
+                raise ValueError(f"{what}: expected float32 chunks of shape ({count}, {self.in_channels}, stride), got {tuple(chunks.shape)}")
+            if chunks.numel() and not ((chunks.shape[2] == 1 or chunks.stride(2) == 1) and chunks.stride(1) >= chunks.shape[2] and chunks.stride(0) >= 0):
+                chunks = chunks.contiguous()
+            if chunks.numel():
+                xptr, istride, rstride = chunks.data_ptr(), int(chunks.stride(0)), int(chunks.stride(1))
+        plan = self.counters.plan(items)                          # sizes the output before anything is launched; refuses what the library would
+        if out is None:
+            out = torch.empty((count, self.out_channels, max(plan, default=0)), dtype=torch.float32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float32 and out.dim() == 3
+                  and out.shape[:2] == (count, self.out_channels) and out.is_contiguous()):
+            raise ValueError(f"{what}: expected out as a contiguous float32 tensor of shape ({count}, {self.out_channels}, out_cols) on {dev}")
+        cols = int(out.shape[2])
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            if self._done is not None and self._last_stream != cur.cuda_stream:
+                cur.wait_event(self._done)       # the rings are the pool's own: order after the previous step when it ran on another stream
+            check(self._lib.fv_cnxpool_step(self._h, arr, count, xptr, istride, rstride, out.data_ptr() if out.numel() else None, cols, got,
+                                            int(cur.cuda_stream)))
+            self._record_done(cur)
+            self._last_stream = cur.cuda_stream
+        emit = _pool_moved(self.counters, items, plan, got, "the ConvNeXt layer pool emitted {emit} frames where the rule says {plan}")
+        return out, emit
+
+    def reset(self, session: int) -> None:
+        """Start the next utterance in one slot: its counters go to 0; its ring rows are kept (nothing they hold is read again)."""
+        self._check_open()
+        check(self._lib.fv_cnxpool_reset(self._h, int(session)))
+        self.counters.reset(int(session))
+
+
 class LayerNorm(nn.Module):
     """weight/bias holder for both data formats of the reference LayerNorm (convnext.py:47-74)."""
 
@@ -266,3 +405,14 @@ class ConvNeXtEncoder(_base.EngineModule):
         if self.training:
             raise RuntimeError(_MSG_INFERENCE.format(type(self).__name__))
         return ConvNeXtStream(self, self.engine(p.device), batch, max_chunk_frames)
+
+    def layer_pool(self, sessions: int, max_chunk_frames: int = 64) -> ConvNeXtPool:
+        """``layer_stream`` for ``sessions`` clients that advance independently (``ConvNeXtPool``): per-slot rings, one step serves any
+        subset of the sessions, and a session's frames have the bits of the batch-invariant ``forward`` of its utterance alone.  The same
+        limits as ``layer_stream``; the pool is closed with the engine, as a stream is."""
+        p = next(self.parameters(), None)
+        if p is None or not p.is_cuda:
+            raise RuntimeError(_MSG_DEVICE.format(f"{type(self).__name__}.layer_pool", getattr(p, "device", None)))
+        if self.training:
+            raise RuntimeError(_MSG_INFERENCE.format(type(self).__name__))
+        return ConvNeXtPool(self, self.engine(p.device), sessions, max_chunk_frames)

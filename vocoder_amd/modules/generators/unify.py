@@ -42,12 +42,14 @@ class UnifyGenerator(nn.Module):
             raise ValueError("VQ module is not present in the model.")
         return CodecDecodeStream(self.head, self.vq, batch, max_chunk_frames, backbone)
 
-    def decode_pool(self, sessions: int, max_chunk_frames: int = 64):
-        """``decode`` for ``sessions`` clients that advance independently (``vocoder_amd.codec.CodecDecodePool`` on the head alone)."""
+    def decode_pool(self, sessions: int, max_chunk_frames: int = 64, backbone: str = "window"):
+        """``decode`` for ``sessions`` clients that advance independently (``vocoder_amd.codec.CodecDecodePool`` on the head alone).
+        ``backbone`` is ``CodecDecodePool``'s option: ``"layers"`` asks for a ConvNeXt backbone stage in front of the head, which this
+        ``decode`` does not run, and is refused by name."""
         from ...codec import CodecDecodePool
         if self.vq is None:
             raise ValueError("VQ module is not present in the model.")
-        return CodecDecodePool(self.head, self.vq, sessions, max_chunk_frames)
+        return CodecDecodePool(self.head, self.vq, sessions, max_chunk_frames, backbone)
 
     def remove_parametrizations(self):
         for m in (self.backbone, self.head):
