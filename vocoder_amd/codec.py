@@ -153,7 +153,30 @@ def _streaming_encoder(codec: VQVAECodec, what: str, layers: bool = False) -> nn
     return enc
 
 
-class CodecEncodePool:
+class _Stages:
+    """What the codec's streams and pools repeat over their stages (``_stages()``: the handles a call runs through, in order): ``reset`` and
+    ``close`` every one, and close on leaving a ``with`` block."""
+
+    def _stages(self) -> tuple:
+        raise NotImplementedError
+
+    def reset(self, *session) -> None:
+        """Start the next utterance (a pool: of one ``session``) in every stage."""
+        for st in self._stages():
+            st.reset(*session)
+
+    def close(self) -> None:
+        for st in self._stages():
+            st.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
+class CodecEncodePool(_Stages):
     """``VQVAECodec.encode`` for live sources that advance independently: ``frontend.wav_pool()`` -> ``encoder.pool()`` (with ``layers``:
     ``encoder.layer_pool()``, a ``ConvNeXtEncoder`` in its batch-invariant mode) -> ``vq.encode``.  The
     front-end's padded frames go straight into the encoder pool's ``step_padded`` and its padded latents into the quantiser with the frame
@@ -189,28 +212,17 @@ class CodecEncodePool:
         wp._check_open(), ep._check_open()
         frames = wp.counters.plan(items)                        # both plans before either launch: a refusal moves neither pool
         enc_items = [(s, f, flush) for (s, _, flush), f in zip(items, frames)]
-        ep.counters.plan(enc_items)
+        ep.plan_frames(enc_items)
         spec, _ = wp.step_padded(items, chunks)
         z, emit = ep.step_padded(enc_items, spec if spec.numel() else None)
         z = z[0] if isinstance(z, tuple) else z
         return self._vq.encode(z, emit), emit
 
-    def reset(self, session: int) -> None:
-        self.wav_pool.reset(session)
-        self.enc_pool.reset(session)
-
-    def close(self) -> None:
-        self.wav_pool.close()
-        self.enc_pool.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
+    def _stages(self) -> tuple:
+        return self.wav_pool, self.enc_pool
 
 
-class CodecEncodeStream:
+class CodecEncodeStream(_Stages):
     """``VQVAECodec.encode`` on a live source: ``frontend.stream()`` -> ``encoder.stream()`` -> ``vq.encode``, every stage on the device.
     ``push(wave (B, c) or (B, 1, c))``, ``c <= max_chunk_samples``, returns the codes of the latent frames that are final — ``(B, k)``, or
     ``(n_q, B, k)`` for the residual form, ``k`` possibly 0; ``flush()`` ends the utterance and returns the rest; ``reset()`` starts the next
@@ -246,19 +258,8 @@ class CodecEncodeStream:
     def flush(self) -> torch.Tensor:
         return self._codes(self._latents(self._fe.flush()) + [self._enc.flush()])
 
-    def reset(self) -> None:
-        self._fe.reset()
-        self._enc.reset()
-
-    def close(self) -> None:
-        self._fe.close()
-        self._enc.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
+    def _stages(self) -> tuple:
+        return self._fe, self._enc
 
 
 def _decoder_stages(decoder: nn.Module, vq, what: str) -> list:
@@ -279,7 +280,7 @@ def _decoder_stages(decoder: nn.Module, vq, what: str) -> list:
     return stages
 
 
-class CodecDecodeStream:
+class CodecDecodeStream(_Stages):
     """``VQVAECodec.decode`` for a live client: ``push(codes (B, c) or (n_q, B, c))``, ``c <= max_chunk_frames``, returns the audio
     ``(B, C_out, k * hop)`` of the frames that are final, ``k`` possibly 0; ``flush()`` ends the utterance and returns the rest; ``reset()``
     starts the next one.  The first stage is a ``CodeStream``: its ring keeps the codes, and its window is decoded from them in the launch
@@ -336,21 +337,8 @@ class CodecDecodeStream:
         rest = self.codes.flush()
         return torch.cat([self.head.push(rest), self.head.flush()], dim=2)
 
-    def reset(self) -> None:
-        self.codes.reset()
-        if self.head is not None:
-            self.head.reset()
-
-    def close(self) -> None:
-        self.codes.close()
-        if self.head is not None:
-            self.head.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
+    def _stages(self) -> tuple:
+        return (self.codes,) if self.head is None else (self.codes, self.head)
 
 
 class _LayerBackbone:
@@ -402,7 +390,7 @@ class _LayerBackbone:
         self.stream.close()
 
 
-class CodecDecodePool:
+class CodecDecodePool(_Stages):
     """``VQVAECodec.decode`` for clients that advance independently: ``step(items)`` takes ``(session, codes, flush)`` tuples — ``codes``:
     ``(n,)`` or ``(n_q, n)`` with ``n <= max_chunk_frames``, or ``None``; ``flush``: the utterance ends with them — and returns one audio
     tensor ``(C_out, k * hop)`` per item, ``k`` possibly 0.  The first stage is a ``CodeSessionPool``: a slot's ring keeps ``n_q`` int32 per
@@ -464,42 +452,14 @@ class CodecDecodePool:
             raise ValueError("CodecDecodePool.step_padded: a single-engine decoder's pool is self.codes: call its step_padded")
         cp._check_open(), hp._check_open()
         items = [(int(s), int(n), bool(f)) for s, n, f in items]
-        frames = cp.state.plan(items).emit_frames                 # every plan before the first launch: a refusal moves no pool
+        frames = cp.plan_frames(items)                            # every plan before the first launch: a refusal moves no pool
         head_items = [(s, k, flush) for (s, _, flush), k in zip(items, frames)]
-        hp.state.plan(head_items)
+        hp.plan_frames(head_items)
         z, _ = cp.step_padded(items, chunks)
         return hp.step_padded(head_items, z if z.numel() else None)
 
-    def reset(self, session: int) -> None:
-        self.codes.reset(session)
-        if self.head is not None:
-            self.head.reset(session)
-
-    def close(self) -> None:
-        self.codes.close()
-        if self.head is not None:
-            self.head.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
-
-
-class _PlanFrames:
-    def __init__(self, emit_frames: list):
-        self.emit_frames = emit_frames
-
-
-class _LayerPoolState:
-    """The face of a ``SessionPool``'s ``state`` over a layer pool's counters: ``plan(items).emit_frames``."""
-
-    def __init__(self, counters):
-        self._counters = counters
-
-    def plan(self, items) -> _PlanFrames:
-        return _PlanFrames(self._counters.plan(items))
+    def _stages(self) -> tuple:
+        return (self.codes,) if self.head is None else (self.codes, self.head)
 
 
 class _LayerBackbonePool:
@@ -515,7 +475,6 @@ class _LayerBackbonePool:
         self.num_quantizers, self.codebook_size = int(vq.num_quantizers), int(vq.codebook_size)
         self.sessions, self.max_chunk_frames, self.out_channels = pool.sessions, pool.max_chunk_frames, pool.out_channels
         self.lookahead_frames = pool.lookahead_frames
-        self.state = _LayerPoolState(pool.counters)
 
     ring_bytes = property(lambda self: self.pool.state_bytes)
 
@@ -527,6 +486,9 @@ class _LayerBackbonePool:
 
     def _check_open(self) -> None:
         self.pool._check_open()
+
+    def plan_frames(self, items) -> list:
+        return self.pool.plan_frames(items)
 
     def gather(self, items, validate: bool = True):
         """``step``'s items -> ``(the (session, n, flush) integers, the padded int32 codes (num_quantizers, count, longest) or None, None)``.

@@ -24,6 +24,8 @@
 // The pool (fv_wnpool_*): the body once more, instantiated with WN_POOL — the stream's form with the column origin, the end and the frontier
 // taken per table entry (blockIdx.z), rings addressed by the entry's slot — for sessions that advance independently: one launch serves
 // every item of a step, and a session has the bits of its whole utterance whatever the other sessions do.
+// The counters of the stream and the pool, the refusals of a push, flush or step and the emission rule are frame_pool.h's (FrameStream,
+// FramePool); this file keeps the rings (WnRings), the tables, the launches and the vqvae mode's refusal.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -32,7 +34,7 @@
 #include <string>
 
 #include "fv_internal.h"
-#include "sample_pool.h"
+#include "frame_pool.h"
 
 namespace fv {
 namespace {
@@ -447,9 +449,8 @@ struct WnRings {
 
 struct fv_wnstream : WnRings {
     fv_posterior* enc = nullptr;
-    int batch = 0, max_chunk = 0;
-    long long N = 0, E = 0;
-    bool flushed = false;
+    int batch = 0;
+    FrameStream count;                  // frame_pool.h
 };
 
 // The encoder for `S` sessions that advance independently (fv_wnpool_*): the stream's rings with one row per slot, addressed by the slot's
@@ -459,10 +460,7 @@ struct fv_wnstream : WnRings {
 // in one step, where a stream's advances by max(max_chunk, R): the rings and g are sized for that.
 struct fv_wnpool : WnRings {
     fv_posterior* enc = nullptr;
-    int S = 0, max_chunk = 0;
-    std::vector<int64_t> N, E;
-    std::vector<int32_t> flushed;
-    int launches = 0;                   // of the last accepted step
+    FramePool count;                    // frame_pool.h
 };
 
 namespace {
@@ -775,48 +773,18 @@ namespace {
 // One push (c frames of d_x) or the flush: validates, then enqueues at most 2 n_layers + 2 launches and moves the counters
 fv_status wn_stream_advance(const char* fn, fv_wnstream* s, const float* d_x, int64_t x_batch_stride, int64_t x_row_stride, int32_t c, bool flush,
                             float* d_z, float* d_mean, float* d_logvar, int64_t y_row_stride, int64_t* emitted, void* stream) {
-    if (!s) {
-        set_error("%s: null stream", fn);
-        return FV_ERR_INVALID;
-    }
+    if (const fv_status rs = frame_stream_chunk(fn, "fv_wnstream_reset", s ? &s->count : nullptr, c)) return rs;
     const fv_posterior* p = s->enc;
     const fv_posterior_config& cfg = p->cfg;
-    if (s->flushed) {
-        set_error("%s: the stream was flushed at %lld frames: fv_wnstream_reset starts the next utterance", fn, s->N);
-        return FV_ERR_STATE;
-    }
-    if (c < 0 || c > s->max_chunk) {
-        set_error("%s: c = %d must lie in [0, max_chunk = %d]", fn, c, s->max_chunk);
-        return FV_ERR_INVALID;
-    }
-    if (s->N + c > kWnMaxFrames) {
-        set_error("%s: %lld + %d frames are more than the 2^30 a stream counts", fn, s->N, c);
-        return FV_ERR_INVALID;
-    }
     if (cfg.mode == 0 && (d_mean || d_logvar)) {
         set_error("%s: %s must be NULL in vqvae mode (posterior_encoder.py:159-160 returns one tensor)", fn, d_mean ? "d_mean" : "d_logvar");
         return FV_ERR_INVALID;
     }
-    if (c > 0 && !d_x) {
-        set_error("%s: null d_x with c = %d", fn, c);
-        return FV_ERR_INVALID;
-    }
-    if (c > 0 && (x_row_stride < c || x_batch_stride < 0)) {
-        set_error("%s: x_row_stride = %lld (the stride between channels) is shorter than a chunk of c = %d frames, or x_batch_stride = %lld is "
-                  "negative", fn, (long long)x_row_stride, c, (long long)x_batch_stride);
-        return FV_ERR_INVALID;
-    }
-    const int R = p->reach, nl = cfg.n_layers, C = cfg.hidden_channels, B = s->batch;
-    const long long N0 = s->N, N1 = N0 + c, E0 = s->E, E1 = flush ? N1 : std::max(E0, N1 - R);
-    const long long k = E1 - E0;
-    if (k > 0 && !d_z) {
-        set_error("%s: null d_z for the %lld frames this call emits", fn, k);
-        return FV_ERR_INVALID;
-    }
-    if (k > 0 && y_row_stride < k) {
-        set_error("%s: y_row_stride = %lld is shorter than the %lld frames this call emits", fn, (long long)y_row_stride, k);
-        return FV_ERR_INVALID;
-    }
+    if (const fv_status rs = s->count.input(fn, d_x, x_batch_stride, x_row_stride, c)) return rs;
+    long long N1, E1;
+    if (const fv_status rs = s->count.output(fn, "d_z", c, flush, d_z != nullptr, y_row_stride, &N1, &E1)) return rs;
+    const int nl = cfg.n_layers, C = cfg.hidden_channels, B = s->batch;
+    const long long N0 = s->count.N, E0 = s->count.E, k = E1 - E0;
     // everything is validated: enqueue
 
     hipStream_t st = (hipStream_t)stream;
@@ -867,8 +835,7 @@ fv_status wn_stream_advance(const char* fn, fv_wnstream* s, const float* d_x, in
         FV_HIP_CHECK(hipGetLastError());
         set_last_kernel("wn_stream_kernel");
     }
-    s->N = N1, s->E = E1, s->flushed = flush;
-    if (emitted) *emitted = k;
+    s->count.commit(N1, E1, flush, emitted);
     return FV_OK;
 }
 
@@ -896,7 +863,8 @@ FV_API fv_status fv_wnstream_create(fv_posterior* p, int32_t batch, int32_t max_
         return FV_ERR_INVALID;
     }
     std::unique_ptr<fv_wnstream> s(new fv_wnstream());
-    s->enc = p, s->batch = batch, s->max_chunk = max_chunk;
+    s->enc = p, s->batch = batch;
+    s->count.max_chunk = max_chunk, s->count.R = p->reach;
     if (const fv_status st = s->create(p, batch, std::max(max_chunk, p->reach))) return st;
     *out = s.release();
     return FV_OK;
@@ -913,44 +881,16 @@ FV_API fv_status fv_wnstream_flush(fv_wnstream* s, float* d_z, float* d_mean, fl
 }
 
 FV_API fv_status fv_wnstream_reset(fv_wnstream* s) {
-    if (!s) {
-        set_error("fv_wnstream_reset: null stream");
-        return FV_ERR_INVALID;
-    }
-    s->N = s->E = 0, s->flushed = false;        // the rings keep their frames: nothing at or past a frontier, or before frame 0, is ever read
-    return FV_OK;
+    return frame_stream_reset("fv_wnstream_reset", s ? &s->count : nullptr);
 }
 
-FV_API int64_t fv_wnstream_pending(const fv_wnstream* s) { return s ? s->N - s->E : -1; }
+FV_API int64_t fv_wnstream_pending(const fv_wnstream* s) { return s ? s->count.pending() : -1; }
 
-FV_API int32_t fv_wnstream_lookahead(const fv_wnstream* s) { return s ? s->enc->reach : -1; }
+FV_API int32_t fv_wnstream_lookahead(const fv_wnstream* s) { return s ? s->count.R : -1; }
 
 FV_API void fv_wnstream_destroy(fv_wnstream* s) { delete s; }
 
 }  // extern "C"
-
-namespace {
-
-// The refusals of a pool step's items (sample_pool_admit, counting frames, 2^30 of them) and the emission rule: N2 and E2 per item
-fv_status wn_pool_admit(const char* fn, int R, int S, int max_chunk, const int64_t* received, const int64_t* emitted, const int32_t* flushed,
-                        const fv_wavpool_item* items, int count, bool buffers, const float* d_x, long long x_row_stride, long long* N2,
-                        long long* E2) {
-    if (const fv_status st = sample_pool_admit(fn, "fv_wnpool_reset", S, max_chunk, received, flushed, items, count, buffers, d_x, x_row_stride, N2,
-                                               "frames", kWnMaxFrames, "2^30"))
-        return st;
-    for (int i = 0; i < count; ++i) E2[i] = items[i].flush ? N2[i] : std::max((long long)emitted[items[i].session], N2[i] - R);
-    return FV_OK;
-}
-
-fv_status wn_pool_range(const char* fn, int sessions, int max_chunk) {
-    if (sessions < 1 || sessions > 65535 || max_chunk < 1 || max_chunk > (1 << 20)) {
-        set_error("%s: sessions (%d) must lie in [1, 65535] and max_chunk (%d) in [1, 2^20]", fn, sessions, max_chunk);
-        return FV_ERR_INVALID;
-    }
-    return FV_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -965,10 +905,10 @@ FV_API fv_status fv_wnpool_create(fv_posterior* p, int32_t sessions, int32_t max
         set_error("%s: the encoder has not been finalized (fv_posterior_finalize)", fn);
         return FV_ERR_STATE;
     }
-    if (const fv_status st = wn_pool_range(fn, sessions, max_chunk)) return st;
+    if (const fv_status st = FramePool::range(fn, sessions, max_chunk)) return st;
     std::unique_ptr<fv_wnpool> s(new fv_wnpool());
-    s->enc = p, s->S = sessions, s->max_chunk = max_chunk;
-    s->N.assign((size_t)sessions, 0), s->E.assign((size_t)sessions, 0), s->flushed.assign((size_t)sessions, 0);
+    s->enc = p;
+    s->count.init(sessions, max_chunk, p->reach);
     // an item may flush with its last frames: its layers then advance by max_chunk + lam[i + 1] <= max_chunk + R frames in one step
     if (const fv_status st = s->create(p, sessions, (long long)max_chunk + p->reach)) return st;
     *out = s.release();
@@ -977,21 +917,7 @@ FV_API fv_status fv_wnpool_create(fv_posterior* p, int32_t sessions, int32_t max
 
 FV_API int64_t fv_wnpool_plan(int32_t reach, int32_t sessions, int32_t max_chunk, const int64_t* received, const int64_t* emitted,
                               const int32_t* flushed, const fv_wavpool_item* items, int32_t count, int64_t* frames_out) {
-    const char* fn = "fv_wnpool_plan";
-    if (reach < 0) {
-        set_error("%s: reach = %d must be >= 0", fn, reach);
-        return FV_ERR_INVALID;
-    }
-    if (const fv_status st = wn_pool_range(fn, sessions, max_chunk)) return st;
-    if (!received || !emitted || (count > 0 && !frames_out)) {
-        set_error("%s: null argument", fn);
-        return FV_ERR_INVALID;
-    }
-    std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
-    if (const fv_status st = wn_pool_admit(fn, reach, sessions, max_chunk, received, emitted, flushed, items, count, false, nullptr, 0, N2.data(),
-                                           E2.data()))
-        return st;
-    return sample_pool_counts(emitted, items, count, E2.data(), frames_out);
+    return FramePool::plan("fv_wnpool_plan", "fv_wnpool_reset", reach, sessions, max_chunk, received, emitted, flushed, items, count, frames_out);
 }
 
 FV_API fv_status fv_wnpool_step(fv_wnpool* p, const fv_wavpool_item* items, int32_t count, const float* d_x, int64_t x_item_stride,
@@ -1008,23 +934,10 @@ FV_API fv_status fv_wnpool_step(fv_wnpool* p, const fv_wavpool_item* items, int3
         set_error("%s: %s must be NULL in vqvae mode (posterior_encoder.py:159-160 returns one tensor)", fn, d_mean ? "d_mean" : "d_logvar");
         return FV_ERR_INVALID;
     }
+    const FramePool& fc = p->count;
     std::vector<long long> N2((size_t)std::max(count, 0)), E2(N2.size());
-    if (const fv_status st = wn_pool_admit(fn, enc->reach, p->S, p->max_chunk, p->N.data(), p->E.data(), p->flushed.data(), items, count, true, d_x,
-                                           x_row_stride, N2.data(), E2.data()))
-        return st;
-    if (d_x && x_item_stride < 0) {
-        set_error("%s: x_item_stride = %lld is negative", fn, (long long)x_item_stride);
-        return FV_ERR_INVALID;
-    }
-    if (out_cols > kWnMaxFrames) {
-        set_error("%s: out_cols = %d is more than 2^30", fn, out_cols);
-        return FV_ERR_INVALID;
-    }
-    if (const fv_status st = sample_pool_output(fn, "frames", items, count, p->E.data(), E2.data(), 1, d_z != nullptr, out_cols, out_cols)) return st;
-    if (count > 0 && out_cols > 0 && !d_z) {
-        set_error("%s: null d_z although every row's first out_cols = %d columns are written", fn, out_cols);
-        return FV_ERR_INVALID;
-    }
+    if (const fv_status st = fc.admit(fn, "fv_wnpool_reset", items, count, d_x, x_row_stride, N2.data(), E2.data())) return st;
+    if (const fv_status st = fc.output(fn, "d_z", items, count, d_x, x_item_stride, E2.data(), d_z != nullptr, out_cols)) return st;
     // everything is validated: enqueue
 
     hipStream_t st = (hipStream_t)stream;
@@ -1042,7 +955,7 @@ FV_API fv_status fv_wnpool_step(fv_wnpool* p, const fv_wavpool_item* items, int3
                 int widest = 0;
                 for (int i = 0; i < nz; ++i) {
                     const int item = first + i;
-                    const WnPoolEntry e = cols(item, (long long)p->N[(size_t)items[item].session], N2[(size_t)item], items[item].flush != 0);
+                    const WnPoolEntry e = cols(item, (long long)fc.N[(size_t)items[item].session], N2[(size_t)item], items[item].flush != 0);
                     t.e[i].col0 = e.col0, t.e[i].end = e.end, t.e[i].front = e.front;
                     widest = std::max(widest, e.end - e.col0);
                 }
@@ -1083,7 +996,7 @@ FV_API fv_status fv_wnpool_step(fv_wnpool* p, const fv_wavpool_item* items, int3
             }
             if (out_cols > 0) {     // every row's out_cols columns: the item's frames [E, E'), then zeros
                 table([&](int item, long long, long long, bool) {
-                    const long long E0 = p->E[(size_t)items[item].session];
+                    const long long E0 = fc.E[(size_t)items[item].session];
                     return WnPoolEntry{0, (int)E0, (int)(E0 + out_cols), (int)E2[(size_t)item]};
                 });
                 WnParams q = rows(wn_params(enc->proj, p->out, (long long)C * p->outW, p->outW, 0, 1));
@@ -1102,44 +1015,25 @@ FV_API fv_status fv_wnpool_step(fv_wnpool* p, const fv_wavpool_item* items, int3
         });
     if (rs != FV_OK) return rs;
     if (launches) set_last_kernel("wn_pool_kernel");
-    for (int i = 0; i < count; ++i) {
-        const size_t s = (size_t)items[i].session;
-        if (frames_out) frames_out[i] = E2[(size_t)i] - p->E[s];
-        p->N[s] = N2[(size_t)i], p->E[s] = E2[(size_t)i];
-        if (items[i].flush) p->flushed[s] = 1;
-    }
-    p->launches = launches;
+    p->count.commit(items, count, N2.data(), E2.data(), frames_out, launches);
     return FV_OK;
 }
 
 FV_API fv_status fv_wnpool_reset(fv_wnpool* p, int32_t session) {
-    const char* fn = "fv_wnpool_reset";
-    if (!p) {
-        set_error("%s: null pool", fn);
-        return FV_ERR_INVALID;
-    }
-    if (session < 0 || session >= p->S) {
-        set_error("%s: session %d lies outside [0, %d)", fn, session, p->S);
-        return FV_ERR_INVALID;
-    }
-    // the slot's ring rows keep their frames: nothing at or past a frontier, or before frame 0, is ever read
-    p->N[(size_t)session] = p->E[(size_t)session] = 0, p->flushed[(size_t)session] = 0;
-    return FV_OK;
+    return frame_pool_reset("fv_wnpool_reset", p ? &p->count : nullptr, session);
 }
 
-FV_API int64_t fv_wnpool_received(const fv_wnpool* p, int32_t session) { return p && session >= 0 && session < p->S ? p->N[(size_t)session] : -1; }
+FV_API int64_t fv_wnpool_received(const fv_wnpool* p, int32_t session) { return p ? p->count.received(session) : -1; }
 
-FV_API int64_t fv_wnpool_emitted(const fv_wnpool* p, int32_t session) { return p && session >= 0 && session < p->S ? p->E[(size_t)session] : -1; }
+FV_API int64_t fv_wnpool_emitted(const fv_wnpool* p, int32_t session) { return p ? p->count.emitted(session) : -1; }
 
-FV_API int64_t fv_wnpool_pending(const fv_wnpool* p, int32_t session) {
-    return p && session >= 0 && session < p->S ? p->N[(size_t)session] - p->E[(size_t)session] : -1;
-}
+FV_API int64_t fv_wnpool_pending(const fv_wnpool* p, int32_t session) { return p ? p->count.pending(session) : -1; }
 
-FV_API int32_t fv_wnpool_lookahead(const fv_wnpool* p) { return p ? p->enc->reach : -1; }
+FV_API int32_t fv_wnpool_lookahead(const fv_wnpool* p) { return p ? p->count.R : -1; }
 
-FV_API int64_t fv_wnpool_max_frames(const fv_wnpool* p) { return p ? (int64_t)p->max_chunk + p->enc->reach : -1; }
+FV_API int64_t fv_wnpool_max_frames(const fv_wnpool* p) { return p ? p->count.max_frames() : -1; }
 
-FV_API int32_t fv_wnpool_launches(const fv_wnpool* p) { return p ? p->launches : -1; }
+FV_API int32_t fv_wnpool_launches(const fv_wnpool* p) { return p ? p->count.launches : -1; }
 
 FV_API void fv_wnpool_destroy(fv_wnpool* p) { delete p; }
 

@@ -961,6 +961,11 @@ class SessionPool(_EngineHandle):
             raise ValueError(f"expected contiguous chunks of shape ({count}, {self.in_channels}, in_frames), got {tuple(chunks.shape)}")
         return int(chunks.shape[2])
 
+    def plan_frames(self, items) -> list:
+        """Frames every ``(session, frames, flush)`` item would emit; refuses what ``step_padded`` would, and nothing moves (the face the
+        layer pools share: ``_frames._FramePool.plan_frames``)."""
+        return self.state.plan(items).emit_frames
+
     # -- counters (host-side: reading them never synchronises) --
     def received_frames(self, session: int) -> int:
         return self.state.received[session]

@@ -15,40 +15,21 @@ same for sessions that advance independently (``ConvNeXtPool``, ``fv_cnxpool_*``
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 
 from .. import _base
 from ... import _lib
-from ..._handle import _Handle, _pool_items, _pool_moved
-from ..._lib import check
+from ..._frames import _MSG_DEVICE, _MSG_INFERENCE, FramePoolCounters, _FramePool, _FrameStream, schedule      # noqa: F401  (schedule: re-exported)
 from ...engine import Engine, convnext_config
-from .posterior_encoder import PosteriorPoolCounters
 
-_MSG_INFERENCE = "{} is inference-only: call .eval() first"
-_MSG_DEVICE = ("{} needs a CUDA/HIP tensor (got {}); vocoder_amd has no CPU path — move the model and "
-               "input to the GPU")
+ConvNeXtPoolCounters = FramePoolCounters
 _PAD = 3        # (7 - 1) / 2: the layer stream serves kernel_size 7
 
 
 def lookahead(depths) -> int:
     """R of the layer stream: the stem and every block reach 3 frames ahead."""
     return _PAD * (1 + sum(int(d) for d in depths))
-
-
-def schedule(chunks, R: int) -> list:
-    """The frames a layer stream of lookahead ``R`` emits: ``(E, E')`` for every push of ``chunks`` (frame counts, zeros allowed) — the push
-    emits ``[E, E')``, ``E' = max(E, N - R)`` — and last ``(E, N)`` for the flush."""
-    out, N, E = [], 0, 0
-    for c in chunks:
-        N += int(c)
-        E2 = max(E, N - int(R))
-        out.append((E, E2))
-        E = E2
-    out.append((E, N))
-    return out
 
 
 def front(N: int, level: int, flush: bool = False) -> int:
@@ -87,122 +68,31 @@ def level_plan(N0: int, N1: int, flush: bool, level: int) -> dict:
                 file_from=lambda j: in0 if j == 0 else out0 + 32 * j + _PAD)
 
 
-class ConvNeXtStream(_Handle):
+class _LayerHandle:
+    """What the layer stream and the layer pool say of themselves: one output tensor per call, and the device memory they hold."""
+    hop = 1
+
+    def _attach(self, module, engine: Engine) -> tuple:
+        return engine._h, engine.in_channels, engine.out_channels
+
+    @property
+    def state_bytes(self) -> int:
+        """Device memory the handle holds: the rings and one call's scratch (``fv_cnxstream_state_bytes`` / ``fv_cnxpool_state_bytes``)."""
+        self._check_open()
+        return int(self._entry["state_bytes"](self._h))
+
+
+class ConvNeXtStream(_LayerHandle, _FrameStream):
     """``ConvNeXtEncoder`` layer by layer and chunk by chunk (``fv_cnxstream_*``, include/fishvoc.h): ``push`` a ``(B, input_channels, c)``
     chunk, ``c <= max_chunk_frames``, and get the frames that need no later input — ``[E, max(E, N - R))``, ``R = lookahead_frames``,
     possibly none; ``flush`` ends the utterance at ``N`` and returns the rest, then pushes raise until ``reset()``.  The concatenation has
     the bits of ``forward`` over the whole utterance with ``batch_invariant = True``, under any chunking (``schedule`` gives the counts).
     The ``batch`` rows advance in lockstep.  A stream dies with the module's engine: ``load_state_dict`` or ``.to()`` closes it."""
-    _destroy = "fv_cnxstream_destroy"
-    _closed = ("this ConvNeXt layer stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
-               "the module): create a new stream")
-
-    def __init__(self, module: "ConvNeXtEncoder", engine: Engine, batch: int, max_chunk_frames: int):
-        self._lib, self._h = _lib.lib(), ctypes.c_void_p()
-        self._module, self._engine = module, engine
-        with torch.cuda.device(engine.device):
-            check(self._lib.fv_cnxstream_create(engine._h, int(batch), int(max_chunk_frames), ctypes.byref(self._h)))
-        engine._streams.add(self)
-        self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
-        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
-        self.hop = 1
-        self._R = int(self._lib.fv_cnxstream_lookahead(self._h))
-        self._N = self._E = 0
-        self._flushed = False
-        self._last_stream = None
-
-    # -- counters (host-side: reading them never synchronises) --
-    @property
-    def received_frames(self) -> int:
-        return self._N
-
-    @property
-    def emitted_frames(self) -> int:
-        return self._E
-
-    @property
-    def pending_frames(self) -> int:
-        """Frames received and not yet emitted, as the library counts them (``fv_cnxstream_pending``)."""
-        self._check_open()
-        return int(self._lib.fv_cnxstream_pending(self._h))
-
-    @property
-    def lookahead_frames(self) -> int:
-        return self._R
-
-    @property
-    def state_bytes(self) -> int:
-        """Device memory the stream holds: the rings and one call's scratch (``fv_cnxstream_state_bytes``)."""
-        self._check_open()
-        return int(self._lib.fv_cnxstream_state_bytes(self._h))
-
-    def schedule(self, chunks) -> list:
-        return schedule(chunks, self._R)
-
-    def plan(self, c: int, flush: bool = False) -> int:
-        """Frames the next ``push`` of ``c`` frames (or the ``flush``) emits: host arithmetic, nothing moves."""
-        return self._N - self._E if flush else max(self._E, self._N + int(c) - self._R) - self._E
-
-    def push(self, x: torch.Tensor) -> torch.Tensor:
-        self._check_open()
-        what = f"{type(self).__name__}.push"
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError(_MSG_DEVICE.format(what, getattr(x, "device", type(x))))
-        if x.dim() != 3 or x.shape[0] != self.batch or x.shape[1] != self.in_channels:
-            raise ValueError(f"{what}: expected ({self.batch}, {self.in_channels}, c), got {tuple(x.shape)}")
-        x = x.detach().to(torch.float32)
-        c = int(x.shape[2])
-        # a slice along T passes as it is (fv_cnxstream_push's strides)
-        if c and not ((c == 1 or x.stride(2) == 1) and x.stride(1) >= c and x.stride(0) >= 0):
-            x = x.contiguous()
-        return self._call(x, c, flush=False)
-
-    def flush(self) -> torch.Tensor:
-        """The frames ``[E, N)`` against the utterance's end; pushes raise afterwards until ``reset()``."""
-        self._check_open()
-        return self._call(None, 0, flush=True)
-
-    def _call(self, x, c: int, flush: bool) -> torch.Tensor:
-        m, dev = self._module, self._engine.device
-        if m.training:
-            raise RuntimeError(_MSG_INFERENCE.format(type(m).__name__))
-        if x is not None and x.device != dev:
-            raise RuntimeError(f"{type(self).__name__}.push: the chunk is on {x.device}, the stream on {dev}")
-        refused = self._flushed or c > self.max_chunk_frames      # a refused call emits nothing; the library says why
-        k = 0 if refused else self.plan(c, flush)
-        y = torch.empty((self.batch, self.out_channels, k), dtype=torch.float32, device=dev)
-        got = ctypes.c_int64(0)
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            if self._done is not None and self._last_stream != cur.cuda_stream:
-                cur.wait_event(self._done)       # the rings are the stream's own: order after the previous call when it ran on another stream
-            tail = (y.data_ptr() if k else None, max(k, 1), ctypes.byref(got), int(cur.cuda_stream))
-            if flush:
-                check(self._lib.fv_cnxstream_flush(self._h, *tail))
-            else:
-                check(self._lib.fv_cnxstream_push(self._h, x.data_ptr() if c else None, x.stride(0) if c else 0, x.stride(1) if c else 0, c, *tail))
-            self._record_done(cur)
-            self._last_stream = cur.cuda_stream
-        if got.value != k:
-            raise RuntimeError(f"ConvNeXt layer stream emitted {got.value} frames where the rule says {k}")
-        self._N += c
-        self._E += k
-        self._flushed = flush
-        return y
-
-    def reset(self) -> None:
-        """Start the next utterance: N = E = 0; the rings are kept (nothing they hold is read again)."""
-        self._check_open()
-        check(self._lib.fv_cnxstream_reset(self._h))
-        self._N = self._E = 0
-        self._flushed = False
+    _prefix, _noun = "fv_cnxstream", "ConvNeXt layer stream"
+    _entries = _FrameStream._entries + ("state_bytes",)
 
 
-class ConvNeXtPoolCounters(PosteriorPoolCounters):
-    """The host counters of a layer pool and the plan of ``fv_cnxpool_plan``: the posterior pool's rule with this backbone's lookahead."""
-
-
-class ConvNeXtPool(_Handle):
+class ConvNeXtPool(_LayerHandle, _FramePool):
     """``ConvNeXtEncoder`` layer by layer for sessions that advance independently (``fv_cnxpool_*``, include/fishvoc.h): what
     ``ConvNeXtStream`` is to rows in lockstep, for ``sessions`` slots with their own counters and their own row of every ring.
     ``step(items)`` takes ``(session, x, flush)`` tuples — ``x``: ``(in_channels, n)`` with ``n <= max_chunk_frames``, or ``None`` for no
@@ -212,118 +102,8 @@ class ConvNeXtPool(_Handle):
     bits of ``forward`` over its whole utterance with ``batch_invariant = True`` (and ``conv_algorithm = "direct"`` where the stem has a
     Winograd form), whatever the other sessions do and in any item order.  Work is enqueued on torch's current stream and calls must be
     ordered; the pool dies with the module's engine, as a ``ConvNeXtStream`` does."""
-    _destroy = "fv_cnxpool_destroy"
-    _closed = ("this ConvNeXt layer pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
-               "the module): create a new pool")
-
-    def __init__(self, module: "ConvNeXtEncoder", engine: Engine, sessions: int, max_chunk_frames: int):
-        self._lib, self._h = _lib.lib(), ctypes.c_void_p()
-        self._module, self._engine = module, engine
-        with torch.cuda.device(engine.device):
-            check(self._lib.fv_cnxpool_create(engine._h, int(sessions), int(max_chunk_frames), ctypes.byref(self._h)))
-        engine._streams.add(self)
-        self.sessions, self.max_chunk_frames = int(sessions), int(max_chunk_frames)
-        self.in_channels, self.out_channels = engine.in_channels, engine.out_channels
-        self.hop = 1
-        self.lookahead_frames = int(self._lib.fv_cnxpool_lookahead(self._h))
-        self.max_frames = int(self._lib.fv_cnxpool_max_frames(self._h))
-        self.counters = ConvNeXtPoolCounters(self.lookahead_frames, self.sessions, self.max_chunk_frames)
-        self._last_stream = None
-
-    # -- counters (host-side: reading them never synchronises) --
-    def received_frames(self, session: int) -> int:
-        return self.counters.received[session]
-
-    def emitted_frames(self, session: int) -> int:
-        return self.counters.emitted[session]
-
-    def pending_frames(self, session: int) -> int:
-        """Frames one session has received and not yet emitted, as the library counts them (``fv_cnxpool_pending``)."""
-        self._check_open()
-        return int(self._lib.fv_cnxpool_pending(self._h, int(session)))
-
-    @property
-    def last_step_launches(self) -> int:
-        """The kernel launches the last accepted step enqueued (``fv_cnxpool_launches``)."""
-        self._check_open()
-        return int(self._lib.fv_cnxpool_launches(self._h))
-
-    @property
-    def state_bytes(self) -> int:
-        """Device memory the pool holds: the slots' rings and one step's scratch (``fv_cnxpool_state_bytes``)."""
-        self._check_open()
-        return int(self._lib.fv_cnxpool_state_bytes(self._h))
-
-    def step(self, items) -> list:
-        """One step for ``items`` (see the class); returns each item's frames, views of the step's output buffer."""
-        self._check_open()
-        what = f"{type(self).__name__}.step"
-        meta, rows = [], []
-        for it in map(tuple, items):
-            s, x, flush = it[0], it[1], it[2] if len(it) > 2 else False
-            if x is not None:
-                if not isinstance(x, torch.Tensor) or not x.is_cuda:
-                    raise RuntimeError(_MSG_DEVICE.format(what, getattr(x, "device", type(x))))
-                if x.dim() != 2 or x.shape[0] != self.in_channels:
-                    raise ValueError(f"{what}: expected ({self.in_channels}, n) or None, got {tuple(x.shape)}")
-            rows.append(x)
-            meta.append((int(s), 0 if x is None else int(x.shape[1]), bool(flush)))
-        longest = max((c for _, c, _ in meta), default=0)
-        chunks = None
-        if longest:
-            chunks = torch.zeros((len(meta), self.in_channels, longest), dtype=torch.float32, device=self._engine.device)
-            for i, x in enumerate(rows):
-                if x is not None and x.shape[1]:
-                    chunks[i, :, :x.shape[1]] = x
-        out, emit = self.step_padded(meta, chunks)
-        return [out[i, :, :k] for i, k in enumerate(emit)]
-
-    def step_padded(self, items, chunks: "torch.Tensor | None", out=None) -> tuple:
-        """The step on the caller's padded buffers, as ``fv_cnxpool_step`` takes them: ``items``: ``(session, frames, flush)`` integers;
-        ``chunks``: ``(count, in_channels, stride)`` with item i's frames first in row i (the rest, NaN included, is never read) — the output
-        of ``WavPool.step_padded`` passes as it is — or ``None`` when no item has frames; ``out``: contiguous ``(count, out_channels,
-        out_cols)``, sized from the Python plan when not given.  Returns ``(out, frames emitted per item)``: row i holds item i's frames
-        first and zeros after them."""
-        self._check_open()
-        m, dev, what = self._module, self._engine.device, f"{type(self).__name__}.step_padded"
-        if m.training:
-            raise RuntimeError(_MSG_INFERENCE.format(type(m).__name__))
-        items, arr, got = _pool_items(items)
-        count, xptr, istride, rstride = len(items), None, 0, 0
-        if chunks is not None:
-            if not isinstance(chunks, torch.Tensor) or not chunks.is_cuda:
-                raise RuntimeError(_MSG_DEVICE.format(what, getattr(chunks, "device", type(chunks))))
-            if chunks.device != dev:
-                raise RuntimeError(f"{what}: the chunks are on {chunks.device}, the pool on {dev}")
-            if chunks.dim() != 3 or chunks.shape[0] != count or chunks.shape[1] != self.in_channels or chunks.dtype != torch.float32:
-                raise ValueError(f"{what}: expected float32 chunks of shape ({count}, {self.in_channels}, stride), got {tuple(chunks.shape)}")
-            if chunks.numel() and not ((chunks.shape[2] == 1 or chunks.stride(2) == 1) and chunks.stride(1) >= chunks.shape[2] and chunks.stride(0) >= 0):
-                chunks = chunks.contiguous()
-            if chunks.numel():
-                xptr, istride, rstride = chunks.data_ptr(), int(chunks.stride(0)), int(chunks.stride(1))
-        plan = self.counters.plan(items)                          # sizes the output before anything is launched; refuses what the library would
-        if out is None:
-            out = torch.empty((count, self.out_channels, max(plan, default=0)), dtype=torch.float32, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float32 and out.dim() == 3
-                  and out.shape[:2] == (count, self.out_channels) and out.is_contiguous()):
-            raise ValueError(f"{what}: expected out as a contiguous float32 tensor of shape ({count}, {self.out_channels}, out_cols) on {dev}")
-        cols = int(out.shape[2])
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            if self._done is not None and self._last_stream != cur.cuda_stream:
-                cur.wait_event(self._done)       # the rings are the pool's own: order after the previous step when it ran on another stream
-            check(self._lib.fv_cnxpool_step(self._h, arr, count, xptr, istride, rstride, out.data_ptr() if out.numel() else None, cols, got,
-                                            int(cur.cuda_stream)))
-            self._record_done(cur)
-            self._last_stream = cur.cuda_stream
-        emit = _pool_moved(self.counters, items, plan, got, "the ConvNeXt layer pool emitted {emit} frames where the rule says {plan}")
-        return out, emit
-
-    def reset(self, session: int) -> None:
-        """Start the next utterance in one slot: its counters go to 0; its ring rows are kept (nothing they hold is read again)."""
-        self._check_open()
-        check(self._lib.fv_cnxpool_reset(self._h, int(session)))
-        self.counters.reset(int(session))
+    _prefix, _noun = "fv_cnxpool", "ConvNeXt layer pool"
+    _entries = _FramePool._entries + ("state_bytes",)
 
 
 class LayerNorm(nn.Module):

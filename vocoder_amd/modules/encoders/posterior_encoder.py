@@ -19,44 +19,10 @@ import torch
 from torch import nn
 
 from ... import _lib
-from ..._handle import _Handle, _pool_items, _pool_moved
+from ..._frames import _MSG_DEVICE, _MSG_INFERENCE, FramePoolCounters, _FramePool, _FrameStream, schedule      # noqa: F401  (schedule: re-exported)
 from ..._lib import check
-from ...sample_pool import SamplePoolCounters
 
-_MSG_INFERENCE = "{} is inference-only: call .eval() first"
-_MSG_DEVICE = ("{} needs a CUDA/HIP tensor (got {}); vocoder_amd has no CPU path — move the model and "
-               "input to the GPU")
-
-
-def schedule(chunks, R: int) -> list:
-    """The frames a stream of reach ``R`` emits: ``(E, E')`` for every push of ``chunks`` (frame counts, zeros allowed) — the push emits the
-    frames ``[E, E')``, ``E' = max(E, N - R)`` — and last ``(E, N)`` for the flush."""
-    out, N, E = [], 0, 0
-    for c in chunks:
-        N += int(c)
-        E2 = max(E, N - int(R))
-        out.append((E, E2))
-        E = E2
-    out.append((E, N))
-    return out
-
-
-class PosteriorPoolCounters(SamplePoolCounters):
-    """The host counters of a posterior pool and the plan of ``fv_wnpool_plan`` in plain Python: ``schedule``'s rule per session.  An item
-    ``(session, frames, flush)`` takes its slot to ``N' = N + frames`` and ``E' = N' if flush else max(E, N' - R)`` and emits ``[E, E')``;
-    ``plan(items)`` gives ``E' - E`` per item and refuses what the library refuses (``SamplePoolCounters``), counting frames."""
-    _unit, _chunk_limit, _chunk_limit_name, _length_limit, _length_limit_name = "frames", 1 << 20, "2^20", 1 << 30, "2^30"
-
-    def __init__(self, reach: int, sessions: int, max_chunk: int):
-        super().__init__(sessions, max_chunk)
-        self.R = int(reach)
-        self.max_frames = self.max_chunk + self.R        # a flush with max_chunk frames after R pending ones
-
-    def _emission(self, i: int, s: int, c: int, flush: bool, N2: int, E: int) -> int:
-        return N2 if flush else max(E, N2 - self.R)
-
-    def pending(self, session: int) -> int:
-        return self.received[session] - self.emitted[session]
+PosteriorPoolCounters = FramePoolCounters
 
 
 class _PosteriorEngine:
@@ -99,232 +65,44 @@ class _PosteriorEngine:
             pass
 
 
-class PosteriorStream(_Handle):
+class _PosteriorOutputs:
+    """What a posterior stream or pool takes and returns per call: ``z`` in ``"vqvae"`` mode; ``z, mean, logvar`` in the vae modes, returned
+    with the float mask as ``forward`` returns them."""
+    _slots = 3
+    _out_names = "(z, mean, logvar)"
+
+    def _attach(self, module, engine) -> tuple:
+        return engine.handle, module.in_channels, module.out_channels
+
+    def _count(self) -> int:
+        return 1 if self._module.mode == "vqvae" else 3
+
+    def _wrap(self, outs, mask_shape: tuple):
+        if len(outs) == 1:
+            return outs[0]
+        return (*outs, torch.ones(mask_shape, dtype=torch.float32, device=self._engine.device))
+
+
+class PosteriorStream(_PosteriorOutputs, _FrameStream):
     """``PosteriorEncoder`` chunk by chunk (``fv_wnstream_*``, include/fishvoc.h): ``push`` a ``(B, in_channels, c)`` chunk, ``c <=
     max_chunk_frames``, and get what ``forward`` returns for the frames that need no later input — ``[E, max(E, N - R))``, ``R =
     lookahead_frames``, possibly none; ``flush`` ends the utterance at ``N`` and returns the rest, then pushes raise until ``reset()``.  The
     concatenation has the bits of ``forward`` over the whole utterance under any chunking (``schedule`` gives the counts).  The ``batch`` rows
     advance in lockstep.  A stream dies with the module's engine: ``load_state_dict`` or ``.to()`` closes it, create a new one then."""
-    _destroy = "fv_wnstream_destroy"
-    _closed = ("this posterior stream is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
-               "the module): create a new stream")
-
-    def __init__(self, module: "PosteriorEncoder", engine: _PosteriorEngine, batch: int, max_chunk_frames: int):
-        self._lib, self._h = _lib.lib(), ctypes.c_void_p()
-        self._module, self._engine = module, engine
-        with torch.cuda.device(engine.device):
-            check(self._lib.fv_wnstream_create(engine.handle, int(batch), int(max_chunk_frames), ctypes.byref(self._h)))
-        engine._streams.add(self)
-        self.batch, self.max_chunk_frames = int(batch), int(max_chunk_frames)
-        self.in_channels, self.out_channels = module.in_channels, module.out_channels
-        self._R = int(self._lib.fv_wnstream_lookahead(self._h))
-        self._N = self._E = 0
-        self._flushed = False
-        self._last_stream = None
-
-    # -- counters (host-side: reading them never synchronises) --
-    @property
-    def received_frames(self) -> int:
-        return self._N
-
-    @property
-    def emitted_frames(self) -> int:
-        return self._E
-
-    @property
-    def pending_frames(self) -> int:
-        """Frames received and not yet emitted, as the library counts them (``fv_wnstream_pending``)."""
-        self._check_open()
-        return int(self._lib.fv_wnstream_pending(self._h))
-
-    @property
-    def lookahead_frames(self) -> int:
-        return self._R
-
-    def push(self, x: torch.Tensor):
-        self._check_open()
-        what = f"{type(self).__name__}.push"
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError(_MSG_DEVICE.format(what, getattr(x, "device", type(x))))
-        if x.dim() != 3 or x.shape[0] != self.batch or x.shape[1] != self.in_channels:
-            raise ValueError(f"{what}: expected ({self.batch}, {self.in_channels}, c), got {tuple(x.shape)}")
-        x = x.detach().to(torch.float32)
-        c = int(x.shape[2])
-        # a slice along T passes as it is (fv_wnstream_push's strides)
-        if c and not ((c == 1 or x.stride(2) == 1) and x.stride(1) >= c and x.stride(0) >= 0):
-            x = x.contiguous()
-        return self._call(x, c, flush=False)
-
-    def flush(self):
-        """The frames ``[E, N)`` against the utterance's end; pushes raise afterwards until ``reset()``."""
-        self._check_open()
-        return self._call(None, 0, flush=True)
-
-    def _call(self, x, c: int, flush: bool):
-        m, dev = self._module, self._engine.device
-        if m.training:
-            raise RuntimeError(_MSG_INFERENCE.format(type(m).__name__))
-        if x is not None and x.device != dev:
-            raise RuntimeError(f"{type(self).__name__}.push: the chunk is on {x.device}, the stream on {dev}")
-        refused = self._flushed or c > self.max_chunk_frames      # a refused call emits nothing; the library says why
-        k = 0 if refused else (self._N - self._E if flush else max(self._E, self._N + c - self._R) - self._E)
-        vae = m.mode != "vqvae"
-        new = lambda: torch.empty((self.batch, self.out_channels, k), dtype=torch.float32, device=dev)      # noqa: E731
-        z, mean, logvar = new(), (new() if vae else None), (new() if vae else None)
-        ptr = lambda t: t.data_ptr() if t is not None and k else None      # noqa: E731
-        got = ctypes.c_int64(0)
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            if self._done is not None and self._last_stream != cur.cuda_stream:
-                cur.wait_event(self._done)       # the rings are the stream's own: order after the previous call when it ran on another stream
-            tail = (ptr(z), ptr(mean), ptr(logvar), max(k, 1), ctypes.byref(got), int(cur.cuda_stream))
-            if flush:
-                check(self._lib.fv_wnstream_flush(self._h, *tail))
-            else:
-                check(self._lib.fv_wnstream_push(self._h, x.data_ptr() if c else None, x.stride(0) if c else 0, x.stride(1) if c else 0, c, *tail))
-            self._record_done(cur)
-            self._last_stream = cur.cuda_stream
-        if got.value != k:
-            raise RuntimeError(f"posterior stream emitted {got.value} frames where the rule says {k}")
-        self._N += c
-        self._E += k
-        self._flushed = flush
-        if not vae:
-            return z
-        return z, mean, logvar, torch.ones(self.batch, 1, k, dtype=torch.float32, device=dev)
-
-    def reset(self) -> None:
-        """Start the next utterance: N = E = 0; the rings are kept (nothing they hold is read again)."""
-        self._check_open()
-        check(self._lib.fv_wnstream_reset(self._h))
-        self._N = self._E = 0
-        self._flushed = False
+    _prefix, _noun = "fv_wnstream", "posterior stream"
 
 
-class PosteriorPool(_Handle):
+class PosteriorPool(_PosteriorOutputs, _FramePool):
     """``PosteriorEncoder`` for sessions that advance independently (``fv_wnpool_*``, include/fishvoc.h): what ``PosteriorStream`` is to rows
     in lockstep, for ``sessions`` slots with their own counters.  ``step(items)`` takes ``(session, x, flush)`` tuples — ``x``: ``(in_channels,
     n)`` with ``n <= max_chunk_frames``, or ``None`` for no frames; ``flush``: the utterance ends with these frames — and returns per item what
     ``forward`` returns for the frames that session emits in this step: ``z (out_channels, k)``, or ``(z, mean, logvar, mask)``; ``k`` may be
-    0.  A session appears at most once per step and refuses items after its flush until ``reset(session)``.  The whole step is checked before
-    anything moves: a refused step leaves every session as it was.  A session's concatenated tensors have the bits of ``forward`` over its
-    whole utterance, whatever the other sessions do.  One step is at most ``2 n_layers + 2`` launches per 128 items.  Work is enqueued on
-    torch's current stream and calls must be ordered; the pool dies with the module's engine, as a ``PosteriorStream`` does."""
-    _destroy = "fv_wnpool_destroy"
-    _closed = ("this posterior pool is closed (its engine was closed or rebuilt — e.g. load_state_dict or .to() on "
-               "the module): create a new pool")
-
-    def __init__(self, module: "PosteriorEncoder", engine: _PosteriorEngine, sessions: int, max_chunk_frames: int):
-        self._lib, self._h = _lib.lib(), ctypes.c_void_p()
-        self._module, self._engine = module, engine
-        with torch.cuda.device(engine.device):
-            check(self._lib.fv_wnpool_create(engine.handle, int(sessions), int(max_chunk_frames), ctypes.byref(self._h)))
-        engine._streams.add(self)
-        self.sessions, self.max_chunk_frames = int(sessions), int(max_chunk_frames)
-        self.in_channels, self.out_channels = module.in_channels, module.out_channels
-        self.lookahead_frames = int(self._lib.fv_wnpool_lookahead(self._h))
-        self.max_frames = int(self._lib.fv_wnpool_max_frames(self._h))
-        self.counters = PosteriorPoolCounters(self.lookahead_frames, self.sessions, self.max_chunk_frames)
-        self._last_stream = None
-
-    # -- counters (host-side: reading them never synchronises) --
-    def received_frames(self, session: int) -> int:
-        return self.counters.received[session]
-
-    def emitted_frames(self, session: int) -> int:
-        return self.counters.emitted[session]
-
-    def pending_frames(self, session: int) -> int:
-        """Frames one session has received and not yet emitted, as the library counts them (``fv_wnpool_pending``)."""
-        self._check_open()
-        return int(self._lib.fv_wnpool_pending(self._h, int(session)))
-
-    @property
-    def last_step_launches(self) -> int:
-        """The kernel launches the last accepted step enqueued (``fv_wnpool_launches``)."""
-        self._check_open()
-        return int(self._lib.fv_wnpool_launches(self._h))
-
-    def step(self, items) -> list:
-        """One step for ``items`` (see the class); returns each item's tensors, views of the step's output buffers."""
-        self._check_open()
-        what = f"{type(self).__name__}.step"
-        meta, rows = [], []
-        for it in map(tuple, items):
-            s, x, flush = it[0], it[1], it[2] if len(it) > 2 else False
-            if x is not None:
-                if not isinstance(x, torch.Tensor) or not x.is_cuda:
-                    raise RuntimeError(_MSG_DEVICE.format(what, getattr(x, "device", type(x))))
-                if x.dim() != 2 or x.shape[0] != self.in_channels:
-                    raise ValueError(f"{what}: expected ({self.in_channels}, n) or None, got {tuple(x.shape)}")
-            rows.append(x)
-            meta.append((int(s), 0 if x is None else int(x.shape[1]), bool(flush)))
-        longest = max((c for _, c, _ in meta), default=0)
-        chunks = None
-        if longest:
-            chunks = torch.zeros((len(meta), self.in_channels, longest), dtype=torch.float32, device=self._engine.device)
-            for i, x in enumerate(rows):
-                if x is not None and x.shape[1]:
-                    chunks[i, :, :x.shape[1]] = x
-        out, emit = self.step_padded(meta, chunks)
-        if self._module.mode == "vqvae":
-            return [out[i, :, :k] for i, k in enumerate(emit)]
-        return [tuple(t[i, :, :k] for t in out) + (torch.ones(1, k, dtype=torch.float32, device=self._engine.device),) for i, k in enumerate(emit)]
-
-    def step_padded(self, items, chunks: "torch.Tensor | None", out=None) -> tuple:
-        """The step on the caller's padded buffers, as ``fv_wnpool_step`` takes them: ``items``: ``(session, frames, flush)`` integers;
-        ``chunks``: ``(count, in_channels, stride)`` with item i's frames first in row i (the rest, NaN included, is never read) — the output
-        of ``WavPool.step_padded`` passes as it is — or ``None`` when no item has frames; ``out``: ``z``, or ``(z, mean, logvar)`` in the vae
-        modes, each contiguous ``(count, out_channels, out_cols)``, sized from the Python plan when not given.  Returns ``(out, frames emitted
-        per item)``: row i holds item i's frames first and zeros after them."""
-        self._check_open()
-        m, dev, what = self._module, self._engine.device, f"{type(self).__name__}.step_padded"
-        if m.training:
-            raise RuntimeError(_MSG_INFERENCE.format(type(m).__name__))
-        items, arr, got = _pool_items(items)
-        count, xptr, istride, rstride = len(items), None, 0, 0
-        if chunks is not None:
-            if not isinstance(chunks, torch.Tensor) or not chunks.is_cuda:
-                raise RuntimeError(_MSG_DEVICE.format(what, getattr(chunks, "device", type(chunks))))
-            if chunks.device != dev:
-                raise RuntimeError(f"{what}: the chunks are on {chunks.device}, the pool on {dev}")
-            if chunks.dim() != 3 or chunks.shape[0] != count or chunks.shape[1] != self.in_channels or chunks.dtype != torch.float32:
-                raise ValueError(f"{what}: expected float32 chunks of shape ({count}, {self.in_channels}, stride), got {tuple(chunks.shape)}")
-            if chunks.numel() and not ((chunks.shape[2] == 1 or chunks.stride(2) == 1) and chunks.stride(1) >= chunks.shape[2] and chunks.stride(0) >= 0):
-                chunks = chunks.contiguous()
-            if chunks.numel():
-                xptr, istride, rstride = chunks.data_ptr(), int(chunks.stride(0)), int(chunks.stride(1))
-        plan = self.counters.plan(items)                          # sizes the output before anything is launched; refuses what the library would
-        vae = m.mode != "vqvae"
-        if out is None:
-            new = lambda: torch.empty((count, self.out_channels, max(plan, default=0)), dtype=torch.float32, device=dev)      # noqa: E731
-            outs = (new(), new(), new()) if vae else (new(),)
-        else:
-            outs = tuple(out) if vae else (out,)
-            ok = len(outs) == (3 if vae else 1) and all(
-                isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.dim() == 3 and t.shape[:2] == (count, self.out_channels)
-                and t.shape == outs[0].shape and t.is_contiguous() for t in outs)
-            if not ok:
-                raise ValueError(f"{what}: expected out as {'(z, mean, logvar), each ' if vae else ''}a contiguous float32 tensor of shape "
-                                 f"({count}, {self.out_channels}, out_cols) on {dev}")
-        cols = int(outs[0].shape[2])
-        ptr = lambda t: t.data_ptr() if t.numel() else None      # noqa: E731
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            if self._done is not None and self._last_stream != cur.cuda_stream:
-                cur.wait_event(self._done)       # the rings are the pool's own: order after the previous step when it ran on another stream
-            check(self._lib.fv_wnpool_step(self._h, arr, count, xptr, istride, rstride, ptr(outs[0]), ptr(outs[1]) if vae else None,
-                                           ptr(outs[2]) if vae else None, cols, got, int(cur.cuda_stream)))
-            self._record_done(cur)
-            self._last_stream = cur.cuda_stream
-        emit = _pool_moved(self.counters, items, plan, got, "the posterior pool emitted {emit} frames where the rule says {plan}")
-        return (outs if vae else outs[0]), emit
-
-    def reset(self, session: int) -> None:
-        """Start the next utterance in one slot: its counters go to 0; its ring rows are kept (nothing they hold is read again)."""
-        self._check_open()
-        check(self._lib.fv_wnpool_reset(self._h, int(session)))
-        self.counters.reset(int(session))
+    0.  ``step_padded`` takes and returns ``z``, or ``(z, mean, logvar)`` in the vae modes.  A session appears at most once per step and
+    refuses items after its flush until ``reset(session)``.  The whole step is checked before anything moves: a refused step leaves every
+    session as it was.  A session's concatenated tensors have the bits of ``forward`` over its whole utterance, whatever the other sessions
+    do.  One step is at most ``2 n_layers + 2`` launches per 128 items.  Work is enqueued on torch's current stream and calls must be
+    ordered; the pool dies with the module's engine, as a ``PosteriorStream`` does."""
+    _prefix, _noun = "fv_wnpool", "posterior pool"
 
 
 class WaveNet(nn.Module):

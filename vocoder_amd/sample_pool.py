@@ -19,7 +19,7 @@ class SamplePoolCounters:
     order per item: ``ValueError`` for a session out of range, a duplicate session and samples outside ``[0, max_chunk]``,
     ``PoolStateError`` for a flushed slot, ``ValueError`` past 2^40 samples; then whatever the pool's own rule refuses.  ``commit`` moves the
     counters as a step that emitted the plan does; ``step`` is both.  A pool that counts something else names its unit and its limits
-    (``PosteriorPoolCounters``: frames, chunks up to 2^20, utterances up to 2^30)."""
+    (``_frames.FramePoolCounters``: frames, chunks up to 2^20, utterances up to 2^30)."""
     _unit, _chunk_limit, _chunk_limit_name, _length_limit, _length_limit_name = "samples", 1 << 28, "2^28", MAX_SAMPLES, "2^40"
 
     def __init__(self, sessions: int, max_chunk: int):
