@@ -1767,6 +1767,79 @@ FV_API int64_t fv_cnxpool_state_bytes(const fv_cnxpool* p);
 FV_API int32_t fv_cnxpool_table_size(void);
 FV_API void fv_cnxpool_destroy(fv_cnxpool* p);
 
+/* -------- the GAN's critics, forward only (fv_disc_*) --------
+ * modules/discriminators/mpd.py (MultiPeriodDiscriminator, kind FV_DISC_PERIOD) and modules/discriminators/mrd.py
+ * (MultiResolutionDiscriminator, kind FV_DISC_RESOLUTION) in eval mode, and the sums behind models/gan.py:149 / 155 / 204.  One handle
+ * holds up to 8 sub-discriminators of one kind.  Activations are channel last, (row, H, W, C):
+ *   period i:      the wave read as (ceil(L / p), p, 1) with zeros past L (mpd.py:47-52); Conv2d(c[l], c[l + 1], (kernel_size, 1),
+ *                  (stride, 1), pad (kernel_size / 2, 0)) + SiLU per channel pair (mpd.py:54-57); conv_post Conv2d(c[-1], 1, (3, 1), pad (1, 0))
+ *   resolution i:  reflect padding ((n_fft - hop) / 2, (n_fft - hop + 1) / 2) at the row's own ends, frames of n_fft at hop, a window of
+ *                  ones of win_length centred in n_fft, sqrt(re^2 + im^2) (mrd.py:52-73): (n_fft / 2 + 1, L / hop, 1); then Conv2d(1, 32,
+ *                  (3, 9), pad (1, 4)), three Conv2d(32, 32, (3, 9), stride (1, 2), pad (1, 4)), Conv2d(32, 32, (3, 3), pad (1, 1)), each
+ *                  + SiLU (mrd.py:41-44); conv_post Conv2d(32, 1, (3, 3), pad (1, 1))
+ * Every conv, the fold and the DFT are one implicit GEMM on v_mfma_f32_32x32x2_f32: an element's sum runs over k ascending in the order
+ * (kh, kw, c) from one accumulator, then the bias.  Weight norm (dim 0: the norm over dims 1-3 per output channel) is folded in fp64 and
+ * rounded once at finalize.  Ragged rows: nothing at or past a row's own (H, W) extent is read, feature maps and scores hold exact zeros
+ * there, and a row has the same bits alone, in any batch, in any order and padded to any T — the reference run on the row alone.
+ * Limits: n_sub in [1, 8]; n_channels in [2, 8], channels[0] = 1, the others multiples of 4 in [4, 1024]; kernel_size in [1, 15], stride
+ * in [1, 16]; period in [1, 4096]; n_fft a multiple of 4 in [4, 4096], hop_length and win_length in [1, n_fft]; batch in [0, 65535], T at
+ * most 2^26 and every feature map at most 2^31 - 1 elements per row.  Not built: spectral norm, gradients. */
+#define FV_DISC_PERIOD 0
+#define FV_DISC_RESOLUTION 1
+typedef struct fv_disc_config {
+    int32_t kind;              /* FV_DISC_PERIOD | FV_DISC_RESOLUTION */
+    int32_t n_sub;             /* sub-discriminators */
+    int32_t period[8];         /* period kind: DiscriminatorP(period=) */
+    int32_t n_fft[8];          /* resolution kind: DiscriminatorR(n_fft=, hop_length=, win_length=) */
+    int32_t hop_length[8];
+    int32_t win_length[8];
+    int32_t n_channels;        /* period kind: len(channels) */
+    int32_t channels[8];       /* DiscriminatorP(channels=), default 1, 64, 128, 256, 512, 1024 */
+    int32_t kernel_size;       /* DiscriminatorP(kernel_size=) */
+    int32_t stride;            /* DiscriminatorP(stride=) */
+} fv_disc_config;
+/* One feature map of the output buffer: (batch, H, W, C) floats at `offset`; the last layer of a sub-discriminator is its score map (C = 1). */
+typedef struct fv_disc_map {
+    int64_t offset;            /* in floats, a multiple of 4 */
+    int32_t H, W, C;           /* the extent of a row of T samples */
+    int32_t sub, layer;
+} fv_disc_map;
+
+typedef struct fv_disc fv_disc;
+
+/* mpd.py:10-41 / mrd.py:8-33.  Validates on the host, no device work.  FV_ERR_INVALID names the field. */
+FV_API fv_status fv_disc_create(const fv_disc_config* cfg, fv_disc** out);
+/* The reference modules' state-dict keys (mpd.py:27-41, mrd.py:24-33 under weight_norm): discriminators.{i}.convs.{l}.bias,
+ * .parametrizations.weight.original0 (N, 1, 1, 1), .parametrizations.weight.original1 (N, C, KH, KW), and discriminators.{i}.conv_post.
+ * the same; the legacy .weight_g / .weight_v are taken for original0 / original1.  host: fp32, torch layout, copied.  An unknown key ->
+ * FV_ERR_INVALID, a wrong shape -> FV_ERR_SHAPE, both by name; after fv_disc_finalize -> FV_ERR_STATE. */
+FV_API fv_status fv_disc_load_weight(fv_disc* d, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+/* Strict load: FV_ERR_MISSING_WEIGHT names the first absent key.  Folds the weight norm (torch's weight_norm, dim 0), reorders to
+ * (out, kh, kw, in), builds the windowed DFT of every resolution (mrd.py:62-69), uploads. */
+FV_API fv_status fv_disc_finalize(fv_disc* d);
+FV_API void fv_disc_destroy(fv_disc* d);
+/* mpd.py:57,60 / mrd.py:44,47, the fmap lists: where every feature map of a (batch, T) call lies in the output buffer, sub-discriminator
+ * by sub-discriminator, layer by layer (maps[sub * layers + layer]; `capacity` entries; maps may be NULL).  *n_maps (may be NULL) receives
+ * their number.  Returns the buffer's size in floats, or -1 for a bad argument (fv_last_error says which).  Pure host. */
+FV_API int64_t fv_disc_layout(const fv_disc* d, int32_t batch, int64_t T, fv_disc_map* maps, int32_t capacity, int32_t* n_maps);
+/* Bytes of device scratch fv_disc_forward and fv_disc_distance need (the larger): the padded wave, the DFT and the magnitudes of one
+ * resolution (mrd.py:52-73); the partial sums of the distance.  0 for a bad argument. */
+FV_API size_t fv_disc_workspace_bytes(const fv_disc* d, int32_t batch, int64_t T);
+/* mpd.py:43-63, :82-86 / mrd.py:35-50, :94-98.  d_x: (batch, T) fp32 samples.  host_lengths: NULL (every row holds T samples) or `batch`
+ * sample counts in [1, T], read before the call returns.  d_out: out_floats >= fv_disc_layout(batch, T) floats; every element of every
+ * map is written, exact zeros at and past a row's own extent.  Refused by name, before anything is enqueued: a row of 0 samples; for the
+ * resolution kind a row not longer than its reflect padding or shorter than one hop (by row and minimum length); buffers that are too
+ * small or not 16-byte aligned.  No allocation, copy or synchronisation.  Asynchronous on `stream`. */
+FV_API fv_status fv_disc_forward(fv_disc* d, const float* d_x, int64_t T, const int32_t* host_lengths, int32_t batch, float* d_out,
+                                 int64_t out_floats, void* d_workspace, size_t workspace_bytes, void* stream);
+/* gan.py:149 (generator's adversarial term), :155 (the critic's) and :204 (feature matching), as sums: d_real / d_fake are two output
+ * buffers of fv_disc_forward for the same (batch, T, host_lengths).  d_sums: (batch, n_sub, layers, 5) float64; per row, sub-discriminator
+ * and layer, over the row's own extent: sum |real - fake|, sum (1 - fake)^2, sum fake^2, sum (real - 1)^2 and the element count (the last
+ * layer's are the score terms).  Terms are fp32 with one rounding per operation, accumulated in fp64 per tile of 4096 elements in a fixed
+ * order, then a finish launch: no float atomics, and a row's sums are bit-identical alone and in any batch.  Asynchronous on `stream`. */
+FV_API fv_status fv_disc_distance(fv_disc* d, const float* d_real, const float* d_fake, int64_t T, const int32_t* host_lengths, int32_t batch,
+                                  double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* -------- per-launch timing (measurement aid; bench.py's roofline leg) --------
  * Between fv_profile_begin and fv_profile_end every kernel that fv_forward enqueues is bracketed by hipEvents recorded
  * on the launch stream.  fv_profile_end synchronises them and writes a JSON array

@@ -93,6 +93,8 @@ EXPORTS = (
     "fv_cnxpool_pending", "fv_cnxpool_lookahead", "fv_cnxpool_max_frames", "fv_cnxpool_launches", "fv_cnxpool_state_bytes",
     "fv_cnxpool_table_size", "fv_cnxpool_destroy",
     "fv_aa_snake_forward", "fv_dwconv_ln_forward",
+    "fv_disc_create", "fv_disc_load_weight", "fv_disc_finalize", "fv_disc_destroy", "fv_disc_layout", "fv_disc_workspace_bytes",
+    "fv_disc_forward", "fv_disc_distance",
 )
 
 _i32 = ctypes.c_int32
@@ -206,6 +208,23 @@ class W2VConfig(ctypes.Structure):
     _fields_ = [("hidden", _i32), ("layers", _i32), ("heads", _i32), ("intermediate", _i32), ("n_conv", _i32),
                 ("conv_dim", _i32 * W2V_MAX_CONV), ("conv_kernel", _i32 * W2V_MAX_CONV), ("conv_stride", _i32 * W2V_MAX_CONV),
                 ("pos_conv_kernel", _i32), ("pos_conv_groups", _i32), ("post_channels", _i32)]
+
+
+FV_DISC_PERIOD, FV_DISC_RESOLUTION = 0, 1
+DISC_MAX_SUB = 8
+DISC_MAX_CHANNELS = 8
+
+
+class DiscConfig(ctypes.Structure):
+    """fv_disc_config, field for field (include/fishvoc.h)."""
+    _fields_ = [("kind", _i32), ("n_sub", _i32), ("period", _i32 * DISC_MAX_SUB), ("n_fft", _i32 * DISC_MAX_SUB),
+                ("hop_length", _i32 * DISC_MAX_SUB), ("win_length", _i32 * DISC_MAX_SUB), ("n_channels", _i32),
+                ("channels", _i32 * DISC_MAX_CHANNELS), ("kernel_size", _i32), ("stride", _i32)]
+
+
+class DiscMap(ctypes.Structure):
+    """fv_disc_map, field for field."""
+    _fields_ = [("offset", ctypes.c_int64), ("H", _i32), ("W", _i32), ("C", _i32), ("sub", _i32), ("layer", _i32)]
 
 
 def build(force: bool = False, jobs: int = 8) -> str:
@@ -665,6 +684,22 @@ def lib() -> ctypes.CDLL:
     L.fv_w2v_forward.restype = _i32
     L.fv_w2v_destroy.argtypes = [vp]
     L.fv_w2v_destroy.restype = None
+    L.fv_disc_create.argtypes = [ctypes.POINTER(DiscConfig), ctypes.POINTER(vp)]
+    L.fv_disc_create.restype = _i32
+    L.fv_disc_load_weight.argtypes = [vp, cp, fp, i64p, _i32]
+    L.fv_disc_load_weight.restype = _i32
+    L.fv_disc_finalize.argtypes = [vp]
+    L.fv_disc_finalize.restype = _i32
+    L.fv_disc_destroy.argtypes = [vp]
+    L.fv_disc_destroy.restype = None
+    L.fv_disc_layout.argtypes = [vp, _i32, i64, ctypes.POINTER(DiscMap), _i32, i32p]
+    L.fv_disc_layout.restype = i64
+    L.fv_disc_workspace_bytes.argtypes = [vp, _i32, i64]
+    L.fv_disc_workspace_bytes.restype = ctypes.c_size_t
+    L.fv_disc_forward.argtypes = [vp, vp, i64, i32p, _i32, vp, i64, vp, ctypes.c_size_t, vp]
+    L.fv_disc_forward.restype = _i32
+    L.fv_disc_distance.argtypes = [vp, vp, vp, i64, i32p, _i32, vp, vp, ctypes.c_size_t, vp]
+    L.fv_disc_distance.restype = _i32
     L.fv_mms_normalize_workspace_bytes.argtypes = [_i32, i64]
     L.fv_mms_normalize_workspace_bytes.restype = ctypes.c_size_t
     L.fv_mms_normalize.argtypes = [vp, i64, i32p, _i32, vp, vp, ctypes.c_size_t, vp]

@@ -31,6 +31,8 @@ TARGET_ALIASES = {
     "fish_vocoder.modules.encoders.posterior_encoder": "vocoder_amd.modules.encoders.posterior_encoder",
     "fish_vocoder.modules.encoders.hubert": "vocoder_amd.modules.encoders.hubert",
     "fish_vocoder.modules.encoders.mms": "vocoder_amd.modules.encoders.mms",
+    "fish_vocoder.modules.discriminators.mpd": "vocoder_amd.modules.discriminators.mpd",
+    "fish_vocoder.modules.discriminators.mrd": "vocoder_amd.modules.discriminators.mrd",
     "fish_vocoder.data.transforms.spectrogram": "vocoder_amd.data.transforms.spectrogram",
 }
 

@@ -8,6 +8,9 @@ For every file under SOURCE that matches ``--glob-pattern`` the file of the same
     stft_sc     spectral convergence, mean over four STFT resolutions (modules/losses/stft.py:55)          [--no-stft leaves both out]
     stft_mag    log-magnitude L1, mean over the same resolutions (modules/losses/stft.py:74)
 
+    critic_{mpd,mrd}_{adv_fake,adv_real,fm}   with ``--critics CKPT``: what the checkpoint's discriminators make of the pair, the terms
+                of models/gan.py:149, :204 and :155 per file (``vocoder_amd.scoring.CriticDistance``)
+
 and the means over the files are printed in eval.py:95-97's format, followed by the counts of scored and skipped pairs.  ``--json PATH`` writes
 the per-file values.  Pairs are scored ``--batch-size`` at a time; a pair's values do not depend on the batch it was scored in.
 
@@ -29,6 +32,7 @@ from pathlib import Path
 
 MAX_LENGTH_DIFFERENCE = 1000      # eval.py:71
 METRICS = ("spec_diff", "stft_sc", "stft_mag")
+CRITIC_METRICS = tuple(f"critic_{key}_{name}" for key in ("mpd", "mrd") for name in ("adv_fake", "adv_real", "fm"))
 
 
 @dataclass(frozen=True)
@@ -95,8 +99,9 @@ def load_mono(path, sr: int, device, resamplers: dict):
     return x
 
 
-def score_pairs(pairs, sr: int, batch_size: int = 16, stft: bool = True, device="cuda"):
-    """``(values, skipped)``: ``values[name] = {metric: float}`` for every pair scored, ``batch_size`` pairs per ``forward_list`` call."""
+def score_pairs(pairs, sr: int, batch_size: int = 16, stft: bool = True, device="cuda", critics=None):
+    """``(values, skipped)``: ``values[name] = {metric: float}`` for every pair scored, ``batch_size`` pairs per ``forward_list`` call.
+    ``critics``: a ``CriticDistance`` whose three numbers per critic join the values."""
     if not pairs:
         return {}, []
     import torch
@@ -104,10 +109,12 @@ def score_pairs(pairs, sr: int, batch_size: int = 16, stft: bool = True, device=
     device = torch.device(device)
     mel = MelDistance(sr).to(device)
     mr = MultiResolutionSTFTDistance().to(device) if stft else None
+    if critics is not None:
+        critics = critics.to(device)
     resamplers: dict = {}
     values, skipped, todo = {}, [], []
     for p in pairs:
-        if mel.too_short(p.length) or (mr is not None and mr.too_short(p.length)):
+        if mel.too_short(p.length) or (mr is not None and mr.too_short(p.length)) or (critics is not None and p.length < critics.min_length()):
             skipped.append((p.name, f"{p.length} samples are too few for the front-ends"))
         else:
             todo.append(p)
@@ -118,6 +125,10 @@ def score_pairs(pairs, sr: int, batch_size: int = 16, stft: bool = True, device=
         cols = {"spec_diff": mel.forward_list(src, gen)}
         if mr is not None:
             cols["stft_sc"], cols["stft_mag"] = mr.forward_list(src, gen)
+        if critics is not None:
+            for key, row in critics.forward_list(src, gen).items():
+                for name in ("adv_fake", "adv_real", "fm"):
+                    cols[f"critic_{key}_{name}"] = row[name]
         cols = {k: v.tolist() for k, v in cols.items()}
         for b, p in enumerate(batch):
             values[p.name] = {k: cols[k][b] for k in cols}
@@ -132,17 +143,26 @@ def main(argv=None) -> int:
     ap.add_argument("--glob-pattern", default="*.wav")
     ap.add_argument("--batch-size", type=int, default=16, help="pairs per call")
     ap.add_argument("--no-stft", action="store_true", help="spec_diff only")
+    ap.add_argument("--critics", default=None, metavar="CKPT", help="a Lightning checkpoint whose discriminators.mpd. / discriminators.mrd. "
+                    "weights score every pair: adds critic_{mpd,mrd}_{adv_fake,adv_real,fm}")
+    ap.add_argument("--periods", type=int, nargs="+", default=None, help="the checkpoint's MPD periods (default: configs/model/gan.yaml's)")
+    ap.add_argument("--resolutions", nargs="+", default=None, metavar="N_FFT,HOP,WIN", help="the checkpoint's MRD resolutions (default: gan.yaml's)")
     ap.add_argument("--json", default=None, metavar="PATH", help="write the per-file values, the means and the skipped pairs here")
     a = ap.parse_args(argv)
     for d in (a.source, a.generated):
         if not Path(d).is_dir():
             ap.error(f"{d} is not a directory")
     pairs, skipped = plan_pairs(a.source, a.generated, a.sr, a.glob_pattern)
-    values, more = score_pairs(pairs, a.sr, a.batch_size, stft=not a.no_stft)
+    critics = None
+    if a.critics:
+        from .scoring import CriticDistance
+        resolutions = None if a.resolutions is None else [tuple(int(v) for v in r.split(",")) for r in a.resolutions]
+        critics = CriticDistance.from_checkpoint(a.critics, periods=a.periods, resolutions=resolutions)
+    values, more = score_pairs(pairs, a.sr, a.batch_size, stft=not a.no_stft, critics=critics)
     skipped = skipped + more
     for name, reason in skipped:
         print(f"skipped {name}: {reason}")
-    means = {k: sum(v[k] for v in values.values()) / len(values) for k in METRICS if values and k in next(iter(values.values()))}
+    means = {k: sum(v[k] for v in values.values()) / len(values) for k in METRICS + CRITIC_METRICS if values and k in next(iter(values.values()))}
     print("Average scores:")
     for k, v in means.items():
         print(f"    {k}: {v:.2f}")

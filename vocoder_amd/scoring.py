@@ -10,6 +10,10 @@ lengths in a fixed order (``spec_distance``)::
 
 The front-ends run batch-invariant, and the reduction's order depends on nothing but the row itself, so a pair's score is the same bits
 whether it is scored alone or in any batch.  eval.py's PESQ is not computed (a standardised CPU algorithm).
+
+``CriticDistance`` adds what the reference logs per critic during training (``models/gan.py:149``, ``:155``, ``:204``): the adversarial terms
+and the feature-matching L1 of a (real, generated) pair under the multi-period and multi-resolution discriminators, from the per-row sums of
+``fv_disc_distance``.
 """
 from __future__ import annotations
 
@@ -218,3 +222,109 @@ class MultiResolutionSTFTDistance(_PairDistance):
         sc = sum(torch.sqrt(s[:, S_SQ]) / torch.sqrt(s[:, S_REF]) for s in sums) / len(sums)
         mag = sum(s[:, S_LOG] / n for s, n in zip(sums, counts)) / len(sums)
         return sc, mag
+
+
+# -- the critics' numbers (models/gan.py:142-155, :197-206) ---------------------------------------------------------------------------------
+from .modules.discriminators._critic import S_ADV_FAKE, S_ADV_REAL, S_COUNT, S_FAKE, S_FM  # noqa: E402
+
+CRITIC_KEYS = ("mpd", "mrd")
+
+
+def reference_losses(sums, key: str) -> dict:
+    """gan.py's three batch numbers of one critic from per-row sums ``(B, subs, layers, 5)`` (``fv_disc_distance``'s columns; a tensor or an
+    array): ``adv`` (gan.py:149), ``fm`` (gan.py:155) and ``disc`` (gan.py:204), as float64.  They are the reference's for rows of one
+    length.  ``key`` is "mpd" or "mrd": gan.py:148 and :203 iterate the scores, which for MPD is a list over sub-discriminators — a mean
+    over (B, n) per sub-discriminator, summed — but for MRD the concatenated (B, sum n) tensor, which iterates by batch ROW: a mean over
+    all resolutions' scores per row, summed over the rows."""
+    if key not in CRITIC_KEYS:
+        raise ValueError(f"reference_losses: key = {key!r} must be one of {CRITIC_KEYS}")
+    s = sums.detach().to("cpu", torch.float64) if torch.is_tensor(sums) else torch.as_tensor(sums, dtype=torch.float64)
+    fm = float((s[..., S_FM].sum(0) / s[..., S_COUNT].sum(0)).sum())
+    score = s[:, :, -1]                                         # (B, subs, 5): conv_post's map is the score
+    if key == "mpd":
+        n = score[..., S_COUNT].sum(0)
+        adv = float((score[..., S_ADV_FAKE].sum(0) / n).sum())
+        disc = float((score[..., S_ADV_REAL].sum(0) / n + score[..., S_FAKE].sum(0) / n).sum())
+    else:
+        n = score[..., S_COUNT].sum(1)
+        adv = float((score[..., S_ADV_FAKE].sum(1) / n).sum())
+        disc = float((score[..., S_ADV_REAL].sum(1) / n + score[..., S_FAKE].sum(1) / n).sum())
+    return dict(adv=adv, fm=fm, disc=disc)
+
+
+class CriticScores(dict):
+    """``CriticDistance``'s result: per critic key a dict of per-row float64 tensors ``adv_fake`` (sum over sub-discriminators of
+    mean (1 - s_fake)^2), ``adv_real`` (of mean (s_real - 1)^2), ``fm`` (sum over sub-discriminators and layers of mean |f_real - f_fake|)
+    and ``sums``, the (B, subs, layers, 5) sums and counts behind them."""
+
+    def reference_losses(self, key: str) -> dict:
+        return reference_losses(self[key]["sums"], key)
+
+
+class CriticDistance(nn.Module):
+    """The critics' view of ragged (real, generated) pairs in one call per critic.  ``mpd`` / ``mrd``: a ``MultiPeriodDiscriminator`` /
+    ``MultiResolutionDiscriminator`` of this package (either may be None).  Inference only; a row's numbers are the same bits alone and in
+    any batch."""
+
+    def __init__(self, mpd=None, mrd=None):
+        super().__init__()
+        if mpd is None and mrd is None:
+            raise ValueError("CriticDistance: no critic (mpd= and mrd= are both None)")
+        self.mpd, self.mrd = mpd, mrd
+        self.eval()
+
+    @classmethod
+    def from_checkpoint(cls, path: str, periods=None, resolutions=None, map_location="cpu"):
+        """The ``discriminators.mpd.`` / ``discriminators.mrd.`` prefixes of a Lightning checkpoint (``GANModel.discriminators``), loaded
+        strictly.  ``periods`` / ``resolutions`` default to configs/model/gan.yaml's; a critic whose prefix the checkpoint lacks is left out."""
+        from .modules.discriminators import MultiPeriodDiscriminator, MultiResolutionDiscriminator
+        ckpt = torch.load(path, map_location=map_location, weights_only=True)
+        state = ckpt.get("state_dict", ckpt)
+        periods = [3, 5, 7, 11, 17, 23, 37] if periods is None else periods
+        resolutions = [(2048, 512, 2048), (1024, 120, 600), (2048, 240, 1200)] if resolutions is None else resolutions
+        critics = {}
+        for key, make in (("mpd", lambda: MultiPeriodDiscriminator(periods)), ("mrd", lambda: MultiResolutionDiscriminator(resolutions))):
+            pfx = f"discriminators.{key}."
+            sub = {k[len(pfx):]: v for k, v in state.items() if k.startswith(pfx)}
+            if sub:
+                critics[key] = make()
+                critics[key].load_state_dict(sub, strict=True)
+        if not critics:
+            raise ValueError(f"CriticDistance.from_checkpoint: {path} holds no 'discriminators.mpd.' or 'discriminators.mrd.' weights")
+        return cls(**critics)
+
+    def critics(self) -> dict:
+        return {k: m for k, m in (("mpd", self.mpd), ("mrd", self.mrd)) if m is not None}
+
+    def min_length(self) -> int:
+        return max([1] + [m.min_length() for m in self.critics().values() if hasattr(m, "min_length")])
+
+    def forward_ragged(self, real: torch.Tensor, fake: torch.Tensor, lengths) -> CriticScores:
+        """Padded batches ``(B, L_max)`` or ``(B, 1, L_max)`` with ``lengths[b]`` valid samples per row."""
+        real, fake = _waves(real, "forward_ragged real"), _waves(fake, "forward_ragged fake")
+        if real.shape != fake.shape:
+            raise ValueError(f"forward_ragged: real {tuple(real.shape)} and fake {tuple(fake.shape)} differ in shape")
+        out = CriticScores()
+        for key, critic in self.critics().items():
+            s = critic.distance_sums(real[:, None], fake[:, None], lengths)
+            mean = s[..., :4] / s[..., S_COUNT:]
+            out[key] = dict(adv_fake=mean[:, :, -1, S_ADV_FAKE].sum(1), adv_real=mean[:, :, -1, S_ADV_REAL].sum(1),
+                            fm=mean[..., S_FM].sum((1, 2)), sums=s)
+        return out
+
+    def forward(self, real: torch.Tensor, fake: torch.Tensor) -> CriticScores:
+        """Rows of one length: ``(B, L)`` or ``(B, 1, L)``."""
+        return self.forward_ragged(real, fake, None)
+
+    def forward_list(self, reals, fakes) -> CriticScores:
+        """Lists of 1-d waveforms, pair by pair: both are cropped to the shorter of the two (eval.py:70-74)."""
+        reals, fakes = [t.reshape(-1) for t in reals], [p.reshape(-1) for p in fakes]
+        if len(reals) != len(fakes) or not reals:
+            raise ValueError(f"forward_list: {len(reals)} real waveforms for {len(fakes)} generated ones (at least one pair)")
+        lengths = [min(int(t.shape[0]), int(p.shape[0])) for t, p in zip(reals, fakes)]
+        shape = (len(reals), max(max(lengths), 1))
+        x = torch.zeros(shape, dtype=torch.float32, device=reals[0].device)
+        y = torch.zeros(shape, dtype=torch.float32, device=reals[0].device)
+        for b, n in enumerate(lengths):
+            x[b, :n], y[b, :n] = reals[b][:n], fakes[b][:n]
+        return self.forward_ragged(x, y, lengths)

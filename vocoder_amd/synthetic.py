@@ -250,6 +250,46 @@ def hubert_state_dict(cfg: dict, seed: int = 0) -> dict:
     return sd
 
 
+def _critic_conv(sd: dict, rng, prefix: str, shape, gain: float) -> None:
+    """One weight-normed Conv2d of a critic, in torch's key order (bias, original0 = g, original1 = v): the folded weight g v / |v| has
+    about ``gain / sqrt(fan_in)`` per element, g lies away from |v| and the bias is not zero."""
+    n, fan_in = int(shape[0]), int(np.prod(shape[1:]))
+    v = rng.normal(0.0, 1.0 / sqrt(fan_in), size=shape)
+    norm = np.sqrt((v ** 2).sum((1, 2, 3)))
+    bias = rng.normal(0.0, 0.1, size=n)
+    sd[f"{prefix}.bias"] = (bias + np.copysign(0.02, bias)).astype(np.float32)
+    sd[f"{prefix}.parametrizations.weight.original0"] = (norm * gain * rng.uniform(0.7, 1.4, size=n)).reshape(n, 1, 1, 1).astype(np.float32)
+    sd[f"{prefix}.parametrizations.weight.original1"] = v.astype(np.float32)
+
+
+def mpd_state_dict(periods, channels=(1, 64, 128, 256, 512, 1024), kernel_size: int = 5, seed: int = 0) -> dict:
+    """State dict of the reference's MultiPeriodDiscriminator (modules/discriminators/mpd.py) with ``DiscriminatorP(channels=channels,
+    kernel_size=kernel_size)`` per period, in the reference's key order.  PCG64 weights scaled for O(1) activations through every layer on a
+    wave of unit variance."""
+    rng = np.random.default_rng(seed)
+    sd: dict = {}
+    channels = list(channels)
+    for i in range(len(list(periods))):
+        for l, (cin, cout) in enumerate(zip(channels[:-1], channels[1:])):
+            _critic_conv(sd, rng, f"discriminators.{i}.convs.{l}", (cout, cin, kernel_size, 1), 1.8)
+        _critic_conv(sd, rng, f"discriminators.{i}.conv_post", (1, channels[-1], 3, 1), 1.8)
+    return sd
+
+
+def mrd_state_dict(resolutions, seed: int = 0) -> dict:
+    """State dict of the reference's MultiResolutionDiscriminator (modules/discriminators/mrd.py) for ``resolutions`` = (n_fft, hop_length,
+    win_length) triples, in the reference's key order.  The first layer is scaled by 1 / sqrt(win_length), the size of a magnitude of a wave
+    of unit variance under a window of ones, so activations are O(1) through every layer."""
+    rng = np.random.default_rng(seed)
+    sd: dict = {}
+    shapes = [(32, 1, 3, 9), (32, 32, 3, 9), (32, 32, 3, 9), (32, 32, 3, 9), (32, 32, 3, 3)]
+    for i, (_, _, win) in enumerate(resolutions):
+        for l, shape in enumerate(shapes):
+            _critic_conv(sd, rng, f"discriminators.{i}.convs.{l}", shape, 1.8 / sqrt(win) if l == 0 else 1.8)
+        _critic_conv(sd, rng, f"discriminators.{i}.conv_post", (1, 32, 3, 3), 1.8)
+    return sd
+
+
 def mms_state_dict(cfg: dict, seed: int = 0) -> dict:
     """State dict of the reference's MMSEncoder over ``Wav2Vec2Model(Wav2Vec2Config(**cfg))`` in the stable-layer-norm family, in the
     reference's key order: ``model.`` + HF's keys and nothing else (the processor holds no tensor).  The backbone's weights are those of
